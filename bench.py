@@ -2,6 +2,7 @@
 """Benchmark of the object-intrinsics hot path on MI355X (contract: see the task statement).
 
     python bench.py --gpus N --steps K --warmup W [--precision f16x3|bf16x6|f32|bf16x3|bf16] [--batch B]
+                    [--warmup-seconds S] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): rendered rays/sec at a 64x64 crop with 128 samples/ray (64 coarse + 64
 importance, 1 up-sampling step = BASELINE config C2), plus discriminator images/sec, whole job
@@ -10,17 +11,23 @@ over N GPUs (weak scaling: every rank renders its own batch; the forward path ha
 One "step" = one `Generator.forward` (pose/latent sampling -> rays -> hierarchical sampling ->
 FiLM-SIREN MLP with analytic normals + albedo -> compositing + Phong maps) over `--batch` images
 per GPU with inputs generated on the device, followed by one ADA-discriminator forward
-(`ADADiscriminatorView`, 64^2) on the rendered images.  Timing: W warm-up steps, then exactly K
-steps bracketed by barrier + torch.cuda.synchronize(), max over ranks; rank 0 prints ONE JSON line.
+(`ADADiscriminatorView`, 64^2) on the rendered images.  Timing: W warm-up steps (more until --warmup-seconds have
+passed: `warmup_steps_run`), then exactly K steps bracketed by barrier + torch.cuda.synchronize(), max over ranks; rank 0
+prints ONE JSON line.
+`value` and `ms_per_step` come from those K steps alone, with nothing instrumented inside them.
 
 `--gpus N` with N > 1 launched from a bare shell (no WORLD_SIZE in the environment) re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU over RCCL.
-The timed region is repeated (each repeat = exactly K steps between barrier + synchronize) until >= 2 s have been
-measured; `value` / `ms_per_step` are over all repeats, `repeats` and the per-repeat spread are reported.
 
-Extra objects in that line:
+`--dump-outputs DIR` writes what the last of the K timed steps returned (rank 0: the render maps and the discriminator's
+logits) as DIR/<name>.npy in float32, at most 64 MB in all.  The seeds are fixed, so the same arguments give the same inputs.
+
+A plain run stops there.  `--full` measures the rest after the headline, and adds these objects to the line:
+  timing        the K-step region again, repeated until >= --min-seconds, with the roofline's HIP events in it: spread per repeat
   roofline      dominant kernel (sdf_mlp_full3_kernel: sdf + d sdf/dx + albedo): algorithmic FLOPs / launch divided by
-                its mean duration measured with HIP events on the launch stream inside the timed region
+                its mean duration measured with HIP events on the launch stream inside that instrumented region
+  d_images_per_s  discriminator forward alone (library plan, and the module's own forward)
+  bf16_mode, training, extras  the secondary legs (--no-bf16, --train-steps 0, --no-extras skip them)
   cpu_baseline  the oracle (CPU restatement, oracle/oi_oracle.py) timed on the host cores on the same
                 workload (N=1, rank 0 only) -- a reported baseline, not the target
 """
@@ -253,8 +260,10 @@ def bench_training(args, gen, disc, device, world, barrier, distributed, sub_leg
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps: the headline is exactly this many steps")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--warmup-seconds", type=float, default=1.0,
+                    help="after the --warmup steps, more warm-up steps until this much time has passed since the first")
     ap.add_argument("--precision", default="f16x3", choices=["f32", "bf16x6", "f16x3", "bf16x3", "bf16"],
                     help="MFMA operand mode of the MLP contractions. bf16x6 (default) and f32 are the fp32-exact 1e-4 "
                          "parity paths (same tolerances in tests/); bf16x3 ~2e-4; bf16 ~1e-2")
@@ -263,15 +272,22 @@ def main():
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--importance", type=int, default=64)
     ap.add_argument("--up-steps", type=int, default=1)
-    ap.add_argument("--train-steps", type=int, default=20, help="full GAN training iterations timed after the main region (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bf16", action="store_true", help="skip the secondary bf16-mode measurement")
-    ap.add_argument("--train-timeout", type=int, default=300, help="watchdog (s) for the secondary training leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary measurements: discriminator-only images/s, the "
+                         "instrumented repeats (timing spread, roofline), the bf16 mode, training, extras, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (render maps, discriminator logits) as DIR/<name>.npy")
+    ap.add_argument("--train-steps", type=int, default=20, help="--full: full GAN training iterations timed after the main region (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-bf16", action="store_true", help="--full: skip the secondary bf16-mode measurement")
+    ap.add_argument("--train-timeout", type=int, default=300, help="--full: watchdog (s) for the secondary training leg")
     ap.add_argument("--no-disc", action="store_true")
     ap.add_argument("--eager-d-steps", action="store_true", help="training legs: discriminator steps eagerly instead of from captured hipGraphs")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the K-step timed region until this much has been measured")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary legs (C5, D batch sweep, shipped-config training, inference)")
+    ap.add_argument("--min-seconds", type=float, default=2.0, help="--full: repeat the instrumented K-step region until this much has been measured")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the secondary legs (C5, D batch sweep, shipped-config training, inference)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher (one process per GPU, RCCL over xGMI)
@@ -315,19 +331,6 @@ def main():
     gen.train()   # perturb on: per-ray jitter drawn on the device, random poses / latents / bg per step
     disc.eval()
 
-    import oi_amd.autograd as A
-    timer = KernelTimer()
-    orig = A.sdf_mlp
-
-    def sdf_mlp_timed(pack, pts, gamma, beta, B_, want_grad, want_rgb, want_feat, scratch=None, **kw):
-        fn = timer.wrap(orig) if (want_grad and timer_on[0] and timer.due()) else orig
-        return fn(pack, pts, gamma, beta, B_, want_grad, want_rgb, want_feat, scratch, **kw)
-
-    timer_on = [False]
-    A.sdf_mlp = sdf_mlp_timed
-    import oi_amd.renderer as RR
-    RR.sdf_mlp = sdf_mlp_timed
-
     def step(it):
         with torch.no_grad():
             out = gen(bs=B, it=it, data={})["box"]["render_out"]
@@ -346,9 +349,92 @@ def main():
             dist_barrier()
         torch.cuda.synchronize()
 
-    for i in range(args.warmup):
+    # Warm-up: W steps, then more until --warmup-seconds have passed.  A GPU that was idle runs its first few tens of ms of
+    # work slowly (a 20-step region right after 5 warm-up steps: +5 %; after 2 s idle: +13 %, the next one +2 %), which a
+    # short timed region would carry.  The seeds are set again afterwards, so the timed steps' inputs do not depend on
+    # how many warm-up steps ran.
+    t0 = time.perf_counter()
+    i = 0
+    while i < args.warmup or time.perf_counter() - t0 < args.warmup_seconds:
         step(i)
-    # discriminator-only timing (images/s), untimed with respect to the main region
+        i += 1
+    args._warmup_run = i
+    torch.manual_seed(1234 + rank)
+    np.random.seed(1234 + rank)
+
+    # ---- the headline: exactly K steps between barrier + synchronize, nothing instrumented; max over ranks
+    barrier()
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        last = step(args.warmup + i)
+    barrier()
+    t = torch.tensor([time.perf_counter() - t0], device=device, dtype=torch.float64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    del last
+    if distributed:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    dt = float(t)                                 # duration of the K-step region (slowest rank)
+    value = world * B * R * R * args.steps / dt
+
+    line = build_line(args, value, dt, world) if rank == 0 else None
+    if args.full:
+        full = full_legs(args, gen, disc, step, barrier, device, world, rank, distributed, line)
+        if rank == 0:
+            line.update(full)
+            if world > 1:  # rank-0-at-N=1 measurements: an explicit pointer instead of an absent key
+                line["cpu_baseline"] = "see the N=1 line (the oracle is timed on rank 0 at N=1 only)"
+                line["extras"] = "see the N=1 line (secondary single-GPU legs)"
+
+    if distributed:   # (rank, LOCAL_RANK, device it would take un-overridden, device it runs on): one small object gather
+        rank_devices = [None] * world
+        dist.all_gather_object(rank_devices, [rank, local_rank, local_rank, dev_index])
+        if rank == 0:
+            line["rank_devices"] = {"columns": ["rank", "local_rank", "cuda_index_by_local_rank", "cuda_index_used"], "rows": rank_devices}
+            if world > 1:
+                line["dist_backend"] = backend + (" (every rank on cuda:0: rehearsal of the N > 1 path on one GPU)" if os.environ.get("OI_BENCH_ONE_DEVICE") == "1" else "")
+        dist_barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        # the JSON line is the LAST thing on stdout: RCCL prints its version banner through C stdio, which is
+        # block-buffered on a pipe and would otherwise surface after it at exit
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+        print(json.dumps(line), flush=True)
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs: all files together
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: what the last timed step returned to its caller -- Generator.forward's render maps and the
+    discriminator's logits -- as <path>/<name>.npy, float32 (float64 stays float64).  If they exceed DUMP_BYTES together,
+    every array is cut to the same fraction of its elements at positions drawn from a fixed seed (flattened, ascending)."""
+    out, d = outputs
+    named = dict(out)
+    if d is not None:
+        named["discriminator_logits"] = d
+    arrays = {}
+    for k, v in named.items():
+        v = v.detach()
+        arrays[k] = (v.double() if v.dtype == torch.float64 else v.float()).contiguous().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        rng = np.random.default_rng(0)
+        for k in sorted(arrays):
+            a = arrays[k].reshape(-1)
+            n = max(1, a.size * DUMP_BYTES // total)
+            arrays[k] = a[np.sort(rng.choice(a.size, n, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def full_legs(args, gen, disc, step, barrier, device, world, rank, distributed, headline):
+    """--full: everything the line carries besides the headline, measured after it (the headline's K steps are never
+    instrumented).  Returns the extra keys of rank 0's line."""
+    R, B = args.res, args.batch
+    # discriminator-only timing (images/s)
     d_img_s = d_img_s_eager = None
     if not args.no_disc:
         from oi_amd.graphed import GraphedDForward
@@ -373,7 +459,21 @@ def main():
         barrier()
         d_img_s = B * n_d / (time.perf_counter() - t0)
 
-    # how many repeats of the K-step region make >= --min-seconds (same number on every rank: decided from the slowest)
+    import oi_amd.autograd as A
+    timer = KernelTimer()
+    orig = A.sdf_mlp
+
+    def sdf_mlp_timed(pack, pts, gamma, beta, B_, want_grad, want_rgb, want_feat, scratch=None, **kw):
+        fn = timer.wrap(orig) if (want_grad and timer_on[0] and timer.due()) else orig
+        return fn(pack, pts, gamma, beta, B_, want_grad, want_rgb, want_feat, scratch, **kw)
+
+    timer_on = [False]
+    A.sdf_mlp = sdf_mlp_timed
+    import oi_amd.renderer as RR
+    RR.sdf_mlp = sdf_mlp_timed
+
+    # the instrumented region: the K-step region again with HIP-event pairs on the dominant kernel (roofline), repeated
+    # until >= --min-seconds (same number of repeats on every rank: decided from the slowest) for the spread per repeat
     barrier()
     t0 = time.perf_counter()
     for i in range(min(5, args.steps)):
@@ -439,7 +539,7 @@ def main():
                 import copy
                 ab = copy.copy(args)
                 ab.train_steps = max(5, min(20, args.train_steps))
-                g_b, d_b = build_models(R, S, I, K, "bf16", device)
+                g_b, d_b = build_models(R, args.samples, args.importance, args.up_steps, "bf16", device)
                 g_b.train()
                 bf16_mode["training"] = bench_training(ab, g_b, d_b, device, 1, torch.cuda.synchronize, False, sub_legs="render")
                 bf16_mode["training"]["what"] = ("Trainer.train_step with the generator in the bf16 operand mode: bf16 forward kernel, "
@@ -453,7 +553,7 @@ def main():
             gen.renderer.pack.set_precision(args.precision)
     timer.override = main_kernel_ms
 
-    # headline reductions first: nothing after this point can take the timed result away
+    # reductions of the instrumented region and the discriminator rates first: nothing after this point can take them away
     t = torch.tensor(dts, device=device, dtype=torch.float64)
     de = torch.tensor([d_img_s_eager or 0.0], device=device, dtype=torch.float64)
     if distributed:
@@ -464,13 +564,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)   # per repeat: the slowest rank
         dist.all_reduce(dd, op=dist.ReduceOp.SUM)
     dts = [float(x) for x in t]
-    dt = sum(dts) / repeats                       # mean duration of one K-step region
-    rays_per_step = world * B * R * R
-    value = rays_per_step * args.steps / dt
-    spread = {"repeats": repeats, "timed_seconds": sum(dts),
+    spread = {"repeats": repeats, "timed_seconds": sum(dts), "ms_per_step_mean": sum(dts) / repeats / args.steps * 1e3,
               "ms_per_step_min": min(dts) / args.steps * 1e3, "ms_per_step_median": float(np.median(dts)) / args.steps * 1e3,
-              "ms_per_step_max": max(dts) / args.steps * 1e3}
-    line = None
+              "ms_per_step_max": max(dts) / args.steps * 1e3,
+              "what": "the K-step region repeated after the headline with the roofline's HIP-event pairs in it; per repeat: slowest rank"}
+    d_rate = float(dd) if d_img_s else None
 
     # ---- full training iteration (3 renders, 6 D forwards, 3 backward + optimiser steps, flat-gradient
     #      all-reduce per network when N > 1); reported next to the headline, not part of `value`.
@@ -482,7 +580,7 @@ def main():
 
         line_ref = []
         if rank == 0:
-            line_ref.append(build_line(args, value, dt, world, timer, float(dd) if d_img_s else None, None, distributed, bf16_mode, spread))
+            line_ref.append({**headline, **full_fields(args, timer, d_rate, None, bf16_mode, spread)})
 
         def _watchdog():  # a thread, not SIGALRM: the main thread would be blocked inside a collective / synchronize
             if rank == 0 and line_ref:
@@ -499,34 +597,17 @@ def main():
             train = {"error": f"{type(ex).__name__}: {ex}"}
         dog.cancel()
 
-    rank_devices = None
-    if distributed:   # (rank, LOCAL_RANK, device it would take un-overridden, device it runs on): one small object gather
-        rank_devices = [None] * world
-        dist.all_gather_object(rank_devices, [rank, local_rank, local_rank, dev_index])
-    if rank == 0:
-        line = build_line(args, value, dt, world, timer, float(dd) if d_img_s else None, train, distributed, bf16_mode, spread)
-        if rank_devices is not None:
-            line["rank_devices"] = {"columns": ["rank", "local_rank", "cuda_index_by_local_rank", "cuda_index_used"], "rows": rank_devices}
-        if world == 1 and not args.no_extras and not args.no_disc:
-            try:
-                line["extras"] = extras(args, gen, device)
-            except Exception as ex:  # never lose the headline line because of a secondary measurement
-                line["extras"] = {"error": f"{type(ex).__name__}: {ex}"}
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args.res, args.samples, args.importance, args.up_steps, args.batch)
-        elif world > 1:  # rank-0-at-N=1 measurements: an explicit pointer instead of an absent key
-            line["cpu_baseline"] = "see the N=1 line (the oracle is timed on rank 0 at N=1 only)"
-            line["extras"] = "see the N=1 line (secondary single-GPU legs)"
-            line["dist_backend"] = backend + (" (every rank on cuda:0: rehearsal of the N > 1 path on one GPU)" if os.environ.get("OI_BENCH_ONE_DEVICE") == "1" else "")
-    if distributed:
-        dist_barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        # the JSON line is the LAST thing on stdout: RCCL prints its version banner through C stdio, which is
-        # block-buffered on a pipe and would otherwise surface after it at exit
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-        print(json.dumps(line), flush=True)
+    if rank != 0:
+        return None
+    out = full_fields(args, timer, d_rate, train, bf16_mode, spread)
+    if world == 1 and not args.no_extras and not args.no_disc:
+        try:
+            out["extras"] = extras(args, gen, device)
+        except Exception as ex:  # never lose the headline line because of a secondary measurement
+            out["extras"] = {"error": f"{type(ex).__name__}: {ex}"}
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(args.res, args.samples, args.importance, args.up_steps, args.batch)
+    return out
 
 
 def _ev_time(fn, n, warm=3):
@@ -702,67 +783,74 @@ def measured_traffic(args, precision=None):
     return None, why
 
 
-def build_line(args, value, dt, world, timer, d_img_s, train, distributed, bf16_mode=None, spread=None):
+def build_line(args, value, dt, world):
+    """The headline: everything a plain run prints."""
     R, S, I, K, B = args.res, args.samples, args.importance, args.up_steps, args.batch
-    if True:
-        n_pts = B * R * R * (S + I)
-        kern_ms = timer.mean_ms()
-        flops = n_pts * (F_SDF + F_GRAD + F_COL)
-        achieved = flops / (kern_ms * 1e-3) / 1e12 if kern_ms else None
-        peak = PEAK_TFLOPS[args.precision]
-        traffic, traffic_src = measured_traffic(args)
-        line = {
-            "metric": "rendered rays/sec (64x64 img, 128 samples/ray) + D-images/sec",
-            "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "timing": spread,
-            "dtype": {"f32": "f32", "bf16x3": "bf16x3 (fp32 split into 2 bf16 MFMA operands, fp32 accumulate)",
-                      "bf16x6": "f32 via bf16x6 (fp32 operands split 3-way, 6 bf16 MFMAs per product, fp32 accumulate: "
-                                "fp32-exact contractions, 1e-4 parity path)",
-                      "f16x3": "f32 via f16x3 (fp32 operands split into 2 fp16 limbs = 22 mantissa bits, 3 fp16 MFMAs "
-                               "per product, fp32 accumulate: 2^-22 relative per product, 1e-4 parity path)",
-                      "bf16": "bf16"}[args.precision],
-            "data": "synthetic (random poses/latents/backgrounds from the data/example prior; sphere-initialised SDF "
-                    "weights, seeded default-init colour/discriminator weights)",
-            "config": {"workload": f"{ {(64, 64, 64, 1): 'C2', (128, 128, 128, 4): 'C4'}.get((R, S, I, K), 'custom') }: {B}x{R}x{R} crop per GPU, {S}+{I} samples/ray, {K} up-sampling step(s), "
-                                   f"Generator.forward (render + Phong maps) + ADADiscriminatorView forward",
-                       "rays_per_step_per_gpu": B * R * R, "points_per_step_per_gpu": n_pts,
-                       "parallelism": f"dp{world} (independent renders, no data-path collective)"},
-            "d_images_per_s": d_img_s,
-            "d_images_per_s_what": "ADADiscriminatorView forward, batch 1 per GPU, through oi_amd.graphed.GraphedDForward: at batch "
-                                   "<= 4 a plan held by the library (oi_disc_graph_*: four launches per image, image pointer "
-                                   "passed per call; OI_DISC_LAUNCH=graph replays them as one hipGraph); d_images_per_s_eager = the "
-                                   "module's own forward (the reference's call), call by call.  Since round 6 both draw the "
-                                   "augmentation parameters INSIDE the library from one seed of numpy's stream per call "
-                                   "(oi_disc_graph_launch_ada): no numpy / Python arithmetic per image",
-            "d_images_per_s_eager": getattr(args, "_d_images_per_s_eager", None),
-            "training": train,
-            "bf16_mode": bf16_mode,
-            "roofline": {"bound": "mfma",
-                         "kernel": ("sdf_mlp_full3_kernel (register-resident: sdf + d sdf/dx + albedo at the fine samples; since round 6 "
-                                    "its per-element table blob is formed by the step's prep launch, so the HIP-event pair covers "
-                                    "this kernel alone -- with OI_STEP_TAIL=0 it also covers film_blob_f3_kernel, ~6 us)"
-                                    if args.precision == "f16x3" else "sdf_mlp_kernel<full> (sdf + d sdf/dx + albedo at the fine samples)"),
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                         "frac": (achieved / peak) if achieved else None,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_flops_per_launch": flops, "kernel_ms": kern_ms,
-                         "kernel_ms_samples": getattr(args, "_kernel_samples", None),
-                         "algorithmic_bytes_per_launch": n_pts * 40,  # 12 B point in, 28 B sdf + gradient + albedo out
-                         # the same launch against the HBM roofline (8 TB/s, MI355X_MICROARCH.md): PMC traffic / live duration
-                         "hbm": ({"achieved": traffic / (kern_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
-                                  "frac": traffic / (kern_ms * 1e-3) / 8e12} if (kern_ms and traffic) else None),
-                         "executed_mfma_frac_of_peak": (achieved * MFMA_PER_MAC[args.precision] / peak) if achieved else None,
-                         "vs_native_fp32_mfma_peak": (achieved / 157.3) if achieved else None,
-                         "note": "kernel_ms = mean of HIP-event pairs around every 4th launch of this kernel inside the timed region "
-                                 "(kernel_ms_samples pairs; a pair costs its launch ~11 us of idle stream); "
-                                 "algorithmic = GEMM MACs x2 of sdf fwd + analytic gradient sweep + colour head per "
-                                 "point. peak = dense MFMA peak of the unit the mode runs on (fp32 MFMA 157.3, fp16 / bf16 MFMA "
-                                 "2500 TFLOP/s); f16x3 / bf16x3 / bf16x6 execute 3 / 3 / 6 16-bit MFMAs per algorithmic MAC "
-                                 "(executed_mfma_frac_of_peak), so their frac is bounded by 1/3 / 1/3 / 1/6; "
-                                 "vs_native_fp32_mfma_peak compares the fp32-exact result rate with the native fp32 roofline"},
-        }
-    return line
+    return {
+        "metric": "rendered rays/sec (64x64 img, 128 samples/ray) + D-images/sec",
+        "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "warmup_steps_run": getattr(args, "_warmup_run", None),
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": {"f32": "f32", "bf16x3": "bf16x3 (fp32 split into 2 bf16 MFMA operands, fp32 accumulate)",
+                  "bf16x6": "f32 via bf16x6 (fp32 operands split 3-way, 6 bf16 MFMAs per product, fp32 accumulate: "
+                            "fp32-exact contractions, 1e-4 parity path)",
+                  "f16x3": "f32 via f16x3 (fp32 operands split into 2 fp16 limbs = 22 mantissa bits, 3 fp16 MFMAs "
+                           "per product, fp32 accumulate: 2^-22 relative per product, 1e-4 parity path)",
+                  "bf16": "bf16"}[args.precision],
+        "data": "synthetic (random poses/latents/backgrounds from the data/example prior; sphere-initialised SDF "
+                "weights, seeded default-init colour/discriminator weights)",
+        "config": {"workload": f"{ {(64, 64, 64, 1): 'C2', (128, 128, 128, 4): 'C4'}.get((R, S, I, K), 'custom') }: {B}x{R}x{R} crop per GPU, {S}+{I} samples/ray, {K} up-sampling step(s), "
+                               f"Generator.forward (render + Phong maps) + ADADiscriminatorView forward",
+                   "rays_per_step_per_gpu": B * R * R, "points_per_step_per_gpu": B * R * R * (S + I),
+                   "parallelism": f"dp{world} (independent renders, no data-path collective)"},
+    }
+
+
+def full_fields(args, timer, d_img_s, train, bf16_mode, spread):
+    """What --full adds to the line (besides extras and cpu_baseline)."""
+    R, S, I, B = args.res, args.samples, args.importance, args.batch
+    n_pts = B * R * R * (S + I)
+    kern_ms = timer.mean_ms()
+    flops = n_pts * (F_SDF + F_GRAD + F_COL)
+    achieved = flops / (kern_ms * 1e-3) / 1e12 if kern_ms else None
+    peak = PEAK_TFLOPS[args.precision]
+    traffic, traffic_src = measured_traffic(args)
+    return {
+        "timing": spread,
+        "d_images_per_s": d_img_s,
+        "d_images_per_s_what": "ADADiscriminatorView forward, batch 1 per GPU, through oi_amd.graphed.GraphedDForward: at batch "
+                               "<= 4 a plan held by the library (oi_disc_graph_*: four launches per image, image pointer "
+                               "passed per call; OI_DISC_LAUNCH=graph replays them as one hipGraph); d_images_per_s_eager = the "
+                               "module's own forward (the reference's call), call by call.  Since round 6 both draw the "
+                               "augmentation parameters INSIDE the library from one seed of numpy's stream per call "
+                               "(oi_disc_graph_launch_ada): no numpy / Python arithmetic per image",
+        "d_images_per_s_eager": getattr(args, "_d_images_per_s_eager", None),
+        "training": train,
+        "bf16_mode": bf16_mode,
+        "roofline": {"bound": "mfma",
+                     "kernel": ("sdf_mlp_full3_kernel (register-resident: sdf + d sdf/dx + albedo at the fine samples; since round 6 "
+                                "its per-element table blob is formed by the step's prep launch, so the HIP-event pair covers "
+                                "this kernel alone -- with OI_STEP_TAIL=0 it also covers film_blob_f3_kernel, ~6 us)"
+                                if args.precision == "f16x3" else "sdf_mlp_kernel<full> (sdf + d sdf/dx + albedo at the fine samples)"),
+                     "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                     "frac": (achieved / peak) if achieved else None,
+                     "traffic": traffic, "traffic_source": traffic_src,
+                     "algorithmic_flops_per_launch": flops, "kernel_ms": kern_ms,
+                     "kernel_ms_samples": getattr(args, "_kernel_samples", None),
+                     "algorithmic_bytes_per_launch": n_pts * 40,  # 12 B point in, 28 B sdf + gradient + albedo out
+                     # the same launch against the HBM roofline (8 TB/s, MI355X_MICROARCH.md): PMC traffic / live duration
+                     "hbm": ({"achieved": traffic / (kern_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
+                              "frac": traffic / (kern_ms * 1e-3) / 8e12} if (kern_ms and traffic) else None),
+                     "executed_mfma_frac_of_peak": (achieved * MFMA_PER_MAC[args.precision] / peak) if achieved else None,
+                     "vs_native_fp32_mfma_peak": (achieved / 157.3) if achieved else None,
+                     "note": "kernel_ms = mean of HIP-event pairs around every 4th launch of this kernel inside the instrumented "
+                             "region after the headline (kernel_ms_samples pairs; a pair costs its launch ~11 us of idle stream); "
+                             "algorithmic = GEMM MACs x2 of sdf fwd + analytic gradient sweep + colour head per "
+                             "point. peak = dense MFMA peak of the unit the mode runs on (fp32 MFMA 157.3, fp16 / bf16 MFMA "
+                             "2500 TFLOP/s); f16x3 / bf16x3 / bf16x6 execute 3 / 3 / 6 16-bit MFMAs per algorithmic MAC "
+                             "(executed_mfma_frac_of_peak), so their frac is bounded by 1/3 / 1/3 / 1/6; "
+                             "vs_native_fp32_mfma_peak compares the fp32-exact result rate with the native fp32 roofline"},
+    }
 
 
 if __name__ == "__main__":

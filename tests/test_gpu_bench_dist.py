@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +19,7 @@ def _run(gpus, extra_env, train_steps=2):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus), "--steps", "3", "--warmup", "1",
            "--min-seconds", "0.1", "--train-steps", str(train_steps), "--no-extras", "--no-cpu-baseline", "--no-bf16"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
@@ -63,3 +64,35 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu():
     assert [r[0] for r in rows] == list(range(8)) and all(r[1] == r[0] == r[2] for r in rows), rows
     assert all(r[3] == 0 for r in rows)   # (this rehearsal: every rank on the one GPU)
     assert "dp8" in line["config"]["parallelism"]
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full): the headline keys over exactly --steps timed steps and nothing of the secondary legs.
+    --dump-outputs writes the last timed step's maps and logits; the seeds are fixed, so a second run writes the same arrays."""
+    lines = []
+    for run in ("a", "b"):
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+               "--dump-outputs", str(tmp_path / run)]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+        out = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, p.stdout[-3000:]
+        lines.append(json.loads(out[0]))
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["unit"] == "rays/s" and line["higher_is_better"] is True and line["steps"] == 4 and line["warmup"] == 2
+    assert line["warmup_steps_run"] >= 2
+    assert abs(line["value"] - line["config"]["rays_per_step_per_gpu"] / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    for k in ("timing", "roofline", "d_images_per_s", "training", "bf16_mode", "extras", "cpu_baseline"):
+        assert k not in line, k
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert names == sorted(f"{k}.npy" for k in ("weight_sum_map", "color_map", "shading_map", "image_no_bg", "image", "mask",
+                                                  "discriminator_logits"))
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), name
+        assert np.array_equal(a, b), name
+    assert np.load(tmp_path / "a" / "image.npy").shape == (1, 3, 64, 64)

@@ -220,3 +220,32 @@ def test_library_ada_draws_match_the_reference_distribution_and_matrix():
     assert aug.fast_draw_ok()
     aug.sample_G_inv = lambda *a, **k: None
     assert not aug.fast_draw_ok()
+
+
+def test_bench_dump_outputs_writes_float32_and_caps_the_total(tmp_path):
+    """bench.py --dump-outputs: small outputs are written whole as float32 (float64 stays float64); above 64 MB in all every
+    array is cut to the same fraction at positions from a fixed seed, so two dumps of the same outputs are identical."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    small = ({"image": torch.rand(1, 3, 8, 8, generator=g), "mask": torch.rand(1, 1, 8, 8, generator=g).half(),
+              "z": torch.rand(1, 2, generator=g, dtype=torch.float64)}, torch.rand(1, 7, generator=g))
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    files = sorted(os.listdir(tmp_path / "small"))
+    assert files == ["discriminator_logits.npy", "image.npy", "mask.npy", "z.npy"]
+    img = np.load(tmp_path / "small" / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (1, 3, 8, 8) and np.array_equal(img, small[0]["image"].numpy())
+    assert np.load(tmp_path / "small" / "mask.npy").dtype == np.float32
+    assert np.load(tmp_path / "small" / "z.npy").dtype == np.float64
+
+    big = ({"image": torch.rand(64, 3, 256, 256, generator=g), "mask": torch.rand(80, 1, 256, 256, generator=g)}, None)
+    assert sum(v.numel() * 4 for v in big[0].values()) > bench.DUMP_BYTES
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    assert sorted(os.listdir(tmp_path / "a")) == ["image.npy", "mask.npy"]
+    total = 0
+    for name in ("image", "mask"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and np.array_equal(a, b)
+        assert np.isin(a, big[0][name].numpy().reshape(-1)).all()
+        total += a.nbytes
+    assert 0.9 * bench.DUMP_BYTES < total <= bench.DUMP_BYTES

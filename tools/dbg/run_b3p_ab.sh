@@ -8,7 +8,7 @@ for v in 1 0 1 0; do
   OI_BF16_PRESCALE=$v python tools/bench_c5.py --modes bf16 >> $O/b3p_c5.log 2>&1
 done
 for v in 1 0; do
-  OI_BF16_PRESCALE=$v python bench.py --precision bf16 --no-cpu-baseline --no-bf16 --no-extras --train-steps 20 2>/dev/null | tail -1 > $O/b3p_bench_$v.json
+  OI_BF16_PRESCALE=$v python bench.py --full --precision bf16 --no-cpu-baseline --no-bf16 --no-extras --train-steps 20 2>/dev/null | tail -1 > $O/b3p_bench_$v.json
 done
 cat $O/b3p_tests.log; cat $O/b3p_c5.log
 python - <<'P'

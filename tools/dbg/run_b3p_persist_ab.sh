@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 for v in 1 0 1 0; do
   echo "persist=$v" >> $O/b3pp.log
   OI_B3P_PERSIST=$v python tools/bench_c5.py --modes bf16 2>&1 | grep '"mode"' >> $O/b3pp.log
-  OI_B3P_PERSIST=$v python bench.py --precision bf16 --no-cpu-baseline --no-bf16 --no-extras --train-steps 0 2>/dev/null | tail -1 | python -c "
+  OI_B3P_PERSIST=$v python bench.py --full --precision bf16 --no-cpu-baseline --no-bf16 --no-extras --train-steps 0 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('  step: rays/s %.0f ms/step %.4f kernel_ms %.4f frac %.4f' % (d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac']))" >> $O/b3pp.log
 done

@@ -2,7 +2,7 @@
 # kernel-level same-box A/B of the backward between library variants: run_bwd_kab.sh <variant> ...
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-TRAIN="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-bf16 --no-extras --min-seconds 0.01"
+TRAIN="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-bf16 --no-extras --min-seconds 0.01"
 : > $O/bwd_kab.log
 for rep in 1 2; do
 for v in "$@"; do

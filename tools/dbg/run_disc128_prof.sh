@@ -27,6 +27,6 @@ for on in (True, False, True, False):
     print(f"128 x 128 batch 1, small path {on}: {rate():8.0f} images/s")
 PY
 for v in 1 0; do
-OI_SMALL128=$v python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-bf16 --min-seconds 0.01 --train-steps 5 2>/dev/null | tail -1 | python -c "
+OI_SMALL128=$v python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-bf16 --min-seconds 0.01 --train-steps 5 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); t=d['extras']['training_shipped_config']; print('small128=$v shipped config', 'ms_per_it', round(t['ms_per_it'],3), 'it_per_s', round(t['it_per_s'],1))"
 done

@@ -49,7 +49,7 @@ def describe(tag):
     if ex(f("bench_f16x3.json")):
         d = bench_line(f("bench_f16x3.json"))
         r, t, b = d["roofline"], d.get("training") or {}, d.get("bf16_mode") or {}
-        s = (f"`python bench.py`, un-profiled: **{d['value'] / 1e6:.3f} M rays/s, {d['ms_per_step']:.4f} ms/step**; dominant kernel "
+        s = (f"`python bench.py --full`, un-profiled: **{d['value'] / 1e6:.3f} M rays/s, {d['ms_per_step']:.4f} ms/step**; dominant kernel "
              f"{r['kernel'].split(' ')[0]} {r['kernel_ms']:.4f} ms by HIP events ({r['kernel_ms_samples']} pairs) = {r['achieved']:.1f} TFLOP/s, "
              f"`frac` {r['frac']:.4f} (executed MFMA {r.get('executed_mfma_frac_of_peak', 0):.3f}); traffic "
              f"{(r['traffic'] or 0) / 1e9:.3f} GB per launch; D forward {d.get('d_images_per_s', 0):.0f} images/s through the plan, "

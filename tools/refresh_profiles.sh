@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 # every profiled run under its own timeout: one hung step (seen once: the one-rank process-group run never returned) must not
 # take the whole refresh -- and the GPU budget -- with it
 RP="timeout 420 rocprofv3"
-BENCH="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-bf16 --no-extras --min-seconds 0.2"
+BENCH="python $R/bench.py --full --warmup-seconds 0 --steps 20 --warmup 5 --no-cpu-baseline --no-bf16 --no-extras --min-seconds 0.2"
 # (forward steps only: the with-gradient renders of the training leg run the same kernel with the feature stores on, and would
 #  pull its average away from what bench.py's HIP events measure; the training kernels are in ${T}_kernel_stats_train.txt)
 rm -rf /tmp/p_ks; $RP --kernel-trace --stats --output-format csv -d /tmp/p_ks -- $BENCH --train-steps 0 > /dev/null 2>&1
@@ -24,7 +24,7 @@ for c in "FETCH_SIZE:fetch" "WRITE_SIZE:write" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY
   python $R/tools/prof_summary.py /tmp/p_$tag $O/${T}_pmc_${tag}_f16x3.txt > /dev/null
 done
 # training iteration: kernel stats, and launches per iteration from the difference of two runs (10 vs 30 iterations)
-TRAIN="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-bf16 --no-extras --min-seconds 0.01"
+TRAIN="python $R/bench.py --full --warmup-seconds 0 --steps 2 --warmup 1 --no-cpu-baseline --no-bf16 --no-extras --min-seconds 0.01"
 rm -rf /tmp/p_t10 /tmp/p_t30
 $RP --kernel-trace --output-format csv -d /tmp/p_t10 -- $TRAIN --train-steps 10 > /dev/null 2>&1
 $RP --kernel-trace --output-format csv -d /tmp/p_t30 -- $TRAIN --train-steps 30 > /dev/null 2>&1
@@ -48,7 +48,7 @@ rm -rf /tmp/p_bsq; $RP --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYC
 python $R/tools/prof_summary.py /tmp/p_bsq $O/${T}_pmc_sq_bf16.txt > /dev/null
 # bf16 mode END TO END (BASELINE configs[1]): the training iteration with the generator in the bf16 operand mode -- kernel stats
 # and the PMC traffic of its backward (mlp_bwd_sweep_kernel<2, ...> + mlp_wgrad_kernel)
-TRAINB="python $R/bench.py --precision bf16 --steps 2 --warmup 1 --no-cpu-baseline --no-bf16 --no-extras --min-seconds 0.01"
+TRAINB="python $R/bench.py --full --warmup-seconds 0 --precision bf16 --steps 2 --warmup 1 --no-cpu-baseline --no-bf16 --no-extras --min-seconds 0.01"
 rm -rf /tmp/p_tb; $RP --kernel-trace --output-format csv -d /tmp/p_tb -- $TRAINB --train-steps 20 > /dev/null 2>&1
 python $R/tools/prof_summary.py /tmp/p_tb $O/${T}_kernel_stats_train_bf16.txt > /dev/null
 for c in "FETCH_SIZE:fetch" "WRITE_SIZE:write"; do
@@ -78,6 +78,6 @@ timeout 300 python $R/tools/bench_c5.py > $O/${T}_c5_mlp_microbench.jsonl 2>/dev
 timeout 600 python $R/tools/grad_margin.py $O/${T}_margins.json > $O/${T}_gradient_margins.txt 2>/dev/null   # (incl. the bf16-mode map margins)
 # the un-profiled bench lines last: they read the traffic file written above (same sources, same digest)
 cp $O/${T}_traffic.json $R/profiles/${T}_traffic.json
-timeout 900 python $R/bench.py 2>/dev/null | tail -1 > $O/${T}_bench_f16x3.json
-timeout 600 python $R/bench.py --res 128 --samples 128 --importance 128 --up-steps 4 --steps 10 --warmup 3 --train-steps 0 --no-bf16 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/${T}_bench_c4_f16x3.json
+timeout 900 python $R/bench.py --full 2>/dev/null | tail -1 > $O/${T}_bench_f16x3.json
+timeout 600 python $R/bench.py --full --res 128 --samples 128 --importance 128 --up-steps 4 --steps 10 --warmup 3 --train-steps 0 --no-bf16 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > $O/${T}_bench_c4_f16x3.json
 ls -la $O/${T}_*

@@ -690,13 +690,7 @@ ada_resample_down2_kernel(const float* __restrict__ canvas, const float* __restr
 // order the threads arrive in does not matter, the result is bit-reproducible) -- then two small fp32 products on the matrix
 // cores.  Same products as the two-launch form in a different association: equal to it within rounding, not bit-identical.
 // ------------------------------------------------------------------------------------------
-#ifndef OI_AS_ABL   // timing ablations (results garbage): 1 = no matrix build, 2 = no first product, 4 = no second product, 8 = no zero fill
-#define OI_AS_ABL 0
-#endif
-#ifndef OI_AS_THREADS
-#define OI_AS_THREADS 1024
-#endif
-constexpr int AS_RB = 16, AS_THREADS = OI_AS_THREADS, AS_NW = AS_THREADS / 64, AS_MAX_C = 3;
+constexpr int AS_RB = 16, AS_THREADS = 1024, AS_NW = AS_THREADS / 64, AS_MAX_C = 3;
 // Per image edge N (64: BASELINE's discriminators; 128: the shipped ones).  LDS row strides (floats) of the MFMA operands are
 // chosen so that the 64 lanes of a fragment read 64 banks: B operands [k][n] N + 16, A operands [m][k] N + 4.
 //   N = 64:  the matrices are accumulated as 2^-56 fixed point in 64 bits and converted into their own float arrays; the image
@@ -776,12 +770,12 @@ ada_sep_kernel(const float* __restrict__ x, const float* __restrict__ theta, con
     fs[tid] = sep_fix28(f[tid]);
     fr[tid] = sep_fix28(2.0f * f[ADA_TAPS - 1 - tid]);
   }
-  for (int i = tid; i < ((OI_AS_ABL & 8) ? 0 : (K::O_FEND - K::O_FX) / 16); i += AS_THREADS)
+  for (int i = tid; i < (K::O_FEND - K::O_FX) / 16; i += AS_THREADS)
     reinterpret_cast<f32x4*>(as_lds + K::O_FX)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
   // the matrices: one task per (row, down-FIR tap k, bilinear corner c) = 6 products through the up-FIR and the reflect pad
   constexpr int NROW = N + (ADJ ? N : AS_RB), NTASK = NROW * ADA_TAPS * 2;
-  for (int t_ = tid; t_ < ((OI_AS_ABL & 1) ? 0 : NTASK); t_ += AS_THREADS) {
+  for (int t_ = tid; t_ < NTASK; t_ += AS_THREADS) {
     // (the row on the lane: the adds of a wave then go to different addresses -- with the taps on the lane up to 24 lanes
     // met in one)
     const int kc = t_ / NROW, row = t_ - kc * NROW, k = kc >> 1, c = kc & 1;
@@ -840,7 +834,7 @@ ada_sep_kernel(const float* __restrict__ x, const float* __restrict__ theta, con
     float ay[KS];
 #pragma unroll
     for (int kk = 0; kk < KS; ++kk) ay[kk] = ayb[l16 * ZS + 4 * kk + kq];
-    for (int p = wave; p < ((OI_AS_ABL & 2) ? 0 : C * NT); p += AS_NW) {
+    for (int p = wave; p < C * NT; p += AS_NW) {
       const int c = p / NT, nt = p - c * NT;
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       if constexpr (K::WIDE) {
@@ -859,7 +853,7 @@ ada_sep_kernel(const float* __restrict__ x, const float* __restrict__ theta, con
     }
   }
   __syncthreads();
-  for (int p = wave; p < ((OI_AS_ABL & 4) ? 0 : C * NT); p += AS_NW) {   // Y = Z A_x^T: (C 16) x N, K = N
+  for (int p = wave; p < C * NT; p += AS_NW) {   // Y = Z A_x^T: (C 16) x N, K = N
     const int c = p / NT, nt = p - c * NT;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -999,8 +993,7 @@ int oi_conv4x4_fwd_arena(const float* x, const float* w, const float* bias, floa
   // this entry): the tiled kernel's UNSCALED fp16 limbs lose precision below |v| ~ 3e-4 and flush below ~3e-8, so such
   // calls stay on the fp32 matrix cores
   const bool any_scale = (flags & OI_CONV_ANY_SCALE) != 0;
-  // large batches: LDS-tiled F16X3 implicit GEMM, K never split (OI_CONV_TILED=0 keeps the per-wave fp32-MFMA path)
-  static const bool tiled_on = [] { const char* e = getenv("OI_CONV_TILED"); return e == nullptr || e[0] != '0'; }();
+  // large batches: LDS-tiled F16X3 implicit GEMM, K never split
   const int K = Cin * 16;
   const bool small = (long long)oi::cdiv(M, 128) * (Cout / 64) < 256;  // fewer workgroups than CUs: halve the pixel tile
   // still short of the CUs and a long K: two K halves.  Exactly two addends into a zeroed output commute, so the result
@@ -1008,7 +1001,7 @@ int oi_conv4x4_fwd_arena(const float* x, const float* w, const float* bias, floa
   const int splits = (small && (long long)oi::cdiv(M, 64) * (Cout / 64) < 192 && K >= 1024) ? 2 : 1;
   // worth it from ~half a chip of workgroups; below that the per-wave split-K kernel spreads the K loop over more CUs
   const bool enough = (long long)oi::cdiv(M, small ? 64 : 128) * (Cout / 64) * splits >= 128;
-  if (tiled_on && !any_scale && M >= 512 && enough && Cout % 64 == 0 && K % 64 == 0) {
+  if (!any_scale && M >= 512 && enough && Cout % 64 == 0 && K % 64 == 0) {
     const int k_per_split = splits == 2 ? ((K / 2 + 63) / 64) * 64 : K;
     const long long total = (long long)B * Cout * Ho * Wo;
     if (splits == 2 && !y_is_zero) {

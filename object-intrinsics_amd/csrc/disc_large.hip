@@ -32,11 +32,6 @@ constexpr int TK = 64;             // k per chunk = 64 consecutive input channel
 constexpr int TM = 128;            // pixels per workgroup (4 waves x 32)
 constexpr int IMG = TN * TK * 2;   // bytes of one limb plane of a chunk image (16 KiB); hi plane then lo plane
 constexpr int MAX_BLOCKS = 8;
-// timing ablations of dl_gemm_kernel (results garbage): bit 1 = B fragments loaded for the first two chunks only, 2 = no epilogue
-// stores, 4 = weight image loaded / stored for the first two chunks only, 8 = no MFMAs
-#ifndef OI_DL_ABL
-#define OI_DL_ABL 0
-#endif
 
 __device__ __forceinline__ void split_half(float v, _Float16& hi, _Float16& lo) {
   hi = (_Float16)v;
@@ -148,14 +143,9 @@ __global__ void __launch_bounds__(256) dl_conv1_kernel(const float* __restrict__
 
 // ---- GEMM layer: out[m][n] = sum_k A[m][k] W[n][k], 4 x 4 stride 2 pad 1, NHWC limb planes in.
 // SPLIT = false: writes lrelu(out) as limb planes; true: writes this K range's fp32 partial plane [split][M][Cout].
-#ifndef OI_DL_WPE
-#define OI_DL_WPE 2
-#endif
-#ifndef OI_DL_WGS
-#define OI_DL_WGS 256
-#endif
+constexpr int DL_WGS = 256;   // split_for: K is split until a layer has this many workgroups
 template <bool SPLIT>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, OI_DL_WPE))) dl_gemm_kernel(const _Float16* __restrict__ in_hi, const _Float16* __restrict__ in_lo,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) dl_gemm_kernel(const _Float16* __restrict__ in_hi, const _Float16* __restrict__ in_lo,
                                                       const char* __restrict__ wimg, _Float16* __restrict__ out_hi,
                                                       _Float16* __restrict__ out_lo, float* __restrict__ part, int B, int Cin,
                                                       int Hin, int Win, int Cout, int chunks_per_split, float slope) {
@@ -210,9 +200,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, OI_
   // The eight A fragments (4 row blocks x hi / lo) of k-step s + 1 are requested before the twelve MFMAs of k-step s are issued:
   // with one wave per SIMD an LDS round trip (~130 cycles with four waves reading) in front of every product otherwise -- a
   // distance of one product left 55 % of the matrix rate (measured: 58 cycles per MFMA).
-#ifndef OI_DL_APF
-#define OI_DL_APF 1
-#endif
   auto compute = [&](int slot, const u32x4 (&h_)[4], const u32x4 (&l_)[4]) {
     const char* a0 = lds + slot * (2 * IMG) + l16;
     f32x4 ah[2][4], al[2][4];
@@ -223,7 +210,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, OI_
     }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      if (s + 1 < 4 && !(OI_DL_ABL & 16)) {   // (ablation 16: A fragments read for k-step 0 only)
+      if (s + 1 < 4) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           ah[(s + 1) & 1][t] = *reinterpret_cast<const f32x4*>(a0 + (t * 4 + s + 1) * 1024);
@@ -233,11 +220,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, OI_
       const f16x8 vh = __builtin_bit_cast(f16x8, h_[s]), vl = __builtin_bit_cast(f16x8, l_[s]);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const f16x8 wh = __builtin_bit_cast(f16x8, ah[(OI_DL_ABL & 16) ? 0 : (s & 1)][t]), wl = __builtin_bit_cast(f16x8, al[(OI_DL_ABL & 16) ? 0 : (s & 1)][t]);
-        if (OI_DL_ABL & 32) {   // (ablation 32: the reads stay, no MFMAs)
-          asm volatile("" ::"v"(wh), "v"(wl));
-          continue;
-        }
+        const f16x8 wh = __builtin_bit_cast(f16x8, ah[s & 1][t]), wl = __builtin_bit_cast(f16x8, al[s & 1][t]);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, vh, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, vl, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, vh, acc[t], 0, 0, 0);
@@ -252,12 +235,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, OI_
   auto step = [&](int c, auto pos) {
     constexpr int P = decltype(pos)::value;   // position of chunk c in the rotation of three B-fragment sets
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (c + 1 < c_end && !(OI_DL_ABL & 4)) store_w((c + 1 - c_beg) & 1);
+    if (c + 1 < c_end) store_w((c + 1 - c_beg) & 1);
     if (c + 2 < c_end) {
-      if (!(OI_DL_ABL & 4)) load_w(c + 2);
-      if (!(OI_DL_ABL & 1)) load_b_steps(c + 2, bh[(P + 2) % 3], bl[(P + 2) % 3]);
+      load_w(c + 2);
+      load_b_steps(c + 2, bh[(P + 2) % 3], bl[(P + 2) % 3]);
     }
-    if (!(OI_DL_ABL & 8)) compute((c - c_beg) & 1, bh[P], bl[P]);
+    compute((c - c_beg) & 1, bh[P], bl[P]);
   };
   if (c_beg < c_end) {
     load_w(c_beg);
@@ -278,7 +261,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, OI_
   }
   // ---- epilogue: slot r of block t in lane-half kg is channel 32 t + 8 (r >> 2) + 4 kg + (r & 3) of pixel m
   if (!valid) return;
-  if ((OI_DL_ABL & 2) && acc[0][0] != 12345.f) return;
   const int n0 = blockIdx.y * TN;
 #pragma unroll
   for (int t = 0; t < 4; ++t)
@@ -395,7 +377,7 @@ bool make_plan(const int* chans, int n_blocks, int out_dim, Plan& p) {
 int split_for(long long M, int Cout, int nchunk) {
   const long long tiles = ((M + TM - 1) / TM) * (Cout / TN);
   int S = 1;
-  while (tiles * S < OI_DL_WGS && S * 2 <= nchunk && S < 32) S *= 2;
+  while (tiles * S < DL_WGS && S * 2 <= nchunk && S < 32) S *= 2;
   return S;
 }
 struct Work {

@@ -541,11 +541,6 @@ static bool fold_fits(const float* theta, int B, int H, int W, int Hp, int Wp) {
   }
   return true;
 }
-// OI_DISC_FOLD=0: always the canvas form (the yardstick of the bit-identity test)
-static int flags_fold_mode() {
-  static const int v = [] { const char* e = getenv("OI_DISC_FOLD"); return e != nullptr && e[0] == '0' ? 0 : 1; }();
-  return v;
-}
 
 // disc.hip: the canvas of the augmentation (reflect pad + x2 up-FIR) for a given stream
 extern "C" int oi_ada_pad_up2(const float* x, const float* f, float* canvas, int B, int C, int H, int W, int mx0, int mx1, int my0,
@@ -588,7 +583,7 @@ static int disc_fwd_small_impl(const float* x, const float* theta_host, const fl
   ThetaArg th = {};
   int rc = OI_OK;
   // the canvas built inside d_aug_conv1_kernel (one launch less) when the host can see that every tile's footprint fits
-  const bool fold = aug && theta_host != nullptr && (flags_fold_mode() != 0) && fold_fits(theta_host, B, H, W, Hp, Wp);
+  const bool fold = aug && theta_host != nullptr && fold_fits(theta_host, B, H, W, Hp, Wp);
   if (aug) {
     if (theta_host != nullptr)
       for (int b = 0; b < B; ++b)
@@ -800,7 +795,7 @@ int oi_disc_graph_launch(oi_disc_graph* g, const float* x, const float* theta_ho
   if (g->aug) {
     for (int b = 0; b < g->B; ++b)
       for (int i = 0; i < 6; ++i) g->th_arg.t[b][i] = theta_host[b * 6 + i];
-    vi = (flags_fold_mode() != 0 && fold_fits(theta_host, g->B, g->H, g->W, g->Hp, g->Wp)) ? 0 : 1;
+    vi = (fold_fits(theta_host, g->B, g->H, g->W, g->Hp, g->Wp)) ? 0 : 1;
   }
   GraphVariant& v = g->v[vi];
   for (int i = 0; i < v.n_nodes; ++i) {

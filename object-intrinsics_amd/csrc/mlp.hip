@@ -360,9 +360,6 @@ __global__ void pack_weights_kernel(const float* __restrict__ w0, const float* _
 // REV: the FiLM rows were staged in REVOLUTIONS (gamma / 2pi, beta' / 2pi; sdf-only F16X3 pass): the phase needs one
 // v_fract (exact, keeps v_sin inside its [-256, 256] domain) instead of the four-operation reduction of sincos_, and no
 // cosine exists in that pass -- the form the register-resident kernel (mlp_fwd3.hip) uses.
-#ifndef OI_SDF_REV
-#define OI_SDF_REV 1
-#endif
 template <bool FAST>
 __device__ __forceinline__ float sin_rev(float phi_rev) {
   return __builtin_amdgcn_sinf(FAST ? phi_rev : __builtin_amdgcn_fractf(phi_rev));
@@ -486,11 +483,8 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[4]) {
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 }
 
-// 1: F16X3 forward layers run layer_fwd_pipelined (FiLM / sin of block t-1 between block t's MFMAs): same-box A/B
-// sdf-only pass 1.61 -> 1.57 ms per 2^21 points, full kernel 1.040 -> 1.026 ms; 0: gemm_layer2 + film_sin2
-#ifndef OI_PIPE_FWD
-#define OI_PIPE_FWD 1
-#endif
+// F16X3 forward layers run layer_fwd_pipelined (FiLM / sin of block t-1 between block t's MFMAs): same-box A/B against
+// gemm_layer2 + film_sin2, sdf-only pass 1.61 -> 1.57 ms per 2^21 points
 #ifdef OI_PROF
 __device__ unsigned long long oi_prof[16];
 #define PROF_T(i)                                                  \
@@ -504,7 +498,7 @@ __device__ unsigned long long oi_prof[16];
 #endif
 
 template <int PREC, bool FAST, bool FULL>
-__global__ void __launch_bounds__(64 * v2_waves(PREC, FULL), 2)
+__global__ void __launch_bounds__(64 * V2_WAVES, 2)
 sdf_mlp_kernel(const float* __restrict__ pts, const char* __restrict__ packed, const float* __restrict__ gamma,
                const float* __restrict__ beta, float* __restrict__ sdf_out, float* __restrict__ grad_out,
                float* __restrict__ rgb_out, float* __restrict__ feat_out, char* __restrict__ scratch,
@@ -517,9 +511,9 @@ sdf_mlp_kernel(const float* __restrict__ pts, const char* __restrict__ packed, c
   const float* hdr = reinterpret_cast<const float*>(packed);
   const char* mats = packed + H_BYTES;
   constexpr int LB = layer_bytes(PREC);
-  constexpr bool RING2 = v2_two_slots(PREC, FULL);
-  constexpr int NWV = v2_waves(PREC, FULL);
-  constexpr bool REV = OI_SDF_REV && PREC == OI_PREC_F16X3 && !FULL;  // FiLM rows in revolutions (see film_sin2)
+  constexpr bool RING2 = v2_two_slots(PREC);
+  constexpr int NWV = V2_WAVES;
+  constexpr bool REV = PREC == OI_PREC_F16X3 && !FULL;  // FiLM rows in revolutions (see film_sin2)
   // double-buffered ring: the next image is requested at the START of a layer into the other slot.
   // single slot (BF16X6): it is requested right AFTER the layer's MFMAs, behind a barrier, and lands while the
   // FiLM/sin VALU phase runs.
@@ -619,12 +613,10 @@ sdf_mlp_kernel(const float* __restrict__ pts, const char* __restrict__ packed, c
     const int next = (l < NL_SDF - 1) ? l : (FULL ? 13 : (PERSIST ? 0 : -1));  // image index, -1: none; PERSIST: the next tile's first
     if (next >= 0) stage_early(next, ((i + 1) & 1) ^ rb);
     const LayOff y = lay_off<PREC>(o, RING2 ? ((i & 1) ^ rb) : 0, l);
-#if OI_PIPE_FWD
     if constexpr (PREC == OI_PREC_F16X3 && RING2) {
       layer_fwd_pipelined<FAST, FULL, REV>(lds, o, y, acc, act, ws, l);
       PROF_T(1);
     } else
-#endif
     {
       zero_acc(acc);
       gemm_layer2<PREC>(lds, y, act, acc);
@@ -819,8 +811,8 @@ sdf_mlp_kernel(const float* __restrict__ pts, const char* __restrict__ packed, c
 template <int PREC, bool FAST, bool FULL>
 int launch_mlp_variant(const float* pts, const char* pk, const float* gamma, const float* beta, float* sdf, float* grad,
                        float* rgb, float* feat, char* scratch, int B, long long n, hipStream_t st) {
-  constexpr int NWV = v2_waves(PREC, FULL);
-  constexpr int LDS_BYTES = v2_lds_total(PREC, FULL);
+  constexpr int NWV = V2_WAVES;
+  constexpr int LDS_BYTES = v2_lds_total(PREC);
   // the sdf-only passes run persistent workgroups (one per CU: the LDS): as many as the device has CUs (/ B), each walks its
   // share of the tiles; OI_V2_PERSIST=0 (environment): one workgroup per tile, the same kernel (A/B switch)
   static const int per_dev = [] {
@@ -832,7 +824,7 @@ int launch_mlp_variant(const float* pts, const char* pk, const float* gamma, con
     return cus > 0 ? cus : 256;
   }();
   const int tiles = oi::cdiv(n, NWV * WAVE_PTS);
-  const bool persist = !FULL && v2_two_slots(PREC, FULL) && per_dev > 0;
+  const bool persist = !FULL && v2_two_slots(PREC) && per_dev > 0;
   dim3 grid(persist ? std::min(tiles, std::max(1, per_dev / B)) : tiles, B), block(64 * NWV);
   auto k = sdf_mlp_kernel<PREC, FAST, FULL>;
   // per launch: the attribute is per device, and a process may drive several
@@ -845,9 +837,14 @@ template <int PREC, bool FAST>
 int launch_mlp(const float* pts, const void* packed, const float* gamma, const float* beta, float* sdf,
                float* grad, float* rgb, float* feat, void* scratch, int B, long long n, hipStream_t st) {
   const char* pk = reinterpret_cast<const char*>(packed);
-  if (grad != nullptr)
-    return launch_mlp_variant<PREC, FAST, true>(pts, pk, gamma, beta, sdf, grad, rgb, feat,
-                                                reinterpret_cast<char*>(scratch), B, n, st);
+  if (grad != nullptr) {
+    // (F16X3 and BF16 with the gradient run the register-resident kernels of mlp_fwd3.hip / mlp_fwd3b.hip)
+    if constexpr (PREC == OI_PREC_F16X3 || PREC == OI_PREC_BF16)
+      return oi::fail(OI_ERR_INVALID_ARG, "oi_sdf_mlp_fwd: precision %d with the gradient has no v2 kernel", PREC);
+    else
+      return launch_mlp_variant<PREC, FAST, true>(pts, pk, gamma, beta, sdf, grad, rgb, feat,
+                                                  reinterpret_cast<char*>(scratch), B, n, st);
+  }
   return launch_mlp_variant<PREC, FAST, false>(pts, pk, gamma, beta, sdf, nullptr, nullptr, feat, nullptr, B, n, st);
 }
 
@@ -979,9 +976,8 @@ size_t oi_mlp_scratch_bytes(int B, long long n_per_elem) {  // upper bound over 
 }
 
 size_t oi_mlp_scratch_bytes_prec(int B, long long n_per_elem, int prec) {
-  static const bool use_v2 = [] { const char* v = getenv("OI_FWD_V2"); return v && v[0] == '1'; }();
-  if (prec == OI_PREC_F16X3 && !use_v2) return oimlp::full3_scratch_bytes(B, n_per_elem);  // 512 B/point
-  if (prec == OI_PREC_BF16 && !use_v2) return oimlp::full3_bf16_scratch_bytes(B);  // mlp_fwd3b.hip: 15 per-element images
+  if (prec == OI_PREC_F16X3) return oimlp::full3_scratch_bytes(B, n_per_elem);  // 512 B/point
+  if (prec == OI_PREC_BF16) return oimlp::full3_bf16_scratch_bytes(B);           // mlp_fwd3b.hip: 15 per-element images
   return oi_mlp_scratch_bytes(B, n_per_elem);                                               // 4.6 KB/point
 }
 
@@ -1005,13 +1001,12 @@ int oi_sdf_mlp_fwd_ex(const float* pts, const void* packed, const float* gamma, 
   OI_REQUIRE(grad != nullptr || rgb == nullptr, "oi_sdf_mlp_fwd: rgb requires grad");
   OI_REQUIRE(grad == nullptr || scratch != nullptr, "oi_sdf_mlp_fwd: grad requires scratch");
   hipStream_t st = oi::as_stream(stream);
-  // F16X3 with the gradient: the register-resident kernel (mlp_fwd3.hip); OI_FWD_V2=1 keeps the scratch-streaming v2
-  static const bool use_v2 = [] { const char* v = getenv("OI_FWD_V2"); return v && v[0] == '1'; }();
-  if (prec == OI_PREC_F16X3 && grad != nullptr && !use_v2)
+  // F16X3 with the gradient: the register-resident kernel (mlp_fwd3.hip)
+  if (prec == OI_PREC_F16X3 && grad != nullptr)
     return oimlp::launch_full3_f16x3(pts, packed, gamma, beta, sdf, grad, rgb, feat, scratch, B, n_per_elem, fast_trig,
                                      (flags & OI_MLP_BLOB_READY) != 0, st);
   // BF16 with the gradient: the register-resident kernel of mlp_fwd3b.hip (no scratch stream)
-  if (prec == OI_PREC_BF16 && grad != nullptr && !use_v2)
+  if (prec == OI_PREC_BF16 && grad != nullptr)
     return oimlp::launch_full3_bf16(pts, packed, gamma, beta, sdf, grad, rgb, feat, scratch, B, n_per_elem, fast_trig, st);
 #define OI_MLP_CASE(P)                                                                                        \
   case P:                                                                                                     \

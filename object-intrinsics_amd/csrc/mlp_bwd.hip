@@ -68,121 +68,29 @@ constexpr int DS_BRGB = 2436;  // [3] (+1 pad)
 constexpr int DS_TOTAL = 2440;
 
 // LDS of the sweep kernel: FiLM rows (slot 0) | small tables | image slot 0 | image slot 1 | reduction rows | FiLM slot 1.
-// One workgroup (4 waves, one per SIMD, 512 registers each) per CU: the next layer's image and FiLM rows are requested
+// One workgroup per CU (BW_NW waves, below): the next layer's image and FiLM rows are requested
 // while the current layer computes, so a layer boundary costs a barrier and not an LDS-DMA round trip + the drain of
 // every scratch store in flight.
 constexpr int L_RACC = L_WBUF + 2 * 65536;  // per-workgroup reduction scratch: [RACC_ROWS][128] floats
-// Waves per workgroup of the sweep (one workgroup per CU either way: the two image slots fill the LDS).  4 = one wave per
-// SIMD with 512 registers; 8 = two waves per SIMD with 256 registers each (the co-resident wave fills the other's LDS /
-// MFMA-result / memory stalls and the VALU issues 1.45 x faster with two waves to pick from: tools/dbg/valu_issue.hip).
-#ifndef OI_BWD_NW
-#define OI_BWD_NW 8
-#endif
-constexpr int BW_NW = OI_BWD_NW, BW_THREADS = 64 * BW_NW, BW_TILE = WAVE_PTS * BW_NW;
-// groups (of 16) of parked phi / vbar fragments the down sweep requests ahead of their use
-// ... and how many of those stay in flight ACROSS the two products (the accumulators are dead during the epilogue: the
-// ring can be deep there even with 256 registers, but only CARRY groups fit next to three point vectors)
-#ifndef OI_BWD_PF
-#define OI_BWD_PF (OI_BWD_NW == 4 ? 16 : 8)
-#endif
-#ifndef OI_BWD_CARRY
-#define OI_BWD_CARRY (OI_BWD_NW == 4 ? 16 : 1)
-#endif
-#ifndef OI_BWD_PF_F32  // the fp32-MFMA product keeps more fragments live
-#define OI_BWD_PF_F32 (OI_BWD_NW == 4 ? 16 : 4)
-#endif
-// the colour head's contribution to abar_8 waits for the down sweep in registers (1) or in scratch slot S_AC (0)
-#ifndef OI_BWD_AC_REGS
-#define OI_BWD_AC_REGS (OI_BWD_NW == 4)
-#endif
-// Point sums of the colour head, of w_sigma and of layer 0 in rows of their own (1): every row is flushed ONCE, behind the last
-// barrier of the kernel -- the colour head's flush (two barriers and 900 atomics in the tile's first microseconds), the barrier
-// of the turn and layer 0's re-zeroing go away.  0: one set of 8 rows, flushed and re-zeroed where each user ends (round 5).
-// Persistent workgroups (1): one per CU (/ B) walks its share of the element's tiles -- tables, layer 0's FiLM rows and the zeroed
-// reduction rows are set up once, the rows are flushed once per workgroup (needs OI_BWD_LATE_FLUSH).  0 (default): one workgroup
-// per tile.  Measured, round 6: 2.78 / 2.83 ms persistent against 2.77 / 2.77 (same box, alternating) -- nothing sits between two
-// tiles of a CU that a loop would remove (the per-CU timelines of tools/dbg/phase_prof_bwd.py: a CU's tiles follow each other
-// within the profiling code's own cost), and tile lifetimes spread 0.55x .. 1.45x around their mean: the tiles wait on the
-// memory system they share, not on their own start.
-#ifndef OI_BWD_PERSIST
-#define OI_BWD_PERSIST 0
-#endif
-#ifndef OI_BWD_LATE_FLUSH
-#define OI_BWD_LATE_FLUSH 1
-#endif
-constexpr int RACC_ROWS = OI_BWD_LATE_FLUSH ? 16 : 8;
-constexpr int RR_COL = OI_BWD_LATE_FLUSH ? 8 : 0;    // the colour head's rows 2..7 -> RR_COL + 2 .. RR_COL + 7
-constexpr int RR_WSIG = OI_BWD_LATE_FLUSH ? 0 : 3;   // (layer 0: rows 1, 3, 4, 5)
+// Waves per workgroup of the sweep (one workgroup per CU: the two image slots fill the LDS): two waves per SIMD with 256
+// registers each (the co-resident wave fills the other's LDS / MFMA-result / memory stalls and the VALU issues 1.45 x faster
+// with two waves to pick from: tools/dbg/valu_issue.hip).
+constexpr int BW_NW = 8, BW_THREADS = 64 * BW_NW, BW_TILE = WAVE_PTS * BW_NW;
+// Point sums in LDS rows: the colour head's (RR_COL + 2 .. RR_COL + 7), w_sigma's (RR_WSIG) and layer 0's (1, 3, 4, 5) rows are
+// their own, and every row is flushed ONCE, behind the last barrier of the kernel.
+constexpr int RACC_ROWS = 16;
+constexpr int RR_COL = 8;
+constexpr int RR_WSIG = 0;
 constexpr int L_FILM2 = L_RACC + RACC_ROWS * C * 4;
 constexpr int L_TOTAL_BWD = L_FILM2 + 1536;
 
-// Cache policy per slot family (aux operand of the buffer instructions; measured in oi_common.h's table):
-//   LOCAL  slots are re-read later in THIS kernel (phi, g, cbar, the colour-head pair),
-//   WGRAD  slots are only written here and consumed by the weight-gradient GEMM (v, gbar, ubar).
-#ifndef OI_BWD_ST_LOCAL
-#define OI_BWD_ST_LOCAL OI_BWD_NT_ST
-#endif
-#ifndef OI_BWD_ST_WGRAD
-#define OI_BWD_ST_WGRAD OI_BWD_NT_ST
-#endif
-#ifndef OI_BWD_LD_EARLY
-#define OI_BWD_LD_EARLY 0  // phi read in phases B and C is read again in phase D: 8.59 vs 8.66 ms per training render
-#endif
-#ifndef OI_BWD_LD_LAST
-#define OI_BWD_LD_LAST OI_BWD_NT_LD
-#endif
-// Round 4, measured and NOT adopted as the default (-DOI_BWD_PACK24=1 builds it): the parked vectors crossing HBM as 24-bit
-// values (F16X3 mode, accurate trig) -- 12 instead of 16 KiB per slot, a quarter of the 19 GB a backward moves.
-//   phase slots   the reduced phase r in [0, 1) as 24-bit FIXED point (2^-24 absolute: finer than fp32's own spacing near 1)
-//   every other   fp32 with the mantissa rounded to 15 stored bits (2^-16 relative)
-// Four values = three dwords, moved by v_perm_b32 (3 to pack + 4 rounding adds, 4 to unpack).  Same box, 30 training
-// iterations: 9.68 -> 9.31 ms per iteration (render forward + backward 5.88 -> 5.57 ms).  The price: the worst parameter-
-// gradient error of the seven f16x3 gradient tests goes from 0.5-1.2e-5 to 1.4-1.8e-5 against a bar of 2e-5 (tools/dbg/
-// run_q24.sh: every slot family contributes -- gamma vbar 1.7e-5, v / phibar 1.5e-5, the colour pair 1.2e-5 on its own); a
-// format that keeps the bar's margin (24-bit fixed point relative to a per-lane maximum) costs 11 + 8 instead of 7 + 4
-// instructions per four values and needs the maxima before the stores: estimated to return less than half of the 0.37 ms.
-#ifndef OI_BWD_PACK24
-#define OI_BWD_PACK24 0
-#endif
-#ifndef OI_WGRAD_BF16
-#define OI_WGRAD_BF16 1   // bf16 operand mode: the two-tiles-in-flight GEMM with bf16 operands (0: the generic fp32-MFMA GEMM)
-#endif
+// Cache policy of the scratch slots: oi::BWD_NT_ST / BWD_NT_LD (measured in oi_common.h's table).
 typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-__device__ __forceinline__ u32x3 pack24f(f32x4 v) {
-  // (element copies first: __builtin_bit_cast applied to a vector-element lvalue read element 0 four times -- hipcc 7.2)
-  const float x0 = v[0], x1 = v[1], x2 = v[2], x3 = v[3];
-  const unsigned b0 = __builtin_bit_cast(unsigned, x0) + 0x80u, b1 = __builtin_bit_cast(unsigned, x1) + 0x80u;
-  const unsigned b2 = __builtin_bit_cast(unsigned, x2) + 0x80u, b3 = __builtin_bit_cast(unsigned, x3) + 0x80u;
-  // bytes 1..3 of every value: {b0.1 b0.2 b0.3 b1.1} {b1.2 b1.3 b2.1 b2.2} {b2.3 b3.1 b3.2 b3.3}
-  return u32x3{__builtin_amdgcn_perm(b1, b0, 0x05030201u), __builtin_amdgcn_perm(b2, b1, 0x06050302u),
-               __builtin_amdgcn_perm(b3, b2, 0x07060503u)};
-}
-__device__ __forceinline__ f32x4 unpack24f(u32x3 d) {
-  const unsigned b0 = __builtin_amdgcn_perm(0u, d[0], 0x0201000cu), b1 = __builtin_amdgcn_perm(d[1], d[0], 0x0504030cu);
-  const unsigned b2 = __builtin_amdgcn_perm(d[2], d[1], 0x0403020cu), b3 = __builtin_amdgcn_perm(0u, d[2], 0x0302010cu);
-  return f32x4{__builtin_bit_cast(float, b0), __builtin_bit_cast(float, b1), __builtin_bit_cast(float, b2),
-               __builtin_bit_cast(float, b3)};
-}
-__device__ __forceinline__ u32x3 pack24q(f32x4 r) {  // r in [0, 1)
-  const unsigned q0 = (unsigned)(r[0] * 16777216.f), q1 = (unsigned)(r[1] * 16777216.f);
-  const unsigned q2 = (unsigned)(r[2] * 16777216.f), q3 = (unsigned)(r[3] * 16777216.f);
-  return u32x3{__builtin_amdgcn_perm(q1, q0, 0x04020100u), __builtin_amdgcn_perm(q2, q1, 0x05040201u),
-               __builtin_amdgcn_perm(q3, q2, 0x06050402u)};
-}
-__device__ __forceinline__ f32x4 unpack24q(u32x3 d) {
-  const unsigned q0 = __builtin_amdgcn_perm(0u, d[0], 0x0c020100u), q1 = __builtin_amdgcn_perm(d[1], d[0], 0x0c050403u);
-  const unsigned q2 = __builtin_amdgcn_perm(d[2], d[1], 0x0c040302u), q3 = __builtin_amdgcn_perm(0u, d[2], 0x0c030201u);
-  constexpr float S = 1.0f / 16777216.f;
-  return f32x4{(float)q0 * S, (float)q1 * S, (float)q2 * S, (float)q3 * S};
-}
 
-// Round 5, the bf16 operand mode only (OI_BWD_PACK16, default on): 16-bit slots -- values as bf16 (v_cvt_pk_bf16_f32: fp32's
+// The bf16 operand mode: 16-bit slots -- values as bf16 (v_cvt_pk_bf16_f32: fp32's
 // range, 8 bits, what the mode's MFMA operands carry anyway), phases REDUCED to [0, 1) and stored as unorm16
 // (v_cvt_pknorm_u16_f32: 1.5e-5 revolutions).  Half the bytes of a backward in the mode BASELINE's configs[1] names; four values
 // = two dwords, 2 instructions to pack, 4 to unpack.
-#ifndef OI_BWD_PACK16
-#define OI_BWD_PACK16 1
-#endif
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u32x2 pack16f(f32x4 v) {
@@ -205,18 +113,15 @@ __device__ __forceinline__ f32x4 unpack16q(u32x2 d) {
   return f32x4{(float)(d[0] & 0xffffu) * S, (float)(d[0] >> 16) * S, (float)(d[1] & 0xffffu) * S, (float)(d[1] >> 16) * S};
 }
 
-// Round 5 (second half), f16x3 mode: the two slot families only the weight-gradient GEMM reads (S_V, S_U: 14 of the 29 slots a
-// sweep writes, 14 of the 28 the GEMM reads) as 24-bit FIXED point relative to a per-lane power-of-two scale (OI_BWD_XQ24).
+// f16x3 mode: the two slot families only the weight-gradient GEMM reads (S_V, S_U: 14 of the 29 slots a sweep writes, 14 of the
+// 28 the GEMM reads) as 24-bit FIXED point relative to a per-lane power-of-two scale ("X slots").
 //   y = x * s + 1.5 with |x| s < 1/4 puts a value into ONE binade: its 23 mantissa bits are fixed point (2^-23 of 4 max|x|:
 //   2^-21 of the lane's largest value, the resolution of the GEMM's own fp16 hi + lo split), rounded to nearest by the FMA.
 //   The low three bytes of y are kept; four values = three dwords [a0 a1 a2 d0] [b0 b1 b2 d1] [c0 c1 c2 d2]: 4 FMA + 3 v_perm to
 //   pack (the round-4 float24 format: 4 adds + 3 v_perm), 3 v_and_or + 3 to unpack, and the de-scaling rides on the multiply by
 //   the launch-wide scale the GEMM applies anyway (x * scx = y * k - 1.5 k, k = scx / s).  The lane's 1 / s sits behind the 16
 //   groups of the slot (byte 12,288 + 4 lane).  The lane maximum exists before the first store because the down sweep stores
-//   v / phibar AFTER its epilogue (OI_BWD_STORES_LAST): one v_max3 per two values, then reused for the launch-wide maxima.
-#ifndef OI_BWD_XQ24
-#define OI_BWD_XQ24 1
-#endif
+//   v / phibar AFTER its epilogue: one v_max3 per two values, then reused for the launch-wide maxima.
 constexpr int XQ_SCALE_OFF = 16 * 768;  // byte offset of the per-lane inverse scales inside a slot
 __device__ __forceinline__ u32x3 pack_q24(f32x4 v, float s) {
   const float y0 = fmaf(v[0], s, 1.5f), y1 = fmaf(v[1], s, 1.5f), y2 = fmaf(v[2], s, 1.5f), y3 = fmaf(v[3], s, 1.5f);
@@ -237,22 +142,16 @@ __device__ __forceinline__ f32x4 unpack_q24(u32x3 q) {
   return f32x4{__builtin_bit_cast(float, a), __builtin_bit_cast(float, b), __builtin_bit_cast(float, c),
                __builtin_bit_cast(float, d)};
 }
-// OI_BWD_PHQ24: the phase slots the same way without a scale -- the parked phase is already reduced to [0, 1) revolutions, so
+// The phase slots (f16x3 mode, accurate trig) the same way without a scale -- the parked phase is already reduced to [0, 1) revolutions, so
 // y = r + 1 is its 23-bit fixed-point form (2^-23 revolutions: 7.5e-7 rad), and v_sin / v_cos take y AS IT IS (the period is 1).
-#ifndef OI_BWD_PHQ24
-#define OI_BWD_PHQ24 1
-#endif
 __device__ __forceinline__ u32x3 pack_q24_phase(f32x4 r) {
   const unsigned a = __builtin_bit_cast(unsigned, r[0] + 1.0f), b = __builtin_bit_cast(unsigned, r[1] + 1.0f);
   const unsigned c = __builtin_bit_cast(unsigned, r[2] + 1.0f), d = __builtin_bit_cast(unsigned, r[3] + 1.0f);
   return u32x3{__builtin_amdgcn_perm(d, a, 0x04020100u), __builtin_amdgcn_perm(d, b, 0x05020100u),
                __builtin_amdgcn_perm(d, c, 0x06020100u)};
 }
-// OI_BWD_VBQ24: the gamma vbar slots (S_VB: written by the up sweep, read by the down sweep and by the GEMM) in the X-slot format;
+// The gamma vbar slots (f16x3 mode; S_VB: written by the up sweep, read by the down sweep and by the GEMM) in the X-slot format;
 // the up sweep finishes the vector in its point registers, takes the lane maximum, then packs and stores
-#ifndef OI_BWD_VBQ24
-#define OI_BWD_VBQ24 1
-#endif
 // s with max|x| * s < 1/4 (mx < 2^(E - 126) for the biased exponent E of mx) and its inverse, both exact powers of two
 __device__ __forceinline__ void q24_scale(float mx, float& s, float& inv_s) {
   int E = (__builtin_bit_cast(int, mx) >> 23) & 0xff;
@@ -285,50 +184,40 @@ __global__ void selftest_q24_kernel(const float* __restrict__ x, float* __restri
   }
 }
 
-// PACK: 0 = fp32 slots (16 bytes per lane and group), 1 = 24-bit (12), 2 = 16-bit (8)
+// PACK: 0 = fp32 slots (16 bytes per lane and group), 2 = 16-bit (8)
 template <int PACK, bool PHQ = false>
 struct WaveScratchT {
   __amdgpu_buffer_rsrc_t rs;
-  int l12;  // 12 * lane (PACK 1) / 8 * lane (PACK 2)
-  static constexpr int GROUP = PACK == 0 ? 1024 : (PACK == 1 ? 768 : 512);   // bytes of one group of a slot
+  int l12;  // 12 * lane (PHQ phase slots) / 8 * lane (PACK 2)
   // (stores: the wave-uniform offset is folded into voffset, soffset = 0: the >64-bit store hazard of oi::buffer_store_b128)
-  template <int AUX = OI_BWD_ST_LOCAL>
+  template <int AUX = oi::BWD_NT_ST>
   __device__ __forceinline__ void store(int slot, int g, int l16, f32x4 v) const {
-#ifdef OI_BWD_Q24_SET  // precision experiment (32-bit slots): round the families in the mask to the 24-bit float format
-    {
-      const int fam = slot >= S_UV ? 3 : (slot >= S_V ? 2 : 1);
-      if ((OI_BWD_Q24_SET >> fam) & 1) v = unpack24f(pack24f(v));
-    }
-#endif
-    if constexpr (PACK == 1) __builtin_amdgcn_raw_buffer_store_b96(pack24f(v), rs, l12 + (slot * 16384 + g * 768), 0, AUX);
-    else if constexpr (PACK == 2) __builtin_amdgcn_raw_buffer_store_b64(pack16f(v), rs, l12 + (slot * 16384 + g * 512), 0, AUX);
+    if constexpr (PACK == 2) __builtin_amdgcn_raw_buffer_store_b64(pack16f(v), rs, l12 + (slot * 16384 + g * 512), 0, AUX);
     else oi::buffer_store_b128<AUX>(__builtin_bit_cast(u32x4, v), rs, l16, slot * 16384 + g * 1024);
   }
-  template <int AUX = OI_BWD_ST_LOCAL>
+  template <int AUX = oi::BWD_NT_ST>
   __device__ __forceinline__ void store_phase(int slot, int g, int l16, f32x4 v) const {
     if constexpr (PHQ) __builtin_amdgcn_raw_buffer_store_b96(pack_q24_phase(v), rs, l12 + (slot * 16384 + g * 768), 0, AUX);
-    else if constexpr (PACK == 1) __builtin_amdgcn_raw_buffer_store_b96(pack24q(v), rs, l12 + (slot * 16384 + g * 768), 0, AUX);
     else if constexpr (PACK == 2) __builtin_amdgcn_raw_buffer_store_b64(pack16q(v), rs, l12 + (slot * 16384 + g * 512), 0, AUX);
     else oi::buffer_store_b128<AUX>(__builtin_bit_cast(u32x4, v), rs, l16, slot * 16384 + g * 1024);
   }
-  // A parked fragment as it arrives (2, 3 or 4 dwords); unpacked where it is USED -- the ring of the down sweep requests
+  // A parked fragment as it arrives (2 or 4 dwords); unpacked where it is USED -- the ring of the down sweep requests
   // fragments a layer ahead, and an unpack next to the load would wait for it on the spot
-  using Frag = std::conditional_t<PACK == 1, u32x3, std::conditional_t<PACK == 2, u32x2, f32x4>>;
-  template <int AUX = OI_BWD_LD_LAST>
+  using Frag = std::conditional_t<PACK == 2, u32x2, f32x4>;
+  template <int AUX = oi::BWD_NT_LD>
   __device__ __forceinline__ Frag load(int slot, int g, int l16) const {
-    if constexpr (PACK == 1) return __builtin_amdgcn_raw_buffer_load_b96(rs, l12, slot * 16384 + g * 768, AUX);
-    else if constexpr (PACK == 2) return __builtin_amdgcn_raw_buffer_load_b64(rs, l12, slot * 16384 + g * 512, AUX);
+    if constexpr (PACK == 2) return __builtin_amdgcn_raw_buffer_load_b64(rs, l12, slot * 16384 + g * 512, AUX);
     else return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, l16, slot * 16384 + g * 1024, AUX));
   }
   static __device__ __forceinline__ f32x4 value(const Frag& f) {
-    if constexpr (PACK == 1) return unpack24f(f); else if constexpr (PACK == 2) return unpack16f(f); else return f;
+    if constexpr (PACK == 2) return unpack16f(f); else return f;
   }
   static __device__ __forceinline__ f32x4 phase(const Frag& f) {
-    if constexpr (PACK == 1) return unpack24q(f); else if constexpr (PACK == 2) return unpack16q(f); else return f;
+    if constexpr (PACK == 2) return unpack16q(f); else return f;
   }
   // phase slots under PHQ: three dwords per four values, whatever the other slots are
   using PFrag = std::conditional_t<PHQ, u32x3, Frag>;
-  template <int AUX = OI_BWD_LD_LAST>
+  template <int AUX = oi::BWD_NT_LD>
   __device__ __forceinline__ PFrag load_phase(int slot, int g, int l16) const {
     if constexpr (PHQ) return __builtin_amdgcn_raw_buffer_load_b96(rs, l12, slot * 16384 + g * 768, AUX);
     else return load<AUX>(slot, g, l16);
@@ -455,9 +344,6 @@ __device__ __forceinline__ void dma_sync_keep() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KEEP) : "memory");
   __syncthreads();
 }
-#ifndef OI_BWD_UP_KEEP
-#define OI_BWD_UP_KEEP 32
-#endif
 
 // One layer product of the backward sweeps: acc = W_img . v with only ONE k-step of A fragments (4 output blocks x hi / lo
 // limb = 32 VGPRs) live at a time -- two 64-register point vectors and the accumulators are live around every product of
@@ -476,9 +362,7 @@ __device__ __forceinline__ void gemm_lean(const char* lds, const LaneOff& o, con
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, bh, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, bl, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, bh, acc[t], 0, 0, 0);
-#if OI_BWD_NW == 8
         if (t & 1) __builtin_amdgcn_sched_barrier(0);  // (256 registers: at most two output blocks' fragments in flight)
-#endif
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -519,16 +403,6 @@ __device__ __forceinline__ void publish_max(float* op_max, int slot, float lane_
     atomicMax(reinterpret_cast<unsigned*>(op_max) + rep * OM_STRIDE + slot, __builtin_bit_cast(unsigned, m));
 }
 
-// timing ablations (results are garbage): -DOI_BWD_ABL=1 no v / ubar stores, 2 no phi / vbar reloads, 4 no up-sweep stores
-#ifndef OI_BWD_ABL
-#define OI_BWD_ABL 0
-#endif
-#ifndef OI_BWD_COL_FENCE
-#define OI_BWD_COL_FENCE 1
-#endif
-#ifndef OI_BWD_STORES_LAST
-#define OI_BWD_STORES_LAST 1
-#endif
 // -DOI_BWD_PROF: per-phase shader-clock accounting of the sweep (tools/dbg/phase_prof_bwd.py)
 #ifdef OI_BWD_PROF
 __device__ unsigned long long oi_prof_bwd[24];
@@ -564,17 +438,8 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   const char* mats = packed + H_BYTES;
   const bool has_col = rgb_fwd != nullptr && g_rgb != nullptr && feat_fwd != nullptr;
   const int n_tiles = (int)((n_per_elem + BW_TILE - 1) / BW_TILE);   // of this launch, per batch element
-#if OI_BWD_PERSIST
-  static_assert(OI_BWD_LATE_FLUSH == 1, "persistent workgroups keep their point sums in LDS across tiles");
-  for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-  const bool first = tile == (int)blockIdx.x, last = tile + (int)gridDim.x >= n_tiles;
-#else
-  {
   const int tile = blockIdx.x;
-  constexpr bool first = true, last = true;
-#endif
-  // (the thread index is taken anew per tile, through an empty asm: everything derived from it -- lane offsets, the per-lane
-  // addresses of the FiLM rows and tables -- would otherwise be hoisted out of the tile loop and kept, i.e. spilled, across it)
+  // (the thread index goes through an empty asm: see late())
   const int tid = late(threadIdx.x), lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, j = lane & 31;
@@ -594,12 +459,12 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   const __amdgpu_buffer_rsrc_t img_rs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(mats), 0, NMAT * layer_bytes(PREC), 0x00020000);
 
-  // (24-bit: accurate trig only -- fast trig parks unreduced phases; the 16-bit format reduces them as it packs)
-  constexpr int PK = (OI_BWD_PACK16 && OI_WGRAD_BF16 && PREC == OI_PREC_BF16) ? 2 : ((OI_BWD_PACK24 && PREC == OI_PREC_F16X3 && !FAST) ? 1 : 0);
-  constexpr bool PHQ = OI_BWD_PHQ24 && PK == 0 && PREC == OI_PREC_F16X3 && !FAST;   // phase slots as 24-bit fixed point
+  // (24-bit phases: accurate trig only -- fast trig parks unreduced phases; the 16-bit format reduces them as it packs)
+  constexpr int PK = PREC == OI_PREC_BF16 ? 2 : 0;
+  constexpr bool PHQ = PREC == OI_PREC_F16X3 && !FAST;   // phase slots as 24-bit fixed point
   WaveScratchT<PK, PHQ> ws;
-  constexpr bool XQ = OI_BWD_XQ24 && PK == 0 && PREC == OI_PREC_F16X3 && OI_BWD_STORES_LAST;  // S_V / S_U as 24-bit fixed point
-  constexpr bool VBQ = OI_BWD_VBQ24 && PK == 0 && PREC == OI_PREC_F16X3;                      // S_VB likewise
+  constexpr bool XQ = PREC == OI_PREC_F16X3;             // S_V / S_U as 24-bit fixed point
+  constexpr bool VBQ = PREC == OI_PREC_F16X3;            // S_VB likewise
   ws.l12 = (PK == 2 ? 8 : 12) * lane;
   asm volatile("" : "+v"(ws.l12));
   {
@@ -647,16 +512,12 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   // prologue is issued AHEAD of them (tables, both sets of FiLM rows, the point, its upstream gradients and forward values), so
   // that the LDS copies of the tables wait for those loads only -- round 5 paid four dependent round trips here (DMA, rows, tables,
   // point) before the first product.
-  // (tables, layer 0's rows and the zeroed reduction rows: the workgroup's first tile only -- the down sweep leaves layer 0's rows
-  // in FiLM slot 0 again)
   FilmRegs fr8{}, fr1{}, fr0{};
   constexpr int NTAB = (H_TABS_END + BW_THREADS - 1) / BW_THREADS;
   float tabv[NTAB];
-  if (first) {
-    fr0 = load_flm(0);
+  fr0 = load_flm(0);
 #pragma unroll
-    for (int i = 0; i < NTAB; ++i) tabv[i] = hdr[min(tid + i * BW_THREADS, H_TABS_END - 1)];
-  }
+  for (int i = 0; i < NTAB; ++i) tabv[i] = hdr[min(tid + i * BW_THREADS, H_TABS_END - 1)];
   if (has_col) fr8 = load_flm(8);
   const float px = pts[pt * 3 + 0], py = pts[pt * 3 + 1], pz = pts[pt * 3 + 2];
   const float gs = (g_sdf ? g_sdf[pt] : 0.f) * vmask;
@@ -679,14 +540,14 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     stage_img(14, 0);
     stage_img(15, 1);
   }
-  if (first) {
+  {
     float* tabs = reinterpret_cast<float*>(lds + L_TABS);
 #pragma unroll
     for (int i = 0; i < NTAB; ++i)
       if (tid + i * BW_THREADS < H_TABS_END) tabs[tid + i * BW_THREADS] = tabv[i];
-    store_flm(fr0, 0);
-    racc_zero(lds, tid);
   }
+  store_flm(fr0, 0);
+  racc_zero(lds, tid);
   if (has_col) store_flm(fr8, 1);
   __syncthreads();
 
@@ -715,13 +576,7 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   };
   // ================= colour head backward (first: its dL/dgrad term is part of gbar_0) =================
   OI_MARK("colour x1");
-  // abar_8 contribution of the colour head: waits for the down sweep in registers (one wave per SIMD: the AGPR half has
-  // room) or in scratch slot S_AC
-#if OI_BWD_AC_REGS
-  float ac[64];
-#pragma unroll
-  for (int k = 0; k < 64; ++k) ac[k] = 0.f;
-#endif
+  // abar_8 contribution of the colour head: waits for the down sweep in scratch slot S_AC
   if (has_col) {
     dma_sync();
     BW_T(14);
@@ -769,9 +624,7 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         ws.store(S_UV, g, o.l16, pvb);
 #pragma unroll
         for (int k = 0; k < 4; ++k) act[4 * g + k] = uvb[k];
-#if OI_BWD_COL_FENCE
         __builtin_amdgcn_sched_barrier(0);
-#endif
       }
 #pragma unroll
       for (int r = 2; r < 8; ++r) {
@@ -798,12 +651,6 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         atomicAdd(d_small + DS_BRGB + 2, b2);
       }
     }
-    if constexpr (!OI_BWD_LATE_FLUSH) {
-      __syncthreads();
-      flush_colour(reinterpret_cast<const float*>(lds + L_FILM2));  // the head's rows sit in FiLM slot 1
-      __syncthreads();
-      racc_zero(lds, tid);
-    }
     BW_T(17);
     // abar_8 from the colour head: Wv[:, :128]^T uvbar   (transposed colour image, matrix 15: resident in slot 1 since the
     // prologue)
@@ -822,12 +669,7 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = fmaf(gf[k], vmask, v[k]);
       }
-#if OI_BWD_AC_REGS
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ac[4 * g + k] = v[k];
-#else
       ws.store(S_AC, g, o.l16, v);
-#endif
     }
   } else if constexpr (GFEAT) {
 #pragma unroll
@@ -835,12 +677,7 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
       f32x4 v = *reinterpret_cast<const f32x4*>(g_feat + pt * C + grp_f0(g) + 4 * h);
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] *= vmask;
-#if OI_BWD_AC_REGS
-#pragma unroll
-      for (int k = 0; k < 4; ++k) ac[4 * g + k] = v[k];
-#else
       ws.store(S_AC, g, o.l16, v);
-#endif
     }
   }
 
@@ -878,8 +715,8 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     __builtin_amdgcn_sched_barrier(0);
   }
   if (h == 0) {  // what the weight-gradient GEMM needs to form phi_0 / vbar_0 itself (lane j = point j)
-    oi::buffer_store_b128<OI_BWD_ST_WGRAD>(__builtin_bit_cast(u32x4, f32x4{px, py, pz, 0.f}), ws.rs, 32 * j, S_PHI * 16384);
-    oi::buffer_store_b128<OI_BWD_ST_WGRAD>(__builtin_bit_cast(u32x4, f32x4{Gx, Gy, Gz, 0.f}), ws.rs, 32 * j + 16, S_PHI * 16384);
+    oi::buffer_store_b128<oi::BWD_NT_ST>(__builtin_bit_cast(u32x4, f32x4{px, py, pz, 0.f}), ws.rs, 32 * j, S_PHI * 16384);
+    oi::buffer_store_b128<oi::BWD_NT_ST>(__builtin_bit_cast(u32x4, f32x4{Gx, Gy, Gz, 0.f}), ws.rs, 32 * j + 16, S_PHI * 16384);
   }
   BW_T(1);
   // The last layer is peeled: its phase and vbar are what the down sweep consumes FIRST, so they stay in the two point
@@ -891,7 +728,7 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     if constexpr (LAST) OI_MARK("up_last x1"); else OI_MARK("up_body x6");
     // layer l's image and FiLM rows have landed; every wave is done with layer l - 1.  The 32 phi / vbar stores of the
     // previous layer were issued after that DMA and need not have drained.
-    if constexpr (OI_BWD_ABL & 4) dma_sync(); else dma_sync_keep<OI_BWD_UP_KEEP>();
+    dma_sync_keep<32>();
     BW_T(2);
     const FilmRegs fr = load_flm(LAST ? l : l + 1);  // next layer's FiLM rows: requested ahead of the image DMA
     stage_img(LAST ? 13 : l, l & 1);  // (the down sweep starts with the transposed image of layer 7)
@@ -914,9 +751,9 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         gb[4 * g + k] = v[k];
       }
       if constexpr (!VBQ)
-        if (!LAST && !(OI_BWD_ABL & 4)) ws.store(S_VB + l, g, o.l16, v);
+        if (!LAST) ws.store(S_VB + l, g, o.l16, v);
     }
-    if constexpr (VBQ && !LAST && !(OI_BWD_ABL & 4)) {  // the vector is complete in gb: lane maximum, then pack and store
+    if constexpr (VBQ && !LAST) {  // the vector is complete in gb: lane maximum, then pack and store
       float mx = 0.f;
 #pragma unroll
       for (int k = 0; k < 64; k += 2) mx = fmaxf(mx, fmaxf(fabsf(gb[k]), fabsf(gb[k + 1])));
@@ -925,10 +762,10 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
         const u32x3 q = pack_q24(f32x4{gb[4 * g], gb[4 * g + 1], gb[4 * g + 2], gb[4 * g + 3]}, sq);
-        __builtin_amdgcn_raw_buffer_store_b96(q, ws.rs, ws.l12 + ((S_VB + l) * 16384 + g * 768), 0, OI_BWD_ST_LOCAL);
+        __builtin_amdgcn_raw_buffer_store_b96(q, ws.rs, ws.l12 + ((S_VB + l) * 16384 + g * 768), 0, oi::BWD_NT_ST);
       }
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, inv_sq), ws.rs,
-                                            4 * lane + ((S_VB + l) * 16384 + XQ_SCALE_OFF), 0, OI_BWD_ST_LOCAL);
+                                            4 * lane + ((S_VB + l) * 16384 + XQ_SCALE_OFF), 0, oi::BWD_NT_ST);
     }
     if constexpr (!LAST) store_flm(fr, (l + 1) & 1);  // FiLM slot of layer l - 1: free since this layer's barrier
     // phi_l / 2pi = G (W_img a_l) + B2 (image scale and bias folded into the staged rows) -> a_{l+1};
@@ -956,7 +793,7 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
           gb[4 * g + k] *= c;
         }
       }
-      if (!(OI_BWD_ABL & 4)) ws.store_phase(S_PHI + l, g, o.l16, ph);
+      ws.store_phase(S_PHI + l, g, o.l16, ph);
       if constexpr (LAST)
         if ((g & 3) == 3) rs.add(RR_WSIG, g >> 2, wsig_row);
       __builtin_amdgcn_sched_barrier(0);
@@ -972,19 +809,15 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     b = oi::wave_sum(b);
     if (lane == 0) atomicAdd(d_small + DS_BSIG, b);
   }
-  if constexpr (!OI_BWD_LATE_FLUSH) {
-    __syncthreads();
-    racc_flush_row(lds, RR_WSIG, d_small + DS_WSIG, 1, tid);
-  }
 
   // ================= down sweep: g_l and abar_l together =================
   // The top layer (7) takes phi_7 / vbar_7 from the point vectors, g_8 = w_sigma from the tables and abar_8 = gs * w_sigma
-  // (+ the colour head's contribution: registers or slot S_AC, which then travels through the phi half of the ring).
-  // the transposed image of layer l sits in image slot l & 1, its FiLM rows in FiLM slot l & 1; phi_l / vbar_l of the WHOLE
-  // layer are requested one layer ahead (128 registers: the reason this kernel runs one wave per SIMD)
-  // (a ring of PF groups: with 512 registers a whole layer, PF = 16, is in flight across the two products)
-  constexpr int PF = PREC == OI_PREC_F32 ? OI_BWD_PF_F32 : OI_BWD_PF, CARRY = OI_BWD_CARRY;
-  static_assert(PF >= 1 && PF <= 16 && (PF & (PF - 1)) == 0 && CARRY >= 1 && CARRY <= PF, "OI_BWD_PF / OI_BWD_CARRY");
+  // (+ the colour head's contribution from slot S_AC, which travels through the phi half of the ring).
+  // the transposed image of layer l sits in image slot l & 1, its FiLM rows in FiLM slot l & 1; phi_l / vbar_l are requested
+  // ahead of their use through a ring of PF groups (the fp32-MFMA product keeps more fragments live), and CARRY of them stay in
+  // flight ACROSS the two products (the accumulators are dead during the epilogue, but with 256 registers only CARRY groups
+  // fit next to three point vectors)
+  constexpr int PF = PREC == OI_PREC_F32 ? 4 : 8, CARRY = 1;
   using Frag = typename WaveScratchT<PK, PHQ>::Frag;
   using PFrag = typename WaveScratchT<PK, PHQ>::PFrag;
   using VFrag = std::conditional_t<VBQ, u32x3, Frag>;
@@ -993,20 +826,17 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   Frag acn[PF < 4 ? PF : 4];   // the colour head's slot S_AC, top layer only (the two rings above are idle there)
   [[maybe_unused]] float vbinv_next = 1.f;   // VBQ: 1 / s of this lane's gamma vbar of the layer about to be swept
   auto load_vb = [&](int slot, int g) -> VFrag {
-    if constexpr (VBQ) return __builtin_amdgcn_raw_buffer_load_b96(ws.rs, ws.l12, slot * 16384 + g * 768, OI_BWD_LD_LAST);
+    if constexpr (VBQ) return __builtin_amdgcn_raw_buffer_load_b96(ws.rs, ws.l12, slot * 16384 + g * 768, oi::BWD_NT_LD);
     else return ws.load(slot, g, o.l16);
   };
   auto load_vb_scale = [&](int slot) {
     if constexpr (VBQ)
       vbinv_next = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ws.rs, 4 * lane, slot * 16384 + XQ_SCALE_OFF,
-                                                                                  OI_BWD_LD_LAST));
+                                                                                  oi::BWD_NT_LD));
   };
-  f32x4 abl_sink;  // (OI_BWD_ABL & 8)
   constexpr int PFT = PF < 4 ? PF : 4;  // ring depth of the top layer (its point vectors carry phi_7 / vbar_7 as well)
-#if !OI_BWD_AC_REGS
 #pragma unroll
   for (int g = 0; g < PFT; ++g) acn[g] = ws.load(S_AC, g, o.l16);  // (no colour head: never written, never used)
-#endif
   BW_T(6);
   // layer 0 is peeled (its extra d W0 rows and missing products are compile-time): no branch inside the unrolled epilogue
   // KIND 0: layers 6..1 (a run-time loop), 1: layer 0, 2: the top layer 7
@@ -1015,13 +845,9 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     if constexpr (L0) OI_MARK("down0 x1"); else if constexpr (TOP) OI_MARK("down_top x1"); else OI_MARK("down_body x6");
     dma_sync();  // layer l's transposed image and FiLM rows have landed
     BW_T(7);
-    if constexpr (L0 && !OI_BWD_LATE_FLUSH) {  // the reduction rows still hold the w_sigma sums of the up sweep (flushed many barriers ago)
-      racc_zero(lds, tid);
-      __syncthreads();
-    }
     const FilmRegs fr = load_flm(l >= 1 ? l - 1 : 0);  // ahead of the image DMA (see film_load)
     [[maybe_unused]] const float vbinv = vbinv_next;   // (requested with this layer's first ring groups, a layer ago)
-    if constexpr (!L0 && !TOP && CARRY < PF && !(OI_BWD_ABL & 2)) {  // groups 0 .. CARRY-1 travelled under the products; fill the ring
+    if constexpr (!L0 && !TOP) {  // groups 0 .. CARRY-1 travelled under the products; fill the ring
 #pragma unroll
       for (int g = CARRY; g < PF; ++g) {
         phn[g] = ws.load_phase(S_PHI + l, g, o.l16);
@@ -1070,11 +896,7 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         f32x4 gnx, abx;  // g_{l+1}, abar_{l+1}
         if constexpr (TOP) {
           gnx = lds_f4(lds, L_TABS + (H_SIG + grp_f0(g)) * 4, o.h16);  // g_8 = w_sigma
-#if OI_BWD_AC_REGS
-          const f32x4 a8 = {ac[4 * g], ac[4 * g + 1], ac[4 * g + 2], ac[4 * g + 3]};
-#else
           const f32x4 a8 = ws.value(acn[g & (PFT - 1)]);
-#endif
 #pragma unroll
           for (int k = 0; k < 4; ++k) abx[k] = (has_col || GFEAT) ? fmaf(gs, gnx[k], a8[k]) : gs * gnx[k];  // abar_8
         } else {
@@ -1092,42 +914,26 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
           ub[k] = fmaf(abx[k], c, -cb * s);                            // phibar_l = ubar_l / gamma_l
           gb[4 * g + k] = vv[k];
           act[4 * g + k] = ub[k];
-#if OI_BWD_NW == 8
           // (pure arithmetic is not ordered against sched_barrier: without this pin LLVM sinks the whole epilogue below
           // the 16 groups' loads and spills the point vectors to make room for 32 in-flight fragments)
           asm volatile("" : "+v"(gb[4 * g + k]), "+v"(act[4 * g + k]));
-#endif
         }
-#if !OI_BWD_STORES_LAST
-        if constexpr (!L0 && !(OI_BWD_ABL & 1)) {
-          ws.template store<OI_BWD_ST_WGRAD>(S_V + l - 1, g, o.l16, vv);
-          ws.template store<OI_BWD_ST_WGRAD>(S_U + l - 1, g, o.l16, ub);
-        }
-#endif
         // this group's fragments are consumed: request the same group of the NEXT layer into the same registers -- the loads
         // travel under the rest of the epilogue and both products, and there is no separate issue phase
-        if constexpr (!(OI_BWD_ABL & 2)) {
-          // ring slot g & (PF - 1) next holds group g + PF of this layer, or group g + PF - 16 of the layer below
-          if constexpr (TOP) {
-#if !OI_BWD_AC_REGS
-            if (g + PFT < 16) acn[g & (PFT - 1)] = ws.load(S_AC, g + PFT, o.l16);
-#endif
-          } else if (!L0 && g + PF < 16) {
-            phn[g & (PF - 1)] = ws.load_phase(S_PHI + l, g + PF, o.l16);
-            vbn[g & (PF - 1)] = load_vb(S_VB + l, g + PF);
-          } else if constexpr (!L0) {
-            // (layer 1 requests CARRY groups of the un-parked layer 0 as well: nobody reads them, and a run-time test of `l`
-            // here splits the unrolled epilogue into blocks the register allocator handles badly -- 220 spilled registers)
-            if (g + PF - 16 < CARRY) {
-              phn[g & (PF - 1)] = ws.load_phase(S_PHI + l - 1, g + PF - 16, o.l16);
-              vbn[g & (PF - 1)] = load_vb(S_VB + l - 1, g + PF - 16);
-              if (g + PF - 16 == 0) load_vb_scale(S_VB + l - 1);
-            }
+        // ring slot g & (PF - 1) next holds group g + PF of this layer, or group g + PF - 16 of the layer below
+        if constexpr (TOP) {
+          if (g + PFT < 16) acn[g & (PFT - 1)] = ws.load(S_AC, g + PFT, o.l16);
+        } else if (!L0 && g + PF < 16) {
+          phn[g & (PF - 1)] = ws.load_phase(S_PHI + l, g + PF, o.l16);
+          vbn[g & (PF - 1)] = load_vb(S_VB + l, g + PF);
+        } else if constexpr (!L0) {
+          // (layer 1 requests CARRY groups of the un-parked layer 0 as well: nobody reads them, and a run-time test of `l`
+          // here splits the unrolled epilogue into blocks the register allocator handles badly -- 220 spilled registers)
+          if (g + PF - 16 < CARRY) {
+            phn[g & (PF - 1)] = ws.load_phase(S_PHI + l - 1, g + PF - 16, o.l16);
+            vbn[g & (PF - 1)] = load_vb(S_VB + l - 1, g + PF - 16);
+            if (g + PF - 16 == 0) load_vb_scale(S_VB + l - 1);
           }
-        }
-        if constexpr (!L0 && (OI_BWD_ABL & 8)) {  // timing ablation: the loads are ISSUED but nothing ever waits for them
-          asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen nt\n\tbuffer_load_dwordx4 %0, %1, %2, 0 offen offset:1024 nt"
-                       : "=&v"(abl_sink) : "v"(o.l16), "s"(ws.rs));
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1147,11 +953,10 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     }
     if (l >= 1) store_flm(fr, (l - 1) & 1);  // FiLM slot of layer l + 1: free since this layer's barrier
     [[maybe_unused]] float mxq_v = 0.f, mxq_u = 0.f;  // lane maxima of the parked vectors (XQ: taken at the stores, reused below)
-#if OI_BWD_STORES_LAST
     // v_l / ubar_l leave AFTER the next layer's phi / vbar have been requested: the vector memory pipe is one in-order
     // queue per wave, and a load issued behind two 1 KiB stores waited for their data to drain first (phase profile: the
     // reloads cost 100k of 470k ticks per tile, 67k of them gone when the stores are removed)
-    if constexpr (!L0 && !(OI_BWD_ABL & 1)) {
+    if constexpr (!L0) {
       if constexpr (XQ) {
         auto store_q = [&](int slot, const float (&v)[64], float& mx) {
           mx = 0.f;
@@ -1163,34 +968,33 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
             const u32x3 q = pack_q24(f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]}, sq);
-            __builtin_amdgcn_raw_buffer_store_b96(q, ws.rs, l12 + (slot * 16384 + g * 768), 0, OI_BWD_ST_WGRAD);
+            __builtin_amdgcn_raw_buffer_store_b96(q, ws.rs, l12 + (slot * 16384 + g * 768), 0, oi::BWD_NT_ST);
           }
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, inv_sq), ws.rs,
-                                                4 * lane + (slot * 16384 + XQ_SCALE_OFF), 0, OI_BWD_ST_WGRAD);
+                                                4 * lane + (slot * 16384 + XQ_SCALE_OFF), 0, oi::BWD_NT_ST);
         };
         store_q(S_V + l - 1, gb, mxq_v);
         store_q(S_U + l - 1, act, mxq_u);
       } else {
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
-        ws.template store<OI_BWD_ST_WGRAD>(S_V + l - 1, g, o.l16, f32x4{gb[4 * g], gb[4 * g + 1], gb[4 * g + 2], gb[4 * g + 3]});
-        ws.template store<OI_BWD_ST_WGRAD>(S_U + l - 1, g, o.l16, f32x4{act[4 * g], act[4 * g + 1], act[4 * g + 2], act[4 * g + 3]});
+        ws.template store<oi::BWD_NT_ST>(S_V + l - 1, g, o.l16, f32x4{gb[4 * g], gb[4 * g + 1], gb[4 * g + 2], gb[4 * g + 3]});
+        ws.template store<oi::BWD_NT_ST>(S_U + l - 1, g, o.l16, f32x4{act[4 * g], act[4 * g + 1], act[4 * g + 2], act[4 * g + 3]});
       }
       }
     }
-#endif
     BW_T(8);
     if constexpr (!L0) {
       // the point vectors hold v_l / gamma_l and phibar_l (what was parked); the products want v_l and ubar_l = gamma_l phibar_l.
       // The launch-wide maxima the weight-gradient GEMM scales its operands with are those of the PARKED vectors.
       auto times_gamma = [&](float (&v)[64], int om_slot, [[maybe_unused]] float mx_known) {
-        float mx = (XQ && !(OI_BWD_ABL & 1)) ? mx_known : 0.f;
+        float mx = XQ ? mx_known : 0.f;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
           const f32x4 gm = lds_f4(lds, L_FILM + grp_f0(g) * 4, ol.h16);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            if constexpr (SC && !(XQ && !(OI_BWD_ABL & 1))) mx = fmaxf(mx, fabsf(v[4 * g + k]));
+            if constexpr (SC && !XQ) mx = fmaxf(mx, fabsf(v[4 * g + k]));
             v[4 * g + k] *= gm[k];
             asm volatile("" : "+v"(v[4 * g + k]));  // (pins the group: see the epilogue above)
           }
@@ -1215,7 +1019,7 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
 #pragma unroll
         for (int r = 0; r < 16; ++r) act[16 * t + r] = SC ? acc[t][r] * f2 : acc[t][r];
     }
-    if constexpr (TOP && !(OI_BWD_ABL & 2)) {  // (the top layer's products run at the register limit: its successor's first
+    if constexpr (TOP) {  // (the top layer's products run at the register limit: its successor's first
 #pragma unroll                                 // groups are requested after them, not under them)
       for (int q = 0; q < CARRY; ++q) {
         phn[q] = ws.load_phase(S_PHI + l - 1, q, o.l16);
@@ -1224,7 +1028,7 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
       load_vb_scale(S_VB + l - 1);
     }
     BW_T(10);
-    if (L0 && last) {   // (a persistent workgroup: after its last tile)
+    if (L0) {
       __syncthreads();
       // the rows hold sums of phibar_0 / (v_0 / gamma_0) terms, R1 = sum phibar_0, R_{3+j} = sum (phibar_0 x_j + v_0/gamma_0 G_j):
       //   d b_0 = gamma_0 R1,  d W0[:, j] = gamma_0 R_{3+j},  d beta_0 = R1,  d gamma_0 = sum_j W0[f][j] R_{3+j} + b_0[f] R1
@@ -1241,10 +1045,8 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         atomicAdd(d_gamma + (size_t)e * 9 * C + t_,
                   fmaf(w[0], racc[3 * C + t_], fmaf(w[1], racc[4 * C + t_], fmaf(w[2], racc[5 * C + t_], hdr[H_BIAS + t_] * r1))));
       }
-      if constexpr (OI_BWD_LATE_FLUSH) {
-        racc_flush_row(lds, RR_WSIG, d_small + DS_WSIG, 1, tid);
-        if (has_col) flush_colour(gamma + ((size_t)e * 9 + 8) * C);
-      }
+      racc_flush_row(lds, RR_WSIG, d_small + DS_WSIG, 1, tid);
+      if (has_col) flush_colour(gamma + ((size_t)e * 9 + 8) * C);
     }
     BW_T(11);
   };
@@ -1272,7 +1074,6 @@ mlp_bwd_sweep_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     }
   }
 #endif
-  }  // tile
 }
 
 // Layer 0 is not parked by the sweep (see S_PHI): the weight-gradient kernels form phi_0 / (gamma vbar)_0 of matrix m = 0 from
@@ -1445,15 +1246,7 @@ mlp_wgrad_kernel(const char* __restrict__ scratch, const char* __restrict__ pack
 
 // ---- F16X3 variant of the weight-gradient GEMM (3 fp16 MFMAs per product instead of 8 fp32-MFMA k-steps per 16
 // points).  The operands are data with no a-priori range: they are scaled (exactly, by a power of two) with the launch-wide
-// maximum the sweep published, before the split.  The fp32 slot copies sit in LDS with a 4-float skew per 32-point block: the 8 consecutive
-// points of one feature that a lane needs for its MFMA operand are then conflict-free dword reads.  The B fragments
-// (Y, all 128 columns) are the same for the four waves: each wave converts one column tile and shares it through LDS.
-__device__ __forceinline__ int slot_index4(int f, int p) {
-  const int t = f >> 5, rr = (f >> 3) & 3, hh = (f >> 2) & 1, k = f & 3;
-  const int blk = (4 * t + rr) * 2 + hh;
-  return (blk * 32 + p) * 4 + k + 4 * blk;
-}
-constexpr int WG16_SLOT_FLOATS = 4096 + 4 * 128;
+// maximum the sweep published, before the split.
 
 __device__ __forceinline__ void pow2_scale_of(float m, float& sc, float& inv) {
   int eb = (__builtin_bit_cast(int, m) >> 23) & 0xff;
@@ -1462,40 +1255,10 @@ __device__ __forceinline__ void pow2_scale_of(float m, float& sc, float& inv) {
   inv = __builtin_bit_cast(float, (eb - 13) << 23);
 }
 
-// 8 consecutive points of feature f (points p0 .. p0+7) from the skewed fp32 LDS copy -> scaled fp16 hi / lo limbs
-__device__ __forceinline__ float frag16(const float* sl, int f, int p0, f16x8& hi, f16x8& lo) {
-  float v[8];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) v[q] = sl[slot_index4(f, p0 + q)];
-  split8_pairs(v, hi, lo);
-  return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));  // used for the bias gradient (sum over points)
-}
-
-// the same 8 points as ONE bf16 fragment (bf16 operand mode: a single MFMA per product, no scale -- bf16 has fp32's range)
-__device__ __forceinline__ float frag_bf16(const float* sl, int f, int p0, f16x8& out) {
-  float v[8];
-  bf16x8 b;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    v[q] = sl[slot_index4(f, p0 + q)];
-    b[q] = (__bf16)v[q];
-  }
-  out = __builtin_bit_cast(f16x8, b);
-  return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-}
-
-// the scratch operands are read exactly once by this kernel: non-temporal loads (streaming-read ceiling of the box
-// 5.8 TB/s ordinary, 6.5-7.0 non-temporal: tools/dbg/hbm_read.hip)
-#ifndef OI_WGRAD_NT
-#define OI_WGRAD_NT 1
-#endif
-#ifndef OI_WG_TARGET
-#define OI_WG_TARGET 2048  // workgroups of the weight-gradient GEMM (8 matrices x chunks)
-#endif
-#ifndef OI_WG_ABL
-#define OI_WG_ABL 0
-#endif
-__device__ __forceinline__ f32x4 ld_once(const f32x4* p) { return OI_WGRAD_NT ? __builtin_nontemporal_load(p) : *p; }
+// the scratch operands are read exactly once by this kernel: non-temporal loads, aux operand WG_NT (streaming-read ceiling
+// of the box 5.8 TB/s ordinary, 6.5-7.0 non-temporal: tools/dbg/hbm_read.hip)
+constexpr int WG_NT = 2;
+constexpr int WG_TARGET = 2048;  // workgroups of the weight-gradient GEMM (8 matrices x chunks)
 
 // -DOI_WG_PROF: per-phase shader-clock accounting of the weight-gradient GEMM (read with oi_prof_bwd_read, slots 0..7)
 #ifdef OI_WG_PROF
@@ -1511,25 +1274,16 @@ __device__ unsigned long long oi_prof_bwd[24];
 #else
 #define WG_T(i)
 #endif
-// OI_WG_TR (round 6, default on): the operands cross LDS as fp16 (bf16) limb planes [32 points][128 features] and come back as MFMA
-// fragments through gfx950's transposing read.  The slots hold "point on the lane, four features per granule"; an MFMA operand is
-// "feature on the lane, eight points per register group" -- a 32 x 128 transposition per operand and wave tile.  Until round 5:
-// fp32 copies in LDS, eight ds_read_b32 per fragment, the fp16 split AFTER the read, the column fragments converted by one wave
-// each and shared through a second LDS buffer -- 120 LDS instructions and five barriers per wave tile; the phase profile
-// (profiles/r6_wgrad_phase_profile.txt) had the matrix cores busy for 13 % of a tile.  Now the split happens on the granule the
-// thread holds anyway, the 8-byte piece (point p, features 4 c .. 4 c + 3) is written once per limb, and ds_read_b64_tr_b16
+// The operands cross LDS as fp16 (bf16) limb planes [32 points][128 features] and come back as MFMA fragments through
+// gfx950's transposing read.  The slots hold "point on the lane, four features per granule"; an MFMA operand is "feature on the
+// lane, eight points per register group" -- a 32 x 128 transposition per operand and wave tile.  The split happens on the
+// granule the thread holds anyway, the 8-byte piece (point p, features 4 c .. 4 c + 3) is written once per limb, and ds_read_b64_tr_b16
 // (each lane of a 16-lane group supplies the address of ONE piece; the group receives the 4 x 16 block transposed: lane t gets
 // column t, rows 0..3 -- tools/dbg/tr_probe2.hip) delivers four points of the lane's feature: two reads = one operand limb.  Both
 // pairs of a tile are staged at once: 32 ds_write_b64 + 80 transposing reads and TWO barriers per wave tile.
 //   piece (p, c) of a plane lives at byte 8 (32 p + (c ^ g(p))),  g(p) = 8 (p & 1) ^ 17 ((p >> 1) & 1) ^ 2 ((p >> 3) & 1):
 //   the 32 pieces a half wave reads (4 points x 8 feature quads) fall on 32 distinct 8-byte bank pairs (conflict-free reads), the
 //   16 a store group writes on 8 (2-way: 8 LDS cycles against the 6 the store's register transfer takes anyway).
-#ifndef OI_WG_TR
-#define OI_WG_TR 1
-#endif
-#ifndef OI_WG_TR_SPREAD
-#define OI_WG_TR_SPREAD 1
-#endif
 constexpr int TR_PLANE = 8192;   // bytes of one limb plane: 32 points x 32 pieces of 8 bytes
 constexpr int TR_PLANES = 8;     // X0h X0l Y0h Y0l X1h X1l Y1h Y1l  (bf16 operands: the four hi planes)
 typedef __fp16 trh4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
@@ -1541,7 +1295,6 @@ __device__ __forceinline__ f16x8 tr_frag(const char* planes, int addr, int imm) 
   const u32x2 ua = __builtin_bit_cast(u32x2, a), ub = __builtin_bit_cast(u32x2, b);
   return __builtin_bit_cast(f16x8, u32x4{ua[0], ua[1], ub[0], ub[1]});
 }
-typedef f16x8 (*SbPtr)[4][2][64];  // [hi|lo][column tile][k-step][lane]
 // COL: the colour-head matrix (m = 7, one pair: X = uvbar, Y = a_8 = sin phi_7); otherwise a layer matrix (two pairs).  A
 // compile-time split: with `m` tested at run time hipcc turned the per-element selects of the hot loop into branches.
 // MODE 0: a layer matrix m = 1..6;  1 (COL): the colour head;  2 (FIRST): m = 0, whose Y operands come from layer 0 -- not
@@ -1550,7 +1303,7 @@ typedef f16x8 (*SbPtr)[4][2][64];  // [hi|lo][column tile][k-step][lane]
 // product, no operand scales.  (Until round 5 that mode fell through to the generic fp32-MFMA GEMM: 3.2 ms per backward against
 // 1.45 ms for this body, the largest kernel of a bf16-mode training iteration.)
 template <int MODE, bool FAST, bool BF = false>
-__device__ __forceinline__ void wgrad_f16_body(float* sx, float* sy, SbPtr sb, char* planes, const float* l0tab, const int m, const char* __restrict__ scratch,
+__device__ __forceinline__ void wgrad_f16_body(char* planes, const float* l0tab, const int m, const char* __restrict__ scratch,
                                                const float* __restrict__ op_max, const char* __restrict__ packed,
                                                size_t plain_offset, const float* __restrict__ gamma,
                                                float* __restrict__ d_wmat, float* __restrict__ d_gamma,
@@ -1609,15 +1362,15 @@ __device__ __forceinline__ void wgrad_f16_body(float* sx, float* sy, SbPtr sb, c
   //   both Y operands of a layer matrix come from the SAME parked phase (reduced, in revolutions): one read, one sin / cos
   //   pair 0: Y = gbar_l = (gamma vbar)_{l-1} cos(phi_{l-1})      pair 1: Y = a_l = sin(phi_{l-1})
   // what the sweep parked (see WaveScratchT): 24-bit values -> 60 staging registers, 16-bit (bf16 mode) -> 40
-  constexpr int PK = BF ? (OI_BWD_PACK16 ? 2 : 0) : ((OI_BWD_PACK24 && !FAST) ? 1 : 0);
-  constexpr bool PHQ = OI_BWD_PHQ24 && PK == 0 && !BF && !FAST;   // (the sweep's condition)
+  constexpr int PK = BF ? 2 : 0;
+  constexpr bool PHQ = !BF && !FAST;   // (the sweep's condition)
   using WS = WaveScratchT<PK, PHQ>;
   using Frag = typename WS::Frag;
   using PFrag = typename WS::PFrag;
-  // X slots of the layer matrices (S_V, S_U) as 24-bit fixed point + a per-lane scale (see OI_BWD_XQ24; the sweep's condition)
-  constexpr bool XQ = OI_BWD_XQ24 && PK == 0 && !BF && !COL && OI_BWD_STORES_LAST;
+  // X slots of the layer matrices (S_V, S_U) as 24-bit fixed point + a per-lane scale (see pack_q24; the sweep's condition)
+  constexpr bool XQ = !BF && !COL;
   using XFrag = std::conditional_t<XQ, u32x3, Frag>;
-  constexpr bool VBQ = OI_BWD_VBQ24 && PK == 0 && !BF;   // (the sweep's condition)
+  constexpr bool VBQ = !BF;   // (the sweep's condition)
   using VFrag = std::conditional_t<VBQ, u32x3, Frag>;
   struct Stage {  // the five slots of one wave tile as they arrive: 80 registers (48 for the colour head); 60 (36) packed
     XFrag xall[2][4];
@@ -1630,34 +1383,33 @@ __device__ __forceinline__ void wgrad_f16_body(float* sx, float* sy, SbPtr sb, c
   Stage stA, stB;
   // through a buffer descriptor over the wave tile (512 KiB): the tile base and the slot offsets travel in SGPRs, the lane
   // offset in ONE VGPR -- with flat pointers hipcc kept 20 address pairs live across the loop and spilled
-  const int t16 = tid * (PK == 1 ? 12 : (PK == 2 ? 8 : 16));
-  // granules [it0, it1) of the tile (the per-lane scales and layer 0's point ride with granule 0): the transposing-read build
-  // issues a tile's requests in four parts BETWEEN its MFMA groups -- issued in one go after the stores they stalled the wave for
+  const int t16 = tid * (PK == 2 ? 8 : 16);
+  // granules [it0, it1) of the tile (the per-lane scales and layer 0's point ride with granule 0): a tile's requests are
+  // issued in four parts BETWEEN its MFMA groups -- issued in one go after the stores they stalled the wave for
   // 14 % of a tile (the vector-memory queue is in order and 6 bits deep), with the matrix cores idle meanwhile
   auto request_part = [&](long long wt, Stage& st, int it0, int it1) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<char*>(scratch) + wt * (long long)(NSLOT_BWD * 16384), 0, NSLOT_BWD * 16384, 0x00020000);
     auto ld = [&](int slot, int it) -> Frag {   // granule q = it 256 + tid of the slot: group q / 64, lane q % 64
-      if constexpr (PK == 1) return __builtin_amdgcn_raw_buffer_load_b96(rs, t16, slot * 16384 + it * 3072, OI_WGRAD_NT ? 2 : 0);
-      else if constexpr (PK == 2) return __builtin_amdgcn_raw_buffer_load_b64(rs, t16, slot * 16384 + it * 2048, OI_WGRAD_NT ? 2 : 0);
+      if constexpr (PK == 2) return __builtin_amdgcn_raw_buffer_load_b64(rs, t16, slot * 16384 + it * 2048, WG_NT);
       else return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, t16, slot * 16384 + it * 4096,
-                                                                                  OI_WGRAD_NT ? 2 : 0));
+                                                                                  WG_NT));
     };
     auto ldx = [&](int slot, int it) -> XFrag {
-      if constexpr (XQ) return __builtin_amdgcn_raw_buffer_load_b96(rs, tid * 12, slot * 16384 + it * 3072, OI_WGRAD_NT ? 2 : 0);
+      if constexpr (XQ) return __builtin_amdgcn_raw_buffer_load_b96(rs, tid * 12, slot * 16384 + it * 3072, WG_NT);
       else return ld(slot, it);
     };
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       if (it < it0 || it >= it1) continue;
       if constexpr (!FIRST) {
-        if constexpr (PHQ) st.ph4[it] = __builtin_amdgcn_raw_buffer_load_b96(rs, tid * 12, (S_PHI + m) * 16384 + it * 3072, OI_WGRAD_NT ? 2 : 0);
+        if constexpr (PHQ) st.ph4[it] = __builtin_amdgcn_raw_buffer_load_b96(rs, tid * 12, (S_PHI + m) * 16384 + it * 3072, WG_NT);
         else st.ph4[it] = ld(S_PHI + m, it);
       }
       st.xall[0][it] = ldx(COL ? S_UV : S_V + m, it);
       if constexpr (!COL) {
         if constexpr (!FIRST) {   // gamma_{l-1} vbar_{l-1}
-          if constexpr (VBQ) st.vb4[it] = __builtin_amdgcn_raw_buffer_load_b96(rs, tid * 12, (S_VB + m) * 16384 + it * 3072, OI_WGRAD_NT ? 2 : 0);
+          if constexpr (VBQ) st.vb4[it] = __builtin_amdgcn_raw_buffer_load_b96(rs, tid * 12, (S_VB + m) * 16384 + it * 3072, WG_NT);
           else st.vb4[it] = ld(S_VB + m, it);
         }
         st.xall[1][it] = ldx(S_U + m, it);
@@ -1666,61 +1418,21 @@ __device__ __forceinline__ void wgrad_f16_body(float* sx, float* sy, SbPtr sb, c
     if (it0 != 0) return;
     if constexpr (VBQ && !FIRST && !COL)
       st.vbinv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, 4 * (tid & 63), (S_VB + m) * 16384 + XQ_SCALE_OFF,
-                                                                                OI_WGRAD_NT ? 2 : 0));
+                                                                                WG_NT));
     if constexpr (XQ) {
       st.xinv[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, 4 * (tid & 63), (S_V + m) * 16384 + XQ_SCALE_OFF,
-                                                                                  OI_WGRAD_NT ? 2 : 0));
+                                                                                  WG_NT));
       st.xinv[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, 4 * (tid & 63), (S_U + m) * 16384 + XQ_SCALE_OFF,
-                                                                                  OI_WGRAD_NT ? 2 : 0));
+                                                                                  WG_NT));
     }
     if constexpr (FIRST) {  // this thread's point (lane j = point j): (x y z .), (Gx Gy Gz .)
 #pragma unroll
       for (int q = 0; q < 2; ++q)
         st.pt[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, 32 * (tid & 31), S_PHI * 16384 + 16 * q,
-                                                                                  OI_WGRAD_NT ? 2 : 0));
+                                                                                  WG_NT));
     }
   };
   auto request = [&](long long wt, Stage& st) { request_part(wt, st, 0, 4); };
-  // fragments of one pair out of the fp32 LDS copies: this wave's column tile of Y -> shared fp16 fragments sb[pr], its
-  // own row strip of X -> registers
-  auto extract = [&](int pr, f16x8 (&ah)[2], f16x8 (&al)[2], bool last_pair) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      f16x8 bh, bl;
-      if constexpr (BF) {
-        frag_bf16(sy, fo, 16 * ks + 8 * h, bh);
-        sb[0][wave][ks][lane] = bh;
-      } else {
-        frag16(sy, fo, 16 * ks + 8 * h, bh, bl);
-        sb[0][wave][ks][lane] = bh;
-        sb[1][wave][ks][lane] = bl;
-      }
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      float xs;
-      if constexpr (BF) xs = frag_bf16(sx, fo, 16 * ks + 8 * h, ah[ks]);
-      else xs = frag16(sx, fo, 16 * ks + 8 * h, ah[ks], al[ks]);
-      if (last_pair) sub += xs;  // the last pair's X is ubar_l / uvbar
-    }
-  };
-  auto products = [&](const f16x8 (&ah)[2], const f16x8 (&al)[2]) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if constexpr (BF) {
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[ks]),
-                                                           __builtin_bit_cast(bf16x8, sb[0][t][ks][lane]), acc[t], 0, 0, 0);
-        } else {
-          const f16x8 bh = sb[0][t][ks][lane], bl = sb[1][t][ks][lane];
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ks], bh, acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks], bl, acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks], bh, acc[t], 0, 0, 0);
-        }
-      }
-    }
-  };
 #ifdef OI_WG_PROF
   unsigned long long wacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long wprev = __builtin_readcyclecounter();
@@ -1736,89 +1448,9 @@ __device__ __forceinline__ void wgrad_f16_body(float* sx, float* sy, SbPtr sb, c
       return WS::value(st.xall[pr][it]) * scx[pr];
     }
   };
-  // one wave tile out of staging set `st`; the set is dead once pair 1 is staged, and the tile TWO ahead is requested into it
-  auto tile = [&](long long wt, Stage& st) {
-#if OI_WG_ABL & 1  // timing ablation: the loads alone (streaming rate of this access pattern)
-    {
-      float z = 0.f;
-#pragma unroll
-      for (int it = 0; it < 4; ++it)
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          z += (FIRST ? st.pt[it & 1][k] : WS::phase_of(st.ph4[it])[k]) + xval(st, 0, it)[k] +
-               (COL ? 0.f : (FIRST ? 0.f : (float)st.vb4[it][k & 1]) + xval(st, 1, it)[k]);
-      sub += z;
-      __builtin_amdgcn_sched_barrier(0);
-      if (wt + 2 < t_end) request(wt + 2, st);
-      return;
-    }
-#endif
-    // pair 0 needs only the cosine (layer matrices) and pair 1 only the sine: the phase stays in its registers until pair 1
-    // is staged, nothing else of the tile does
-    f32x4 y0[4], ph4[4];
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      f32x4 vb4;
-      if constexpr (FIRST) {
-        l0_phase_vb<FAST>(l0tab, st.pt[0], st.pt[1], grp_f0(4 * it + wave) + 4 * h, ph4[it], vb4);
-      } else {
-        ph4[it] = WS::phase_of(st.ph4[it]);
-        if constexpr (!COL) {
-          if constexpr (VBQ) vb4 = unpack_q24(st.vb4[it]); else vb4 = WS::value(st.vb4[it]);
-        }
-      }
-      // (VBQ: vb4 holds y = vbar s + 1.5; the de-scaling joins the multiply by the launch-wide scale)
-      const float kv = (VBQ && !FIRST && !COL) ? st.vbinv * scy[0] : scy[0], cv = (VBQ && !FIRST && !COL) ? -1.5f * kv : 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)  // colour head (one pair): Y = a_8 = sin
-        y0[it][k] = COL ? __builtin_amdgcn_sinf(ph4[it][k]) * scy[0] : fmaf(vb4[k], kv, cv) * __builtin_amdgcn_cosf(ph4[it][k]);
-    }
-    WG_T(0);
-    __syncthreads();  // (1) the previous tile's readers of sx / sy / sb are done
-    WG_T(1);
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int q = it * 256 + tid;
-      const int dq = q + (q >> 5);  // + 4 floats per 32-point block
-      reinterpret_cast<f32x4*>(sx)[dq] = xval(st, 0, it);
-      reinterpret_cast<f32x4*>(sy)[dq] = y0[it];
-    }
-    WG_T(2);
-    __syncthreads();  // (2)
-    f16x8 ah[2], al[2];
-    extract(0, ah, al, npair == 1);
-    WG_T(3);
-    __syncthreads();  // (3) sx / sy are free again, sb is complete
-    if constexpr (npair == 2) {
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const int q = it * 256 + tid;
-        const int dq = q + (q >> 5);
-        reinterpret_cast<f32x4*>(sx)[dq] = xval(st, 1, it);
-        f32x4 y1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) y1[k] = __builtin_amdgcn_sinf(ph4[it][k]) * scy[1];
-        reinterpret_cast<f32x4*>(sy)[dq] = y1;
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    if (wt + 2 < t_end) request(wt + 2, st);  // every register of the set is dead: two tiles are in flight from here on
-    __builtin_amdgcn_sched_barrier(0);
-    WG_T(4);
-    products(ah, al);
-    WG_T(5);
-    if constexpr (npair == 2) {
-      __syncthreads();  // (4)
-      extract(1, ah, al, true);
-      WG_T(6);
-      __syncthreads();  // (5)
-      products(ah, al);
-      WG_T(7);
-    }
-  };
-  // ---- OI_WG_TR: fp16 limb planes + transposing reads (see the flag) ----
+  // fp16 limb planes + transposing reads: this thread's write and read addresses
   int wr[4], rdy[4], rdx = 0;
-  if constexpr (OI_WG_TR) {
+  {
     const int p = lane & 31, gp = tr_g(p);
 #pragma unroll
     for (int it = 0; it < 4; ++it) wr[it] = 8 * (32 * p + ((8 * it + 2 * wave + h) ^ gp));   // granule `it`: features 32 it + 8 wave + 4 h ..
@@ -1872,20 +1504,14 @@ __device__ __forceinline__ void wgrad_f16_body(float* sx, float* sy, SbPtr sb, c
     WG_T(1);
     __syncthreads();  // (B) the planes are complete
     WG_T(2);
-    // every register of the set is dead: the tile two ahead is requested from here on, a part per MFMA group (OI_WG_TR_SPREAD=0:
-    // all at once, in front of the groups)
+    // every register of the set is dead: the tile two ahead is requested from here on, a part per MFMA group
     const bool more = wt + 2 < t_end;
-    if (!OI_WG_TR_SPREAD) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (more) request(wt + 2, st);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     WG_T(3);
 #pragma unroll
     for (int pr = 0; pr < npair; ++pr) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        if (OI_WG_TR_SPREAD) {
+        {
           const int part = pr * 2 + ks, nparts = 2 * npair;   // 4 granules over the 2 or 4 groups
           __builtin_amdgcn_sched_barrier(0);
           if (more) request_part(wt + 2, st, part * 4 / nparts, (part + 1) * 4 / nparts);
@@ -1929,13 +1555,8 @@ __device__ __forceinline__ void wgrad_f16_body(float* sx, float* sy, SbPtr sb, c
   if (t_begin < t_end) request(t_begin, stA);
   if (t_begin + 1 < t_end) request(t_begin + 1, stB);
   for (long long wt = t_begin; wt < t_end; wt += 2) {
-    if constexpr (OI_WG_TR) {
-      tile_tr(wt, stA);
-      if (wt + 1 < t_end) tile_tr(wt + 1, stB);
-    } else {
-      tile(wt, stA);
-      if (wt + 1 < t_end) tile(wt + 1, stB);
-    }
+    tile_tr(wt, stA);
+    if (wt + 1 < t_end) tile_tr(wt + 1, stB);
   }
 #ifdef OI_WG_PROF
   if (lane == 0 && !COL) {
@@ -1959,31 +1580,21 @@ mlp_wgrad_f16_kernel(const char* __restrict__ scratch, const float* __restrict__
                      size_t plain_offset, const float* __restrict__ gamma, const float* __restrict__ beta,
                      float* __restrict__ d_wmat, float* __restrict__ d_gamma, float* __restrict__ d_beta,
                      float* __restrict__ d_small, long long wt_per_elem, int tiles_per_chunk, int has_col) {
-#if OI_WG_TR
   __shared__ __attribute__((aligned(16))) char planes[TR_PLANES * TR_PLANE];   // 64 KiB: two workgroups per CU
   __shared__ __attribute__((aligned(16))) float l0tab[L0TAB_FLOATS];
-  float *sx = nullptr, *sy = nullptr;
-  SbPtr sb = nullptr;
-#else
-  __shared__ __attribute__((aligned(16))) float sx[WG16_SLOT_FLOATS], sy[WG16_SLOT_FLOATS];
-  __shared__ __attribute__((aligned(16))) float l0tab[L0TAB_FLOATS];
-  // ONE copy for both pairs (barrier 4 separates pair 0's readers from pair 1's writers)
-  __shared__ __attribute__((aligned(16))) f16x8 sb[2][4][2][64];
-  char* planes = nullptr;
-#endif
   const int m = blockIdx.y;
   // a compile-time split per kind of matrix: with `m` tested at run time hipcc turned per-element selects into branches
   if (m == 7) {
     if (has_col)
-      wgrad_f16_body<1, FAST, BF>(sx, sy, sb, planes, l0tab, 7, scratch, op_max, packed, plain_offset, gamma, d_wmat, d_gamma, d_beta,
+      wgrad_f16_body<1, FAST, BF>(planes, l0tab, 7, scratch, op_max, packed, plain_offset, gamma, d_wmat, d_gamma, d_beta,
                               d_small, wt_per_elem, tiles_per_chunk);
   } else if (m == 0) {
     l0tab_fill(l0tab, reinterpret_cast<const float*>(packed), gamma, beta, blockIdx.z, threadIdx.x);
     __syncthreads();
-    wgrad_f16_body<2, FAST, BF>(sx, sy, sb, planes, l0tab, 0, scratch, op_max, packed, plain_offset, gamma, d_wmat, d_gamma, d_beta,
+    wgrad_f16_body<2, FAST, BF>(planes, l0tab, 0, scratch, op_max, packed, plain_offset, gamma, d_wmat, d_gamma, d_beta,
                             d_small, wt_per_elem, tiles_per_chunk);
   } else {
-    wgrad_f16_body<0, FAST, BF>(sx, sy, sb, planes, l0tab, m, scratch, op_max, packed, plain_offset, gamma, d_wmat, d_gamma, d_beta,
+    wgrad_f16_body<0, FAST, BF>(planes, l0tab, m, scratch, op_max, packed, plain_offset, gamma, d_wmat, d_gamma, d_beta,
                             d_small, wt_per_elem, tiles_per_chunk);
   }
 }
@@ -2014,17 +1625,7 @@ int launch_bwd(const float* pts, const void* packed, const float* gamma, const f
   for (long long t0 = 0; t0 < tiles_all; t0 += tiles_fit) {
     const long long nt = std::min(tiles_fit, tiles_all - t0);
     const long long off = t0 * BW_TILE, cn = std::min<long long>(nt * BW_TILE, n - off);
-#if OI_BWD_PERSIST
-    static const int cus = [] {
-      int dev = 0, n_ = 256;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&n_, hipDeviceAttributeMultiprocessorCount, dev);
-      return n_ > 0 ? n_ : 256;
-    }();
-    dim3 grid((unsigned)std::min<long long>(nt, std::max(1, cus / B)), B), block(256);
-#else
     dim3 grid((unsigned)nt, B), block(256);
-#endif
     if constexpr (PREC == OI_PREC_F16X3) {
       hipError_t e = oi::zero_async(op_max, OM_FLOATS, st);
       if (e != hipSuccess) return oi::fail(OI_ERR_LAUNCH, "oi_sdf_mlp_bwd: zero fill: %s", hipGetErrorString(e));
@@ -2035,13 +1636,13 @@ int launch_bwd(const float* pts, const void* packed, const float* gamma, const f
     if (rc != OI_OK) return rc;
     const long long wt_per_elem = nt * BW_NW, n_wt = (long long)B * wt_per_elem;
     // ~2048 workgroups in total; a chunk never straddles two batch elements (per-element FiLM gradients)
-    const int chunk = (int)std::min<long long>(wt_per_elem, std::max<long long>(1, (n_wt * 8 + OI_WG_TARGET - 1) / OI_WG_TARGET));
+    const int chunk = (int)std::min<long long>(wt_per_elem, std::max<long long>(1, (n_wt * 8 + WG_TARGET - 1) / WG_TARGET));
     dim3 g2(oi::cdiv(wt_per_elem, chunk), 8, B);
     const char* pk = reinterpret_cast<const char*>(packed);
     if constexpr (PREC == OI_PREC_F16X3) {
       hipLaunchKernelGGL(mlp_wgrad_f16_kernel<FAST>, g2, block, 0, st, tiles, op_max, pk, plain_off(PREC), gamma, beta,
                          d_wmat, d_gamma, d_beta, d_small, wt_per_elem, chunk, has_col);
-    } else if constexpr (PREC == OI_PREC_BF16 && OI_WGRAD_BF16) {
+    } else if constexpr (PREC == OI_PREC_BF16) {
       hipLaunchKernelGGL((mlp_wgrad_f16_kernel<FAST, true>), g2, block, 0, st, tiles, op_max, pk, plain_off(PREC), gamma, beta,
                          d_wmat, d_gamma, d_beta, d_small, wt_per_elem, chunk, has_col);
     } else {

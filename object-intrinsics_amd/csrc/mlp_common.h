@@ -60,35 +60,16 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // residual a - float(hi) is exact in fp32, and v_fma_mixlo_f16 / v_fma_mixhi_f16 form it (fp16 operand read straight from
 // the packed dword) and round it to fp16 into the low / high half of the lo dword: 3 instructions per pair, bit-identical
 // to the cvt-back / subtract / cvt_pk form (tools/dbg/run_fwd_ab.sh compares whole forward passes bit for bit) and to
-// round 2's v_fma_mix_f32 x 2 + v_cvt_pk (4 per pair, OI_SPLIT_MIXLO=0).
-#ifndef OI_SPLIT_MIXLO
-#define OI_SPLIT_MIXLO 1
-#endif
+// round 2's v_fma_mix_f32 x 2 + v_cvt_pk (4 per pair).
 __device__ __forceinline__ void split_pair(float a, float b, unsigned& hi, unsigned& lo) {
   const f16x2 hv = {(_Float16)a, (_Float16)b};
   hi = __builtin_bit_cast(unsigned, hv);
-#ifdef OI_F3_ABL_PIECE
-  if (OI_F3_ABL_PIECE & 8) {
-    lo = hi;
-    return;
-  }
-#endif
-#if OI_SPLIT_MIXLO
   // the residual of each value, rounded to fp16 straight into its half of the lo dword (the residual is exact in fp32,
   // so this is the same single rounding v_cvt_pk_f16_f32 applies): 3 instructions per pair
   asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
       "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
       : "=&v"(lo)
       : "v"(hi), "v"(a), "v"(b));
-#else
-  float ra, rb;
-  asm("v_fma_mix_f32 %0, %2, -1.0, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mix_f32 %1, %2, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(ra), "=&v"(rb)
-      : "v"(hi), "v"(a), "v"(b));
-  const f16x2 lv = {(_Float16)ra, (_Float16)rb};
-  lo = __builtin_bit_cast(unsigned, lv);
-#endif
 }
 // eight fp32 values -> the hi and lo fp16 limb fragments (8 x fp16 each) of an MFMA operand: 16 instructions
 __device__ __forceinline__ void split8_pairs(const float* v, f16x8& hi, f16x8& lo) {
@@ -323,24 +304,15 @@ __device__ __forceinline__ void gemm_layer(const char* lds, const LaneOff& o, co
   gemm_layer2<PREC>(lds, y, act, acc);
 }
 
-// sin and cos of one fp32 phase.  Three accurate forms (OI_TRIG_HW), measured A/B on one MI355X (full f16x3 kernel):
-//   2 (default)  whole-period reduction in revolutions + v_sin_f32 / v_cos_f32                      1.03 ms
-//   1            n = round(phi/pi) by magic-number FMA, 2-constant Cody-Waite, then v_sin / v_cos     1.08 ms
-//   0            the same reduction, weighted-minimax polynomials on [-pi/2, pi/2] (1.4e-8 / 7e-9), shared sign by
-//                xor: 19 VALU ops per pair, all FP                                                     1.12 ms
-// All three are 1e-7-class (hardware: 1.3e-7 absolute on [-1/2, 1/2] revolutions, tools/dbg/trans_acc.hip) and give the
-// same parity margins; the transcendental instructions issue beside the FP VALU / MFMA work, the polynomial adds to it.
+// sin and cos of one fp32 phase.  Accurate form: whole-period reduction in revolutions + v_sin_f32 / v_cos_f32 (the fastest
+// of the 1e-7-class forms measured; the transcendental instructions issue beside the FP VALU / MFMA work).
 // Fast form (FAST = true, bf16 throughput mode): v_sin / v_cos on phi/(2 pi) with no reduction (error ~ |phi| * 6e-8).
-#ifndef OI_TRIG_HW
-#define OI_TRIG_HW 2
-#endif
 template <bool FAST>
 __device__ __forceinline__ void sincos_(float x, float& s, float& c) {
   if constexpr (FAST) {
     s = __sinf(x);
     c = __cosf(x);
   } else {
-#if OI_TRIG_HW == 2
     // Whole-period reduction in REVOLUTIONS, then the transcendental unit: n = round(x / 2pi); the fractional part
     // x/(2pi) - n comes out of ONE fma (exact product, single rounding of a value <= 1/2) plus the low word of 1/(2pi),
     // so it is good to ~3e-8 revolutions for the |phi| <= a few hundred radians of this network; v_sin / v_cos are
@@ -352,32 +324,6 @@ __device__ __forceinline__ void sincos_(float x, float& s, float& c) {
     r = fmaf(x, 6.4206383266e-09f, r);  // 1/(2 pi) - float(1/(2 pi)) = 0.15915494309189535 - 0.15915493667125702
     s = __builtin_amdgcn_sinf(r);
     c = __builtin_amdgcn_cosf(r);
-#else
-    constexpr float MAGIC = 12582912.f;  // 1.5 * 2^23: nf = MAGIC + round(x / pi), parity of n in mantissa bit 0
-    const float nf = fmaf(x, 0.318309886183790671538f, MAGIC);
-    const float n = nf - MAGIC;
-    float r = fmaf(n, -3.1415927410125732f, x);
-    r = fmaf(n, 8.742278000372485e-08f, r);  // float(pi) - pi
-#if OI_TRIG_HW == 1
-    // the transcendental unit on the exactly reduced argument (|r| <= pi/2 -> |t| <= 1/4 revolution)
-    const float t = r * 0.15915494309189533577f;
-    const float ps = __builtin_amdgcn_sinf(t);
-    const float pc = __builtin_amdgcn_cosf(t);
-#else
-    const float t = r * r;
-    float ps = fmaf(t, 2.5999420359e-06f, -1.9806565251e-04f);
-    ps = fmaf(t, ps, 8.3330161870e-03f);
-    ps = fmaf(t, ps, -1.6666656733e-01f);
-    ps = fmaf(t * r, ps, r);
-    float pc = fmaf(t, -2.6192776659e-07f, 2.4769255106e-05f);
-    pc = fmaf(t, pc, -1.3888567919e-03f);
-    pc = fmaf(t, pc, 4.1666656733e-02f);
-    pc = fmaf(t * t, pc, fmaf(t, -0.5f, 1.0f));
-#endif
-    const unsigned sign = __builtin_bit_cast(unsigned, nf) << 31;
-    s = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, ps) ^ sign);
-    c = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, pc) ^ sign);
-#endif
   }
 }
 
@@ -386,10 +332,10 @@ __device__ __forceinline__ void sincos_(float x, float& s, float& c) {
 struct WaveScratch {
   __amdgpu_buffer_rsrc_t rs;
   __device__ __forceinline__ void store(int slot, int g, int l16, f32x4 v) const {
-    oi::buffer_store_b128<OI_FWD_NT_ST>(__builtin_bit_cast(u32x4, v), rs, l16, slot * 16384 + g * 1024);
+    oi::buffer_store_b128<oi::FWD_NT_ST>(__builtin_bit_cast(u32x4, v), rs, l16, slot * 16384 + g * 1024);
   }
   __device__ __forceinline__ f32x4 load(int slot, int g, int l16) const {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, l16, slot * 16384 + g * 1024, OI_FWD_NT_LD));
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, l16, slot * 16384 + g * 1024, oi::FWD_NT_LD));
   }
 };
 
@@ -500,7 +446,7 @@ struct FwdScratch {
       for (int k = 0; k < 4; ++k) hv[k] = (_Float16)v[k];
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hv), rs, o.l16 >> 1, slot * 8192 + g * 512, 0);
     } else {
-      oi::buffer_store_b128<OI_FWD_NT_ST>(__builtin_bit_cast(u32x4, v), rs, o.l16, slot * 16384 + g * 1024);
+      oi::buffer_store_b128<oi::FWD_NT_ST>(__builtin_bit_cast(u32x4, v), rs, o.l16, slot * 16384 + g * 1024);
     }
   }
   __device__ __forceinline__ f32x4 load(int slot, int g, const LaneOff& o) const {
@@ -511,35 +457,23 @@ struct FwdScratch {
       for (int k = 0; k < 4; ++k) v[k] = (float)hv[k];
       return v;
     } else {
-      return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o.l16, slot * 16384 + g * 1024, OI_FWD_NT_LD));
+      return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o.l16, slot * 16384 + g * 1024, oi::FWD_NT_LD));
     }
   }
 };
 
-constexpr int V2_WAVES = 8;                   // scratch is sized for 8-wave tiles (an upper bound for 4-wave tiles)
+constexpr int V2_WAVES = 8;                   // wavefronts per workgroup (see "Workgroup shape" below)
 constexpr int V2_TILE = V2_WAVES * WAVE_PTS;  // 256 points
 constexpr int V2_FILM = 0;                    // [9][gamma 128 | beta' 128],  beta' = gamma * bias + beta
 constexpr int V2_TABS = 9 * 1024;             // 9216
 constexpr int V2_WBUF = V2_TABS + H_TABS_END * 4;  // 15488
 // Workgroup shape.  Every mode runs 8 wavefronts (256 points) per workgroup and CU with a double-buffered image
-// ring, except BF16X6 (96 KiB images: one slot).  F16X3 can alternatively be built with 4-wave workgroups and ONE
-// 64 KiB slot (79 KiB LDS, two independent workgroups per CU): measured 1.5 % slower (tools/bench_c5.py) -- on
-// gfx950 FP VALU and MFMA time of co-resident waves add up, so running the two workgroups out of phase buys nothing.
-#ifndef OI_F16X3_FULL_WAVES
-#define OI_F16X3_FULL_WAVES 8
-#endif
-#ifndef OI_F16X3_SDF_WAVES
-#define OI_F16X3_SDF_WAVES 8
-#endif
-__host__ __device__ constexpr int v2_waves(int prec, bool full) {
-  return prec == OI_PREC_F16X3 ? (full ? OI_F16X3_FULL_WAVES : OI_F16X3_SDF_WAVES) : 8;
-}
+// ring, except BF16X6 (96 KiB images: one slot).  (4-wave F16X3 workgroups with ONE 64 KiB slot, two independent
+// workgroups per CU, measured 1.5 % slower: on gfx950 FP VALU and MFMA time of co-resident waves add up.)
 // BF16X6 images are 96 KiB: a single ring slot, refilled behind a barrier while the VALU phase runs
-__host__ __device__ constexpr bool v2_two_slots(int prec, bool full) {
-  return prec != OI_PREC_BF16X6 && !(prec == OI_PREC_F16X3 && v2_waves(prec, full) == 4);
-}
-__host__ __device__ constexpr int v2_lds_total(int prec, bool full) {
-  return V2_WBUF + (v2_two_slots(prec, full) ? 2 : 1) * layer_bytes(prec);
+__host__ __device__ constexpr bool v2_two_slots(int prec) { return prec != OI_PREC_BF16X6; }
+__host__ __device__ constexpr int v2_lds_total(int prec) {
+  return V2_WBUF + (v2_two_slots(prec) ? 2 : 1) * layer_bytes(prec);
 }
 
 

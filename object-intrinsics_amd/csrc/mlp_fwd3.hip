@@ -35,16 +35,12 @@ using oif3::F3_FILM;       // 0
 using oif3::F3_FILM_ROW;   // 3 * C * 4 bytes per FiLM layer
 using oif3::F3_TABS;       // 15360
 using oif3::F3_GMAX;       // [16] max |G_l| per FiLM layer (9: max |G7 w_sigma|)
-// OI_F3_BLOB (round 5): everything in front of the image ring depends on the batch element only, so ONE launch per call
+// Everything in front of the image ring depends on the batch element only, so ONE launch per call
 // (film_blob_f3_kernel, a block per element) writes it as a 22 KiB blob and a tile's prologue is 22 LDS-DMA copies of 1 KiB
 // instead of ~25 dependent global loads per thread, 21 KB of ds_writes, the row maxima and two barriers -- 4,096 workgroups of
 // a C2 launch repeated that work, 8.7k of a tile's 136k cycles with nothing to hide behind (one workgroup per CU).
-#ifndef OI_F3_BLOB
-#define OI_F3_BLOB 1
-#endif
-using oif3::F3_BLOB;       // 22528
-constexpr int F3_WBUF = OI_F3_BLOB ? F3_BLOB : F3_GMAX + 64;  // 22,528 (21,696 without the blob)
-constexpr int F3_LDS = F3_WBUF + 2 * 65536;                 // 153,600 of the CU's 163,840 bytes
+using oif3::F3_BLOB;       // 22528: the image ring follows the blob
+constexpr int F3_LDS = F3_BLOB + 2 * 65536;                 // 153,600 of the CU's 163,840 bytes
 
 // One parked 128-vector of this lane's point: [group g][k]  <->  act[4 g + k].  The values are pinned to the ACCUMULATOR
 // half of the register file through the "a" constraint: left to itself hipcc's allocator treats them as ordinary
@@ -52,24 +48,12 @@ constexpr int F3_LDS = F3_WBUF + 2 * 65536;                 // 153,600 of the CU
 // scratch memory (-Rpass-analysis=kernel-resource-usage); as AGPR-class values they cost one v_accvgpr_write and one
 // v_accvgpr_read each and never compete with the VALU operands.
 typedef float Bank[16][4];
-// timing ablations of single epilogue pieces (results garbage): -DOI_F3_ABL_PIECE bit 1 = no v_sin / v_cos (a multiply
-// instead), 2 = no v_fract, 4 = no AGPR parks, 8 = fp16 split without the residual (hi limb twice)
-#ifndef OI_F3_ABL_PIECE
-#define OI_F3_ABL_PIECE 0
-#endif
-__device__ __forceinline__ float f3_sin(float r) { return (OI_F3_ABL_PIECE & 1) ? r * 0.75f : __builtin_amdgcn_sinf(r); }
-__device__ __forceinline__ float f3_cos(float r) { return (OI_F3_ABL_PIECE & 1) ? r * 0.85f : __builtin_amdgcn_cosf(r); }
 __device__ __forceinline__ float to_acc(float v) {
-  if (OI_F3_ABL_PIECE & 4) {
-    asm volatile("" ::"v"(v));
-    return 0.25f;
-  }
   float a;
   asm("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(v));
   return a;
 }
 __device__ __forceinline__ float from_acc(float a) {
-  if (OI_F3_ABL_PIECE & 4) return a;
   float v;
   asm("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
   return v;
@@ -85,44 +69,16 @@ __device__ __forceinline__ int cu_slot_id() {
 }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-// Packed fp32 arithmetic of the epilogues.  OI_F3_PK: 0 = scalar source, 1 = 2-vectors (hipcc unpacks v_pk_*_f32 it finds in
-// the shadow of an MFMA on gfx950 again), 2 = the packed instruction as written (inline asm)
-#ifndef OI_F3_PK
-#define OI_F3_PK 1
-#endif
-#ifndef OI_F3_MAX3
-#define OI_F3_MAX3 1
-#endif
+// Packed fp32 arithmetic of the epilogues, as 2-vectors (hipcc unpacks v_pk_*_f32 it finds in the shadow of an MFMA on gfx950)
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-#if OI_F3_PK == 2
-  f32x2 r;
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-#elif OI_F3_PK == 1
   return __builtin_elementwise_fma(a, b, c);
-#else
-  return f32x2{fmaf(a[0], b[0], c[0]), fmaf(a[1], b[1], c[1])};
-#endif
 }
 __device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) {
-#if OI_F3_PK == 2
-  f32x2 r;
-  asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-#else
   return a * b;
-#endif
 }
 // a * s with the scalar s taken from the low dword of its register for both halves
 __device__ __forceinline__ f32x2 pk_mul_s(f32x2 a, float s) {
-#if OI_F3_PK == 2
-  f32x2 r, sv;
-  sv[0] = s;
-  asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(a), "v"(sv));
-  return r;
-#else
   return a * s;
-#endif
 }
 // FiLM phase of an accumulator pair (the rows and the accumulators sit in aligned register pairs)
 __device__ __forceinline__ f32x2 film_phase2(const f32x4& a, const f32x4& b, int k, float acc0, float acc1) {
@@ -130,13 +86,9 @@ __device__ __forceinline__ f32x2 film_phase2(const f32x4& a, const f32x4& b, int
 }
 // max(m, |x|, |y|) in one v_max3_f32
 __device__ __forceinline__ float max3_abs(float m, float x, float y) {
-#if OI_F3_MAX3
   float r;
   asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(r) : "v"(m), "v"(x), "v"(y));
   return r;
-#else
-  return fmaxf(m, fmaxf(fabsf(x), fabsf(y)));
-#endif
 }
 
 typedef unsigned Limbs[8][4];  // one fp16 limb plane of a B operand: [k-step][dword d] = act indices 8 s + 2 d, 8 s + 2 d + 1
@@ -184,24 +136,8 @@ template <> struct is_no_tail<NoTail> { static constexpr bool value = true; };
 // With ONE wave per SIMD nothing but the wave's own independent instructions fills a dependency stall, and an MFMA that
 // follows an MFMA waits for the matrix pipe with the whole wave behind it: sched_group_barrier pins every window to
 // MFMA, n VALU, MFMA, n VALU, MFMA, rest.
-#ifndef OI_F3_GROUPS
-#define OI_F3_GROUPS 1
-#endif
-#ifndef OI_F3_ADIST
-#define OI_F3_ADIST 1
-#endif
-#ifndef OI_F3_ABL_EPI
-#define OI_F3_ABL_EPI 0
-#endif
-#ifndef OI_F3_WINSTEPS
-#define OI_F3_WINSTEPS 1
-#endif
-#ifndef OI_F3_DSFIRST
-#define OI_F3_DSFIRST 0
-#endif
-#ifndef OI_F3_VALU_PER_MFMA
-#define OI_F3_VALU_PER_MFMA 6
-#endif
+constexpr int F3_ADIST = 1;           // A-fragment k-steps requested ahead (see stream_layer)
+constexpr int F3_VALU_PER_MFMA = 6;   // n per epilogue pair
 struct NoMid {
   __device__ __forceinline__ void operator()() const {}
 };
@@ -209,9 +145,8 @@ template <class TAIL, class MID, class EPI>
 __device__ __forceinline__ void stream_layer(const char* lds, const LayOff& y, const Limbs& bh, const Limbs& bl,
                                              f32x16 (&acc)[4], TAIL&& tail, MID&& mid, EPI&& epi) {
   constexpr bool HAS_TAIL = !is_no_tail<std::remove_cv_t<std::remove_reference_t<TAIL>>>::value;
-  // A fragments (hi / lo limb of the image) are requested OI_F3_ADIST k-steps ahead of their MFMAs: with one wave per
-  // SIMD a ds_read_b128 issued only one window (~100 cycles) ahead is not back when its MFMA comes up
-  constexpr int AD = OI_F3_ADIST;
+  // A fragments (hi / lo limb of the image) are requested F3_ADIST k-steps ahead of their MFMAs
+  constexpr int AD = F3_ADIST;
   f32x4 ah[AD + 1], al[AD + 1];
 #pragma unroll
   for (int i = 0; i < AD; ++i) {
@@ -225,14 +160,11 @@ __device__ __forceinline__ void stream_layer(const char* lds, const LayOff& y, c
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const int cur = t * 8 + s, nxt = cur + AD;
-      if (nxt < 32 && !(OI_F3_ABL_EPI == 2 && nxt >= 2)) {  // ablation 2: no A-fragment reads after the first two
+      if (nxt < 32) {
         ah[nxt % (AD + 1)] = lds_f4(lds, nxt * 1024, y.wl);
         al[nxt % (AD + 1)] = lds_f4(lds, nxt * 1024, y.wh);
       }
       int npairs = 0;
-#if OI_F3_ABL_EPI  // timing ablation: no epilogue work at all (the accumulators are only kept alive)
-      if (t > 0) asm volatile("" ::"v"(acc[t - 1][2 * s]), "v"(acc[t - 1][2 * s + 1]));
-#else
       if (t == 0) {
         if (HAS_TAIL && s < 6) {
           constexpr int first[7] = {0, 2, 3, 4, 6, 7, 8};
@@ -243,8 +175,7 @@ __device__ __forceinline__ void stream_layer(const char* lds, const LayOff& y, c
         epi(t - 1, s);
         npairs = 1;
       }
-#endif
-      const int ci = (OI_F3_ABL_EPI == 2 ? cur & 1 : cur) % (AD + 1);
+      const int ci = cur % (AD + 1);
       const f16x8 wh = __builtin_bit_cast(f16x8, ah[ci]);
       const f16x8 wl = __builtin_bit_cast(f16x8, al[ci]);
       const u32x4 uh = {bh[s][0], bh[s][1], bh[s][2], bh[s][3]}, ul = {bl[s][0], bl[s][1], bl[s][2], bl[s][3]};
@@ -253,23 +184,18 @@ __device__ __forceinline__ void stream_layer(const char* lds, const LayOff& y, c
       acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, vh, acc[t], 0, 0, 0);
       acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, vl, acc[t], 0, 0, 0);
       acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, vh, acc[t], 0, 0, 0);
-      // OI_F3_WINSTEPS k-steps per scheduling window: with 2, two epilogue pairs (four independent chains) share a window
-      // and hide each other's dependency stalls (v_sin -> cvt_pk -> fma_mix -> cvt_pk is a serial chain)
-      if (OI_F3_WINSTEPS == 1 || (s % OI_F3_WINSTEPS) == OI_F3_WINSTEPS - 1) {
-        if (OI_F3_GROUPS && (npairs >= 1 || OI_F3_WINSTEPS > 1)) {
-          if (OI_F3_DSFIRST) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);  // every LDS read of the window first
+      // one k-step per scheduling window
+      if (npairs >= 1) {
 #pragma unroll
-          for (int q = 0; q < 3 * OI_F3_WINSTEPS - 1; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if (npairs <= 1) __builtin_amdgcn_sched_group_barrier(0x002, OI_F3_VALU_PER_MFMA, 0);
-            else __builtin_amdgcn_sched_group_barrier(0x002, 2 * OI_F3_VALU_PER_MFMA, 0);
-          }
+        for (int q = 0; q < 2; ++q) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          if (npairs <= 1) __builtin_amdgcn_sched_group_barrier(0x002, F3_VALU_PER_MFMA, 0);
+          else __builtin_amdgcn_sched_group_barrier(0x002, 2 * F3_VALU_PER_MFMA, 0);
         }
-        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       }
+      __builtin_amdgcn_sched_barrier(0);
     }
-    if (OI_F3_ABL_PIECE & 16) asm volatile("" ::"v"(acc[t]));  // keeps the MFMAs alive when nothing reads them
     if (t == 0) {
       mid();  // the previous layer's output vector is complete here (its block-3 pairs ran above): scale decisions
       __builtin_amdgcn_sched_barrier(0);
@@ -279,7 +205,6 @@ __device__ __forceinline__ void stream_layer(const char* lds, const LayOff& y, c
 // block 3's epilogue with nothing to hide behind: two pairs (four independent chains) per window
 template <class EPI>
 __device__ __forceinline__ void run_tail(EPI&& epi) {
-  if (OI_F3_ABL_EPI) return;
 #pragma unroll
   for (int rp = 0; rp < 8; ++rp) {
     epi(3, rp);
@@ -287,8 +212,7 @@ __device__ __forceinline__ void run_tail(EPI&& epi) {
   }
 }
 
-// -DOI_F3_PROF: per-phase shader-clock accounting (tools/dbg/phase_prof3.py); -DOI_F3_ABL_NOPREFETCH: timing ablation
-// without the weight stream (results are garbage)
+// -DOI_F3_PROF: per-phase shader-clock accounting (tools/dbg/phase_prof3.py)
 #ifdef OI_F3_PROF
 __device__ unsigned long long oi_prof3[16];
 #define F3_T(i)                                                  \
@@ -374,9 +298,6 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   const __amdgpu_buffer_rsrc_t img_rs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(mats), 0, NMAT * LB, 0x00020000);
   auto prefetch = [&](int pos) {
-#ifdef OI_F3_ABL_NOPREFETCH
-    if (pos >= 2) return;
-#endif
     const int m = pos < 7 ? pos : (pos < 12 ? 20 - pos : (pos < 14 ? pos - 12 : (pos < 16 ? 22 - pos : 14)));
     // a wave copies 16 consecutive KiB, 4 KiB per (M0, soffset) setting: the instruction's immediate offset advances the
     // LDS and the global address alike, so four 1 KiB copies share one M0 / soffset pair (6 instead of 16 instructions per
@@ -384,7 +305,7 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
 #pragma unroll
     for (int q = 0; q < LB / 4096 / F3_WAVES; ++q) {
       const int c = (wave * (LB / 4096 / F3_WAVES) + q) * 4096;
-      auto* dst = (__attribute__((address_space(3))) void*)(lds + F3_WBUF + (pos & 1) * LB + c);
+      auto* dst = (__attribute__((address_space(3))) void*)(lds + F3_BLOB + (pos & 1) * LB + c);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 0, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 1024, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 2048, 0);
@@ -393,7 +314,7 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   };
   auto lay = [&](int pos) {  // A-image lane bases of ring position pos
     LayOff y;
-    y.wl = o.l16 + F3_WBUF + (pos & 1) * LB;
+    y.wl = o.l16 + F3_BLOB + (pos & 1) * LB;
     y.wh = y.wl + 32768;
     y.wq = 0;
     y.f16 = 0;
@@ -402,7 +323,6 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   // lane base of FiLM layer l's rows: [A | B | G] x 128 floats (see the staging loop)
   auto film_base = [&](int l) { return o.h16 + F3_FILM + l * F3_FILM_ROW; };
 
-#if OI_F3_BLOB
   float px, py, pz;
   {
     bool valid;
@@ -424,47 +344,6 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   // point + blob landed (everything older than image 0's 16 copies per wave: the counter retires in issue order), and visible
   // to every wave; image 0 stays in flight
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(LB / 1024 / F3_WAVES) : "memory");
-#else
-  prefetch(0);
-  {  // small tables + the FiLM rows of all 9 layers, once.  The phase is formed in REVOLUTIONS so that the range reduction
-     // is  r = phi - rint(phi)  (exact):  phi / 2pi = A * acc + B  with  A = gamma * 2^-k_image / 2pi  (2^-k: the power-of-
-     // two scale baked into the layer's MFMA image) and  B = (gamma * bias + beta) / 2pi;  G = gamma * 2^-k_image is the
-     // factor of cos(phi) in the reverse sweep.  Row 9: G7 * w_sigma (layer 7 emits the reverse sweep's first operand).
-    float* tabs = reinterpret_cast<float*>(lds + F3_TABS);
-    for (int i = tid; i < H_TABS_END; i += 64 * F3_WAVES) tabs[i] = hdr[i];
-    float* film = reinterpret_cast<float*>(lds + F3_FILM);
-    constexpr float INV_2PI = 0.15915494309189533577f;
-    for (int i = tid; i < 9 * C; i += 64 * F3_WAVES) {
-      const int l = i / C, f = i % C;
-      const float gm = gamma[((size_t)e * 9 + l) * C + f];
-      const float wsc = l == 0 ? 1.f : hdr[H_WSCALE + (l < NL_SDF ? l - 1 : 14)];
-      const float G = gm * wsc;
-      film[l * (F3_FILM_ROW / 4) + f] = G * INV_2PI;
-      film[l * (F3_FILM_ROW / 4) + C + f] = fmaf(gm, hdr[H_BIAS + l * C + f], beta[((size_t)e * 9 + l) * C + f]) * INV_2PI;
-      film[l * (F3_FILM_ROW / 4) + 2 * C + f] = G;
-      if (l == 7) film[9 * (F3_FILM_ROW / 4) + f] = G * hdr[H_SIG + f];
-    }
-  }
-  float px, py, pz;
-  {
-    bool valid;
-    const long long pt = point_of(valid);
-    px = pts[pt * 3 + 0], py = pts[pt * 3 + 1], pz = pts[pt * 3 + 2];
-  }
-  __syncthreads();  // tables visible (image 0 still in flight)
-  {  // max |G_l| per layer (and of row 9): with the per-image bounds of the packed header they bound the growth of an
-     // adjoint vector through one reverse layer, which is what lets its fp16 scale be chosen BEFORE it is complete
-    const float* film = reinterpret_cast<const float*>(lds + F3_FILM);
-    float* gmax = reinterpret_cast<float*>(lds + F3_GMAX);
-    for (int l = wave; l < 10; l += F3_WAVES) {
-      const int off = l * (F3_FILM_ROW / 4) + (l == 9 ? 0 : 2 * C);
-      const float m = oi::wave_max(fmaxf(fabsf(film[off + lane]), fabsf(film[off + 64 + lane])));
-      if (lane == 0) gmax[l] = m;
-    }
-  }
-  __syncthreads();
-
-#endif
 #ifdef OI_F3_PROF
   unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tprev = __builtin_readcyclecounter();
@@ -473,21 +352,7 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
 #endif
   float act[64];                 // fp32 staging of an adjoint vector before its normalisation (reverse layers only)
   f32x16 acc[4];
-#if OI_F3_ABL_PIECE & 16  // timing ablation: the epilogues read a plain VGPR instead of the accumulators
-  float acc_dummy = 0.37f * lane;
-  asm volatile("" : "+v"(acc_dummy));
-#define F3_ACC(TB, I) acc_dummy
-#else
-#define F3_ACC(TB, I) acc[TB][I]
-#endif
   Limbs AH, AL, BH, BL;          // two B-operand limb sets: a layer reads one and its epilogue fills the other
-#if OI_F3_ABL_EPI
-  for (int s_ = 0; s_ < 8; ++s_)
-    for (int d_ = 0; d_ < 4; ++d_) {
-      AH[s_][d_] = AL[s_][d_] = BH[s_][d_] = BL[s_][d_] = lane * 77u + s_;
-      asm volatile("" : "+v"(AH[s_][d_]), "+v"(AL[s_][d_]), "+v"(BH[s_][d_]), "+v"(BL[s_][d_]));
-    }
-#endif
   Bank P0, P1, P2, P3;           // parked REDUCED PHASES r_l (revolutions, |r| <= 1/2) or one parked adjoint vector
   // FiLM / table rows of the epilogue group in flight, double-buffered by group parity: the rows of group g + 1 are
   // requested while group g is processed (an LDS round trip in front of every group's first FMA otherwise)
@@ -500,7 +365,7 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   // phi (revolutions) -> reduced phase; v_sin_f32 / v_cos_f32 take revolutions and are specified on [-256, 256]: v_fract
   // (exact) keeps any phase inside that domain.  (Feeding the unreduced phase differs by at most 1 ulp inside the
   // domain, tools/dbg/sin_rev_probe.hip: the FAST flavour does that.)
-  auto reduce = [&](float phi) { return (FAST || (OI_F3_ABL_PIECE & 2)) ? phi : __builtin_amdgcn_fractf(phi); };
+  auto reduce = [&](float phi) { return FAST ? phi : __builtin_amdgcn_fractf(phi); };
   auto ld = [&](int imm, int base) { return lds_f4(lds, imm, base); };
 #define ROW_A(FB, G) ld(grp_f0(G) * 4, FB)
 #define ROW_B(FB, G) ld((C + grp_f0(G)) * 4, FB)
@@ -522,7 +387,7 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         const f32x4 w = lds_f4(lds, F3_TABS + H_TAB0 * 4 + (grp_f0(g) + k) * 16, o.h64);
         const float u = fmaf(pz, w[2], fmaf(py, w[1], px * w[0]));
         const float r = reduce(fmaf(a4[k], u, b4[k]));
-        sn[k] = f3_sin(r);
+        sn[k] = __builtin_amdgcn_sinf(r);
         park(g, k, r);
       }
       split_pair(sn[0], sn[1], NH[g >> 1][2 * (g & 1)], NL[g >> 1][2 * (g & 1)]);
@@ -546,11 +411,11 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         NEXT;                                                                                              \
       }                                                                                                    \
     }                                                                                                      \
-    const f32x2 ph = film_phase2(R.a, R.b, k, F3_ACC(tb, 2 * rp), F3_ACC(tb, 2 * rp + 1));                 \
+    const f32x2 ph = film_phase2(R.a, R.b, k, acc[tb][2 * rp], acc[tb][2 * rp + 1]);                 \
     const float r0 = reduce(ph[0]), r1 = reduce(ph[1]);                                                    \
     PARK(g, k, r0);                                                                                        \
     PARK(g, k + 1, r1);                                                                                    \
-    split_pair(f3_sin(r0), f3_sin(r1), NH[2 * tb + (rp >> 2)][rp & 3],       \
+    split_pair(__builtin_amdgcn_sinf(r0), __builtin_amdgcn_sinf(r1), NH[2 * tb + (rp >> 2)][rp & 3],       \
                NL[2 * tb + (rp >> 2)][rp & 3]);                                                            \
   }
   // Reverse sweep bookkeeping.  A reverse layer's input V_l = v_l * S_l is held as fp16 limbs with a power-of-two scale
@@ -587,8 +452,8 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         NEXT;                                                                                              \
       }                                                                                                    \
     }                                                                                                      \
-    const f32x2 cs = {f3_cos(from_acc(BANK[g][k])), f3_cos(from_acc(BANK[g][k + 1]))};                     \
-    const f32x2 v = pk_mul(pk_mul_s(f32x2{F3_ACC(tb, 2 * rp), F3_ACC(tb, 2 * rp + 1)}, sg),                \
+    const f32x2 cs = {__builtin_amdgcn_cosf(from_acc(BANK[g][k])), __builtin_amdgcn_cosf(from_acc(BANK[g][k + 1]))};                     \
+    const f32x2 v = pk_mul(pk_mul_s(f32x2{acc[tb][2 * rp], acc[tb][2 * rp + 1]}, sg),                \
                            pk_mul(f32x2{R.c[k], R.c[k + 1]}, cs));                                         \
     vmax = max3_abs(vmax, v[0], v[1]);                                                                     \
     split_pair(v[0], v[1], NH[2 * tb + (rp >> 2)][rp & 3], NL[2 * tb + (rp >> 2)][rp & 3]);                \
@@ -667,15 +532,15 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         NEXT_G(F6);
       }
     }
-    const f32x2 ph = film_phase2(R.a, R.b, k, F3_ACC(tb, 2 * rp), F3_ACC(tb, 2 * rp + 1));
+    const f32x2 ph = film_phase2(R.a, R.b, k, acc[tb][2 * rp], acc[tb][2 * rp + 1]);
     f32x2 cs;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const float r = reduce(ph[i]);
-      const float sn = f3_sin(r);
+      const float sn = __builtin_amdgcn_sinf(r);
       fv[k + i] = sn;
       sdf_part = fmaf(sn, R.d[k + i], sdf_part);
-      cs[i] = f3_cos(r);
+      cs[i] = __builtin_amdgcn_cosf(r);
     }
     const f32x2 v = pk_mul(pk_mul_s(f32x2{R.c[k], R.c[k + 1]}, sg7), cs);
     vmax = max3_abs(vmax, v[0], v[1]);
@@ -731,7 +596,7 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   asm volatile("" : "+v"(one));
   auto pg3 = [&](int tb, int rp) {
     const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
-    const f32x2 a = pk_mul_s(f32x2{F3_ACC(tb, 2 * rp), F3_ACC(tb, 2 * rp + 1)}, one);
+    const f32x2 a = pk_mul_s(f32x2{acc[tb][2 * rp], acc[tb][2 * rp + 1]}, one);
     vmax = max3_abs(vmax, a[0], a[1]);
     P0[g][k] = to_acc(a[0]);
     P0[g][k + 1] = to_acc(a[1]);
@@ -772,8 +637,8 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
         NEXT_G(F1);
       }
     }
-    const f32x2 ph = film_phase2(R.a, R.b, k, F3_ACC(tb, 2 * rp), F3_ACC(tb, 2 * rp + 1));
-    const f32x2 cs = {f3_cos(reduce(ph[0])), f3_cos(reduce(ph[1]))};
+    const f32x2 ph = film_phase2(R.a, R.b, k, acc[tb][2 * rp], acc[tb][2 * rp + 1]);
+    const f32x2 cs = {__builtin_amdgcn_cosf(reduce(ph[0])), __builtin_amdgcn_cosf(reduce(ph[1]))};
     const f32x2 v = pk_mul(pk_mul_s(f32x2{from_acc(P0[g][k]), from_acc(P0[g][k + 1])}, sg2), pk_mul(f32x2{R.c[k], R.c[k + 1]}, cs));
     vmax = max3_abs(vmax, v[0], v[1]);
     split_pair(v[0], v[1], AH[2 * tb + (rp >> 2)][rp & 3], AL[2 * tb + (rp >> 2)][rp & 3]);
@@ -796,8 +661,8 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
     Rows& R = rw[g & 1];
     if (k == 0 && g < 15) rw[(g + 1) & 1].c = ROW_G(F0, g + 1);
-    const f32x2 cs = {f3_cos(from_acc(P1[g][k])), f3_cos(from_acc(P1[g][k + 1]))};
-    const f32x2 v = pk_mul(f32x2{F3_ACC(tb, 2 * rp), F3_ACC(tb, 2 * rp + 1)}, pk_mul(f32x2{R.c[k], R.c[k + 1]}, cs));
+    const f32x2 cs = {__builtin_amdgcn_cosf(from_acc(P1[g][k])), __builtin_amdgcn_cosf(from_acc(P1[g][k + 1]))};
+    const f32x2 v = pk_mul(f32x2{acc[tb][2 * rp], acc[tb][2 * rp + 1]}, pk_mul(f32x2{R.c[k], R.c[k + 1]}, cs));
     act[4 * g + k] = v[0];
     act[4 * g + k + 1] = v[1];
   };
@@ -868,8 +733,8 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const f32x4 w = lds_f4(lds, F3_TABS + H_TABV * 4 + (grp_f0(g) + k + i) * 16, o.h64);
-        const float u = F3_ACC(tb, 2 * rp + i) + fmaf(vz, w[2], fmaf(vy, w[1], vx * w[0]));
-        const float sn = f3_sin(reduce(fmaf(R.a[k + i], u, R.b[k + i])));
+        const float u = acc[tb][2 * rp + i] + fmaf(vz, w[2], fmaf(vy, w[1], vx * w[0]));
+        const float sn = __builtin_amdgcn_sinf(reduce(fmaf(R.a[k + i], u, R.b[k + i])));
         r0 = fmaf(sn, w0[k + i], r0);
         r1 = fmaf(sn, w1[k + i], r1);
         r2 = fmaf(sn, w2[k + i], r2);
@@ -938,9 +803,7 @@ int launch_full3(const float* pts, const char* pk, const float* gamma, const flo
   auto k = sdf_mlp_full3_kernel<FAST>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS);
   char* blob = scratch + full3_slot_bytes(B, n);   // behind the feature slots
-#if OI_F3_BLOB
   if (!blob_ready) hipLaunchKernelGGL(film_blob_f3_kernel, dim3(B, 9), dim3(128), 0, st, pk, gamma, beta, blob);
-#endif
   hipLaunchKernelGGL(k, grid, block, F3_LDS, st, pts, pk, gamma, beta, sdf, grad, rgb, feat, scratch, blob, n);
   return oi::check_launch("oi_sdf_mlp_fwd(full3)");
 }

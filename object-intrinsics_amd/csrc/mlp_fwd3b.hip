@@ -18,12 +18,9 @@
 //  * Every layer product is formed output block by output block; the FiLM / sin / cos (or cos-multiply) work of block
 //    t-1 is issued between block t's MFMAs.  The first MFMA of a block takes an inline-constant zero accumulator.
 //
-// Two kernels share the machinery above:
-//   sdf_mlp_full3p_kernel (round 5, the default)   per-element images diag(gamma) W built once per call by film_images_b_kernel
-//                                                   (the accumulator IS the phase: no FiLM arithmetic in the epilogues) and a
-//                                                   per-element table blob fetched by LDS-DMA -- see the section further down;
-//   sdf_mlp_full3b_kernel (round 4)                 shared bf16(W) images + FiLM rows staged per tile; kept behind the run-time
-//                                                   switch OI_BF16_PRESCALE=0 as the same-box A/B reference of the former.
+// The kernel, sdf_mlp_full3p_kernel, runs on per-element images diag(gamma) W built once per call by film_images_b_kernel
+// (the accumulator IS the phase: no FiLM arithmetic in the epilogues) and a per-element table blob fetched by LDS-DMA -- see
+// the section further down.
 #include <algorithm>
 #include <type_traits>
 
@@ -37,22 +34,10 @@ constexpr int B3_WAVES = 4;
 constexpr int B3_TILE = B3_WAVES * WAVE_PTS;  // 128 points per workgroup
 constexpr int LBB = 32768;                    // bytes of one bf16 image
 constexpr int B3_NSLOT = 4;                   // ring slots
-// LDS: FiLM rows [10][A 128 | B 128 | G 128] floats, small tables, image ring
-constexpr int B3_FILM = 0;
-constexpr int B3_FILM_ROW = 3 * C * 4;                      // bytes per FiLM layer
-constexpr int B3_TABS = B3_FILM + 10 * B3_FILM_ROW;         // 15360
-constexpr int B3_WBUF = B3_TABS + H_TABS_END * 4;           // 21632
 // Two small A images for the K = 128 -> 3 products at the ends of the network (d sdf/dx = W0^T v0; rgb = Wrgb sin(phi_v)): rows
 // 0..2 = the bf16 hi limb of the three output rows, 3..5 their lo limbs, 6..7 zero; [k-step 8][lane half 2][row 8][8 x bf16].
 // (Lanes read row (lane & 7): MFMA output rows >= 8 then hold copies nobody reads.)
-constexpr int B3_SIMG = B3_WBUF + B3_NSLOT * LBB;           // 152,704
 constexpr int SIMG_BYTES = 8 * 2 * 8 * 16;                  // 2 KiB each
-constexpr int B3_LDS = B3_SIMG + 2 * SIMG_BYTES;            // 156,800 of the CU's 163,840 bytes
-// The three-input-column products (layer 0, the albedo head's gradient columns), the three-output-row products (d sdf/dx, rgb)
-// on the matrix cores instead of the VALU: 1 = on (default), 0 = the round-4a VALU forms (A/B switch)
-#ifndef OI_B3_MFMA_EDGES
-#define OI_B3_MFMA_EDGES 1
-#endif
 
 typedef unsigned Limb[8][4];   // bf16 B operand of one layer: [k-step][dword d] = act indices 8 s + 2 d, 8 s + 2 d + 1
 typedef unsigned BankB[16][2];  // one parked 128-vector of cos(phi) as fp16 pairs: [group g][pair] <-> act[4 g + 2 pair (+1)]
@@ -76,18 +61,6 @@ __device__ __forceinline__ unsigned pk_f16(float a, float b) {  // v_cvt_pk_f16_
   const f16x2 v = {(_Float16)a, (_Float16)b};
   return __builtin_bit_cast(unsigned, v);
 }
-// x * (fp16 half of c): v_fma_mix_f32 reads the half in place (hipcc's own choice is v_cvt_f32_f16 + v_mul_f32).  `x` must be
-// the result of an instruction the compiler knows (it pads no MFMA-result hazard for an inline-asm reader).
-__device__ __forceinline__ float mul_lo(float x, unsigned c) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(x), "v"(c));
-  return r;
-}
-__device__ __forceinline__ float mul_hi(float x, unsigned c) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(x), "v"(c));
-  return r;
-}
 
 struct NoTailB {
   __device__ __forceinline__ void operator()(int, int) const {}
@@ -97,22 +70,7 @@ template <> struct is_no_tail_b<NoTailB> { static constexpr bool value = true; }
 
 // A fragments are requested this many k-steps ahead of their MFMA (a window is ~40 cycles here, an LDS round trip of a lone
 // wave 64-130)
-#ifndef OI_B3_ADIST
-#define OI_B3_ADIST 3
-#endif
-#ifndef OI_B3_GROUPS
-#define OI_B3_GROUPS 1
-#endif
-#ifndef OI_B3_WINSTEPS
-#define OI_B3_WINSTEPS 1
-#endif
-#ifndef OI_B3_VALU_PER_MFMA
-#define OI_B3_VALU_PER_MFMA 8
-#endif
-// timing ablations (results garbage): 1 = no epilogue work, 2 = additionally no A-fragment reads after the first
-#ifndef OI_B3_ABL
-#define OI_B3_ABL 0
-#endif
+constexpr int B3_ADIST = 3;
 
 // One layer product of the stream: acc = W_img . B, output block t outer, one scheduling window per k-step = 1 MFMA + the
 // epilogue pair that hides behind it:
@@ -138,7 +96,7 @@ __device__ __forceinline__ void stream_layer_b(const char* lds, int wl, const Li
                                                EPI&& epi, POST&& post = POST(), INIT&& init = INIT()) {
   constexpr bool HAS_TAIL = !is_no_tail_b<std::remove_cv_t<std::remove_reference_t<TAIL>>>::value;
   constexpr bool HAS_INIT = !is_no_init_b<std::remove_cv_t<std::remove_reference_t<INIT>>>::value;
-  constexpr int AD = OI_B3_ADIST;
+  constexpr int AD = B3_ADIST;
   f32x4 a[AD + 1];
 #pragma unroll
   for (int i = 0; i < AD; ++i) a[i] = lds_f4(lds, i * 1024, wl);
@@ -148,11 +106,8 @@ __device__ __forceinline__ void stream_layer_b(const char* lds, int wl, const Li
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const int cur = t * 8 + s, nxt = cur + AD;
-      if (nxt < 32 && !(OI_B3_ABL == 2)) a[nxt % (AD + 1)] = lds_f4(lds, nxt * 1024, wl);
+      if (nxt < 32) a[nxt % (AD + 1)] = lds_f4(lds, nxt * 1024, wl);
       int npairs = 0;
-#if OI_B3_ABL
-      if (t > 0) asm volatile("" ::"v"(acc[t - 1][2 * s]), "v"(acc[t - 1][2 * s + 1]));
-#else
       if (t == 0) {
         if (HAS_TAIL && s < 6) {
           constexpr int first[7] = {0, 2, 3, 4, 6, 7, 8};
@@ -163,26 +118,17 @@ __device__ __forceinline__ void stream_layer_b(const char* lds, int wl, const Li
         epi(t - 1, s);
         npairs = 1;
       }
-#endif
-      const bf16x8 w = __builtin_bit_cast(bf16x8, a[(OI_B3_ABL == 2 ? cur % AD : cur) % (AD + 1)]);
+      const bf16x8 w = __builtin_bit_cast(bf16x8, a[cur % (AD + 1)]);
       const u32x4 ub = {bh[s][0], bh[s][1], bh[s][2], bh[s][3]};
       const bf16x8 v = __builtin_bit_cast(bf16x8, ub);
       if (HAS_INIT && s == 4 && t < 3) acc[t + 1] = init(t + 1);
       acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, v, (s == 0 && !HAS_INIT) ? zero : acc[t], 0, 0, 0);
-      // OI_B3_WINSTEPS k-steps per scheduling window: with 2, two epilogue pairs (independent chains) share a window and fill
-      // each other's wait states (accvgpr read -> use, v_fma_mix -> v_cvt_pk: an s_nop each when a pair is alone)
-      if (OI_B3_WINSTEPS == 1 || (s % OI_B3_WINSTEPS) == OI_B3_WINSTEPS - 1) {
-        if (OI_B3_GROUPS && npairs >= 1) {
-#pragma unroll
-          for (int q = 0; q + 1 < OI_B3_WINSTEPS; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // an MFMA opens each part, the epilogue fills its shadow
-            __builtin_amdgcn_sched_group_barrier(0x002, OI_B3_VALU_PER_MFMA, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 64, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
+      // one k-step per scheduling window: the MFMA opens it, the epilogue fills its shadow
+      if (npairs >= 1) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 64, 0);
       }
+      __builtin_amdgcn_sched_barrier(0);
     }
     post(t, acc[t]);
   }
@@ -190,7 +136,6 @@ __device__ __forceinline__ void stream_layer_b(const char* lds, int wl, const Li
 // block 3's epilogue with nothing to hide behind: two pairs (four independent chains) per window
 template <class EPI>
 __device__ __forceinline__ void run_tail_b(EPI&& epi) {
-  if (OI_B3_ABL) return;
 #pragma unroll
   for (int rp = 0; rp < 8; ++rp) {
     epi(3, rp);
@@ -215,570 +160,15 @@ __device__ unsigned long long oi_prof3b[1024][16];  // replicated by workgroup: 
 // wait until at most KEEP of this wave's vector-memory operations are outstanding (they retire in issue order: everything
 // older -- the image this layer reads -- has landed), then rendezvous: image resident for every wave, the slot of the
 // layer before free
-// OI_B3_BARE_BARRIER (round 5): __syncthreads() carries workgroup-scope fences, and for those hipcc drains EVERY outstanding
+// A bare s_barrier, not __syncthreads(): __syncthreads() carries workgroup-scope fences, and for those hipcc drains EVERY outstanding
 // vector-memory operation in front of the s_barrier (`s_waitcnt vmcnt(0) lgkmcnt(0)` right behind the counted wait below: read off
 // the ISA) -- the two younger images included, i.e. the ring never had more than the image it was waiting for in flight.  A bare
 // s_barrier behind the counted wait keeps them in flight; LDS visibility of the awaited image follows from the wait itself plus
 // the barrier (MI355X_MICROARCH.md: "nothing orders a ds_read behind a pending LDS-DMA except the issuing wave's covering vmcnt
 // (plus a barrier, for other waves' reads)").
-#ifndef OI_B3_BARE_BARRIER
-#define OI_B3_BARE_BARRIER 1
-#endif
 template <int KEEP>
 __device__ __forceinline__ void ring_sync_b() {
-#if OI_B3_BARE_BARRIER
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(KEEP) : "memory");
-#else
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KEEP) : "memory");
-  __syncthreads();
-#endif
-}
-
-template <bool FAST>
-__global__ void __launch_bounds__(64 * B3_WAVES) __attribute__((amdgpu_waves_per_eu(1, 1)))
-sdf_mlp_full3b_kernel(const float* __restrict__ pts, const char* __restrict__ packed, const float* __restrict__ gamma,
-                      const float* __restrict__ beta, float* __restrict__ sdf_out, float* __restrict__ grad_out,
-                      float* __restrict__ rgb_out, float* __restrict__ feat_out, long long n_per_elem) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-#ifdef OI_B3_PROF
-  const unsigned long long t_entry = __builtin_readcyclecounter();
-  const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();  // constant 100 MHz
-#endif
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, j = lane & 31;
-  const int e = blockIdx.y;
-  const float* hdr = reinterpret_cast<const float*>(packed);
-  const char* mats = packed + H_BYTES;
-
-  LaneOff o;
-  o.h16 = 16 * h;
-  o.h64 = 64 * h;
-  o.l16 = 16 * lane;
-  o.l16hi = 0;
-  asm volatile("" : "+v"(o.h16), "+v"(o.h64), "+v"(o.l16));
-
-  auto point_of = [&](bool& valid) {
-    int jj = lane & 31;
-    asm volatile("" : "+v"(jj));
-    const long long local = (long long)blockIdx.x * B3_TILE + wave * WAVE_PTS + jj;
-    valid = local < n_per_elem;
-    return (long long)e * n_per_elem + (valid ? local : n_per_elem - 1);
-  };
-
-  // optional feature output through a buffer descriptor: an absent output (0 records) or a tail lane (offset past the
-  // end) is dropped by the hardware's range check -- no branch inside the layer bodies
-  __amdgpu_buffer_rsrc_t feat_rs;
-  int feat_off;
-  {
-    const long long base_pt = (long long)e * n_per_elem + (long long)blockIdx.x * B3_TILE + wave * WAVE_PTS;
-    const long long left = n_per_elem - ((long long)blockIdx.x * B3_TILE + wave * WAVE_PTS);
-    const int npts = feat_out == nullptr ? 0 : (left >= WAVE_PTS ? WAVE_PTS : (left > 0 ? (int)left : 0));
-    feat_rs = __builtin_amdgcn_make_buffer_rsrc(feat_out + base_pt * C, 0, npts * C * 4, 0x00020000);
-    feat_off = j * C * 4 + 16 * h;
-  }
-
-  // image sequence (ring slot = position & 3):
-  //   0..6    forward layers 1..7       (mats 0..6)
-  //   7..13   transposed layers 7..1    (mats 13..7)
-  //   14      albedo head               (mat 14)
-  const __amdgpu_buffer_rsrc_t img_rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(mats), 0, NMAT * LBB, 0x00020000);
-  auto prefetch = [&](int pos) {  // 8 KiB per wave: 4 KiB per (M0, soffset) setting, the immediate advances both addresses
-    const int m = pos < 7 ? pos : (pos < 14 ? 20 - pos : 14);
-#pragma unroll
-    for (int q = 0; q < LBB / 4096 / B3_WAVES; ++q) {
-      const int c = (wave * (LBB / 4096 / B3_WAVES) + q) * 4096;
-      auto* dst = (__attribute__((address_space(3))) void*)(lds + B3_WBUF + (pos & (B3_NSLOT - 1)) * LBB + c);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LBB + c, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LBB + c, 1024, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LBB + c, 2048, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LBB + c, 3072, 0);
-    }
-  };
-  constexpr int DMA_PER_IMAGE = LBB / 1024 / B3_WAVES;  // vector-memory instructions per wave and image: 8
-  // lane base of ring position pos, laundered: the A-fragment reads then are <this VGPR> + a 16-bit immediate (left to
-  // itself hipcc folds the slot base into the immediate, overflows its 16 bits and forms a new address on the VALU per read)
-  auto lay = [&](int pos) {
-    int b = o.l16 + B3_WBUF + (pos & (B3_NSLOT - 1)) * LBB;
-    asm volatile("" : "+v"(b));
-    return b;
-  };
-  auto film_base = [&](int l) { return o.h16 + B3_FILM + l * B3_FILM_ROW; };
-
-  float px, py, pz;
-  {
-    bool valid;
-    const long long pt = point_of(valid);
-    px = pts[pt * 3 + 0], py = pts[pt * 3 + 1], pz = pts[pt * 3 + 2];
-  }
-  {  // small tables + the FiLM rows of all 9 layers, once.  The phase is formed in REVOLUTIONS: phi / 2pi = A * acc + B with
-     // A = gamma / 2pi and B = (gamma * bias + beta) / 2pi;  G = gamma is the factor of cos(phi) in the reverse sweep.
-     // Row 9: G7 * w_sigma (layer 7 emits the reverse sweep's first operand).
-    float* tabs = reinterpret_cast<float*>(lds + B3_TABS);
-    for (int i = tid; i < H_TABS_END; i += 64 * B3_WAVES) tabs[i] = hdr[i];
-    float* film = reinterpret_cast<float*>(lds + B3_FILM);
-    constexpr float INV_2PI = 0.15915494309189533577f;
-    for (int i = tid; i < 9 * C; i += 64 * B3_WAVES) {
-      const int l = i / C, f = i % C;
-      const float gm = gamma[((size_t)e * 9 + l) * C + f];
-      film[l * (B3_FILM_ROW / 4) + f] = gm * INV_2PI;
-      film[l * (B3_FILM_ROW / 4) + C + f] = fmaf(gm, hdr[H_BIAS + l * C + f], beta[((size_t)e * 9 + l) * C + f]) * INV_2PI;
-      film[l * (B3_FILM_ROW / 4) + 2 * C + f] = gm;
-      if (l == 7) film[9 * (B3_FILM_ROW / 4) + f] = gm * hdr[H_SIG + f];
-    }
-  }
-#if OI_B3_MFMA_EDGES
-  {  // the two 3-row A images: entry (image, k-step s, half hh, row i): 8 bf16 = M[i][feat_of(8 s + j, hh)], j = 0..7
-    const int img = tid >> 7, s_ = (tid >> 4) & 7, hh = (tid >> 3) & 1, i = tid & 7;
-    const int c = i < 3 ? i : i - 3;
-    unsigned d[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[2];
-#pragma unroll
-      for (int e_ = 0; e_ < 2; ++e_) {
-        const int f = feat_of(8 * s_ + 2 * q + e_, hh);
-        const float w = i < 6 ? (img == 0 ? hdr[H_TAB0 + 4 * f + c] : hdr[H_RGB + c * C + f]) : 0.f;
-        const float whi = (float)(__bf16)w;
-        v[e_] = i < 3 ? whi : w - whi;
-      }
-      d[q] = pk_bf16(v[0], v[1]);
-    }
-    *reinterpret_cast<u32x4*>(lds + B3_SIMG + img * SIMG_BYTES + ((s_ * 2 + hh) * 8 + i) * 16) = u32x4{d[0], d[1], d[2], d[3]};
-  }
-#endif
-  // (the prologue's loads are complete: hipcc waits with vmcnt(0) for them before the LDS writes above -- the image DMA is
-  //  issued behind them so that those waits do not drain it)
-  prefetch(0);
-  prefetch(1);
-  prefetch(2);
-  __syncthreads();  // tables visible
-
-#ifdef OI_B3_PROF
-  unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tprev = __builtin_readcyclecounter();
-  const unsigned long long tstart = tprev;
-  pacc[4] = tstart - t_entry;  // prologue
-#endif
-  f32x16 acc[4];
-  Limb AH, BH, CH;               // two B-operand limb sets in turn + the features a_8 for the albedo head
-#if OI_B3_ABL
-  for (int s_ = 0; s_ < 8; ++s_)
-    for (int d_ = 0; d_ < 4; ++d_) {
-      AH[s_][d_] = BH[s_][d_] = CH[s_][d_] = lane * 77u + s_;
-      asm volatile("" : "+v"(AH[s_][d_]), "+v"(BH[s_][d_]), "+v"(CH[s_][d_]));
-    }
-#endif
-  BankB P0, P1, P2, P3, P4, P5, P6;  // cos(phi_l), l = 0..6, fp16 pairs in the AGPR half
-  // FiLM / table rows of the epilogue groups in flight: the rows of group g + 2 are requested while group g is processed
-  struct Rows {
-    f32x4 a, b, c, d;
-  } rw[4];
-  f32x4 fv;
-  float sdf_part = 0.f;
-
-  auto reduce = [&](float phi) { return FAST ? phi : __builtin_amdgcn_fractf(phi); };
-  auto ld = [&](int imm, int base) { return lds_f4(lds, imm, base); };
-#define ROW_A(FB, G) ld(grp_f0(G) * 4, FB)
-#define ROW_B(FB, G) ld((C + grp_f0(G)) * 4, FB)
-#define ROW_G(FB, G) ld((2 * C + grp_f0(G)) * 4, FB)
-#define ROW_SIG(G) ld(B3_TABS + (H_SIG + grp_f0(G)) * 4, o.h16)
-  // row requests by epilogue kind: the rows of group G of the layer whose rows sit at lane base FB -> rw[G & 3].  (A ring of
-  // four: the block-3 pairs of a layer run inside the next layer, and while groups 14 / 15 are processed the NEXT epilogue's
-  // groups 0 / 1 are requested -- 16 = 0 mod 4 keeps the two sequences on one ring.)
-#define REQ_AB(FB) [&](int g_) { rw[g_ & 3].a = ROW_A(FB, g_); rw[g_ & 3].b = ROW_B(FB, g_); }
-#define REQ_G(FB) [&](int g_) { rw[g_ & 3].c = ROW_G(FB, g_); }
-  auto req_none = [](int) {};
-
-  // ---- layer 0 (K = 3) on the VALU: sin(phi_0) -> limb set NH; cos(phi_0) -> P0
-  auto layer0 = [&](Limb& NH) {
-    const int fb = film_base(0);
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const f32x4 a4 = ROW_A(fb, g), b4 = ROW_B(fb, g);
-      float sn[4], cs[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const f32x4 w = lds_f4(lds, B3_TABS + H_TAB0 * 4 + (grp_f0(g) + k) * 16, o.h64);
-        const float u = fmaf(pz, w[2], fmaf(py, w[1], px * w[0]));
-        const float r = reduce(fmaf(a4[k], u, b4[k]));
-        sn[k] = __builtin_amdgcn_sinf(r);
-        cs[k] = __builtin_amdgcn_cosf(r);
-      }
-      NH[g >> 1][2 * (g & 1)] = pk_bf16(sn[0], sn[1]);
-      NH[g >> 1][2 * (g & 1) + 1] = pk_bf16(sn[2], sn[3]);
-      P0[g][0] = to_acc_u(pk_f16(cs[0], cs[1]));
-      P0[g][1] = to_acc_u(pk_f16(cs[2], cs[3]));
-      if (g & 1) __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-
-  // B fragment of a three-column product: the 3-vector v as bf16 hi + lo limbs in the K slots
-  //   half 0: (vh.x vh.y vh.z | vl.x vl.y vl.z | 0 0)   half 1: (vh.x vh.y vh.z | 0 ..)
-  // against A rows  half 0: (wh.x wh.y wh.z | wh.x wh.y wh.z | 0 0)   half 1: (wl.x wl.y wl.z | 0 ..):  vh wh + vl wh + vh wl
-  auto frag3_b = [&](float vx, float vy, float vz) {
-    const float hx = (float)(__bf16)vx, hy = (float)(__bf16)vy, hz = (float)(__bf16)vz;
-    const unsigned d0 = pk_bf16(hx, hy);
-    const unsigned d1 = h == 0 ? pk_bf16(hz, vx - hx) : pk_bf16(hz, 0.f);
-    const unsigned d2 = h == 0 ? pk_bf16(vy - hy, vz - hz) : 0u;
-    return __builtin_bit_cast(bf16x8, u32x4{d0, d1, d2, 0u});
-  };
-  // A fragment of output block t from a [128][4] fp32 table (w.x w.y w.z 0 per feature) at LDS offset TAB
-  auto frag3_a = [&](int tab, int t) {
-    const f32x4 w = lds_f4(lds, tab + t * 32 * 16, 16 * (lane & 31));
-    const float hx = (float)(__bf16)w[0], hy = (float)(__bf16)w[1], hz = (float)(__bf16)w[2];
-    const float ax = h == 0 ? hx : w[0] - hx, ay = h == 0 ? hy : w[1] - hy, az = h == 0 ? hz : w[2] - hz;
-    const unsigned d0 = pk_bf16(ax, ay);
-    const unsigned d1 = h == 0 ? pk_bf16(az, hx) : pk_bf16(az, 0.f);
-    const unsigned d2 = h == 0 ? pk_bf16(hy, hz) : 0u;
-    return __builtin_bit_cast(bf16x8, u32x4{d0, d1, d2, 0u});
-  };
-  // A fragment (k-step s) of one of the two small 3-row images
-  auto simg = [&](int img, int s_) {
-    return __builtin_bit_cast(bf16x8, lds_f4(lds, B3_SIMG + img * SIMG_BYTES + s_ * 256, 128 * h + 16 * (lane & 7)));
-  };
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  // rows 0..2 (hi limb) + rows 3..5 (lo limb) of a 3-row product: row = (reg & 3) + 8 (reg >> 2) + 4 h
-  auto rows3 = [&](const f32x16& a, float& r0, float& r1, float& r2) {
-    const float u0 = __shfl_xor(a[0], 32, 64), u1 = __shfl_xor(a[1], 32, 64);  // rows 4, 5 sit in the other lane half
-    r0 = a[0] + a[3];
-    r1 = a[1] + u0;
-    r2 = a[2] + u1;   // (valid in the half-0 lanes: they hold rows 0..3 and receive rows 4, 5)
-  };
-
-  // Epilogue pair (tb, rp) of a forward FiLM layer whose rows sit at lane base FB: sin(phi) -> next limb set NH,
-  // cos(phi) -> BANK.  REQ: requester of this layer's rows; NEXT: requester of the rows of whatever epilogue follows.
-#define OI_FWD_EPI(FB, NH, BANK, NEXT)                                                                     \
-  [&](int tb, int rp) {                                                                                    \
-    const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);                                                    \
-    const Rows& R = rw[g & 3];                                                                             \
-    if (k == 0) {                                                                                          \
-      if (g + 2 < 16) {                                                                                    \
-        REQ_AB(FB)(g + 2);                                                                                 \
-      } else {                                                                                             \
-        NEXT(g + 2 - 16);                                                                                  \
-      }                                                                                                    \
-    }                                                                                                      \
-    const float r0 = reduce(fmaf(R.a[k], acc[tb][2 * rp], R.b[k]));                                        \
-    const float r1 = reduce(fmaf(R.a[k + 1], acc[tb][2 * rp + 1], R.b[k + 1]));                            \
-    NH[2 * tb + (rp >> 2)][rp & 3] = pk_bf16(__builtin_amdgcn_sinf(r0), __builtin_amdgcn_sinf(r1));        \
-    BANK[g][k >> 1] = to_acc_u(pk_f16(__builtin_amdgcn_cosf(r0), __builtin_amdgcn_cosf(r1)));              \
-  }
-  // Epilogue pair of the transposed product of layer l: V_{l-1} = g_l * G_{l-1} * cos(phi_{l-1}) -> limb set NH; the cosines
-  // come from BANK (layer l - 1), the G rows of layer l - 1 sit at FB.  (acc * G is formed by an instruction the compiler
-  // knows before the asm multiply reads it: see mul_lo.)
-#define OI_REV_EPI(FB, BANK, NH, NEXT)                                                                     \
-  [&](int tb, int rp) {                                                                                    \
-    const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);                                                    \
-    const Rows& R = rw[g & 3];                                                                             \
-    if (k == 0) {                                                                                          \
-      if (g + 2 < 16) {                                                                                    \
-        REQ_G(FB)(g + 2);                                                                                  \
-      } else {                                                                                             \
-        NEXT(g + 2 - 16);                                                                                  \
-      }                                                                                                    \
-    }                                                                                                      \
-    const unsigned c2 = from_acc_u(BANK[g][k >> 1]);                                                       \
-    const float v0 = mul_lo(acc[tb][2 * rp] * R.c[k], c2), v1 = mul_hi(acc[tb][2 * rp + 1] * R.c[k + 1], c2); \
-    NH[2 * tb + (rp >> 2)][rp & 3] = pk_bf16(v0, v1);                                                      \
-  }
-
-  const int F0 = film_base(0), F1 = film_base(1), F2 = film_base(2), F3 = film_base(3), F4 = film_base(4),
-            F5 = film_base(5), F6 = film_base(6), F7 = film_base(7), F8 = film_base(8), F9 = film_base(9);
-
-  // ================= forward, layers 0..7 =================
-#if OI_B3_MFMA_EDGES
-  {  // layer 0 (K = 3) on the matrix cores: one MFMA per output block, then the ordinary forward epilogue
-    REQ_AB(F0)(0);
-    REQ_AB(F0)(1);
-    const bf16x8 bp = frag3_b(px, py, pz);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag3_a(B3_TABS + H_TAB0 * 4, t), bp, zero16, 0, 0, 0);
-    auto e0 = OI_FWD_EPI(F0, AH, P0, REQ_AB(F1));
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int rp = 0; rp < 8; ++rp) {
-        e0(t, rp);
-        if (rp & 1) __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
-#else
-  layer0(AH);
-  REQ_AB(F1)(0);
-  REQ_AB(F1)(1);
-#endif
-  B3_T(0);
-  ring_sync_b<2 * DMA_PER_IMAGE>();  // image 0 resident (1 and 2 may still be in flight)
-  B3_T(2);
-  prefetch(3);
-  auto e1 = OI_FWD_EPI(F1, BH, P1, REQ_AB(F2));
-  stream_layer_b(lds, lay(0), AH, acc, NoTailB(), e1);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(4);
-  auto e2 = OI_FWD_EPI(F2, AH, P2, REQ_AB(F3));
-  stream_layer_b(lds, lay(1), BH, acc, e1, e2);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(5);
-  auto e3 = OI_FWD_EPI(F3, BH, P3, REQ_AB(F4));
-  stream_layer_b(lds, lay(2), AH, acc, e2, e3);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(6);
-  auto e4 = OI_FWD_EPI(F4, AH, P4, REQ_AB(F5));
-  stream_layer_b(lds, lay(3), BH, acc, e3, e4);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(7);
-  auto e5 = OI_FWD_EPI(F5, BH, P5, REQ_AB(F6));
-  stream_layer_b(lds, lay(4), AH, acc, e4, e5);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(8);
-  // layer 7's epilogue needs four rows per group: A7, B7, row 9 = G7 * w_sigma, w_sigma
-  auto req7 = [&](int g_) {
-    Rows& N = rw[g_ & 3];
-    N.a = ROW_A(F7, g_);
-    N.b = ROW_B(F7, g_);
-    N.c = ROW_A(F9, g_);
-    N.d = ROW_SIG(g_);
-  };
-  auto e6 = OI_FWD_EPI(F6, AH, P6, req7);
-  stream_layer_b(lds, lay(5), BH, acc, e5, e6);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(9);
-  // layer 7: features a8 = sin(phi7) -> limb set CH (+ feat_out), sdf = a8 . wsig + bsig on the fly, and the reverse
-  // sweep's first operand v7 = wsig * G7 * cos(phi7) is formed in place (cos(phi7) is never parked)
-  auto e7 = [&](int tb, int rp) {
-    const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
-    const Rows& R = rw[g & 3];
-    if (k == 0) {
-      if (g + 2 < 16) req7(g + 2);
-      else REQ_G(F6)(g + 2 - 16);
-    }
-    float sn[2], v[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float r = reduce(fmaf(R.a[k + i], acc[tb][2 * rp + i], R.b[k + i]));
-      sn[i] = __builtin_amdgcn_sinf(r);
-      fv[k + i] = sn[i];
-      sdf_part = fmaf(sn[i], R.d[k + i], sdf_part);
-      v[i] = R.c[k + i] * __builtin_amdgcn_cosf(r);
-    }
-    CH[2 * tb + (rp >> 2)][rp & 3] = pk_bf16(sn[0], sn[1]);
-    BH[2 * tb + (rp >> 2)][rp & 3] = pk_bf16(v[0], v[1]);
-    if (k == 2) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, fv), feat_rs, feat_off + grp_f0(g) * 4, 0, 0);
-  };
-  stream_layer_b(lds, lay(6), AH, acc, e6, e7);
-  B3_T(1);
-  // (16 feature stores per wave were issued behind image 9's DMA: more younger operations than the count, never fewer)
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(10);
-
-  // ================= reverse, layers 7..1 =================
-  auto r7 = OI_REV_EPI(F6, P6, AH, REQ_G(F5));   // V6 = g7 * G6 cos(phi6)
-  stream_layer_b(lds, lay(7), BH, acc, e7, r7);
-  {
-    sdf_part += __shfl_xor(sdf_part, 32, 64);  // complete since e7's last pair (inside the layer above)
-    const float sdf_v = sdf_part + *reinterpret_cast<const float*>(lds + B3_TABS + (H_SIG + C) * 4);
-    bool valid;
-    const long long pt = point_of(valid);
-    if (valid && h == 0) sdf_out[pt] = sdf_v;
-  }
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(11);
-  auto r6 = OI_REV_EPI(F5, P5, BH, REQ_G(F4));
-  stream_layer_b(lds, lay(8), AH, acc, r7, r6);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(12);
-  auto r5 = OI_REV_EPI(F4, P4, AH, REQ_G(F3));
-  stream_layer_b(lds, lay(9), BH, acc, r6, r5);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(13);
-  auto r4 = OI_REV_EPI(F3, P3, BH, REQ_G(F2));
-  stream_layer_b(lds, lay(10), AH, acc, r5, r4);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();
-  B3_T(2);
-  prefetch(14);
-  auto r3 = OI_REV_EPI(F2, P2, AH, REQ_G(F1));
-  stream_layer_b(lds, lay(11), BH, acc, r4, r3);
-  B3_T(1);
-  ring_sync_b<2 * DMA_PER_IMAGE>();  // image 12 resident; 13 and 14 in flight, nothing more to request
-  B3_T(2);
-  auto r2 = OI_REV_EPI(F1, P1, BH, REQ_G(F0));   // V1 = g2 * G1 cos(phi1)
-  stream_layer_b(lds, lay(12), AH, acc, r3, r2);
-  B3_T(1);
-  ring_sync_b<DMA_PER_IMAGE>();      // image 13 resident
-  B3_T(2);
-#if OI_B3_MFMA_EDGES
-  // transposed layer 1: V0 = g1 * G0 cos(phi0) as limbs; then d sdf/dx = W0^T V0 (K = 128 -> 3 rows) as eight MFMAs against
-  // the small image
-  auto r1 = OI_REV_EPI(F0, P0, AH, req_none);
-  stream_layer_b(lds, lay(13), BH, acc, r2, r1);
-  B3_T(1);
-  run_tail_b(r1);
-  B3_T(3);
-  float gx, gy, gz;
-  {
-    f32x16 a0 = zero16;
-#pragma unroll
-    for (int s_ = 0; s_ < 8; ++s_) {
-      const u32x4 ub = {AH[s_][0], AH[s_][1], AH[s_][2], AH[s_][3]};
-      a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(simg(0, s_), __builtin_bit_cast(bf16x8, ub), a0, 0, 0, 0);
-    }
-    rows3(a0, gx, gy, gz);
-    gx = __shfl(gx, lane & 31, 64);  // both halves of the point need the gradient (the albedo head's B fragment)
-    gy = __shfl(gy, lane & 31, 64);
-    gz = __shfl(gz, lane & 31, 64);
-  }
-#else
-  // transposed layer 1: v0 = g1 * G0 cos(phi0) stays fp32 (layer 0's transposed product, K = 128 -> 3, runs on the VALU)
-  float act[64];
-  auto r1 = [&](int tb, int rp) {
-    const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
-    const Rows& R = rw[g & 3];
-    if (k == 0 && g + 2 < 16) REQ_G(F0)(g + 2);
-    const unsigned c2 = from_acc_u(P0[g][k >> 1]);
-    act[4 * g + k] = mul_lo(acc[tb][2 * rp] * R.c[k], c2);
-    act[4 * g + k + 1] = mul_hi(acc[tb][2 * rp + 1] * R.c[k + 1], c2);
-  };
-  stream_layer_b(lds, lay(13), BH, acc, r2, r1);
-  B3_T(1);
-  run_tail_b(r1);
-  B3_T(3);
-  float gx = 0.f, gy = 0.f, gz = 0.f;
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const f32x4 w = lds_f4(lds, B3_TABS + H_TAB0 * 4 + (grp_f0(g) + k) * 16, o.h64);
-      const float v = act[4 * g + k];
-      gx = fmaf(v, w[0], gx);
-      gy = fmaf(v, w[1], gy);
-      gz = fmaf(v, w[2], gz);
-    }
-    if (g & 1) __builtin_amdgcn_sched_barrier(0);
-  }
-  gx += __shfl_xor(gx, 32, 64);
-  gy += __shfl_xor(gy, 32, 64);
-  gz += __shfl_xor(gz, 32, 64);
-#endif
-  bool valid;
-  const long long pt = point_of(valid);
-  if (valid && h == 0) {
-    grad_out[pt * 3 + 0] = gx;
-    grad_out[pt * 3 + 1] = gy;
-    grad_out[pt * 3 + 2] = gz;
-  }
-
-  {
-    // ---- albedo head: sigmoid(Wrgb sin(gv * (Wv [feat, grad] + bv) + bv') + brgb)   (fields.py:89-101)
-    ring_sync_b<0>();  // image 14 resident
-    float r0 = 0.f, r1c = 0.f, r2c = 0.f;
-    REQ_AB(F8)(0);
-    REQ_AB(F8)(1);
-#if OI_B3_MFMA_EDGES
-    // the head's three gradient columns are a ninth MFMA of every output block; its activations sin(phi_v) go on as bf16 limbs
-    // (AH: free) and rgb = Wrgb sin(phi_v) is eight MFMAs against the second small image
-    const bf16x8 bg3 = frag3_b(gx, gy, gz);
-    auto post = [&](int t, f32x16& a) { a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag3_a(B3_TABS + H_TABV * 4, t), bg3, a, 0, 0, 0); };
-    auto ec = [&](int tb, int rp) {
-      const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
-      const Rows& R = rw[g & 3];
-      if (k == 0 && g + 2 < 16) REQ_AB(F8)(g + 2);
-      const float s0 = __builtin_amdgcn_sinf(reduce(fmaf(R.a[k], acc[tb][2 * rp], R.b[k])));
-      const float s1 = __builtin_amdgcn_sinf(reduce(fmaf(R.a[k + 1], acc[tb][2 * rp + 1], R.b[k + 1])));
-      AH[2 * tb + (rp >> 2)][rp & 3] = pk_bf16(s0, s1);
-    };
-    B3_T(5);
-    stream_layer_b(lds, lay(14), CH, acc, NoTailB(), ec, post);
-    B3_T(1);
-    run_tail_b(ec);
-    {
-      f32x16 a0 = zero16;
-#pragma unroll
-      for (int s_ = 0; s_ < 8; ++s_) {
-        const u32x4 ub = {AH[s_][0], AH[s_][1], AH[s_][2], AH[s_][3]};
-        a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(simg(1, s_), __builtin_bit_cast(bf16x8, ub), a0, 0, 0, 0);
-      }
-      rows3(a0, r0, r1c, r2c);
-    }
-    B3_T(3);
-#else
-    f32x4 w0, w1, w2;
-    auto ec = [&](int tb, int rp) {
-      const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
-      const Rows& R = rw[g & 3];
-      if (k == 0) {
-        if (g + 2 < 16) REQ_AB(F8)(g + 2);
-        w0 = lds_f4(lds, B3_TABS + (H_RGB + 0 * C + grp_f0(g)) * 4, o.h16);
-        w1 = lds_f4(lds, B3_TABS + (H_RGB + 1 * C + grp_f0(g)) * 4, o.h16);
-        w2 = lds_f4(lds, B3_TABS + (H_RGB + 2 * C + grp_f0(g)) * 4, o.h16);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const f32x4 w = lds_f4(lds, B3_TABS + H_TABV * 4 + (grp_f0(g) + k + i) * 16, o.h64);
-        const float u = acc[tb][2 * rp + i] + fmaf(gz, w[2], fmaf(gy, w[1], gx * w[0]));
-        const float sn = __builtin_amdgcn_sinf(reduce(fmaf(R.a[k + i], u, R.b[k + i])));
-        r0 = fmaf(sn, w0[k + i], r0);
-        r1c = fmaf(sn, w1[k + i], r1c);
-        r2c = fmaf(sn, w2[k + i], r2c);
-      }
-    };
-    B3_T(5);
-    stream_layer_b(lds, lay(14), CH, acc, NoTailB(), ec);
-    B3_T(1);
-    run_tail_b(ec);
-    B3_T(3);
-    r0 += __shfl_xor(r0, 32, 64);
-    r1c += __shfl_xor(r1c, 32, 64);
-    r2c += __shfl_xor(r2c, 32, 64);
-#endif
-    if (valid && h == 0 && rgb_out != nullptr) {
-      const float* brgb = reinterpret_cast<const float*>(lds + B3_TABS + (H_RGB + 3 * C) * 4);
-      rgb_out[pt * 3 + 0] = oi::sigmoidf_(r0 + brgb[0]);
-      rgb_out[pt * 3 + 1] = oi::sigmoidf_(r1c + brgb[1]);
-      rgb_out[pt * 3 + 2] = oi::sigmoidf_(r2c + brgb[2]);
-    }
-  }
-#ifdef OI_B3_PROF
-  B3_T(5);
-  if (lane == 0) {
-    unsigned long long* pr = oi_prof3b[(blockIdx.x * 4 + wave) & 1023];
-    for (int i = 0; i < 6; ++i) atomicAdd(&pr[i], pacc[i]);
-    atomicAdd(&pr[6], __builtin_readcyclecounter() - tstart);
-    atomicAdd(&pr[7], 1ull);
-    atomicAdd(&pr[8], __builtin_readcyclecounter() - t_entry);  // with [9]: the shader clock in the kernel
-    atomicAdd(&pr[9], __builtin_amdgcn_s_memrealtime() - rt_entry);
-  }
-#endif
-#undef OI_FWD_EPI
-#undef OI_REV_EPI
-#undef REQ_AB
-#undef REQ_G
-#undef ROW_A
-#undef ROW_B
-#undef ROW_G
-#undef ROW_SIG
 }
 
 
@@ -1309,15 +699,6 @@ int launch_full3p(const float* pts, const char* pk, const float* gamma, const fl
   return oi::check_launch("oi_sdf_mlp_fwd(full3p)");
 }
 
-template <bool FAST>
-int launch_full3b(const float* pts, const char* pk, const float* gamma, const float* beta, float* sdf, float* grad,
-                  float* rgb, float* feat, int B, long long n, hipStream_t st) {
-  dim3 grid(oi::cdiv(n, B3_TILE), B), block(64 * B3_WAVES);
-  auto k = sdf_mlp_full3b_kernel<FAST>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, B3_LDS);
-  hipLaunchKernelGGL(k, grid, block, B3_LDS, st, pts, pk, gamma, beta, sdf, grad, rgb, feat, n);
-  return oi::check_launch("oi_sdf_mlp_fwd(full3b)");
-}
 
 }  // namespace
 
@@ -1325,16 +706,11 @@ namespace oimlp {
 
 size_t full3_bf16_scratch_bytes(int B) { return full3p_scratch(B); }
 
-// OI_BF16_PRESCALE=0 (environment, read once) keeps the round-4 kernel with shared images + FiLM rows: the same-box A/B switch
 int launch_full3_bf16(const float* pts, const void* packed, const float* gamma, const float* beta, float* sdf, float* grad,
                       float* rgb, float* feat, void* scratch, int B, long long n, int fast_trig, hipStream_t st) {
   const char* pk = reinterpret_cast<const char*>(packed);
-  static const bool prescale = [] { const char* v = getenv("OI_BF16_PRESCALE"); return !(v && v[0] == '0'); }();
-  if (prescale)
-    return fast_trig ? launch_full3p<true>(pts, pk, gamma, beta, sdf, grad, rgb, feat, scratch, B, n, st)
-                     : launch_full3p<false>(pts, pk, gamma, beta, sdf, grad, rgb, feat, scratch, B, n, st);
-  return fast_trig ? launch_full3b<true>(pts, pk, gamma, beta, sdf, grad, rgb, feat, B, n, st)
-                   : launch_full3b<false>(pts, pk, gamma, beta, sdf, grad, rgb, feat, B, n, st);
+  return fast_trig ? launch_full3p<true>(pts, pk, gamma, beta, sdf, grad, rgb, feat, scratch, B, n, st)
+                   : launch_full3p<false>(pts, pk, gamma, beta, sdf, grad, rgb, feat, scratch, B, n, st);
 }
 
 }  // namespace oimlp

@@ -107,18 +107,7 @@ __device__ __forceinline__ float wave_scan_add(float v, int lane) {
 //                    only re-read miss, a non-temporal LOAD tells the caches the line is dead after its last use;
 //   backward sweep  (46 slots, 25 GB, most of it consumed by the NEXT kernel):  both nt 68.0 it/s of training,
 //                    loads only 67.5, stores only 67.5, neither 66.6.
-#ifndef OI_FWD_NT_LD
-#define OI_FWD_NT_LD 2
-#endif
-#ifndef OI_FWD_NT_ST
-#define OI_FWD_NT_ST 0
-#endif
-#ifndef OI_BWD_NT_LD
-#define OI_BWD_NT_LD 2
-#endif
-#ifndef OI_BWD_NT_ST
-#define OI_BWD_NT_ST 2
-#endif
+constexpr int FWD_NT_LD = 2, FWD_NT_ST = 0, BWD_NT_LD = 2, BWD_NT_ST = 2;
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 template <int AUX>
 __device__ __forceinline__ void buffer_store_b128(u32x4_t v, __amdgpu_buffer_rsrc_t rs, int voff, int uoff) {

@@ -133,6 +133,17 @@ int oi_sdf_mlp_fwd_ex(const float* pts, const void* packed, const float* gamma, 
                       float* sdf, float* grad, float* rgb, float* feat, void* scratch,
                       int B, long long n_per_elem, int prec, int fast_trig, int flags, oi_stream_t stream);
 
+/* The sdf-only pass of oi_sdf_mlp_fwd on a LATTICE: the points are not read from memory but computed from their index.
+ * Replaces the point source of the reference's extract_fields (src/third_party/neus/models/renderer.py:15-31: torch.meshgrid
+ * chunks of 64^3 points, each handed to query_func = -sdf_network.sdf(pts, z, w), renderer.py:480-486).
+ *   xs [nx], ys [ny], zs [nz]: the axis coordinates (the caller fills them with torch.linspace, as renderer.py:17-19);
+ *   out [B][nx][ny][nz] = scale * sdf(xs[ix], ys[iy], zs[iz]) of batch element b (gamma / beta row b); scale = -1 is the
+ *   reference's u.  nx * ny * nz < 2^31.  Every precision / fast_trig of the sdf-only pass; per point the arithmetic is that
+ *   of oi_sdf_mlp_fwd with grad == NULL, so the values are bit-identical to it on the same points. */
+int oi_sdf_lattice(const void* packed, const float* gamma, const float* beta, int B, const float* xs, const float* ys,
+                   const float* zs, int nx, int ny, int nz, float scale, float* out, int prec, int fast_trig,
+                   oi_stream_t stream);
+
 /* Backward of oi_sdf_mlp_fwd w.r.t. every parameter and the FiLM vectors -- including the second-order
  * terms that arise because d sdf/dx is a forward output (the reference: autograd with create_graph=True
  * through fields.py:104-122, backward at gan_pose_trainer.py:141).  Upstream gradients g_sdf [B*n],
@@ -711,6 +722,27 @@ int oi_disc_large_pack(const float* const* w_blocks, const float* w_head, const 
 size_t oi_disc_large_workspace_bytes(const int* chans, int n_blocks, int out_dim, int B, int H);
 int oi_disc_fwd_large(const float* x, const float* w1, const void* packed, const float* bhead, void* workspace, size_t workspace_bytes,
                       float* logits, const int* chans, int n_blocks, int out_dim, int B, int H, float slope, oi_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh extraction: marching cubes on a dense field (csrc/mesh.hip).  Replaces mcubes.marching_cubes(u,
+ * threshold) (PyMCubes, on the host) in the reference's extract_geometry (src/third_party/neus/models/renderer.py:33-41).
+ *   field [nx][ny][nz] fp32 (z fastest), every axis 2..1024 (OI_ERR_INVALID_ARG otherwise).  A lattice point is inside iff
+ *   u > threshold.  Case table csrc/mc_tables.h (generated by tools/gen_mc_tables.py: crack-free face rule, triangles
+ *   counter-clockwise seen from the outside, u <= threshold).  Deterministic: no atomics decide the output order.
+ * oi_mc_workspace_bytes: the workspace of one call pair (about 12 B per lattice point: the per-(point, axis) vertex-id map);
+ *   0 for a lattice outside the limits.
+ * oi_mc_count: counts per 4096-point chunk, scans them, and copies the totals to the HOST array totals[3] = (n_vertices,
+ *   n_triangles, n_nonfinite) -- it synchronises `stream` once (the outputs' sizes).  A field with a non-finite value fails
+ *   with OI_ERR_INVALID_ARG (totals still filled), as does a mesh of 2^31 vertices or more.
+ * oi_mc_emit: after oi_mc_count on the same field / threshold / workspace: vertices [n_vertices][3] in index space (point +
+ *   t along the crossing axis, t = (threshold - u0) / (u1 - u0), PyMCubes' interpolation), ordered by the owning point's linear
+ *   index then axis x, y, z; triangles [n_triangles][3] int32 vertex ids ordered by cell linear index then table order.
+ *   n_vertices / n_triangles are the sizes from oi_mc_count (nothing is written past them). */
+size_t oi_mc_workspace_bytes(int nx, int ny, int nz);
+int oi_mc_count(const float* field, int nx, int ny, int nz, float threshold, void* workspace, size_t workspace_bytes,
+                long long* totals, oi_stream_t stream);
+int oi_mc_emit(const float* field, int nx, int ny, int nz, float threshold, void* workspace, size_t workspace_bytes,
+               float* vertices, long long n_vertices, int* triangles, long long n_triangles, oi_stream_t stream);
 
 #ifdef __cplusplus
 }

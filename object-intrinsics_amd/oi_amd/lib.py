@@ -148,6 +148,11 @@ _SIGS = {
     "oi_multi_rmsprop": (_i, [_vp, _i, _f, _f, _f, _vp]),
     "oi_multi_lerp": (_i, [_vp, _i, _f, _vp]),
     "oi_multi_copy": (_i, [_vp, _i, _vp]),
+    # mesh extraction: the reference's extract_fields point source (renderer.py:15-31) and mcubes.marching_cubes (:33-41)
+    "oi_sdf_lattice": (_i, [_vp] * 3 + [_i] + [_vp] * 3 + [_i] * 3 + [_f, _vp, _i, _i, _vp]),
+    "oi_mc_workspace_bytes": (_sz, [_i] * 3),
+    "oi_mc_count": (_i, [_vp] + [_i] * 3 + [_f, _vp, _sz, ctypes.POINTER(_ll), _vp]),
+    "oi_mc_emit": (_i, [_vp] + [_i] * 3 + [_f, _vp, _sz, _vp, _ll, _vp, _ll, _vp]),
 }
 
 # entry points added by later source files (backward kernels); bound when present in the .so

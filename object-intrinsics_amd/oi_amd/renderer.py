@@ -9,6 +9,7 @@ shapes in the dict `render()` returns.  Every stage is a HIP kern
     SDF + d sdf/dx + albedo    oi_sdf_mlp_fwd        (:241-261; ONE pass instead of the reference's three)
     compositing (+ Phong maps) oi_composite_fwd      (:266-311, 338; generator.py:80-174)
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -108,6 +109,24 @@ class NeuSRenderer:
                                 outputs=("weights", "cdf", "inside_sphere", "pts_norm", "weight_sum", "weight_max",
                                          "color_fine", "reduce4"))
         return assemble_render_dict(s, c, self.deviation_network.variance, background_rgb)
+
+    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, siren_network=None, z=None, w=None):
+        """renderer.py:475-492: the mesh of u = -sdf at `threshold` -> numpy (V, 3) float64 world-space vertices, (F, 3) int64
+        triangles.  The field comes from one lattice launch (oi_sdf_lattice: no points materialised, no query_func) and the
+        marching cubes run on the GPU (oi_mc_count / oi_mc_emit)."""
+        from . import mesh
+        if siren_network is not None:
+            raise NotImplementedError("siren_network is not on the path (as in render())")
+        if z is None and w is None:
+            raise ValueError("extract_geometry: ShapeNetwork.sdf needs a latent -- pass z or w")
+        B = (w if w is not None else z).shape[0]
+        if B != 1:
+            raise ValueError(f"extract_geometry: one latent expected, got a batch of {B} (the reference's sdf(pts, z) would "
+                             "split the lattice across them)")
+        u = mesh.sdf_lattice(self.pack, bound_min, bound_max, resolution, z=z, w=w, scale=-1.0)[0]
+        vertices, triangles = mesh.marching_cubes(u, threshold)
+        vertices = vertices.cpu().numpy().astype(np.float64)
+        return mesh.to_world(vertices, bound_min, bound_max, resolution), triangles.cpu().numpy().astype(np.int64)
 
 
 class _RenderScalars(torch.autograd.Function):

@@ -381,7 +381,8 @@ int oi_render_stats(const float* block_partials, int n_blocks, long long N, int 
  * per-ray [N] / [N][3] for the maps, g_weights [N][T], g_reduce4 [4] (device; grads of the three global sums).
  * Results: d_sdf [N][T], d_grad [N][T][3], d_rgb [N][T][3] (written), and accumulated with atomics into
  * caller-zeroed d_variance [1], d_light [3] (param_ambient, param_specular, param_shininess),
- * d_light_dir [B][3] (w.r.t. the normalised direction). */
+ * d_light_dir [B][3] (w.r.t. the normalised direction).  T <= 1280 (the launch holds 3 floats per sample of its 4 rays in
+ * 60 KiB of LDS; OI_ERR_INVALID_ARG beyond, nothing written) -- the forward has no such limit. */
 typedef struct oi_composite_grads {
   const float* g_weights;
   const float* g_weight_sum;

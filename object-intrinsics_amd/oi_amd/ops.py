@@ -161,13 +161,14 @@ def color_head_bwd(feat, normals, gamma, beta, wv, bv, wrgb, brgb, g_rgb, B):
 # ------------------------------------------------------------------------------------------
 
 def film_params(style_w, style_b, gw, gb, bw, bb, z=None, w=None):
-    """(w, gamma[B,NL,128], beta[B,NL,128]); give z (style MLP runs) or w."""
+    """(w, gamma[B,NL,128], beta[B,NL,128]); give z (style MLP runs) or w.  Without FiLM heads (gw None: the style MLP
+    alone) gamma and beta are None -- the kernel writes none."""
     L = _l.load()
     assert (z is None) != (w is None)
     src = z if z is not None else w
     B, NL = src.shape[0], (gw.shape[0] if gw is not None else 0)
     w_out = _new(src, B, 64) if w is None else _c(w)
-    gamma, beta = _new(src, B, max(NL, 1), 128), _new(src, B, max(NL, 1), 128)
+    gamma, beta = (_new(src, B, NL, 128), _new(src, B, NL, 128)) if NL else (None, None)
     z_ = _c(z)
     args = [_c(style_w), _c(style_b), z_, w_out, _c(gw), _c(gb), _c(bw), _c(bb)]
     _l.check(L.oi_film_params(*[_p(a) for a in args], _p(gamma), _p(beta), B, NL, _stream()), "oi_film_params")
@@ -190,7 +191,7 @@ def prep_render(b2w, w2b, c2b, offs, bg, kinv, R, S, jitter, light_direction, fi
         dst[:B] = a
     NL = film_P["gw"].shape[0]
     N = B * R * R
-    f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+    f = lambda *sh: _new(z, *sh)
     out = {"pose": f(B * 53), "rays_o": f(B, R, R, 3), "rays_d": f(B, R, R, 3), "near": f(N, 1), "far": f(N, 1),
            "light_dir": f(B, 3), "z_coarse": f(N, S), "pts_coarse": f(N, S, 3), "w": f(B, 64), "gamma": f(B, NL, 128),
            "beta": f(B, NL, 128)}
@@ -213,12 +214,12 @@ def film_params_bwd(d_gamma, d_beta, w, gw, bw, style_w=None, style_b=None, z=No
     L = _l.load()
     B, NL = d_gamma.shape[0], d_gamma.shape[1]
     d_gamma, d_beta, w = _c(d_gamma), _c(d_beta), _c(w)
-    out = {"d_gw": torch.empty_like(gw), "d_gb": _new(w, NL, 128), "d_bw": torch.empty_like(bw), "d_bb": _new(w, NL, 128),
+    out = {"d_gw": _new(w, *gw.shape), "d_gb": _new(w, NL, 128), "d_bw": _new(w, *bw.shape), "d_bb": _new(w, NL, 128),
            "d_w": _zeros_split(w.device, w.shape)[0] if d_w_in is None else d_w_in.contiguous().clone()}
     if z is not None:
         out["d_style_w"], out["d_style_b"] = _zeros_split(w.device, style_w.shape, style_b.shape)
         if want_dz:
-            out["d_z"] = torch.empty_like(z)
+            out["d_z"] = _new(z, *z.shape)
     _l.check(L.oi_film_params_bwd(_p(d_gamma), _p(d_beta), _p(w), _p(_c(gw)), _p(_c(bw)), _p(out["d_gw"]), _p(out["d_gb"]),
                                   _p(out["d_bw"]), _p(out["d_bb"]), _p(out["d_w"]), _p(_c(style_w)), _p(_c(style_b)),
                                   _p(_c(z)), _p(out.get("d_style_w")), _p(out.get("d_style_b")), _p(out.get("d_z")), B, NL,
@@ -620,7 +621,7 @@ class GradSink:
 def lrelu_mask_mul(v, ref, slope):
     L = _l.load()
     v, ref = _c(v), _c(ref)
-    out = torch.empty_like(v)
+    out = _new(v, *v.shape)
     _l.check(L.oi_lrelu_mask_mul(_p(v), _p(ref), _p(out), v.numel(), float(slope), _stream()), "oi_lrelu_mask_mul")
     return out
 
@@ -733,7 +734,7 @@ def weighted_sum_fwd(terms, weights):
     n = len(terms)
     ptrs = (ctypes.c_void_p * n)(*[_p(t).value for t in terms])
     ws = (ctypes.c_float * n)(*[float(w) for w in weights])
-    out = torch.empty((), dtype=torch.float32, device=terms[0].device)
+    out = _new(terms[0])
     _l.check(L.oi_weighted_sum_fwd(ptrs, ws, n, _p(out), _stream()), "oi_weighted_sum_fwd")
     return out
 
@@ -743,7 +744,7 @@ def weighted_sum_bwd(g_out, weights, device):
     L = _l.load()
     n = len(weights)
     ws = (ctypes.c_float * n)(*[float(w) for w in weights])
-    g = torch.empty(n, dtype=torch.float32, device=device)
+    g = _new(g_out, n)
     _l.check(L.oi_weighted_sum_bwd(_p(g_out), ws, n, _p(g), _stream()), "oi_weighted_sum_bwd")
     return g
 
@@ -755,9 +756,9 @@ def gan_losses_bwd(g_total, d_real, d_fake, pose, gx, aux_w, reg_w, want_real, w
     if out is not None:
         g_real, g_fake, g_gx = out
     else:
-        g_real = torch.empty_like(d_real) if want_real else None
-        g_fake = torch.empty_like(d_fake) if want_fake else None
-        g_gx = torch.empty_like(gx) if want_gx else None
+        g_real = _new(d_real, *d_real.shape) if want_real else None
+        g_fake = _new(d_fake, *d_fake.shape) if want_fake else None
+        g_gx = _new(gx, *gx.shape) if want_gx else None
     _l.check(L.oi_gan_losses_bwd(_p(g_total), _p(d_real), _p(d_fake), _p(pose), _p(gx), _p(aux_w), float(reg_w), _p(g_real),
                                  _p(g_fake), _p(g_gx), B, K, N, _stream()), "oi_gan_losses_bwd")
     return g_real, g_fake, g_gx
@@ -994,7 +995,7 @@ def ada_geom_sep_host(x, theta_np, f12, margins):
     assert th.shape == (B, 2, 3) and f12.numel() == 12
     if np.any(th[:, 0, 1] != 0) or np.any(th[:, 1, 0] != 0):   # (the kernel does not read them: it would silently drop a rotation)
         raise ValueError("ada_geom_sep_host: a sampling matrix with off-diagonal entries (rotation) -- use ada_geom_fwd")
-    y = torch.empty_like(x)
+    y = _new(x, *x.shape)
     _l.check(_l.load().oi_ada_geom_sep_fwd(_p(x), None, th.ctypes.data_as(_vp), _p(f12), _p(y), B, C, H, W, mx0, mx1, my0, my1,
                                            _stream()), "oi_ada_geom_sep_fwd")
     return y
@@ -1005,7 +1006,7 @@ def ada_geom_adj_sep(gy, theta, f12, margins):
     gy, theta, f12 = _c(gy), _c(theta), _c(f12)
     B, C, H, W = gy.shape
     mx0, my0, mx1, my1 = margins
-    gx = torch.empty_like(gy)
+    gx = _new(gy, *gy.shape)
     _l.check(_l.load().oi_ada_geom_sep_adj(_p(gy), _p(theta), None, _p(f12), _p(gx), B, C, H, W, mx0, mx1, my0, my1, _stream()),
              "oi_ada_geom_sep_adj")
     return gx
@@ -1019,7 +1020,7 @@ def ada_geom_fwd(x, theta, f12, margins, axis_aligned=False):
     B, C, H, W = x.shape
     mx0, my0, mx1, my1 = margins
     assert f12.numel() == 12 and theta.shape == (B, 2, 3)
-    y = torch.empty_like(x)
+    y = _new(x, *x.shape)
     if axis_aligned and ADA_SEPARABLE and B <= 65535 and L.oi_ada_geom_sep_supported(C, H, W):
         _l.check(L.oi_ada_geom_sep_fwd(_p(x), _p(theta), None, _p(f12), _p(y), B, C, H, W, mx0, mx1, my0, my1, _stream()),
                  "oi_ada_geom_sep_fwd")

@@ -10,8 +10,10 @@ import torch
 import oi_oracle as O
 O_ref = O
 from conftest import load_golden, maxdiff, sub_sd, record_margin
+from helpers.guarded import guarded_ops  # noqa: F401  (fixture)
 
-pytestmark = pytest.mark.gpu
+# every output of oi_amd.ops is a guarded, poisoned arena view (tests/helpers/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_ops")]
 
 
 def dev(d):
@@ -129,7 +131,8 @@ def test_sdf_mlp_ragged_tiles(ops, packed_all, sdf_sd, col_sd, n, mode):
     rgb_o = O.color_head(col_sd, feat_o, grad_o, w)
     _, gamma, beta = ops.film_params(P["style_w"], P["style_b"], P["gw"], P["gb"], P["bw"], P["bb"], w=w.cuda())
     prec = {"f32": 0, "bf16": 2, "f16x3": 4}[mode]
-    # guard bands around every output: a tail lane that stored past its element would land here
+    # guard bands around every output (the module's guarded_ops fixture): a tail lane that stored past its element would land
+    # there, and an element of a skipped tile would still hold the poison word
     sdf, grad, rgb, feat, _ = ops.sdf_mlp_fwd(pts.cuda(), packs[mode], gamma, beta, B, prec, fast_trig=(mode == "bf16"),
                                               want_grad=True, want_rgb=True, want_feat=True)
     t_sdf, t_grad, t_rgb = RAGGED_TOL[mode]

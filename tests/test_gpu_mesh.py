@@ -10,8 +10,10 @@ import torch
 import oi_oracle as O
 from conftest import GOLDEN
 from helpers import mc_numpy as M
+from helpers.guarded import guarded_ops  # noqa: F401  (fixture)
 
-pytestmark = pytest.mark.gpu
+# every output of oi_amd.ops is a guarded, poisoned arena view (tests/helpers/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_ops")]
 
 KW = dict(D=8, W=128, input_ch=3, input_ch_views=3, style_dim=64)
 

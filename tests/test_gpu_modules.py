@@ -8,8 +8,10 @@ import torch
 
 import oi_oracle as O
 from conftest import GOLDEN, load_golden, maxdiff, sub_sd, record_margin
+from helpers.guarded import guarded_ops  # noqa: F401  (fixture)
 
-pytestmark = pytest.mark.gpu
+# every output of oi_amd.ops is a guarded, poisoned arena view (tests/helpers/guarded.py)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("guarded_ops")]
 NET_KW = dict(D=8, W=128, input_ch=3, input_ch_views=3, style_dim=64)
 SDF_NPZ = os.path.join(GOLDEN, "weights_sdf.npz")
 

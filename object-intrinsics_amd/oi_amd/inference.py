@@ -1,4 +1,4 @@
-"""Inference driver of the path: camera walks and latent walks at a resolution / depth multiple of the
+"""Inference driver of the path: camera walks, latent walks and light walks at a resolution / depth multiple of the
 training configuration, rendered in ray chunks (the second caller of Generator.forward in the reference:
 scripts/test.py:231-244, 274-281; src/utils/test.py:55-66, 131-155).  Returns frame tensors; writing
 mp4/html is the reference's visualisation stack and out of scope."""
@@ -92,3 +92,48 @@ def camera_walk(gen, z, b2w0, n_frames=128, **kw):
 def latent_walk(gen, z0, z1, b2w, n_frames=128, **kw):
     ts = torch.linspace(0, 1, n_frames)
     return render_frames(gen, [slerp(z0, z1, t) for t in ts], [b2w] * n_frames, **kw)
+
+
+def light_walk_directions(direction, n_frames, axis=(0.0, -1.0, 0.0)):
+    """Unit world-frame light directions turning through 360 degrees about `axis` (rotation_walk's axis convention), frame 0
+    = direction / |direction|.  -> (n_frames, 3) float64 numpy."""
+    from scipy.spatial.transform import Rotation as R
+    d = np.asarray(direction, dtype=np.float64).reshape(3)
+    d = d / np.linalg.norm(d)
+    ax = np.asarray(axis, dtype=np.float64)
+    return np.stack([R.from_rotvec(ax * (2 * math.pi * i / n_frames)).as_matrix() @ d for i in range(n_frames)])
+
+
+def _frames(cap, out, keys, n):
+    """relight's (L, 1, C, H, W) maps and the capture's light-independent maps -> render_frames' {key: (n, C, H, W)}."""
+    frames = {}
+    for k in keys:
+        frames[k] = out[k][:, 0] if k in out else cap.maps[k][0].expand(n, *cap.maps[k].shape[1:])
+    return frames
+
+
+def relight_frames(gen, z, b2w, lights, keys=("image", "mask", "normal_map", "shading_map"), bg=None, max_ray_batch=None):
+    """One view (z (z_dim,), b2w (4, 4)) under each of `lights` (oi_amd.relight.Light): one capture, then relight launches
+    instead of a render per light.  -> {key: (len(lights), C, H, W)}, as render_frames; the light-independent keys
+    (oi_amd.relight.CAPTURE_MAP_KEYS) are the capture's maps, the same for every frame."""
+    from . import relight as RL
+    cap = RL.capture(gen, z=z[None], b2w=b2w[None], bg=bg, max_ray_batch=max_ray_batch)
+    lights = list(lights)
+    unknown = [k for k in keys if k not in RL.MAP_KEYS and k not in RL.CAPTURE_MAP_KEYS]
+    if unknown:
+        raise ValueError(f"relight_frames: keys {unknown} are neither relit maps {RL.MAP_KEYS} nor capture maps "
+                         f"{RL.CAPTURE_MAP_KEYS}")
+    out = RL.relight(cap, lights, outputs=tuple(k for k in keys if k in RL.MAP_KEYS))
+    return _frames(cap, out, keys, len(lights))
+
+
+def light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), **kw):
+    """The light walk of scripts/test.py:256-258, whose function the reference never shipped: the trained light's direction
+    turns through 360 degrees about `axis` (rotation_walk's convention) while the view stays; colours and shininess stay
+    the trained ones.  Frame 0 is the trained light itself.  One capture, then one relight launch per 256 frames.
+    -> {key: (n_frames, C, H, W)} as render_frames (keyword arguments: relight_frames')."""
+    from .relight import Light
+    base = Light.from_module(gen.light)
+    dirs = light_walk_directions(base.direction, n_frames, axis)
+    lights = [base] + [base.replace(direction=tuple(d)) for d in dirs[1:]]
+    return relight_frames(gen, z, b2w, lights, **kw)

@@ -1,4 +1,4 @@
-"""ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h).
+"""ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h and include/oi_relight.h).
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -44,6 +44,16 @@ class PrepParams(ctypes.Structure):
                                     "pose_out", "rays_o", "rays_d", "near_", "far_", "light_dir", "z_coarse", "pts_coarse",
                                     "w_out", "gamma", "beta")] +
                 [("jitter_normal", _i), ("f3_packed", _vp), ("f3_blob", _vp)])
+
+
+RELIGHT_LIGHT_FLOATS, RELIGHT_MAX_LIGHTS = 16, 256
+
+
+class RelightParams(ctypes.Structure):
+    """Mirror of `oi_relight_params` (include/oi_relight.h)."""
+    _fields_ = ([(n, _vp) for n in ("weights", "grad", "rgb", "mid_z", "rays_o", "rays_d", "w2b", "lights", "bg")] +
+                [("N", _ll), ("T", _i), ("B", _i), ("L", _i)] +
+                [(n, _vp) for n in ("image", "image_no_bg", "shading", "diffuse", "specular")])
 
 
 class CompositeGrads(ctypes.Structure):
@@ -155,6 +165,12 @@ _SIGS = {
     "oi_mc_emit": (_i, [_vp] + [_i] * 3 + [_f, _vp, _sz, _vp, _ll, _vp, _ll, _vp]),
 }
 
+# include/oi_relight.h: relighting of a captured render (no reference counterpart, so not in oi_hip.h and not in _SIGS,
+# which lists exactly what oi_hip.h declares: tests/test_cabi_cpu.py)
+_RELIGHT_SIGS = {
+    "oi_relight_fwd": (_i, [ctypes.POINTER(RelightParams), _vp]),
+}
+
 # entry points added by later source files (backward kernels); bound when present in the .so
 _OPTIONAL_SIGS = {}
 
@@ -165,6 +181,11 @@ class OiHipError(RuntimeError):
 
 def declared_symbols():
     return sorted(_SIGS)
+
+
+def relight_symbols():
+    """The entry points of include/oi_relight.h."""
+    return sorted(_RELIGHT_SIGS)
 
 
 def load():
@@ -185,7 +206,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python object-intrinsics_amd/build.py` (hipcc, gfx950). "
                 "oi_amd has no CPU or PyTorch fallback for its kernels.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_OPTIONAL_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_OPTIONAL_SIGS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError:

@@ -501,6 +501,47 @@ def composite_bwd(sdf, grad, rgb, dists, mid_z, rays_o, rays_d, light_dir, bg, v
     return d_sdf, d_grad, d_rgb, d_var, d_light, d_ldir
 
 
+RELIGHT_OUT = ("image", "image_no_bg", "shading", "diffuse", "specular")
+
+
+def relight_fwd(weights, grad, rgb, mid_z, rays_o, rays_d, w2b, lights, bg, B, outputs=("image",), out=None):
+    """Shades and composites a captured render under L lights in one launch (oi_relight_fwd, include/oi_relight.h).
+    weights / mid_z (N, T), grad / rgb (N, T, 3), rays_o / rays_d (N, 3), w2b (B, 4, 4), lights (L, 16) (oi_amd.relight.
+    stack_lights), bg (B, 3) or None.  -> {name: (L, B, 3, N / B)} for each name of `outputs` (RELIGHT_OUT).
+    `out`: {name: (L, B, 3, N / B) contiguous tensor} to write into instead of new buffers."""
+    L_ = _l.load()
+    N, T = weights.shape
+    nl = lights.shape[0]
+    for name in outputs:
+        if name not in RELIGHT_OUT:
+            raise ValueError(f"relight_fwd: unknown output {name!r} (one of {RELIGHT_OUT})")
+    if nl < 1 or nl > _l.RELIGHT_MAX_LIGHTS or tuple(lights.shape[1:]) != (_l.RELIGHT_LIGHT_FLOATS,):
+        raise ValueError(f"relight_fwd: lights {tuple(lights.shape)}, expected (L, {_l.RELIGHT_LIGHT_FLOATS}) with 1 <= L <= "
+                         f"{_l.RELIGHT_MAX_LIGHTS}")
+    if B < 1 or N % B != 0:
+        raise ValueError(f"relight_fwd: {N} rays cannot be split over {B} elements")
+    P = _l.RelightParams()
+    keep = []
+    for name, t in (("weights", weights), ("grad", grad), ("rgb", rgb), ("mid_z", mid_z), ("rays_o", rays_o),
+                    ("rays_d", rays_d), ("w2b", w2b), ("lights", lights), ("bg", bg)):
+        t = _c(t)
+        keep.append(t)
+        setattr(P, name, _p(t))
+    P.N, P.T, P.B, P.L = N, T, B, nl
+    res = {}
+    for name in RELIGHT_OUT:
+        if name in outputs:
+            t = out.get(name) if out is not None else None
+            if t is None:
+                t = _new(weights, nl, B, 3, N // B)
+            elif tuple(t.shape) != (nl, B, 3, N // B) or not t.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError(f"relight_fwd: out[{name!r}] must be a contiguous float32 {(nl, B, 3, N // B)} tensor")
+            res[name] = t
+        setattr(P, name, _p(res.get(name)))
+    _l.check(L_.oi_relight_fwd(ctypes.byref(P), _stream()), "oi_relight_fwd")
+    return res
+
+
 # ------------------------------------------------------------------------------------------
 # discriminator side
 # ------------------------------------------------------------------------------------------

@@ -137,3 +137,53 @@ def light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), **kw):
     dirs = light_walk_directions(base.direction, n_frames, axis)
     lights = [base] + [base.replace(direction=tuple(d)) for d in dirs[1:]]
     return relight_frames(gen, z, b2w, lights, **kw)
+
+
+@torch.no_grad()
+def shade_vertices(positions, normals, albedo, light, eye=None):
+    """Phong colour (V, 3) of mesh vertices under `light` (oi_amd.relight.Light; its direction in the mesh's own frame): each
+    vertex is a one-sample ray of weight 1 through the relighting launch (oi_relight_fwd with T = 1, one element, identity
+    frame, no background).  View direction: towards `eye` (3 floats, the mesh's frame) when given, else along the normal."""
+    from . import ops
+    from .relight import stack_lights
+    V = positions.shape[0]
+    dev = positions.device
+    if V == 0:
+        return torch.empty(0, 3, device=dev)
+    if eye is None:
+        rays_d, mid_z = -normals, torch.ones(V, 1, device=dev)
+        rays_o = positions + normals
+    else:
+        rays_o = torch.as_tensor(eye, dtype=torch.float32).to(dev).reshape(1, 3).expand(V, 3).contiguous()
+        d = positions - rays_o
+        mid_z = d.norm(dim=-1, keepdim=True)
+        rays_d = d / mid_z.clamp(min=1e-12)
+    out = ops.relight_fwd(torch.ones(V, 1, device=dev), normals.view(V, 1, 3), albedo.view(V, 1, 3), mid_z, rays_o, rays_d,
+                          torch.eye(4, device=dev)[None], stack_lights(light, dev), None, 1, outputs=("image_no_bg",))
+    return out["image_no_bg"][0, 0].t().contiguous()
+
+
+@torch.no_grad()
+def export_mesh(gen, z, path, resolution=256, refine=2, light=None, threshold=0.0, bound_min=(-1.0, -1.0, -1.0),
+                bound_max=(1.0, 1.0, 1.0), eye=None):
+    """The instance of latent z (z_dim,) or (1, z_dim) as a PLY asset at `path`: triangles, vertices on the surface, analytic
+    normals and per-vertex colours (oi_amd.mesh.extract_intrinsic_mesh; save_ply's attribute layout).  Colours are the
+    albedo, or with `light` (oi_amd.relight.Light, e.g. Light.from_module(gen.light)) the shaded colour of shade_vertices.
+    Checks the weights first (FieldPack.check: an inf / NaN weight is refused before anything is launched).
+    -> the IntrinsicMesh that was written (with `shaded` (V, 3) set when a light was given)."""
+    from . import mesh, ops
+    gen.eval()
+    pack = mesh._field_pack(gen, "export_mesh")
+    pack.check()
+    dev = gen.it.device
+    z = z.to(dev).reshape(1, -1)
+    m = mesh.extract_intrinsic_mesh(pack, z=z, resolution=resolution, threshold=threshold, bound_min=bound_min,
+                                    bound_max=bound_max, refine=refine, want_record=light is None)
+    if light is None:
+        record = m.record
+    else:
+        m.shaded = shade_vertices(m.positions, m.normals, m.albedo, light, eye)
+        record = m.record = ops.mesh_vertex_record(m.positions, m.normals, m.shaded) if len(m.positions) else \
+            torch.empty(0, mesh.RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    mesh.save_ply(path, record, m.triangles)
+    return m

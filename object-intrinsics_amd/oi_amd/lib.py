@@ -1,4 +1,4 @@
-"""ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h and include/oi_relight.h).
+"""ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h and include/oi_mesh_attr.h).
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -171,6 +171,16 @@ _RELIGHT_SIGS = {
     "oi_relight_fwd": (_i, [ctypes.POINTER(RelightParams), _vp]),
 }
 
+# include/oi_mesh_attr.h: the vertex pass of the intrinsic mesh export (no reference counterpart either)
+MESH_FLAG_NONFINITE, MESH_FLAG_SMALL_GRADIENT, MESH_FLAG_LIMIT = 1, 2, 4
+MESH_MAX_REFINE, MESH_RECORD_BYTES = 8, 27
+_MESH_ATTR_SIGS = {
+    "oi_mesh_vertex_world": (_i, [_vp, _ll] + [_vp] * 3 + [_i] * 3 + [_vp, _vp, _vp]),
+    "oi_mesh_newton": (_i, [_vp] * 4 + [_ll] + [_f] * 4 + [_vp, _vp, _vp]),
+    "oi_mesh_attr_finalize": (_i, [_vp] * 4 + [_ll, _f] + [_vp] * 5),
+    "oi_mesh_vertex_record": (_i, [_vp] * 3 + [_ll, _vp, _vp]),
+}
+
 # entry points added by later source files (backward kernels); bound when present in the .so
 _OPTIONAL_SIGS = {}
 
@@ -186,6 +196,11 @@ def declared_symbols():
 def relight_symbols():
     """The entry points of include/oi_relight.h."""
     return sorted(_RELIGHT_SIGS)
+
+
+def mesh_attr_symbols():
+    """The entry points of include/oi_mesh_attr.h."""
+    return sorted(_MESH_ATTR_SIGS)
 
 
 def load():
@@ -206,7 +221,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python object-intrinsics_amd/build.py` (hipcc, gfx950). "
                 "oi_amd has no CPU or PyTorch fallback for its kernels.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_OPTIONAL_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_OPTIONAL_SIGS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError:

@@ -4,15 +4,21 @@
     sdf_lattice      dense SDF field of a latent on a lattice   oi_sdf_lattice   (the points are never materialised)
     marching_cubes   triangle mesh of a field                   oi_mc_count + oi_mc_emit
     extract_fields / extract_geometry   the reference's functions with a caller-supplied query_func (64^3 chunks)
-    save_ply         binary little-endian PLY with numpy only
+    save_ply         binary little-endian PLY with numpy only (optionally with normals and colours)
+    vertex_attributes / extract_intrinsic_mesh   the intrinsic mesh: vertices moved onto the level set, analytic normals
+                     and albedo per vertex   oi_mesh_vertex_world + (oi_sdf_mlp_fwd + oi_mesh_newton) x refine +
+                     oi_sdf_mlp_fwd + oi_mesh_attr_finalize   (include/oi_mesh_attr.h)
 
-DESIGN section 4.10 has the table rule, the output order and the measured numbers."""
+DESIGN section 4.10 has the table rule, the output order and the measured numbers; section 4.12 the vertex pass."""
 import ctypes
+import dataclasses
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import lib as _l
+from . import ops
 from .ops import _p, _stream
 
 MAX_RESOLUTION = 1024  # per axis (oi_mc_workspace_bytes)
@@ -114,17 +120,186 @@ def extract_geometry(bound_min, bound_max, resolution, threshold, query_func):
     return to_world(vertices, bound_min, bound_max, resolution), triangles
 
 
-def save_ply(path, vertices, triangles):
-    """Binary little-endian PLY: float32 x y z per vertex, uchar count + int32 indices per face (numpy only)."""
-    v = np.ascontiguousarray(np.asarray(vertices, dtype="<f4").reshape(-1, 3))
-    t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+RECORD_DTYPE = np.dtype([("p", "<f4", (3,)), ("n", "<f4", (3,)), ("c", "u1", (3,))])   # OI_MESH_RECORD_BYTES = 27, packed
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def quantise_colours(c):
+    """float RGB -> uint8 as the record holds it: round-to-nearest-even of clamp(c, 0, 1) * 255 in float32 (NaN -> 0);
+    uint8 input is returned as it is."""
+    c = _host(c)
+    if c.dtype == np.uint8:
+        return c.reshape(-1, 3)
+    c = np.nan_to_num(c.astype(np.float32).reshape(-1, 3), nan=0.0)
+    return np.rint(np.clip(c, np.float32(0), np.float32(1)) * np.float32(255)).astype(np.uint8)
+
+
+def save_ply(path, vertices, triangles, normals=None, colors=None):
+    """Binary little-endian PLY: float32 x y z per vertex, uchar count + int32 indices per face (numpy only).
+    normals (V, 3): adds float nx ny nz; colors (V, 3), float in [0, 1] or uint8: adds uchar red green blue (the property
+    names MeshLab and Blender read).  `vertices` may instead be the interleaved record of vertex_attributes(...,
+    want_record=True) -- a (V, 27) uint8 tensor or array, x y z nx ny nz r g b -- which is written as it is (one
+    device -> host copy, no pass over the vertices on the host); normals and colors must then be None.
+    With neither normals nor colors nor a record, the file is what this function always wrote."""
+    t = np.asarray(_host(triangles), dtype=np.int64).reshape(-1, 3)
     faces = np.empty(len(t), dtype=[("n", "u1"), ("i", "<i4", (3,))])
     faces["n"] = 3
     faces["i"] = t
+    v = _host(vertices)
+    props = "property float x\nproperty float y\nproperty float z\n"
+    p_nrm = "property float nx\nproperty float ny\nproperty float nz\n"
+    p_col = "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    if v.dtype == np.uint8 and v.ndim == 2 and v.shape[1] == RECORD_DTYPE.itemsize:
+        if normals is not None or colors is not None:
+            raise ValueError("save_ply: an interleaved vertex record already holds normals and colours")
+        nv, body, props = len(v), np.ascontiguousarray(v).tobytes(), props + p_nrm + p_col
+    else:
+        v = np.ascontiguousarray(np.asarray(v, dtype="<f4").reshape(-1, 3))
+        nv = len(v)
+        if normals is None and colors is None:
+            body = v.tobytes()
+        else:
+            fields = [("p", "<f4", (3,))]
+            cols = {"p": v}
+            if normals is not None:
+                cols["n"] = np.asarray(_host(normals), dtype="<f4").reshape(-1, 3)
+                fields.append(("n", "<f4", (3,)))
+                props += p_nrm
+            if colors is not None:
+                cols["c"] = quantise_colours(colors)
+                fields.append(("c", "u1", (3,)))
+                props += p_col
+            for k, a in cols.items():
+                if len(a) != nv:
+                    raise ValueError(f"save_ply: {nv} vertices but {len(a)} rows of {'normals' if k == 'n' else 'colors'}")
+            rec = np.empty(nv, dtype=np.dtype(fields))   # packed: no padding between the fields
+            for k, a in cols.items():
+                rec[k] = a
+            body = rec.tobytes()
     head = ("ply\nformat binary_little_endian 1.0\n"
-            f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+            f"element vertex {nv}\n" + props +
             f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as fh:
         fh.write(head.encode("ascii"))
-        fh.write(v.tobytes())
+        fh.write(body)
         fh.write(faces.tobytes())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the intrinsic mesh (include/oi_mesh_attr.h, DESIGN section 4.12)
+# ---------------------------------------------------------------------------------------------------------------------
+MAX_REFINE = _l.MESH_MAX_REFINE
+
+
+@dataclasses.dataclass
+class IntrinsicMesh:
+    """The vertex pass's result, CUDA tensors: positions (V, 3) world space, on sdf = -threshold; normals (V, 3) unit
+    d sdf/dx (outward); albedo (V, 3) float32 RGB; residual (refine + 1, V): |sdf + threshold| / |d sdf/dx| before each
+    Newton step and after the last; flags (V,) uint8 (oi_amd.lib.MESH_FLAG_*: a flagged vertex stopped where it was);
+    record (V, 27) uint8 or None: x y z nx ny nz float32 + r g b uint8 per vertex, as save_ply writes it;
+    triangles (F, 3) int32 or None (extract_intrinsic_mesh sets it); shaded (V, 3) or None: the vertex colours under a
+    light (inference.export_mesh(..., light=...) sets it)."""
+    positions: torch.Tensor
+    normals: torch.Tensor
+    albedo: torch.Tensor
+    residual: torch.Tensor
+    flags: torch.Tensor
+    record: Optional[torch.Tensor] = None
+    triangles: Optional[torch.Tensor] = None
+    shaded: Optional[torch.Tensor] = None
+
+
+def _check_refine(refine, what):
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= int(refine) <= MAX_REFINE:
+        raise ValueError(f"{what}: refine={refine!r} (an integer, 0 <= refine <= {MAX_REFINE})")
+    return int(refine)
+
+
+def _field_pack(obj, what):
+    """The FieldPack with shape AND colour weights of a FieldPack, a NeuSRenderer (.pack) or a Generator (.renderer.pack)."""
+    from .fields import FieldPack
+    pack = obj
+    if not isinstance(pack, FieldPack):
+        pack = getattr(getattr(obj, "renderer", obj), "pack", None)
+    if not isinstance(pack, FieldPack) and hasattr(obj, "_own_pack"):
+        pack = obj._own_pack()
+    if not isinstance(pack, FieldPack):
+        raise TypeError(f"{what}: expected a FieldPack, a NeuSRenderer or a Generator, got {type(obj).__name__}")
+    if pack.color_network is None:
+        raise ValueError(f"{what}: the albedo needs the colour head, and this field has none (a bare ShapeNetwork): pass the "
+                         "FieldPack that holds both networks (NeuSRenderer.pack, Generator.renderer.pack)")
+    return pack
+
+
+def vertex_attributes(pack_or_generator, vertices_index, bound_min, bound_max, resolution, z=None, w=None, refine=2,
+                      threshold=0.0, want_record=False):
+    """Index-space marching-cubes vertices (V, 3) (CUDA, as marching_cubes returns them for a field of sdf_lattice on the same
+    bounds and resolution) -> IntrinsicMesh: world positions moved onto the level set by `refine` Newton steps
+    p <- p - s g / |g|^2 (s = sdf + threshold, g = d sdf/dx), unit normals g / |g| and albedo there.  The mesh is the
+    surface u = -sdf = threshold, so the steps go towards sdf = -threshold.  A vertex never moves further than half a lattice
+    cell per axis from its marching-cubes position; one that would, or whose sdf / gradient is not finite or whose gradient
+    vanishes, stays where it was and is flagged.  refine = 0: the marching-cubes vertices with their attributes.
+    Every pass is the full MLP forward (sdf, gradient, albedo) in the pack's precision -- the only pass with a gradient the
+    library has; the albedo of the refinement passes is discarded.  One latent: z (1, 64) or w (1, 64)."""
+    refine = _check_refine(refine, "vertex_attributes")
+    pack = _field_pack(pack_or_generator, "vertex_attributes")
+    if z is None and w is None:
+        raise ValueError("vertex_attributes: a latent z or a style vector w is needed")
+    if not torch.is_tensor(vertices_index) or vertices_index.dim() != 2 or vertices_index.shape[1] != 3:
+        raise ValueError("vertex_attributes: vertices_index must be a (V, 3) tensor of index-space vertices")
+    if not vertices_index.is_cuda:
+        raise _l.OiHipError("vertex_attributes: vertices_index must be on the GPU (there is no CPU path)")
+    vi = vertices_index.detach().float().contiguous()
+    V = vi.shape[0]
+    if V >= 1 << 31:
+        raise ValueError(f"vertex_attributes: {V} vertices (at most 2^31 - 1)")
+    dev = vi.device
+    if V == 0:   # a field without a crossing: nothing is launched
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
+        return IntrinsicMesh(e(0, 3), e(0, 3), e(0, 3), e(refine + 1, 0), e(0, dt=torch.uint8),
+                             e(0, RECORD_DTYPE.itemsize, dt=torch.uint8) if want_record else None)
+    with torch.no_grad():
+        w_, gamma, beta = pack.film(z=z if w is None else None, w=w)
+        if w_.shape[0] != 1:
+            raise ValueError(f"vertex_attributes: one latent expected, got a batch of {w_.shape[0]}")
+        gamma, beta, packed = gamma.contiguous(), beta.contiguous(), pack.packed()
+        xs, ys, zs = _axes(bound_min, bound_max, resolution, dev)
+        bmin, bmax = ([float(v) for v in _host(b).reshape(-1)] for b in (bound_min, bound_max))
+        limits = [0.5 * (bmax[a] - bmin[a]) / (len(x) - 1) for a, x in enumerate((xs, ys, zs))]
+        pos, flags = ops.mesh_vertex_world(vi, xs, ys, zs)
+        pos0 = pos.clone() if refine else pos
+        residual = ops._new(pos, refine + 1, V)
+        scratch = torch.empty(ops.mlp_scratch_bytes(1, V, pack.prec), dtype=torch.uint8, device=dev)
+        fwd = lambda: ops.sdf_mlp_fwd(pos, packed, gamma, beta, 1, pack.prec, pack.fast_trig, want_grad=True, want_rgb=True,
+                                      scratch=scratch)
+        for k in range(refine):
+            sdf, grad, _, _, _ = fwd()
+            ops.mesh_newton(pos, pos0, sdf, grad, threshold, limits, residual[k], flags)
+        sdf, grad, rgb, _, _ = fwd()
+        normals, albedo, record = ops.mesh_attr_finalize(pos, sdf, grad, rgb, threshold, residual[refine], want_record)
+    return IntrinsicMesh(pos, normals, albedo, residual, flags, record)
+
+
+def extract_intrinsic_mesh(renderer_or_generator, z=None, w=None, resolution=256, threshold=0.0,
+                           bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), refine=2, want_record=False):
+    """sdf_lattice -> marching_cubes -> vertex_attributes, nothing on the host in between except the mesh's sizes.
+    -> IntrinsicMesh with triangles (F, 3) int32, the array marching_cubes returns for the same field.  The mesh is the level
+    set u = -sdf = threshold (extract_geometry's convention): with threshold != 0 the vertices are refined towards
+    sdf = -threshold."""
+    refine = _check_refine(refine, "extract_intrinsic_mesh")
+    pack = _field_pack(renderer_or_generator, "extract_intrinsic_mesh")
+    if z is None and w is None:
+        raise ValueError("extract_intrinsic_mesh: a latent z or a style vector w is needed")
+    B = (w if w is not None else z).shape[0]
+    if B != 1:
+        raise ValueError(f"extract_intrinsic_mesh: one latent expected, got a batch of {B}")
+    u = sdf_lattice(pack, bound_min, bound_max, resolution, z=z, w=w, scale=-1.0)[0]
+    vi, tris = marching_cubes(u, threshold)
+    del u
+    out = vertex_attributes(pack, vi, bound_min, bound_max, resolution, z=z, w=w, refine=refine, threshold=threshold,
+                            want_record=want_record)
+    out.triangles = tris
+    return out

@@ -543,6 +543,51 @@ def relight_fwd(weights, grad, rgb, mid_z, rays_o, rays_d, w2b, lights, bg, B, o
 
 
 # ------------------------------------------------------------------------------------------
+# intrinsic mesh export (include/oi_mesh_attr.h); oi_amd.mesh.vertex_attributes sequences these around sdf_mlp_fwd
+# ------------------------------------------------------------------------------------------
+
+def _bytes(ref, n):
+    return torch.empty(int(n), dtype=torch.uint8, device=ref.device)
+
+
+def mesh_vertex_world(verts_index, xs, ys, zs):
+    """Index-space vertices (V, 3) -> world positions (V, 3) through the lattice's axis arrays, and cleared flags (V,) uint8."""
+    V = verts_index.shape[0]
+    pos, flags = _new(verts_index, V, 3), _bytes(verts_index, V)
+    _l.check(_l.load().oi_mesh_vertex_world(_p(verts_index), V, _p(xs), _p(ys), _p(zs), len(xs), len(ys), len(zs), _p(pos),
+                                            _p(flags), _stream()), "oi_mesh_vertex_world")
+    return pos, flags
+
+
+def mesh_newton(pos, pos0, sdf, grad, threshold, limits, residual, flags):
+    """One projection step of `pos` (in place) towards sdf = -threshold; residual (V,) and flags (V,) are written / OR-ed."""
+    _l.check(_l.load().oi_mesh_newton(_p(pos), _p(pos0), _p(sdf), _p(grad), pos.shape[0], float(threshold),
+                                      *(float(v) for v in limits), _p(residual), _p(flags), _stream()), "oi_mesh_newton")
+
+
+def mesh_attr_finalize(pos, sdf, grad, rgb, threshold, residual=None, want_record=False):
+    """-> unit normals (V, 3), albedo (V, 3), the interleaved record (V, 27) uint8 or None; residual (V,) is written."""
+    V = pos.shape[0]
+    normals, albedo = _new(pos, V, 3), _new(pos, V, 3)
+    record = _bytes(pos, V * _l.MESH_RECORD_BYTES).view(V, _l.MESH_RECORD_BYTES) if want_record else None
+    _l.check(_l.load().oi_mesh_attr_finalize(_p(pos), _p(sdf), _p(grad), _p(rgb), V, float(threshold), _p(normals),
+                                             _p(albedo), _p(residual), _p(record), _stream()), "oi_mesh_attr_finalize")
+    return normals, albedo, record
+
+
+def mesh_vertex_record(pos, normals, rgb):
+    """The interleaved record (V, 27) uint8 of positions, normals and colours (V, 3) each."""
+    V = pos.shape[0]
+    if normals.shape != pos.shape or rgb.shape != pos.shape:
+        raise ValueError(f"mesh_vertex_record: positions {tuple(pos.shape)}, normals {tuple(normals.shape)}, colours "
+                         f"{tuple(rgb.shape)}")
+    record = _bytes(pos, V * _l.MESH_RECORD_BYTES).view(V, _l.MESH_RECORD_BYTES)
+    _l.check(_l.load().oi_mesh_vertex_record(_p(_c(pos)), _p(_c(normals)), _p(_c(rgb)), V, _p(record), _stream()),
+             "oi_mesh_vertex_record")
+    return record
+
+
+# ------------------------------------------------------------------------------------------
 # discriminator side
 # ------------------------------------------------------------------------------------------
 

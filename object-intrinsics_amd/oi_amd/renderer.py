@@ -128,6 +128,20 @@ class NeuSRenderer:
         vertices = vertices.cpu().numpy().astype(np.float64)
         return mesh.to_world(vertices, bound_min, bound_max, resolution), triangles.cpu().numpy().astype(np.int64)
 
+    def extract_intrinsic_geometry(self, bound_min, bound_max, resolution, threshold=0.0, siren_network=None, z=None, w=None,
+                                   refine=2):
+        """extract_geometry's arguments (plus `refine`), the intrinsic mesh out: numpy (V, 3) float64 world-space vertices moved
+        onto the level set sdf = -threshold by `refine` Newton steps, (F, 3) int64 triangles (those of extract_geometry),
+        (V, 3) float32 unit normals d sdf/dx / |d sdf/dx| and (V, 3) float32 albedo.  oi_amd.mesh.extract_intrinsic_mesh has
+        the device tensors, the residuals and the per-vertex flags."""
+        from . import mesh
+        if siren_network is not None:
+            raise NotImplementedError("siren_network is not on the path (as in render())")
+        m = mesh.extract_intrinsic_mesh(self, z=z, w=w, resolution=resolution, threshold=threshold, bound_min=bound_min,
+                                        bound_max=bound_max, refine=refine)
+        return (m.positions.cpu().numpy().astype(np.float64), m.triangles.cpu().numpy().astype(np.int64),
+                m.normals.cpu().numpy(), m.albedo.cpu().numpy())
+
 
 class _RenderScalars(torch.autograd.Function):
     """(gradient_error, surface_loss) from the compositing reductions in one launch each way (oi_render_scalars_fwd / _bwd);

@@ -5,7 +5,10 @@
   field_ms       the lattice field (oi_sdf_lattice, one launch)
   points_ms      the same R^3 points through the existing sdf-only path on materialised points (oi_sdf_mlp_fwd)
   mc_ms          marching cubes alone on the field (oi_mc_count + its totals copy + oi_mc_emit)
-  extract_ms     NeuSRenderer.extract_geometry as a whole (field, marching cubes, mesh to the host, world scaling)"""
+  extract_ms     NeuSRenderer.extract_geometry as a whole (field, marching cubes, mesh to the host, world scaling)
+  attr0_ms / attr2_ms   the vertex pass of the intrinsic mesh (mesh.vertex_attributes) on the device
+                 mesh with refine = 0 / 2; attr2_vs_extract = attr2_ms / extract_ms; flagged = flagged vertices at refine = 2;
+                 residual_before / residual_after = median |sdf| / |grad| at the marching-cubes vertices / after two steps"""
 import argparse
 import json
 import os
@@ -64,9 +67,15 @@ with torch.no_grad():
             "extract_ms": median_ms(lambda: r.extract_geometry(bmin, bmax, R, 0.0, z=z)),
         }
         v, t = mesh.marching_cubes(u, 0.0)
+        row["attr0_ms"] = median_ms(lambda: mesh.vertex_attributes(r.pack, v, bmin, bmax, R, z=z, refine=0))
+        row["attr2_ms"] = median_ms(lambda: mesh.vertex_attributes(r.pack, v, bmin, bmax, R, z=z, refine=2))
+        m = mesh.vertex_attributes(r.pack, v, bmin, bmax, R, z=z, refine=2)
+        row.update(attr2_vs_extract=row["attr2_ms"] / row["extract_ms"], flagged=int((m.flags != 0).sum()),
+                   residual_before=float(m.residual[0].median()), residual_after=float(m.residual[-1].median()))
+        del m
         row.update(n_vertices=int(v.shape[0]), n_triangles=int(t.shape[0]),
                    field_vs_points=row["field_ms"] / row["points_ms"], mc_vs_field=row["mc_ms"] / row["field_ms"])
-        out["res"][str(R)] = {k: (round(x, 4) if isinstance(x, float) else x) for k, x in row.items()}
+        out["res"][str(R)] = {k: ((round(x, 4) if abs(x) >= 0.01 else float(f"{x:.4g}")) if isinstance(x, float) else x) for k, x in row.items()}
         del pts, u, v, t
         torch.cuda.empty_cache()
 print(json.dumps(out))

@@ -139,6 +139,65 @@ def light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), **kw):
     return relight_frames(gen, z, b2w, lights, **kw)
 
 
+SURFACE_KEYS = ("image", "depth", "position", "normal_map", "normal_object", "albedo", "mask", "visibility")
+
+
+@torch.no_grad()
+def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"), lights=None, shadows=False, bg=None, **kw):
+    """render_frames by ray / surface intersection (oi_amd.trace.render_surface) instead of the volume render: one frame per
+    (z, b2w) pair under ONE light (`lights`: a Light, default the trained one).  -> {key: (n, C, H, W)} for keys of
+    SURFACE_KEYS ("visibility" needs shadows=True).  Keyword arguments: render_surface's (bias, tol, omega, max_steps)."""
+    from . import trace
+    from .relight import Light
+    unknown = [k for k in keys if k not in SURFACE_KEYS]
+    if unknown or ("visibility" in keys and not shadows):
+        raise ValueError(f"surface_frames: keys {unknown or ['visibility']} (one of {SURFACE_KEYS}; visibility with shadows=True)")
+    if lights is not None and not isinstance(lights, Light):
+        raise TypeError("surface_frames: one Light per walk (surface_light_walk varies the light)")
+    gen.eval()
+    gen.renderer.pack.check()
+    frames = {k: [] for k in keys}
+    for z, b2w in zip(zs, b2ws):
+        out = trace.render_surface(gen, z, b2w, lights=lights, shadows=shadows, bg=bg, **kw)
+        for k in keys:
+            frames[k].append(out[k][0])
+    return {k: torch.stack(v) for k, v in frames.items()}
+
+
+@torch.no_grad()
+def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True, bg=None, bias=None, **kw):
+    """light_walk on the traced surface, with cast shadows: ONE primary trace and ONE full MLP pass at its hits for the whole
+    walk, one shadow trace and one shade launch per 256 lights.  Frame 0 is the trained light.  -> {"image": (n_frames, 3,
+    H, W), "visibility": (n_frames, 1, H, W) when shadows, "mask" / "depth" (1, 1, H, W), "stats"}."""
+    from . import lib, trace
+    from .relight import Light, stack_lights
+    base = Light.from_module(gen.light)
+    dirs = light_walk_directions(base.direction, n_frames, axis)
+    dev = gen.it.device
+    lt = stack_lights([base] + [base.replace(direction=tuple(d)) for d in dirs[1:]], dev)
+    gen.eval()
+    gen.renderer.pack.check()
+    s = trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw)
+    H = s.H
+    image = torch.empty(n_frames, 3, s.N, device=dev)
+    vis_all = torch.empty(n_frames, s.N, device=dev) if shadows else None
+    step = lib.RELIGHT_MAX_LIGHTS
+    maps = None
+    for a in range(0, n_frames, step):
+        b = min(n_frames, a + step)
+        vis = s.visibility(lt[a:b]) if shadows else None
+        if shadows:
+            vis_all[a:b] = vis
+        out = s.shade(lt[a:b], trace._bg(bg, dev), vis, outputs=("image",) if maps is not None else ("depth", "mask", "image"),
+                      image_out=image[a:b])
+        maps = maps or out
+    res = {"image": image.view(n_frames, 3, H, H), "mask": maps["mask"].view(1, 1, H, H), "depth": maps["depth"].view(1, 1, H, H),
+           "stats": s.stats()}
+    if shadows:
+        res["visibility"] = vis_all.view(n_frames, 1, H, H)
+    return res
+
+
 @torch.no_grad()
 def shade_vertices(positions, normals, albedo, light, eye=None):
     """Phong colour (V, 3) of mesh vertices under `light` (oi_amd.relight.Light; its direction in the mesh's own frame): each

@@ -1,4 +1,5 @@
-"""ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h and include/oi_mesh_attr.h).
+"""ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h, include/oi_mesh_attr.h and
+include/oi_trace.h).
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -181,6 +182,38 @@ _MESH_ATTR_SIGS = {
     "oi_mesh_vertex_record": (_i, [_vp] * 3 + [_ll, _vp, _vp]),
 }
 
+# include/oi_trace.h: sphere-traced surface rendering (no reference counterpart either)
+TRACE_MISS, TRACE_HIT, TRACE_LIMIT, TRACE_START_INSIDE, TRACE_NONFINITE, TRACE_BACKFACING = 0, 1, 2, 3, 4, 5
+TRACE_MARCH, TRACE_REFINE = 16, 17
+TRACE_STATUS_NAMES = {TRACE_MISS: "miss", TRACE_HIT: "hit", TRACE_LIMIT: "limit", TRACE_START_INSIDE: "start_inside",
+                      TRACE_NONFINITE: "nonfinite", TRACE_BACKFACING: "backfacing"}
+TRACE_DEFAULT_TOL, TRACE_DEFAULT_OMEGA, TRACE_DEFAULT_MAX_STEPS, TRACE_DEFAULT_BIAS = 1e-5, 1.0, 64, 1e-2
+TRACE_MAX_STEPS, TRACE_COUNT_WORDS = 1024, 1026
+
+
+class TraceState(ctypes.Structure):
+    """Mirror of `oi_trace_state` (include/oi_trace.h)."""
+    _fields_ = [("N", _ll)] + [(n, _vp) for n in ("rays_o", "rays_d", "near_", "far_", "t", "status", "steps", "bracket",
+                                                  "side", "active", "points", "counts")]
+
+
+class SurfaceParams(ctypes.Structure):
+    """Mirror of `oi_surface_params` (include/oi_trace.h)."""
+    _fields_ = ([("N", _ll), ("n_hit", _ll), ("L", _i)] +
+                [(n, _vp) for n in ("rays_o", "rays_d", "t", "status", "hit_slot", "hit_points", "grad", "rgb", "w2b",
+                                    "lights", "bg", "visibility", "depth", "position", "normal", "normal_world", "albedo",
+                                    "mask", "image")])
+
+
+_TRACE_SIGS = {
+    "oi_trace_begin": (_i, [ctypes.POINTER(TraceState), _vp]),
+    "oi_trace_step": (_i, [ctypes.POINTER(TraceState), _vp, _ll, _i, _f, _f, _vp]),
+    "oi_trace_finish": (_i, [ctypes.POINTER(TraceState), _vp, _vp, _vp, _vp]),
+    "oi_trace_shadow_begin": (_i, [ctypes.POINTER(TraceState), _vp, _vp, _ll, _vp, _i, _vp, _f, _vp]),
+    "oi_trace_visibility": (_i, [_vp, _vp, _ll, _ll, _i, _vp, _vp]),
+    "oi_surface_shade": (_i, [ctypes.POINTER(SurfaceParams), _vp]),
+}
+
 # entry points added by later source files (backward kernels); bound when present in the .so
 _OPTIONAL_SIGS = {}
 
@@ -203,6 +236,11 @@ def mesh_attr_symbols():
     return sorted(_MESH_ATTR_SIGS)
 
 
+def trace_symbols():
+    """The entry points of include/oi_trace.h."""
+    return sorted(_TRACE_SIGS)
+
+
 def load():
     """Load (once) and return the ctypes handle.  Raises OiHipError when the library is missing."""
     global _lib
@@ -221,7 +259,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python object-intrinsics_amd/build.py` (hipcc, gfx950). "
                 "oi_amd has no CPU or PyTorch fallback for its kernels.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_OPTIONAL_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_TRACE_SIGS, **_OPTIONAL_SIGS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError:

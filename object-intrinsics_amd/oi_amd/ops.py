@@ -588,6 +588,117 @@ def mesh_vertex_record(pos, normals, rgb):
 
 
 # ------------------------------------------------------------------------------------------
+# sphere-traced surface rendering (include/oi_trace.h); oi_amd.trace sequences these around sdf_mlp_fwd
+# ------------------------------------------------------------------------------------------
+
+def _ip(t):
+    """Raw pointer of a contiguous device tensor of any dtype (int32 lists, uint8 states)."""
+    if t is None:
+        return None
+    if not t.is_cuda or not t.is_contiguous():
+        raise _l.OiHipError("oi_amd ops need contiguous CUDA/HIP tensors (there is no CPU path)")
+    return _vp(t.data_ptr())
+
+
+class TraceState:
+    """The arrays of one oi_trace_state for N rays.  t (N,) float32 is an output (ops._new); status (N,) uint8, steps (N,)
+    int16 (the header's uint16: at most 1024) are outputs too; the rest is working memory.  rays_o / rays_d (N, 3), near /
+    far (N,): the caller's for a primary trace, allocated here for a shadow trace (ref: any tensor on the device)."""
+
+    def __init__(self, N, rays_o=None, rays_d=None, near=None, far=None, ref=None):
+        ref = rays_o if rays_o is not None else ref
+        dev = ref.device
+        e = lambda *sh, dt=torch.float32: torch.empty(sh, dtype=dt, device=dev)
+        self.N = int(N)
+        self.rays_o = _c(rays_o).reshape(N, 3) if rays_o is not None else e(N, 3)
+        self.rays_d = _c(rays_d).reshape(N, 3) if rays_d is not None else e(N, 3)
+        self.near = _c(near).reshape(N) if near is not None else e(N)
+        self.far = _c(far).reshape(N) if far is not None else e(N)
+        self.t = _new(ref, N)
+        self.status = e(N, dt=torch.uint8)
+        self.steps = e(N, dt=torch.int16)
+        self.bracket, self.side = e(N, 4), e(N, dt=torch.uint8)
+        self.active, self.points = e(2, N, dt=torch.int32), e(N, 3)
+        self.counts = e(_l.TRACE_COUNT_WORDS, dt=torch.int32)
+        S = self.c = _l.TraceState()
+        S.N = self.N
+        S.rays_o, S.rays_d, S.near_, S.far_ = _p(self.rays_o), _p(self.rays_d), _p(self.near), _p(self.far)
+        S.t, S.status, S.steps, S.bracket, S.side = _p(self.t), _p(self.status), _ip(self.steps), _p(self.bracket), _p(self.side)
+        S.active, S.points, S.counts = _ip(self.active), _p(self.points), _ip(self.counts)
+
+
+def trace_begin(st):
+    _l.check(_l.load().oi_trace_begin(ctypes.byref(st.c), _stream()), "oi_trace_begin")
+
+
+def trace_step(st, sdf, bound, k, tol, omega):
+    _l.check(_l.load().oi_trace_step(ctypes.byref(st.c), _p(sdf), int(bound), int(k), float(tol), float(omega), _stream()),
+             "oi_trace_step")
+
+
+def trace_finish(st):
+    """-> hit_index (N,) int32 (its first n_hit entries are written), hit_points (N, 3), hit_slot (N,) int32."""
+    dev = st.t.device
+    hit_index = torch.empty(st.N, dtype=torch.int32, device=dev)
+    hit_points = torch.empty(st.N, 3, dtype=torch.float32, device=dev)
+    hit_slot = torch.empty(st.N, dtype=torch.int32, device=dev)
+    _l.check(_l.load().oi_trace_finish(ctypes.byref(st.c), _ip(hit_index), _p(hit_points), _ip(hit_slot), _stream()),
+             "oi_trace_finish")
+    return hit_index, hit_points, hit_slot
+
+
+def trace_shadow_begin(st, hit_points, grad, n_hit, lights, w2b, bias):
+    _l.check(_l.load().oi_trace_shadow_begin(ctypes.byref(st.c), _p(hit_points), _p(grad), int(n_hit), _p(lights),
+                                             lights.shape[0], _p(w2b), float(bias), _stream()), "oi_trace_shadow_begin")
+
+
+def trace_visibility(shadow_status, hit_slot, N, n_hit, L):
+    """-> visibility (L, N) float32."""
+    vis = _new(hit_slot, L, N)
+    _l.check(_l.load().oi_trace_visibility(_p(shadow_status), _ip(hit_slot), int(N), int(n_hit), int(L), _p(vis), _stream()),
+             "oi_trace_visibility")
+    return vis
+
+
+SURFACE_OUT = {"depth": (1,), "position": (3,), "normal": (3,), "normal_world": (3,), "albedo": (3,), "mask": (1,)}
+
+
+def surface_shade(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b, lights=None, bg=None,
+                  visibility=None, outputs=tuple(SURFACE_OUT) + ("image",), image_out=None):
+    """The G-buffer and the Phong image of a traced view (oi_surface_shade).  -> {name: (N,) or (N, 3)} for the names of
+    SURFACE_OUT in `outputs`, and "image" (L, 3, N) (written into `image_out` when given)."""
+    N = t.shape[0]
+    for name in outputs:
+        if name not in SURFACE_OUT and name != "image":
+            raise ValueError(f"surface_shade: unknown output {name!r} (one of {tuple(SURFACE_OUT) + ('image',)})")
+    nl = 0 if lights is None else lights.shape[0]
+    if "image" in outputs and (nl < 1 or nl > _l.RELIGHT_MAX_LIGHTS or tuple(lights.shape[1:]) != (_l.RELIGHT_LIGHT_FLOATS,)):
+        raise ValueError(f"surface_shade: lights {None if lights is None else tuple(lights.shape)}, expected (L, "
+                         f"{_l.RELIGHT_LIGHT_FLOATS}) with 1 <= L <= {_l.RELIGHT_MAX_LIGHTS}")
+    if visibility is not None and tuple(visibility.shape) != (nl, N):
+        raise ValueError(f"surface_shade: visibility {tuple(visibility.shape)}, expected {(nl, N)}")
+    P = _l.SurfaceParams()
+    P.N, P.n_hit, P.L = N, int(n_hit), nl
+    keep = [_c(x) for x in (rays_o, rays_d, t, hit_points, grad, rgb, w2b, lights, bg, visibility)]
+    (P.rays_o, P.rays_d, P.t, P.hit_points, P.grad, P.rgb, P.w2b, P.lights, P.bg, P.visibility) = (_p(x) for x in keep)
+    P.status, P.hit_slot = _p(status), _ip(hit_slot)
+    res = {}
+    for name, sh in SURFACE_OUT.items():
+        if name in outputs:
+            res[name] = _new(t, N) if sh == (1,) else _new(t, N, 3)
+        setattr(P, name, _p(res.get(name)))
+    if "image" in outputs:
+        if image_out is None:
+            image_out = _new(t, nl, 3, N)
+        elif tuple(image_out.shape) != (nl, 3, N) or not image_out.is_contiguous() or image_out.dtype != torch.float32:
+            raise ValueError(f"surface_shade: image_out must be a contiguous float32 {(nl, 3, N)} tensor")
+        res["image"] = image_out
+    P.image = _p(res.get("image"))
+    _l.check(_l.load().oi_surface_shade(ctypes.byref(P), _stream()), "oi_surface_shade")
+    return res
+
+
+# ------------------------------------------------------------------------------------------
 # discriminator side
 # ------------------------------------------------------------------------------------------
 

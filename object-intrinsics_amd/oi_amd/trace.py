@@ -1,0 +1,266 @@
+"""Sphere-traced surface rendering: ray / surface intersection, a G-buffer at the visible surface point, cast shadows
+(include/oi_trace.h).
+
+    sphere_trace     rays against the learned SDF -> per-ray t, status, evaluations, the dense list of hits
+    render_surface   one view of a Generator: depth, position, normals, albedo, mask, the Phong image under L lights,
+                     optionally with cast shadows (one shadow ray per light and visible point)
+
+The loop runs on the host: oi_trace_begin, then per step the library's sdf-only MLP pass (unchanged) on the rays still in
+flight and oi_trace_step, which advances them and compacts the survivors.  The number of rays in flight lives on the device;
+the host launches each pass on the last count it read (a valid upper bound: the count never grows) and reads the count back
+every step while more than READBACK_DENSE rays were in flight, every READBACK_SPARSE steps after that."""
+import dataclasses
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import lib as _l
+from . import ops
+
+# read-back cadence of the number of rays in flight (DESIGN section 4.13 has the measurements)
+READBACK_DENSE = 1024    # above this many rays a stale bound costs MLP time: read every step
+READBACK_SPARSE = 4      # below it a pass is launch-bound whatever its size: read every 4th step
+
+DEFAULT_TOL, DEFAULT_OMEGA, DEFAULT_MAX_STEPS, DEFAULT_BIAS = (_l.TRACE_DEFAULT_TOL, _l.TRACE_DEFAULT_OMEGA,
+                                                               _l.TRACE_DEFAULT_MAX_STEPS, _l.TRACE_DEFAULT_BIAS)
+
+
+@dataclasses.dataclass
+class TraceResult:
+    """CUDA tensors per ray: t (N,) float32 (the hit's ray parameter; the last sample's otherwise), status (N,) uint8
+    (oi_amd.lib.TRACE_*), steps (N,) int16 (sdf evaluations the ray used); hit_index (n_hit,) int32: the rays with
+    TRACE_HIT, in no fixed order; n_evals: points sent through the sdf-only MLP pass (the cost, stale bounds included);
+    n_steps: loop iterations run.  hit_points (n_hit, 3) and hit_slot (N,) (position in hit_index, or -1) go with hit_index."""
+    t: torch.Tensor
+    status: torch.Tensor
+    steps: torch.Tensor
+    hit_index: torch.Tensor
+    n_evals: int
+    n_steps: int = 0
+    hit_points: Optional[torch.Tensor] = None
+    hit_slot: Optional[torch.Tensor] = None
+
+    def counts(self):
+        """{status name: rays} (one device -> host copy)."""
+        c = torch.bincount(self.status.long(), minlength=6).tolist()
+        return {name: int(c[code]) for code, name in _l.TRACE_STATUS_NAMES.items()}
+
+
+def _check_params(tol, omega, max_steps, readback, what):
+    if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or not 1 <= int(max_steps) <= _l.TRACE_MAX_STEPS:
+        raise ValueError(f"{what}: max_steps={max_steps!r} (an integer, 1 <= max_steps <= {_l.TRACE_MAX_STEPS})")
+    if not (float(tol) > 0 and np.isfinite(float(tol)) and float(omega) > 0 and np.isfinite(float(omega))):
+        raise ValueError(f"{what}: tol={tol!r}, omega={omega!r} (both positive and finite)")
+    if readback != "auto" and (isinstance(readback, bool) or not isinstance(readback, (int, np.integer)) or int(readback) < 1):
+        raise ValueError(f"{what}: readback={readback!r} ('auto' or a positive number of steps)")
+
+
+class _Field:
+    """One latent's sdf field: the pack, its packed weights and the FiLM rows."""
+
+    def __init__(self, pack_or_generator, z, w, what):
+        from .mesh import _field_pack
+        self.pack = _field_pack(pack_or_generator, what)
+        if z is None and w is None:
+            raise ValueError(f"{what}: a latent z or a style vector w is needed")
+        lat = w if w is not None else z
+        B = lat.shape[0] if lat.dim() > 1 else 1
+        if B != 1:
+            raise ValueError(f"{what}: one latent expected, got a batch of {B}")
+
+    def prepare(self, z, w):
+        with torch.no_grad():
+            lat = w if w is not None else z
+            lat = lat.reshape(1, -1)
+            _, gamma, beta = self.pack.film(z=None if w is not None else lat, w=lat if w is not None else None)
+        self.gamma, self.beta, self.packed = gamma.contiguous(), beta.contiguous(), self.pack.packed()
+        return self
+
+    def sdf(self, pts):
+        p = self.pack
+        return ops.sdf_mlp_fwd(pts, self.packed, self.gamma, self.beta, 1, p.prec, p.fast_trig)[0]
+
+    def full(self, pts):
+        p = self.pack
+        sdf, grad, rgb, _, _ = ops.sdf_mlp_fwd(pts, self.packed, self.gamma, self.beta, 1, p.prec, p.fast_trig, want_grad=True,
+                                               want_rgb=True)
+        return sdf, grad, rgb
+
+
+def _march(field, st, bound, tol, omega, max_steps, readback):
+    """The loop on a state that oi_trace_begin / oi_trace_shadow_begin has filled.  -> (points evaluated, steps run).
+    Two launches per step through the C ABI directly, with the pointers converted once: the loop's tail is a handful of rays
+    per step, where the host's time per launch is the frame's time."""
+    import ctypes
+    L, p = _l.load(), field.pack
+    sdf = torch.empty(st.N, dtype=torch.float32, device=st.t.device)   # working memory: step k's pass writes sdf[:bound]
+    pts_p, sdf_p, state_p, stream = ops._p(st.points), ops._p(sdf), ctypes.byref(st.c), ops._stream()
+    packed_p, gamma_p, beta_p = ops._p(field.packed), ops._p(field.gamma), ops._p(field.beta)
+    prec, trig = p.prec, int(bool(p.fast_trig))
+    n_evals = k = since = 0
+    while k < max_steps and bound > 0:
+        rc = L.oi_sdf_mlp_fwd(pts_p, packed_p, gamma_p, beta_p, sdf_p, None, None, None, None, 1, bound, prec, trig, stream)
+        if rc:
+            _l.check(rc, "oi_sdf_mlp_fwd")
+        rc = L.oi_trace_step(state_p, sdf_p, bound, k, tol, omega, stream)
+        if rc:
+            _l.check(rc, "oi_trace_step")
+        n_evals += bound
+        k += 1
+        since += 1
+        every = (1 if bound > READBACK_DENSE else READBACK_SPARSE) if readback == "auto" else int(readback)
+        if since >= every and k < max_steps:
+            bound, since = int(st.counts[k].item()), 0
+    return n_evals, k
+
+
+def _finish(st, n_evals, n_steps):
+    hit_index, hit_points, hit_slot = ops.trace_finish(st)
+    n_hit = int(st.counts[-1].item())
+    return TraceResult(st.t, st.status, st.steps, hit_index[:n_hit], n_evals, n_steps, hit_points[:n_hit], hit_slot)
+
+
+@torch.no_grad()
+def sphere_trace(pack_or_generator, rays_o, rays_d, near=None, far=None, z=None, w=None, tol=DEFAULT_TOL, omega=DEFAULT_OMEGA,
+                 max_steps=DEFAULT_MAX_STEPS, siren_network=None, readback="auto"):
+    """Rays (N, 3) + (N, 3) (CUDA, any leading shape) against the SDF of one latent z (1, 64) or style vector w (1, 64) of a
+    FieldPack, a NeuSRenderer or a Generator, in the pack's precision.  near / far (N,): default near_far_from_sphere (the
+    unit sphere's mid-point -1 / +1).  Per ray: march t += max(omega sdf, tol) from near; |sdf| <= tol is a hit; the first
+    negative sample closes a bracket that Illinois regula falsi refines until |sdf| <= tol (include/oi_trace.h has the state
+    machine).  readback: 'auto' or the number of steps between reads of the number of rays in flight.  -> TraceResult."""
+    if siren_network is not None:
+        raise NotImplementedError("siren_network is not on the path (as in render())")
+    _check_params(tol, omega, max_steps, readback, "sphere_trace")
+    field = _Field(pack_or_generator, z, w, "sphere_trace")
+    if not torch.is_tensor(rays_o) or not torch.is_tensor(rays_d) or rays_o.shape != rays_d.shape or rays_o.shape[-1] != 3:
+        raise ValueError("sphere_trace: rays_o and rays_d must be tensors of the same (..., 3) shape")
+    if not rays_o.is_cuda:
+        raise _l.OiHipError("sphere_trace: the rays must be on the GPU (there is no CPU path)")
+    ro, rd = rays_o.detach().float().reshape(-1, 3).contiguous(), rays_d.detach().float().reshape(-1, 3).contiguous()
+    N, dev = ro.shape[0], ro.device
+    if N >= 1 << 31:
+        raise ValueError(f"sphere_trace: {N} rays (at most 2^31 - 1)")
+    if N == 0:   # nothing is launched
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
+        return TraceResult(e(0), e(0, dt=torch.uint8), e(0, dt=torch.int16), e(0, dt=torch.int32), 0, 0, e(0, 3), e(0, dt=torch.int32))
+    if near is None or far is None:
+        mid = -(ro * rd).sum(-1) / (rd * rd).sum(-1)   # generator.py:336-342
+        near = mid - 1.0 if near is None else near
+        far = mid + 1.0 if far is None else far
+    near, far = (torch.as_tensor(v, dtype=torch.float32, device=dev).reshape(-1).expand(N) for v in (near, far))
+    field.prepare(z, w)
+    st = ops.TraceState(N, ro, rd, near, far)
+    ops.trace_begin(st)
+    n_evals, k = _march(field, st, N, float(tol), float(omega), int(max_steps), readback)
+    return _finish(st, n_evals, k)
+
+
+def _view_rays(gen, b2w):
+    """The rays of Generator.forward for one pose (4, 4): its own oi_gen_rays path.  -> rays_o, rays_d (N, 3), near, far (N,),
+    w2b (4, 4)."""
+    dev = gen.it.device
+    prior = gen.sample_prior(1, {"b2w": b2w.to(dev, torch.float32).reshape(1, 4, 4)})
+    rays = gen.gen_rays_at({}, prior)
+    return (rays["rays_o"].reshape(-1, 3), rays["rays_d"].reshape(-1, 3), rays["near"].reshape(-1), rays["far"].reshape(-1),
+            prior["w2b"][0].contiguous())
+
+
+class _Surface:
+    """One traced view and everything the light-dependent stages reuse: the primary trace, the full MLP pass at its hits."""
+
+    def __init__(self, gen, z, b2w, bias, trace_kw, w=None):
+        tol, omega = trace_kw.get("tol", DEFAULT_TOL), trace_kw.get("omega", DEFAULT_OMEGA)
+        max_steps, readback = trace_kw.get("max_steps", DEFAULT_MAX_STEPS), trace_kw.get("readback", "auto")
+        unknown = set(trace_kw) - {"tol", "omega", "max_steps", "readback"}
+        if unknown:
+            raise TypeError(f"render_surface: unknown arguments {sorted(unknown)}")
+        _check_params(tol, omega, max_steps, readback, "render_surface")
+        if not (float(bias) >= 0 and np.isfinite(float(bias))):
+            raise ValueError(f"render_surface: bias={bias!r} (>= 0 and finite)")
+        self.kw = (float(tol), float(omega), int(max_steps), readback)
+        self.bias = float(bias)
+        self.field = _Field(gen, z, w, "render_surface")
+        gen.eval()
+        dev = gen.it.device
+        self.field.prepare(None if z is None else z.to(dev), None if w is None else w.to(dev))
+        self.ro, self.rd, near, far, self.w2b = _view_rays(gen, b2w)
+        self.N, self.H = self.ro.shape[0], gen.resolution
+        st = ops.TraceState(self.N, self.ro, self.rd, near, far)
+        ops.trace_begin(st)
+        n_evals, k = _march(self.field, st, self.N, *self.kw)
+        self.res = _finish(st, n_evals, k)
+        self.n_hit = self.res.hit_index.shape[0]
+        self.grad = self.rgb = None
+        if self.n_hit:
+            _, self.grad, self.rgb = self.field.full(self.res.hit_points)
+        self.shadow_evals = 0
+        self.shadow = None
+
+    def visibility(self, lights):
+        """(L, N) visibility of `lights` (L, 16): one shadow trace over all L x n_hit rays."""
+        L = lights.shape[0]
+        if self.n_hit == 0:
+            return torch.ones(L, self.N, device=self.ro.device)
+        st = ops.TraceState(L * self.n_hit, ref=self.ro)
+        ops.trace_shadow_begin(st, self.res.hit_points, self.grad, self.n_hit, lights, self.w2b, self.bias)
+        bound = int(st.counts[0].item())
+        n_evals, _ = _march(self.field, st, bound, *self.kw)
+        ops.trace_finish(st)   # in-flight rays -> LIMIT
+        self.shadow_evals += n_evals
+        self.shadow = st
+        return ops.trace_visibility(st.status, self.res.hit_slot, self.N, self.n_hit, L)
+
+    def shade(self, lights, bg, visibility=None, outputs=tuple(ops.SURFACE_OUT) + ("image",), image_out=None):
+        r = self.res
+        dummy = self.ro   # never read when n_hit == 0
+        return ops.surface_shade(self.ro, self.rd, r.t, r.status, r.hit_slot, r.hit_points if self.n_hit else dummy,
+                                 self.grad if self.n_hit else dummy, self.rgb if self.n_hit else dummy, self.n_hit, self.w2b,
+                                 lights, bg, visibility, outputs, image_out)
+
+    def stats(self):
+        s = self.res.counts()
+        s.update(n_rays=self.N, n_evals=self.res.n_evals, n_steps=self.res.n_steps, shadow_evals=self.shadow_evals)
+        return s
+
+
+def _bg(bg, dev):
+    return None if bg is None else torch.as_tensor(bg, dtype=torch.float32).to(dev).reshape(3).contiguous()
+
+
+def _maps(out, H, W):
+    """(N,) / (N, 3) G-buffer arrays -> (1, C, H, W) maps."""
+    return {k: (v.view(1, H, W, -1).permute(0, 3, 1, 2) if v.dim() == 2 else v.view(1, 1, H, W)) for k, v in out.items()}
+
+
+_MAP_NAMES = {"depth": "depth", "position": "position", "normal_world": "normal_map", "normal": "normal_object",
+              "albedo": "albedo", "mask": "mask"}
+
+
+@torch.no_grad()
+def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAULT_BIAS, **trace_kw):
+    """One view of `gen` (latent z (z_dim,) or (1, z_dim), pose b2w (4, 4)) by intersecting each pixel's ray with the surface:
+    -> dict of depth (1, 1, H, W) (the ray parameter; NaN off the mask), position, normal_map (world frame), normal_object,
+    albedo (1, 3, H, W), mask (1, 1, H, W), image (L, 3, H, W) under `lights` (oi_amd.relight.Light objects; default the
+    generator's trained light), visibility (L, 1, H, W) when `shadows` (one shadow ray per light and visible point, offset by
+    `bias` along the normal), stats (rays per status, sdf evaluations), trace (the primary TraceResult).  The rays are Generator.forward's.  bg: (3,)
+    background colour (black when None).  trace_kw: tol, omega, max_steps, readback of sphere_trace."""
+    from .relight import Light, stack_lights
+    dev = gen.it.device
+    z = z.to(dev).reshape(1, -1)
+    s = _Surface(gen, z, b2w, bias, trace_kw)
+    lt = stack_lights(Light.from_module(gen.light) if lights is None else lights, dev)
+    if lt.shape[0] > _l.RELIGHT_MAX_LIGHTS:
+        raise ValueError(f"render_surface: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS}; inference.surface_light_walk "
+                         "splits larger sets)")
+    vis = s.visibility(lt) if shadows else None
+    out = s.shade(lt, _bg(bg, dev), vis)
+    H = s.H
+    res = {_MAP_NAMES[k]: v for k, v in _maps({k: v for k, v in out.items() if k != "image"}, H, H).items()}
+    res["image"] = out["image"].view(-1, 3, H, H)
+    if shadows:
+        res["visibility"] = vis.view(-1, 1, H, H)
+        res["shadow_trace"] = s.shadow   # ops.TraceState of the L x n_hit shadow rays (ray l * n_hit + i), or None without a hit
+    res["stats"] = s.stats()
+    res["trace"] = s.res
+    return res

@@ -26,6 +26,7 @@
 
 #include "mlp_common.h"
 #include "f3_blob.h"
+#include "../../include/oi_mesh_band.h"
 
 namespace {
 
@@ -497,7 +498,7 @@ __device__ unsigned long long oi_prof[16];
 #define PROF_T(i)
 #endif
 
-// The kernel is stamped out twice from sdf_mlp_kernel.inc, once per point source, rather than shared through a device
+// The kernel is stamped out three times from sdf_mlp_kernel.inc, once per point source, rather than shared through a device
 // function: a forced-inline body is simplified by hipcc before it is inlined, and that alone changed the instructions and
 // register counts of every array instantiation.  Included, the array kernel is token for token what it was.
 //   OI_SDF_LATTICE 0: sdf_mlp_kernel<PREC, FAST, FULL>, points read from pts[pt * 3 + {0,1,2}];
@@ -519,6 +520,39 @@ __device__ unsigned long long oi_prof[16];
 #include "sdf_mlp_kernel.inc"
 #undef OI_SDF_LATTICE
 #undef OI_LATTICE_POINT
+
+//   OI_SDF_LATTICE 2: sdf_band_kernel<PREC, FAST, false> (oi_sdf_lattice_band, include/oi_mesh_band.h): point loc of the
+//     launch is the local point loc % b^3 = (lx * b + ly) * b + lz of block band_list[loc / b^3] = (bi * nby + bj) * nbz + bk,
+//     b = 1 << band_lb; it reads (xs[b bi + lx], ys[b bj + ly], zs[b bk + lz]), each index clamped to its axis, and stores
+//     scale * sdf to the dense field at (ix * ny + iy) * nz + iz -- or nothing when the point lies beyond the lattice (the
+//     ragged last block of an axis) or the block id beyond the block lattice.  n_active * b^3 <= 2^30 (axes <= 1024).
+//     The two stampings above are, token for token, what they were before this one existed.
+#define OI_BAND_INDEX                                                                                                  \
+  const unsigned loc_ = (unsigned)(pt - (long long)e * n_per_elem), bm_ = (1u << band_lb) - 1u;                        \
+  const unsigned blk_ = band_list[loc_ >> (3 * band_lb)], l_ = loc_ & ((1u << (3 * band_lb)) - 1u);                    \
+  const unsigned nbx_ = ((unsigned)lat_nx + bm_) >> band_lb, nby_ = ((unsigned)lat_ny + bm_) >> band_lb,               \
+                 nbz_ = ((unsigned)lat_nz + bm_) >> band_lb;                                                           \
+  const unsigned bi_ = blk_ / (nby_ * nbz_), br_ = blk_ - bi_ * (nby_ * nbz_), bj_ = br_ / nbz_, bk_ = br_ - bj_ * nbz_; \
+  const unsigned ix_ = (bi_ << band_lb) + (l_ >> (2 * band_lb)), iy_ = (bj_ << band_lb) + ((l_ >> band_lb) & bm_),     \
+                 iz_ = (bk_ << band_lb) + (l_ & bm_)
+#define OI_LATTICE_POINT(x, y, z)                                                                                      \
+  do {                                                                                                                 \
+    OI_BAND_INDEX;                                                                                                     \
+    x = xs[min(ix_, (unsigned)lat_nx - 1u)], y = ys[min(iy_, (unsigned)lat_ny - 1u)],                                  \
+    z = zs[min(iz_, (unsigned)lat_nz - 1u)];                                                                           \
+  } while (0)
+#define OI_LATTICE_STORE(v)                                                                                            \
+  do {                                                                                                                 \
+    OI_BAND_INDEX;                                                                                                     \
+    if (bi_ < nbx_ && ix_ < (unsigned)lat_nx && iy_ < (unsigned)lat_ny && iz_ < (unsigned)lat_nz)                      \
+      sdf_out[((size_t)ix_ * (unsigned)lat_ny + iy_) * (unsigned)lat_nz + iz_] = (v);                                  \
+  } while (0)
+#define OI_SDF_LATTICE 2
+#include "sdf_mlp_kernel.inc"
+#undef OI_SDF_LATTICE
+#undef OI_LATTICE_POINT
+#undef OI_LATTICE_STORE
+#undef OI_BAND_INDEX
 
 template <int PREC, bool FAST, bool FULL>
 int launch_mlp_variant(const float* pts, const char* pk, const float* gamma, const float* beta, float* sdf, float* grad,
@@ -572,6 +606,36 @@ int launch_lattice(const float* xs, const float* ys, const float* zs, int ny, in
   }
   hipLaunchKernelGGL(k, grid, block, LDS_BYTES, st, xs, ys, zs, ny, nz, scale, pk, gamma, beta, out, n);
   return oi::check_launch("oi_sdf_lattice");
+}
+
+// oi_sdf_lattice_band: launch_lattice's grid rule and LDS attribute for the block-list stamping, one batch element
+template <int PREC, bool FAST>
+int launch_band(const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, int lb, const unsigned* list,
+                float scale, const char* pk, const float* gamma, const float* beta, float* out, long long n,
+                hipStream_t st) {
+  constexpr int NWV = V2_WAVES;
+  constexpr int LDS_BYTES = v2_lds_total(PREC);
+  static const int cus = [] {
+    int dev = 0, c = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
+    return c > 0 ? c : 256;
+  }();
+  const int tiles = oi::cdiv(n, NWV * WAVE_PTS);
+  dim3 grid(v2_two_slots(PREC) ? std::min(tiles, cus) : tiles, 1), block(64 * NWV);
+  auto k = sdf_band_kernel<PREC, FAST, false>;
+  // dynamic LDS above 64 KiB: the attribute, once per device (bit d of `set`; a process may drive several)
+  static std::atomic<unsigned long long> set{0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev >= 64 || !((set.load() >> dev) & 1ull)) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) !=
+        hipSuccess)
+      return oi::fail(OI_ERR_LAUNCH, "oi_sdf_lattice_band: hipFuncSetAttribute(%d B of LDS) failed", LDS_BYTES);
+    if (dev < 64) set.fetch_or(1ull << dev);
+  }
+  hipLaunchKernelGGL(k, grid, block, LDS_BYTES, st, xs, ys, zs, nx, ny, nz, lb, list, scale, pk, gamma, beta, out, n);
+  return oi::check_launch("oi_sdf_lattice_band");
 }
 
 template <int PREC, bool FAST>
@@ -788,6 +852,40 @@ int oi_sdf_lattice(const void* packed, const float* gamma, const float* beta, in
       return oi::fail(OI_ERR_INVALID_ARG, "oi_sdf_lattice: bad precision %d", prec);
   }
 #undef OI_LAT_CASE
+}
+
+// include/oi_mesh_band.h: the band launch of narrow-band mesh extraction (accelerates renderer.py:15-41)
+int oi_sdf_lattice_band(const void* packed, const float* gamma, const float* beta, int B, const float* xs, const float* ys,
+                        const float* zs, int nx, int ny, int nz, int block, const unsigned* list, long long n_active,
+                        float scale, float* field, int prec, int fast_trig, oi_stream_t stream) {
+  OI_REQUIRE(B == 1, "oi_sdf_lattice_band: B=%d (one element per call: a batch is refused)", B);
+  OI_REQUIRE(block == 4 || block == 8, "oi_sdf_lattice_band: block=%d (4 or 8)", block);
+  OI_REQUIRE(nx >= OI_BAND_MIN_RES && ny >= OI_BAND_MIN_RES && nz >= OI_BAND_MIN_RES && nx <= OI_BAND_MAX_RES &&
+                 ny <= OI_BAND_MAX_RES && nz <= OI_BAND_MAX_RES,
+             "oi_sdf_lattice_band: lattice %d x %d x %d (every axis 2..%d)", nx, ny, nz, OI_BAND_MAX_RES);
+  const long long nblk = (long long)((nx + block - 1) / block) * ((ny + block - 1) / block) * ((nz + block - 1) / block);
+  OI_REQUIRE(n_active >= 0 && n_active <= nblk, "oi_sdf_lattice_band: n_active=%lld (0..%lld blocks)", n_active, nblk);
+  OI_REQUIRE(scale == scale, "oi_sdf_lattice_band: scale is NaN");
+  if (n_active == 0) return OI_OK;
+  OI_REQUIRE(packed && gamma && beta && xs && ys && zs && list && field, "oi_sdf_lattice_band: null pointer");
+  const int lb = block == 4 ? 2 : 3;
+  const long long n = n_active << (3 * lb);  // <= 2^30: the local index fits 32 bits
+  const char* pk = reinterpret_cast<const char*>(packed);
+  hipStream_t st = oi::as_stream(stream);
+#define OI_BAND_CASE(P)                                                                                              \
+  case P:                                                                                                            \
+    return fast_trig ? launch_band<P, true>(xs, ys, zs, nx, ny, nz, lb, list, scale, pk, gamma, beta, field, n, st)  \
+                     : launch_band<P, false>(xs, ys, zs, nx, ny, nz, lb, list, scale, pk, gamma, beta, field, n, st);
+  switch (prec) {
+    OI_BAND_CASE(OI_PREC_F32)
+    OI_BAND_CASE(OI_PREC_BF16X3)
+    OI_BAND_CASE(OI_PREC_BF16)
+    OI_BAND_CASE(OI_PREC_BF16X6)
+    OI_BAND_CASE(OI_PREC_F16X3)
+    default:
+      return oi::fail(OI_ERR_INVALID_ARG, "oi_sdf_lattice_band: bad precision %d", prec);
+  }
+#undef OI_BAND_CASE
 }
 
 }  // extern "C"

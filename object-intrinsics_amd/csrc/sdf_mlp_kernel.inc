@@ -1,9 +1,21 @@
-// The sdf MLP forward kernel, included twice by mlp.hip (see the comment there): OI_SDF_LATTICE 0 defines
+// The sdf MLP forward kernel, included three times by mlp.hip (see the comment there): OI_SDF_LATTICE 0 defines
 // sdf_mlp_kernel<PREC, FAST, FULL> (points from pts[]), OI_SDF_LATTICE 1 defines sdf_lattice_kernel<PREC, FAST, false>
-// (points from the lattice axes through OI_LATTICE_POINT, output scale * sdf).  No include guard, on purpose.
+// (points from the lattice axes through OI_LATTICE_POINT, output scale * sdf), OI_SDF_LATTICE 2 defines
+// sdf_band_kernel<PREC, FAST, false> (points of the listed blocks of the lattice through OI_LATTICE_POINT, output scale * sdf
+// scattered into the dense field through OI_LATTICE_STORE).  No include guard, on purpose.
 template <int PREC, bool FAST, bool FULL>
 __global__ void __launch_bounds__(64 * V2_WAVES, 2)
-#if OI_SDF_LATTICE
+#if OI_SDF_LATTICE == 2
+sdf_band_kernel(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs, int lat_nx, int lat_ny,
+                int lat_nz, int band_lb, const unsigned* __restrict__ band_list, float scale, const char* __restrict__ packed,
+                const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ sdf_out,
+                long long n_per_elem) {
+  static_assert(!FULL, "the block-list point source serves the sdf-only pass");
+  float* const grad_out = nullptr;
+  float* const rgb_out = nullptr;
+  float* const feat_out = nullptr;
+  char* const scratch = nullptr;
+#elif OI_SDF_LATTICE
 sdf_lattice_kernel(const float* __restrict__ xs, const float* __restrict__ ys, const float* __restrict__ zs, int lat_ny,
                    int lat_nz, float scale, const char* __restrict__ packed, const float* __restrict__ gamma,
                    const float* __restrict__ beta, float* __restrict__ sdf_out, long long n_per_elem) {
@@ -167,7 +179,9 @@ sdf_mlp_kernel(const float* __restrict__ pts, const char* __restrict__ packed, c
     part += __shfl_xor(part, 32, 64);
     sdf_v = part + *reinterpret_cast<const float*>(lds + V2_TABS + (H_SIG + C) * 4);
   }
-#if OI_SDF_LATTICE
+#if OI_SDF_LATTICE == 2
+  if (valid && h == 0) OI_LATTICE_STORE(scale * sdf_v);
+#elif OI_SDF_LATTICE
   if (valid && h == 0) sdf_out[pt] = scale * sdf_v;
 #else
   if (valid && h == 0) sdf_out[pt] = sdf_v;

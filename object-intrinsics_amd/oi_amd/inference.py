@@ -224,10 +224,11 @@ def shade_vertices(positions, normals, albedo, light, eye=None):
 
 @torch.no_grad()
 def export_mesh(gen, z, path, resolution=256, refine=2, light=None, threshold=0.0, bound_min=(-1.0, -1.0, -1.0),
-                bound_max=(1.0, 1.0, 1.0), eye=None):
+                bound_max=(1.0, 1.0, 1.0), eye=None, band=False, lipschitz=None, block=None):
     """The instance of latent z (z_dim,) or (1, z_dim) as a PLY asset at `path`: triangles, vertices on the surface, analytic
     normals and per-vertex colours (oi_amd.mesh.extract_intrinsic_mesh; save_ply's attribute layout).  Colours are the
     albedo, or with `light` (oi_amd.relight.Light, e.g. Light.from_module(gen.light)) the shaded colour of shade_vertices.
+    band=True (lipschitz, block): the field comes from mesh.sdf_lattice_band; the file is the same, the BandInfo is in m.band.
     Checks the weights first (FieldPack.check: an inf / NaN weight is refused before anything is launched).
     -> the IntrinsicMesh that was written (with `shaded` (V, 3) set when a light was given)."""
     from . import mesh, ops
@@ -237,7 +238,8 @@ def export_mesh(gen, z, path, resolution=256, refine=2, light=None, threshold=0.
     dev = gen.it.device
     z = z.to(dev).reshape(1, -1)
     m = mesh.extract_intrinsic_mesh(pack, z=z, resolution=resolution, threshold=threshold, bound_min=bound_min,
-                                    bound_max=bound_max, refine=refine, want_record=light is None)
+                                    bound_max=bound_max, refine=refine, want_record=light is None, band=band,
+                                    lipschitz=lipschitz, block=block)
     if light is None:
         record = m.record
     else:

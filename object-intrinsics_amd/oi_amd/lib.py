@@ -1,5 +1,5 @@
-"""ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h, include/oi_mesh_attr.h and
-include/oi_trace.h).
+"""ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h, include/oi_mesh_attr.h,
+include/oi_trace.h and include/oi_mesh_band.h).
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -214,6 +214,16 @@ _TRACE_SIGS = {
     "oi_surface_shade": (_i, [ctypes.POINTER(SurfaceParams), _vp]),
 }
 
+# include/oi_mesh_band.h: narrow-band mesh extraction (accelerates renderer.py:15-41; no reference counterpart either)
+BAND_MIN_RES, BAND_MAX_RES = 2, 1024
+_d = ctypes.c_double
+_MESH_BAND_SIGS = {
+    "oi_band_workspace_bytes": (_sz, [_i] * 4),
+    "oi_band_classify": (_i, [_vp] + [_i] * 5 + [_d] * 3 + [_f, _f, _d, _vp, _vp, _sz, ctypes.POINTER(_ll),
+                                                              ctypes.POINTER(_f), _vp]),
+    "oi_sdf_lattice_band": (_i, [_vp] * 3 + [_i] + [_vp] * 3 + [_i] * 4 + [_vp, _ll, _f, _vp, _i, _i, _vp]),
+}
+
 # entry points added by later source files (backward kernels); bound when present in the .so
 _OPTIONAL_SIGS = {}
 
@@ -241,6 +251,11 @@ def trace_symbols():
     return sorted(_TRACE_SIGS)
 
 
+def mesh_band_symbols():
+    """The entry points of include/oi_mesh_band.h."""
+    return sorted(_MESH_BAND_SIGS)
+
+
 def load():
     """Load (once) and return the ctypes handle.  Raises OiHipError when the library is missing."""
     global _lib
@@ -259,7 +274,7 @@ def load():
                 f"{LIB_PATH} not found: build it with `python object-intrinsics_amd/build.py` (hipcc, gfx950). "
                 "oi_amd has no CPU or PyTorch fallback for its kernels.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_TRACE_SIGS, **_OPTIONAL_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_TRACE_SIGS, **_MESH_BAND_SIGS, **_OPTIONAL_SIGS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError:

@@ -5,11 +5,14 @@
     marching_cubes   triangle mesh of a field                   oi_mc_count + oi_mc_emit
     extract_fields / extract_geometry   the reference's functions with a caller-supplied query_func (64^3 chunks)
     save_ply         binary little-endian PLY with numpy only (optionally with normals and colours)
+    sdf_lattice_band the same field with the MLP run only near the level set   oi_sdf_lattice (one value per block) +
+                     oi_band_classify + oi_sdf_lattice_band   (include/oi_mesh_band.h; marching cubes gives the same mesh)
     vertex_attributes / extract_intrinsic_mesh   the intrinsic mesh: vertices moved onto the level set, analytic normals
                      and albedo per vertex   oi_mesh_vertex_world + (oi_sdf_mlp_fwd + oi_mesh_newton) x refine +
                      oi_sdf_mlp_fwd + oi_mesh_attr_finalize   (include/oi_mesh_attr.h)
 
-DESIGN section 4.10 has the table rule, the output order and the measured numbers; section 4.12 the vertex pass."""
+DESIGN section 4.10 has the table rule, the output order and the measured numbers; section 4.12 the vertex pass; section 4.14
+the narrow band."""
 import ctypes
 import dataclasses
 from typing import Optional
@@ -52,6 +55,132 @@ def sdf_lattice(pack, bound_min, bound_max, resolution, z=None, w=None, scale=1.
                                   _p(zs), nx, ny, nz, float(scale), _p(out), pack.prec, int(bool(pack.fast_trig)), _stream()),
                  "oi_sdf_lattice")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the narrow band (include/oi_mesh_band.h)
+# ---------------------------------------------------------------------------------------------------------------------
+# Bound on |d sdf/dx|: twice the largest gradient norm of the golden field over the box [-1, 1]^3, corners included, rounded up
+# to one significant digit (DESIGN 4.14 has the measurement).  The slope guard is the runtime net below it.
+DEFAULT_LIPSCHITZ = 20.0
+DEFAULT_BLOCK = 4   # 30 % of the points at 512^3 against 71 % for block 8
+
+
+@dataclasses.dataclass
+class BandInfo:
+    """What sdf_lattice_band did: blocks of `block` points per axis; active ones went through the MLP, inactive ones hold their
+    centre's value, above (u > iso) or below the level; points_evaluated: the coarse pass plus the band launch (ragged ends
+    included); max_slope: the largest slope seen between the centres of face-adjacent blocks, a lower bound of the true
+    bound on |d sdf/dx|; lipschitz: the bound the call used.  coarse (nbx, nby, nbz): the coarse pass (scale applied);
+    active_list (active_blocks,) int32: the ids of the active blocks, in no particular order."""
+    block: int
+    blocks: int
+    active_blocks: int
+    inactive_above: int
+    inactive_below: int
+    points_evaluated: int
+    max_slope: float
+    lipschitz: float
+    coarse: Optional[torch.Tensor] = None
+    active_list: Optional[torch.Tensor] = None
+
+    @property
+    def inactive_blocks(self):
+        return self.inactive_above + self.inactive_below
+
+    @property
+    def active_fraction(self):
+        return self.active_blocks / max(self.blocks, 1)
+
+
+def _check_band_args(what, lipschitz, block):
+    lipschitz = DEFAULT_LIPSCHITZ if lipschitz is None else lipschitz
+    block = DEFAULT_BLOCK if block is None else block
+    if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or int(block) not in (4, 8):
+        raise ValueError(f"{what}: block={block!r} (4 or 8)")
+    if isinstance(lipschitz, bool) or not isinstance(lipschitz, (int, float, np.integer, np.floating)) or \
+            not (float(lipschitz) > 0.0 and np.isfinite(float(lipschitz))):
+        raise ValueError(f"{what}: lipschitz={lipschitz!r} (a finite bound > 0 on |d sdf/dx| inside the box)")
+    return float(lipschitz), int(block)
+
+
+def sdf_lattice_band(pack, bound_min, bound_max, resolution, iso, z=None, w=None, scale=1.0, lipschitz=None, block=None):
+    """sdf_lattice for marching cubes at level `iso`, with the network evaluated only near that level (the rule is stated in
+    include/oi_mesh_band.h): -> (field (1, nx, ny, nz), BandInfo).  The field equals sdf_lattice's bit for bit at every point
+    of an active block and holds the block's centre value -- of the same side of iso -- everywhere else, so
+    marching_cubes(field[0], iso) is the dense field's mesh, byte for byte, as long as `lipschitz` bounds |d sdf/dx| in the
+    box (grown by (block - 1) / 2 cells).  A slope between two block centres above `lipschitz` proves the bound wrong:
+    ValueError, no field.  One latent; lipschitz / block default to DEFAULT_LIPSCHITZ / DEFAULT_BLOCK."""
+    from .fields import FieldPack
+    lipschitz, block = _check_band_args("sdf_lattice_band", lipschitz, block)
+    if not isinstance(pack, FieldPack):
+        pack = pack._own_pack()
+    if z is None and w is None:
+        raise ValueError("sdf_lattice_band: a latent z or a style vector w is needed")
+    B = (w if w is not None else z).shape[0]
+    if B != 1:
+        raise ValueError(f"sdf_lattice_band: one latent expected, got a batch of {B}")
+    res = (resolution,) * 3 if np.isscalar(resolution) else tuple(resolution)
+    nx, ny, nz = (int(r) for r in res)
+    if not all(_l.BAND_MIN_RES <= n <= _l.BAND_MAX_RES for n in (nx, ny, nz)):
+        raise ValueError(f"sdf_lattice_band: lattice {nx} x {ny} x {nz} (every axis {_l.BAND_MIN_RES}..{_l.BAND_MAX_RES})")
+    iso, scale = float(iso), float(scale)
+    if not (np.isfinite(iso) and np.isfinite(scale) and scale != 0.0):
+        raise ValueError(f"sdf_lattice_band: iso={iso} scale={scale} (finite, scale != 0)")
+    bmin = [float(v) for v in _host(bound_min).reshape(-1)]
+    bmax = [float(v) for v in _host(bound_max).reshape(-1)]
+    h = [abs(bmax[a] - bmin[a]) / (n - 1) for a, n in enumerate((nx, ny, nz))]
+    if not all(v > 0.0 and np.isfinite(v) for v in h):
+        raise ValueError(f"sdf_lattice_band: empty box {bmin} .. {bmax}")
+    L = _l.load()
+    with torch.no_grad():
+        _, gamma, beta = pack.film(z=z if w is None else None, w=w)
+        gamma, beta, packed = gamma.contiguous(), beta.contiguous(), pack.packed()
+        dev = gamma.device
+        xs, ys, zs = _axes(bmin, bmax, (nx, ny, nz), dev)
+        # the coarse pass: index block * i + (block - 1) / 2 per axis, on the line through the axis' end points (float64 on
+        # the host, as tests/helpers/band_ref.py builds them)
+        nb = [(n + block - 1) // block for n in (nx, ny, nz)]
+        cax = [torch.from_numpy((bmin[a] + (block * np.arange(nb[a], dtype=np.float64) + (block - 1) / 2.0) *
+                                 ((bmax[a] - bmin[a]) / (n - 1))).astype(np.float32)).to(dev)
+               for a, n in enumerate((nx, ny, nz))]
+        fast = int(bool(pack.fast_trig))
+        coarse = torch.empty(nb[0], nb[1], nb[2], dtype=torch.float32, device=dev)
+        _l.check(L.oi_sdf_lattice(_p(packed), _p(gamma), _p(beta), 1, _p(cax[0]), _p(cax[1]), _p(cax[2]), nb[0], nb[1], nb[2],
+                                  scale, _p(coarse), pack.prec, fast, _stream()), "oi_sdf_lattice")
+        nbytes = L.oi_band_workspace_bytes(nx, ny, nz, block)
+        if nbytes == 0:
+            msg = L.oi_last_error()
+            raise _l.OiHipError(f"sdf_lattice_band: {msg.decode() if msg else 'bad lattice'}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        field = torch.empty(1, nx, ny, nz, dtype=torch.float32, device=dev)
+        counts = (ctypes.c_longlong * 4)()
+        slope = ctypes.c_float(0.0)
+        _l.check(L.oi_band_classify(_p(coarse), 1, nx, ny, nz, block, h[0], h[1], h[2], iso, scale, lipschitz, _p(field),
+                                    _p(ws), nbytes, counts, ctypes.byref(slope), _stream()), "oi_band_classify")
+        n_active = int(counts[1])
+        if not slope.value <= lipschitz:
+            raise ValueError(f"sdf_lattice_band: slope {slope.value:.6g} seen between two block centres, above lipschitz="
+                             f"{lipschitz:.6g}: the bound on |d sdf/dx| is wrong for this field, no band field is returned "
+                             "(pass a larger lipschitz, or band=False)")
+        _l.check(L.oi_sdf_lattice_band(_p(packed), _p(gamma), _p(beta), 1, _p(xs), _p(ys), _p(zs), nx, ny, nz, block, _p(ws),
+                                       n_active, scale, _p(field), pack.prec, fast, _stream()), "oi_sdf_lattice_band")
+        active_list = ws[:4 * n_active].view(torch.int32)
+    info = BandInfo(block, int(counts[0]), n_active, int(counts[2]), int(counts[3]),
+                    int(counts[0]) + n_active * block ** 3, float(slope.value), lipschitz, coarse, active_list)
+    return field, info
+
+
+def _level_field(pack, bound_min, bound_max, resolution, threshold, z, w, band, lipschitz, block, what):
+    """The field u = -sdf the mesh entries run marching cubes on: dense (band=False, the path they always took) or narrow
+    band at the call's threshold.  -> (u (nx, ny, nz), BandInfo or None)."""
+    if not band:
+        if lipschitz is not None or block is not None:
+            raise ValueError(f"{what}: lipschitz= and block= belong to band=True")
+        return sdf_lattice(pack, bound_min, bound_max, resolution, z=z, w=w, scale=-1.0)[0], None
+    u, info = sdf_lattice_band(pack, bound_min, bound_max, resolution, threshold, z=z, w=w, scale=-1.0, lipschitz=lipschitz,
+                               block=block)
+    return u[0], info
 
 
 def marching_cubes(volume, isovalue):
@@ -210,6 +339,7 @@ class IntrinsicMesh:
     record: Optional[torch.Tensor] = None
     triangles: Optional[torch.Tensor] = None
     shaded: Optional[torch.Tensor] = None
+    band: Optional[BandInfo] = None   # extract_intrinsic_mesh(..., band=True) sets it
 
 
 def _check_refine(refine, what):
@@ -284,8 +414,11 @@ def vertex_attributes(pack_or_generator, vertices_index, bound_min, bound_max, r
 
 
 def extract_intrinsic_mesh(renderer_or_generator, z=None, w=None, resolution=256, threshold=0.0,
-                           bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), refine=2, want_record=False):
+                           bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), refine=2, want_record=False, band=False,
+                           lipschitz=None, block=None):
     """sdf_lattice -> marching_cubes -> vertex_attributes, nothing on the host in between except the mesh's sizes.
+    band=True: the field comes from sdf_lattice_band at `threshold` (lipschitz, block: its arguments) -- the same mesh from
+    fewer MLP evaluations; the BandInfo is returned in .band.
     -> IntrinsicMesh with triangles (F, 3) int32, the array marching_cubes returns for the same field.  The mesh is the level
     set u = -sdf = threshold (extract_geometry's convention): with threshold != 0 the vertices are refined towards
     sdf = -threshold."""
@@ -296,10 +429,12 @@ def extract_intrinsic_mesh(renderer_or_generator, z=None, w=None, resolution=256
     B = (w if w is not None else z).shape[0]
     if B != 1:
         raise ValueError(f"extract_intrinsic_mesh: one latent expected, got a batch of {B}")
-    u = sdf_lattice(pack, bound_min, bound_max, resolution, z=z, w=w, scale=-1.0)[0]
+    u, info = _level_field(pack, bound_min, bound_max, resolution, threshold, z, w, band, lipschitz, block,
+                           "extract_intrinsic_mesh")
     vi, tris = marching_cubes(u, threshold)
     del u
     out = vertex_attributes(pack, vi, bound_min, bound_max, resolution, z=z, w=w, refine=refine, threshold=threshold,
                             want_record=want_record)
     out.triangles = tris
+    out.band = info
     return out

@@ -110,10 +110,12 @@ class NeuSRenderer:
                                          "color_fine", "reduce4"))
         return assemble_render_dict(s, c, self.deviation_network.variance, background_rgb)
 
-    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, siren_network=None, z=None, w=None):
+    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, siren_network=None, z=None, w=None, band=False,
+                         lipschitz=None, block=None):
         """renderer.py:475-492: the mesh of u = -sdf at `threshold` -> numpy (V, 3) float64 world-space vertices, (F, 3) int64
         triangles.  The field comes from one lattice launch (oi_sdf_lattice: no points materialised, no query_func) and the
-        marching cubes run on the GPU (oi_mc_count / oi_mc_emit)."""
+        marching cubes run on the GPU (oi_mc_count / oi_mc_emit).  band=True: the field comes from mesh.sdf_lattice_band at
+        `threshold` (lipschitz, block: its arguments): the network runs only near the surface, the mesh is the same."""
         from . import mesh
         if siren_network is not None:
             raise NotImplementedError("siren_network is not on the path (as in render())")
@@ -123,14 +125,15 @@ class NeuSRenderer:
         if B != 1:
             raise ValueError(f"extract_geometry: one latent expected, got a batch of {B} (the reference's sdf(pts, z) would "
                              "split the lattice across them)")
-        u = mesh.sdf_lattice(self.pack, bound_min, bound_max, resolution, z=z, w=w, scale=-1.0)[0]
+        u, _ = mesh._level_field(self.pack, bound_min, bound_max, resolution, threshold, z, w, band, lipschitz, block,
+                                 "extract_geometry")
         vertices, triangles = mesh.marching_cubes(u, threshold)
         vertices = vertices.cpu().numpy().astype(np.float64)
         return mesh.to_world(vertices, bound_min, bound_max, resolution), triangles.cpu().numpy().astype(np.int64)
 
     def extract_intrinsic_geometry(self, bound_min, bound_max, resolution, threshold=0.0, siren_network=None, z=None, w=None,
-                                   refine=2):
-        """extract_geometry's arguments (plus `refine`), the intrinsic mesh out: numpy (V, 3) float64 world-space vertices moved
+                                   refine=2, band=False, lipschitz=None, block=None):
+        """extract_geometry's arguments (plus `refine`; band, lipschitz, block as there), the intrinsic mesh out: numpy (V, 3) float64 world-space vertices moved
         onto the level set sdf = -threshold by `refine` Newton steps, (F, 3) int64 triangles (those of extract_geometry),
         (V, 3) float32 unit normals d sdf/dx / |d sdf/dx| and (V, 3) float32 albedo.  oi_amd.mesh.extract_intrinsic_mesh has
         the device tensors, the residuals and the per-vertex flags."""
@@ -138,7 +141,7 @@ class NeuSRenderer:
         if siren_network is not None:
             raise NotImplementedError("siren_network is not on the path (as in render())")
         m = mesh.extract_intrinsic_mesh(self, z=z, w=w, resolution=resolution, threshold=threshold, bound_min=bound_min,
-                                        bound_max=bound_max, refine=refine)
+                                        bound_max=bound_max, refine=refine, band=band, lipschitz=lipschitz, block=block)
         return (m.positions.cpu().numpy().astype(np.float64), m.triangles.cpu().numpy().astype(np.int64),
                 m.normals.cpu().numpy(), m.albedo.cpu().numpy())
 

@@ -8,7 +8,16 @@
   extract_ms     NeuSRenderer.extract_geometry as a whole (field, marching cubes, mesh to the host, world scaling)
   attr0_ms / attr2_ms   the vertex pass of the intrinsic mesh (mesh.vertex_attributes) on the device
                  mesh with refine = 0 / 2; attr2_vs_extract = attr2_ms / extract_ms; flagged = flagged vertices at refine = 2;
-                 residual_before / residual_after = median |sdf| / |grad| at the marching-cubes vertices / after two steps"""
+                 residual_before / residual_after = median |sdf| / |grad| at the marching-cubes vertices / after two steps
+
+--band: the narrow band instead, per resolution (default 128,256,512,1024) and block size 4 and 8, dense
+and band timed in the same session:
+  field_dense_ms / field_band_ms       sdf_lattice / sdf_lattice_band (coarse pass + classification + band launch + read-back)
+  coarse_ms                            the dense kernel on the coarse lattice alone
+  extract_dense_ms / extract_band_ms   NeuSRenderer.extract_geometry(band=False / True)
+  intrinsic_dense_ms / intrinsic_band_ms   mesh.extract_intrinsic_mesh(refine=2, band=False / True)
+  active_fraction (of the blocks), evaluated_fraction a (active-block points / lattice points), points_evaluated, n_triangles,
+  identical (vertices, triangles and records byte-identical), bar_ms = 1.5 (a field_dense_ms + coarse_ms), bar_met"""
 import argparse
 import json
 import os
@@ -25,10 +34,13 @@ from oi_amd.fields import ShapeNetwork, ColorNetwork, SingleVarianceNetwork  # n
 from oi_amd.renderer import NeuSRenderer  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--res", default="128,256,512")
+ap.add_argument("--res", default=None)
+ap.add_argument("--band", action="store_true")
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=10)
 args = ap.parse_args()
+if args.res is None:
+    args.res = "128,256,512,1024" if args.band else "128,256,512"
 
 
 def median_ms(fn):
@@ -52,6 +64,39 @@ r = NeuSRenderer(None, net, SingleVarianceNetwork(0.3).cuda(), ColorNetwork(**kw
 z = torch.randn(1, 64, generator=torch.Generator().manual_seed(0)).cuda()
 bmin, bmax = torch.tensor([-1.0, -1.0, -1.0]), torch.tensor([1.0, 1.0, 1.0])
 out = {"tool": "bench_mesh", "precision": "f16x3", "iters": args.iters, "warmup": args.warmup, "res": {}}
+if args.band:
+    out["band"] = {}
+    with torch.no_grad():
+        for R in (int(x) for x in args.res.split(",")):
+            dense = {"field_dense_ms": median_ms(lambda: mesh.sdf_lattice(r.pack, bmin, bmax, R, z=z, scale=-1.0)),
+                     "extract_dense_ms": median_ms(lambda: r.extract_geometry(bmin, bmax, R, 0.0, z=z)),
+                     "intrinsic_dense_ms": median_ms(lambda: mesh.extract_intrinsic_mesh(r, z=z, resolution=R, refine=2))}
+            v0, t0 = r.extract_geometry(bmin, bmax, R, 0.0, z=z)
+            m0 = mesh.extract_intrinsic_mesh(r, z=z, resolution=R, refine=2, want_record=True)
+            for block in (4, 8):
+                nb = (R + block - 1) // block
+                row = dict(dense)
+                row["field_band_ms"] = median_ms(lambda: mesh.sdf_lattice_band(r.pack, bmin, bmax, R, 0.0, z=z, scale=-1.0, block=block))
+                row["coarse_ms"] = median_ms(lambda: mesh.sdf_lattice(r.pack, bmin, bmax, max(nb, 2), z=z, scale=-1.0))
+                row["extract_band_ms"] = median_ms(lambda: r.extract_geometry(bmin, bmax, R, 0.0, z=z, band=True, block=block))
+                row["intrinsic_band_ms"] = median_ms(lambda: mesh.extract_intrinsic_mesh(r, z=z, resolution=R, refine=2, band=True, block=block))
+                _, info = mesh.sdf_lattice_band(r.pack, bmin, bmax, R, 0.0, z=z, scale=-1.0, block=block)
+                v1, t1 = r.extract_geometry(bmin, bmax, R, 0.0, z=z, band=True, block=block)
+                m1 = mesh.extract_intrinsic_mesh(r, z=z, resolution=R, refine=2, want_record=True, band=True, block=block)
+                a = info.active_blocks * block ** 3 / float(R) ** 3
+                row.update(active_fraction=info.active_fraction, evaluated_fraction=a, points_evaluated=info.points_evaluated,
+                           max_slope=info.max_slope, n_triangles=int(t0.shape[0]),
+                           identical=bool(v0.tobytes() == v1.tobytes() and t0.tobytes() == t1.tobytes() and
+                                          torch.equal(m0.record, m1.record) and torch.equal(m0.triangles, m1.triangles)),
+                           bar_ms=1.5 * (a * row["field_dense_ms"] + row["coarse_ms"]))
+                row["bar_met"] = bool(row["field_band_ms"] <= row["bar_ms"])
+                out["band"].setdefault(str(R), {})[str(block)] = {k: (round(x, 4) if isinstance(x, float) else x) for k, x in row.items()}
+                del m1, v1, t1
+            del m0, v0, t0
+            torch.cuda.empty_cache()
+    print(json.dumps(out))
+    sys.exit(0)
+
 with torch.no_grad():
     _, gamma, beta = r.pack.film(z=z)
     for R in (int(x) for x in args.res.split(",")):

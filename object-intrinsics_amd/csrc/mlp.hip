@@ -498,159 +498,458 @@ __device__ unsigned long long oi_prof[16];
 #define PROF_T(i)
 #endif
 
-// The kernel is stamped out three times from sdf_mlp_kernel.inc, once per point source, rather than shared through a device
-// function: a forced-inline body is simplified by hipcc before it is inlined, and that alone changed the instructions and
-// register counts of every array instantiation.  Included, the array kernel is token for token what it was.
-//   OI_SDF_LATTICE 0: sdf_mlp_kernel<PREC, FAST, FULL>, points read from pts[pt * 3 + {0,1,2}];
-//   OI_SDF_LATTICE 1: sdf_lattice_kernel<PREC, FAST, false> (oi_sdf_lattice), the point of local index
-//     loc = (ix * ny + iy) * nz + iz computed from xs[nx], ys[ny], zs[nz] -- z fastest, the order of torch.meshgrid
-//     (indexing='ij') in the reference's extract_fields (renderer.py:15-31) -- and out = scale * sdf.  nx * ny * nz < 2^31
-//     (checked by oi_sdf_lattice), so the local index fits 32 bits.
-#define OI_SDF_LATTICE 0
-#include "sdf_mlp_kernel.inc"
-#undef OI_SDF_LATTICE
+// POINT SOURCES of sdf_mlp_kernel.  A source is a struct that provides
+//   Arg                               the kernel's first argument, which the source is built from: the struct itself, or for
+//                                     ArraySrc the restrict pointer (inside a struct it loses noalias and its early kernarg load);
+//   static constexpr bool ARRAY       true: the caller owns a point array, so the full pass (FULL) and feat_out exist;
+//   load(pt, e, n_per_elem, x, y, z)  the coordinates of global point pt = e * n_per_elem + local index (always in range);
+//   store(out, pt, e, n_per_elem, sdf) the write of that point's sdf -- called for valid points only, once per point.
+// The lattice sources recover the local index as a 32-bit value: oi_sdf_lattice checks n < 2^31 and oi_sdf_lattice_band
+// n_active * b^3 <= 2^30 (axes <= 1024) before they launch.
+struct ArraySrc {  // points read from pts[pt * 3 + {0,1,2}]
+  const float* __restrict__ pts;
+  using Arg = const float* __restrict__;
+  static constexpr bool ARRAY = true;
+  __device__ __forceinline__ void load(long long pt, int, long long, float& x, float& y, float& z) const {
+    x = pts[pt * 3 + 0], y = pts[pt * 3 + 1], z = pts[pt * 3 + 2];
+  }
+  __device__ __forceinline__ void store(float* __restrict__ out, long long pt, int, long long, float sdf) const {
+    out[pt] = sdf;
+  }
+};
 
-#define OI_LATTICE_POINT(x, y, z)                                                                            \
-  do {                                                                                                       \
-    const unsigned loc_ = (unsigned)(pt - (long long)e * n_per_elem), nyz_ = (unsigned)lat_ny * lat_nz;      \
-    const unsigned ix_ = loc_ / nyz_, r_ = loc_ - ix_ * nyz_, iy_ = r_ / (unsigned)lat_nz;                   \
-    x = xs[ix_], y = ys[iy_], z = zs[r_ - iy_ * (unsigned)lat_nz];                                           \
-  } while (0)
-#define OI_SDF_LATTICE 1
-#include "sdf_mlp_kernel.inc"
-#undef OI_SDF_LATTICE
-#undef OI_LATTICE_POINT
+// oi_sdf_lattice: the point of local index loc = (ix * ny + iy) * nz + iz computed from xs[nx], ys[ny], zs[nz] -- z fastest,
+// the order of torch.meshgrid (indexing='ij') in the reference's extract_fields (renderer.py:15-31) -- and out = scale * sdf.
+struct LatticeSrc {
+  const float *__restrict__ xs, *__restrict__ ys, *__restrict__ zs;
+  int ny, nz;
+  float scale;
+  using Arg = LatticeSrc;
+  static constexpr bool ARRAY = false;
+  __device__ __forceinline__ void load(long long pt, int e, long long n_per_elem, float& x, float& y, float& z) const {
+    const unsigned loc_ = (unsigned)(pt - (long long)e * n_per_elem), nyz_ = (unsigned)ny * nz;
+    const unsigned ix_ = loc_ / nyz_, r_ = loc_ - ix_ * nyz_, iy_ = r_ / (unsigned)nz;
+    x = xs[ix_], y = ys[iy_], z = zs[r_ - iy_ * (unsigned)nz];
+  }
+  __device__ __forceinline__ void store(float* __restrict__ out, long long pt, int, long long, float sdf) const {
+    out[pt] = scale * sdf;
+  }
+};
 
-//   OI_SDF_LATTICE 2: sdf_band_kernel<PREC, FAST, false> (oi_sdf_lattice_band, include/oi_mesh_band.h): point loc of the
-//     launch is the local point loc % b^3 = (lx * b + ly) * b + lz of block band_list[loc / b^3] = (bi * nby + bj) * nbz + bk,
-//     b = 1 << band_lb; it reads (xs[b bi + lx], ys[b bj + ly], zs[b bk + lz]), each index clamped to its axis, and stores
-//     scale * sdf to the dense field at (ix * ny + iy) * nz + iz -- or nothing when the point lies beyond the lattice (the
-//     ragged last block of an axis) or the block id beyond the block lattice.  n_active * b^3 <= 2^30 (axes <= 1024).
-//     The two stampings above are, token for token, what they were before this one existed.
-#define OI_BAND_INDEX                                                                                                  \
-  const unsigned loc_ = (unsigned)(pt - (long long)e * n_per_elem), bm_ = (1u << band_lb) - 1u;                        \
-  const unsigned blk_ = band_list[loc_ >> (3 * band_lb)], l_ = loc_ & ((1u << (3 * band_lb)) - 1u);                    \
-  const unsigned nbx_ = ((unsigned)lat_nx + bm_) >> band_lb, nby_ = ((unsigned)lat_ny + bm_) >> band_lb,               \
-                 nbz_ = ((unsigned)lat_nz + bm_) >> band_lb;                                                           \
-  const unsigned bi_ = blk_ / (nby_ * nbz_), br_ = blk_ - bi_ * (nby_ * nbz_), bj_ = br_ / nbz_, bk_ = br_ - bj_ * nbz_; \
-  const unsigned ix_ = (bi_ << band_lb) + (l_ >> (2 * band_lb)), iy_ = (bj_ << band_lb) + ((l_ >> band_lb) & bm_),     \
-                 iz_ = (bk_ << band_lb) + (l_ & bm_)
-#define OI_LATTICE_POINT(x, y, z)                                                                                      \
-  do {                                                                                                                 \
-    OI_BAND_INDEX;                                                                                                     \
-    x = xs[min(ix_, (unsigned)lat_nx - 1u)], y = ys[min(iy_, (unsigned)lat_ny - 1u)],                                  \
-    z = zs[min(iz_, (unsigned)lat_nz - 1u)];                                                                           \
-  } while (0)
-#define OI_LATTICE_STORE(v)                                                                                            \
-  do {                                                                                                                 \
-    OI_BAND_INDEX;                                                                                                     \
-    if (bi_ < nbx_ && ix_ < (unsigned)lat_nx && iy_ < (unsigned)lat_ny && iz_ < (unsigned)lat_nz)                      \
-      sdf_out[((size_t)ix_ * (unsigned)lat_ny + iy_) * (unsigned)lat_nz + iz_] = (v);                                  \
-  } while (0)
-#define OI_SDF_LATTICE 2
-#include "sdf_mlp_kernel.inc"
-#undef OI_SDF_LATTICE
-#undef OI_LATTICE_POINT
-#undef OI_LATTICE_STORE
-#undef OI_BAND_INDEX
+// oi_sdf_lattice_band (include/oi_mesh_band.h): point loc of the launch is the local point loc % b^3 = (lx * b + ly) * b + lz of
+// block list[loc / b^3] = (bi * nby + bj) * nbz + bk, b = 1 << lb; it reads (xs[b bi + lx], ys[b bj + ly], zs[b bk + lz]), each
+// index clamped to its axis, and stores scale * sdf to the dense field at (ix * ny + iy) * nz + iz -- or nothing when the point
+// lies beyond the lattice (the ragged last block of an axis) or the block id beyond the block lattice.
+struct BandSrc {
+  const float *__restrict__ xs, *__restrict__ ys, *__restrict__ zs;
+  int nx, ny, nz, lb;
+  const unsigned* __restrict__ list;
+  float scale;
+  using Arg = BandSrc;
+  static constexpr bool ARRAY = false;
+  struct Index { unsigned bi, nbx, ix, iy, iz; };
+  __device__ __forceinline__ Index index(long long pt, int e, long long n_per_elem) const {
+    const unsigned loc_ = (unsigned)(pt - (long long)e * n_per_elem), bm_ = (1u << lb) - 1u;
+    const unsigned blk_ = list[loc_ >> (3 * lb)], l_ = loc_ & ((1u << (3 * lb)) - 1u);
+    const unsigned nbx_ = ((unsigned)nx + bm_) >> lb, nby_ = ((unsigned)ny + bm_) >> lb, nbz_ = ((unsigned)nz + bm_) >> lb;
+    const unsigned bi_ = blk_ / (nby_ * nbz_), br_ = blk_ - bi_ * (nby_ * nbz_), bj_ = br_ / nbz_, bk_ = br_ - bj_ * nbz_;
+    return {bi_, nbx_, (bi_ << lb) + (l_ >> (2 * lb)), (bj_ << lb) + ((l_ >> lb) & bm_), (bk_ << lb) + (l_ & bm_)};
+  }
+  __device__ __forceinline__ void load(long long pt, int e, long long n_per_elem, float& x, float& y, float& z) const {
+    const Index i = index(pt, e, n_per_elem);
+    x = xs[min(i.ix, (unsigned)nx - 1u)], y = ys[min(i.iy, (unsigned)ny - 1u)], z = zs[min(i.iz, (unsigned)nz - 1u)];
+  }
+  __device__ __forceinline__ void store(float* __restrict__ out, long long pt, int e, long long n_per_elem, float sdf) const {
+    const Index i = index(pt, e, n_per_elem);
+    if (i.bi < i.nbx && i.ix < (unsigned)nx && i.iy < (unsigned)ny && i.iz < (unsigned)nz)
+      out[((size_t)i.ix * (unsigned)ny + i.iy) * (unsigned)nz + i.iz] = scale * sdf;
+  }
+};
 
-template <int PREC, bool FAST, bool FULL>
-int launch_mlp_variant(const float* pts, const char* pk, const float* gamma, const float* beta, float* sdf, float* grad,
-                       float* rgb, float* feat, char* scratch, int B, long long n, hipStream_t st) {
+template <int PREC, bool FAST, bool FULL, class SRC>
+__global__ void __launch_bounds__(64 * V2_WAVES, 2)
+sdf_mlp_kernel(const typename SRC::Arg arg, const char* __restrict__ packed, const float* __restrict__ gamma,
+               const float* __restrict__ beta, float* __restrict__ sdf_out, float* __restrict__ grad_out,
+               float* __restrict__ rgb_out, float* __restrict__ feat_out, char* __restrict__ scratch,
+               long long n_per_elem) {
+  static_assert(!FULL || SRC::ARRAY, "the lattice point sources serve the sdf-only pass");
+  const SRC src{arg};
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int h = lane >> 5, j = lane & 31;
+  const int e = blockIdx.y;
+  const float* hdr = reinterpret_cast<const float*>(packed);
+  const char* mats = packed + H_BYTES;
+  constexpr int LB = layer_bytes(PREC);
+  constexpr bool RING2 = v2_two_slots(PREC);
   constexpr int NWV = V2_WAVES;
-  constexpr int LDS_BYTES = v2_lds_total(PREC);
-  // the sdf-only passes run persistent workgroups (one per CU: the LDS): as many as the device has CUs (/ B), each walks its
-  // share of the tiles; OI_V2_PERSIST=0 (environment): one workgroup per tile, the same kernel (A/B switch)
-  static const int per_dev = [] {
+  constexpr bool REV = PREC == OI_PREC_F16X3 && !FULL;  // FiLM rows in revolutions (see film_sin2)
+  // double-buffered ring: the next image is requested at the START of a layer into the other slot.
+  // single slot (BF16X6): it is requested right AFTER the layer's MFMAs, behind a barrier, and lands while the
+  // FiLM/sin VALU phase runs.
+  LaneOff o;
+  o.h16 = 16 * h;
+  o.h64 = 64 * h;
+  o.l16 = 16 * lane;
+  o.l16hi = 16 * lane + 32768;
+  asm volatile("" : "+v"(o.h16), "+v"(o.h64), "+v"(o.l16), "+v"(o.l16hi));
+
+  const __amdgpu_buffer_rsrc_t img_rs =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(mats), 0, NMAT * LB, 0x00020000);
+  auto stage_early = [&](int image, int slot) {
+    if constexpr (RING2) prefetch_image<PREC, NWV>(lds, img_rs, image * LB, slot, wave, o.l16);
+  };
+  auto stage_late = [&](int image) {
+    if constexpr (!RING2) {
+      __syncthreads();
+      prefetch_image<PREC, NWV>(lds, img_rs, image * LB, 0, wave, o.l16);
+    }
+  };
+
+  constexpr int NW = NWV, NT = 64 * NW;
+  // PERSISTENT workgroups for the sdf-only passes (round 5; launch_sdf sizes the grid): a workgroup walks tiles
+  // blockIdx.x, + gridDim.x, ... of its batch element -- tables and FiLM rows are staged once instead of once per tile, the
+  // last layer of a tile requests image 0 of the next one (7 images on a two-slot ring: `rb` swaps the slots per tile).
+  constexpr bool PERSIST = !FULL && RING2;
+  const int ntiles = (int)((n_per_elem + NW * WAVE_PTS - 1) / (NW * WAVE_PTS));
+  int tile = blockIdx.x, rb = 0;
+  bool valid;
+  long long pt;
+  auto set_point = [&](int t_) {
+    const long long local = (long long)t_ * (NW * WAVE_PTS) + wave * WAVE_PTS + j;
+    valid = local < n_per_elem;
+    pt = (long long)e * n_per_elem + (valid ? local : n_per_elem - 1);
+  };
+  set_point(tile);
+
+  constexpr bool HALF_SCR = PREC == OI_PREC_BF16;
+  constexpr int SLOT_B = HALF_SCR ? 8192 : 16384;
+  FwdScratch<HALF_SCR> ws;
+  {
+    const long long wt = ((long long)e * gridDim.x + blockIdx.x) * NW + wave;
+    char* wbase = FULL ? scratch + wt * (long long)(NSLOT * SLOT_B) : nullptr;
+    ws.rs = __builtin_amdgcn_make_buffer_rsrc(wbase, 0, FULL ? NSLOT * SLOT_B : 0, 0x00020000);
+  }
+
+  // image sequence: i = 0..6 forward layers 1..7 (mats 0..6), i = 7..13 transposed layers 7..1 (mats 13..7),
+  // i = 14 colour head (mat 14); image i lives in ring slot i & 1.
+  prefetch_image<PREC, NWV>(lds, img_rs, 0, 0, wave, o.l16);
+  {  // small tables + FiLM rows of all 9 layers (gamma | beta | bias), once
+    float* tabs = reinterpret_cast<float*>(lds + V2_TABS);
+    for (int i = tid; i < H_TABS_END; i += NT) tabs[i] = hdr[i];
+    float* film = reinterpret_cast<float*>(lds + V2_FILM);
+    for (int i = tid; i < 9 * C; i += NT) {
+      const int l = i / C, f = i % C;
+      const float gm = gamma[((size_t)e * 9 + l) * C + f];
+      // image scale of the layer's MFMA operand folded into the multiplier of u (layer 0 runs on the VALU)
+      const float ws = l == 0 ? 1.f : hdr[H_WSCALE + (l < NL_SDF ? l - 1 : 14)];
+      constexpr float TO_REV = REV ? 0.15915494309189533577f : 1.f;
+      film[l * 256 + f] = gm * ws * TO_REV;
+      film[l * 256 + C + f] = fmaf(gm, hdr[H_BIAS + l * C + f], beta[((size_t)e * 9 + l) * C + f]) * TO_REV;
+    }
+  }
+  float px, py, pz;
+  src.load(pt, e, n_per_elem, px, py, pz);
+  __syncthreads();  // tables visible (image 0 still in flight)
+
+  float act[64];
+  f32x16 acc[4];
+#ifdef OI_PROF
+  unsigned long long pacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long tprev = __builtin_readcyclecounter();
+  const unsigned long long tstart = tprev;
+#endif
+  for (;;) {  // ---- one tile per trip (exactly one unless PERSIST)
+  const int ntile = tile + (int)gridDim.x;
+  float nx = 0.f, ny = 0.f, nz = 0.f;
+  if constexpr (PERSIST) {  // the next tile's point, used a tile later (a clamped re-read of this one on the last trip)
+    set_point(ntile < ntiles ? ntile : tile);
+    src.load(pt, e, n_per_elem, nx, ny, nz);
+    set_point(tile);
+  }
+
+  // ---- layer 0 (K = 3) on the VALU, overlapping the first image's DMA
+  {
+    const LayOff y = lay_off<PREC>(o, 0, 0);
+    film_sin2<FAST, FULL, 1, FwdScratch<HALF_SCR>, REV>(lds, o, y, acc, act, ws, 0, H_TAB0, px, py, pz);
+  }
+  PROF_T(0);
+  ring_sync();
+  PROF_T(4);
+
+  // ---- layers 1..7 on MFMA
+  for (int l = 1; l < NL_SDF; ++l) {
+    const int i = l - 1;
+    // next image: forward layer l+1, or the first transposed image (layer 7) / nothing for the sdf-only variant
+    const int next = (l < NL_SDF - 1) ? l : (FULL ? 13 : (PERSIST ? 0 : -1));  // image index, -1: none; PERSIST: the next tile's first
+    if (next >= 0) stage_early(next, ((i + 1) & 1) ^ rb);
+    const LayOff y = lay_off<PREC>(o, RING2 ? ((i & 1) ^ rb) : 0, l);
+    if constexpr (PREC == OI_PREC_F16X3 && RING2) {
+      layer_fwd_pipelined<FAST, FULL, REV>(lds, o, y, acc, act, ws, l);
+      PROF_T(1);
+    } else
+    {
+      zero_acc(acc);
+      gemm_layer2<PREC>(lds, y, act, acc);
+      PROF_T(1);
+      if (next >= 0) stage_late(next);
+      PROF_T(2);
+      film_sin2<FAST, FULL, 0, FwdScratch<HALF_SCR>, REV>(lds, o, y, acc, act, ws, l, 0, 0.f, 0.f, 0.f);
+    }
+    PROF_T(3);
+    ring_sync();
+    PROF_T(4);
+  }
+
+  // ---- sdf = a8 . wsig + bsig   (fields.py:68; LinearLayer std_init=1, bias_init=0)
+  float sdf_v;
+  {
+    float part = 0.f;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      const f32x4 w = lds_f4(lds, V2_TABS + (H_SIG + grp_f0(g)) * 4, o.h16);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) part = fmaf(act[4 * g + k], w[k], part);
+    }
+    part += __shfl_xor(part, 32, 64);
+    sdf_v = part + *reinterpret_cast<const float*>(lds + V2_TABS + (H_SIG + C) * 4);
+  }
+  if (valid && h == 0) src.store(sdf_out, pt, e, n_per_elem, sdf_v);
+
+  if (SRC::ARRAY && feat_out != nullptr && valid) {
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      f32x4 v;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = act[4 * g + k];
+      *reinterpret_cast<f32x4*>(feat_out + pt * C + grp_f0(g) + 4 * h) = v;
+    }
+  }
+
+  if (!PERSIST || ntile >= ntiles) break;
+  tile = ntile;
+  rb ^= 1;
+  set_point(tile);
+  px = nx, py = ny, pz = nz;
+  }  // tiles
+
+  if constexpr (FULL) {
+    // park the features (slot 8) and start the reverse sweep with g8 = wsig
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      f32x4 v;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = act[4 * g + k];
+      ws.store(8, g, o, v);
+    }
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      const f32x4 w = lds_f4(lds, V2_TABS + (H_SIG + grp_f0(g)) * 4, o.h16);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) act[4 * g + k] = w[k];
+    }
+    float run = 1.f;
+    // gamma * cos(phi) of the layer about to be swept: requested ONE GEMM AHEAD (inside the previous layer's MFMA loop,
+    // into registers the consumed B operand has just freed) so that the HBM latency hides under the MFMAs instead of
+    // stalling the top of every layer
+    f32x4 cn[16];
+#pragma unroll
+    for (int g = 0; g < 16; ++g) cn[g] = ws.load(NL_SDF - 1, g, o);
+    for (int l = NL_SDF - 1; l >= 1; --l) {
+      const int i = 14 - l;  // image index of transposed layer l
+#pragma unroll
+      for (int g = 0; g < 16; ++g) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) act[4 * g + k] *= cn[g][k];
+      }
+      if constexpr (PREC == OI_PREC_F16X3) {
+        // adjoints have no a-priori range: bring this point's vector (its 128 entries live in lanes j and j+32)
+        // to max |.| in [2^13, 2^14) with an exact power-of-two scale.  The scale is NOT undone layer by layer: `run`
+        // carries the product of the inverse scales (true vector = act * run) and multiplies the final gradient once.
+        float m = 0.f;
+#pragma unroll
+        for (int k = 0; k < 64; k += 2) m = fmaxf(m, fmaxf(fabsf(act[k]), fabsf(act[k + 1])));
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        int eb = (__builtin_bit_cast(int, m) >> 23) & 0xff;
+        eb = eb < 14 ? 14 : (eb > 254 ? 254 : eb);
+        float sc = __builtin_bit_cast(float, (267 - eb) << 23);  // 2^(13 - (eb - 127))
+        // fence tied to sc (= to every c * g product): keeps the GEMM's A-fragment ds_reads from being scheduled
+        // into the scratch-load phase while the 64 c registers are still live (140 spilled VGPRs otherwise)
+        asm volatile("" : "+v"(sc) : : "memory");
+        run *= __builtin_bit_cast(float, (eb - 13) << 23);             // 1 / sc
+#pragma unroll
+        for (int k = 0; k < 64; ++k) act[k] *= sc;
+      }
+      // next image after the scratch loads have been consumed (an in-flight LDS-DMA would otherwise be
+      // drained by the vmcnt wait hipcc places in front of the first use of an ordinary load)
+      const int next = (l > 1) ? 7 + l - 2 : (rgb_out != nullptr ? 14 : -1);
+      if (next >= 0) stage_early(next, (i + 1) & 1);
+      const LayOff y = lay_off<PREC>(o, RING2 ? (i & 1) : 0, l);
+      zero_acc(acc);
+      PROF_T(5);
+      gemm_layer2<PREC>(lds, y, act, acc, [&](int s) {
+        cn[2 * s] = ws.load(l - 1, 2 * s, o);
+        cn[2 * s + 1] = ws.load(l - 1, 2 * s + 1, o);
+      });
+      PROF_T(6);
+      if (next >= 0) stage_late(next);
+      PROF_T(7);
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) act[16 * t + r] = acc[t][r];
+      ring_sync();
+      PROF_T(8);
+    }
+    // layer 0: grad = W0^T (g1 * c0)
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      const f32x4 c = cn[g];  // slot 0, requested during the last transposed GEMM
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float v = act[4 * g + k] * c[k];
+        const f32x4 w = lds_f4(lds, V2_TABS + H_TAB0 * 4 + (grp_f0(g) + k) * 16, o.h64);
+        gx = fmaf(v, w[0], gx);
+        gy = fmaf(v, w[1], gy);
+        gz = fmaf(v, w[2], gz);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    gx += __shfl_xor(gx, 32, 64);
+    gy += __shfl_xor(gy, 32, 64);
+    gz += __shfl_xor(gz, 32, 64);
+    gx *= run;  // identical in both lanes of a point (the max was taken over the pair)
+    gy *= run;
+    gz *= run;
+    if (valid && h == 0) {
+      grad_out[pt * 3 + 0] = gx;
+      grad_out[pt * 3 + 1] = gy;
+      grad_out[pt * 3 + 2] = gz;
+    }
+
+    if (rgb_out != nullptr) {
+      // ---- colour head: sigmoid(Wrgb sin(gv * (Wv [feat, grad] + bv) + bv') + brgb)   (fields.py:89-101)
+      // image 14 (ring slot 0) was prefetched during transposed layer 1 and is resident after its ring_sync
+#pragma unroll
+      for (int g = 0; g < 16; ++g) {
+        const f32x4 v = ws.load(8, g, o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) act[4 * g + k] = v[k];
+        if ((g & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+      }
+      const LayOff y = lay_off<PREC>(o, 0, 8);
+      zero_acc(acc);
+      gemm_layer2<PREC>(lds, y, act, acc);
+      // the accumulators carry the image scale 2^k (1 unless F16X3): bring the rank-3 gradient term to the same scale
+      const float cs = 1.0f / hdr[H_WSCALE + 14];
+      film_sin2<FAST, false, 2>(lds, o, y, acc, act, ws, 0, H_TABV, gx * cs, gy * cs, gz * cs);
+      float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+#pragma unroll
+      for (int g = 0; g < 16; ++g) {
+        const f32x4 w0 = lds_f4(lds, V2_TABS + (H_RGB + 0 * C + grp_f0(g)) * 4, o.h16);
+        const f32x4 w1 = lds_f4(lds, V2_TABS + (H_RGB + 1 * C + grp_f0(g)) * 4, o.h16);
+        const f32x4 w2 = lds_f4(lds, V2_TABS + (H_RGB + 2 * C + grp_f0(g)) * 4, o.h16);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          r0 = fmaf(act[4 * g + k], w0[k], r0);
+          r1 = fmaf(act[4 * g + k], w1[k], r1);
+          r2 = fmaf(act[4 * g + k], w2[k], r2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      r0 += __shfl_xor(r0, 32, 64);
+      r1 += __shfl_xor(r1, 32, 64);
+      r2 += __shfl_xor(r2, 32, 64);
+      if (valid && h == 0) {
+        const float* brgb = reinterpret_cast<const float*>(lds + V2_TABS + (H_RGB + 3 * C) * 4);
+        rgb_out[pt * 3 + 0] = oi::sigmoidf_(r0 + brgb[0]);
+        rgb_out[pt * 3 + 1] = oi::sigmoidf_(r1 + brgb[1]);
+        rgb_out[pt * 3 + 2] = oi::sigmoidf_(r2 + brgb[2]);
+      }
+    }
+  }
+#ifdef OI_PROF
+  PROF_T(9);
+  if (lane == 0 && FULL) {
+    for (int i = 0; i < 10; ++i) atomicAdd(&oi_prof[i], pacc[i]);
+    atomicAdd(&oi_prof[10], __builtin_readcyclecounter() - tstart);
+    atomicAdd(&oi_prof[11], 1ull);
+  }
+#endif
+}
+
+// CUs of the device, read once: the size of a persistent grid.  0 with OI_V2_PERSIST=0 in the environment (A/B switch: one
+// workgroup per tile, the same kernel); the switch governs all three point sources.
+int persist_cus() {
+  static const int cus = [] {
     const char* v = getenv("OI_V2_PERSIST");
     if (v && v[0] == '0') return 0;
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return cus > 0 ? cus : 256;
-  }();
-  const int tiles = oi::cdiv(n, NWV * WAVE_PTS);
-  const bool persist = !FULL && v2_two_slots(PREC) && per_dev > 0;
-  dim3 grid(persist ? std::min(tiles, std::max(1, per_dev / B)) : tiles, B), block(64 * NWV);
-  auto k = sdf_mlp_kernel<PREC, FAST, FULL>;
-  // per launch: the attribute is per device, and a process may drive several
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-  hipLaunchKernelGGL(k, grid, block, LDS_BYTES, st, pts, pk, gamma, beta, sdf, grad, rgb, feat, scratch, n);
-  return oi::check_launch("oi_sdf_mlp_fwd");
-}
-
-template <int PREC, bool FAST>
-int launch_lattice(const float* xs, const float* ys, const float* zs, int ny, int nz, float scale, const char* pk,
-                   const float* gamma, const float* beta, float* out, int B, long long n, hipStream_t st) {
-  constexpr int NWV = V2_WAVES;
-  constexpr int LDS_BYTES = v2_lds_total(PREC);
-  // the grid of launch_mlp_variant's sdf-only pass: persistent workgroups (one per CU) on the two-slot precisions
-  static const int cus = [] {
     int dev = 0, c = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
     return c > 0 ? c : 256;
   }();
-  const int tiles = oi::cdiv(n, NWV * WAVE_PTS);
-  dim3 grid(v2_two_slots(PREC) ? std::min(tiles, std::max(1, cus / B)) : tiles, B), block(64 * NWV);
-  auto k = sdf_lattice_kernel<PREC, FAST, false>;
-  // dynamic LDS above 64 KiB: the attribute, once per device (bit d of `set`; a process may drive several)
-  static std::atomic<unsigned long long> set{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 64 || !((set.load() >> dev) & 1ull)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) !=
-        hipSuccess)
-      return oi::fail(OI_ERR_LAUNCH, "oi_sdf_lattice: hipFuncSetAttribute(%d B of LDS) failed", LDS_BYTES);
-    if (dev < 64) set.fetch_or(1ull << dev);
-  }
-  hipLaunchKernelGGL(k, grid, block, LDS_BYTES, st, xs, ys, zs, ny, nz, scale, pk, gamma, beta, out, n);
-  return oi::check_launch("oi_sdf_lattice");
+  return cus;
 }
 
-// oi_sdf_lattice_band: launch_lattice's grid rule and LDS attribute for the block-list stamping, one batch element
-template <int PREC, bool FAST>
-int launch_band(const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, int lb, const unsigned* list,
-                float scale, const char* pk, const float* gamma, const float* beta, float* out, long long n,
-                hipStream_t st) {
-  constexpr int NWV = V2_WAVES;
-  constexpr int LDS_BYTES = v2_lds_total(PREC);
-  static const int cus = [] {
-    int dev = 0, c = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-    return c > 0 ? c : 256;
-  }();
-  const int tiles = oi::cdiv(n, NWV * WAVE_PTS);
-  dim3 grid(v2_two_slots(PREC) ? std::min(tiles, cus) : tiles, 1), block(64 * NWV);
-  auto k = sdf_band_kernel<PREC, FAST, false>;
-  // dynamic LDS above 64 KiB: the attribute, once per device (bit d of `set`; a process may drive several)
-  static std::atomic<unsigned long long> set{0};
+// dynamic LDS above 64 KiB needs the attribute: set once per device (bit d of the kernel's `set`; a process may drive several)
+int allow_dynamic_lds(const void* kernel, int bytes, std::atomic<unsigned long long>& set, const char* name) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev >= 64 || !((set.load() >> dev) & 1ull)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) !=
-        hipSuccess)
-      return oi::fail(OI_ERR_LAUNCH, "oi_sdf_lattice_band: hipFuncSetAttribute(%d B of LDS) failed", LDS_BYTES);
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+      return oi::fail(OI_ERR_LAUNCH, "%s: hipFuncSetAttribute(%d B of LDS) failed", name, bytes);
     if (dev < 64) set.fetch_or(1ull << dev);
   }
-  hipLaunchKernelGGL(k, grid, block, LDS_BYTES, st, xs, ys, zs, nx, ny, nz, lb, list, scale, pk, gamma, beta, out, n);
-  return oi::check_launch("oi_sdf_lattice_band");
+  return OI_OK;
+}
+
+// One launch of sdf_mlp_kernel for entry point `name`.  The sdf-only passes of the two-slot precisions run persistent
+// workgroups (one per CU: the LDS), as many as the device has CUs (/ B), each walking its share of the tiles.
+template <int PREC, bool FAST, bool FULL, class SRC>
+int launch_sdf(const typename SRC::Arg& arg, const void* packed, const float* gamma, const float* beta, float* sdf, float* grad,
+               float* rgb, float* feat, void* scratch, int B, long long n, const char* name, hipStream_t st) {
+  constexpr int LDS_BYTES = v2_lds_total(PREC);
+  const int tiles = oi::cdiv(n, V2_WAVES * WAVE_PTS), cus = persist_cus();
+  const bool persist = !FULL && v2_two_slots(PREC) && cus > 0;
+  dim3 grid(persist ? std::min(tiles, std::max(1, cus / B)) : tiles, B), block(64 * V2_WAVES);
+  auto k = sdf_mlp_kernel<PREC, FAST, FULL, SRC>;
+  static std::atomic<unsigned long long> lds_set{0};
+  if (const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(k), LDS_BYTES, lds_set, name)) return rc;
+  hipLaunchKernelGGL(k, grid, block, LDS_BYTES, st, arg, static_cast<const char*>(packed), gamma, beta, sdf, grad, rgb, feat,
+                     static_cast<char*>(scratch), n);
+  return oi::check_launch(name);
 }
 
 template <int PREC, bool FAST>
 int launch_mlp(const float* pts, const void* packed, const float* gamma, const float* beta, float* sdf,
                float* grad, float* rgb, float* feat, void* scratch, int B, long long n, hipStream_t st) {
-  const char* pk = reinterpret_cast<const char*>(packed);
   if (grad != nullptr) {
     // (F16X3 and BF16 with the gradient run the register-resident kernels of mlp_fwd3.hip / mlp_fwd3b.hip)
     if constexpr (PREC == OI_PREC_F16X3 || PREC == OI_PREC_BF16)
       return oi::fail(OI_ERR_INVALID_ARG, "oi_sdf_mlp_fwd: precision %d with the gradient has no v2 kernel", PREC);
     else
-      return launch_mlp_variant<PREC, FAST, true>(pts, pk, gamma, beta, sdf, grad, rgb, feat,
-                                                  reinterpret_cast<char*>(scratch), B, n, st);
+      return launch_sdf<PREC, FAST, true, ArraySrc>(pts, packed, gamma, beta, sdf, grad, rgb, feat, scratch, B, n,
+                                                    "oi_sdf_mlp_fwd", st);
   }
-  return launch_mlp_variant<PREC, FAST, false>(pts, pk, gamma, beta, sdf, nullptr, nullptr, feat, nullptr, B, n, st);
+  return launch_sdf<PREC, FAST, false, ArraySrc>(pts, packed, gamma, beta, sdf, nullptr, nullptr, feat, nullptr, B, n,
+                                                 "oi_sdf_mlp_fwd", st);
+}
+
+// (prec, fast_trig) -> f(std::integral_constant<int, PREC>, std::bool_constant<FAST>); a bad precision is `who`'s error
+template <class F>
+int dispatch_prec(int prec, int fast_trig, const char* who, F&& f) {
+  auto trig = [&](auto P) { return fast_trig ? f(P, std::true_type{}) : f(P, std::false_type{}); };
+  switch (prec) {
+    case OI_PREC_F32: return trig(std::integral_constant<int, OI_PREC_F32>{});
+    case OI_PREC_BF16X3: return trig(std::integral_constant<int, OI_PREC_BF16X3>{});
+    case OI_PREC_BF16: return trig(std::integral_constant<int, OI_PREC_BF16>{});
+    case OI_PREC_BF16X6: return trig(std::integral_constant<int, OI_PREC_BF16X6>{});
+    case OI_PREC_F16X3: return trig(std::integral_constant<int, OI_PREC_F16X3>{});
+    default: return oi::fail(OI_ERR_INVALID_ARG, "%s: bad precision %d", who, prec);
+  }
 }
 
 // the device sin/cos of the MLP kernels, exposed for tests (include/oi_hip.h: oi_selftest_sincos)
@@ -724,31 +1023,11 @@ int oi_mlp_pack_weights(const float* w0, const float* b0, const float* wh, const
   dim3 grid(C * C / (256 * PK_PER), NMAT + 1), block(256);
   char* p = reinterpret_cast<char*>(packed);
   hipStream_t st = oi::as_stream(stream);
-  switch (prec) {
-    case OI_PREC_F32:
-      hipLaunchKernelGGL(pack_weights_kernel<OI_PREC_F32>, grid, block, 0, st, w0, b0, wh, bh, wsig, bsig, wv, bv,
-                         wrgb, brgb, p);
-      break;
-    case OI_PREC_BF16X3:
-      hipLaunchKernelGGL(pack_weights_kernel<OI_PREC_BF16X3>, grid, block, 0, st, w0, b0, wh, bh, wsig, bsig, wv, bv,
-                         wrgb, brgb, p);
-      break;
-    case OI_PREC_BF16:
-      hipLaunchKernelGGL(pack_weights_kernel<OI_PREC_BF16>, grid, block, 0, st, w0, b0, wh, bh, wsig, bsig, wv, bv,
-                         wrgb, brgb, p);
-      break;
-    case OI_PREC_BF16X6:
-      hipLaunchKernelGGL(pack_weights_kernel<OI_PREC_BF16X6>, grid, block, 0, st, w0, b0, wh, bh, wsig, bsig, wv, bv,
-                         wrgb, brgb, p);
-      break;
-    case OI_PREC_F16X3:
-      hipLaunchKernelGGL(pack_weights_kernel<OI_PREC_F16X3>, grid, block, 0, st, w0, b0, wh, bh, wsig, bsig, wv, bv,
-                         wrgb, brgb, p);
-      break;
-    default:
-      return oi::fail(OI_ERR_INVALID_ARG, "oi_mlp_pack_weights: bad precision %d", prec);
-  }
-  return oi::check_launch("oi_mlp_pack_weights");
+  return dispatch_prec(prec, 0, "oi_mlp_pack_weights", [&](auto P, auto) {
+    hipLaunchKernelGGL(pack_weights_kernel<decltype(P)::value>, grid, block, 0, st, w0, b0, wh, bh, wsig, bsig, wv, bv, wrgb,
+                       brgb, p);
+    return oi::check_launch("oi_mlp_pack_weights");
+  });
 }
 
 int oi_selftest_sincos(const float* x, float* s, float* c, long long n, int fast, oi_stream_t stream) {
@@ -813,20 +1092,10 @@ int oi_sdf_mlp_fwd_ex(const float* pts, const void* packed, const float* gamma, 
   // BF16 with the gradient: the register-resident kernel of mlp_fwd3b.hip (no scratch stream)
   if (prec == OI_PREC_BF16 && grad != nullptr)
     return oimlp::launch_full3_bf16(pts, packed, gamma, beta, sdf, grad, rgb, feat, scratch, B, n_per_elem, fast_trig, st);
-#define OI_MLP_CASE(P)                                                                                        \
-  case P:                                                                                                     \
-    return fast_trig ? launch_mlp<P, true>(pts, packed, gamma, beta, sdf, grad, rgb, feat, scratch, B, n_per_elem, st) \
-                     : launch_mlp<P, false>(pts, packed, gamma, beta, sdf, grad, rgb, feat, scratch, B, n_per_elem, st);
-  switch (prec) {
-    OI_MLP_CASE(OI_PREC_F32)
-    OI_MLP_CASE(OI_PREC_BF16X3)
-    OI_MLP_CASE(OI_PREC_BF16)
-    OI_MLP_CASE(OI_PREC_BF16X6)
-    OI_MLP_CASE(OI_PREC_F16X3)
-    default:
-      return oi::fail(OI_ERR_INVALID_ARG, "oi_sdf_mlp_fwd: bad precision %d", prec);
-  }
-#undef OI_MLP_CASE
+  return dispatch_prec(prec, fast_trig, "oi_sdf_mlp_fwd", [&](auto P, auto F) {
+    return launch_mlp<decltype(P)::value, decltype(F)::value>(pts, packed, gamma, beta, sdf, grad, rgb, feat, scratch, B,
+                                                              n_per_elem, st);
+  });
 }
 
 int oi_sdf_lattice(const void* packed, const float* gamma, const float* beta, int B, const float* xs, const float* ys,
@@ -836,22 +1105,12 @@ int oi_sdf_lattice(const void* packed, const float* gamma, const float* beta, in
   OI_REQUIRE(B > 0 && nx > 0 && ny > 0 && nz > 0, "oi_sdf_lattice: B=%d nx=%d ny=%d nz=%d", B, nx, ny, nz);
   const long long n = (long long)nx * ny * nz;
   OI_REQUIRE(n < (1ll << 31), "oi_sdf_lattice: %d x %d x %d = %lld points per element (at most 2^31 - 1)", nx, ny, nz, n);
-  const char* pk = reinterpret_cast<const char*>(packed);
   hipStream_t st = oi::as_stream(stream);
-#define OI_LAT_CASE(P)                                                                                           \
-  case P:                                                                                                        \
-    return fast_trig ? launch_lattice<P, true>(xs, ys, zs, ny, nz, scale, pk, gamma, beta, out, B, n, st)        \
-                     : launch_lattice<P, false>(xs, ys, zs, ny, nz, scale, pk, gamma, beta, out, B, n, st);
-  switch (prec) {
-    OI_LAT_CASE(OI_PREC_F32)
-    OI_LAT_CASE(OI_PREC_BF16X3)
-    OI_LAT_CASE(OI_PREC_BF16)
-    OI_LAT_CASE(OI_PREC_BF16X6)
-    OI_LAT_CASE(OI_PREC_F16X3)
-    default:
-      return oi::fail(OI_ERR_INVALID_ARG, "oi_sdf_lattice: bad precision %d", prec);
-  }
-#undef OI_LAT_CASE
+  const LatticeSrc src{xs, ys, zs, ny, nz, scale};
+  return dispatch_prec(prec, fast_trig, "oi_sdf_lattice", [&](auto P, auto F) {
+    return launch_sdf<decltype(P)::value, decltype(F)::value, false, LatticeSrc>(src, packed, gamma, beta, out, nullptr, nullptr,
+                                                                                 nullptr, nullptr, B, n, "oi_sdf_lattice", st);
+  });
 }
 
 // include/oi_mesh_band.h: the band launch of narrow-band mesh extraction (accelerates renderer.py:15-41)
@@ -870,22 +1129,12 @@ int oi_sdf_lattice_band(const void* packed, const float* gamma, const float* bet
   OI_REQUIRE(packed && gamma && beta && xs && ys && zs && list && field, "oi_sdf_lattice_band: null pointer");
   const int lb = block == 4 ? 2 : 3;
   const long long n = n_active << (3 * lb);  // <= 2^30: the local index fits 32 bits
-  const char* pk = reinterpret_cast<const char*>(packed);
   hipStream_t st = oi::as_stream(stream);
-#define OI_BAND_CASE(P)                                                                                              \
-  case P:                                                                                                            \
-    return fast_trig ? launch_band<P, true>(xs, ys, zs, nx, ny, nz, lb, list, scale, pk, gamma, beta, field, n, st)  \
-                     : launch_band<P, false>(xs, ys, zs, nx, ny, nz, lb, list, scale, pk, gamma, beta, field, n, st);
-  switch (prec) {
-    OI_BAND_CASE(OI_PREC_F32)
-    OI_BAND_CASE(OI_PREC_BF16X3)
-    OI_BAND_CASE(OI_PREC_BF16)
-    OI_BAND_CASE(OI_PREC_BF16X6)
-    OI_BAND_CASE(OI_PREC_F16X3)
-    default:
-      return oi::fail(OI_ERR_INVALID_ARG, "oi_sdf_lattice_band: bad precision %d", prec);
-  }
-#undef OI_BAND_CASE
+  const BandSrc src{xs, ys, zs, nx, ny, nz, lb, list, scale};
+  return dispatch_prec(prec, fast_trig, "oi_sdf_lattice_band", [&](auto P, auto F) {
+    return launch_sdf<decltype(P)::value, decltype(F)::value, false, BandSrc>(src, packed, gamma, beta, field, nullptr, nullptr,
+                                                                              nullptr, nullptr, 1, n, "oi_sdf_lattice_band", st);
+  });
 }
 
 }  // extern "C"

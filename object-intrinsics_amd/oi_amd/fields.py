@@ -325,3 +325,53 @@ class FieldPack:
     def film(self, z=None, w=None):
         from .autograd import film_params
         return film_params(self, z=z, w=w)
+
+
+def field_pack(obj, what, need_color=True):
+    """The FieldPack of a FieldPack, a NeuSRenderer (.pack), a Generator (.renderer.pack) or a bare ShapeNetwork (its own
+    pack, which has no colour head); need_color: refuse a pack without one."""
+    pack = obj
+    if not isinstance(pack, FieldPack):
+        pack = getattr(getattr(obj, "renderer", obj), "pack", None)
+    if not isinstance(pack, FieldPack) and hasattr(obj, "_own_pack"):
+        pack = obj._own_pack()
+    if not isinstance(pack, FieldPack):
+        raise TypeError(f"{what}: expected a FieldPack, a NeuSRenderer or a Generator, got {type(obj).__name__}")
+    if need_color and pack.color_network is None:
+        raise ValueError(f"{what}: the albedo needs the colour head, and this field has none (a bare ShapeNetwork): pass the "
+                         "FieldPack that holds both networks (NeuSRenderer.pack, Generator.renderer.pack)")
+    return pack
+
+
+class LatentField:
+    """The field of one latent as the C ABI takes it.  The constructor checks on the host, for the caller `what`: the pack
+    (field_pack), that z or w is given, and that it is one latent (batch_ok: a batch (B, 64) is accepted).  prepare(z, w)
+    evaluates the FiLM rows and leaves pack, B, gamma, beta, packed (contiguous CUDA tensors), prec and fast (ints)."""
+
+    def __init__(self, obj, z, w, what, need_color=True, batch_ok=False):
+        self.pack = field_pack(obj, what, need_color)
+        if z is None and w is None:
+            raise ValueError(f"{what}: a latent z or a style vector w is needed")
+        lat = w if w is not None else z
+        B = lat.shape[0] if lat.dim() > 1 else 1
+        if B != 1 and not batch_ok:
+            raise ValueError(f"{what}: one latent expected, got a batch of {B}")
+        self.batch_ok = batch_ok
+
+    def prepare(self, z, w):
+        with torch.no_grad():
+            lat = w if w is not None else z
+            if not self.batch_ok:
+                lat = lat.reshape(1, -1)
+            w_, gamma, beta = self.pack.film(z=None if w is not None else lat, w=lat if w is not None else None)
+        self.B, self.gamma, self.beta, self.packed = w_.shape[0], gamma.contiguous(), beta.contiguous(), self.pack.packed()
+        self.prec, self.fast = self.pack.prec, int(bool(self.pack.fast_trig))
+        return self
+
+    def sdf(self, pts):
+        return ops.sdf_mlp_fwd(pts, self.packed, self.gamma, self.beta, self.B, self.prec, self.fast)[0]
+
+    def full(self, pts, scratch=None):
+        """sdf, d sdf/dx and albedo at pts (the full MLP pass)."""
+        return ops.sdf_mlp_fwd(pts, self.packed, self.gamma, self.beta, self.B, self.prec, self.fast, want_grad=True,
+                               want_rgb=True, scratch=scratch)[:3]

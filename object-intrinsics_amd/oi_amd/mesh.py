@@ -22,6 +22,7 @@ import torch
 
 from . import lib as _l
 from . import ops
+from .fields import LatentField, field_pack as _field_pack   # (inference.export_mesh resolves its pack through it)
 from .ops import _p, _stream
 
 MAX_RESOLUTION = 1024  # per axis (oi_mc_workspace_bytes)
@@ -39,21 +40,15 @@ def sdf_lattice(pack, bound_min, bound_max, resolution, z=None, w=None, scale=1.
     """(B, nx, ny, nz) CUDA field scale * sdf on the lattice of torch.linspace(bound_min[a], bound_max[a], resolution[a])
     for latents z (B, 64) or style vectors w (B, 64).  `pack`: a ShapeNetwork or a fields.FieldPack (its precision and
     fast_trig).  One launch of oi_sdf_lattice; no graph (the field is not differentiable)."""
-    from .fields import FieldPack
-    if not isinstance(pack, FieldPack):
-        pack = pack._own_pack()
-    if z is None and w is None:
-        raise ValueError("sdf_lattice: a latent z or a style vector w is needed")
+    f = LatentField(pack, z, w, "sdf_lattice", need_color=False, batch_ok=True)
     L = _l.load()
     with torch.no_grad():
-        w_, gamma, beta = pack.film(z=z if w is None else None, w=w)
-        B = w_.shape[0]
-        xs, ys, zs = _axes(bound_min, bound_max, resolution, gamma.device)
+        f.prepare(z, w)
+        xs, ys, zs = _axes(bound_min, bound_max, resolution, f.gamma.device)
         nx, ny, nz = len(xs), len(ys), len(zs)
-        out = torch.empty(B, nx, ny, nz, dtype=torch.float32, device=gamma.device)
-        _l.check(L.oi_sdf_lattice(_p(pack.packed()), _p(gamma.contiguous()), _p(beta.contiguous()), B, _p(xs), _p(ys),
-                                  _p(zs), nx, ny, nz, float(scale), _p(out), pack.prec, int(bool(pack.fast_trig)), _stream()),
-                 "oi_sdf_lattice")
+        out = torch.empty(f.B, nx, ny, nz, dtype=torch.float32, device=f.gamma.device)
+        _l.check(L.oi_sdf_lattice(_p(f.packed), _p(f.gamma), _p(f.beta), f.B, _p(xs), _p(ys), _p(zs), nx, ny, nz, float(scale),
+                                  _p(out), f.prec, f.fast, _stream()), "oi_sdf_lattice")
     return out
 
 
@@ -111,15 +106,8 @@ def sdf_lattice_band(pack, bound_min, bound_max, resolution, iso, z=None, w=None
     marching_cubes(field[0], iso) is the dense field's mesh, byte for byte, as long as `lipschitz` bounds |d sdf/dx| in the
     box (grown by (block - 1) / 2 cells).  A slope between two block centres above `lipschitz` proves the bound wrong:
     ValueError, no field.  One latent; lipschitz / block default to DEFAULT_LIPSCHITZ / DEFAULT_BLOCK."""
-    from .fields import FieldPack
     lipschitz, block = _check_band_args("sdf_lattice_band", lipschitz, block)
-    if not isinstance(pack, FieldPack):
-        pack = pack._own_pack()
-    if z is None and w is None:
-        raise ValueError("sdf_lattice_band: a latent z or a style vector w is needed")
-    B = (w if w is not None else z).shape[0]
-    if B != 1:
-        raise ValueError(f"sdf_lattice_band: one latent expected, got a batch of {B}")
+    f = LatentField(pack, z, w, "sdf_lattice_band", need_color=False)
     res = (resolution,) * 3 if np.isscalar(resolution) else tuple(resolution)
     nx, ny, nz = (int(r) for r in res)
     if not all(_l.BAND_MIN_RES <= n <= _l.BAND_MAX_RES for n in (nx, ny, nz)):
@@ -134,9 +122,8 @@ def sdf_lattice_band(pack, bound_min, bound_max, resolution, iso, z=None, w=None
         raise ValueError(f"sdf_lattice_band: empty box {bmin} .. {bmax}")
     L = _l.load()
     with torch.no_grad():
-        _, gamma, beta = pack.film(z=z if w is None else None, w=w)
-        gamma, beta, packed = gamma.contiguous(), beta.contiguous(), pack.packed()
-        dev = gamma.device
+        f.prepare(z, w)
+        gamma, beta, packed, dev = f.gamma, f.beta, f.packed, f.gamma.device
         xs, ys, zs = _axes(bmin, bmax, (nx, ny, nz), dev)
         # the coarse pass: index block * i + (block - 1) / 2 per axis, on the line through the axis' end points (float64 on
         # the host, as tests/helpers/band_ref.py builds them)
@@ -144,10 +131,9 @@ def sdf_lattice_band(pack, bound_min, bound_max, resolution, iso, z=None, w=None
         cax = [torch.from_numpy((bmin[a] + (block * np.arange(nb[a], dtype=np.float64) + (block - 1) / 2.0) *
                                  ((bmax[a] - bmin[a]) / (n - 1))).astype(np.float32)).to(dev)
                for a, n in enumerate((nx, ny, nz))]
-        fast = int(bool(pack.fast_trig))
         coarse = torch.empty(nb[0], nb[1], nb[2], dtype=torch.float32, device=dev)
         _l.check(L.oi_sdf_lattice(_p(packed), _p(gamma), _p(beta), 1, _p(cax[0]), _p(cax[1]), _p(cax[2]), nb[0], nb[1], nb[2],
-                                  scale, _p(coarse), pack.prec, fast, _stream()), "oi_sdf_lattice")
+                                  scale, _p(coarse), f.prec, f.fast, _stream()), "oi_sdf_lattice")
         nbytes = L.oi_band_workspace_bytes(nx, ny, nz, block)
         if nbytes == 0:
             msg = L.oi_last_error()
@@ -164,7 +150,7 @@ def sdf_lattice_band(pack, bound_min, bound_max, resolution, iso, z=None, w=None
                              f"{lipschitz:.6g}: the bound on |d sdf/dx| is wrong for this field, no band field is returned "
                              "(pass a larger lipschitz, or band=False)")
         _l.check(L.oi_sdf_lattice_band(_p(packed), _p(gamma), _p(beta), 1, _p(xs), _p(ys), _p(zs), nx, ny, nz, block, _p(ws),
-                                       n_active, scale, _p(field), pack.prec, fast, _stream()), "oi_sdf_lattice_band")
+                                       n_active, scale, _p(field), f.prec, f.fast, _stream()), "oi_sdf_lattice_band")
         active_list = ws[:4 * n_active].view(torch.int32)
     info = BandInfo(block, int(counts[0]), n_active, int(counts[2]), int(counts[3]),
                     int(counts[0]) + n_active * block ** 3, float(slope.value), lipschitz, coarse, active_list)
@@ -348,22 +334,6 @@ def _check_refine(refine, what):
     return int(refine)
 
 
-def _field_pack(obj, what):
-    """The FieldPack with shape AND colour weights of a FieldPack, a NeuSRenderer (.pack) or a Generator (.renderer.pack)."""
-    from .fields import FieldPack
-    pack = obj
-    if not isinstance(pack, FieldPack):
-        pack = getattr(getattr(obj, "renderer", obj), "pack", None)
-    if not isinstance(pack, FieldPack) and hasattr(obj, "_own_pack"):
-        pack = obj._own_pack()
-    if not isinstance(pack, FieldPack):
-        raise TypeError(f"{what}: expected a FieldPack, a NeuSRenderer or a Generator, got {type(obj).__name__}")
-    if pack.color_network is None:
-        raise ValueError(f"{what}: the albedo needs the colour head, and this field has none (a bare ShapeNetwork): pass the "
-                         "FieldPack that holds both networks (NeuSRenderer.pack, Generator.renderer.pack)")
-    return pack
-
-
 def vertex_attributes(pack_or_generator, vertices_index, bound_min, bound_max, resolution, z=None, w=None, refine=2,
                       threshold=0.0, want_record=False):
     """Index-space marching-cubes vertices (V, 3) (CUDA, as marching_cubes returns them for a field of sdf_lattice on the same
@@ -375,9 +345,7 @@ def vertex_attributes(pack_or_generator, vertices_index, bound_min, bound_max, r
     Every pass is the full MLP forward (sdf, gradient, albedo) in the pack's precision -- the only pass with a gradient the
     library has; the albedo of the refinement passes is discarded.  One latent: z (1, 64) or w (1, 64)."""
     refine = _check_refine(refine, "vertex_attributes")
-    pack = _field_pack(pack_or_generator, "vertex_attributes")
-    if z is None and w is None:
-        raise ValueError("vertex_attributes: a latent z or a style vector w is needed")
+    f = LatentField(pack_or_generator, z, w, "vertex_attributes")
     if not torch.is_tensor(vertices_index) or vertices_index.dim() != 2 or vertices_index.shape[1] != 3:
         raise ValueError("vertex_attributes: vertices_index must be a (V, 3) tensor of index-space vertices")
     if not vertices_index.is_cuda:
@@ -392,23 +360,18 @@ def vertex_attributes(pack_or_generator, vertices_index, bound_min, bound_max, r
         return IntrinsicMesh(e(0, 3), e(0, 3), e(0, 3), e(refine + 1, 0), e(0, dt=torch.uint8),
                              e(0, RECORD_DTYPE.itemsize, dt=torch.uint8) if want_record else None)
     with torch.no_grad():
-        w_, gamma, beta = pack.film(z=z if w is None else None, w=w)
-        if w_.shape[0] != 1:
-            raise ValueError(f"vertex_attributes: one latent expected, got a batch of {w_.shape[0]}")
-        gamma, beta, packed = gamma.contiguous(), beta.contiguous(), pack.packed()
+        f.prepare(z, w)
         xs, ys, zs = _axes(bound_min, bound_max, resolution, dev)
         bmin, bmax = ([float(v) for v in _host(b).reshape(-1)] for b in (bound_min, bound_max))
         limits = [0.5 * (bmax[a] - bmin[a]) / (len(x) - 1) for a, x in enumerate((xs, ys, zs))]
         pos, flags = ops.mesh_vertex_world(vi, xs, ys, zs)
         pos0 = pos.clone() if refine else pos
         residual = ops._new(pos, refine + 1, V)
-        scratch = torch.empty(ops.mlp_scratch_bytes(1, V, pack.prec), dtype=torch.uint8, device=dev)
-        fwd = lambda: ops.sdf_mlp_fwd(pos, packed, gamma, beta, 1, pack.prec, pack.fast_trig, want_grad=True, want_rgb=True,
-                                      scratch=scratch)
+        scratch = torch.empty(ops.mlp_scratch_bytes(1, V, f.prec), dtype=torch.uint8, device=dev)
         for k in range(refine):
-            sdf, grad, _, _, _ = fwd()
+            sdf, grad, _ = f.full(pos, scratch)
             ops.mesh_newton(pos, pos0, sdf, grad, threshold, limits, residual[k], flags)
-        sdf, grad, rgb, _, _ = fwd()
+        sdf, grad, rgb = f.full(pos, scratch)
         normals, albedo, record = ops.mesh_attr_finalize(pos, sdf, grad, rgb, threshold, residual[refine], want_record)
     return IntrinsicMesh(pos, normals, albedo, residual, flags, record)
 
@@ -423,12 +386,7 @@ def extract_intrinsic_mesh(renderer_or_generator, z=None, w=None, resolution=256
     set u = -sdf = threshold (extract_geometry's convention): with threshold != 0 the vertices are refined towards
     sdf = -threshold."""
     refine = _check_refine(refine, "extract_intrinsic_mesh")
-    pack = _field_pack(renderer_or_generator, "extract_intrinsic_mesh")
-    if z is None and w is None:
-        raise ValueError("extract_intrinsic_mesh: a latent z or a style vector w is needed")
-    B = (w if w is not None else z).shape[0]
-    if B != 1:
-        raise ValueError(f"extract_intrinsic_mesh: one latent expected, got a batch of {B}")
+    pack = LatentField(renderer_or_generator, z, w, "extract_intrinsic_mesh").pack
     u, info = _level_field(pack, bound_min, bound_max, resolution, threshold, z, w, band, lipschitz, block,
                            "extract_intrinsic_mesh")
     vi, tris = marching_cubes(u, threshold)

@@ -17,6 +17,7 @@ import torch
 
 from . import lib as _l
 from . import ops
+from .fields import LatentField
 
 # read-back cadence of the number of rays in flight (DESIGN section 4.13 has the measurements)
 READBACK_DENSE = 1024    # above this many rays a stale bound costs MLP time: read every step
@@ -56,48 +57,16 @@ def _check_params(tol, omega, max_steps, readback, what):
         raise ValueError(f"{what}: readback={readback!r} ('auto' or a positive number of steps)")
 
 
-class _Field:
-    """One latent's sdf field: the pack, its packed weights and the FiLM rows."""
-
-    def __init__(self, pack_or_generator, z, w, what):
-        from .mesh import _field_pack
-        self.pack = _field_pack(pack_or_generator, what)
-        if z is None and w is None:
-            raise ValueError(f"{what}: a latent z or a style vector w is needed")
-        lat = w if w is not None else z
-        B = lat.shape[0] if lat.dim() > 1 else 1
-        if B != 1:
-            raise ValueError(f"{what}: one latent expected, got a batch of {B}")
-
-    def prepare(self, z, w):
-        with torch.no_grad():
-            lat = w if w is not None else z
-            lat = lat.reshape(1, -1)
-            _, gamma, beta = self.pack.film(z=None if w is not None else lat, w=lat if w is not None else None)
-        self.gamma, self.beta, self.packed = gamma.contiguous(), beta.contiguous(), self.pack.packed()
-        return self
-
-    def sdf(self, pts):
-        p = self.pack
-        return ops.sdf_mlp_fwd(pts, self.packed, self.gamma, self.beta, 1, p.prec, p.fast_trig)[0]
-
-    def full(self, pts):
-        p = self.pack
-        sdf, grad, rgb, _, _ = ops.sdf_mlp_fwd(pts, self.packed, self.gamma, self.beta, 1, p.prec, p.fast_trig, want_grad=True,
-                                               want_rgb=True)
-        return sdf, grad, rgb
-
-
 def _march(field, st, bound, tol, omega, max_steps, readback):
     """The loop on a state that oi_trace_begin / oi_trace_shadow_begin has filled.  -> (points evaluated, steps run).
     Two launches per step through the C ABI directly, with the pointers converted once: the loop's tail is a handful of rays
     per step, where the host's time per launch is the frame's time."""
     import ctypes
-    L, p = _l.load(), field.pack
+    L = _l.load()
     sdf = torch.empty(st.N, dtype=torch.float32, device=st.t.device)   # working memory: step k's pass writes sdf[:bound]
     pts_p, sdf_p, state_p, stream = ops._p(st.points), ops._p(sdf), ctypes.byref(st.c), ops._stream()
     packed_p, gamma_p, beta_p = ops._p(field.packed), ops._p(field.gamma), ops._p(field.beta)
-    prec, trig = p.prec, int(bool(p.fast_trig))
+    prec, trig = field.prec, field.fast
     n_evals = k = since = 0
     while k < max_steps and bound > 0:
         rc = L.oi_sdf_mlp_fwd(pts_p, packed_p, gamma_p, beta_p, sdf_p, None, None, None, None, 1, bound, prec, trig, stream)
@@ -132,7 +101,7 @@ def sphere_trace(pack_or_generator, rays_o, rays_d, near=None, far=None, z=None,
     if siren_network is not None:
         raise NotImplementedError("siren_network is not on the path (as in render())")
     _check_params(tol, omega, max_steps, readback, "sphere_trace")
-    field = _Field(pack_or_generator, z, w, "sphere_trace")
+    field = LatentField(pack_or_generator, z, w, "sphere_trace")
     if not torch.is_tensor(rays_o) or not torch.is_tensor(rays_d) or rays_o.shape != rays_d.shape or rays_o.shape[-1] != 3:
         raise ValueError("sphere_trace: rays_o and rays_d must be tensors of the same (..., 3) shape")
     if not rays_o.is_cuda:
@@ -180,7 +149,7 @@ class _Surface:
             raise ValueError(f"render_surface: bias={bias!r} (>= 0 and finite)")
         self.kw = (float(tol), float(omega), int(max_steps), readback)
         self.bias = float(bias)
-        self.field = _Field(gen, z, w, "render_surface")
+        self.field = LatentField(gen, z, w, "render_surface")
         gen.eval()
         dev = gen.it.device
         self.field.prepare(None if z is None else z.to(dev), None if w is None else w.to(dev))

@@ -1,0 +1,193 @@
+// Soft shadows and ambient occlusion for the sphere-traced renderer (include/oi_occlusion.h), gfx950.
+// One thread per secondary ray or pixel, around the library's own sdf-only MLP passes:
+//   light_begin / ambient_begin   S sample directions per (light, visible point): a cap about the light's direction, uniform
+//                                 in solid angle, or the cosine-weighted hemisphere about the normal; offset along the
+//                                 normal, compacted like a step
+//   step                          trace_common.h's state machine in its any-hit form: the first occluder ends the ray
+//   resolve                       S ray states per light and pixel -> the share that ended MISS
+//   shade_ao                      trace_common.h's shading with an occlusion factor on the ambient term
+// No float atomics, no scratch; the only atomics are the compaction's integer counters (one add per workgroup).
+#include "trace_common.h"
+#include "../../include/oi_occlusion.h"
+
+namespace {
+
+constexpr float HALF_PI = 1.57079632679489662f;
+
+// the header's sample numbers: a 32-bit mix of (pixel, seed), one stratum per sample, a 24-bit rotation
+__device__ __forceinline__ void sample_numbers(unsigned pix, unsigned seed, unsigned j, int S, float& u1, float& u2) {
+  unsigned x = pix * 0x9E3779B9u + seed;
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  u1 = ((float)j + 0.5f) / (float)S;
+  u2 = (float)((j * 2654435769u + x) >> 8) * 0x1p-24f;
+}
+
+// d = sa cos(phi) t1 + sa sin(phi) t2 + ca a in the header's frame of the unit axis a; sa == 0 returns a itself
+__device__ __forceinline__ void direction_about(float ax, float ay, float az, float sa, float ca, float u2, float& dx, float& dy,
+                                                float& dz) {
+  const float sg = copysignf(1.0f, az);
+  const float A = -1.0f / (sg + az), B = ax * ay * A;
+  const float t1x = 1.0f + sg * ax * ax * A, t1y = sg * B, t1z = -sg * ax;
+  const float t2x = B, t2y = sg + ay * ay * A, t2z = -ay;
+  float sp, cp;
+  sincospif(2.0f * u2, &sp, &cp);  // phi = 2 pi u2
+  const float e1 = sa * cp, e2 = sa * sp;
+  dx = e1 * t1x + e2 * t2x + ca * ax;
+  dy = e1 * t1y + e2 * t2y + ca * ay;
+  dz = e1 * t1z + e2 * t2z + ca * az;
+  if (sa == 0.f) dx = ax, dy = ay, dz = az;  // (the sums above give a up to the sign of a zero)
+}
+
+// AMBIENT = false: rays to L lights of angular radius radius[l].  AMBIENT = true: L = 1, the hemisphere about the normal.
+template <bool AMBIENT>
+__global__ void __launch_bounds__(TR_THREADS) occlusion_begin_kernel(const oi_trace_state s,
+                                                                     const float* __restrict__ hit_points,
+                                                                     const float* __restrict__ grad,
+                                                                     const int* __restrict__ hit_index, long long n_hit,
+                                                                     const float* __restrict__ lights,
+                                                                     const float* __restrict__ radius, int S,
+                                                                     const float* __restrict__ w2b, float bias, float distance,
+                                                                     unsigned seed) {
+  __shared__ unsigned lds[TR_WAVES + 1];
+  const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  bool traced = false;
+  float ox = 0.f, oy = 0.f, oz = 0.f;
+  if (q < s.N) {
+    const long long lj = q / n_hit, i = q - lj * n_hit;
+    const long long l = lj / S;
+    const unsigned j = (unsigned)(lj - l * S);
+    const float gx = grad[i * 3 + 0], gy = grad[i * 3 + 1], gz = grad[i * 3 + 2];
+    const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
+    const float nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
+    float u1, u2;
+    sample_numbers((unsigned)hit_index[i], seed, j, S, u1, u2);
+    float ax, ay, az, sa, ca;
+    if (AMBIENT) {
+      ax = nx, ay = ny, az = nz;
+      ca = sqrtf(1.0f - u1);
+      sa = sqrtf(u1);
+    } else {
+      light_dir(lights + l * OI_RELIGHT_LIGHT_FLOATS, w2b, ax, ay, az);
+      const float rad = fminf(fmaxf(radius[l], 0.f), HALF_PI);  // (fmaxf drops a NaN)
+      const float m = u1 * (1.0f - cosf(rad));
+      ca = 1.0f - m;
+      sa = sqrtf(fmaxf(m * (2.0f - m), 0.f));  // sqrt(1 - ca^2) without the cancellation
+    }
+    float dx, dy, dz;
+    direction_about(ax, ay, az, sa, ca, u2, dx, dy, dz);
+    traced = nx * dx + ny * dy + nz * dz > 0.f;
+    ox = __fmaf_rn(bias, nx, hit_points[i * 3 + 0]);
+    oy = __fmaf_rn(bias, ny, hit_points[i * 3 + 1]);
+    oz = __fmaf_rn(bias, nz, hit_points[i * 3 + 2]);
+    float far = unit_sphere_exit(ox, oy, oz, dx, dy, dz);
+    if (AMBIENT) far = fminf(far, distance);
+    s.rays_o[q * 3 + 0] = ox, s.rays_o[q * 3 + 1] = oy, s.rays_o[q * 3 + 2] = oz;
+    s.rays_d[q * 3 + 0] = dx, s.rays_d[q * 3 + 1] = dy, s.rays_d[q * 3 + 2] = dz;
+    s.near_[q] = 0.f;
+    s.far_[q] = far;
+    s.t[q] = 0.f;
+    s.status[q] = traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING;
+    s.steps[q] = 0;
+    s.side[q] = 0;
+    s.bracket[q * 4 + 0] = s.bracket[q * 4 + 1] = s.bracket[q * 4 + 2] = s.bracket[q * 4 + 3] = 0.f;
+  }
+  const long long slot = wg_slot(traced, s.counts, lds);
+  if (traced) {
+    s.active[slot] = (int)q;
+    s.points[slot * 3 + 0] = ox, s.points[slot * 3 + 1] = oy, s.points[slot * 3 + 2] = oz;  // o + 0 d
+  }
+}
+
+__global__ void __launch_bounds__(TR_THREADS) occlusion_resolve_kernel(const uint8_t* __restrict__ status,
+                                                                       const int* __restrict__ hit_slot, long long N,
+                                                                       long long n_hit, int L, int S, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= N * L) return;
+  const long long l = i / N, px = i - l * N;
+  const int slot = hit_slot[px];
+  if (slot < 0) {
+    out[i] = 1.0f;
+    return;
+  }
+  const uint8_t* __restrict__ st = status + l * S * n_hit + slot;
+  int lit = 0;
+  for (int j = 0; j < S; ++j) lit += st[(long long)j * n_hit] == OI_TRACE_MISS ? 1 : 0;
+  out[i] = (float)lit / (float)S;
+}
+
+__global__ void __launch_bounds__(TR_THREADS) surface_shade_ao_kernel(const oi_surface_ao_params p) {
+  surface_shade_pixel(p, p.ambient_occlusion);
+}
+
+// what the two begin entries share: the state, the counts and the ray layout
+int check_begin(const char* what, const oi_trace_state* s, long long n_hit, int L, int S, float bias) {
+  int rc = check_state(s, what);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "%s: L=%d (1 .. %d lights)", what, L, OI_RELIGHT_MAX_LIGHTS);
+  OI_REQUIRE(S >= 1 && S <= OI_OCCLUSION_MAX_SAMPLES, "%s: S=%d (1 .. %d samples)", what, S, OI_OCCLUSION_MAX_SAMPLES);
+  OI_REQUIRE(n_hit >= 1 && n_hit < (1ll << 31) && n_hit * L * S == s->N,
+             "%s: n_hit=%lld, L=%d, S=%d, N=%lld (N must be L * S * n_hit, below 2^31)", what, n_hit, L, S, s->N);
+  OI_REQUIRE(bias >= 0.f && bias < INFINITY, "%s: bias %g (>= 0, finite)", what, (double)bias);
+  return OI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int oi_occlusion_light_begin(const oi_trace_state* s, const float* hit_points, const float* grad, const int* hit_index,
+                             long long n_hit, const float* lights, const float* radius, int L, int S, const float* w2b,
+                             float bias, unsigned seed, oi_stream_t stream) {
+  int rc = check_begin("oi_occlusion_light_begin", s, n_hit, L, S, bias);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(radius != nullptr, "oi_occlusion_light_begin: null radius (one angular radius per light, device memory)");
+  OI_REQUIRE(hit_points && grad && hit_index && lights && w2b, "oi_occlusion_light_begin: null input pointer");
+  const hipStream_t st = oi::as_stream(stream);
+  hipLaunchKernelGGL(trace_clear_counts_kernel, dim3(1), dim3(TR_THREADS), 0, st, s->counts);
+  hipLaunchKernelGGL(occlusion_begin_kernel<false>, dim3(n_blocks(s->N)), dim3(TR_THREADS), 0, st, *s, hit_points, grad, hit_index,
+                     n_hit, lights, radius, S, w2b, bias, 0.f, seed);
+  return oi::check_launch("oi_occlusion_light_begin");
+}
+
+int oi_occlusion_ambient_begin(const oi_trace_state* s, const float* hit_points, const float* grad, const int* hit_index,
+                               long long n_hit, int S, float bias, float distance, unsigned seed, oi_stream_t stream) {
+  int rc = check_begin("oi_occlusion_ambient_begin", s, n_hit, 1, S, bias);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(distance > 0.f && distance < INFINITY, "oi_occlusion_ambient_begin: distance %g (> 0, finite)", (double)distance);
+  OI_REQUIRE(hit_points && grad && hit_index, "oi_occlusion_ambient_begin: null input pointer");
+  const hipStream_t st = oi::as_stream(stream);
+  hipLaunchKernelGGL(trace_clear_counts_kernel, dim3(1), dim3(TR_THREADS), 0, st, s->counts);
+  hipLaunchKernelGGL(occlusion_begin_kernel<true>, dim3(n_blocks(s->N)), dim3(TR_THREADS), 0, st, *s, hit_points, grad, hit_index,
+                     n_hit, (const float*)nullptr, (const float*)nullptr, S, (const float*)nullptr, bias, distance, seed);
+  return oi::check_launch("oi_occlusion_ambient_begin");
+}
+
+int oi_occlusion_step(const oi_trace_state* s, const float* sdf, long long bound, int k, float tol, float omega,
+                      oi_stream_t stream) {
+  return launch_step<true>("oi_occlusion_step", s, sdf, bound, k, tol, omega, stream);
+}
+
+int oi_occlusion_resolve(const uint8_t* status, const int* hit_slot, long long N, long long n_hit, int L, int S, float* out,
+                         oi_stream_t stream) {
+  OI_REQUIRE(N >= 1 && N < (1ll << 31) && n_hit >= 0 && n_hit <= N, "oi_occlusion_resolve: N=%lld, n_hit=%lld", N, n_hit);
+  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "oi_occlusion_resolve: L=%d (1 .. %d lights)", L, OI_RELIGHT_MAX_LIGHTS);
+  OI_REQUIRE(S >= 1 && S <= OI_OCCLUSION_MAX_SAMPLES, "oi_occlusion_resolve: S=%d (1 .. %d samples)", S, OI_OCCLUSION_MAX_SAMPLES);
+  OI_REQUIRE(n_hit * L * S < (1ll << 31), "oi_occlusion_resolve: L * S * n_hit = %lld rays (below 2^31)", n_hit * L * S);
+  OI_REQUIRE(hit_slot && out && (status || n_hit == 0), "oi_occlusion_resolve: null pointer");
+  hipLaunchKernelGGL(occlusion_resolve_kernel, dim3(n_blocks(N * L)), dim3(TR_THREADS), 0, oi::as_stream(stream), status, hit_slot,
+                     N, n_hit, L, S, out);
+  return oi::check_launch("oi_occlusion_resolve");
+}
+
+int oi_surface_shade_ao(const oi_surface_ao_params* p, oi_stream_t stream) {
+  int rc = check_surface("oi_surface_shade_ao", p);
+  if (rc != OI_OK) return rc;
+  hipLaunchKernelGGL(surface_shade_ao_kernel, dim3(n_blocks(p->N)), dim3(TR_THREADS), 0, oi::as_stream(stream), *p);
+  return oi::check_launch("oi_surface_shade_ao");
+}
+
+}  // extern "C"

@@ -1,0 +1,278 @@
+// What trace.hip and occlusion.hip share (include/oi_trace.h, include/oi_occlusion.h; DESIGN sections 4.13 and 4.16): the
+// workgroup compaction, the ray state machine (the full one and its any-hit form, one template), the light's direction and
+// the per-pixel shading.  Everything here has internal linkage; each source file instantiates what it exports.
+#ifndef OI_TRACE_COMMON_H_
+#define OI_TRACE_COMMON_H_
+
+#include "oi_common.h"
+#include "../../include/oi_trace.h"
+
+namespace {
+
+constexpr int TR_THREADS = 256;
+constexpr int TR_WAVES = TR_THREADS / 64;
+constexpr int N_HIT_WORD = OI_TRACE_COUNT_WORDS - 1;
+static_assert(OI_TRACE_COUNT_WORDS == OI_TRACE_MAX_STEPS + 2, "counts[0 .. MAX_STEPS] and the hit count");
+
+__device__ __forceinline__ bool finite_(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+__device__ __forceinline__ void normalize3(float& x, float& y, float& z, float eps) {
+  // F.normalize(v, eps): v / max(|v|, eps)   (relight.hip's helper)
+  const float n = fmaxf(sqrtf(x * x + y * y + z * z), eps);
+  x /= n;
+  y /= n;
+  z /= n;
+}
+
+// the sample point of ray (o, d) at t: the one expression every kernel here uses, so a hit's position is bit-equal to the
+// point the MLP was given
+__device__ __forceinline__ void point_at(const float* __restrict__ o, const float* __restrict__ d, long long r, float t,
+                                         float* __restrict__ dst) {
+  dst[0] = __fmaf_rn(t, d[r * 3 + 0], o[r * 3 + 0]);
+  dst[1] = __fmaf_rn(t, d[r * 3 + 1], o[r * 3 + 1]);
+  dst[2] = __fmaf_rn(t, d[r * 3 + 2], o[r * 3 + 2]);
+}
+
+// Dense output slot of this thread (meaningful where `keep`), the workgroup's kept threads in thread order behind
+// `*counter`'s previous value.  Every thread of the workgroup calls it.  lds: TR_WAVES + 1 words.
+__device__ __forceinline__ long long wg_slot(bool keep, int* counter, unsigned* lds) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(keep);
+  const unsigned pre = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+  if (lane == 0) lds[wave] = (unsigned)__popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned tot = 0;
+    for (int w = 0; w < TR_WAVES; ++w) {
+      const unsigned c = lds[w];
+      lds[w] = tot;
+      tot += c;
+    }
+    lds[TR_WAVES] = tot ? (unsigned)atomicAdd(counter, (int)tot) : 0u;
+  }
+  __syncthreads();
+  return (long long)lds[TR_WAVES] + lds[wave] + pre;
+}
+
+__device__ __forceinline__ void clear_counts(int* counts, int first) {
+  if (blockIdx.x == 0)
+    for (int i = threadIdx.x; i < OI_TRACE_COUNT_WORDS; i += TR_THREADS) counts[i] = i == 0 ? first : 0;
+}
+
+__global__ void __launch_bounds__(TR_THREADS) trace_clear_counts_kernel(int* counts) { clear_counts(counts, 0); }
+
+// One step of the ray state machine on the sdf of the last MLP pass, and the compaction of the rays still in flight.
+// ANYHIT = false: oi_trace_step (march, bracket, Illinois regula falsi).  ANYHIT = true: oi_occlusion_step, whose MARCH
+// phase is the same and whose first later negative sample ends the ray as a HIT at that sample: there is no REFINE state.
+template <bool ANYHIT>
+__global__ void __launch_bounds__(TR_THREADS) trace_step_kernel(const oi_trace_state s, const float* __restrict__ sdf,
+                                                                long long bound, int k, float tol, float omega) {
+  __shared__ unsigned lds[TR_WAVES + 1];
+  long long cnt = s.counts[k];
+  cnt = cnt < bound ? cnt : bound;
+  const long long j0 = (long long)blockIdx.x * TR_THREADS;
+  if (j0 >= cnt) return;  // the whole workgroup: slots at or above the count hold rays that ended earlier
+  const long long j = j0 + threadIdx.x;
+  const int* __restrict__ act_in = s.active + (long long)(k & 1) * s.N;
+  int* __restrict__ act_out = s.active + (long long)((k + 1) & 1) * s.N;
+  bool alive = false;
+  long long r = 0;
+  float tn = 0.f;
+  if (j < cnt) {
+    r = act_in[j];
+    const float v = sdf[j];
+    float t = s.t[r];
+    const unsigned n_eval = (unsigned)s.steps[r] + 1u;
+    s.steps[r] = (uint16_t)n_eval;
+    unsigned st = s.status[r];
+    if (!finite_(v)) {
+      st = OI_TRACE_NONFINITE;
+    } else if (fabsf(v) <= tol) {
+      st = OI_TRACE_HIT;
+    } else if (st == OI_TRACE_MARCH && v > 0.f) {
+      if (!ANYHIT) {  // the bracket's low end: only a refinement reads it
+        s.bracket[r * 4 + 0] = t;
+        s.bracket[r * 4 + 1] = v;
+      }
+      t += fmaxf(omega * v, tol);
+      if (t > s.far_[r]) st = OI_TRACE_MISS;
+      else alive = true;
+    } else if (st == OI_TRACE_MARCH && n_eval == 1u) {
+      st = OI_TRACE_START_INSIDE;
+    } else if (ANYHIT) {
+      st = OI_TRACE_HIT;  // an occluder: nobody reads the root
+    } else {
+      float t_lo = s.bracket[r * 4 + 0], s_lo = s.bracket[r * 4 + 1], t_hi, s_hi;
+      unsigned side = 0;
+      if (st == OI_TRACE_MARCH) {  // the first negative sample closes the bracket
+        t_hi = t;
+        s_hi = v;
+        st = OI_TRACE_REFINE;
+      } else {
+        t_hi = s.bracket[r * 4 + 2];
+        s_hi = s.bracket[r * 4 + 3];
+        side = s.side[r];
+        if (v > 0.f) {
+          if (side == 1u) s_hi *= 0.5f;
+          t_lo = t;
+          s_lo = v;
+          side = 1u;
+        } else {
+          if (side == 2u) s_lo *= 0.5f;
+          t_hi = t;
+          s_hi = v;
+          side = 2u;
+        }
+      }
+      t = __fmaf_rn(t_hi - t_lo, s_lo / (s_lo - s_hi), t_lo);
+      if (!(t > t_lo && t < t_hi)) t = 0.5f * (t_lo + t_hi);
+      if (!(t > t_lo && t < t_hi)) {  // the ends are adjacent numbers: nothing left to split
+        t = t_hi;
+        st = OI_TRACE_HIT;
+      } else {
+        alive = true;
+        s.bracket[r * 4 + 0] = t_lo;
+        s.bracket[r * 4 + 1] = s_lo;
+        s.bracket[r * 4 + 2] = t_hi;
+        s.bracket[r * 4 + 3] = s_hi;
+        s.side[r] = (uint8_t)side;
+      }
+    }
+    s.t[r] = t;
+    s.status[r] = (uint8_t)st;
+    tn = t;
+  }
+  const long long slot = wg_slot(alive, s.counts + k + 1, lds);
+  if (alive) {
+    act_out[slot] = (int)r;
+    point_at(s.rays_o, s.rays_d, r, tn, s.points + slot * 3);
+  }
+}
+
+// light l's unit direction in the object frame: relight.hip's expressions
+__device__ __forceinline__ void light_dir(const float* __restrict__ lt, const float* __restrict__ Wb, float& lx, float& ly,
+                                          float& lz) {
+  const float l0 = lt[0], l1 = lt[1], l2 = lt[2];
+  const float ln = sqrtf(l0 * l0 + l1 * l1 + l2 * l2);
+  lx = Wb[0] * (l0 / ln) + Wb[1] * (l1 / ln) + Wb[2] * (l2 / ln);
+  ly = Wb[4] * (l0 / ln) + Wb[5] * (l1 / ln) + Wb[6] * (l2 / ln);
+  lz = Wb[8] * (l0 / ln) + Wb[9] * (l1 / ln) + Wb[10] * (l2 / ln);
+  normalize3(lx, ly, lz, 1e-6f);
+}
+
+// The exit of the unit sphere along (o, d), |o + t d| = 1: 0 when the origin is outside and the ray leaves it.
+__device__ __forceinline__ float unit_sphere_exit(float ox, float oy, float oz, float dx, float dy, float dz) {
+  const float b = ox * dx + oy * dy + oz * dz, c = ox * ox + oy * oy + oz * oz - 1.0f;
+  const float disc = b * b - c;
+  return disc > 0.f ? fmaxf(sqrtf(disc) - b, 0.f) : 0.f;
+}
+
+// One pixel of the G-buffer and of the Phong image.  P: oi_surface_params or a struct with the same fields; ao: [N] ambient
+// occlusion or nullptr (the ambient term as it is).
+template <class P>
+__device__ __forceinline__ void surface_shade_pixel(const P& p, const float* __restrict__ ao) {
+  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (r >= p.N) return;
+  const bool hit = p.status[r] == OI_TRACE_HIT;
+  const float b3[3] = {p.bg ? p.bg[0] : 0.f, p.bg ? p.bg[1] : 0.f, p.bg ? p.bg[2] : 0.f};
+  float pos[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f}, nw[3] = {0.f, 0.f, 0.f}, alb[3] = {0.f, 0.f, 0.f};
+  float vx = 0.f, vy = 0.f, vz = 0.f;
+  const float* Wb = p.w2b;
+  if (hit) {
+    const long long k = p.hit_slot[r];
+    const float gx = p.grad[k * 3 + 0], gy = p.grad[k * 3 + 1], gz = p.grad[k * 3 + 2];
+    const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);  // relight.hip's normal
+    n[0] = gx / gnc, n[1] = gy / gnc, n[2] = gz / gnc;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      pos[a] = p.hit_points[k * 3 + a];
+      alb[a] = p.rgb[k * 3 + a];
+      nw[a] = Wb[0 + a] * n[0] + Wb[4 + a] * n[1] + Wb[8 + a] * n[2];  // w2b[:3,:3]^T n
+    }
+    vx = p.rays_o[r * 3 + 0] - pos[0], vy = p.rays_o[r * 3 + 1] - pos[1], vz = p.rays_o[r * 3 + 2] - pos[2];
+    normalize3(vx, vy, vz, 1e-6f);
+  }
+  if (p.depth) p.depth[r] = hit ? p.t[r] : __uint_as_float(0x7fc00000u);
+  if (p.mask) p.mask[r] = hit ? 1.0f : 0.0f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (p.position) p.position[r * 3 + a] = pos[a];
+    if (p.normal) p.normal[r * 3 + a] = n[a];
+    if (p.normal_world) p.normal_world[r * 3 + a] = nw[a];
+    if (p.albedo) p.albedo[r * 3 + a] = alb[a];
+  }
+  if (!p.image) return;
+  const bool occluded = ao != nullptr;
+  const float aov = occluded && hit ? ao[r] : 1.0f;
+  for (int l = 0; l < p.L; ++l) {
+    float* img = p.image + (long long)l * 3 * p.N + r;
+    if (!hit) {
+      img[0] = b3[0], img[p.N] = b3[1], img[2 * p.N] = b3[2];
+      continue;
+    }
+    const float* lt = p.lights + (long long)l * OI_RELIGHT_LIGHT_FLOATS;
+    float lx, ly, lz;
+    light_dir(lt, Wb, lx, ly, lz);
+    // Phong terms: relight_kernel's expressions at weight 1 (relight.hip)
+    const float ndl = n[0] * lx + n[1] * ly + n[2] * lz;
+    const float rl = fmaxf(ndl, 0.f);
+    const float rx = -lx + 2.0f * (ndl * n[0]), ry = -ly + 2.0f * (ndl * n[1]), rz = -lz + 2.0f * (ndl * n[2]);
+    const float al = fmaxf(vx * rx + vy * ry + vz * rz, 0.f) * (ndl > 0.f ? 1.f : 0.f);
+    const float pw = powf(al, lt[15]);
+    const bool shadowed = p.visibility != nullptr;
+    const float vis = shadowed ? p.visibility[(long long)l * p.N + r] : 1.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float diff = lt[8 + c] * rl, spec = lt[12 + c] * pw;
+      if (shadowed) diff *= vis, spec *= vis;
+      // (a product rounded on its own: the sum below contracts with the diffuse term whether or not ao is given)
+      const float amb = occluded ? __fmul_rn(aov, lt[4 + c]) : lt[4 + c];
+      const float shade = amb + diff;
+      img[c * p.N] = shade * alb[c] + spec;
+    }
+  }
+}
+
+inline unsigned n_blocks(long long n) { return (unsigned)((n + TR_THREADS - 1) / TR_THREADS); }
+
+inline int check_state(const oi_trace_state* s, const char* what) {
+  OI_REQUIRE(s != nullptr, "%s: null state", what);
+  OI_REQUIRE(s->N >= 1 && s->N < (1ll << 31), "%s: N=%lld rays (1 <= N < 2^31)", what, s->N);
+  OI_REQUIRE(s->rays_o && s->rays_d && s->near_ && s->far_ && s->t && s->status && s->steps && s->bracket && s->side &&
+                 s->active && s->points && s->counts,
+             "%s: null pointer in the state", what);
+  return OI_OK;
+}
+
+// Arguments of oi_trace_step and oi_occlusion_step, then the launch.
+template <bool ANYHIT>
+inline int launch_step(const char* what, const oi_trace_state* s, const float* sdf, long long bound, int k, float tol,
+                       float omega, oi_stream_t stream) {
+  int rc = check_state(s, what);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(k >= 0 && k < OI_TRACE_MAX_STEPS, "%s: step k=%d (0 <= k < %d)", what, k, OI_TRACE_MAX_STEPS);
+  OI_REQUIRE(bound >= 0 && bound <= s->N, "%s: bound=%lld (0 <= bound <= N=%lld)", what, bound, s->N);
+  OI_REQUIRE(tol > 0.f && omega > 0.f && tol < INFINITY && omega < INFINITY, "%s: tol %g, omega %g (both > 0, finite)", what,
+             (double)tol, (double)omega);
+  if (bound == 0) return OI_OK;
+  OI_REQUIRE(sdf != nullptr, "%s: null sdf", what);
+  hipLaunchKernelGGL(trace_step_kernel<ANYHIT>, dim3(n_blocks(bound)), dim3(TR_THREADS), 0, oi::as_stream(stream), *s, sdf, bound,
+                     k, tol, omega);
+  return oi::check_launch(what);
+}
+
+// Arguments of oi_surface_shade and oi_surface_shade_ao (P: oi_surface_params or a struct with the same fields).
+template <class P>
+inline int check_surface(const char* what, const P* p) {
+  OI_REQUIRE(p != nullptr, "%s: null params", what);
+  OI_REQUIRE(p->N >= 1 && p->N < (1ll << 31) && p->n_hit >= 0 && p->n_hit <= p->N, "%s: N=%lld, n_hit=%lld", what, p->N, p->n_hit);
+  OI_REQUIRE(p->image ? (p->L >= 1 && p->L <= OI_RELIGHT_MAX_LIGHTS && p->lights) : p->L >= 0,
+             "%s: L=%d (1 .. %d lights with an image)", what, p->L, OI_RELIGHT_MAX_LIGHTS);
+  OI_REQUIRE(p->rays_o && p->rays_d && p->t && p->status && p->hit_slot && p->w2b, "%s: null input pointer", what);
+  OI_REQUIRE(p->n_hit == 0 || (p->hit_points && p->grad && p->rgb), "%s: null hit arrays with n_hit=%lld", what, p->n_hit);
+  return OI_OK;
+}
+
+}  // namespace
+
+#endif  // OI_TRACE_COMMON_H_

@@ -139,19 +139,31 @@ def light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), **kw):
     return relight_frames(gen, z, b2w, lights, **kw)
 
 
-SURFACE_KEYS = ("image", "depth", "position", "normal_map", "normal_object", "albedo", "mask", "visibility")
+SURFACE_KEYS = ("image", "depth", "position", "normal_map", "normal_object", "albedo", "mask", "visibility", "ambient_occlusion")
+
+# Bytes of device memory per ray of one secondary (shadow / ambient-occlusion) trace: the arrays of an ops.TraceState (rays_o
+# 12, rays_d 12, near 4, far 4, t 4, status 1, steps 2, bracket 16, side 1, active 2 x 4, points 12 = 76), the sdf buffer of
+# the loop (4) and oi_trace_finish's outputs (hit_index 4, hit_points 12, hit_slot 4).
+TRACE_BYTES_PER_RAY = 76 + 4 + 20
+# Rays one secondary trace of a light walk may hold: a budget of 2 GiB of device memory for its working set -- small beside
+# the card's HBM, and large enough that a 128-frame walk at 128^2 with 16 samples per light (7 M rays) is one trace -- and
+# below oi_trace_state's 2^31 rays.
+OCCLUSION_MAX_RAYS = min((2 << 30) // TRACE_BYTES_PER_RAY, (1 << 31) - 1)
 
 
 @torch.no_grad()
 def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"), lights=None, shadows=False, bg=None, **kw):
     """render_frames by ray / surface intersection (oi_amd.trace.render_surface) instead of the volume render: one frame per
     (z, b2w) pair under ONE light (`lights`: a Light, default the trained one).  -> {key: (n, C, H, W)} for keys of
-    SURFACE_KEYS ("visibility" needs shadows=True).  Keyword arguments: render_surface's (bias, tol, omega, max_steps)."""
+    SURFACE_KEYS ("visibility" needs shadows=True, "ambient_occlusion" ao_samples > 0).  Keyword arguments: render_surface's
+    (bias, tol, omega, max_steps; shadow_samples, light_radius, ao_samples, ao_distance, seed)."""
     from . import trace
     from .relight import Light
     unknown = [k for k in keys if k not in SURFACE_KEYS]
     if unknown or ("visibility" in keys and not shadows):
         raise ValueError(f"surface_frames: keys {unknown or ['visibility']} (one of {SURFACE_KEYS}; visibility with shadows=True)")
+    if "ambient_occlusion" in keys and not kw.get("ao_samples", 0):
+        raise ValueError("surface_frames: keys ['ambient_occlusion'] need ao_samples > 0")
     if lights is not None and not isinstance(lights, Light):
         raise TypeError("surface_frames: one Light per walk (surface_light_walk varies the light)")
     gen.eval()
@@ -165,10 +177,15 @@ def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"),
 
 
 @torch.no_grad()
-def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True, bg=None, bias=None, **kw):
+def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True, bg=None, bias=None, shadow_samples=1,
+                       light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0, **kw):
     """light_walk on the traced surface, with cast shadows: ONE primary trace and ONE full MLP pass at its hits for the whole
     walk, one shadow trace and one shade launch per 256 lights.  Frame 0 is the trained light.  -> {"image": (n_frames, 3,
-    H, W), "visibility": (n_frames, 1, H, W) when shadows, "mask" / "depth" (1, 1, H, W), "stats"}."""
+    H, W), "visibility": (n_frames, 1, H, W) when shadows, "mask" / "depth" (1, 1, H, W), "stats"}.
+    shadow_samples, light_radius (a scalar or one value per frame), ao_samples, ao_distance, seed: render_surface's.  Soft shadows trace
+    shadow_samples rays per light and visible point, so the lights are split further until one trace holds at most
+    OCCLUSION_MAX_RAYS rays; the frames do not depend on the split (rays are independent, the samples keyed on pixel and seed).
+    Ambient occlusion does not depend on the light: ONE trace for the walk, returned as "ambient_occlusion" (1, 1, H, W)."""
     from . import lib, trace
     from .relight import Light, stack_lights
     base = Light.from_module(gen.light)
@@ -177,24 +194,34 @@ def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True,
     lt = stack_lights([base] + [base.replace(direction=tuple(d)) for d in dirs[1:]], dev)
     gen.eval()
     gen.renderer.pack.check()
+    radii = trace._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_frames,
+                                   "surface_light_walk")
     s = trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw)
     H = s.H
     image = torch.empty(n_frames, 3, s.N, device=dev)
     vis_all = torch.empty(n_frames, s.N, device=dev) if shadows else None
     step = lib.RELIGHT_MAX_LIGHTS
+    if radii is not None:
+        step = max(1, min(step, OCCLUSION_MAX_RAYS // (int(shadow_samples) * max(1, s.n_hit))))
+        radii = torch.tensor(radii, dtype=torch.float32, device=dev)
+    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed)) if ao_samples else None
     maps = None
     for a in range(0, n_frames, step):
         b = min(n_frames, a + step)
-        vis = s.visibility(lt[a:b]) if shadows else None
         if shadows:
+            vis = s.visibility(lt[a:b]) if radii is None else s.visibility(lt[a:b], radii[a:b], int(shadow_samples), int(seed))
             vis_all[a:b] = vis
+        else:
+            vis = None
         out = s.shade(lt[a:b], trace._bg(bg, dev), vis, outputs=("image",) if maps is not None else ("depth", "mask", "image"),
-                      image_out=image[a:b])
+                      image_out=image[a:b], ambient_occlusion=ao)
         maps = maps or out
     res = {"image": image.view(n_frames, 3, H, H), "mask": maps["mask"].view(1, 1, H, H), "depth": maps["depth"].view(1, 1, H, H),
            "stats": s.stats()}
     if shadows:
         res["visibility"] = vis_all.view(n_frames, 1, H, H)
+    if ao_samples:
+        res["ambient_occlusion"] = ao.view(1, 1, H, H)
     return res
 
 

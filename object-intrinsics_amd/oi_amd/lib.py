@@ -1,5 +1,5 @@
 """ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h, include/oi_mesh_attr.h,
-include/oi_trace.h and include/oi_mesh_band.h).
+include/oi_trace.h, include/oi_occlusion.h and include/oi_mesh_band.h).
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -214,6 +214,25 @@ _TRACE_SIGS = {
     "oi_surface_shade": (_i, [ctypes.POINTER(SurfaceParams), _vp]),
 }
 
+# include/oi_occlusion.h: soft shadows and ambient occlusion on the traced surface (an addition to oi_trace.h; its entries
+# work on an oi_trace_state)
+OCCLUSION_MAX_SAMPLES = 256
+
+
+class SurfaceAoParams(ctypes.Structure):
+    """Mirror of `oi_surface_ao_params` (include/oi_occlusion.h): SurfaceParams' fields, then the occlusion factor."""
+    _fields_ = SurfaceParams._fields_ + [("ambient_occlusion", _vp)]
+
+
+_u = ctypes.c_uint
+_OCCLUSION_SIGS = {
+    "oi_occlusion_light_begin": (_i, [ctypes.POINTER(TraceState), _vp, _vp, _vp, _ll, _vp, _vp, _i, _i, _vp, _f, _u, _vp]),
+    "oi_occlusion_ambient_begin": (_i, [ctypes.POINTER(TraceState), _vp, _vp, _vp, _ll, _i, _f, _f, _u, _vp]),
+    "oi_occlusion_step": (_i, [ctypes.POINTER(TraceState), _vp, _ll, _i, _f, _f, _vp]),
+    "oi_occlusion_resolve": (_i, [_vp, _vp, _ll, _ll, _i, _i, _vp, _vp]),
+    "oi_surface_shade_ao": (_i, [ctypes.POINTER(SurfaceAoParams), _vp]),
+}
+
 # include/oi_mesh_band.h: narrow-band mesh extraction (accelerates renderer.py:15-41; no reference counterpart either)
 BAND_MIN_RES, BAND_MAX_RES = 2, 1024
 _d = ctypes.c_double
@@ -251,6 +270,11 @@ def trace_symbols():
     return sorted(_TRACE_SIGS)
 
 
+def occlusion_symbols():
+    """The entry points of include/oi_occlusion.h."""
+    return sorted(_OCCLUSION_SIGS)
+
+
 def mesh_band_symbols():
     """The entry points of include/oi_mesh_band.h."""
     return sorted(_MESH_BAND_SIGS)
@@ -274,7 +298,8 @@ def load():
                 f"{LIB_PATH} not found: build it with `python object-intrinsics_amd/build.py` (hipcc, gfx950). "
                 "oi_amd has no CPU or PyTorch fallback for its kernels.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_TRACE_SIGS, **_MESH_BAND_SIGS, **_OPTIONAL_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_TRACE_SIGS, **_OCCLUSION_SIGS, **_MESH_BAND_SIGS,
+                                   **_OPTIONAL_SIGS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError:

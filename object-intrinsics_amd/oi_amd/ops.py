@@ -663,21 +663,19 @@ def trace_visibility(shadow_status, hit_slot, N, n_hit, L):
 SURFACE_OUT = {"depth": (1,), "position": (3,), "normal": (3,), "normal_world": (3,), "albedo": (3,), "mask": (1,)}
 
 
-def surface_shade(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b, lights=None, bg=None,
-                  visibility=None, outputs=tuple(SURFACE_OUT) + ("image",), image_out=None):
-    """The G-buffer and the Phong image of a traced view (oi_surface_shade).  -> {name: (N,) or (N, 3)} for the names of
-    SURFACE_OUT in `outputs`, and "image" (L, 3, N) (written into `image_out` when given)."""
+def _surface_shade(what, P, rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b, lights, bg, visibility,
+                   outputs, image_out):
+    """The arguments surface_shade and surface_shade_ao share, filled into the struct P.  -> (outputs, tensors to keep)."""
     N = t.shape[0]
     for name in outputs:
         if name not in SURFACE_OUT and name != "image":
-            raise ValueError(f"surface_shade: unknown output {name!r} (one of {tuple(SURFACE_OUT) + ('image',)})")
+            raise ValueError(f"{what}: unknown output {name!r} (one of {tuple(SURFACE_OUT) + ('image',)})")
     nl = 0 if lights is None else lights.shape[0]
     if "image" in outputs and (nl < 1 or nl > _l.RELIGHT_MAX_LIGHTS or tuple(lights.shape[1:]) != (_l.RELIGHT_LIGHT_FLOATS,)):
-        raise ValueError(f"surface_shade: lights {None if lights is None else tuple(lights.shape)}, expected (L, "
+        raise ValueError(f"{what}: lights {None if lights is None else tuple(lights.shape)}, expected (L, "
                          f"{_l.RELIGHT_LIGHT_FLOATS}) with 1 <= L <= {_l.RELIGHT_MAX_LIGHTS}")
     if visibility is not None and tuple(visibility.shape) != (nl, N):
-        raise ValueError(f"surface_shade: visibility {tuple(visibility.shape)}, expected {(nl, N)}")
-    P = _l.SurfaceParams()
+        raise ValueError(f"{what}: visibility {tuple(visibility.shape)}, expected {(nl, N)}")
     P.N, P.n_hit, P.L = N, int(n_hit), nl
     keep = [_c(x) for x in (rays_o, rays_d, t, hit_points, grad, rgb, w2b, lights, bg, visibility)]
     (P.rays_o, P.rays_d, P.t, P.hit_points, P.grad, P.rgb, P.w2b, P.lights, P.bg, P.visibility) = (_p(x) for x in keep)
@@ -691,10 +689,67 @@ def surface_shade(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_
         if image_out is None:
             image_out = _new(t, nl, 3, N)
         elif tuple(image_out.shape) != (nl, 3, N) or not image_out.is_contiguous() or image_out.dtype != torch.float32:
-            raise ValueError(f"surface_shade: image_out must be a contiguous float32 {(nl, 3, N)} tensor")
+            raise ValueError(f"{what}: image_out must be a contiguous float32 {(nl, 3, N)} tensor")
         res["image"] = image_out
     P.image = _p(res.get("image"))
+    return res, keep
+
+
+def surface_shade(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b, lights=None, bg=None,
+                  visibility=None, outputs=tuple(SURFACE_OUT) + ("image",), image_out=None):
+    """The G-buffer and the Phong image of a traced view (oi_surface_shade).  -> {name: (N,) or (N, 3)} for the names of
+    SURFACE_OUT in `outputs`, and "image" (L, 3, N) (written into `image_out` when given)."""
+    P = _l.SurfaceParams()
+    res, _keep = _surface_shade("surface_shade", P, rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b, lights,
+                                bg, visibility, outputs, image_out)
     _l.check(_l.load().oi_surface_shade(ctypes.byref(P), _stream()), "oi_surface_shade")
+    return res
+
+
+# ------------------------------------------------------------------------------------------
+# soft shadows and ambient occlusion on the traced surface (include/oi_occlusion.h)
+# ------------------------------------------------------------------------------------------
+
+def occlusion_light_begin(st, hit_points, grad, hit_index, n_hit, lights, radius, samples, w2b, bias, seed=0):
+    """S = samples rays per (light, hit) into the TraceState st of L * S * n_hit rays; radius (L,) float32 on the device."""
+    if not torch.is_tensor(radius) or radius.dtype != torch.float32 or tuple(radius.shape) != (lights.shape[0],):
+        raise ValueError(f"occlusion_light_begin: radius must be a float32 tensor of shape ({lights.shape[0]},), one per light")
+    _l.check(_l.load().oi_occlusion_light_begin(ctypes.byref(st.c), _p(hit_points), _p(grad), _ip(hit_index), int(n_hit), _p(lights),
+                                                _p(radius), lights.shape[0], int(samples), _p(w2b), float(bias), int(seed),
+                                                _stream()), "oi_occlusion_light_begin")
+
+
+def occlusion_ambient_begin(st, hit_points, grad, hit_index, n_hit, samples, bias, distance, seed=0):
+    """S = samples hemisphere rays per hit into the TraceState st of S * n_hit rays."""
+    _l.check(_l.load().oi_occlusion_ambient_begin(ctypes.byref(st.c), _p(hit_points), _p(grad), _ip(hit_index), int(n_hit),
+                                                  int(samples), float(bias), float(distance), int(seed), _stream()),
+             "oi_occlusion_ambient_begin")
+
+
+def occlusion_step(st, sdf, bound, k, tol, omega):
+    _l.check(_l.load().oi_occlusion_step(ctypes.byref(st.c), _p(sdf), int(bound), int(k), float(tol), float(omega), _stream()),
+             "oi_occlusion_step")
+
+
+def occlusion_resolve(status, hit_slot, N, n_hit, L, samples):
+    """-> (L, N) float32: the share of each pixel's `samples` rays per light that ended TRACE_MISS (1 off the mask)."""
+    out = _new(hit_slot, L, N)
+    _l.check(_l.load().oi_occlusion_resolve(_p(status), _ip(hit_slot), int(N), int(n_hit), int(L), int(samples), _p(out),
+                                            _stream()), "oi_occlusion_resolve")
+    return out
+
+
+def surface_shade_ao(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b, lights=None, bg=None,
+                     visibility=None, ambient_occlusion=None, outputs=tuple(SURFACE_OUT) + ("image",), image_out=None):
+    """surface_shade with an occlusion factor (N,) in [0, 1] on the ambient term (oi_surface_shade_ao)."""
+    if ambient_occlusion is not None and tuple(ambient_occlusion.shape) != (t.shape[0],):
+        raise ValueError(f"surface_shade_ao: ambient_occlusion {tuple(ambient_occlusion.shape)}, expected {(t.shape[0],)}")
+    P = _l.SurfaceAoParams()
+    res, _keep = _surface_shade("surface_shade_ao", P, rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b,
+                                lights, bg, visibility, outputs, image_out)
+    ao = _c(ambient_occlusion)
+    P.ambient_occlusion = _p(ao)
+    _l.check(_l.load().oi_surface_shade_ao(ctypes.byref(P), _stream()), "oi_surface_shade_ao")
     return res
 
 

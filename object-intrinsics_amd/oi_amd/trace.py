@@ -3,7 +3,9 @@
 
     sphere_trace     rays against the learned SDF -> per-ray t, status, evaluations, the dense list of hits
     render_surface   one view of a Generator: depth, position, normals, albedo, mask, the Phong image under L lights,
-                     optionally with cast shadows (one shadow ray per light and visible point)
+                     optionally with cast shadows (one shadow ray per light and visible point, or `shadow_samples` rays
+                     towards a light of angular radius `light_radius`: penumbrae) and ambient occlusion (`ao_samples` rays
+                     over the hemisphere of each visible point; include/oi_occlusion.h)
 
 The loop runs on the host: oi_trace_begin, then per step the library's sdf-only MLP pass (unchanged) on the rays still in
 flight and oi_trace_step, which advances them and compacts the survivors.  The number of rays in flight lives on the device;
@@ -57,8 +59,9 @@ def _check_params(tol, omega, max_steps, readback, what):
         raise ValueError(f"{what}: readback={readback!r} ('auto' or a positive number of steps)")
 
 
-def _march(field, st, bound, tol, omega, max_steps, readback):
-    """The loop on a state that oi_trace_begin / oi_trace_shadow_begin has filled.  -> (points evaluated, steps run).
+def _march(field, st, bound, tol, omega, max_steps, readback, anyhit=False):
+    """The loop on a state that oi_trace_begin / oi_trace_shadow_begin / oi_occlusion_*_begin has filled.  -> (points
+    evaluated, steps run).  anyhit: step with oi_occlusion_step (a ray ends at its first occluder) instead of oi_trace_step.
     Two launches per step through the C ABI directly, with the pointers converted once: the loop's tail is a handful of rays
     per step, where the host's time per launch is the frame's time."""
     import ctypes
@@ -67,14 +70,15 @@ def _march(field, st, bound, tol, omega, max_steps, readback):
     pts_p, sdf_p, state_p, stream = ops._p(st.points), ops._p(sdf), ctypes.byref(st.c), ops._stream()
     packed_p, gamma_p, beta_p = ops._p(field.packed), ops._p(field.gamma), ops._p(field.beta)
     prec, trig = field.prec, field.fast
+    step, step_name = (L.oi_occlusion_step, "oi_occlusion_step") if anyhit else (L.oi_trace_step, "oi_trace_step")
     n_evals = k = since = 0
     while k < max_steps and bound > 0:
         rc = L.oi_sdf_mlp_fwd(pts_p, packed_p, gamma_p, beta_p, sdf_p, None, None, None, None, 1, bound, prec, trig, stream)
         if rc:
             _l.check(rc, "oi_sdf_mlp_fwd")
-        rc = L.oi_trace_step(state_p, sdf_p, bound, k, tol, omega, stream)
+        rc = step(state_p, sdf_p, bound, k, tol, omega, stream)
         if rc:
-            _l.check(rc, "oi_trace_step")
+            _l.check(rc, step_name)
         n_evals += bound
         k += 1
         since += 1
@@ -163,34 +167,90 @@ class _Surface:
         self.grad = self.rgb = None
         if self.n_hit:
             _, self.grad, self.rgb = self.field.full(self.res.hit_points)
-        self.shadow_evals = 0
-        self.shadow = None
+        self.shadow_evals = self.ao_evals = 0
+        self.shadow = self.ao = None
 
-    def visibility(self, lights):
-        """(L, N) visibility of `lights` (L, 16): one shadow trace over all L x n_hit rays."""
+    def _secondary(self, st):
+        """The any-hit loop on a state an oi_occlusion_*_begin has filled; rays in flight at the end -> LIMIT."""
+        n_evals, _ = _march(self.field, st, int(st.counts[0].item()), *self.kw, anyhit=True)
+        ops.trace_finish(st)
+        return n_evals
+
+    def visibility(self, lights, radius=None, samples=1, seed=0):
+        """(L, N) visibility of `lights` (L, 16).  radius None and one sample: one shadow trace over all L x n_hit rays (0 or
+        1 per pixel).  Otherwise radius (L,) holds the lights' angular radii and one any-hit trace runs over all
+        L x samples x n_hit rays: the share of a pixel's samples that reach the light."""
         L = lights.shape[0]
         if self.n_hit == 0:
             return torch.ones(L, self.N, device=self.ro.device)
-        st = ops.TraceState(L * self.n_hit, ref=self.ro)
-        ops.trace_shadow_begin(st, self.res.hit_points, self.grad, self.n_hit, lights, self.w2b, self.bias)
-        bound = int(st.counts[0].item())
-        n_evals, _ = _march(self.field, st, bound, *self.kw)
-        ops.trace_finish(st)   # in-flight rays -> LIMIT
-        self.shadow_evals += n_evals
+        if radius is None and samples == 1:
+            st = ops.TraceState(L * self.n_hit, ref=self.ro)
+            ops.trace_shadow_begin(st, self.res.hit_points, self.grad, self.n_hit, lights, self.w2b, self.bias)
+            bound = int(st.counts[0].item())
+            n_evals, _ = _march(self.field, st, bound, *self.kw)
+            ops.trace_finish(st)   # in-flight rays -> LIMIT
+            self.shadow_evals += n_evals
+            self.shadow = st
+            return ops.trace_visibility(st.status, self.res.hit_slot, self.N, self.n_hit, L)
+        if radius is None:
+            radius = torch.zeros(L, device=self.ro.device)
+        st = ops.TraceState(L * samples * self.n_hit, ref=self.ro)
+        ops.occlusion_light_begin(st, self.res.hit_points, self.grad, self.res.hit_index, self.n_hit, lights, radius, samples,
+                                  self.w2b, self.bias, seed)
+        self.shadow_evals += self._secondary(st)
         self.shadow = st
-        return ops.trace_visibility(st.status, self.res.hit_slot, self.N, self.n_hit, L)
+        return ops.occlusion_resolve(st.status, self.res.hit_slot, self.N, self.n_hit, L, samples)
 
-    def shade(self, lights, bg, visibility=None, outputs=tuple(ops.SURFACE_OUT) + ("image",), image_out=None):
+    def ambient(self, samples, distance, seed=0):
+        """(N,) ambient occlusion: the share of `samples` cosine-weighted hemisphere rays per visible point that leave the
+        point's neighbourhood (`distance`) without meeting the surface; 1 off the mask."""
+        if self.n_hit == 0:
+            return torch.ones(self.N, device=self.ro.device)
+        st = ops.TraceState(samples * self.n_hit, ref=self.ro)
+        ops.occlusion_ambient_begin(st, self.res.hit_points, self.grad, self.res.hit_index, self.n_hit, samples, self.bias,
+                                    distance, seed)
+        self.ao_evals += self._secondary(st)
+        self.ao = st
+        return ops.occlusion_resolve(st.status, self.res.hit_slot, self.N, self.n_hit, 1, samples).view(self.N)
+
+    def shade(self, lights, bg, visibility=None, outputs=tuple(ops.SURFACE_OUT) + ("image",), image_out=None,
+              ambient_occlusion=None):
         r = self.res
         dummy = self.ro   # never read when n_hit == 0
-        return ops.surface_shade(self.ro, self.rd, r.t, r.status, r.hit_slot, r.hit_points if self.n_hit else dummy,
-                                 self.grad if self.n_hit else dummy, self.rgb if self.n_hit else dummy, self.n_hit, self.w2b,
-                                 lights, bg, visibility, outputs, image_out)
+        args = (self.ro, self.rd, r.t, r.status, r.hit_slot, r.hit_points if self.n_hit else dummy,
+                self.grad if self.n_hit else dummy, self.rgb if self.n_hit else dummy, self.n_hit, self.w2b, lights, bg, visibility)
+        if ambient_occlusion is None:
+            return ops.surface_shade(*args, outputs, image_out)
+        return ops.surface_shade_ao(*args, ambient_occlusion, outputs, image_out)
 
     def stats(self):
         s = self.res.counts()
-        s.update(n_rays=self.N, n_evals=self.res.n_evals, n_steps=self.res.n_steps, shadow_evals=self.shadow_evals)
+        s.update(n_rays=self.N, n_evals=self.res.n_evals, n_steps=self.res.n_steps, shadow_evals=self.shadow_evals,
+                 ao_evals=self.ao_evals)
         return s
+
+
+def _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_lights, what):
+    """-> the lights' angular radii as a list of n_lights floats, or None for hard shadows (one ray, no radius)."""
+    def count(v, lo):
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and lo <= int(v) <= _l.OCCLUSION_MAX_SAMPLES
+    if not count(shadow_samples, 1):
+        raise ValueError(f"{what}: shadow_samples={shadow_samples!r} (an integer, 1 <= shadow_samples <= {_l.OCCLUSION_MAX_SAMPLES})")
+    if not count(ao_samples, 0):
+        raise ValueError(f"{what}: ao_samples={ao_samples!r} (an integer, 0 <= ao_samples <= {_l.OCCLUSION_MAX_SAMPLES})")
+    if not (float(ao_distance) > 0 and np.isfinite(float(ao_distance))):
+        raise ValueError(f"{what}: ao_distance={ao_distance!r} (positive and finite)")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 32:
+        raise ValueError(f"{what}: seed={seed!r} (an integer, 0 <= seed < 2^32)")
+    rad = np.asarray(light_radius.detach().cpu() if torch.is_tensor(light_radius) else light_radius, dtype=np.float64)
+    if rad.ndim > 1 or (rad.ndim == 1 and rad.shape[0] != n_lights):
+        raise ValueError(f"{what}: light_radius of shape {rad.shape} (a scalar or one value per light: {n_lights})")
+    if not (np.isfinite(rad).all() and (rad >= 0).all() and (rad <= np.pi / 2).all()):
+        raise ValueError(f"{what}: light_radius={light_radius!r} (radians, 0 <= light_radius <= pi / 2)")
+    soft = int(shadow_samples) != 1 or bool((rad != 0).any())
+    if soft and not shadows:
+        raise ValueError(f"{what}: shadow_samples / light_radius need shadows=True")
+    return np.broadcast_to(rad, (n_lights,)).tolist() if soft else None
 
 
 def _bg(bg, dev):
@@ -207,13 +267,20 @@ _MAP_NAMES = {"depth": "depth", "position": "position", "normal_world": "normal_
 
 
 @torch.no_grad()
-def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAULT_BIAS, **trace_kw):
+def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAULT_BIAS, shadow_samples=1, light_radius=0.0,
+                   ao_samples=0, ao_distance=0.5, seed=0, **trace_kw):
     """One view of `gen` (latent z (z_dim,) or (1, z_dim), pose b2w (4, 4)) by intersecting each pixel's ray with the surface:
     -> dict of depth (1, 1, H, W) (the ray parameter; NaN off the mask), position, normal_map (world frame), normal_object,
     albedo (1, 3, H, W), mask (1, 1, H, W), image (L, 3, H, W) under `lights` (oi_amd.relight.Light objects; default the
     generator's trained light), visibility (L, 1, H, W) when `shadows` (one shadow ray per light and visible point, offset by
     `bias` along the normal), stats (rays per status, sdf evaluations), trace (the primary TraceResult).  The rays are Generator.forward's.  bg: (3,)
-    background colour (black when None).  trace_kw: tol, omega, max_steps, readback of sphere_trace."""
+    background colour (black when None).  trace_kw: tol, omega, max_steps, readback of sphere_trace.
+    Soft shadows: light_radius (radians; a scalar or one value per light) gives the lights an angular size and shadow_samples
+    (1 .. 256) rays per light and visible point sample its cap, so `visibility` is the share in [0, 1] that reaches the light.
+    Ambient occlusion: ao_samples > 0 sends that many cosine-weighted rays over each visible point's hemisphere, as far as
+    ao_distance; the share that escapes multiplies the ambient term and is returned as ambient_occlusion (1, 1, H, W).  The
+    samples are a function of pixel, sample number and `seed` alone.  With shadow_samples == 1, light_radius == 0 and
+    ao_samples == 0 the launches are those of a call without these arguments."""
     from .relight import Light, stack_lights
     dev = gen.it.device
     z = z.to(dev).reshape(1, -1)
@@ -222,14 +289,23 @@ def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAUL
     if lt.shape[0] > _l.RELIGHT_MAX_LIGHTS:
         raise ValueError(f"render_surface: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS}; inference.surface_light_walk "
                          "splits larger sets)")
-    vis = s.visibility(lt) if shadows else None
-    out = s.shade(lt, _bg(bg, dev), vis)
+    radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surface")
+    if radii is None:
+        vis = s.visibility(lt) if shadows else None
+    else:
+        vis = s.visibility(lt, torch.tensor(radii, dtype=torch.float32, device=dev), int(shadow_samples), int(seed))
+    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed)) if ao_samples else None
+    out = s.shade(lt, _bg(bg, dev), vis, ambient_occlusion=ao)
     H = s.H
     res = {_MAP_NAMES[k]: v for k, v in _maps({k: v for k, v in out.items() if k != "image"}, H, H).items()}
     res["image"] = out["image"].view(-1, 3, H, H)
     if shadows:
         res["visibility"] = vis.view(-1, 1, H, H)
         res["shadow_trace"] = s.shadow   # ops.TraceState of the L x n_hit shadow rays (ray l * n_hit + i), or None without a hit
+                                         # (soft shadows: L x shadow_samples x n_hit, ray (l * S + j) * n_hit + i)
+    if ao_samples:
+        res["ambient_occlusion"] = ao.view(1, 1, H, H)
+        res["ao_trace"] = s.ao           # ops.TraceState of the ao_samples x n_hit rays (ray j * n_hit + i), or None
     res["stats"] = s.stats()
     res["trace"] = s.res
     return res

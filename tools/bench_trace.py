@@ -9,7 +9,14 @@ calls after --warmup calls, golden SDF weights, one latent and pose, for each re
   readback              surface_ms with the count of rays in flight read every step / every 4th / every 16th step / 'auto'
   mlp_share             share of surface_ms spent in the sdf-only MLP passes (their launches re-timed alone on the same bounds)
   stats                 rays per status, sdf evaluations, steps
-and, at --walk-res, the 128-frame light walk: surface_light_walk with and without shadows against inference.light_walk."""
+and, at --walk-res, the 128-frame light walk: surface_light_walk with and without shadows against inference.light_walk.
+
+With --shadow-samples S > 1 / --light-radius r > 0 / --ao-samples A > 0 each resolution also gets
+
+  soft                  ms per frame of soft shadows alone, ambient occlusion alone and both together, the secondary rays
+                        and their LIMIT share, and the sdf evaluations per traced secondary ray through the any-hit step
+                        against the full step on the same rays (count read every step)
+and the light walk a row with the soft settings."""
 import argparse
 import json
 import os
@@ -32,6 +39,9 @@ ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--precision", default="f16x3")
 ap.add_argument("--no-volume-above", type=int, default=128, help="skip the volume render above this resolution")
+ap.add_argument("--shadow-samples", type=int, default=1, help="shadow rays per light and visible point")
+ap.add_argument("--light-radius", type=float, default=0.0, help="angular radius of the light, radians")
+ap.add_argument("--ao-samples", type=int, default=0, help="ambient-occlusion rays per visible point (0: none)")
 args = ap.parse_args()
 
 
@@ -59,6 +69,43 @@ def setup(R):
     return gen, z, b2w
 
 
+SOFT = args.shadow_samples > 1 or args.light_radius > 0
+SOFT_KW = dict(shadows=True, shadow_samples=args.shadow_samples, light_radius=args.light_radius) if SOFT else {}
+AO_KW = dict(ao_samples=args.ao_samples) if args.ao_samples else {}
+
+
+def secondary(gen, z, b2w):
+    """Per secondary trace of one frame: rays, traced rays, LIMIT share, evaluations per traced ray any-hit / full."""
+    from oi_amd import lib, ops
+    from oi_amd.relight import Light, stack_lights
+    s = trace._Surface(gen, z.cuda().reshape(1, -1), b2w, trace.DEFAULT_BIAS, {})
+    tol, omega, max_steps, _ = s.kw
+    lt = stack_lights(Light.from_module(gen.light), "cuda")
+    begins = {}
+    if SOFT:
+        radius = torch.full((1,), args.light_radius, device="cuda")
+        begins["shadow"] = (args.shadow_samples, lambda st: ops.occlusion_light_begin(
+            st, s.res.hit_points, s.grad, s.res.hit_index, s.n_hit, lt, radius, args.shadow_samples, s.w2b, s.bias, 0))
+    if args.ao_samples:
+        begins["ao"] = (args.ao_samples, lambda st: ops.occlusion_ambient_begin(
+            st, s.res.hit_points, s.grad, s.res.hit_index, s.n_hit, args.ao_samples, s.bias, 0.5, 0))
+    rows = {}
+    for name, (S, begin) in begins.items():
+        row = {"rays": S * s.n_hit}
+        for anyhit in (True, False):
+            st = ops.TraceState(S * s.n_hit, ref=s.ro)
+            begin(st)
+            traced = int(st.counts[0].item())
+            n_evals, _ = trace._march(s.field, st, traced, tol, omega, max_steps, 1, anyhit=anyhit)
+            ops.trace_finish(st)
+            row["traced"] = traced
+            row["evals_per_ray_anyhit" if anyhit else "evals_per_ray_full"] = n_evals / max(1, traced)
+            if anyhit:
+                row["limit_share"] = int((st.status == lib.TRACE_LIMIT).sum()) / max(1, traced)
+        rows[name] = row
+    return rows
+
+
 out = {"tool": "bench_trace", "precision": args.precision, "iters": args.iters, "warmup": args.warmup, "res": {}}
 with torch.no_grad():
     for R in (int(r) for r in args.res.split(",")):
@@ -84,6 +131,17 @@ with torch.no_grad():
         row["mlp_passes_ms"] = median_ms(mlp_only)
         row["mlp_share"] = row["mlp_passes_ms"] / row["readback"]["1"]
         row["steps_run"] = len(counts)
+        if SOFT or AO_KW:
+            soft = {"shadow_samples": args.shadow_samples, "light_radius": args.light_radius, "ao_samples": args.ao_samples}
+            if SOFT:
+                soft["soft_shadow_ms"] = median_ms(lambda: trace.render_surface(gen, z, b2w, **SOFT_KW))
+            if AO_KW:
+                soft["ao_ms"] = median_ms(lambda: trace.render_surface(gen, z, b2w, **AO_KW))
+            if SOFT and AO_KW:
+                soft["soft_shadow_ao_ms"] = median_ms(lambda: trace.render_surface(gen, z, b2w, **SOFT_KW, **AO_KW))
+            soft["stats"] = trace.render_surface(gen, z, b2w, **SOFT_KW, **AO_KW)["stats"]
+            soft["secondary"] = secondary(gen, z, b2w)
+            row["soft"] = soft
         if R <= args.no_volume_above:
             row["volume_ms"] = median_ms(lambda: inference.render_frames(gen, [z], [b2w], keys=("image", "normal_map", "shading_map")),
                                          iters=max(3, args.iters // 2))
@@ -98,4 +156,7 @@ with torch.no_grad():
         "surface_no_shadows_ms": median_ms(lambda: inference.surface_light_walk(gen, z, b2w, n_frames=n, shadows=False), iters=5),
         "relight_walk_ms": median_ms(lambda: inference.light_walk(gen, z, b2w, n_frames=n, keys=("image",)), iters=3),
         "stats": inference.surface_light_walk(gen, z, b2w, n_frames=n, shadows=True)["stats"]}
+    if SOFT or AO_KW:
+        out["light_walk"]["soft_ms"] = median_ms(lambda: inference.surface_light_walk(gen, z, b2w, n_frames=n, **SOFT_KW, **AO_KW), iters=5)
+        out["light_walk"]["soft_stats"] = inference.surface_light_walk(gen, z, b2w, n_frames=n, **SOFT_KW, **AO_KW)["stats"]
 print(json.dumps(out))

@@ -27,6 +27,7 @@
 #include "mlp_common.h"
 #include "f3_blob.h"
 #include "../../include/oi_mesh_band.h"
+#include "../../include/oi_trace_batch.h"
 
 namespace {
 
@@ -563,6 +564,26 @@ struct BandSrc {
     const Index i = index(pt, e, n_per_elem);
     if (i.bi < i.nbx && i.ix < (unsigned)nx && i.iy < (unsigned)ny && i.iz < (unsigned)nz)
       out[((size_t)i.ix * (unsigned)ny + i.iy) * (unsigned)nz + i.iz] = scale * sdf;
+  }
+};
+
+// oi_sdf_mlp_fwd_segments (include/oi_trace_batch.h): element e's points are the first n_per_elem of a segment of `stride`
+// points -- the point of local index loc is read from pts[(e * stride + loc) * 3 ..] and its sdf stored to out[e * stride + loc].
+// The batched sphere trace marches every element's compacted rays this way, in one launch per step.
+struct SegmentSrc {
+  const float* __restrict__ pts;
+  long long stride;
+  using Arg = SegmentSrc;
+  static constexpr bool ARRAY = false;
+  __device__ __forceinline__ long long at(long long pt, int e, long long n_per_elem) const {
+    return pt + (long long)e * (stride - n_per_elem);  // e * stride + (pt - e * n_per_elem)
+  }
+  __device__ __forceinline__ void load(long long pt, int e, long long n_per_elem, float& x, float& y, float& z) const {
+    const long long q = at(pt, e, n_per_elem);
+    x = pts[q * 3 + 0], y = pts[q * 3 + 1], z = pts[q * 3 + 2];
+  }
+  __device__ __forceinline__ void store(float* __restrict__ out, long long pt, int e, long long n_per_elem, float sdf) const {
+    out[at(pt, e, n_per_elem)] = sdf;
   }
 };
 
@@ -1134,6 +1155,23 @@ int oi_sdf_lattice_band(const void* packed, const float* gamma, const float* bet
   return dispatch_prec(prec, fast_trig, "oi_sdf_lattice_band", [&](auto P, auto F) {
     return launch_sdf<decltype(P)::value, decltype(F)::value, false, BandSrc>(src, packed, gamma, beta, field, nullptr, nullptr,
                                                                               nullptr, nullptr, 1, n, "oi_sdf_lattice_band", st);
+  });
+}
+
+// include/oi_trace_batch.h: the sdf-only pass of the batched sphere trace
+int oi_sdf_mlp_fwd_segments(const float* pts, const void* packed, const float* gamma, const float* beta, float* sdf, int B,
+                            long long n_per_elem, long long stride, int prec, int fast_trig, oi_stream_t stream) {
+  OI_REQUIRE(pts && packed && gamma && beta && sdf, "oi_sdf_mlp_fwd_segments: null pointer");
+  OI_REQUIRE(B > 0 && n_per_elem > 0 && n_per_elem <= stride, "oi_sdf_mlp_fwd_segments: B=%d n=%lld stride=%lld (B > 0, 0 < n <= stride)",
+             B, n_per_elem, stride);
+  OI_REQUIRE(stride < (1ll << 31) && (long long)B * stride < (1ll << 31),
+             "oi_sdf_mlp_fwd_segments: B=%d x stride=%lld points (B * stride < 2^31)", B, stride);
+  hipStream_t st = oi::as_stream(stream);
+  const SegmentSrc src{pts, stride};
+  return dispatch_prec(prec, fast_trig, "oi_sdf_mlp_fwd_segments", [&](auto P, auto F) {
+    return launch_sdf<decltype(P)::value, decltype(F)::value, false, SegmentSrc>(src, packed, gamma, beta, sdf, nullptr, nullptr,
+                                                                                 nullptr, nullptr, B, n_per_elem,
+                                                                                 "oi_sdf_mlp_fwd_segments", st);
   });
 }
 

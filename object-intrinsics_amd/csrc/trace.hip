@@ -7,50 +7,21 @@
 //   shadow_begin   one shadow ray per (light, hit) facing the light, offset along the normal, compacted like a step
 //   visibility     shadow-ray states -> the (L, N) visibility map
 //   shade          G-buffer (depth, position, normals, albedo, mask) and the Phong image under L lights
-// The step kernel, the compaction and the shading live in trace_common.h, which occlusion.hip shares.
+// The per-ray work of begin, step and finish, the compaction and the shading live in trace_common.h, which occlusion.hip and
+// trace_batch.hip share.
 // Compaction inside a workgroup: one 64-bit ballot per wave (popcount on the lower lanes) and an LDS scan over the waves,
 // as mesh.hip; across workgroups one integer atomicAdd per workgroup on the step's counter.  No float atomics, no scratch.
 #include "trace_common.h"
 
 namespace {
 
-__global__ void __launch_bounds__(TR_THREADS) trace_begin_kernel(const oi_trace_state s) {
-  clear_counts(s.counts, (int)s.N);
-  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  if (r >= s.N) return;
-  const float t = s.near_[r];
-  s.t[r] = t;
-  s.status[r] = OI_TRACE_MARCH;
-  s.steps[r] = 0;
-  s.side[r] = 0;
-  s.bracket[r * 4 + 0] = t;
-  s.bracket[r * 4 + 1] = 0.f;
-  s.bracket[r * 4 + 2] = t;
-  s.bracket[r * 4 + 3] = 0.f;
-  s.active[r] = (int)r;
-  point_at(s.rays_o, s.rays_d, r, t, s.points + r * 3);
-}
+__global__ void __launch_bounds__(TR_THREADS) trace_begin_kernel(const oi_trace_state s) { trace_begin_rays(s); }
 
 __global__ void __launch_bounds__(TR_THREADS) trace_finish_kernel(const oi_trace_state s, int* __restrict__ hit_index,
                                                                   float* __restrict__ hit_points,
                                                                   int* __restrict__ hit_slot) {
   __shared__ unsigned lds[TR_WAVES + 1];
-  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  bool hit = false;
-  if (r < s.N) {
-    unsigned st = s.status[r];
-    if (st >= OI_TRACE_MARCH) {
-      st = OI_TRACE_LIMIT;
-      s.status[r] = (uint8_t)st;
-    }
-    hit = st == OI_TRACE_HIT;
-  }
-  const long long slot = wg_slot(hit, s.counts + N_HIT_WORD, lds);
-  if (r < s.N) hit_slot[r] = hit ? (int)slot : -1;
-  if (hit) {
-    hit_index[slot] = (int)r;
-    point_at(s.rays_o, s.rays_d, r, s.t[r], hit_points + slot * 3);
-  }
+  trace_finish_rays<true>(s, hit_index, hit_points, hit_slot, lds);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) trace_shadow_begin_kernel(const oi_trace_state s,

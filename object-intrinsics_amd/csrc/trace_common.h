@@ -35,7 +35,10 @@ __device__ __forceinline__ void point_at(const float* __restrict__ o, const floa
 
 // Dense output slot of this thread (meaningful where `keep`), the workgroup's kept threads in thread order behind
 // `*counter`'s previous value.  Every thread of the workgroup calls it.  lds: TR_WAVES + 1 words.
-__device__ __forceinline__ long long wg_slot(bool keep, int* counter, unsigned* lds) {
+// live (the batched trace, include/oi_trace_batch.h): a word that follows the maximum of several counters.  The counter's
+// value after this workgroup's add goes into it with one integer atomicMax; the workgroup that adds last holds the final
+// count, so when the launch has ended the word is the largest of the final counts.
+__device__ __forceinline__ long long wg_slot(bool keep, int* counter, unsigned* lds, int* live = nullptr) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned long long m = __ballot(keep);
   const unsigned pre = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
@@ -49,6 +52,7 @@ __device__ __forceinline__ long long wg_slot(bool keep, int* counter, unsigned* 
       tot += c;
     }
     lds[TR_WAVES] = tot ? (unsigned)atomicAdd(counter, (int)tot) : 0u;
+    if (live != nullptr && tot) atomicMax(live, (int)(lds[TR_WAVES] + tot));
   }
   __syncthreads();
   return (long long)lds[TR_WAVES] + lds[wave] + pre;
@@ -64,10 +68,11 @@ __global__ void __launch_bounds__(TR_THREADS) trace_clear_counts_kernel(int* cou
 // One step of the ray state machine on the sdf of the last MLP pass, and the compaction of the rays still in flight.
 // ANYHIT = false: oi_trace_step (march, bracket, Illinois regula falsi).  ANYHIT = true: oi_occlusion_step, whose MARCH
 // phase is the same and whose first later negative sample ends the ray as a HIT at that sample: there is no REFINE state.
+// s: the state of the rays this workgroup serves (a whole trace, or one element's view of a batched one: element_view);
+// live: wg_slot's, nullptr for a single trace.  Every thread of the workgroup calls it.
 template <bool ANYHIT>
-__global__ void __launch_bounds__(TR_THREADS) trace_step_kernel(const oi_trace_state s, const float* __restrict__ sdf,
-                                                                long long bound, int k, float tol, float omega) {
-  __shared__ unsigned lds[TR_WAVES + 1];
+__device__ __forceinline__ void trace_step_rays(const oi_trace_state& s, const float* __restrict__ sdf, long long bound, int k,
+                                                float tol, float omega, unsigned* lds, int* live = nullptr) {
   long long cnt = s.counts[k];
   cnt = cnt < bound ? cnt : bound;
   const long long j0 = (long long)blockIdx.x * TR_THREADS;
@@ -142,10 +147,59 @@ __global__ void __launch_bounds__(TR_THREADS) trace_step_kernel(const oi_trace_s
     s.status[r] = (uint8_t)st;
     tn = t;
   }
-  const long long slot = wg_slot(alive, s.counts + k + 1, lds);
+  const long long slot = wg_slot(alive, s.counts + k + 1, lds, live);
   if (alive) {
     act_out[slot] = (int)r;
     point_at(s.rays_o, s.rays_d, r, tn, s.points + slot * 3);
+  }
+}
+
+template <bool ANYHIT>
+__global__ void __launch_bounds__(TR_THREADS) trace_step_kernel(const oi_trace_state s, const float* __restrict__ sdf,
+                                                                long long bound, int k, float tol, float omega) {
+  __shared__ unsigned lds[TR_WAVES + 1];
+  trace_step_rays<ANYHIT>(s, sdf, bound, k, tol, omega, lds);
+}
+
+// oi_trace_begin's work for ray blockIdx.x * TR_THREADS + threadIdx.x of s, and the counters of s.
+__device__ __forceinline__ void trace_begin_rays(const oi_trace_state& s) {
+  clear_counts(s.counts, (int)s.N);
+  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (r >= s.N) return;
+  const float t = s.near_[r];
+  s.t[r] = t;
+  s.status[r] = OI_TRACE_MARCH;
+  s.steps[r] = 0;
+  s.side[r] = 0;
+  s.bracket[r * 4 + 0] = t;
+  s.bracket[r * 4 + 1] = 0.f;
+  s.bracket[r * 4 + 2] = t;
+  s.bracket[r * 4 + 3] = 0.f;
+  s.active[r] = (int)r;
+  point_at(s.rays_o, s.rays_d, r, t, s.points + r * 3);
+}
+
+// oi_trace_finish's work: rays in flight -> LIMIT, the hits listed densely (hit_index, hit_slot; POINTS: hit_points too).
+// Every thread of the workgroup calls it; live: wg_slot's.
+template <bool POINTS>
+__device__ __forceinline__ void trace_finish_rays(const oi_trace_state& s, int* __restrict__ hit_index,
+                                                  float* __restrict__ hit_points, int* __restrict__ hit_slot, unsigned* lds,
+                                                  int* live = nullptr) {
+  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  bool hit = false;
+  if (r < s.N) {
+    unsigned st = s.status[r];
+    if (st >= OI_TRACE_MARCH) {
+      st = OI_TRACE_LIMIT;
+      s.status[r] = (uint8_t)st;
+    }
+    hit = st == OI_TRACE_HIT;
+  }
+  const long long slot = wg_slot(hit, s.counts + N_HIT_WORD, lds, live);
+  if (r < s.N) hit_slot[r] = hit ? (int)slot : -1;
+  if (hit) {
+    hit_index[slot] = (int)r;
+    if (POINTS) point_at(s.rays_o, s.rays_d, r, s.t[r], hit_points + slot * 3);
   }
 }
 

@@ -152,13 +152,20 @@ OCCLUSION_MAX_RAYS = min((2 << 30) // TRACE_BYTES_PER_RAY, (1 << 31) - 1)
 
 
 @torch.no_grad()
-def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"), lights=None, shadows=False, bg=None, **kw):
+def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"), lights=None, shadows=False, bg=None, batch=1,
+                   **kw):
     """render_frames by ray / surface intersection (oi_amd.trace.render_surface) instead of the volume render: one frame per
     (z, b2w) pair under ONE light (`lights`: a Light, default the trained one).  -> {key: (n, C, H, W)} for keys of
     SURFACE_KEYS ("visibility" needs shadows=True, "ambient_occlusion" ao_samples > 0).  Keyword arguments: render_surface's
-    (bias, tol, omega, max_steps; shadow_samples, light_radius, ao_samples, ao_distance, seed)."""
-    from . import trace
+    (bias, tol, omega, max_steps; shadow_samples, light_radius, ao_samples, ao_distance, seed).
+    batch: frames per primary trace, 1 .. 1024.  1: one render_surface per frame.  E > 1: the frames go through
+    oi_amd.trace.render_surfaces in groups of E (the last group may be smaller) -- one chain of trace steps and one full MLP
+    pass per group instead of per frame; shadow and occlusion rays are still traced per frame.  The
+    frames are those of batch=1."""
+    from . import lib, trace
     from .relight import Light
+    if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= int(batch) <= lib.TRACE_BATCH_MAX_ELEMS:
+        raise ValueError(f"surface_frames: batch={batch!r} (an integer, 1 <= batch <= {lib.TRACE_BATCH_MAX_ELEMS})")
     unknown = [k for k in keys if k not in SURFACE_KEYS]
     if unknown or ("visibility" in keys and not shadows):
         raise ValueError(f"surface_frames: keys {unknown or ['visibility']} (one of {SURFACE_KEYS}; visibility with shadows=True)")
@@ -169,6 +176,15 @@ def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"),
     gen.eval()
     gen.renderer.pack.check()
     frames = {k: [] for k in keys}
+    if batch > 1:
+        pairs = list(zip(zs, b2ws))
+        for a in range(0, len(pairs), int(batch)):
+            group = pairs[a:a + int(batch)]
+            for out in trace.render_surfaces(gen, [z for z, _ in group], [b for _, b in group], lights=lights, shadows=shadows,
+                                             bg=bg, **kw):
+                for k in keys:
+                    frames[k].append(out[k][0])
+        return {k: torch.stack(v) for k, v in frames.items()}
     for z, b2w in zip(zs, b2ws):
         out = trace.render_surface(gen, z, b2w, lights=lights, shadows=shadows, bg=bg, **kw)
         for k in keys:

@@ -1,5 +1,5 @@
 """ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h, include/oi_mesh_attr.h,
-include/oi_trace.h, include/oi_occlusion.h and include/oi_mesh_band.h).
+include/oi_trace.h, include/oi_occlusion.h, include/oi_mesh_band.h and include/oi_trace_batch.h).
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -243,6 +243,23 @@ _MESH_BAND_SIGS = {
     "oi_sdf_lattice_band": (_i, [_vp] * 3 + [_i] + [_vp] * 3 + [_i] * 4 + [_vp, _ll, _f, _vp, _i, _i, _vp]),
 }
 
+# include/oi_trace_batch.h: E latents / views in one chain of trace steps (an addition to oi_trace.h)
+TRACE_BATCH_MAX_ELEMS = 1024
+
+
+class TraceBatch(ctypes.Structure):
+    """Mirror of `oi_trace_batch` (include/oi_trace_batch.h)."""
+    _fields_ = [("s", TraceState), ("E", _i), ("live", _vp)]
+
+
+_TRACE_BATCH_SIGS = {
+    "oi_sdf_mlp_fwd_segments": (_i, [_vp] * 5 + [_i, _ll, _ll, _i, _i, _vp]),
+    "oi_trace_batch_begin": (_i, [ctypes.POINTER(TraceBatch), _vp]),
+    "oi_trace_batch_step": (_i, [ctypes.POINTER(TraceBatch), _vp, _ll, _i, _f, _f, _vp]),
+    "oi_trace_batch_finish": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _vp]),
+    "oi_trace_batch_gather": (_i, [ctypes.POINTER(TraceBatch), _vp, _ll, _vp, _vp]),
+}
+
 # entry points added by later source files (backward kernels); bound when present in the .so
 _OPTIONAL_SIGS = {}
 
@@ -280,6 +297,11 @@ def mesh_band_symbols():
     return sorted(_MESH_BAND_SIGS)
 
 
+def trace_batch_symbols():
+    """The entry points of include/oi_trace_batch.h."""
+    return sorted(_TRACE_BATCH_SIGS)
+
+
 def load():
     """Load (once) and return the ctypes handle.  Raises OiHipError when the library is missing."""
     global _lib
@@ -299,7 +321,7 @@ def load():
                 "oi_amd has no CPU or PyTorch fallback for its kernels.")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_TRACE_SIGS, **_OCCLUSION_SIGS, **_MESH_BAND_SIGS,
-                                   **_OPTIONAL_SIGS}.items():
+                                   **_TRACE_BATCH_SIGS, **_OPTIONAL_SIGS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError:

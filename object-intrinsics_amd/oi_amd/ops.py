@@ -707,6 +707,74 @@ def surface_shade(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_
 
 
 # ------------------------------------------------------------------------------------------
+# batched sphere tracing (include/oi_trace_batch.h); oi_amd.trace.sphere_trace_batch sequences these
+# ------------------------------------------------------------------------------------------
+
+def sdf_mlp_fwd_segments(pts, packed, gamma, beta, sdf, B, n_per_elem, prec, fast_trig=False):
+    """The sdf-only pass on the first n_per_elem points of each of B segments: pts (B, stride, 3) -> sdf (B, stride), the
+    caller's, of which [:, :n_per_elem] is written and the rest left as it is."""
+    if pts.dim() != 3 or pts.shape[0] != B or pts.shape[2] != 3 or tuple(sdf.shape) != tuple(pts.shape[:2]):
+        raise ValueError(f"sdf_mlp_fwd_segments: pts {tuple(pts.shape)}, sdf {tuple(sdf.shape)}, expected ({B}, stride, 3) and ({B}, stride)")
+    _l.check(_l.load().oi_sdf_mlp_fwd_segments(_p(pts), _p(packed), _p(gamma), _p(beta), _p(sdf), int(B), int(n_per_elem),
+                                               pts.shape[1], prec, int(bool(fast_trig)), _stream()), "oi_sdf_mlp_fwd_segments")
+    return sdf
+
+
+class TraceBatchState:
+    """The arrays of one oi_trace_batch: E elements of N rays each, every array of TraceState with a leading element
+    dimension, counts (E, TRACE_COUNT_WORDS) and live (TRACE_COUNT_WORDS,) int32.  rays_o / rays_d (E, N, 3), near / far
+    (E, N) are the caller's.  t (E, N) is an output (ops._new), status and steps are outputs too; the rest is working memory."""
+
+    def __init__(self, E, N, rays_o, rays_d, near, far):
+        dev = rays_o.device
+        e = lambda *sh, dt=torch.float32: torch.empty(sh, dtype=dt, device=dev)
+        self.E, self.N = int(E), int(N)
+        self.rays_o, self.rays_d = _c(rays_o).reshape(E, N, 3), _c(rays_d).reshape(E, N, 3)
+        self.near, self.far = _c(near).reshape(E, N), _c(far).reshape(E, N)
+        self.t = _new(rays_o, E, N)
+        self.status = e(E, N, dt=torch.uint8)
+        self.steps = e(E, N, dt=torch.int16)
+        self.bracket, self.side = e(E, N, 4), e(E, N, dt=torch.uint8)
+        self.active, self.points = e(E, 2, N, dt=torch.int32), e(E, N, 3)
+        self.counts = e(E, _l.TRACE_COUNT_WORDS, dt=torch.int32)
+        self.live = e(_l.TRACE_COUNT_WORDS, dt=torch.int32)
+        B = self.c = _l.TraceBatch()
+        S = B.s
+        S.N = self.N
+        S.rays_o, S.rays_d, S.near_, S.far_ = _p(self.rays_o), _p(self.rays_d), _p(self.near), _p(self.far)
+        S.t, S.status, S.steps, S.bracket, S.side = _p(self.t), _p(self.status), _ip(self.steps), _p(self.bracket), _p(self.side)
+        S.active, S.points, S.counts = _ip(self.active), _p(self.points), _ip(self.counts)
+        B.E, B.live = self.E, _ip(self.live)
+
+
+def trace_batch_begin(st):
+    _l.check(_l.load().oi_trace_batch_begin(ctypes.byref(st.c), _stream()), "oi_trace_batch_begin")
+
+
+def trace_batch_step(st, sdf, bound, k, tol, omega):
+    _l.check(_l.load().oi_trace_batch_step(ctypes.byref(st.c), _p(sdf), int(bound), int(k), float(tol), float(omega), _stream()),
+             "oi_trace_batch_step")
+
+
+def trace_batch_finish(st):
+    """-> hit_index (E, N) int32 (the first n_hit_e entries of row e are written), hit_slot (E, N) int32."""
+    dev = st.t.device
+    hit_index = torch.empty(st.E, st.N, dtype=torch.int32, device=dev)
+    hit_slot = torch.empty(st.E, st.N, dtype=torch.int32, device=dev)
+    _l.check(_l.load().oi_trace_batch_finish(ctypes.byref(st.c), _ip(hit_index), _ip(hit_slot), _stream()), "oi_trace_batch_finish")
+    return hit_index, hit_slot
+
+
+def trace_batch_gather(st, hit_index, n_pad):
+    """-> hit_points_padded (E, n_pad, 3): row e holds its n_hit_e hit points, then the coordinate origin."""
+    out = _new(st.t, st.E, int(n_pad), 3)
+    if n_pad:
+        _l.check(_l.load().oi_trace_batch_gather(ctypes.byref(st.c), _ip(hit_index), int(n_pad), _p(out), _stream()),
+                 "oi_trace_batch_gather")
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # soft shadows and ambient occlusion on the traced surface (include/oi_occlusion.h)
 # ------------------------------------------------------------------------------------------
 

@@ -2,6 +2,10 @@
 (include/oi_trace.h).
 
     sphere_trace     rays against the learned SDF -> per-ray t, status, evaluations, the dense list of hits
+    sphere_trace_batch  the same for E latents with N rays each in ONE chain of steps (include/oi_trace_batch.h; DESIGN
+                     section 4.17)
+    render_surfaces  E views of a Generator (a latent and a pose each): one batched primary trace and one full MLP pass for
+                     all of them, then render_surface's light-dependent stages per view
     render_surface   one view of a Generator: depth, position, normals, albedo, mask, the Phong image under L lights,
                      optionally with cast shadows (one shadow ray per light and visible point, or `shadow_samples` rays
                      towards a light of angular radius `light_radius`: penumbrae) and ambient occlusion (`ao_samples` rays
@@ -129,6 +133,96 @@ def sphere_trace(pack_or_generator, rays_o, rays_d, near=None, far=None, z=None,
     return _finish(st, n_evals, k)
 
 
+class TraceResults(list):
+    """E TraceResults, views of the batched arrays of one sphere_trace_batch.  n_evals: points sent through the sdf-only MLP
+    pass by the whole batch, E * sum_k bound_k (each element carries its share, sum_k bound_k); n_steps: loop iterations run;
+    n_pad: the largest hit count; hit_points_padded (E, n_pad, 3): row e holds hit_points of element e, then the coordinate
+    origin; n_hit: the hit counts; counts (E, TRACE_COUNT_WORDS) / live (TRACE_COUNT_WORDS,) int32: the device's counters
+    (counts[e][k]: rays of element e in flight before step k; live[k] their maximum)."""
+    n_evals = n_steps = n_pad = 0
+    hit_points_padded = counts = live = None
+    n_hit = ()
+
+
+def _march_batch(field, st, tol, omega, max_steps, readback):
+    """_march on a state that oi_trace_batch_begin has filled: the bound is live[k] = the largest count of any element, read
+    by the same rule.  -> (sum of the bounds, steps run)."""
+    import ctypes
+    L = _l.load()
+    sdf = torch.empty(st.E, st.N, dtype=torch.float32, device=st.t.device)   # working memory: step k's pass writes sdf[:, :bound]
+    pts_p, sdf_p, state_p, stream = ops._p(st.points), ops._p(sdf), ctypes.byref(st.c), ops._stream()
+    packed_p, gamma_p, beta_p = ops._p(field.packed), ops._p(field.gamma), ops._p(field.beta)
+    prec, trig, E, N = field.prec, field.fast, st.E, st.N
+    bound, total, k, since = N, 0, 0, 0
+    while k < max_steps and bound > 0:
+        rc = L.oi_sdf_mlp_fwd_segments(pts_p, packed_p, gamma_p, beta_p, sdf_p, E, bound, N, prec, trig, stream)
+        if rc:
+            _l.check(rc, "oi_sdf_mlp_fwd_segments")
+        rc = L.oi_trace_batch_step(state_p, sdf_p, bound, k, tol, omega, stream)
+        if rc:
+            _l.check(rc, "oi_trace_batch_step")
+        total += bound
+        k += 1
+        since += 1
+        every = (1 if bound > READBACK_DENSE else READBACK_SPARSE) if readback == "auto" else int(readback)
+        if since >= every and k < max_steps:
+            bound, since = int(st.live[k].item()), 0
+    return total, k
+
+
+@torch.no_grad()
+def sphere_trace_batch(pack_or_generator, rays_o, rays_d, near=None, far=None, z=None, w=None, tol=DEFAULT_TOL,
+                       omega=DEFAULT_OMEGA, max_steps=DEFAULT_MAX_STEPS, readback="auto"):
+    """sphere_trace for E latents at once: rays (E, N, 3) + (E, N, 3) (CUDA), z or w (E, 64), near / far (E, N) (default: as
+    sphere_trace).  ONE chain of steps marches all E * N rays: per step one sdf-only MLP pass over the first live[k] compacted
+    points of every element and one oi_trace_batch_step, where live[k] is the largest number of rays any element still has
+    in flight; the host reads that one word by sphere_trace's rule (every step while live[k] > READBACK_DENSE).  Per ray
+    the result is sphere_trace's on that element alone, bit for bit.  -> TraceResults: E TraceResult objects that are views of
+    the batched arrays, and the batch's n_evals = E * sum_k bound_k.  E * N == 0 launches nothing."""
+    _check_params(tol, omega, max_steps, readback, "sphere_trace_batch")
+    field = LatentField(pack_or_generator, z, w, "sphere_trace_batch", batch_ok=True)
+    if (not torch.is_tensor(rays_o) or not torch.is_tensor(rays_d) or rays_o.shape != rays_d.shape or rays_o.dim() != 3
+            or rays_o.shape[-1] != 3):
+        raise ValueError("sphere_trace_batch: rays_o and rays_d must be tensors of the same (E, N, 3) shape")
+    lat = w if w is not None else z
+    E, N, dev = rays_o.shape[0], rays_o.shape[1], rays_o.device
+    if lat.dim() != 2 or lat.shape[0] != E:
+        raise ValueError(f"sphere_trace_batch: latents {tuple(lat.shape)} for {E} elements (one row per element)")
+    if E > _l.TRACE_BATCH_MAX_ELEMS or E * N >= 1 << 31:
+        raise ValueError(f"sphere_trace_batch: {E} elements x {N} rays (at most {_l.TRACE_BATCH_MAX_ELEMS} elements, E * N < 2^31)")
+    if not rays_o.is_cuda:
+        raise _l.OiHipError("sphere_trace_batch: the rays must be on the GPU (there is no CPU path)")
+    out = TraceResults()
+    if E * N == 0:   # nothing is launched
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
+        out.extend(TraceResult(e(N), e(N, dt=torch.uint8), e(N, dt=torch.int16), e(0, dt=torch.int32), 0, 0, e(0, 3),
+                               e(N, dt=torch.int32)) for _ in range(E))
+        out.hit_points_padded, out.n_hit = e(E, 0, 3), (0,) * E
+        return out
+    ro, rd = rays_o.detach().float().contiguous(), rays_d.detach().float().contiguous()
+    if near is None or far is None:
+        mid = -(ro * rd).sum(-1) / (rd * rd).sum(-1)   # generator.py:336-342
+        near = mid - 1.0 if near is None else near
+        far = mid + 1.0 if far is None else far
+    near, far = (torch.as_tensor(v, dtype=torch.float32, device=dev).expand(E, N) for v in (near, far))
+    field.prepare(z, w)
+    return _trace_batch(field, ops.TraceBatchState(E, N, ro, rd, near, far), float(tol), float(omega), int(max_steps), readback)
+
+
+def _trace_batch(field, st, tol, omega, max_steps, readback):
+    ops.trace_batch_begin(st)
+    total, k = _march_batch(field, st, tol, omega, max_steps, readback)
+    hit_index, hit_slot = ops.trace_batch_finish(st)
+    n_pad = int(st.live[-1].item())                        # the one word the host waits for
+    padded = ops.trace_batch_gather(st, hit_index, n_pad)
+    n_hit = st.counts[:, -1].tolist()                      # slicing the views below needs every element's count
+    out = TraceResults(TraceResult(st.t[e], st.status[e], st.steps[e], hit_index[e, :n_hit[e]], total, k, padded[e, :n_hit[e]],
+                                   hit_slot[e]) for e in range(st.E))
+    out.n_evals, out.n_steps, out.n_pad, out.hit_points_padded, out.n_hit = st.E * total, k, n_pad, padded, tuple(n_hit)
+    out.counts, out.live = st.counts, st.live
+    return out
+
+
 def _view_rays(gen, b2w):
     """The rays of Generator.forward for one pose (4, 4): its own oi_gen_rays path.  -> rays_o, rays_d (N, 3), near, far (N,),
     w2b (4, 4)."""
@@ -142,17 +236,21 @@ def _view_rays(gen, b2w):
 class _Surface:
     """One traced view and everything the light-dependent stages reuse: the primary trace, the full MLP pass at its hits."""
 
-    def __init__(self, gen, z, b2w, bias, trace_kw, w=None):
+    @staticmethod
+    def params(bias, trace_kw, what="render_surface"):
+        """The checked trace parameters (tol, omega, max_steps, readback) and the bias."""
         tol, omega = trace_kw.get("tol", DEFAULT_TOL), trace_kw.get("omega", DEFAULT_OMEGA)
         max_steps, readback = trace_kw.get("max_steps", DEFAULT_MAX_STEPS), trace_kw.get("readback", "auto")
         unknown = set(trace_kw) - {"tol", "omega", "max_steps", "readback"}
         if unknown:
-            raise TypeError(f"render_surface: unknown arguments {sorted(unknown)}")
-        _check_params(tol, omega, max_steps, readback, "render_surface")
+            raise TypeError(f"{what}: unknown arguments {sorted(unknown)}")
+        _check_params(tol, omega, max_steps, readback, what)
         if not (float(bias) >= 0 and np.isfinite(float(bias))):
-            raise ValueError(f"render_surface: bias={bias!r} (>= 0 and finite)")
-        self.kw = (float(tol), float(omega), int(max_steps), readback)
-        self.bias = float(bias)
+            raise ValueError(f"{what}: bias={bias!r} (>= 0 and finite)")
+        return (float(tol), float(omega), int(max_steps), readback), float(bias)
+
+    def __init__(self, gen, z, b2w, bias, trace_kw, w=None):
+        self.kw, self.bias = self.params(bias, trace_kw)
         self.field = LatentField(gen, z, w, "render_surface")
         gen.eval()
         dev = gen.it.device
@@ -169,6 +267,17 @@ class _Surface:
             _, self.grad, self.rgb = self.field.full(self.res.hit_points)
         self.shadow_evals = self.ao_evals = 0
         self.shadow = self.ao = None
+
+    @classmethod
+    def from_batch(cls, field, kw, bias, ro, rd, w2b, H, res, grad, rgb):
+        """One element of render_surfaces: slices of the batched arrays, its own w2b and FiLM rows (field: B = 1)."""
+        self = cls.__new__(cls)
+        self.kw, self.bias, self.field = kw, bias, field
+        self.ro, self.rd, self.w2b, self.N, self.H = ro, rd, w2b, ro.shape[0], H
+        self.res, self.n_hit, self.grad, self.rgb = res, res.hit_index.shape[0], grad, rgb
+        self.shadow_evals = self.ao_evals = 0
+        self.shadow = self.ao = None
+        return self
 
     def _secondary(self, st):
         """The any-hit loop on a state an oi_occlusion_*_begin has filled; rays in flight at the end -> LIMIT."""
@@ -290,6 +399,11 @@ def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAUL
         raise ValueError(f"render_surface: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS}; inference.surface_light_walk "
                          "splits larger sets)")
     radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surface")
+    return _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev)
+
+
+def _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev):
+    """The light-dependent stages of one traced view (a _Surface) and render_surface's dict."""
     if radii is None:
         vis = s.visibility(lt) if shadows else None
     else:
@@ -309,3 +423,49 @@ def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAUL
     res["stats"] = s.stats()
     res["trace"] = s.res
     return res
+
+
+@torch.no_grad()
+def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEFAULT_BIAS, shadow_samples=1, light_radius=0.0,
+                    ao_samples=0, ao_distance=0.5, seed=0, **trace_kw):
+    """render_surface for E views at once (latents zs: E of (z_dim,) or (E, z_dim); poses b2ws: E of (4, 4)), 1 <= E <= 1024:
+    ONE batched primary trace (sphere_trace_batch's chain of steps for all E * H * W rays) and ONE full MLP pass at the hits
+    of all views, padded per view to the largest hit count.  Each view then is what render_surface holds -- slices of the
+    batched arrays, its own w2b and FiLM rows -- and the light-dependent stages run per view, unchanged: the shading, and with
+    `shadows` / `ao_samples` the single-latent shadow and occlusion traces.  Batching those secondary rays is out of scope.
+    The other arguments are render_surface's, the same for every view.  -> a list of E dicts as render_surface returns
+    them; per view the maps are render_surface's own, bit for bit."""
+    import copy
+    from .relight import Light, stack_lights
+    dev = gen.it.device
+    kw, bias = _Surface.params(bias, trace_kw, "render_surfaces")
+    zs = (zs if torch.is_tensor(zs) else torch.stack([z.reshape(-1) for z in zs])).to(dev).float()
+    zs = zs.reshape(-1, zs.shape[-1])
+    E = zs.shape[0]
+    if len(b2ws) != E or not 1 <= E <= _l.TRACE_BATCH_MAX_ELEMS:
+        raise ValueError(f"render_surfaces: {E} latents and {len(b2ws)} poses (one pose per latent, 1 .. {_l.TRACE_BATCH_MAX_ELEMS} views)")
+    lt = stack_lights(Light.from_module(gen.light) if lights is None else lights, dev)
+    if lt.shape[0] > _l.RELIGHT_MAX_LIGHTS:
+        raise ValueError(f"render_surfaces: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS})")
+    radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surfaces")
+    field = LatentField(gen, zs, None, "render_surfaces", batch_ok=True)
+    gen.eval()
+    field.prepare(zs, None)
+    views = [_view_rays(gen, b2w) for b2w in b2ws]
+    ro, rd, near, far = (torch.stack([v[i] for v in views]) for i in range(4))
+    N = ro.shape[1]
+    st = ops.TraceBatchState(E, N, ro, rd, near, far)
+    res = _trace_batch(field, st, *kw)
+    grad = rgb = None
+    if res.n_pad:   # the full pass: the library's own, B = E elements of n_pad points
+        _, grad, rgb = field.full(res.hit_points_padded.view(E * res.n_pad, 3))
+        grad, rgb = grad.view(E, res.n_pad, 3), rgb.view(E, res.n_pad, 3)
+    out = []
+    for e in range(E):
+        one = copy.copy(field)   # the element's own FiLM rows: the field of one latent
+        one.B, one.gamma, one.beta = 1, field.gamma[e:e + 1], field.beta[e:e + 1]
+        n = res.n_hit[e]
+        s = _Surface.from_batch(one, kw, bias, st.rays_o[e], st.rays_d[e], views[e][4], gen.resolution, res[e],
+                                grad[e, :n] if n else None, rgb[e, :n] if n else None)
+        out.append(_lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev))
+    return out

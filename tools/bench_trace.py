@@ -16,7 +16,15 @@ With --shadow-samples S > 1 / --light-radius r > 0 / --ao-samples A > 0 (DESIGN 
   soft                  ms per frame of soft shadows alone, ambient occlusion alone and both together, the secondary rays
                         and their LIMIT share, and the sdf evaluations per traced secondary ray through the any-hit step
                         against the full step on the same rays (count read every step)
-and the light walk a row with the soft settings."""
+and the light walk a row with the soft settings.
+
+With --batch E[,E...] the tool measures ONLY the batched walk: --walk-frames frames at --walk-res, a
+latent walk between two seeded latents under as many sampled poses, through inference.surface_frames(batch=E) against the
+same call's unchanged per-frame loop (batch=1) in the same session, without and with cast shadows:
+
+  loop_ms / batch_ms    ms per frame;   speedup  their ratio
+  evals_per_ray         sdf evaluations per primary ray (the stale and the shared bounds included)
+  n_pad_over_mean_hit   points per element of the padded full pass over the mean hit count;  padding_waste  its unread share"""
 import argparse
 import json
 import os
@@ -42,6 +50,7 @@ ap.add_argument("--no-volume-above", type=int, default=128, help="skip the volum
 ap.add_argument("--shadow-samples", type=int, default=1, help="shadow rays per light and visible point")
 ap.add_argument("--light-radius", type=float, default=0.0, help="angular radius of the light, radians")
 ap.add_argument("--ao-samples", type=int, default=0, help="ambient-occlusion rays per visible point (0: none)")
+ap.add_argument("--batch", default="", help="frames per batched primary trace, e.g. 16,128: measure only the batched walk")
 args = ap.parse_args()
 
 
@@ -105,6 +114,44 @@ def secondary(gen, z, b2w):
         rows[name] = row
     return rows
 
+
+def batched_walk():
+    gen, _, _ = setup(args.walk_res)
+    n, N = args.walk_frames, args.walk_res ** 2
+    g = torch.Generator().manual_seed(0)
+    z0, z1 = torch.randn(64, generator=g), torch.randn(64, generator=g)
+    zs = [torch.lerp(z0, z1, i / max(1, n - 1)) for i in range(n)]
+    np.random.seed(0)
+    b2ws = list(torch.tensor(gen.pose_prior(n), dtype=torch.float32))
+    keys = ("image", "mask", "normal_map", "depth")
+    frames = lambda E, sh: inference.surface_frames(gen, zs, b2ws, keys=keys, shadows=sh, batch=E)
+    row = {"res": args.walk_res, "frames": n, "batch": {}}
+    loop = {sh: median_ms(lambda: frames(1, sh), iters=5) / n for sh in (False, True)}
+    row["loop_ms"], row["loop_shadow_ms"] = loop[False], loop[True]
+    row["loop_evals_per_ray"] = float(np.mean([trace.render_surface(gen, z, b)["stats"]["n_evals"] for z, b in zip(zs, b2ws)])) / N
+    ref = frames(1, False)
+    for E in (int(e) for e in args.batch.split(",")):
+        r = {sh: median_ms(lambda: frames(E, sh), iters=5) / n for sh in (False, True)}
+        got = frames(E, False)
+        same = all(bool(((got[k] == ref[k]) | (got[k].isnan() & ref[k].isnan())).all()) for k in keys)
+        evals, pad, hits = 0, 0, 0
+        for a in range(0, n, E):
+            res = trace.render_surfaces(gen, zs[a:a + E], b2ws[a:a + E])
+            t0 = res[0]["trace"]
+            evals += t0.n_evals * len(res)                       # every element of a group carries the group's bounds
+            pad += len(res) * max(len(o["trace"].hit_index) for o in res)
+            hits += sum(len(o["trace"].hit_index) for o in res)
+        row["batch"][str(E)] = {"batch_ms": r[False], "batch_shadow_ms": r[True], "speedup": loop[False] / r[False],
+                                "speedup_shadow": loop[True] / r[True], "evals_per_ray": evals / (n * N),
+                                "n_pad_over_mean_hit": pad / max(1, hits), "padding_waste": 1.0 - hits / max(1, pad),
+                                "frames_equal_loop": same}
+    return row
+
+
+if args.batch:
+    with torch.no_grad():
+        print(json.dumps({"tool": "bench_trace", "precision": args.precision, "warmup": args.warmup, "batched_walk": batched_walk()}))
+    sys.exit(0)
 
 out = {"tool": "bench_trace", "precision": args.precision, "iters": args.iters, "warmup": args.warmup, "res": {}}
 with torch.no_grad():

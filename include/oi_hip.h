@@ -686,7 +686,9 @@ int oi_reflect_pad_bwd(const float* gy, float* gx, int BC, int H, int W, int px0
  *   Adam:    m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g^2; p -= lr/bc1 * m / (sqrt(v)/bc2_sqrt + eps)
  *   RMSprop: s = alpha s + (1-alpha) g^2; p -= lr * g / (sqrt(s) + eps)
  *   EMA:     p = lerp(g, p, beta)
- * bias_correction1 = 1 - b1^step, bias_correction2_sqrt = sqrt(1 - b2^step) are computed by the caller. */
+ * bias_correction1 = 1 - b1^step, bias_correction2_sqrt = sqrt(1 - b2^step) are computed by the caller, and so are the
+ * complements one_minus_beta1 / one_minus_beta2 / one_minus_alpha: (float)(1.0 - beta) from the caller's double, rounded once
+ * as torch rounds them.  (1.0f - (float)beta differs from that by up to 1.3e-5 relative at beta = 0.999.) */
 typedef struct oi_mt_chunk {
   float* p;
   const float* g;
@@ -696,9 +698,10 @@ typedef struct oi_mt_chunk {
   int reserved;
 } oi_mt_chunk;
 int oi_mt_chunk_elems(void);
-int oi_multi_adam(const oi_mt_chunk* table, int n_chunks, float lr, float beta1, float beta2, float eps,
-                  float bias_correction1, float bias_correction2_sqrt, oi_stream_t stream);
-int oi_multi_rmsprop(const oi_mt_chunk* table, int n_chunks, float lr, float alpha, float eps, oi_stream_t stream);
+int oi_multi_adam(const oi_mt_chunk* table, int n_chunks, float lr, float beta1, float beta2, float one_minus_beta1,
+                  float one_minus_beta2, float eps, float bias_correction1, float bias_correction2_sqrt, oi_stream_t stream);
+int oi_multi_rmsprop(const oi_mt_chunk* table, int n_chunks, float lr, float alpha, float one_minus_alpha, float eps,
+                     oi_stream_t stream);
 int oi_multi_lerp(const oi_mt_chunk* table, int n_chunks, float beta, oi_stream_t stream);
 /* p <- g for every chunk: many small tensors gathered into (slices of) one buffer in ONE launch -- the stacked parameter
  * layouts of oi_film_params / oi_mlp_pack_weights after an optimiser step (oi_amd.params.StackCache; the reference's modules

@@ -19,13 +19,13 @@ __device__ __forceinline__ float lerp_(float a, float b, float w) {
 }
 
 __global__ void __launch_bounds__(256)
-multi_adam_kernel(const oi_mt_chunk* __restrict__ table, float lr_over_bc1, float beta1, float beta2, float eps,
-                  float bc2_sqrt) {
+multi_adam_kernel(const oi_mt_chunk* __restrict__ table, float lr_over_bc1, float w1, float beta2, float w2, float eps,
+                  float bc2_sqrt) {  // w1 = 1 - beta1, w2 = 1 - beta2: the caller's, rounded once (see oi_multi_adam)
   const oi_mt_chunk c = table[blockIdx.x];
   for (int i = threadIdx.x; i < c.n; i += 256) {
     const float g = c.g[i];
-    const float m = lerp_(c.s0[i], g, 1.0f - beta1);
-    const float v = fmaf(g * g, 1.0f - beta2, c.s1[i] * beta2);
+    const float m = lerp_(c.s0[i], g, w1);
+    const float v = fmaf(g * g, w2, c.s1[i] * beta2);
     c.s0[i] = m;
     c.s1[i] = v;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
@@ -34,11 +34,11 @@ multi_adam_kernel(const oi_mt_chunk* __restrict__ table, float lr_over_bc1, floa
 }
 
 __global__ void __launch_bounds__(256)
-multi_rmsprop_kernel(const oi_mt_chunk* __restrict__ table, float lr, float alpha, float eps) {
+multi_rmsprop_kernel(const oi_mt_chunk* __restrict__ table, float lr, float alpha, float w, float eps) {  // w = 1 - alpha
   const oi_mt_chunk c = table[blockIdx.x];
   for (int i = threadIdx.x; i < c.n; i += 256) {
     const float g = c.g[i];
-    const float sq = fmaf(g * g, 1.0f - alpha, c.s0[i] * alpha);
+    const float sq = fmaf(g * g, w, c.s0[i] * alpha);
     c.s0[i] = sq;
     c.p[i] = c.p[i] - lr * (g / (sqrtf(sq) + eps));
   }
@@ -111,21 +111,26 @@ int oi_zero_fill(float* p, long long n_floats, oi_stream_t stream) {
 
 int oi_mt_chunk_elems(void) { return CHUNK; }
 
-int oi_multi_adam(const oi_mt_chunk* table, int n_chunks, float lr, float beta1, float beta2, float eps,
-                  float bias_correction1, float bias_correction2_sqrt, oi_stream_t stream) {
+// one_minus_beta1 / one_minus_beta2 (and RMSprop's one_minus_alpha) are the caller's complements, formed in double and rounded
+// once as torch forms them: 1.0f - beta from the already rounded float is 0.00099998713 for beta2 = 0.999, 1.3e-5 (relative)
+// from torch's 0.001, and exp_avg_sq inherits exactly that factor.
+int oi_multi_adam(const oi_mt_chunk* table, int n_chunks, float lr, float beta1, float beta2, float one_minus_beta1,
+                  float one_minus_beta2, float eps, float bias_correction1, float bias_correction2_sqrt, oi_stream_t stream) {
   OI_REQUIRE(table != nullptr || n_chunks == 0, "oi_multi_adam: null table");
   OI_REQUIRE(n_chunks >= 0 && bias_correction1 > 0.f && bias_correction2_sqrt > 0.f, "oi_multi_adam: bad arguments");
   if (n_chunks == 0) return OI_OK;
   hipLaunchKernelGGL(multi_adam_kernel, dim3(n_chunks), dim3(256), 0, oi::as_stream(stream), table,
-                     lr / bias_correction1, beta1, beta2, eps, bias_correction2_sqrt);
+                     lr / bias_correction1, one_minus_beta1, beta2, one_minus_beta2, eps, bias_correction2_sqrt);
   return oi::check_launch("oi_multi_adam");
 }
 
-int oi_multi_rmsprop(const oi_mt_chunk* table, int n_chunks, float lr, float alpha, float eps, oi_stream_t stream) {
+int oi_multi_rmsprop(const oi_mt_chunk* table, int n_chunks, float lr, float alpha, float one_minus_alpha, float eps,
+                     oi_stream_t stream) {
   OI_REQUIRE(table != nullptr || n_chunks == 0, "oi_multi_rmsprop: null table");
   OI_REQUIRE(n_chunks >= 0, "oi_multi_rmsprop: n_chunks=%d", n_chunks);
   if (n_chunks == 0) return OI_OK;
-  hipLaunchKernelGGL(multi_rmsprop_kernel, dim3(n_chunks), dim3(256), 0, oi::as_stream(stream), table, lr, alpha, eps);
+  hipLaunchKernelGGL(multi_rmsprop_kernel, dim3(n_chunks), dim3(256), 0, oi::as_stream(stream), table, lr, alpha, one_minus_alpha,
+                     eps);
   return oi::check_launch("oi_multi_rmsprop");
 }
 

@@ -155,8 +155,8 @@ _SIGS = {
     "oi_reflect_pad_fwd": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
     "oi_reflect_pad_bwd": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
     "oi_mt_chunk_elems": (_i, []),
-    "oi_multi_adam": (_i, [_vp, _i, _f, _f, _f, _f, _f, _f, _vp]),
-    "oi_multi_rmsprop": (_i, [_vp, _i, _f, _f, _f, _vp]),
+    "oi_multi_adam": (_i, [_vp, _i, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
+    "oi_multi_rmsprop": (_i, [_vp, _i, _f, _f, _f, _f, _vp]),
     "oi_multi_lerp": (_i, [_vp, _i, _f, _vp]),
     "oi_multi_copy": (_i, [_vp, _i, _vp]),
     # mesh extraction: the reference's extract_fields point source (renderer.py:15-31) and mcubes.marching_cubes (:33-41)

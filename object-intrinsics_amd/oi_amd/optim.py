@@ -82,6 +82,13 @@ def _written(tensors):
     torch.autograd.graph.increment_version(tensors)
 
 
+def _complement(beta):
+    """1 - beta for the kernels, formed in double (ctypes rounds it to float once) as torch forms the `1 - beta1`, `1 - beta2`,
+    `1 - alpha` it hands to lerp_ / addcmul_.  Formed from the rounded float instead, 1 - 0.999 is 0.00099998713: exp_avg_sq
+    would sit 1.3e-5 (relative) from torch's and a state_dict would not interchange at the suite's 1e-6."""
+    return 1.0 - float(beta)
+
+
 def _check(p):
     if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
         raise ValueError("fused optimisers need contiguous fp32 CUDA parameters")
@@ -157,8 +164,8 @@ class FusedAdam(_StepCounts, torch.optim.Optimizer):
             b1, b2 = group["betas"]
             for k, (step, quads) in enumerate(sorted(by_step.items())):
                 table, n = self._tables.setdefault((gi, k), _ChunkTable()).get(quads)
-                rc = L.oi_multi_adam(table.data_ptr(), n, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                     1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), _stream())
+                rc = L.oi_multi_adam(table.data_ptr(), n, float(group["lr"]), float(b1), float(b2), _complement(b1), _complement(b2),
+                                     float(group["eps"]), 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), _stream())
                 if rc:
                     raise _l.OiHipError(L.oi_last_error().decode())
                 _written([t for q in quads for t in (q[0], q[2], q[3])])
@@ -194,8 +201,8 @@ class FusedRMSprop(_StepCounts, torch.optim.Optimizer):
             if not quads:
                 continue
             table, n = self._tables.setdefault(gi, _ChunkTable()).get(quads)
-            rc = L.oi_multi_rmsprop(table.data_ptr(), n, float(group["lr"]), float(group["alpha"]), float(group["eps"]),
-                                    _stream())
+            rc = L.oi_multi_rmsprop(table.data_ptr(), n, float(group["lr"]), float(group["alpha"]), _complement(group["alpha"]),
+                                    float(group["eps"]), _stream())
             if rc:
                 raise _l.OiHipError(L.oi_last_error().decode())
             _written([t for q in quads for t in (q[0], q[2])])

@@ -752,10 +752,11 @@ def test_multi_tensor_steps_chunk_edges(guarded_ops, kind, packed):
     lr, b1, b2, eps, step = 1e-3, 0.5, 0.9, 1e-8, 3
     bc1, bc2s = 1 - b1 ** step, math.sqrt(1 - b2 ** step)
     if kind == "adam":
-        ok(L.oi_multi_adam(vp(table), rows, ctypes.c_float(lr), ctypes.c_float(b1), ctypes.c_float(b2), ctypes.c_float(eps),
-                           ctypes.c_float(bc1), ctypes.c_float(bc2s), stream()), "oi_multi_adam")
+        ok(L.oi_multi_adam(vp(table), rows, ctypes.c_float(lr), ctypes.c_float(b1), ctypes.c_float(b2), ctypes.c_float(1 - b1),
+                           ctypes.c_float(1 - b2), ctypes.c_float(eps), ctypes.c_float(bc1), ctypes.c_float(bc2s), stream()), "oi_multi_adam")
     elif kind == "rmsprop":
-        ok(L.oi_multi_rmsprop(vp(table), rows, ctypes.c_float(lr), ctypes.c_float(0.99), ctypes.c_float(eps), stream()),
+        ok(L.oi_multi_rmsprop(vp(table), rows, ctypes.c_float(lr), ctypes.c_float(0.99), ctypes.c_float(1 - 0.99), ctypes.c_float(eps),
+                              stream()),
            "oi_multi_rmsprop")
     elif kind == "lerp":
         ok(L.oi_multi_lerp(vp(table), rows, ctypes.c_float(0.999), stream()), "oi_multi_lerp")

@@ -241,6 +241,35 @@ def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True,
     return res
 
 
+def env_walk_rotations(n_frames, axis=(0.0, 0.0, 1.0)):
+    """World rotations through 360 degrees about `axis` (any non-zero length), frame 0 the identity.  -> n_frames (3, 3)
+    float64 arrays."""
+    from .envlight import axis_rotation
+    if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or n_frames < 1:
+        raise ValueError(f"env_walk: n_frames={n_frames!r} (a positive integer)")
+    return [axis_rotation(axis, 2 * math.pi * i / n_frames) for i in range(int(n_frames))]
+
+
+@torch.no_grad()
+def env_walk(gen, z, b2w, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64, seed=0, bg=None, bias=None, **kw):
+    """The environment `env` (oi_amd.envlight.EnvLight) turning through 360 degrees about the world `axis` while the view
+    stays: ONE capture (oi_amd.trace.capture_transfer: the primary trace, the full MLP pass at its hits and transfer_samples
+    secondary rays per visible point), then n_frames rotations of the 9 x 3 coefficients on the host and one shade launch per
+    256 frames.  Frame 0 is `env` itself.  -> {"image", "shading": (n_frames, 3, H, W), "transfer": (1, 9, H, W), "mask" /
+    "depth" (1, 1, H, W), "stats"}.  Keyword arguments: capture_transfer's (tol, omega, max_steps, readback)."""
+    from . import trace
+    from .envlight import EnvLight
+    if not isinstance(env, EnvLight):
+        raise TypeError(f"env_walk: expected an EnvLight, got {type(env).__name__}")
+    rots = env_walk_rotations(n_frames, axis)
+    gen.eval()
+    gen.renderer.pack.check()
+    cap = trace.capture_transfer(gen, z, b2w, transfer_samples, seed, trace.DEFAULT_BIAS if bias is None else bias, **kw)
+    res = cap.shade([env.rotated(R) for R in rots], bg)
+    res.update(transfer=cap.transfer, mask=cap.maps["mask"], depth=cap.maps["depth"], stats=cap.stats())
+    return res
+
+
 @torch.no_grad()
 def shade_vertices(positions, normals, albedo, light, eye=None):
     """Phong colour (V, 3) of mesh vertices under `light` (oi_amd.relight.Light; its direction in the mesh's own frame): each

@@ -1,5 +1,5 @@
 """ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h, include/oi_mesh_attr.h,
-include/oi_trace.h, include/oi_occlusion.h, include/oi_mesh_band.h and include/oi_trace_batch.h).
+include/oi_trace.h, include/oi_occlusion.h, include/oi_mesh_band.h, include/oi_trace_batch.h and include/oi_envlight.h).
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -260,6 +260,24 @@ _TRACE_BATCH_SIGS = {
     "oi_trace_batch_gather": (_i, [ctypes.POINTER(TraceBatch), _vp, _ll, _vp, _vp]),
 }
 
+# include/oi_envlight.h: SH environment lights and per-pixel transfer on the traced surface (an addition to oi_occlusion.h)
+ENV_COEFFS, ENV_FLOATS, ENV_MAX_ENVS = 9, 27, 256
+
+
+class EnvShadeParams(ctypes.Structure):
+    """Mirror of `oi_env_shade_params` (include/oi_envlight.h)."""
+    _fields_ = ([("N", _ll), ("n_hit", _ll), ("F", _i)] +
+                [(n, _vp) for n in ("status", "hit_slot", "rgb", "transfer", "envs", "bg", "shading", "image")])
+
+
+_ENVLIGHT_SIGS = {
+    "oi_env_project_partial_floats": (_sz, [_i, _i, _i]),
+    "oi_env_project": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "oi_transfer_resolve": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, _vp, _vp]),
+    "oi_transfer_normal": (_i, [_vp, _vp, _ll, _ll, _vp, _vp, _vp]),
+    "oi_env_shade": (_i, [ctypes.POINTER(EnvShadeParams), _vp]),
+}
+
 # entry points added by later source files (backward kernels); bound when present in the .so
 _OPTIONAL_SIGS = {}
 
@@ -302,6 +320,11 @@ def trace_batch_symbols():
     return sorted(_TRACE_BATCH_SIGS)
 
 
+def envlight_symbols():
+    """The entry points of include/oi_envlight.h."""
+    return sorted(_ENVLIGHT_SIGS)
+
+
 def load():
     """Load (once) and return the ctypes handle.  Raises OiHipError when the library is missing."""
     global _lib
@@ -321,7 +344,7 @@ def load():
                 "oi_amd has no CPU or PyTorch fallback for its kernels.")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_TRACE_SIGS, **_OCCLUSION_SIGS, **_MESH_BAND_SIGS,
-                                   **_TRACE_BATCH_SIGS, **_OPTIONAL_SIGS}.items():
+                                   **_TRACE_BATCH_SIGS, **_ENVLIGHT_SIGS, **_OPTIONAL_SIGS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError:

@@ -822,6 +822,75 @@ def surface_shade_ao(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb,
 
 
 # ------------------------------------------------------------------------------------------
+# environment lighting on the traced surface (include/oi_envlight.h)
+# ------------------------------------------------------------------------------------------
+
+def env_project(radiance):
+    """Equirectangular maps (E, 3, He, We) float32 on the device -> SH coefficients (E, 9, 3) (oi_env_project)."""
+    if not torch.is_tensor(radiance) or radiance.dim() != 4 or radiance.shape[1] != 3:
+        raise ValueError(f"env_project: radiance {tuple(getattr(radiance, 'shape', ()))}, expected (E, 3, He, We)")
+    E, _, He, We = radiance.shape
+    if not (1 <= E <= _l.ENV_MAX_ENVS and He >= 1 and We >= 1 and E * He * We < 1 << 31):
+        raise ValueError(f"env_project: E={E}, He={He}, We={We} (1 <= E <= {_l.ENV_MAX_ENVS}, He, We >= 1, E * He * We < 2^31)")
+    radiance = _c(radiance)
+    L = _l.load()
+    partial = _new(radiance, L.oi_env_project_partial_floats(E, He, We))
+    coeffs = _new(radiance, E, _l.ENV_COEFFS, 3)
+    _l.check(L.oi_env_project(_p(radiance), E, He, We, _p(partial), _p(coeffs), _stream()), "oi_env_project")
+    return coeffs
+
+
+def transfer_resolve(status, rays_d, hit_slot, N, n_hit, samples, w2b):
+    """The finished states (S * n_hit,) uint8 and directions (S * n_hit, 3) of an ambient-occlusion trace -> the transfer map
+    (9, N) float32: per pixel the mean over its `samples` rays of [escaped] y_c(world direction); zeros off the mask."""
+    out = _new(hit_slot, _l.ENV_COEFFS, N)
+    _l.check(_l.load().oi_transfer_resolve(_p(status), _p(rays_d), _ip(hit_slot), int(N), int(n_hit), int(samples), _p(w2b),
+                                           _p(out), _stream()), "oi_transfer_resolve")
+    return out
+
+
+def transfer_normal(grad, hit_slot, N, n_hit, w2b):
+    """The unshadowed transfer map (9, N) of the normals grad (n_hit, 3): A_band y_c(world normal); zeros off the mask."""
+    out = _new(hit_slot, _l.ENV_COEFFS, N)
+    _l.check(_l.load().oi_transfer_normal(_p(grad), _ip(hit_slot), int(N), int(n_hit), _p(w2b), _p(out), _stream()),
+             "oi_transfer_normal")
+    return out
+
+
+ENV_SHADE_OUT = ("shading", "image")
+
+
+def env_shade(status, hit_slot, rgb, n_hit, transfer, envs, bg=None, outputs=ENV_SHADE_OUT, out=None):
+    """One captured view under the environments envs (F, 9, 3) (oi_env_shade).  -> {name: (F, 3, N)} for the names of
+    ENV_SHADE_OUT in `outputs` (written into out[name] when given)."""
+    N = transfer.shape[1]
+    F = envs.shape[0] if torch.is_tensor(envs) and envs.dim() == 3 else 0
+    if not 1 <= F <= _l.ENV_MAX_ENVS or tuple(envs.shape[1:]) != (_l.ENV_COEFFS, 3):
+        raise ValueError(f"env_shade: envs {tuple(getattr(envs, 'shape', ()))}, expected (F, {_l.ENV_COEFFS}, 3) with "
+                         f"1 <= F <= {_l.ENV_MAX_ENVS}")
+    if tuple(transfer.shape) != (_l.ENV_COEFFS, N) or not outputs:
+        raise ValueError(f"env_shade: transfer {tuple(transfer.shape)}, expected ({_l.ENV_COEFFS}, N); outputs {outputs!r}")
+    res = {}
+    for name in outputs:
+        if name not in ENV_SHADE_OUT:
+            raise ValueError(f"env_shade: unknown output {name!r} (one of {ENV_SHADE_OUT})")
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = _new(transfer, F, 3, N)
+        elif tuple(t.shape) != (F, 3, N) or not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"env_shade: out[{name!r}] must be a contiguous float32 {(F, 3, N)} tensor")
+        res[name] = t
+    P = _l.EnvShadeParams()
+    P.N, P.n_hit, P.F = N, int(n_hit), F
+    keep = [_c(x) for x in (rgb if n_hit else None, transfer, envs, bg)]
+    P.rgb, P.transfer, P.envs, P.bg = (_p(x) for x in keep)
+    P.status, P.hit_slot = _p(status), _ip(hit_slot)
+    P.shading, P.image = _p(res.get("shading")), _p(res.get("image"))
+    _l.check(_l.load().oi_env_shade(ctypes.byref(P), _stream()), "oi_env_shade")
+    return res
+
+
+# ------------------------------------------------------------------------------------------
 # discriminator side
 # ------------------------------------------------------------------------------------------
 

@@ -10,6 +10,10 @@
                      optionally with cast shadows (one shadow ray per light and visible point, or `shadow_samples` rays
                      towards a light of angular radius `light_radius`: penumbrae) and ambient occlusion (`ao_samples` rays
                      over the hemisphere of each visible point; include/oi_occlusion.h)
+    capture_transfer one view's secondary rays traced ONCE into a per-pixel SH transfer map; the TransferCapture is then shaded
+                     under any number of environment lights (oi_amd.envlight.EnvLight), 256 per launch
+                     (include/oi_envlight.h)
+    render_surface_env  capture_transfer + shade in one call
 
 The loop runs on the host: oi_trace_begin, then per step the library's sdf-only MLP pass (unchanged) on the rays still in
 flight and oi_trace_step, which advances them and compacts the survivors.  The number of rays in flight lives on the device;
@@ -28,6 +32,10 @@ from .fields import LatentField
 # read-back cadence of the number of rays in flight (DESIGN section 4.13 has the measurements)
 READBACK_DENSE = 1024    # above this many rays a stale bound costs MLP time: read every step
 READBACK_SPARSE = 4      # below it a pass is launch-bound whatever its size: read every 4th step
+
+# how far the transfer rays of capture_transfer go: beyond the unit sphere's diameter, so `far` is the sphere's exit
+TRANSFER_DISTANCE = 4.0
+ENV_MAX_ENVS = _l.ENV_MAX_ENVS   # environments per oi_env_shade launch; larger sets are split
 
 DEFAULT_TOL, DEFAULT_OMEGA, DEFAULT_MAX_STEPS, DEFAULT_BIAS = (_l.TRACE_DEFAULT_TOL, _l.TRACE_DEFAULT_OMEGA,
                                                                _l.TRACE_DEFAULT_MAX_STEPS, _l.TRACE_DEFAULT_BIAS)
@@ -265,8 +273,8 @@ class _Surface:
         self.grad = self.rgb = None
         if self.n_hit:
             _, self.grad, self.rgb = self.field.full(self.res.hit_points)
-        self.shadow_evals = self.ao_evals = 0
-        self.shadow = self.ao = None
+        self.shadow_evals = self.ao_evals = self.transfer_evals = 0
+        self.shadow = self.ao = self.transfer_state = None
 
     @classmethod
     def from_batch(cls, field, kw, bias, ro, rd, w2b, H, res, grad, rgb):
@@ -275,8 +283,8 @@ class _Surface:
         self.kw, self.bias, self.field = kw, bias, field
         self.ro, self.rd, self.w2b, self.N, self.H = ro, rd, w2b, ro.shape[0], H
         self.res, self.n_hit, self.grad, self.rgb = res, res.hit_index.shape[0], grad, rgb
-        self.shadow_evals = self.ao_evals = 0
-        self.shadow = self.ao = None
+        self.shadow_evals = self.ao_evals = self.transfer_evals = 0
+        self.shadow = self.ao = self.transfer_state = None
         return self
 
     def _secondary(self, st):
@@ -321,6 +329,20 @@ class _Surface:
         self.ao_evals += self._secondary(st)
         self.ao = st
         return ops.occlusion_resolve(st.status, self.res.hit_slot, self.N, self.n_hit, 1, samples).view(self.N)
+
+    def transfer(self, samples, seed=0):
+        """(9, N) SH transfer map (include/oi_envlight.h): ambient()'s rays as far as the exit of the unit sphere, resolved
+        into the mean of [escaped] y_c(world direction) per pixel; samples == 0: the unshadowed closed form, nothing traced."""
+        if self.n_hit == 0:
+            return torch.zeros(_l.ENV_COEFFS, self.N, device=self.ro.device)
+        if samples == 0:
+            return ops.transfer_normal(self.grad, self.res.hit_slot, self.N, self.n_hit, self.w2b)
+        st = ops.TraceState(samples * self.n_hit, ref=self.ro)
+        ops.occlusion_ambient_begin(st, self.res.hit_points, self.grad, self.res.hit_index, self.n_hit, samples, self.bias,
+                                    TRANSFER_DISTANCE, seed)
+        self.transfer_evals += self._secondary(st)
+        self.transfer_state = st
+        return ops.transfer_resolve(st.status, st.rays_d, self.res.hit_slot, self.N, self.n_hit, samples, self.w2b)
 
     def shade(self, lights, bg, visibility=None, outputs=tuple(ops.SURFACE_OUT) + ("image",), image_out=None,
               ambient_occlusion=None):
@@ -469,3 +491,81 @@ def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEF
                                 grad[e, :n] if n else None, rgb[e, :n] if n else None)
         out.append(_lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# environment lighting (include/oi_envlight.h)
+# ---------------------------------------------------------------------------------------------------------------------
+def _check_transfer(transfer_samples, seed, what):
+    """_check_occlusion's rule for ao_samples and seed."""
+    v = transfer_samples
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= _l.OCCLUSION_MAX_SAMPLES:
+        raise ValueError(f"{what}: transfer_samples={v!r} (an integer, 0 <= transfer_samples <= {_l.OCCLUSION_MAX_SAMPLES})")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 32:
+        raise ValueError(f"{what}: seed={seed!r} (an integer, 0 <= seed < 2^32)")
+    return int(v), int(seed)
+
+
+class TransferCapture:
+    """One traced view and its SH transfer map: everything shade() needs, none of which depends on the light.
+    surface: the _Surface (primary trace, gradients and albedo at the hits); transfer (1, 9, H, W); maps: render_surface's
+    G-buffer maps (depth, position, normal_map, normal_object, albedo, mask)."""
+
+    def __init__(self, surface, transfer, maps, samples):
+        self.surface, self.samples, self.maps = surface, samples, maps
+        self._transfer = transfer                       # (9, N), planar: what oi_env_shade reads
+        self.H = self.W = surface.H
+        self.transfer = transfer.view(1, _l.ENV_COEFFS, self.H, self.W)
+
+    def shade(self, envs, bg=None):
+        """The view under each of `envs` (an EnvLight or a sequence of them; any number: launches of ENV_MAX_ENVS).
+        -> {"image": (F, 3, H, W) = max(shading, 0) albedo on the mask, bg off it; "shading": (F, 3, H, W), not clamped}."""
+        from .envlight import stack_envs
+        s = self.surface
+        dev = s.ro.device
+        ev = stack_envs(envs, dev)
+        F, N = ev.shape[0], s.N
+        out = {k: ops._new(s.ro, F, 3, N) for k in ops.ENV_SHADE_OUT}
+        bgv = _bg(bg, dev)
+        for a in range(0, F, ENV_MAX_ENVS):
+            b = min(F, a + ENV_MAX_ENVS)
+            ops.env_shade(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, ev[a:b], bgv,
+                          out={k: v[a:b] for k, v in out.items()})
+        return {k: v.view(F, 3, self.H, self.W) for k, v in out.items()}
+
+    def stats(self):
+        st = self.surface.stats()
+        st["transfer_evals"] = self.surface.transfer_evals
+        return st
+
+
+@torch.no_grad()
+def capture_transfer(gen, z, b2w, transfer_samples=64, seed=0, bias=DEFAULT_BIAS, **trace_kw):
+    """One view of `gen` (latent z, pose b2w: render_surface's) prepared for environment lighting: the primary trace, the full
+    MLP pass at its hits, and `transfer_samples` (0 .. 256) cosine-weighted rays per visible point -- render_surface's ambient-
+    occlusion rays for the same seed, followed to the exit of the unit sphere -- resolved into a 9-coefficient transfer vector
+    per pixel.  transfer_samples == 0: the unshadowed closed form of the normal, nothing traced.  trace_kw: tol, omega,
+    max_steps, readback of sphere_trace.  -> TransferCapture."""
+    samples, seed = _check_transfer(transfer_samples, seed, "capture_transfer")
+    dev = gen.it.device
+    s = _Surface(gen, z.to(dev).reshape(1, -1), b2w, bias, trace_kw)
+    transfer = s.transfer(samples, seed)
+    g = s.shade(None, None, outputs=tuple(ops.SURFACE_OUT))
+    maps = {_MAP_NAMES[k]: v for k, v in _maps(g, s.H, s.H).items()}
+    return TransferCapture(s, transfer, maps, samples)
+
+
+@torch.no_grad()
+def render_surface_env(gen, z, b2w, envs, transfer_samples=64, seed=0, bg=None, bias=DEFAULT_BIAS, **trace_kw):
+    """capture_transfer + shade: one view of `gen` under the environment lights `envs` (oi_amd.envlight.EnvLight objects).
+    -> render_surface's G-buffer keys (depth, position, normal_map, normal_object, albedo, mask), image (F, 3, H, W), shading
+    (F, 3, H, W) (not clamped), transfer (1, 9, H, W), stats (with transfer_evals), trace (the primary TraceResult) and
+    transfer_trace (ops.TraceState of the transfer_samples x n_hit rays, ray j * n_hit + i, or None)."""
+    cap = capture_transfer(gen, z, b2w, transfer_samples, seed, bias, **trace_kw)
+    res = dict(cap.maps)
+    res.update(cap.shade(envs, bg))
+    res["transfer"] = cap.transfer
+    res["transfer_trace"] = cap.surface.transfer_state
+    res["stats"] = cap.stats()
+    res["trace"] = cap.surface.res
+    return res

@@ -1,0 +1,390 @@
+// A scene of many instances for gfx950 (include/oi_scene.h): the layer around the batched trace
+// (trace_batch.hip) that makes E instances ONE picture.  Small memory-bound kernels, one thread per ray or scene pixel:
+//   begin          the windowed rays of every instance (render.hip's make_ray), the bounding-sphere cull, the state of the
+//                  batched trace with the entered rays compacted within their element
+//   resolve        per scene pixel the nearest hit among the instances whose window covers it
+//   visible        per instance the dense list of the rays that own their pixel: the input of the full MLP pass
+//   shade          trace_common.h's per-pixel shading on the owner's slices, the instance map, world positions
+//   points         the visible points of all instances as one world-frame list
+//   shadow_begin   per occluder instance one shadow ray per (light, visible point): the owner's own ray by trace.hip's
+//                  expressions, any other instance's moved into its box frame and culled against its unit sphere
+//   visibility     a pixel is lit when its shadow ray missed every instance
+// The march, the finish, the gather and both MLP passes are the library's own.  The compaction is trace_common.h's wg_slot:
+// one integer atomicAdd and one atomicMax per workgroup; resolve and visibility loop over the elements in a fixed order and
+// use no atomics.  No LDS beyond the compaction's counter words, no scratch.
+#include "ray_common.h"
+#include "trace_common.h"
+
+#include "../../include/oi_scene.h"
+
+namespace {
+
+// The unit sphere's chord on the ray (o, d): false when the ray passes at 1 or more from the centre or the sphere lies wholly
+// behind the origin; otherwise near_ = max(mid - h, 0), far_ = mid + h.  Contraction off: tests/helpers/scene_ref.py restates
+// these expressions.
+__device__ __forceinline__ bool unit_sphere_chord(const float* o, const float* d, float& near_, float& far_) {
+#pragma clang fp contract(off)
+  const float dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+  const float od = o[0] * d[0] + o[1] * d[1] + o[2] * d[2];
+  const float mid = -od / dd;
+  const float cx = o[0] + mid * d[0], cy = o[1] + mid * d[1], cz = o[2] + mid * d[2];
+  const float c2 = cx * cx + cy * cy + cz * cz;
+  if (!(c2 < 1.0f)) return false;
+  const float h = sqrtf((1.0f - c2) / dd);
+  far_ = mid + h;
+  near_ = fmaxf(mid - h, 0.f);
+  return far_ > 0.f;
+}
+
+// M (4x4, rigid) applied to the point v: three products and three sums per component, contraction off
+__device__ __forceinline__ void transform_point(const float* __restrict__ M, const float* v, float* out) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int a = 0; a < 3; ++a) out[a] = M[a * 4 + 0] * v[0] + M[a * 4 + 1] * v[1] + M[a * 4 + 2] * v[2] + M[a * 4 + 3];
+}
+
+// every counter of every element and of live, and points = the coordinate origin: the slots behind an element's entered rays
+// are input of the first MLP passes (the bound is the largest count of any element)
+__global__ void __launch_bounds__(TR_THREADS) scene_clear_kernel(const oi_trace_state s, int* __restrict__ live) {
+  if (blockIdx.x == 0 && blockIdx.y == 0)
+    for (int i = threadIdx.x; i < OI_TRACE_COUNT_WORDS; i += TR_THREADS) live[i] = 0;
+  const oi_trace_state v = element_view(s, blockIdx.y);
+  clear_counts(v.counts, 0);
+  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (r < s.N) v.points[r * 3 + 0] = v.points[r * 3 + 1] = v.points[r * 3 + 2] = 0.f;
+}
+
+// ray r of the view v: everything oi_trace_batch_begin writes, for an entered ray (near_ .. far_) or a culled one
+__device__ __forceinline__ void write_ray(const oi_trace_state& v, long long r, const float* o, const float* d, float near_,
+                                          float far_, unsigned status) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) v.rays_o[r * 3 + a] = o[a], v.rays_d[r * 3 + a] = d[a];
+  v.near_[r] = near_;
+  v.far_[r] = far_;
+  v.t[r] = near_;
+  v.status[r] = (uint8_t)status;
+  v.steps[r] = 0;
+  v.side[r] = 0;
+  v.bracket[r * 4 + 0] = near_;
+  v.bracket[r * 4 + 1] = 0.f;
+  v.bracket[r * 4 + 2] = near_;
+  v.bracket[r * 4 + 3] = 0.f;
+}
+
+// the entered rays of this workgroup, compacted behind the element's counter: active list and first sample points
+__device__ __forceinline__ void enter_rays(const oi_trace_state& v, long long r, bool entered, float near_, int* live,
+                                           unsigned* lds) {
+  const long long slot = wg_slot(entered, v.counts, lds, live);
+  if (entered) {
+    v.active[slot] = (int)r;
+    point_at(v.rays_o, v.rays_d, r, near_, v.points + slot * 3);
+  }
+}
+
+__global__ void __launch_bounds__(TR_THREADS) scene_begin_kernel(const oi_trace_state s, int* __restrict__ live,
+                                                                 const float* __restrict__ c2b, const float* __restrict__ kinv,
+                                                                 const int* __restrict__ window, int W, int S) {
+  __shared__ unsigned lds[TR_WAVES + 1];
+  const int e = blockIdx.y;
+  const oi_trace_state v = element_view(s, e);
+  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  bool entered = false;
+  float near_ = 0.f;
+  if (r < s.N) {
+    const int j = (int)(r / W), i = (int)(r - (long long)j * W);
+    const long long X = (long long)window[e * 2 + 0] + i, Y = (long long)window[e * 2 + 1] + j;
+    const bool inside = X >= 0 && X < S && Y >= 0 && Y < S;
+    // (a pixel outside the image has no ray: its slot holds pixel (0, 0)'s, never traced)
+    const RayOD ry = make_ray(c2b + (long long)e * 16, kinv, 0.f, 0.f, S, inside ? (int)X : 0, inside ? (int)Y : 0);
+    float far_ = 0.f;
+    entered = unit_sphere_chord(ry.o, ry.d, near_, far_) && inside;
+    if (!entered) near_ = far_ = 0.f;
+    write_ray(v, r, ry.o, ry.d, near_, far_, entered ? OI_TRACE_MARCH : OI_TRACE_MISS);
+  }
+  enter_rays(v, r, entered, near_, live, lds);
+}
+
+__global__ void __launch_bounds__(TR_THREADS) scene_resolve_kernel(const oi_trace_state s, int E, const int* __restrict__ window,
+                                                                   int W, int S, int* __restrict__ owner,
+                                                                   int* __restrict__ owner_ray) {
+  const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (q >= (long long)S * S) return;
+  const int Y = (int)(q / S), X = (int)(q - (long long)Y * S);
+  int best = -1, best_ray = -1;
+  float best_t = INFINITY;
+  for (int e = 0; e < E; ++e) {  // window: wave-uniform reads
+    const long long i = (long long)X - window[e * 2 + 0], j = (long long)Y - window[e * 2 + 1];
+    if (i < 0 || i >= W || j < 0 || j >= W) continue;
+    const long long r = j * W + i, g = (long long)e * s.N + r;
+    if (s.status[g] != OI_TRACE_HIT) continue;
+    const float t = s.t[g];
+    if (best < 0 || t < best_t) best = e, best_ray = (int)r, best_t = t;  // equal t: the lowest element index stays
+  }
+  owner[q] = best;
+  owner_ray[q] = best_ray;
+}
+
+__global__ void __launch_bounds__(TR_THREADS) scene_clear_hits_kernel(int* __restrict__ counts, int* __restrict__ live, int E) {
+  const int e = blockIdx.x * TR_THREADS + threadIdx.x;
+  if (e < E) counts[(long long)e * OI_TRACE_COUNT_WORDS + N_HIT_WORD] = 0;
+  if (e == 0) live[N_HIT_WORD] = 0;
+}
+
+__global__ void __launch_bounds__(TR_THREADS) scene_visible_kernel(const oi_trace_state s, int* __restrict__ live,
+                                                                   const int* __restrict__ owner,
+                                                                   const int* __restrict__ window, int W, int S,
+                                                                   int* __restrict__ vis_index, int* __restrict__ vis_slot) {
+  __shared__ unsigned lds[TR_WAVES + 1];
+  const int e = blockIdx.y;
+  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x, base = (long long)e * s.N;
+  bool mine = false;
+  if (r < s.N) {
+    const int j = (int)(r / W), i = (int)(r - (long long)j * W);
+    const long long X = (long long)window[e * 2 + 0] + i, Y = (long long)window[e * 2 + 1] + j;
+    mine = X >= 0 && X < S && Y >= 0 && Y < S && owner[Y * S + X] == e;
+  }
+  const long long slot = wg_slot(mine, s.counts + (long long)e * OI_TRACE_COUNT_WORDS + N_HIT_WORD, lds, live + N_HIT_WORD);
+  if (r < s.N) vis_slot[base + r] = mine ? (int)slot : -1;
+  if (mine) vis_index[base + slot] = (int)r;
+}
+
+// oi_surface_params' fields for one element of the scene (surface_shade_at's P)
+struct ElementSurface {
+  int L;
+  const float *rays_o, *rays_d, *t;
+  const int* hit_slot;
+  const float *hit_points, *grad, *rgb, *w2b, *lights, *bg, *visibility;
+  float *depth, *position, *normal, *normal_world, *albedo, *mask, *image;
+};
+
+__global__ void __launch_bounds__(TR_THREADS) scene_shade_kernel(const oi_scene_shade_params p) {
+  const long long M = (long long)p.S * p.S, N = (long long)p.W * p.W;
+  const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (q >= M) return;
+  const int e = p.owner[q];
+  const bool hit = e >= 0 && e < p.E && p.n_pad > 0;
+  const long long eo = hit ? e : 0, r = hit ? p.owner_ray[q] : 0;
+  ElementSurface v;
+  v.L = p.L;
+  v.rays_o = p.rays_o + eo * N * 3, v.rays_d = p.rays_d + eo * N * 3, v.t = p.t + eo * N;
+  v.hit_slot = p.vis_slot + eo * N;
+  v.hit_points = p.hit_points + eo * p.n_pad * 3, v.grad = p.grad + eo * p.n_pad * 3, v.rgb = p.rgb + eo * p.n_pad * 3;
+  v.w2b = p.w2b + eo * 16, v.lights = p.lights, v.bg = p.bg, v.visibility = p.visibility;
+  v.depth = p.depth, v.position = nullptr, v.normal = p.normal, v.normal_world = p.normal_world, v.albedo = p.albedo;
+  v.mask = p.mask, v.image = p.image;
+  if (p.instance) p.instance[q] = hit ? e : -1;
+  if (p.position) {
+    float w[3] = {0.f, 0.f, 0.f};
+    if (hit) transform_point(p.b2w + eo * 16, v.hit_points + (long long)v.hit_slot[r] * 3, w);
+    p.position[q * 3 + 0] = w[0], p.position[q * 3 + 1] = w[1], p.position[q * 3 + 2] = w[2];
+  }
+  surface_shade_at(v, nullptr, r, hit, q, M);
+}
+
+__global__ void __launch_bounds__(TR_THREADS) scene_points_kernel(const int* __restrict__ counts,
+                                                                  const float* __restrict__ hit_points,
+                                                                  const float* __restrict__ grad, long long n_pad,
+                                                                  const int* __restrict__ offset, long long n_vis,
+                                                                  const float* __restrict__ b2w, const float* __restrict__ w2b,
+                                                                  float* __restrict__ position, float* __restrict__ normal,
+                                                                  int* __restrict__ elem) {
+  const int e = blockIdx.y;
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= n_pad || i >= counts[(long long)e * OI_TRACE_COUNT_WORDS + N_HIT_WORD]) return;
+  const long long g = (long long)offset[e] + i, k = (long long)e * n_pad + i;
+  if (g >= n_vis) return;  // (offsets that do not belong to these counts: nothing is written outside the lists)
+  float w[3];
+  transform_point(b2w + (long long)e * 16, hit_points + k * 3, w);
+  const float gx = grad[k * 3 + 0], gy = grad[k * 3 + 1], gz = grad[k * 3 + 2];
+  const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);  // surface_shade_at's normal
+  const float n[3] = {gx / gnc, gy / gnc, gz / gnc};
+  const float* Wb = w2b + (long long)e * 16;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    position[g * 3 + a] = w[a];
+    normal[g * 3 + a] = Wb[0 + a] * n[0] + Wb[4 + a] * n[1] + Wb[8 + a] * n[2];  // w2b[:3,:3]^T n
+  }
+  elem[g] = e;
+}
+
+__global__ void __launch_bounds__(TR_THREADS) scene_shadow_begin_kernel(const oi_trace_state s, int* __restrict__ live,
+                                                                        const float* __restrict__ hit_points,
+                                                                        const float* __restrict__ grad, long long n_pad,
+                                                                        const int* __restrict__ offset,
+                                                                        const int* __restrict__ elem,
+                                                                        const float* __restrict__ position,
+                                                                        const float* __restrict__ normal, long long n_vis,
+                                                                        const float* __restrict__ lights,
+                                                                        const float* __restrict__ w2b, float bias) {
+  __shared__ unsigned lds[TR_WAVES + 1];
+  const int eo = blockIdx.y;  // the occluder
+  const oi_trace_state v = element_view(s, eo);
+  const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  bool entered = false;
+  float near_ = 0.f;
+  if (q < s.N) {
+    const long long l = q / n_vis, g = q - l * n_vis;
+    const int e = elem[g];  // the point's owner
+    const float* lt = lights + l * OI_RELIGHT_LIGHT_FLOATS;
+    const ShadowRay own = shadow_ray(hit_points + (long long)e * n_pad * 3, grad + (long long)e * n_pad * 3, g - offset[e], lt,
+                                     w2b + (long long)e * 16, bias);
+    float o[3] = {own.o[0], own.o[1], own.o[2]}, d[3] = {own.l[0], own.l[1], own.l[2]}, far_ = own.far_;
+    unsigned status = OI_TRACE_BACKFACING;
+    if (own.traced && e == eo) {
+      entered = true;
+      status = OI_TRACE_MARCH;
+    } else if (own.traced) {
+      const float* Wb = w2b + (long long)eo * 16;
+      float ow[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) ow[a] = __fmaf_rn(bias, normal[g * 3 + a], position[g * 3 + a]);
+      transform_point(Wb, ow, o);
+      light_dir(lt, Wb, d[0], d[1], d[2]);
+      entered = unit_sphere_chord(o, d, near_, far_);
+      status = entered ? OI_TRACE_MARCH : OI_TRACE_MISS;
+    }
+    if (!entered) near_ = far_ = 0.f;
+    write_ray(v, q, o, d, near_, far_, status);
+  }
+  enter_rays(v, q, entered, near_, live, lds);
+}
+
+__global__ void __launch_bounds__(TR_THREADS) scene_visibility_kernel(const uint8_t* __restrict__ status,
+                                                                      const int* __restrict__ owner,
+                                                                      const int* __restrict__ owner_ray,
+                                                                      const int* __restrict__ vis_slot,
+                                                                      const int* __restrict__ offset, int E, long long N, int L,
+                                                                      long long n_vis, long long M, float* __restrict__ vis) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= M * L) return;
+  const long long l = i / M, q = i - l * M;
+  const int e = owner[q];
+  float out = 1.0f;
+  if (e >= 0) {
+    const long long g = (long long)offset[e] + vis_slot[(long long)e * N + owner_ray[q]];
+    for (int eo = 0; eo < E; ++eo)
+      if (status[((long long)eo * L + l) * n_vis + g] != OI_TRACE_MISS) out = 0.0f;
+  }
+  vis[i] = out;
+}
+
+inline int check_scene(const oi_trace_batch* b, int W, int S, const char* what) {
+  int rc = check_batch(b, what);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(W >= 1 && (long long)W * W == b->s.N, "%s: W=%d, N=%lld rays per element (N must be W * W)", what, W, b->s.N);
+  OI_REQUIRE(S >= 1 && S <= OI_SCENE_MAX_RESOLUTION, "%s: S=%d (1 .. %d)", what, S, OI_SCENE_MAX_RESOLUTION);
+  return OI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int oi_scene_begin(const oi_trace_batch* b, const float* c2b, const float* kinv, const int* window, int W, int S,
+                   oi_stream_t stream) {
+  const char* what = "oi_scene_begin";
+  int rc = check_scene(b, W, S, what);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(c2b && kinv && window, "%s: null input pointer", what);
+  const hipStream_t st = oi::as_stream(stream);
+  const dim3 grid(n_blocks(b->s.N), b->E);
+  hipLaunchKernelGGL(scene_clear_kernel, grid, dim3(TR_THREADS), 0, st, b->s, b->live);
+  hipLaunchKernelGGL(scene_begin_kernel, grid, dim3(TR_THREADS), 0, st, b->s, b->live, c2b, kinv, window, W, S);
+  return oi::check_launch(what);
+}
+
+int oi_scene_resolve(const oi_trace_batch* b, const int* window, int W, int S, int* owner, int* owner_ray,
+                     oi_stream_t stream) {
+  const char* what = "oi_scene_resolve";
+  int rc = check_scene(b, W, S, what);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(window && owner && owner_ray, "%s: null pointer", what);
+  hipLaunchKernelGGL(scene_resolve_kernel, dim3(n_blocks((long long)S * S)), dim3(TR_THREADS), 0, oi::as_stream(stream), b->s,
+                     b->E, window, W, S, owner, owner_ray);
+  return oi::check_launch(what);
+}
+
+int oi_scene_visible(const oi_trace_batch* b, const int* owner, const int* window, int W, int S, int* vis_index,
+                     int* vis_slot, oi_stream_t stream) {
+  const char* what = "oi_scene_visible";
+  int rc = check_scene(b, W, S, what);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(owner && window && vis_index && vis_slot, "%s: null pointer", what);
+  const hipStream_t st = oi::as_stream(stream);
+  hipLaunchKernelGGL(scene_clear_hits_kernel, dim3(n_blocks(b->E)), dim3(TR_THREADS), 0, st, b->s.counts, b->live, b->E);
+  hipLaunchKernelGGL(scene_visible_kernel, dim3(n_blocks(b->s.N), b->E), dim3(TR_THREADS), 0, st, b->s, b->live, owner, window,
+                     W, S, vis_index, vis_slot);
+  return oi::check_launch(what);
+}
+
+int oi_scene_shade(const oi_scene_shade_params* p, oi_stream_t stream) {
+  const char* what = "oi_scene_shade";
+  OI_REQUIRE(p != nullptr, "%s: null params", what);
+  OI_REQUIRE(p->E >= 1 && p->E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, p->E, OI_TRACE_BATCH_MAX_ELEMS);
+  OI_REQUIRE(p->W >= 1 && (long long)p->E * p->W * p->W < (1ll << 31), "%s: E=%d, W=%d (W >= 1, E * W * W < 2^31)", what, p->E,
+             p->W);
+  OI_REQUIRE(p->S >= 1 && p->S <= OI_SCENE_MAX_RESOLUTION, "%s: S=%d (1 .. %d)", what, p->S, OI_SCENE_MAX_RESOLUTION);
+  OI_REQUIRE(p->n_pad >= 0 && p->n_pad <= (long long)p->W * p->W, "%s: n_pad=%lld (0 <= n_pad <= W * W = %lld)", what, p->n_pad,
+             (long long)p->W * p->W);
+  OI_REQUIRE(p->image ? (p->L >= 1 && p->L <= OI_RELIGHT_MAX_LIGHTS && p->lights) : p->L >= 0,
+             "%s: L=%d (1 .. %d lights with an image)", what, p->L, OI_RELIGHT_MAX_LIGHTS);
+  OI_REQUIRE(p->owner && p->owner_ray, "%s: null owner map", what);
+  OI_REQUIRE(p->n_pad == 0 || (p->rays_o && p->rays_d && p->t && p->vis_slot && p->hit_points && p->grad && p->rgb &&
+                               p->w2b && p->b2w),
+             "%s: null input pointer with n_pad=%lld", what, p->n_pad);
+  hipLaunchKernelGGL(scene_shade_kernel, dim3(n_blocks((long long)p->S * p->S)), dim3(TR_THREADS), 0, oi::as_stream(stream), *p);
+  return oi::check_launch(what);
+}
+
+int oi_scene_points(const oi_trace_batch* b, const float* hit_points, const float* grad, long long n_pad, const int* offset,
+                    long long n_vis, const float* b2w, const float* w2b, float* position, float* normal, int* elem,
+                    oi_stream_t stream) {
+  const char* what = "oi_scene_points";
+  int rc = check_batch(b, what);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(n_pad >= 1 && n_pad <= b->s.N, "%s: n_pad=%lld (1 <= n_pad <= N=%lld)", what, n_pad, b->s.N);
+  OI_REQUIRE(n_vis >= 1 && n_vis <= b->E * n_pad, "%s: n_vis=%lld (1 <= n_vis <= E * n_pad = %lld)", what, n_vis, b->E * n_pad);
+  OI_REQUIRE(hit_points && grad && offset && b2w && w2b && position && normal && elem, "%s: null pointer", what);
+  hipLaunchKernelGGL(scene_points_kernel, dim3(n_blocks(n_pad), b->E), dim3(TR_THREADS), 0, oi::as_stream(stream), b->s.counts,
+                     hit_points, grad, n_pad, offset, n_vis, b2w, w2b, position, normal, elem);
+  return oi::check_launch(what);
+}
+
+int oi_scene_shadow_begin(const oi_trace_batch* sb, const float* hit_points, const float* grad, long long n_pad,
+                          const int* offset, const int* elem, const float* position, const float* normal, long long n_vis,
+                          const float* lights, int L, const float* w2b, float bias, oi_stream_t stream) {
+  const char* what = "oi_scene_shadow_begin";
+  int rc = check_batch(sb, what);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "%s: L=%d (1 .. %d lights)", what, L, OI_RELIGHT_MAX_LIGHTS);
+  OI_REQUIRE(n_vis >= 1 && n_vis * L == sb->s.N, "%s: n_vis=%lld, L=%d, N=%lld (N must be L * n_vis)", what, n_vis, L, sb->s.N);
+  OI_REQUIRE(n_pad >= 1 && n_vis <= sb->E * n_pad, "%s: n_pad=%lld, n_vis=%lld (n_pad >= 1, n_vis <= E * n_pad)", what, n_pad,
+             n_vis);
+  OI_REQUIRE(bias >= 0.f && bias < INFINITY, "%s: bias %g (>= 0, finite)", what, (double)bias);
+  OI_REQUIRE(hit_points && grad && offset && elem && position && normal && lights && w2b, "%s: null input pointer", what);
+  const hipStream_t st = oi::as_stream(stream);
+  const dim3 grid(n_blocks(sb->s.N), sb->E);
+  hipLaunchKernelGGL(scene_clear_kernel, grid, dim3(TR_THREADS), 0, st, sb->s, sb->live);
+  hipLaunchKernelGGL(scene_shadow_begin_kernel, grid, dim3(TR_THREADS), 0, st, sb->s, sb->live, hit_points, grad, n_pad, offset,
+                     elem, position, normal, n_vis, lights, w2b, bias);
+  return oi::check_launch(what);
+}
+
+int oi_scene_visibility(const uint8_t* shadow_status, const int* owner, const int* owner_ray, const int* vis_slot,
+                        const int* offset, int E, long long N, int L, long long n_vis, int S, float* visibility,
+                        oi_stream_t stream) {
+  const char* what = "oi_scene_visibility";
+  OI_REQUIRE(E >= 1 && E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, E, OI_TRACE_BATCH_MAX_ELEMS);
+  OI_REQUIRE(N >= 1 && E * N < (1ll << 31), "%s: E=%d x N=%lld rays (N >= 1, E * N < 2^31)", what, E, N);
+  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "%s: L=%d (1 .. %d lights)", what, L, OI_RELIGHT_MAX_LIGHTS);
+  OI_REQUIRE(S >= 1 && S <= OI_SCENE_MAX_RESOLUTION, "%s: S=%d (1 .. %d)", what, S, OI_SCENE_MAX_RESOLUTION);
+  OI_REQUIRE(n_vis >= 0 && n_vis <= E * N && (long long)E * L * n_vis < (1ll << 31),
+             "%s: n_vis=%lld (0 <= n_vis <= E * N, E * L * n_vis < 2^31)", what, n_vis);
+  OI_REQUIRE(owner && owner_ray && visibility && (n_vis == 0 || (shadow_status && vis_slot && offset)), "%s: null pointer", what);
+  const long long M = (long long)S * S;
+  hipLaunchKernelGGL(scene_visibility_kernel, dim3(n_blocks(M * L)), dim3(TR_THREADS), 0, oi::as_stream(stream), shadow_status,
+                     owner, owner_ray, vis_slot, offset, E, N, L, n_vis, M, visibility);
+  return oi::check_launch(what);
+}
+
+}  // extern "C"

@@ -35,20 +35,13 @@ __global__ void __launch_bounds__(TR_THREADS) trace_shadow_begin_kernel(const oi
   float ox = 0.f, oy = 0.f, oz = 0.f;
   if (q < s.N) {
     const long long l = q / n_hit, i = q - l * n_hit;
-    float lx, ly, lz;
-    light_dir(lights + l * OI_RELIGHT_LIGHT_FLOATS, w2b, lx, ly, lz);
-    const float gx = grad[i * 3 + 0], gy = grad[i * 3 + 1], gz = grad[i * 3 + 2];
-    const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
-    const float nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
-    traced = nx * lx + ny * ly + nz * lz > 0.f;
-    ox = __fmaf_rn(bias, nx, hit_points[i * 3 + 0]);
-    oy = __fmaf_rn(bias, ny, hit_points[i * 3 + 1]);
-    oz = __fmaf_rn(bias, nz, hit_points[i * 3 + 2]);
-    const float far = unit_sphere_exit(ox, oy, oz, lx, ly, lz);
+    const ShadowRay ry = shadow_ray(hit_points, grad, i, lights + l * OI_RELIGHT_LIGHT_FLOATS, w2b, bias);
+    traced = ry.traced;
+    ox = ry.o[0], oy = ry.o[1], oz = ry.o[2];
     s.rays_o[q * 3 + 0] = ox, s.rays_o[q * 3 + 1] = oy, s.rays_o[q * 3 + 2] = oz;
-    s.rays_d[q * 3 + 0] = lx, s.rays_d[q * 3 + 1] = ly, s.rays_d[q * 3 + 2] = lz;
+    s.rays_d[q * 3 + 0] = ry.l[0], s.rays_d[q * 3 + 1] = ry.l[1], s.rays_d[q * 3 + 2] = ry.l[2];
     s.near_[q] = 0.f;
-    s.far_[q] = far;
+    s.far_[q] = ry.far_;
     s.t[q] = 0.f;
     s.status[q] = traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING;
     s.steps[q] = 0;

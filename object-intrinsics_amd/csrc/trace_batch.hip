@@ -6,29 +6,7 @@
 // points, which makes the E ragged hit lists one (E, n_pad) input of the library's full MLP pass.
 #include "trace_common.h"
 
-#include "../../include/oi_trace_batch.h"
-
 namespace {
-
-// element e's segment of every array of the batched state
-__device__ __forceinline__ oi_trace_state element_view(const oi_trace_state& s, long long e) {
-  const long long o = e * s.N;
-  oi_trace_state v;
-  v.N = s.N;
-  v.rays_o = s.rays_o + o * 3;
-  v.rays_d = s.rays_d + o * 3;
-  v.near_ = s.near_ + o;
-  v.far_ = s.far_ + o;
-  v.t = s.t + o;
-  v.status = s.status + o;
-  v.steps = s.steps + o;
-  v.bracket = s.bracket + o * 4;
-  v.side = s.side + o;
-  v.active = s.active + o * 2;
-  v.points = s.points + o * 3;
-  v.counts = s.counts + e * OI_TRACE_COUNT_WORDS;
-  return v;
-}
 
 __global__ void __launch_bounds__(TR_THREADS) trace_batch_begin_kernel(const oi_trace_state s, int* __restrict__ live) {
   if (blockIdx.x == 0 && blockIdx.y == 0)
@@ -63,16 +41,6 @@ __global__ void __launch_bounds__(TR_THREADS) trace_batch_gather_kernel(const oi
   } else {
     dst[0] = dst[1] = dst[2] = 0.f;  // padding: a valid point for the full pass, whose output for it nobody reads
   }
-}
-
-inline int check_batch(const oi_trace_batch* b, const char* what) {
-  OI_REQUIRE(b != nullptr, "%s: null batch", what);
-  OI_REQUIRE(b->E >= 1 && b->E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, b->E, OI_TRACE_BATCH_MAX_ELEMS);
-  int rc = check_state(&b->s, what);
-  if (rc != OI_OK) return rc;
-  OI_REQUIRE((long long)b->E * b->s.N < (1ll << 31), "%s: E=%d x N=%lld rays (E * N < 2^31)", what, b->E, b->s.N);
-  OI_REQUIRE(b->live != nullptr, "%s: null live", what);
-  return OI_OK;
 }
 
 }  // namespace

@@ -1,11 +1,12 @@
-// What trace.hip and occlusion.hip share (include/oi_trace.h, include/oi_occlusion.h; DESIGN sections 4.13 and 4.16): the
-// workgroup compaction, the ray state machine (the full one and its any-hit form, one template), the light's direction and
-// the per-pixel shading.  Everything here has internal linkage; each source file instantiates what it exports.
+// What trace.hip, occlusion.hip, trace_batch.hip and scene.hip share (include/oi_trace.h, include/oi_occlusion.h,
+// include/oi_trace_batch.h, include/oi_scene.h; DESIGN sections 4.13, 4.16, 4.17 and 4.19): the workgroup compaction, the ray
+// state machine (the full one and its any-hit form, one template), the light's direction, the shadow ray of a surface point
+// and the per-pixel shading.  Everything here has internal linkage; each source file instantiates what it exports.
 #ifndef OI_TRACE_COMMON_H_
 #define OI_TRACE_COMMON_H_
 
 #include "oi_common.h"
-#include "../../include/oi_trace.h"
+#include "../../include/oi_trace_batch.h"
 
 namespace {
 
@@ -56,6 +57,26 @@ __device__ __forceinline__ long long wg_slot(bool keep, int* counter, unsigned* 
   }
   __syncthreads();
   return (long long)lds[TR_WAVES] + lds[wave] + pre;
+}
+
+// element e's segment of every array of the batched state
+__device__ __forceinline__ oi_trace_state element_view(const oi_trace_state& s, long long e) {
+  const long long o = e * s.N;
+  oi_trace_state v;
+  v.N = s.N;
+  v.rays_o = s.rays_o + o * 3;
+  v.rays_d = s.rays_d + o * 3;
+  v.near_ = s.near_ + o;
+  v.far_ = s.far_ + o;
+  v.t = s.t + o;
+  v.status = s.status + o;
+  v.steps = s.steps + o;
+  v.bracket = s.bracket + o * 4;
+  v.side = s.side + o;
+  v.active = s.active + o * 2;
+  v.points = s.points + o * 3;
+  v.counts = s.counts + e * OI_TRACE_COUNT_WORDS;
+  return v;
 }
 
 __device__ __forceinline__ void clear_counts(int* counts, int first) {
@@ -221,13 +242,34 @@ __device__ __forceinline__ float unit_sphere_exit(float ox, float oy, float oz, 
   return disc > 0.f ? fmaxf(sqrtf(disc) - b, 0.f) : 0.f;
 }
 
+// oi_trace_shadow_begin's ray of hit i under the light lt: n = g / max(|g|, 1e-6), l = the light's direction in the object
+// frame; origin = point + bias n, direction = l, far = the exit of the unit sphere; traced: n . l > 0.
+struct ShadowRay {
+  float o[3], l[3], far_;
+  bool traced;
+};
+__device__ __forceinline__ ShadowRay shadow_ray(const float* __restrict__ hit_points, const float* __restrict__ grad, long long i,
+                                                const float* __restrict__ lt, const float* __restrict__ w2b, float bias) {
+  ShadowRay r;
+  light_dir(lt, w2b, r.l[0], r.l[1], r.l[2]);
+  const float gx = grad[i * 3 + 0], gy = grad[i * 3 + 1], gz = grad[i * 3 + 2];
+  const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
+  const float nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
+  r.traced = nx * r.l[0] + ny * r.l[1] + nz * r.l[2] > 0.f;
+  r.o[0] = __fmaf_rn(bias, nx, hit_points[i * 3 + 0]);
+  r.o[1] = __fmaf_rn(bias, ny, hit_points[i * 3 + 1]);
+  r.o[2] = __fmaf_rn(bias, nz, hit_points[i * 3 + 2]);
+  r.far_ = unit_sphere_exit(r.o[0], r.o[1], r.o[2], r.l[0], r.l[1], r.l[2]);
+  return r;
+}
+
 // One pixel of the G-buffer and of the Phong image.  P: oi_surface_params or a struct with the same fields; ao: [N] ambient
-// occlusion or nullptr (the ambient term as it is).
+// occlusion or nullptr (the ambient term as it is).  The inputs are read at ray r of p (only where `hit`), the outputs
+// written at pixel q of planes of M pixels (p.visibility is read there too): r == q and M == p.N for a single view; a scene
+// (scene.hip) reads the owner's ray and writes the scene's pixel.
 template <class P>
-__device__ __forceinline__ void surface_shade_pixel(const P& p, const float* __restrict__ ao) {
-  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  if (r >= p.N) return;
-  const bool hit = p.status[r] == OI_TRACE_HIT;
+__device__ __forceinline__ void surface_shade_at(const P& p, const float* __restrict__ ao, long long r, bool hit, long long q,
+                                                 long long M) {
   const float b3[3] = {p.bg ? p.bg[0] : 0.f, p.bg ? p.bg[1] : 0.f, p.bg ? p.bg[2] : 0.f};
   float pos[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f}, nw[3] = {0.f, 0.f, 0.f}, alb[3] = {0.f, 0.f, 0.f};
   float vx = 0.f, vy = 0.f, vz = 0.f;
@@ -246,22 +288,22 @@ __device__ __forceinline__ void surface_shade_pixel(const P& p, const float* __r
     vx = p.rays_o[r * 3 + 0] - pos[0], vy = p.rays_o[r * 3 + 1] - pos[1], vz = p.rays_o[r * 3 + 2] - pos[2];
     normalize3(vx, vy, vz, 1e-6f);
   }
-  if (p.depth) p.depth[r] = hit ? p.t[r] : __uint_as_float(0x7fc00000u);
-  if (p.mask) p.mask[r] = hit ? 1.0f : 0.0f;
+  if (p.depth) p.depth[q] = hit ? p.t[r] : __uint_as_float(0x7fc00000u);
+  if (p.mask) p.mask[q] = hit ? 1.0f : 0.0f;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    if (p.position) p.position[r * 3 + a] = pos[a];
-    if (p.normal) p.normal[r * 3 + a] = n[a];
-    if (p.normal_world) p.normal_world[r * 3 + a] = nw[a];
-    if (p.albedo) p.albedo[r * 3 + a] = alb[a];
+    if (p.position) p.position[q * 3 + a] = pos[a];
+    if (p.normal) p.normal[q * 3 + a] = n[a];
+    if (p.normal_world) p.normal_world[q * 3 + a] = nw[a];
+    if (p.albedo) p.albedo[q * 3 + a] = alb[a];
   }
   if (!p.image) return;
   const bool occluded = ao != nullptr;
   const float aov = occluded && hit ? ao[r] : 1.0f;
   for (int l = 0; l < p.L; ++l) {
-    float* img = p.image + (long long)l * 3 * p.N + r;
+    float* img = p.image + (long long)l * 3 * M + q;
     if (!hit) {
-      img[0] = b3[0], img[p.N] = b3[1], img[2 * p.N] = b3[2];
+      img[0] = b3[0], img[M] = b3[1], img[2 * M] = b3[2];
       continue;
     }
     const float* lt = p.lights + (long long)l * OI_RELIGHT_LIGHT_FLOATS;
@@ -274,7 +316,7 @@ __device__ __forceinline__ void surface_shade_pixel(const P& p, const float* __r
     const float al = fmaxf(vx * rx + vy * ry + vz * rz, 0.f) * (ndl > 0.f ? 1.f : 0.f);
     const float pw = powf(al, lt[15]);
     const bool shadowed = p.visibility != nullptr;
-    const float vis = shadowed ? p.visibility[(long long)l * p.N + r] : 1.0f;
+    const float vis = shadowed ? p.visibility[(long long)l * M + q] : 1.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       float diff = lt[8 + c] * rl, spec = lt[12 + c] * pw;
@@ -282,9 +324,16 @@ __device__ __forceinline__ void surface_shade_pixel(const P& p, const float* __r
       // (a product rounded on its own: the sum below contracts with the diffuse term whether or not ao is given)
       const float amb = occluded ? __fmul_rn(aov, lt[4 + c]) : lt[4 + c];
       const float shade = amb + diff;
-      img[c * p.N] = shade * alb[c] + spec;
+      img[c * M] = shade * alb[c] + spec;
     }
   }
+}
+
+template <class P>
+__device__ __forceinline__ void surface_shade_pixel(const P& p, const float* __restrict__ ao) {
+  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (r >= p.N) return;
+  surface_shade_at(p, ao, r, p.status[r] == OI_TRACE_HIT, r, p.N);
 }
 
 inline unsigned n_blocks(long long n) { return (unsigned)((n + TR_THREADS - 1) / TR_THREADS); }
@@ -295,6 +344,16 @@ inline int check_state(const oi_trace_state* s, const char* what) {
   OI_REQUIRE(s->rays_o && s->rays_d && s->near_ && s->far_ && s->t && s->status && s->steps && s->bracket && s->side &&
                  s->active && s->points && s->counts,
              "%s: null pointer in the state", what);
+  return OI_OK;
+}
+
+inline int check_batch(const oi_trace_batch* b, const char* what) {
+  OI_REQUIRE(b != nullptr, "%s: null batch", what);
+  OI_REQUIRE(b->E >= 1 && b->E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, b->E, OI_TRACE_BATCH_MAX_ELEMS);
+  int rc = check_state(&b->s, what);
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE((long long)b->E * b->s.N < (1ll << 31), "%s: E=%d x N=%lld rays (E * N < 2^31)", what, b->E, b->s.N);
+  OI_REQUIRE(b->live != nullptr, "%s: null live", what);
   return OI_OK;
 }
 

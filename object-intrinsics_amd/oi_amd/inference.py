@@ -241,6 +241,48 @@ def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True,
     return res
 
 
+@torch.no_grad()
+def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True, bg=None, bias=None, window=None,
+                     max_shadow_rays=None, **kw):
+    """surface_light_walk on a scene of K instances (oi_amd.scene): the scene is traced ONCE -- one batched
+    march, one depth resolve, one full MLP pass at the visible hits -- and shaded under the walk of lights, each instance
+    shadowing itself and the others.  Frame 0 is the trained light.  The lights are split so that one shadow batch holds at
+    most max_shadow_rays rays (default oi_amd.scene.MAX_SHADOW_RAYS), counted as K * lights * visible points, and at most 256
+    lights; the frames do not depend on the split (rays are independent).  -> {"image": (n_frames, 3, S, S), "visibility":
+    (n_frames, 1, S, S) when shadows, "mask" / "depth" / "instance" (1, 1, S, S), "stats"}.  kw: tol, omega, max_steps,
+    readback of sphere_trace."""
+    from . import lib, scene, trace
+    from .relight import Light, stack_lights
+    base = Light.from_module(gen.light)
+    dirs = light_walk_directions(base.direction, n_frames, axis)
+    dev = gen.it.device
+    lt = stack_lights([base] + [base.replace(direction=tuple(d)) for d in dirs[1:]], dev)
+    gen.eval()
+    gen.renderer.pack.check()
+    limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
+    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, **kw)
+    S, M = s.S, s.S * s.S
+    image = torch.empty(n_frames, 3, M, device=dev)
+    vis_all = torch.empty(n_frames, M, device=dev) if shadows else None
+    step = lib.RELIGHT_MAX_LIGHTS
+    if shadows:   # (one light above the limit: SceneSurface.visibility refuses it, naming the count)
+        step = max(1, min(step, limit // max(1, s.E * sum(s.n_vis))))
+    maps = None
+    for a in range(0, n_frames, step):
+        b = min(n_frames, a + step)
+        vis = s.visibility(lt[a:b], limit) if shadows else None
+        if shadows:
+            vis_all[a:b] = vis
+        out = s._shade(lt[a:b], trace._bg(bg, dev), vis, ("image",) if maps is not None else ("depth", "mask", "instance", "image"),
+                       image[a:b])
+        maps = maps or out
+    res = {"image": image.view(n_frames, 3, S, S), "stats": s.stats()}
+    res.update({k: maps[k].view(1, 1, S, S) for k in ("mask", "depth", "instance")})
+    if shadows:
+        res["visibility"] = vis_all.view(n_frames, 1, S, S)
+    return res
+
+
 def env_walk_rotations(n_frames, axis=(0.0, 0.0, 1.0)):
     """World rotations through 360 degrees about `axis` (any non-zero length), frame 0 the identity.  -> n_frames (3, 3)
     float64 arrays."""

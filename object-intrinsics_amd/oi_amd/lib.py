@@ -1,5 +1,6 @@
 """ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h, include/oi_mesh_attr.h,
-include/oi_trace.h, include/oi_occlusion.h, include/oi_mesh_band.h, include/oi_trace_batch.h and include/oi_envlight.h).
+include/oi_trace.h, include/oi_occlusion.h, include/oi_mesh_band.h, include/oi_trace_batch.h, include/oi_envlight.h and
+include/oi_scene.h).
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -278,6 +279,28 @@ _ENVLIGHT_SIGS = {
     "oi_env_shade": (_i, [ctypes.POINTER(EnvShadeParams), _vp]),
 }
 
+# include/oi_scene.h: many instances in one scene image (an addition to oi_trace_batch.h)
+SCENE_MAX_RESOLUTION = 32768
+
+
+class SceneShadeParams(ctypes.Structure):
+    """Mirror of `oi_scene_shade_params` (include/oi_scene.h)."""
+    _fields_ = ([(n, _i) for n in ("E", "W", "S", "L")] + [("n_pad", _ll)] +
+                [(n, _vp) for n in ("owner", "owner_ray", "rays_o", "rays_d", "t", "vis_slot", "hit_points", "grad", "rgb", "w2b",
+                                    "b2w", "lights", "bg", "visibility", "depth", "position", "normal", "normal_world", "albedo",
+                                    "mask", "instance", "image")])
+
+
+_SCENE_SIGS = {
+    "oi_scene_begin": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _vp, _i, _i, _vp]),
+    "oi_scene_resolve": (_i, [ctypes.POINTER(TraceBatch), _vp, _i, _i, _vp, _vp, _vp]),
+    "oi_scene_visible": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "oi_scene_shade": (_i, [ctypes.POINTER(SceneShadeParams), _vp]),
+    "oi_scene_points": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _ll, _vp, _ll] + [_vp] * 6),
+    "oi_scene_shadow_begin": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _i, _vp, _f, _vp]),
+    "oi_scene_visibility": (_i, [_vp] * 5 + [_i, _ll, _i, _ll, _i, _vp, _vp]),
+}
+
 # entry points added by later source files (backward kernels); bound when present in the .so
 _OPTIONAL_SIGS = {}
 
@@ -325,6 +348,11 @@ def envlight_symbols():
     return sorted(_ENVLIGHT_SIGS)
 
 
+def scene_symbols():
+    """The entry points of include/oi_scene.h."""
+    return sorted(_SCENE_SIGS)
+
+
 def load():
     """Load (once) and return the ctypes handle.  Raises OiHipError when the library is missing."""
     global _lib
@@ -344,7 +372,7 @@ def load():
                 "oi_amd has no CPU or PyTorch fallback for its kernels.")
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_TRACE_SIGS, **_OCCLUSION_SIGS, **_MESH_BAND_SIGS,
-                                   **_TRACE_BATCH_SIGS, **_ENVLIGHT_SIGS, **_OPTIONAL_SIGS}.items():
+                                   **_TRACE_BATCH_SIGS, **_ENVLIGHT_SIGS, **_SCENE_SIGS, **_OPTIONAL_SIGS}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError:

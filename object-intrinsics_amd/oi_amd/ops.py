@@ -775,6 +775,106 @@ def trace_batch_gather(st, hit_index, n_pad):
 
 
 # ------------------------------------------------------------------------------------------
+# many instances in one scene image (include/oi_scene.h); oi_amd.scene sequences these around the batched march
+# ------------------------------------------------------------------------------------------
+
+def trace_batch_state_empty(E, N, ref):
+    """A TraceBatchState whose rays, near and far the begin kernel writes (oi_scene_begin, oi_scene_shadow_begin)."""
+    return TraceBatchState(E, N, _new(ref, E, N, 3), _new(ref, E, N, 3), _new(ref, E, N), _new(ref, E, N))
+
+
+def scene_begin(st, c2b, kinv, window, W, S):
+    """st: TraceBatchState of E elements x W * W rays; c2b (E, 4, 4), kinv (3, 3), window (E, 2) int32."""
+    _l.check(_l.load().oi_scene_begin(ctypes.byref(st.c), _p(c2b), _p(kinv), _ip(window), int(W), int(S), _stream()),
+             "oi_scene_begin")
+
+
+def scene_resolve(st, window, W, S):
+    """-> owner, owner_ray (S * S,) int32."""
+    # (int32 outputs through _new, the same width: the tests' guarded arenas see them)
+    owner, owner_ray = _new(st.t, S * S).view(torch.int32), _new(st.t, S * S).view(torch.int32)
+    _l.check(_l.load().oi_scene_resolve(ctypes.byref(st.c), _ip(window), int(W), int(S), _ip(owner), _ip(owner_ray), _stream()),
+             "oi_scene_resolve")
+    return owner, owner_ray
+
+
+def scene_visible(st, owner, window, W, S):
+    """-> vis_index (E, N) int32 (the first n_vis_e entries of row e are written), vis_slot (E, N) int32.  Overwrites the hit
+    words of st.counts and st.live with the visible counts."""
+    vis_index = torch.empty(st.E, st.N, dtype=torch.int32, device=st.t.device)
+    vis_slot = _new(st.t, st.E, st.N).view(torch.int32)
+    _l.check(_l.load().oi_scene_visible(ctypes.byref(st.c), _ip(owner), _ip(window), int(W), int(S), _ip(vis_index), _ip(vis_slot),
+                                        _stream()), "oi_scene_visible")
+    return vis_index, vis_slot
+
+
+SCENE_OUT = {"depth": (1,), "position": (3,), "normal": (3,), "normal_world": (3,), "albedo": (3,), "mask": (1,), "instance": (1,)}
+
+
+def scene_shade(st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_pad, w2b, b2w, lights=None, bg=None,
+                visibility=None, outputs=tuple(SCENE_OUT) + ("image",), image_out=None):
+    """The G-buffer and the Phong image of a scene (oi_scene_shade).  hit_points, grad, rgb (E, n_pad, 3) (None with n_pad ==
+    0).  -> {name: (S * S,) or (S * S, 3)} for the names of SCENE_OUT in `outputs` ("instance": int32), and "image" (L, 3,
+    S * S) (written into `image_out` when given)."""
+    M = S * S
+    for name in outputs:
+        if name not in SCENE_OUT and name != "image":
+            raise ValueError(f"scene_shade: unknown output {name!r} (one of {tuple(SCENE_OUT) + ('image',)})")
+    nl = 0 if lights is None else lights.shape[0]
+    if "image" in outputs and (nl < 1 or nl > _l.RELIGHT_MAX_LIGHTS or tuple(lights.shape[1:]) != (_l.RELIGHT_LIGHT_FLOATS,)):
+        raise ValueError(f"scene_shade: lights {None if lights is None else tuple(lights.shape)}, expected (L, "
+                         f"{_l.RELIGHT_LIGHT_FLOATS}) with 1 <= L <= {_l.RELIGHT_MAX_LIGHTS}")
+    if visibility is not None and tuple(visibility.shape) != (nl, M):
+        raise ValueError(f"scene_shade: visibility {tuple(visibility.shape)}, expected {(nl, M)}")
+    P = _l.SceneShadeParams()
+    P.E, P.W, P.S, P.L, P.n_pad = st.E, int(W), int(S), nl, int(n_pad)
+    keep = [_c(x) for x in (hit_points, grad, rgb, w2b, b2w, lights, bg, visibility)]
+    P.hit_points, P.grad, P.rgb, P.w2b, P.b2w, P.lights, P.bg, P.visibility = (_p(x) for x in keep)
+    P.rays_o, P.rays_d, P.t = _p(st.rays_o), _p(st.rays_d), _p(st.t)
+    P.owner, P.owner_ray, P.vis_slot = _ip(owner), _ip(owner_ray), _ip(vis_slot)
+    res = {}
+    for name, sh in SCENE_OUT.items():
+        if name in outputs:
+            res[name] = _new(st.t, M) if sh == (1,) else _new(st.t, M, 3)
+            if name == "instance":
+                res[name] = res[name].view(torch.int32)
+        setattr(P, name, _ip(res.get(name)))
+    if "image" in outputs:
+        if image_out is None:
+            image_out = _new(st.t, nl, 3, M)
+        elif tuple(image_out.shape) != (nl, 3, M) or not image_out.is_contiguous() or image_out.dtype != torch.float32:
+            raise ValueError(f"scene_shade: image_out must be a contiguous float32 {(nl, 3, M)} tensor")
+        res["image"] = image_out
+    P.image = _p(res.get("image"))
+    _l.check(_l.load().oi_scene_shade(ctypes.byref(P), _stream()), "oi_scene_shade")
+    return res
+
+
+def scene_points(st, hit_points, grad, n_pad, offset, n_vis, b2w, w2b):
+    """-> position, normal (n_vis, 3) in the world frame, elem (n_vis,) int32: the visible points of all elements, point
+    offset[e] + slot."""
+    pos, nrm, elem = _new(st.t, n_vis, 3), _new(st.t, n_vis, 3), _new(st.t, n_vis).view(torch.int32)
+    _l.check(_l.load().oi_scene_points(ctypes.byref(st.c), _p(hit_points), _p(grad), int(n_pad), _ip(offset), int(n_vis), _p(_c(b2w)),
+                                       _p(_c(w2b)), _p(pos), _p(nrm), _ip(elem), _stream()), "oi_scene_points")
+    return pos, nrm, elem
+
+
+def scene_shadow_begin(sb, hit_points, grad, n_pad, offset, elem, position, normal, n_vis, lights, w2b, bias):
+    """sb: TraceBatchState of E occluder elements x L * n_vis rays (trace_batch_state_empty)."""
+    _l.check(_l.load().oi_scene_shadow_begin(ctypes.byref(sb.c), _p(hit_points), _p(grad), int(n_pad), _ip(offset), _ip(elem),
+                                             _p(position), _p(normal), int(n_vis), _p(lights), lights.shape[0], _p(_c(w2b)),
+                                             float(bias), _stream()), "oi_scene_shadow_begin")
+
+
+def scene_visibility(shadow_status, owner, owner_ray, vis_slot, offset, E, N, L, n_vis, S):
+    """-> visibility (L, S * S) float32."""
+    vis = _new(owner, L, S * S)
+    _l.check(_l.load().oi_scene_visibility(_p(shadow_status), _ip(owner), _ip(owner_ray), _ip(vis_slot), _ip(offset), int(E), int(N),
+                                           int(L), int(n_vis), int(S), _p(vis), _stream()), "oi_scene_visibility")
+    return vis
+
+
+# ------------------------------------------------------------------------------------------
 # soft shadows and ambient occlusion on the traced surface (include/oi_occlusion.h)
 # ------------------------------------------------------------------------------------------
 

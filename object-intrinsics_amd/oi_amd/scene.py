@@ -1,0 +1,248 @@
+"""A scene of many instances: K latents at K rigid poses in ONE scene image of the generator's own camera -- the picture
+the model was trained from -- with occlusion between the instances and the shadows they cast on each other
+(include/oi_scene.h).
+
+    sample_scene   K latents and K poses from the generator's latent distribution and pose prior
+    trace_scene    the light-independent half: windowed scene rays with a bounding-sphere cull, ONE batched march for all
+                   instances (oi_amd.trace's, unchanged), the depth resolve across instances, the full MLP pass at the
+                   VISIBLE hits only -> SceneSurface
+    SceneSurface.shade  the scene under L lights, optionally with one shadow ray per light and visible point tested against
+                   EVERY instance
+    render_scene   both
+
+The union of K surfaces is traced exactly by tracing each instance in its own box frame and keeping the nearest hit per
+pixel: the camera is shared and the poses are rigid, so the ray parameter of one scene pixel is comparable between
+instances.  Per ray the trace is oi_amd.trace.sphere_trace's on that instance alone, bit for bit."""
+import math
+
+import numpy as np
+import torch
+
+from . import lib as _l
+from . import ops
+from . import trace as _t
+from .fields import LatentField
+
+DEFAULT_BIAS = _t.DEFAULT_BIAS
+MAX_SHADOW_RAYS = 1 << 24     # rays of one shadow batch, counted as E * L * n_vis (about 80 bytes of state each)
+
+
+def sample_scene(gen, K, seed):
+    """K instances for one scene: latents zs (K, z_dim) from the generator's latent distribution (standard normal) and poses
+    b2ws (K, 4, 4) from gen.pose_prior, both a function of `seed` alone.  The pose prior draws from numpy's global generator;
+    its state is put back."""
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= _l.TRACE_BATCH_MAX_ELEMS:
+        raise ValueError(f"sample_scene: K={K!r} instances (an integer, 1 .. {_l.TRACE_BATCH_MAX_ELEMS})")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 32:
+        raise ValueError(f"sample_scene: seed={seed!r} (an integer, 0 <= seed < 2^32)")
+    zs = torch.randn(int(K), gen.z_dim, generator=torch.Generator().manual_seed(int(seed)))
+    state = np.random.get_state()
+    try:
+        np.random.seed(int(seed))
+        b2ws = np.asarray(gen.pose_prior(int(K)), dtype=np.float32)
+    finally:
+        np.random.set_state(state)
+    return zs, torch.from_numpy(b2ws)
+
+
+def scene_windows(gen, b2ws, window=None, what="trace_scene"):
+    """The windows of the instances in the scene image, on the host in float64.  b2ws (K, 4, 4).  -> (W, origins (K, 2)
+    int64): instance e covers scene pixels (x0 + i, y0 + j), 0 <= i, j < W.  W: `window`, or the smallest value for which
+    every instance's unit sphere projects inside its window: seen from the camera the sphere's extent along x is the pair of
+    tangents tan(atan2(c_x, c_z) -+ asin(1 / hypot(c_x, c_z))) at the centre c, likewise along y; pixel X looks along
+    (X S / (S - 1) - K_02) / K_00.  The origins centre the projection in the window.
+    Refused, naming the instance: a camera inside or within 1 of an instance's unit sphere, an instance behind the camera."""
+    b2w = np.asarray(b2ws.detach().cpu() if torch.is_tensor(b2ws) else b2ws, dtype=np.float64).reshape(-1, 4, 4)
+    S = int(gen.scene_resolution)
+    Kc = gen.camera.intrinsics.detach().cpu().double().numpy()
+    w2c = gen.camera.w2c.detach().cpu().double().numpy()
+    lo, hi = np.zeros((len(b2w), 2), dtype=np.int64), np.zeros((len(b2w), 2), dtype=np.int64)
+    for e, m in enumerate(b2w):
+        c = (w2c @ m)[:3, 3]
+        if not np.isfinite(c).all():
+            raise ValueError(f"{what}: instance {e}: the pose is not finite")
+        if c[2] <= 0:
+            raise ValueError(f"{what}: instance {e} is behind the camera (depth {c[2]:.4g})")
+        if np.linalg.norm(c) < 2.0:
+            raise ValueError(f"{what}: instance {e}: the camera is inside or within 1 of its unit sphere (distance "
+                             f"{np.linalg.norm(c):.4g} from its centre, at least 2 needed)")
+        if c[2] <= 1.0:
+            raise ValueError(f"{what}: instance {e} is behind the camera (its unit sphere reaches the camera plane: depth {c[2]:.4g})")
+        for a in range(2):
+            mid, half = math.atan2(c[a], c[2]), math.asin(1.0 / math.hypot(c[a], c[2]))
+            px = [Kc[a, a] * math.tan(mid + s * half) + Kc[a, 2] for s in (-1, 1)]
+            scale = (S - 1) / S if S > 1 else 1.0
+            lo[e, a], hi[e, a] = math.floor(px[0] * scale), math.ceil(px[1] * scale)
+    if window is None:
+        W = int((hi - lo).max()) + 1
+    else:
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or int(window) < 1:
+            raise ValueError(f"{what}: window={window!r} (a positive number of scene pixels)")
+        W = int(window)
+    origin = lo - (W - (hi - lo + 1)) // 2
+    return W, origin
+
+
+class SceneSurface:
+    """One traced scene and what the light-dependent stages reuse: the batched state (rays, t, status per instance), the
+    owner map, the visible hits of every instance and the gradient and albedo there.
+    E instances, window W, scene resolution S; window (E, 2) int32; n_entered / n_hit / n_vis: per instance the rays
+    entered, the hits and the hits that own their pixel; n_pad = max(n_vis); state: ops.TraceBatchState."""
+
+    def __init__(self, gen, zs, b2ws, window, bias, trace_kw):
+        self.kw, self.bias = _t._Surface.params(bias, trace_kw, "trace_scene")
+        dev = gen.it.device
+        zs = (zs if torch.is_tensor(zs) else torch.stack([z.reshape(-1) for z in zs])).to(dev).float()
+        zs = zs.reshape(-1, zs.shape[-1])
+        b2ws = (b2ws if torch.is_tensor(b2ws) else torch.stack([torch.as_tensor(b) for b in b2ws])).float().reshape(-1, 4, 4)
+        E = zs.shape[0]
+        if b2ws.shape[0] != E or not 1 <= E <= _l.TRACE_BATCH_MAX_ELEMS:
+            raise ValueError(f"trace_scene: {E} latents and {b2ws.shape[0]} poses (one pose per latent, 1 .. "
+                             f"{_l.TRACE_BATCH_MAX_ELEMS} instances)")
+        W, origin = scene_windows(gen, b2ws, window)
+        if E * W * W >= 1 << 31:
+            raise ValueError(f"trace_scene: {E} instances x {W} x {W} window rays = {E * W * W} (E * W^2 < 2^31)")
+        S = int(gen.scene_resolution)
+        if not 1 <= S <= _l.SCENE_MAX_RESOLUTION:
+            raise ValueError(f"trace_scene: scene_resolution={S} (1 .. {_l.SCENE_MAX_RESOLUTION})")
+        self.gen, self.E, self.W, self.S, self.N = gen, E, W, S, W * W
+        self.field = LatentField(gen, zs, None, "trace_scene", batch_ok=True)
+        gen.eval()
+        self.field.prepare(zs, None)
+        prior = gen.sample_prior(E, {"b2w": b2ws.to(dev)})
+        self.b2w, self.w2b = prior["b2w"].contiguous(), prior["w2b"].contiguous()
+        self.window = torch.from_numpy(origin.astype(np.int32)).to(dev)
+        st = self.state = ops.trace_batch_state_empty(E, self.N, self.b2w)
+        ops.scene_begin(st, prior["c2b"].contiguous(), gen._kinv(dev), self.window, W, S)
+        self.n_evals = self.n_steps = self.shadow_evals = self.n_pad = 0
+        self.n_hit = self.n_vis = [0] * E
+        self.owner = self.owner_ray = self.vis_slot = self.offset = self.points = self.grad = self.rgb = None
+        self._world = self.shadow = None
+        bound = int(st.live[0].item())
+        self.n_entered = st.counts[:, 0].tolist()
+        if bound == 0:      # nothing enters a window: every ray is a MISS already
+            return
+        total, self.n_steps = _t._march_batch(self.field, st, *self.kw, bound=bound)
+        self.n_evals = total
+        hit_index, _ = ops.trace_batch_finish(st)
+        if int(st.live[-1].item()) == 0:   # nothing is hit
+            return
+        self.n_hit = st.counts[:, -1].tolist()
+        self.owner, self.owner_ray = ops.scene_resolve(st, self.window, W, S)
+        vis_index, self.vis_slot = ops.scene_visible(st, self.owner, self.window, W, S)
+        self.n_pad = int(st.live[-1].item())
+        self.n_vis = st.counts[:, -1].tolist()
+        self.points = ops.trace_batch_gather(st, vis_index, self.n_pad)
+        _, grad, rgb = self.field.full(self.points.view(E * self.n_pad, 3))
+        self.grad, self.rgb = grad.view(E, self.n_pad, 3), rgb.view(E, self.n_pad, 3)
+        self.offset = torch.tensor(np.concatenate([[0], np.cumsum(self.n_vis)[:-1]]), dtype=torch.int32, device=dev)
+
+    def world_points(self):
+        """position, normal (n_vis, 3) in the world frame and elem (n_vis,) int32 of the visible points of all instances, point
+        offset[e] + slot; computed once."""
+        if self._world is None:
+            self._world = ops.scene_points(self.state, self.points, self.grad, self.n_pad, self.offset, sum(self.n_vis), self.b2w,
+                                           self.w2b)
+        return self._world
+
+    def visibility(self, lights, max_shadow_rays=MAX_SHADOW_RAYS):
+        """(L, S * S) visibility of `lights` (L, 16): one shadow ray per light and visible point, marched against EVERY
+        instance in one batch of E occluder elements; a pixel is lit when its ray missed them all."""
+        L, n_vis = lights.shape[0], sum(self.n_vis)
+        if n_vis == 0:
+            return torch.ones(L, self.S * self.S, device=lights.device)
+        rays = self.E * L * n_vis
+        if rays > max_shadow_rays or rays >= 1 << 31:
+            raise ValueError(f"SceneSurface.shade: {self.E} instances x {L} lights x {n_vis} visible points = {rays} shadow rays "
+                             f"(at most max_shadow_rays={max_shadow_rays} and below 2^31; inference.scene_light_walk splits the lights)")
+        pos, nrm, elem = self.world_points()
+        sb = ops.trace_batch_state_empty(self.E, L * n_vis, pos)
+        ops.scene_shadow_begin(sb, self.points, self.grad, self.n_pad, self.offset, elem, pos, nrm, n_vis, lights, self.w2b, self.bias)
+        bound = int(sb.live[0].item())
+        if bound:
+            total, _ = _t._march_batch(self.field, sb, *self.kw, bound=bound)
+            self.shadow_evals += total
+            ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
+        self.shadow = sb
+        return ops.scene_visibility(sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, L, n_vis, self.S)
+
+    def _shade(self, lt, bg, vis, outputs, image_out=None):
+        """ops.scene_shade on this scene; without a visible hit nothing is launched and every map is its off-mask value."""
+        M, dev = self.S * self.S, lt.device if lt is not None else self.b2w.device
+        if self.n_pad:
+            return ops.scene_shade(self.state, self.W, self.S, self.owner, self.owner_ray, self.vis_slot, self.points, self.grad,
+                                   self.rgb, self.n_pad, self.w2b, self.b2w, lt, bg, vis, outputs, image_out)
+        res = {}
+        for k in outputs:
+            if k == "image":
+                fill = (torch.zeros(3, device=dev) if bg is None else bg).view(1, 3, 1).expand(lt.shape[0], 3, M)
+                res[k] = fill.contiguous() if image_out is None else image_out.copy_(fill)
+            elif k == "instance":
+                res[k] = torch.full((M,), -1, dtype=torch.int32, device=dev)
+            elif k == "depth":
+                res[k] = torch.full((M,), float("nan"), device=dev)
+            else:
+                res[k] = torch.zeros((M,) if ops.SCENE_OUT[k] == (1,) else (M, 3), device=dev)
+        return res
+
+    def shade(self, lights=None, shadows=False, bg=None, max_shadow_rays=MAX_SHADOW_RAYS):
+        """The scene under `lights` (oi_amd.relight.Light objects in the WORLD frame; default the generator's trained light; at
+        most RELIGHT_MAX_LIGHTS).  -> dict of image (L, 3, S, S); depth (the ray parameter; NaN off the mask), mask, instance
+        (int32, -1 off the mask) (1, 1, S, S); position (world frame), normal_map (world frame), albedo (1, 3, S, S);
+        visibility (L, 1, S, S) when `shadows` (refused above max_shadow_rays = E * L * n_vis rays); stats.  bg: (3,)
+        background colour (black when None)."""
+        from .relight import Light, stack_lights
+        dev = self.b2w.device
+        lt = stack_lights(Light.from_module(self.gen.light) if lights is None else lights, dev)
+        if lt.shape[0] > _l.RELIGHT_MAX_LIGHTS:
+            raise ValueError(f"SceneSurface.shade: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS}; inference.scene_light_walk "
+                             "splits larger sets)")
+        vis = self.visibility(lt, max_shadow_rays) if shadows else None
+        out = self._shade(lt, _t._bg(bg, dev), vis, ("depth", "position", "normal_world", "albedo", "mask", "instance", "image"))
+        S = self.S
+        res = {_MAP_NAMES[k]: v for k, v in _t._maps({k: v for k, v in out.items() if k != "image"}, S, S).items()}
+        res["image"] = out["image"].view(-1, 3, S, S)
+        if shadows:
+            res["visibility"] = vis.view(-1, 1, S, S)
+        res["stats"] = self.stats()
+        return res
+
+    def stats(self):
+        """Per instance: rays entered and culled, rays per status (culled rays are misses), hits, visible hits; sdf
+        evaluations of the primary march and of the shadow marches so far (every instance carries the batch's bound)."""
+        st = self.state
+        per = torch.stack([torch.bincount(st.status[e].long(), minlength=6)[:6] for e in range(self.E)]).tolist()
+        out = []
+        for e in range(self.E):
+            s = {name: int(per[e][code]) for code, name in _l.TRACE_STATUS_NAMES.items()}
+            s.update(n_rays=self.N, entered=int(self.n_entered[e]), culled=self.N - int(self.n_entered[e]), hits=int(self.n_hit[e]),
+                     visible=int(self.n_vis[e]), n_evals=self.n_evals, n_steps=self.n_steps, shadow_evals=self.shadow_evals)
+            out.append(s)
+        return out
+
+
+_MAP_NAMES = {"depth": "depth", "position": "position", "normal_world": "normal_map", "albedo": "albedo", "mask": "mask",
+              "instance": "instance"}
+
+
+@torch.no_grad()
+def trace_scene(gen, zs, b2ws, window=None, bias=DEFAULT_BIAS, **trace_kw):
+    """The scene of K instances of `gen` (latents zs: K of (z_dim,) or (K, z_dim); rigid poses b2ws: K of (4, 4), as
+    sample_prior takes them), 1 <= K <= 1024, in the S x S scene image of the generator's camera (S = gen.scene_resolution),
+    traced once: -> SceneSurface.  window: the side W of every instance's window in scene pixels (default: the smallest that
+    holds every unit sphere's projection; scene_windows); K * W^2 < 2^31.  trace_kw: tol, omega, max_steps, readback of
+    sphere_trace.  Refused with ValueError, naming the instance: a camera inside or within 1 of an instance's unit sphere, an
+    instance behind the camera."""
+    return SceneSurface(gen, zs, b2ws, window, bias, trace_kw)
+
+
+@torch.no_grad()
+def render_scene(gen, zs, b2ws, lights=None, shadows=False, bg=None, window=None, bias=DEFAULT_BIAS,
+                 max_shadow_rays=MAX_SHADOW_RAYS, **trace_kw):
+    """trace_scene + SceneSurface.shade: K instances in one scene image, nearer instances hiding farther ones and, with
+    `shadows`, every instance throwing its shadow on itself and on the others.  -> SceneSurface.shade's dict, with "scene" (the
+    SceneSurface)."""
+    s = trace_scene(gen, zs, b2ws, window, bias, **trace_kw)
+    res = s.shade(lights, shadows, bg, max_shadow_rays)
+    res["scene"] = s
+    return res

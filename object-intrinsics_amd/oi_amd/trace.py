@@ -152,16 +152,17 @@ class TraceResults(list):
     n_hit = ()
 
 
-def _march_batch(field, st, tol, omega, max_steps, readback):
+def _march_batch(field, st, tol, omega, max_steps, readback, bound=None):
     """_march on a state that oi_trace_batch_begin has filled: the bound is live[k] = the largest count of any element, read
-    by the same rule.  -> (sum of the bounds, steps run)."""
+    by the same rule.  bound: live[0] where a begin kernel enters only some of the rays (oi_amd.scene), else N.
+    -> (sum of the bounds, steps run)."""
     import ctypes
     L = _l.load()
     sdf = torch.empty(st.E, st.N, dtype=torch.float32, device=st.t.device)   # working memory: step k's pass writes sdf[:, :bound]
     pts_p, sdf_p, state_p, stream = ops._p(st.points), ops._p(sdf), ctypes.byref(st.c), ops._stream()
     packed_p, gamma_p, beta_p = ops._p(field.packed), ops._p(field.gamma), ops._p(field.beta)
     prec, trig, E, N = field.prec, field.fast, st.E, st.N
-    bound, total, k, since = N, 0, 0, 0
+    bound, total, k, since = (N if bound is None else int(bound)), 0, 0, 0
     while k < max_steps and bound > 0:
         rc = L.oi_sdf_mlp_fwd_segments(pts_p, packed_p, gamma_p, beta_p, sdf_p, E, bound, N, prec, trig, stream)
         if rc:

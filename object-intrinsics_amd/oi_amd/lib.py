@@ -1,6 +1,9 @@
-"""ctypes binding of liboi_hip.so (C ABI declared in include/oi_hip.h, include/oi_relight.h, include/oi_mesh_attr.h,
-include/oi_trace.h, include/oi_occlusion.h, include/oi_mesh_band.h, include/oi_trace_batch.h, include/oi_envlight.h and
-include/oi_scene.h).
+"""ctypes binding of liboi_hip.so: the C ABI that the public headers under include/ declare.
+
+SIGS is the one binding table, header file name -> {entry: (restype, argtypes)}, in the order the headers were added;
+symbols(header) lists a header's entries.  The table is the reviewed statement of the ABI on the Python side (the headers
+are not part of the installed package); tests/helpers/cabi.py holds it against the headers prototype by prototype,
+argument by argument, and the struct mirrors below field by field.
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -21,6 +24,7 @@ PRECISIONS = {"f32": OI_PREC_F32, "fp32": OI_PREC_F32, "bf16x3": OI_PREC_BF16X3,
               "bf16x6": OI_PREC_BF16X6, "f16x3": OI_PREC_F16X3}
 
 _vp, _i, _ll, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_size_t
+_u, _ull, _d, _str, _P = ctypes.c_uint, ctypes.c_ulonglong, ctypes.c_double, ctypes.c_char_p, ctypes.POINTER
 
 
 class CompositeParams(ctypes.Structure):
@@ -65,125 +69,11 @@ class CompositeGrads(ctypes.Structure):
                                    "d_sdf", "d_grad", "d_rgb", "d_variance", "d_light", "d_light_dir", "ray_partials")]
 
 
-_SIGS = {
-    "oi_version": (_i, []),
-    "oi_arch": (ctypes.c_char_p, []),
-    "oi_last_error": (ctypes.c_char_p, []),
-    "oi_film_params": (_i, [_vp] * 10 + [_i, _i, _vp]),
-    "oi_film_params_bwd": (_i, [_vp] * 16 + [_i, _i, _vp]),
-    "oi_mlp_packed_bytes": (_sz, [_i]),
-    "oi_mlp_pack_weights": (_i, [_vp] * 11 + [_i, _vp]),
-    "oi_mlp_pack_status": (_i, [_vp, _vp]),
-    "oi_mlp_scratch_bytes": (_sz, [_i, _ll]),
-    "oi_mlp_scratch_bytes_prec": (_sz, [_i, _ll, _i]),
-    "oi_sdf_mlp_fwd": (_i, [_vp] * 9 + [_i, _ll, _i, _i, _vp]),
-    "oi_sdf_mlp_fwd_ex": (_i, [_vp] * 9 + [_i, _ll, _i, _i, _i, _vp]),
-    "oi_mlp_f3_blob_offset": (_sz, [_i, _ll]),
-    "oi_mlp_f3_blob_bytes": (_sz, []),
-    "oi_selftest_sincos": (_i, [_vp, _vp, _vp, _ll, _i, _vp]),
-    "oi_selftest_q24": (_i, [_vp, _vp, _ll, _i, _vp]),
-    "oi_selftest_cu_slots": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
-    "oi_mlp_bwd_scratch_bytes": (_sz, [_i, _ll]),
-    "oi_mlp_bwd_scratch_bytes_capped": (_sz, [_i, _ll, _sz]),
-    "oi_mlp_bwd_small_floats": (_i, []),
-    "oi_sdf_mlp_bwd": (_i, [_vp] * 15 + [_sz, _i, _ll, _i, _i, _vp]),
-    "oi_sdf_mlp_bwd_feat": (_i, [_vp] * 16 + [_sz, _i, _ll, _i, _i, _vp]),
-    "oi_color_head_fwd": (_i, [_vp] * 4 + [_ll] + [_vp] * 5 + [_i, _ll, _vp]),
-    "oi_color_head_bwd_workspace_bytes": (_sz, [_i, _ll]),
-    "oi_color_head_bwd": (_i, [_vp] * 4 + [_ll] + [_vp] * 9 + [_ll] + [_vp] * 5 + [_sz, _i, _ll, _vp]),
-    "oi_composite_bwd": (_i, [ctypes.POINTER(CompositeParams), ctypes.POINTER(CompositeGrads), _vp]),
-    "oi_render_stats": (_i, [_vp, _i, _ll, _i, _vp, _vp]),
-    "oi_composite_num_blocks": (_i, [_ll]),
-    "oi_gen_rays": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "oi_gen_rays_light": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "oi_coarse_samples": (_i, [_vp] * 5 + [_ll, _i, _vp, _vp, _vp]),
-    "oi_prep_render": (_i, [_vp, _vp]),
-    "oi_upsample": (_i, [_vp] * 4 + [_ll, _i, _i, _f, _vp, _vp, _vp, _vp]),
-    "oi_upsample_mid": (_i, [_vp] * 4 + [_ll, _i, _i, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
-    "oi_merge_sorted": (_i, [_vp] * 4 + [_ll, _i, _i, _vp, _vp, _vp]),
-    "oi_midpoints": (_i, [_vp] * 3 + [_ll, _i, _f, _vp, _vp, _vp, _vp]),
-    "oi_composite_fwd": (_i, [ctypes.POINTER(CompositeParams), _vp]),
-    "oi_conv4x4_fwd": (_i, [_vp] * 4 + [_i] * 7 + [_f, _vp]),
-    "oi_conv4x4_fwd_into": (_i, [_vp] * 4 + [_i] * 7 + [_f, _f, _i, _vp]),
-    "oi_conv4x4_fwd_arena": (_i, [_vp] * 4 + [_i] * 7 + [_f, _f, _i, ctypes.c_longlong, _vp]),
-    "oi_conv4x4_dgrad": (_i, [_vp] * 3 + [_i] * 7 + [_vp]),
-    "oi_conv4x4_wgrad": (_i, [_vp] * 3 + [_i] * 7 + [_vp]),
-    "oi_conv4x4_dgrad_masked": (_i, [_vp, _vp, _f, _vp, _vp] + [_i] * 7 + [_vp]),
-    "oi_conv4x4_wgrad_masked": (_i, [_vp, _vp, _f, _vp, _vp, _i] + [_i] * 7 + [_vp]),
-    "oi_conv4x4_bwd_masked": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _i] + [_i] * 7 + [_vp]),
-    "oi_conv4x4_bwd_pre": (_i, [_vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _i] + [_i] * 7 + [_vp]),
-    "oi_conv4x4_dgrad_pre": (_i, [_vp, _vp, _vp, _f, _vp] + [_i] * 7 + [_vp]),
-    "oi_lrelu_mask_mul": (_i, [_vp] * 3 + [_ll, _f, _vp]),
-    "oi_channel_sum": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "oi_upfirdn2d": (_i, [_vp] * 3 + [_i] * 14 + [_f, _vp]),
-    "oi_ada_geom_fwd": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
-    "oi_ada_geom_sep_supported": (_i, [_i] * 3),
-    "oi_ada_geom_sep_fwd": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
-    "oi_ada_geom_sep_adj": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
-    "oi_ada_pad_up2": (_i, [_vp] * 3 + [_i] * 8 + [_vp]),
-    "oi_disc_fwd_small_workspace_floats": (_sz, [_i] * 6),
-    "oi_disc_fwd_small": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 9 + [_i] * 6 + [_f, _vp]),
-    "oi_disc_large_packed_bytes": (_sz, [_vp, _i, _i]),
-    "oi_disc_large_pack": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "oi_disc_large_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "oi_disc_fwd_large": (_i, [_vp] * 5 + [_sz, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "oi_disc_graph_create": (_i, [_vp, _i, _vp] + [_i] * 4 + [_vp] * 9 + [_i] * 6 + [_f]),
-    "oi_disc_graph_launch": (_i, [_vp, _vp, _vp, _vp]),
-    "oi_disc_fwd_small128_workspace_floats": (_sz, [_i] * 6),
-    "oi_disc_fwd_small128": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 10 + [_i] * 4 + [_f, _vp]),
-    "oi_disc_graph_create128": (_i, [_vp, _i, _vp] + [_i] * 4 + [_vp] * 10 + [_i] * 4 + [_f]),
-    "oi_disc_graph_launch_eager": (_i, [_vp, _vp, _vp, _vp, _vp]),
-    "oi_ada_theta_xint_scale": (_i, [ctypes.c_ulonglong] + [_i] * 7 + [_f] * 4 + [_vp, _vp]),
-    "oi_disc_graph_launch_ada": (_i, [_vp, _vp, ctypes.c_ulonglong, _f, _f, _f, _f, _vp, _i, _vp]),
-    "oi_disc_graph_destroy": (None, [_vp]),
-    "oi_outputs_prezeroed_stream": (_i, [_vp, _i]),
-    "oi_light_dir_fwd": (_i, [_vp, _vp, _vp, _i, _vp]),
-    "oi_light_dir_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
-    "oi_gan_losses_fwd": (_i, [_vp] * 5 + [_f, _vp, _i, _i, _ll, _vp]),
-    "oi_gan_losses_bwd": (_i, [_vp] * 6 + [_f, _vp, _vp, _vp, _i, _i, _ll, _vp]),
-    "oi_stage_inputs": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
-    "oi_render_scalars_fwd": (_i, [_vp, _f, _vp, _vp]),
-    "oi_zero_fill": (_i, [_vp, _ll, _vp]),
-    "oi_scalar_glue": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "oi_render_scalars_bwd": (_i, [_vp, _vp, _vp, _f, _vp, _vp]),
-    "oi_weighted_sum_fwd": (_i, [_vp, _vp, _i, _vp, _vp]),
-    "oi_weighted_sum_bwd": (_i, [_vp, _vp, _i, _vp, _vp]),
-    "oi_affine_grid_sample_fwd": (_i, [_vp] * 3 + [_i] * 6 + [_vp]),
-    "oi_affine_grid_sample_bwd": (_i, [_vp] * 3 + [_i] * 6 + [_vp]),
-    "oi_fused_bias_act": (_i, [_vp] * 4 + [_i, _i, _f, _f, _ll, _ll, _i, _vp]),
-    "oi_grid_sample_fwd": (_i, [_vp] * 3 + [_i] * 6 + [_vp]),
-    "oi_grid_sample_bwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
-    "oi_reflect_pad_fwd": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
-    "oi_reflect_pad_bwd": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
-    "oi_mt_chunk_elems": (_i, []),
-    "oi_multi_adam": (_i, [_vp, _i, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
-    "oi_multi_rmsprop": (_i, [_vp, _i, _f, _f, _f, _f, _vp]),
-    "oi_multi_lerp": (_i, [_vp, _i, _f, _vp]),
-    "oi_multi_copy": (_i, [_vp, _i, _vp]),
-    # mesh extraction: the reference's extract_fields point source (renderer.py:15-31) and mcubes.marching_cubes (:33-41)
-    "oi_sdf_lattice": (_i, [_vp] * 3 + [_i] + [_vp] * 3 + [_i] * 3 + [_f, _vp, _i, _i, _vp]),
-    "oi_mc_workspace_bytes": (_sz, [_i] * 3),
-    "oi_mc_count": (_i, [_vp] + [_i] * 3 + [_f, _vp, _sz, ctypes.POINTER(_ll), _vp]),
-    "oi_mc_emit": (_i, [_vp] + [_i] * 3 + [_f, _vp, _sz, _vp, _ll, _vp, _ll, _vp]),
-}
-
-# include/oi_relight.h: relighting of a captured render (no reference counterpart, so not in oi_hip.h and not in _SIGS,
-# which lists exactly what oi_hip.h declares: tests/test_cabi_cpu.py)
-_RELIGHT_SIGS = {
-    "oi_relight_fwd": (_i, [ctypes.POINTER(RelightParams), _vp]),
-}
-
-# include/oi_mesh_attr.h: the vertex pass of the intrinsic mesh export (no reference counterpart either)
+# include/oi_mesh_attr.h
 MESH_FLAG_NONFINITE, MESH_FLAG_SMALL_GRADIENT, MESH_FLAG_LIMIT = 1, 2, 4
 MESH_MAX_REFINE, MESH_RECORD_BYTES = 8, 27
-_MESH_ATTR_SIGS = {
-    "oi_mesh_vertex_world": (_i, [_vp, _ll] + [_vp] * 3 + [_i] * 3 + [_vp, _vp, _vp]),
-    "oi_mesh_newton": (_i, [_vp] * 4 + [_ll] + [_f] * 4 + [_vp, _vp, _vp]),
-    "oi_mesh_attr_finalize": (_i, [_vp] * 4 + [_ll, _f] + [_vp] * 5),
-    "oi_mesh_vertex_record": (_i, [_vp] * 3 + [_ll, _vp, _vp]),
-}
 
-# include/oi_trace.h: sphere-traced surface rendering (no reference counterpart either)
+# include/oi_trace.h
 TRACE_MISS, TRACE_HIT, TRACE_LIMIT, TRACE_START_INSIDE, TRACE_NONFINITE, TRACE_BACKFACING = 0, 1, 2, 3, 4, 5
 TRACE_MARCH, TRACE_REFINE = 16, 17
 TRACE_STATUS_NAMES = {TRACE_MISS: "miss", TRACE_HIT: "hit", TRACE_LIMIT: "limit", TRACE_START_INSIDE: "start_inside",
@@ -206,17 +96,7 @@ class SurfaceParams(ctypes.Structure):
                                     "mask", "image")])
 
 
-_TRACE_SIGS = {
-    "oi_trace_begin": (_i, [ctypes.POINTER(TraceState), _vp]),
-    "oi_trace_step": (_i, [ctypes.POINTER(TraceState), _vp, _ll, _i, _f, _f, _vp]),
-    "oi_trace_finish": (_i, [ctypes.POINTER(TraceState), _vp, _vp, _vp, _vp]),
-    "oi_trace_shadow_begin": (_i, [ctypes.POINTER(TraceState), _vp, _vp, _ll, _vp, _i, _vp, _f, _vp]),
-    "oi_trace_visibility": (_i, [_vp, _vp, _ll, _ll, _i, _vp, _vp]),
-    "oi_surface_shade": (_i, [ctypes.POINTER(SurfaceParams), _vp]),
-}
-
-# include/oi_occlusion.h: soft shadows and ambient occlusion on the traced surface (an addition to oi_trace.h; its entries
-# work on an oi_trace_state)
+# include/oi_occlusion.h
 OCCLUSION_MAX_SAMPLES = 256
 
 
@@ -225,26 +105,10 @@ class SurfaceAoParams(ctypes.Structure):
     _fields_ = SurfaceParams._fields_ + [("ambient_occlusion", _vp)]
 
 
-_u = ctypes.c_uint
-_OCCLUSION_SIGS = {
-    "oi_occlusion_light_begin": (_i, [ctypes.POINTER(TraceState), _vp, _vp, _vp, _ll, _vp, _vp, _i, _i, _vp, _f, _u, _vp]),
-    "oi_occlusion_ambient_begin": (_i, [ctypes.POINTER(TraceState), _vp, _vp, _vp, _ll, _i, _f, _f, _u, _vp]),
-    "oi_occlusion_step": (_i, [ctypes.POINTER(TraceState), _vp, _ll, _i, _f, _f, _vp]),
-    "oi_occlusion_resolve": (_i, [_vp, _vp, _ll, _ll, _i, _i, _vp, _vp]),
-    "oi_surface_shade_ao": (_i, [ctypes.POINTER(SurfaceAoParams), _vp]),
-}
-
-# include/oi_mesh_band.h: narrow-band mesh extraction (accelerates renderer.py:15-41; no reference counterpart either)
+# include/oi_mesh_band.h
 BAND_MIN_RES, BAND_MAX_RES = 2, 1024
-_d = ctypes.c_double
-_MESH_BAND_SIGS = {
-    "oi_band_workspace_bytes": (_sz, [_i] * 4),
-    "oi_band_classify": (_i, [_vp] + [_i] * 5 + [_d] * 3 + [_f, _f, _d, _vp, _vp, _sz, ctypes.POINTER(_ll),
-                                                              ctypes.POINTER(_f), _vp]),
-    "oi_sdf_lattice_band": (_i, [_vp] * 3 + [_i] + [_vp] * 3 + [_i] * 4 + [_vp, _ll, _f, _vp, _i, _i, _vp]),
-}
 
-# include/oi_trace_batch.h: E latents / views in one chain of trace steps (an addition to oi_trace.h)
+# include/oi_trace_batch.h
 TRACE_BATCH_MAX_ELEMS = 1024
 
 
@@ -253,15 +117,7 @@ class TraceBatch(ctypes.Structure):
     _fields_ = [("s", TraceState), ("E", _i), ("live", _vp)]
 
 
-_TRACE_BATCH_SIGS = {
-    "oi_sdf_mlp_fwd_segments": (_i, [_vp] * 5 + [_i, _ll, _ll, _i, _i, _vp]),
-    "oi_trace_batch_begin": (_i, [ctypes.POINTER(TraceBatch), _vp]),
-    "oi_trace_batch_step": (_i, [ctypes.POINTER(TraceBatch), _vp, _ll, _i, _f, _f, _vp]),
-    "oi_trace_batch_finish": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _vp]),
-    "oi_trace_batch_gather": (_i, [ctypes.POINTER(TraceBatch), _vp, _ll, _vp, _vp]),
-}
-
-# include/oi_envlight.h: SH environment lights and per-pixel transfer on the traced surface (an addition to oi_occlusion.h)
+# include/oi_envlight.h
 ENV_COEFFS, ENV_FLOATS, ENV_MAX_ENVS = 9, 27, 256
 
 
@@ -271,15 +127,7 @@ class EnvShadeParams(ctypes.Structure):
                 [(n, _vp) for n in ("status", "hit_slot", "rgb", "transfer", "envs", "bg", "shading", "image")])
 
 
-_ENVLIGHT_SIGS = {
-    "oi_env_project_partial_floats": (_sz, [_i, _i, _i]),
-    "oi_env_project": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
-    "oi_transfer_resolve": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, _vp, _vp]),
-    "oi_transfer_normal": (_i, [_vp, _vp, _ll, _ll, _vp, _vp, _vp]),
-    "oi_env_shade": (_i, [ctypes.POINTER(EnvShadeParams), _vp]),
-}
-
-# include/oi_scene.h: many instances in one scene image (an addition to oi_trace_batch.h)
+# include/oi_scene.h
 SCENE_MAX_RESOLUTION = 32768
 
 
@@ -291,66 +139,181 @@ class SceneShadeParams(ctypes.Structure):
                                     "mask", "instance", "image")])
 
 
-_SCENE_SIGS = {
-    "oi_scene_begin": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _vp, _i, _i, _vp]),
-    "oi_scene_resolve": (_i, [ctypes.POINTER(TraceBatch), _vp, _i, _i, _vp, _vp, _vp]),
-    "oi_scene_visible": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _i, _i, _vp, _vp, _vp]),
-    "oi_scene_shade": (_i, [ctypes.POINTER(SceneShadeParams), _vp]),
-    "oi_scene_points": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _ll, _vp, _ll] + [_vp] * 6),
-    "oi_scene_shadow_begin": (_i, [ctypes.POINTER(TraceBatch), _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _i, _vp, _f, _vp]),
-    "oi_scene_visibility": (_i, [_vp] * 5 + [_i, _ll, _i, _ll, _i, _vp, _vp]),
+SIGS = {
+    # include/oi_hip.h: the drop-in boundary, what replaces the reference's modules
+    "oi_hip.h": {
+        "oi_version": (_i, []),
+        "oi_arch": (_str, []),
+        "oi_last_error": (_str, []),
+        "oi_film_params": (_i, [_vp] * 10 + [_i, _i, _vp]),
+        "oi_film_params_bwd": (_i, [_vp] * 16 + [_i, _i, _vp]),
+        "oi_mlp_packed_bytes": (_sz, [_i]),
+        "oi_mlp_pack_weights": (_i, [_vp] * 11 + [_i, _vp]),
+        "oi_mlp_pack_status": (_i, [_vp, _vp]),
+        "oi_mlp_scratch_bytes": (_sz, [_i, _ll]),
+        "oi_mlp_scratch_bytes_prec": (_sz, [_i, _ll, _i]),
+        "oi_sdf_mlp_fwd": (_i, [_vp] * 9 + [_i, _ll, _i, _i, _vp]),
+        "oi_sdf_mlp_fwd_ex": (_i, [_vp] * 9 + [_i, _ll, _i, _i, _i, _vp]),
+        "oi_mlp_f3_blob_offset": (_sz, [_i, _ll]),
+        "oi_mlp_f3_blob_bytes": (_sz, []),
+        "oi_selftest_sincos": (_i, [_vp, _vp, _vp, _ll, _i, _vp]),
+        "oi_selftest_q24": (_i, [_vp, _vp, _ll, _i, _vp]),
+        "oi_selftest_cu_slots": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+        "oi_mlp_bwd_scratch_bytes": (_sz, [_i, _ll]),
+        "oi_mlp_bwd_scratch_bytes_capped": (_sz, [_i, _ll, _sz]),
+        "oi_mlp_bwd_small_floats": (_i, []),
+        "oi_sdf_mlp_bwd": (_i, [_vp] * 15 + [_sz, _i, _ll, _i, _i, _vp]),
+        "oi_sdf_mlp_bwd_feat": (_i, [_vp] * 16 + [_sz, _i, _ll, _i, _i, _vp]),
+        "oi_color_head_fwd": (_i, [_vp] * 4 + [_ll] + [_vp] * 5 + [_i, _ll, _vp]),
+        "oi_color_head_bwd_workspace_bytes": (_sz, [_i, _ll]),
+        "oi_color_head_bwd": (_i, [_vp] * 4 + [_ll] + [_vp] * 9 + [_ll] + [_vp] * 5 + [_sz, _i, _ll, _vp]),
+        "oi_composite_bwd": (_i, [_P(CompositeParams), _P(CompositeGrads), _vp]),
+        "oi_render_stats": (_i, [_vp, _i, _ll, _i, _vp, _vp]),
+        "oi_composite_num_blocks": (_i, [_ll]),
+        "oi_gen_rays": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+        "oi_gen_rays_light": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "oi_coarse_samples": (_i, [_vp] * 5 + [_ll, _i, _vp, _vp, _vp]),
+        "oi_prep_render": (_i, [_P(PrepParams), _vp]),
+        "oi_upsample": (_i, [_vp] * 4 + [_ll, _i, _i, _f, _vp, _vp, _vp, _vp]),
+        "oi_upsample_mid": (_i, [_vp] * 4 + [_ll, _i, _i, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+        "oi_merge_sorted": (_i, [_vp] * 4 + [_ll, _i, _i, _vp, _vp, _vp]),
+        "oi_midpoints": (_i, [_vp] * 3 + [_ll, _i, _f, _vp, _vp, _vp, _vp]),
+        "oi_composite_fwd": (_i, [_P(CompositeParams), _vp]),
+        "oi_conv4x4_fwd": (_i, [_vp] * 4 + [_i] * 7 + [_f, _vp]),
+        "oi_conv4x4_fwd_into": (_i, [_vp] * 4 + [_i] * 7 + [_f, _f, _i, _vp]),
+        "oi_conv4x4_fwd_arena": (_i, [_vp] * 4 + [_i] * 7 + [_f, _f, _i, _ll, _vp]),
+        "oi_conv4x4_dgrad": (_i, [_vp] * 3 + [_i] * 7 + [_vp]),
+        "oi_conv4x4_wgrad": (_i, [_vp] * 3 + [_i] * 7 + [_vp]),
+        "oi_conv4x4_dgrad_masked": (_i, [_vp, _vp, _f, _vp, _vp] + [_i] * 7 + [_vp]),
+        "oi_conv4x4_wgrad_masked": (_i, [_vp, _vp, _f, _vp, _vp] + [_i] * 8 + [_vp]),
+        "oi_conv4x4_bwd_masked": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp] + [_i] * 8 + [_vp]),
+        "oi_conv4x4_bwd_pre": (_i, [_vp, _vp, _f, _vp, _vp, _f, _vp, _vp] + [_i] * 8 + [_vp]),
+        "oi_conv4x4_dgrad_pre": (_i, [_vp, _vp, _vp, _f, _vp] + [_i] * 7 + [_vp]),
+        "oi_lrelu_mask_mul": (_i, [_vp] * 3 + [_ll, _f, _vp]),
+        "oi_channel_sum": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+        "oi_upfirdn2d": (_i, [_vp] * 3 + [_i] * 14 + [_f, _vp]),
+        "oi_ada_geom_fwd": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
+        "oi_ada_geom_sep_supported": (_i, [_i] * 3),
+        "oi_ada_geom_sep_fwd": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
+        "oi_ada_geom_sep_adj": (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
+        "oi_ada_pad_up2": (_i, [_vp] * 3 + [_i] * 8 + [_vp]),
+        "oi_disc_fwd_small_workspace_floats": (_sz, [_i] * 6),
+        "oi_disc_fwd_small": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 9 + [_i] * 6 + [_f, _vp]),
+        "oi_disc_large_packed_bytes": (_sz, [_vp, _i, _i]),
+        "oi_disc_large_pack": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+        "oi_disc_large_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+        "oi_disc_fwd_large": (_i, [_vp] * 5 + [_sz, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+        "oi_disc_graph_create": (_i, [_vp, _i, _vp] + [_i] * 4 + [_vp] * 9 + [_i] * 6 + [_f]),
+        "oi_disc_graph_launch": (_i, [_vp, _vp, _vp, _vp]),
+        "oi_disc_fwd_small128_workspace_floats": (_sz, [_i] * 6),
+        "oi_disc_fwd_small128": (_i, [_vp] * 4 + [_i] * 4 + [_vp] * 10 + [_i] * 4 + [_f, _vp]),
+        "oi_disc_graph_create128": (_i, [_vp, _i, _vp] + [_i] * 4 + [_vp] * 10 + [_i] * 4 + [_f]),
+        "oi_disc_graph_launch_eager": (_i, [_vp, _vp, _vp, _vp, _vp]),
+        "oi_ada_theta_xint_scale": (_i, [_ull] + [_i] * 7 + [_f] * 4 + [_vp, _vp]),
+        "oi_disc_graph_launch_ada": (_i, [_vp, _vp, _ull, _f, _f, _f, _f, _vp, _i, _vp]),
+        "oi_disc_graph_destroy": (None, [_vp]),
+        "oi_outputs_prezeroed_stream": (_i, [_vp, _i]),
+        "oi_light_dir_fwd": (_i, [_vp, _vp, _vp, _i, _vp]),
+        "oi_light_dir_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+        "oi_gan_losses_fwd": (_i, [_vp] * 5 + [_f, _vp, _i, _i, _ll, _vp]),
+        "oi_gan_losses_bwd": (_i, [_vp] * 6 + [_f, _vp, _vp, _vp, _i, _i, _ll, _vp]),
+        "oi_stage_inputs": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+        "oi_render_scalars_fwd": (_i, [_vp, _f, _vp, _vp]),
+        "oi_zero_fill": (_i, [_vp, _ll, _vp]),
+        "oi_scalar_glue": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+        "oi_render_scalars_bwd": (_i, [_vp, _vp, _vp, _f, _vp, _vp]),
+        "oi_weighted_sum_fwd": (_i, [_vp, _vp, _i, _vp, _vp]),
+        "oi_weighted_sum_bwd": (_i, [_vp, _vp, _i, _vp, _vp]),
+        "oi_affine_grid_sample_fwd": (_i, [_vp] * 3 + [_i] * 6 + [_vp]),
+        "oi_affine_grid_sample_bwd": (_i, [_vp] * 3 + [_i] * 6 + [_vp]),
+        "oi_fused_bias_act": (_i, [_vp] * 4 + [_i, _i, _f, _f, _ll, _ll, _i, _vp]),
+        "oi_grid_sample_fwd": (_i, [_vp] * 3 + [_i] * 6 + [_vp]),
+        "oi_grid_sample_bwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
+        "oi_reflect_pad_fwd": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
+        "oi_reflect_pad_bwd": (_i, [_vp, _vp] + [_i] * 7 + [_vp]),
+        "oi_mt_chunk_elems": (_i, []),
+        "oi_multi_adam": (_i, [_vp, _i, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
+        "oi_multi_rmsprop": (_i, [_vp, _i, _f, _f, _f, _f, _vp]),
+        "oi_multi_lerp": (_i, [_vp, _i, _f, _vp]),
+        "oi_multi_copy": (_i, [_vp, _i, _vp]),
+        # mesh extraction: the reference's extract_fields point source (renderer.py:15-31) and mcubes.marching_cubes (:33-41)
+        "oi_sdf_lattice": (_i, [_vp] * 3 + [_i] + [_vp] * 3 + [_i] * 3 + [_f, _vp, _i, _i, _vp]),
+        "oi_mc_workspace_bytes": (_sz, [_i] * 3),
+        "oi_mc_count": (_i, [_vp] + [_i] * 3 + [_f, _vp, _sz, _P(_ll), _vp]),
+        "oi_mc_emit": (_i, [_vp] + [_i] * 3 + [_f, _vp, _sz, _vp, _ll, _vp, _ll, _vp]),
+    },
+    # include/oi_relight.h: relighting of a captured render (no reference counterpart, so not in oi_hip.h)
+    "oi_relight.h": {
+        "oi_relight_fwd": (_i, [_P(RelightParams), _vp]),
+    },
+    # include/oi_mesh_attr.h: the vertex pass of the intrinsic mesh export (no reference counterpart either)
+    "oi_mesh_attr.h": {
+        "oi_mesh_vertex_world": (_i, [_vp, _ll] + [_vp] * 3 + [_i] * 3 + [_vp, _vp, _vp]),
+        "oi_mesh_newton": (_i, [_vp] * 4 + [_ll] + [_f] * 4 + [_vp, _vp, _vp]),
+        "oi_mesh_attr_finalize": (_i, [_vp] * 4 + [_ll, _f] + [_vp] * 5),
+        "oi_mesh_vertex_record": (_i, [_vp] * 3 + [_ll, _vp, _vp]),
+    },
+    # include/oi_trace.h: sphere-traced surface rendering (no reference counterpart either)
+    "oi_trace.h": {
+        "oi_trace_begin": (_i, [_P(TraceState), _vp]),
+        "oi_trace_step": (_i, [_P(TraceState), _vp, _ll, _i, _f, _f, _vp]),
+        "oi_trace_finish": (_i, [_P(TraceState), _vp, _vp, _vp, _vp]),
+        "oi_trace_shadow_begin": (_i, [_P(TraceState), _vp, _vp, _ll, _vp, _i, _vp, _f, _vp]),
+        "oi_trace_visibility": (_i, [_vp, _vp, _ll, _ll, _i, _vp, _vp]),
+        "oi_surface_shade": (_i, [_P(SurfaceParams), _vp]),
+    },
+    # include/oi_occlusion.h: soft shadows and ambient occlusion on the traced surface (an addition to oi_trace.h; its
+    # entries work on an oi_trace_state)
+    "oi_occlusion.h": {
+        "oi_occlusion_light_begin": (_i, [_P(TraceState), _vp, _vp, _vp, _ll, _vp, _vp, _i, _i, _vp, _f, _u, _vp]),
+        "oi_occlusion_ambient_begin": (_i, [_P(TraceState), _vp, _vp, _vp, _ll, _i, _f, _f, _u, _vp]),
+        "oi_occlusion_step": (_i, [_P(TraceState), _vp, _ll, _i, _f, _f, _vp]),
+        "oi_occlusion_resolve": (_i, [_vp, _vp, _ll, _ll, _i, _i, _vp, _vp]),
+        "oi_surface_shade_ao": (_i, [_P(SurfaceAoParams), _vp]),
+    },
+    # include/oi_mesh_band.h: narrow-band mesh extraction (accelerates renderer.py:15-41; no reference counterpart either)
+    "oi_mesh_band.h": {
+        "oi_band_workspace_bytes": (_sz, [_i] * 4),
+        "oi_band_classify": (_i, [_vp] + [_i] * 5 + [_d] * 3 + [_f, _f, _d, _vp, _vp, _sz, _P(_ll), _P(_f), _vp]),
+        "oi_sdf_lattice_band": (_i, [_vp] * 3 + [_i] + [_vp] * 3 + [_i] * 4 + [_vp, _ll, _f, _vp, _i, _i, _vp]),
+    },
+    # include/oi_trace_batch.h: E latents / views in one chain of trace steps (an addition to oi_trace.h)
+    "oi_trace_batch.h": {
+        "oi_sdf_mlp_fwd_segments": (_i, [_vp] * 5 + [_i, _ll, _ll, _i, _i, _vp]),
+        "oi_trace_batch_begin": (_i, [_P(TraceBatch), _vp]),
+        "oi_trace_batch_step": (_i, [_P(TraceBatch), _vp, _ll, _i, _f, _f, _vp]),
+        "oi_trace_batch_finish": (_i, [_P(TraceBatch), _vp, _vp, _vp]),
+        "oi_trace_batch_gather": (_i, [_P(TraceBatch), _vp, _ll, _vp, _vp]),
+    },
+    # include/oi_envlight.h: SH environment lights and per-pixel transfer on the traced surface (an addition to
+    # oi_occlusion.h)
+    "oi_envlight.h": {
+        "oi_env_project_partial_floats": (_sz, [_i, _i, _i]),
+        "oi_env_project": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+        "oi_transfer_resolve": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _vp, _vp, _vp]),
+        "oi_transfer_normal": (_i, [_vp, _vp, _ll, _ll, _vp, _vp, _vp]),
+        "oi_env_shade": (_i, [_P(EnvShadeParams), _vp]),
+    },
+    # include/oi_scene.h: many instances in one scene image (an addition to oi_trace_batch.h)
+    "oi_scene.h": {
+        "oi_scene_begin": (_i, [_P(TraceBatch), _vp, _vp, _vp, _i, _i, _vp]),
+        "oi_scene_resolve": (_i, [_P(TraceBatch), _vp, _i, _i, _vp, _vp, _vp]),
+        "oi_scene_visible": (_i, [_P(TraceBatch), _vp, _vp, _i, _i, _vp, _vp, _vp]),
+        "oi_scene_shade": (_i, [_P(SceneShadeParams), _vp]),
+        "oi_scene_points": (_i, [_P(TraceBatch), _vp, _vp, _ll, _vp, _ll] + [_vp] * 6),
+        "oi_scene_shadow_begin": (_i, [_P(TraceBatch), _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _i, _vp, _f, _vp]),
+        "oi_scene_visibility": (_i, [_vp] * 5 + [_i, _ll, _i, _ll, _i, _vp, _vp]),
+    },
 }
-
-# entry points added by later source files (backward kernels); bound when present in the .so
-_OPTIONAL_SIGS = {}
 
 
 class OiHipError(RuntimeError):
     pass
 
 
-def declared_symbols():
-    return sorted(_SIGS)
-
-
-def relight_symbols():
-    """The entry points of include/oi_relight.h."""
-    return sorted(_RELIGHT_SIGS)
-
-
-def mesh_attr_symbols():
-    """The entry points of include/oi_mesh_attr.h."""
-    return sorted(_MESH_ATTR_SIGS)
-
-
-def trace_symbols():
-    """The entry points of include/oi_trace.h."""
-    return sorted(_TRACE_SIGS)
-
-
-def occlusion_symbols():
-    """The entry points of include/oi_occlusion.h."""
-    return sorted(_OCCLUSION_SIGS)
-
-
-def mesh_band_symbols():
-    """The entry points of include/oi_mesh_band.h."""
-    return sorted(_MESH_BAND_SIGS)
-
-
-def trace_batch_symbols():
-    """The entry points of include/oi_trace_batch.h."""
-    return sorted(_TRACE_BATCH_SIGS)
-
-
-def envlight_symbols():
-    """The entry points of include/oi_envlight.h."""
-    return sorted(_ENVLIGHT_SIGS)
-
-
-def scene_symbols():
-    """The entry points of include/oi_scene.h."""
-    return sorted(_SCENE_SIGS)
+def symbols(header):
+    """The entry points that include/<header> declares, sorted."""
+    return sorted(SIGS[header])
 
 
 def load():
@@ -371,16 +334,14 @@ def load():
                 f"{LIB_PATH} not found: build it with `python object-intrinsics_amd/build.py` (hipcc, gfx950). "
                 "oi_amd has no CPU or PyTorch fallback for its kernels.")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_RELIGHT_SIGS, **_MESH_ATTR_SIGS, **_TRACE_SIGS, **_OCCLUSION_SIGS, **_MESH_BAND_SIGS,
-                                   **_TRACE_BATCH_SIGS, **_ENVLIGHT_SIGS, **_SCENE_SIGS, **_OPTIONAL_SIGS}.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                if name in _OPTIONAL_SIGS:
-                    continue
-                raise OiHipError(f"{LIB_PATH} does not export {name}; rebuild the library")
-            fn.restype = res
-            fn.argtypes = args
+        for entries in SIGS.values():
+            for name, (res, args) in entries.items():
+                try:
+                    fn = getattr(lib, name)
+                except AttributeError:
+                    raise OiHipError(f"{LIB_PATH} does not export {name}; rebuild the library")
+                fn.restype = res
+                fn.argtypes = args
         _lib = lib
     return _lib
 

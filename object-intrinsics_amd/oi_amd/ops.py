@@ -600,31 +600,33 @@ def _ip(t):
     return _vp(t.data_ptr())
 
 
+def _ray_state(st, S, lead, N, ref, rays_o, rays_d, near, far):
+    """The arrays of an oi_trace_state of N rays under the leading shape `lead` (() for TraceState, (E,) for
+    TraceBatchState) as attributes of `st`, and their pointers in the struct S.  t is an output (ops._new); status (uint8)
+    and steps (int16: the header's uint16, at most 1024) are outputs too; the rest is working memory.  rays_o, rays_d, near,
+    far: the caller's, or None to allocate them (ref: any tensor on the device)."""
+    e = lambda *sh, dt=torch.float32: torch.empty(lead + sh, dtype=dt, device=ref.device)
+    own = lambda x, *sh: _c(x).reshape(lead + sh) if x is not None else e(*sh)
+    st.N = int(N)
+    st.rays_o, st.rays_d, st.near, st.far = own(rays_o, N, 3), own(rays_d, N, 3), own(near, N), own(far, N)
+    st.t = _new(ref, *lead, N)
+    st.status, st.steps = e(N, dt=torch.uint8), e(N, dt=torch.int16)
+    st.bracket, st.side = e(N, 4), e(N, dt=torch.uint8)
+    st.active, st.points = e(2, N, dt=torch.int32), e(N, 3)
+    st.counts = e(_l.TRACE_COUNT_WORDS, dt=torch.int32)
+    S.N = st.N
+    S.rays_o, S.rays_d, S.near_, S.far_ = _p(st.rays_o), _p(st.rays_d), _p(st.near), _p(st.far)
+    S.t, S.status, S.steps, S.bracket, S.side = _p(st.t), _p(st.status), _ip(st.steps), _p(st.bracket), _p(st.side)
+    S.active, S.points, S.counts = _ip(st.active), _p(st.points), _ip(st.counts)
+
+
 class TraceState:
-    """The arrays of one oi_trace_state for N rays.  t (N,) float32 is an output (ops._new); status (N,) uint8, steps (N,)
-    int16 (the header's uint16: at most 1024) are outputs too; the rest is working memory.  rays_o / rays_d (N, 3), near /
-    far (N,): the caller's for a primary trace, allocated here for a shadow trace (ref: any tensor on the device)."""
+    """The arrays of one oi_trace_state for N rays (_ray_state).  rays_o / rays_d (N, 3), near / far (N,): the caller's for a
+    primary trace, allocated here for a shadow trace (ref: any tensor on the device)."""
 
     def __init__(self, N, rays_o=None, rays_d=None, near=None, far=None, ref=None):
-        ref = rays_o if rays_o is not None else ref
-        dev = ref.device
-        e = lambda *sh, dt=torch.float32: torch.empty(sh, dtype=dt, device=dev)
-        self.N = int(N)
-        self.rays_o = _c(rays_o).reshape(N, 3) if rays_o is not None else e(N, 3)
-        self.rays_d = _c(rays_d).reshape(N, 3) if rays_d is not None else e(N, 3)
-        self.near = _c(near).reshape(N) if near is not None else e(N)
-        self.far = _c(far).reshape(N) if far is not None else e(N)
-        self.t = _new(ref, N)
-        self.status = e(N, dt=torch.uint8)
-        self.steps = e(N, dt=torch.int16)
-        self.bracket, self.side = e(N, 4), e(N, dt=torch.uint8)
-        self.active, self.points = e(2, N, dt=torch.int32), e(N, 3)
-        self.counts = e(_l.TRACE_COUNT_WORDS, dt=torch.int32)
-        S = self.c = _l.TraceState()
-        S.N = self.N
-        S.rays_o, S.rays_d, S.near_, S.far_ = _p(self.rays_o), _p(self.rays_d), _p(self.near), _p(self.far)
-        S.t, S.status, S.steps, S.bracket, S.side = _p(self.t), _p(self.status), _ip(self.steps), _p(self.bracket), _p(self.side)
-        S.active, S.points, S.counts = _ip(self.active), _p(self.points), _ip(self.counts)
+        self.c = _l.TraceState()
+        _ray_state(self, self.c, (), N, rays_o if rays_o is not None else ref, rays_o, rays_d, near, far)
 
 
 def trace_begin(st):
@@ -667,32 +669,43 @@ def _surface_shade(what, P, rays_o, rays_d, t, status, hit_slot, hit_points, gra
                    outputs, image_out):
     """The arguments surface_shade and surface_shade_ao share, filled into the struct P.  -> (outputs, tensors to keep)."""
     N = t.shape[0]
+    res = _shade_planes(what, SURFACE_OUT, P, N, t, outputs, lights, visibility, image_out)
+    P.N, P.n_hit = N, int(n_hit)
+    keep = [_c(x) for x in (rays_o, rays_d, t, hit_points, grad, rgb, w2b, lights, bg, visibility)]
+    (P.rays_o, P.rays_d, P.t, P.hit_points, P.grad, P.rgb, P.w2b, P.lights, P.bg, P.visibility) = (_p(x) for x in keep)
+    P.status, P.hit_slot = _p(status), _ip(hit_slot)
+    return res, keep
+
+
+def _shade_planes(what, table, P, M, ref, outputs, lights, visibility, image_out):
+    """What the shade entries share, for M pixels and the output table `table` (SURFACE_OUT or SCENE_OUT): the checks of
+    `outputs`, the lights, the visibility's shape and `image_out`, and the output planes, whose pointers and L go into the
+    struct P.  -> {name: plane} of (M,) or (M, 3) for the names of `table` in `outputs` ("instance": int32) and "image"
+    (L, 3, M) (`image_out` when given)."""
     for name in outputs:
-        if name not in SURFACE_OUT and name != "image":
-            raise ValueError(f"{what}: unknown output {name!r} (one of {tuple(SURFACE_OUT) + ('image',)})")
+        if name not in table and name != "image":
+            raise ValueError(f"{what}: unknown output {name!r} (one of {tuple(table) + ('image',)})")
     nl = 0 if lights is None else lights.shape[0]
     if "image" in outputs and (nl < 1 or nl > _l.RELIGHT_MAX_LIGHTS or tuple(lights.shape[1:]) != (_l.RELIGHT_LIGHT_FLOATS,)):
         raise ValueError(f"{what}: lights {None if lights is None else tuple(lights.shape)}, expected (L, "
                          f"{_l.RELIGHT_LIGHT_FLOATS}) with 1 <= L <= {_l.RELIGHT_MAX_LIGHTS}")
-    if visibility is not None and tuple(visibility.shape) != (nl, N):
-        raise ValueError(f"{what}: visibility {tuple(visibility.shape)}, expected {(nl, N)}")
-    P.N, P.n_hit, P.L = N, int(n_hit), nl
-    keep = [_c(x) for x in (rays_o, rays_d, t, hit_points, grad, rgb, w2b, lights, bg, visibility)]
-    (P.rays_o, P.rays_d, P.t, P.hit_points, P.grad, P.rgb, P.w2b, P.lights, P.bg, P.visibility) = (_p(x) for x in keep)
-    P.status, P.hit_slot = _p(status), _ip(hit_slot)
-    res = {}
-    for name, sh in SURFACE_OUT.items():
+    if visibility is not None and tuple(visibility.shape) != (nl, M):
+        raise ValueError(f"{what}: visibility {tuple(visibility.shape)}, expected {(nl, M)}")
+    P.L, res = nl, {}
+    for name, sh in table.items():
         if name in outputs:
-            res[name] = _new(t, N) if sh == (1,) else _new(t, N, 3)
-        setattr(P, name, _p(res.get(name)))
+            res[name] = _new(ref, M) if sh == (1,) else _new(ref, M, 3)
+            if name == "instance":
+                res[name] = res[name].view(torch.int32)
+        setattr(P, name, _ip(res.get(name)))
     if "image" in outputs:
         if image_out is None:
-            image_out = _new(t, nl, 3, N)
-        elif tuple(image_out.shape) != (nl, 3, N) or not image_out.is_contiguous() or image_out.dtype != torch.float32:
-            raise ValueError(f"{what}: image_out must be a contiguous float32 {(nl, 3, N)} tensor")
+            image_out = _new(ref, nl, 3, M)
+        elif tuple(image_out.shape) != (nl, 3, M) or not image_out.is_contiguous() or image_out.dtype != torch.float32:
+            raise ValueError(f"{what}: image_out must be a contiguous float32 {(nl, 3, M)} tensor")
         res["image"] = image_out
     P.image = _p(res.get("image"))
-    return res, keep
+    return res
 
 
 def surface_shade(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b, lights=None, bg=None,
@@ -722,29 +735,14 @@ def sdf_mlp_fwd_segments(pts, packed, gamma, beta, sdf, B, n_per_elem, prec, fas
 
 class TraceBatchState:
     """The arrays of one oi_trace_batch: E elements of N rays each, every array of TraceState with a leading element
-    dimension, counts (E, TRACE_COUNT_WORDS) and live (TRACE_COUNT_WORDS,) int32.  rays_o / rays_d (E, N, 3), near / far
-    (E, N) are the caller's.  t (E, N) is an output (ops._new), status and steps are outputs too; the rest is working memory."""
+    dimension (_ray_state), so counts (E, TRACE_COUNT_WORDS), and live (TRACE_COUNT_WORDS,) int32.  rays_o / rays_d (E, N, 3),
+    near / far (E, N) are the caller's."""
 
     def __init__(self, E, N, rays_o, rays_d, near, far):
-        dev = rays_o.device
-        e = lambda *sh, dt=torch.float32: torch.empty(sh, dtype=dt, device=dev)
-        self.E, self.N = int(E), int(N)
-        self.rays_o, self.rays_d = _c(rays_o).reshape(E, N, 3), _c(rays_d).reshape(E, N, 3)
-        self.near, self.far = _c(near).reshape(E, N), _c(far).reshape(E, N)
-        self.t = _new(rays_o, E, N)
-        self.status = e(E, N, dt=torch.uint8)
-        self.steps = e(E, N, dt=torch.int16)
-        self.bracket, self.side = e(E, N, 4), e(E, N, dt=torch.uint8)
-        self.active, self.points = e(E, 2, N, dt=torch.int32), e(E, N, 3)
-        self.counts = e(E, _l.TRACE_COUNT_WORDS, dt=torch.int32)
-        self.live = e(_l.TRACE_COUNT_WORDS, dt=torch.int32)
-        B = self.c = _l.TraceBatch()
-        S = B.s
-        S.N = self.N
-        S.rays_o, S.rays_d, S.near_, S.far_ = _p(self.rays_o), _p(self.rays_d), _p(self.near), _p(self.far)
-        S.t, S.status, S.steps, S.bracket, S.side = _p(self.t), _p(self.status), _ip(self.steps), _p(self.bracket), _p(self.side)
-        S.active, S.points, S.counts = _ip(self.active), _p(self.points), _ip(self.counts)
-        B.E, B.live = self.E, _ip(self.live)
+        self.E, self.c = int(E), _l.TraceBatch()
+        _ray_state(self, self.c.s, (self.E,), N, rays_o, rays_o, rays_d, near, far)
+        self.live = torch.empty(_l.TRACE_COUNT_WORDS, dtype=torch.int32, device=rays_o.device)
+        self.c.E, self.c.live = self.E, _ip(self.live)
 
 
 def trace_batch_begin(st):
@@ -816,36 +814,13 @@ def scene_shade(st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_p
     """The G-buffer and the Phong image of a scene (oi_scene_shade).  hit_points, grad, rgb (E, n_pad, 3) (None with n_pad ==
     0).  -> {name: (S * S,) or (S * S, 3)} for the names of SCENE_OUT in `outputs` ("instance": int32), and "image" (L, 3,
     S * S) (written into `image_out` when given)."""
-    M = S * S
-    for name in outputs:
-        if name not in SCENE_OUT and name != "image":
-            raise ValueError(f"scene_shade: unknown output {name!r} (one of {tuple(SCENE_OUT) + ('image',)})")
-    nl = 0 if lights is None else lights.shape[0]
-    if "image" in outputs and (nl < 1 or nl > _l.RELIGHT_MAX_LIGHTS or tuple(lights.shape[1:]) != (_l.RELIGHT_LIGHT_FLOATS,)):
-        raise ValueError(f"scene_shade: lights {None if lights is None else tuple(lights.shape)}, expected (L, "
-                         f"{_l.RELIGHT_LIGHT_FLOATS}) with 1 <= L <= {_l.RELIGHT_MAX_LIGHTS}")
-    if visibility is not None and tuple(visibility.shape) != (nl, M):
-        raise ValueError(f"scene_shade: visibility {tuple(visibility.shape)}, expected {(nl, M)}")
     P = _l.SceneShadeParams()
-    P.E, P.W, P.S, P.L, P.n_pad = st.E, int(W), int(S), nl, int(n_pad)
+    res = _shade_planes("scene_shade", SCENE_OUT, P, S * S, st.t, outputs, lights, visibility, image_out)
+    P.E, P.W, P.S, P.n_pad = st.E, int(W), int(S), int(n_pad)
     keep = [_c(x) for x in (hit_points, grad, rgb, w2b, b2w, lights, bg, visibility)]
     P.hit_points, P.grad, P.rgb, P.w2b, P.b2w, P.lights, P.bg, P.visibility = (_p(x) for x in keep)
     P.rays_o, P.rays_d, P.t = _p(st.rays_o), _p(st.rays_d), _p(st.t)
     P.owner, P.owner_ray, P.vis_slot = _ip(owner), _ip(owner_ray), _ip(vis_slot)
-    res = {}
-    for name, sh in SCENE_OUT.items():
-        if name in outputs:
-            res[name] = _new(st.t, M) if sh == (1,) else _new(st.t, M, 3)
-            if name == "instance":
-                res[name] = res[name].view(torch.int32)
-        setattr(P, name, _ip(res.get(name)))
-    if "image" in outputs:
-        if image_out is None:
-            image_out = _new(st.t, nl, 3, M)
-        elif tuple(image_out.shape) != (nl, 3, M) or not image_out.is_contiguous() or image_out.dtype != torch.float32:
-            raise ValueError(f"scene_shade: image_out must be a contiguous float32 {(nl, 3, M)} tensor")
-        res["image"] = image_out
-    P.image = _p(res.get("image"))
     _l.check(_l.load().oi_scene_shade(ctypes.byref(P), _stream()), "oi_scene_shade")
     return res
 

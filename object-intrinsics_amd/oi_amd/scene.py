@@ -31,10 +31,9 @@ def sample_scene(gen, K, seed):
     """K instances for one scene: latents zs (K, z_dim) from the generator's latent distribution (standard normal) and poses
     b2ws (K, 4, 4) from gen.pose_prior, both a function of `seed` alone.  The pose prior draws from numpy's global generator;
     its state is put back."""
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= _l.TRACE_BATCH_MAX_ELEMS:
+    if not _t._is_count(K, 1, _l.TRACE_BATCH_MAX_ELEMS):
         raise ValueError(f"sample_scene: K={K!r} instances (an integer, 1 .. {_l.TRACE_BATCH_MAX_ELEMS})")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 32:
-        raise ValueError(f"sample_scene: seed={seed!r} (an integer, 0 <= seed < 2^32)")
+    _t._check_seed(seed, "sample_scene")
     zs = torch.randn(int(K), gen.z_dim, generator=torch.Generator().manual_seed(int(seed)))
     state = np.random.get_state()
     try:
@@ -92,8 +91,7 @@ class SceneSurface:
     def __init__(self, gen, zs, b2ws, window, bias, trace_kw):
         self.kw, self.bias = _t._Surface.params(bias, trace_kw, "trace_scene")
         dev = gen.it.device
-        zs = (zs if torch.is_tensor(zs) else torch.stack([z.reshape(-1) for z in zs])).to(dev).float()
-        zs = zs.reshape(-1, zs.shape[-1])
+        zs = _t._latents(zs, dev)
         b2ws = (b2ws if torch.is_tensor(b2ws) else torch.stack([torch.as_tensor(b) for b in b2ws])).float().reshape(-1, 4, 4)
         E = zs.shape[0]
         if b2ws.shape[0] != E or not 1 <= E <= _l.TRACE_BATCH_MAX_ELEMS:
@@ -191,12 +189,8 @@ class SceneSurface:
         (int32, -1 off the mask) (1, 1, S, S); position (world frame), normal_map (world frame), albedo (1, 3, S, S);
         visibility (L, 1, S, S) when `shadows` (refused above max_shadow_rays = E * L * n_vis rays); stats.  bg: (3,)
         background colour (black when None)."""
-        from .relight import Light, stack_lights
         dev = self.b2w.device
-        lt = stack_lights(Light.from_module(self.gen.light) if lights is None else lights, dev)
-        if lt.shape[0] > _l.RELIGHT_MAX_LIGHTS:
-            raise ValueError(f"SceneSurface.shade: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS}; inference.scene_light_walk "
-                             "splits larger sets)")
+        lt = _t._stack_lights(self.gen, lights, dev, "SceneSurface.shade", "; inference.scene_light_walk splits larger sets")
         vis = self.visibility(lt, max_shadow_rays) if shadows else None
         out = self._shade(lt, _t._bg(bg, dev), vis, ("depth", "position", "normal_world", "albedo", "mask", "instance", "image"))
         S = self.S

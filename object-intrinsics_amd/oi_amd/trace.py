@@ -19,6 +19,7 @@ The loop runs on the host: oi_trace_begin, then per step the library's sdf-only 
 flight and oi_trace_step, which advances them and compacts the survivors.  The number of rays in flight lives on the device;
 the host launches each pass on the last count it read (a valid upper bound: the count never grows) and reads the count back
 every step while more than READBACK_DENSE rays were in flight, every READBACK_SPARSE steps after that."""
+import ctypes
 import dataclasses
 from typing import Optional
 
@@ -72,32 +73,40 @@ def _check_params(tol, omega, max_steps, readback, what):
 
 
 def _march(field, st, bound, tol, omega, max_steps, readback, anyhit=False):
-    """The loop on a state that oi_trace_begin / oi_trace_shadow_begin / oi_occlusion_*_begin has filled.  -> (points
-    evaluated, steps run).  anyhit: step with oi_occlusion_step (a ray ends at its first occluder) instead of oi_trace_step.
-    Two launches per step through the C ABI directly, with the pointers converted once: the loop's tail is a handful of rays
-    per step, where the host's time per launch is the frame's time."""
-    import ctypes
+    """The one march loop, on a state that a begin entry has filled.  -> (sum of the bounds = points evaluated, per element
+    of a batch; steps run).  An ops.TraceState steps with oi_trace_step -- anyhit: oi_occlusion_step, a ray ends at its first
+    occluder -- after oi_sdf_mlp_fwd with B = 1 on the first `bound` points, and reads counts[k]; an ops.TraceBatchState steps
+    with oi_trace_batch_step after oi_sdf_mlp_fwd_segments on the first `bound` points of each of its E segments of N, and
+    reads live[k], the largest count of any element.  Two launches per step through the C ABI directly, the pointers converted
+    and these differences bound once, before the loop: its tail is a handful of rays per step, where the host's time per
+    launch is the frame's time."""
     L = _l.load()
-    sdf = torch.empty(st.N, dtype=torch.float32, device=st.t.device)   # working memory: step k's pass writes sdf[:bound]
+    sdf = torch.empty(st.t.shape, dtype=torch.float32, device=st.t.device)   # working memory: step k's pass writes the first `bound`
     pts_p, sdf_p, state_p, stream = ops._p(st.points), ops._p(sdf), ctypes.byref(st.c), ops._stream()
-    packed_p, gamma_p, beta_p = ops._p(field.packed), ops._p(field.gamma), ops._p(field.beta)
-    prec, trig = field.prec, field.fast
-    step, step_name = (L.oi_occlusion_step, "oi_occlusion_step") if anyhit else (L.oi_trace_step, "oi_trace_step")
-    n_evals = k = since = 0
+    mlp_args = [pts_p, ops._p(field.packed), ops._p(field.gamma), ops._p(field.beta), sdf_p]
+    if isinstance(st, ops.TraceBatchState):
+        mlp_name, step_name, counter = "oi_sdf_mlp_fwd_segments", "oi_trace_batch_step", st.live
+        mlp_args, at = mlp_args + [st.E, bound, st.N, field.prec, field.fast, stream], 6       # at: where the bound goes
+    else:
+        mlp_name, step_name, counter = "oi_sdf_mlp_fwd", "oi_occlusion_step" if anyhit else "oi_trace_step", st.counts
+        mlp_args, at = mlp_args + [None, None, None, None, 1, bound, field.prec, field.fast, stream], 10
+    mlp, step = getattr(L, mlp_name), getattr(L, step_name)
+    total = k = since = 0
     while k < max_steps and bound > 0:
-        rc = L.oi_sdf_mlp_fwd(pts_p, packed_p, gamma_p, beta_p, sdf_p, None, None, None, None, 1, bound, prec, trig, stream)
+        mlp_args[at] = bound
+        rc = mlp(*mlp_args)
         if rc:
-            _l.check(rc, "oi_sdf_mlp_fwd")
+            _l.check(rc, mlp_name)
         rc = step(state_p, sdf_p, bound, k, tol, omega, stream)
         if rc:
             _l.check(rc, step_name)
-        n_evals += bound
+        total += bound
         k += 1
         since += 1
         every = (1 if bound > READBACK_DENSE else READBACK_SPARSE) if readback == "auto" else int(readback)
         if since >= every and k < max_steps:
-            bound, since = int(st.counts[k].item()), 0
-    return n_evals, k
+            bound, since = int(counter[k].item()), 0
+    return total, k
 
 
 def _finish(st, n_evals, n_steps):
@@ -153,30 +162,9 @@ class TraceResults(list):
 
 
 def _march_batch(field, st, tol, omega, max_steps, readback, bound=None):
-    """_march on a state that oi_trace_batch_begin has filled: the bound is live[k] = the largest count of any element, read
-    by the same rule.  bound: live[0] where a begin kernel enters only some of the rays (oi_amd.scene), else N.
-    -> (sum of the bounds, steps run)."""
-    import ctypes
-    L = _l.load()
-    sdf = torch.empty(st.E, st.N, dtype=torch.float32, device=st.t.device)   # working memory: step k's pass writes sdf[:, :bound]
-    pts_p, sdf_p, state_p, stream = ops._p(st.points), ops._p(sdf), ctypes.byref(st.c), ops._stream()
-    packed_p, gamma_p, beta_p = ops._p(field.packed), ops._p(field.gamma), ops._p(field.beta)
-    prec, trig, E, N = field.prec, field.fast, st.E, st.N
-    bound, total, k, since = (N if bound is None else int(bound)), 0, 0, 0
-    while k < max_steps and bound > 0:
-        rc = L.oi_sdf_mlp_fwd_segments(pts_p, packed_p, gamma_p, beta_p, sdf_p, E, bound, N, prec, trig, stream)
-        if rc:
-            _l.check(rc, "oi_sdf_mlp_fwd_segments")
-        rc = L.oi_trace_batch_step(state_p, sdf_p, bound, k, tol, omega, stream)
-        if rc:
-            _l.check(rc, "oi_trace_batch_step")
-        total += bound
-        k += 1
-        since += 1
-        every = (1 if bound > READBACK_DENSE else READBACK_SPARSE) if readback == "auto" else int(readback)
-        if since >= every and k < max_steps:
-            bound, since = int(st.live[k].item()), 0
-    return total, k
+    """_march on an ops.TraceBatchState.  bound: live[0] where a begin kernel enters only some of the rays (oi_amd.scene),
+    else N."""
+    return _march(field, st, st.N if bound is None else int(bound), tol, omega, max_steps, readback)
 
 
 @torch.no_grad()
@@ -259,21 +247,24 @@ class _Surface:
         return (float(tol), float(omega), int(max_steps), readback), float(bias)
 
     def __init__(self, gen, z, b2w, bias, trace_kw, w=None):
-        self.kw, self.bias = self.params(bias, trace_kw)
-        self.field = LatentField(gen, z, w, "render_surface")
+        kw, bias = self.params(bias, trace_kw)
+        field = LatentField(gen, z, w, "render_surface")
         gen.eval()
         dev = gen.it.device
-        self.field.prepare(None if z is None else z.to(dev), None if w is None else w.to(dev))
-        self.ro, self.rd, near, far, self.w2b = _view_rays(gen, b2w)
-        self.N, self.H = self.ro.shape[0], gen.resolution
-        st = ops.TraceState(self.N, self.ro, self.rd, near, far)
+        field.prepare(None if z is None else z.to(dev), None if w is None else w.to(dev))
+        ro, rd, near, far, w2b = _view_rays(gen, b2w)
+        st = ops.TraceState(ro.shape[0], ro, rd, near, far)
         ops.trace_begin(st)
-        n_evals, k = _march(self.field, st, self.N, *self.kw)
-        self.res = _finish(st, n_evals, k)
-        self.n_hit = self.res.hit_index.shape[0]
-        self.grad = self.rgb = None
-        if self.n_hit:
-            _, self.grad, self.rgb = self.field.full(self.res.hit_points)
+        res = _finish(st, *_march(field, st, st.N, *kw))
+        grad = rgb = None
+        if res.hit_index.shape[0]:
+            _, grad, rgb = field.full(res.hit_points)
+        self._set(field, kw, bias, ro, rd, w2b, gen.resolution, res, grad, rgb)
+
+    def _set(self, field, kw, bias, ro, rd, w2b, H, res, grad, rgb):
+        self.kw, self.bias, self.field = kw, bias, field
+        self.ro, self.rd, self.w2b, self.N, self.H = ro, rd, w2b, ro.shape[0], H
+        self.res, self.n_hit, self.grad, self.rgb = res, res.hit_index.shape[0], grad, rgb
         self.shadow_evals = self.ao_evals = self.transfer_evals = 0
         self.shadow = self.ao = self.transfer_state = None
 
@@ -281,16 +272,13 @@ class _Surface:
     def from_batch(cls, field, kw, bias, ro, rd, w2b, H, res, grad, rgb):
         """One element of render_surfaces: slices of the batched arrays, its own w2b and FiLM rows (field: B = 1)."""
         self = cls.__new__(cls)
-        self.kw, self.bias, self.field = kw, bias, field
-        self.ro, self.rd, self.w2b, self.N, self.H = ro, rd, w2b, ro.shape[0], H
-        self.res, self.n_hit, self.grad, self.rgb = res, res.hit_index.shape[0], grad, rgb
-        self.shadow_evals = self.ao_evals = self.transfer_evals = 0
-        self.shadow = self.ao = self.transfer_state = None
+        self._set(field, kw, bias, ro, rd, w2b, H, res, grad, rgb)
         return self
 
-    def _secondary(self, st):
-        """The any-hit loop on a state an oi_occlusion_*_begin has filled; rays in flight at the end -> LIMIT."""
-        n_evals, _ = _march(self.field, st, int(st.counts[0].item()), *self.kw, anyhit=True)
+    def _secondary(self, st, anyhit=True):
+        """The loop on a state of secondary rays that a begin entry has filled (any-hit after an oi_occlusion_*_begin); rays in
+        flight at the end -> LIMIT."""
+        n_evals, _ = _march(self.field, st, int(st.counts[0].item()), *self.kw, anyhit=anyhit)
         ops.trace_finish(st)
         return n_evals
 
@@ -304,10 +292,7 @@ class _Surface:
         if radius is None and samples == 1:
             st = ops.TraceState(L * self.n_hit, ref=self.ro)
             ops.trace_shadow_begin(st, self.res.hit_points, self.grad, self.n_hit, lights, self.w2b, self.bias)
-            bound = int(st.counts[0].item())
-            n_evals, _ = _march(self.field, st, bound, *self.kw)
-            ops.trace_finish(st)   # in-flight rays -> LIMIT
-            self.shadow_evals += n_evals
+            self.shadow_evals += self._secondary(st, anyhit=False)
             self.shadow = st
             return ops.trace_visibility(st.status, self.res.hit_slot, self.N, self.n_hit, L)
         if radius is None:
@@ -362,18 +347,25 @@ class _Surface:
         return s
 
 
+def _is_count(v, lo, hi=_l.OCCLUSION_MAX_SAMPLES):
+    """An integer (no bool) with lo <= v <= hi: a number of samples, instances or lights."""
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and lo <= int(v) <= hi
+
+
+def _check_seed(seed, what):
+    if not _is_count(seed, 0, (1 << 32) - 1):
+        raise ValueError(f"{what}: seed={seed!r} (an integer, 0 <= seed < 2^32)")
+
+
 def _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_lights, what):
     """-> the lights' angular radii as a list of n_lights floats, or None for hard shadows (one ray, no radius)."""
-    def count(v, lo):
-        return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and lo <= int(v) <= _l.OCCLUSION_MAX_SAMPLES
-    if not count(shadow_samples, 1):
+    if not _is_count(shadow_samples, 1):
         raise ValueError(f"{what}: shadow_samples={shadow_samples!r} (an integer, 1 <= shadow_samples <= {_l.OCCLUSION_MAX_SAMPLES})")
-    if not count(ao_samples, 0):
+    if not _is_count(ao_samples, 0):
         raise ValueError(f"{what}: ao_samples={ao_samples!r} (an integer, 0 <= ao_samples <= {_l.OCCLUSION_MAX_SAMPLES})")
     if not (float(ao_distance) > 0 and np.isfinite(float(ao_distance))):
         raise ValueError(f"{what}: ao_distance={ao_distance!r} (positive and finite)")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 32:
-        raise ValueError(f"{what}: seed={seed!r} (an integer, 0 <= seed < 2^32)")
+    _check_seed(seed, what)
     rad = np.asarray(light_radius.detach().cpu() if torch.is_tensor(light_radius) else light_radius, dtype=np.float64)
     if rad.ndim > 1 or (rad.ndim == 1 and rad.shape[0] != n_lights):
         raise ValueError(f"{what}: light_radius of shape {rad.shape} (a scalar or one value per light: {n_lights})")
@@ -387,6 +379,22 @@ def _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_dista
 
 def _bg(bg, dev):
     return None if bg is None else torch.as_tensor(bg, dtype=torch.float32).to(dev).reshape(3).contiguous()
+
+
+def _stack_lights(gen, lights, dev, what, hint=""):
+    """`lights` (oi_amd.relight.Light objects; default the generator's trained light) as (L, 16) on dev.  More than
+    RELIGHT_MAX_LIGHTS are refused in the name of `what`; hint: where larger sets are split."""
+    from .relight import Light, stack_lights
+    lt = stack_lights(Light.from_module(gen.light) if lights is None else lights, dev)
+    if lt.shape[0] > _l.RELIGHT_MAX_LIGHTS:
+        raise ValueError(f"{what}: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS}{hint})")
+    return lt
+
+
+def _latents(zs, dev):
+    """E latents, a tensor (E, z_dim) or a sequence of (z_dim,) or (1, z_dim) -> (E, z_dim) float32 on dev."""
+    zs = (zs if torch.is_tensor(zs) else torch.stack([z.reshape(-1) for z in zs])).to(dev).float()
+    return zs.reshape(-1, zs.shape[-1])
 
 
 def _maps(out, H, W):
@@ -413,14 +421,10 @@ def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAUL
     ao_distance; the share that escapes multiplies the ambient term and is returned as ambient_occlusion (1, 1, H, W).  The
     samples are a function of pixel, sample number and `seed` alone.  With shadow_samples == 1, light_radius == 0 and
     ao_samples == 0 the launches are those of a call without these arguments."""
-    from .relight import Light, stack_lights
     dev = gen.it.device
     z = z.to(dev).reshape(1, -1)
     s = _Surface(gen, z, b2w, bias, trace_kw)
-    lt = stack_lights(Light.from_module(gen.light) if lights is None else lights, dev)
-    if lt.shape[0] > _l.RELIGHT_MAX_LIGHTS:
-        raise ValueError(f"render_surface: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS}; inference.surface_light_walk "
-                         "splits larger sets)")
+    lt = _stack_lights(gen, lights, dev, "render_surface", "; inference.surface_light_walk splits larger sets")
     radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surface")
     return _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev)
 
@@ -459,17 +463,13 @@ def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEF
     The other arguments are render_surface's, the same for every view.  -> a list of E dicts as render_surface returns
     them; per view the maps are render_surface's own, bit for bit."""
     import copy
-    from .relight import Light, stack_lights
     dev = gen.it.device
     kw, bias = _Surface.params(bias, trace_kw, "render_surfaces")
-    zs = (zs if torch.is_tensor(zs) else torch.stack([z.reshape(-1) for z in zs])).to(dev).float()
-    zs = zs.reshape(-1, zs.shape[-1])
+    zs = _latents(zs, dev)
     E = zs.shape[0]
     if len(b2ws) != E or not 1 <= E <= _l.TRACE_BATCH_MAX_ELEMS:
         raise ValueError(f"render_surfaces: {E} latents and {len(b2ws)} poses (one pose per latent, 1 .. {_l.TRACE_BATCH_MAX_ELEMS} views)")
-    lt = stack_lights(Light.from_module(gen.light) if lights is None else lights, dev)
-    if lt.shape[0] > _l.RELIGHT_MAX_LIGHTS:
-        raise ValueError(f"render_surfaces: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS})")
+    lt = _stack_lights(gen, lights, dev, "render_surfaces")
     radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surfaces")
     field = LatentField(gen, zs, None, "render_surfaces", batch_ok=True)
     gen.eval()
@@ -500,10 +500,9 @@ def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEF
 def _check_transfer(transfer_samples, seed, what):
     """_check_occlusion's rule for ao_samples and seed."""
     v = transfer_samples
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= _l.OCCLUSION_MAX_SAMPLES:
+    if not _is_count(v, 0):
         raise ValueError(f"{what}: transfer_samples={v!r} (an integer, 0 <= transfer_samples <= {_l.OCCLUSION_MAX_SAMPLES})")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 32:
-        raise ValueError(f"{what}: seed={seed!r} (an integer, 0 <= seed < 2^32)")
+    _check_seed(seed, what)
     return int(v), int(seed)
 
 

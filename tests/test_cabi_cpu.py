@@ -1,34 +1,100 @@
 """CPU-only checks of the drop-in boundary: the C-ABI library builds/loads, exports every symbol that
-include/oi_hip.h declares, and the host modules import and keep the reference's names (no compute)."""
-import os
-import re
+include/oi_hip.h declares and binds each as declared (tests/helpers/cabi.py, with that helper's own negative checks), and
+the host modules import and keep the reference's names (no compute)."""
+import ctypes
+import types
 
 import pytest
 import torch
 
-from conftest import ROOT
-
-
-def _declared():
-    text = open(os.path.join(ROOT, "include", "oi_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(oi_[a-z0-9_]+)\s*\(", text)))
+from helpers import cabi
 
 
 def test_library_exports_every_declared_symbol():
-    import __graft_entry__ as ge
-    ge.build()
-    from oi_amd import lib
-    L = lib.load()
-    names = _declared()
+    lib, L = cabi.built_lib()
+    names, mirrors = cabi.check_header("oi_hip.h", lib)
     assert len(names) >= 25
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/oi_hip.h but not exported"
-    assert set(names) == set(lib.declared_symbols()), set(names) ^ set(lib.declared_symbols())
+    assert mirrors == ["PrepParams", "CompositeParams", "CompositeGrads"]
     assert L.oi_arch() == b"gfx950"
     assert L.oi_mlp_packed_bytes(0) == 2816 * 4 + 16 * 65536 + 8 * 65536  # header, 16 MFMA images, 8 plain fp32 matrices
     assert L.oi_mlp_packed_bytes(2) == 2816 * 4 + 16 * 32768 + 8 * 65536
     assert L.oi_mlp_packed_bytes(3) == 2816 * 4 + 16 * 98304 + 8 * 65536
+
+
+def test_every_mirror_is_checked_against_its_header():
+    lib, _ = cabi.built_lib()
+    checked = [m for h in lib.SIGS for m in cabi.check_header(h, lib)[1]]
+    assert sorted(checked) == sorted(n for n, c in vars(lib).items() if isinstance(c, type) and issubclass(c, ctypes.Structure))
+    assert sorted(checked) == ["CompositeGrads", "CompositeParams", "EnvShadeParams", "PrepParams", "RelightParams",
+                               "SceneShadeParams", "SurfaceAoParams", "SurfaceParams", "TraceBatch", "TraceState"]
+
+
+HEADER_FIXTURE = """
+#define OI_ROWS 8
+typedef void* oi_stream_t; /* a stream */
+typedef struct oi_pair_params {
+  float m[OI_ROWS][16], v[3];  // arrays
+  long long N;
+  int A, B;
+  const float *src, *dst;
+} oi_pair_params;
+typedef struct oi_not_mirrored { int x; } oi_not_mirrored;
+int oi_pair(const oi_pair_params* p, const float* x, long long n, unsigned seed, oi_stream_t stream);
+size_t oi_pair_bytes(int n, double scale);  /* int oi_in_a_comment(int n); */
+const char* oi_pair_name(void);
+void oi_pair_free(oi_not_mirrored** p);
+"""
+
+
+_vp, _i, _ll, _f, _u = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_uint
+PAIR_FIELDS = dict(m=(_f * 16) * 8, v=_f * 3, N=_ll, A=_i, B=_i, src=_vp, dst=_vp)
+
+
+def _mirror(**changes):
+    return type("PairParams", (ctypes.Structure,), {"_fields_": list({**PAIR_FIELDS, **changes}.items())})
+
+
+PAIR = _mirror()
+
+
+def _fixture_lib(mirror=PAIR, other="oi_other", **changes):
+    """A stand-in for oi_amd.lib that binds HEADER_FIXTURE correctly, but for `changes`."""
+    sigs = {"oi_pair": (_i, [ctypes.POINTER(mirror), _vp, _ll, _u, _vp]), "oi_pair_bytes": (ctypes.c_size_t, [_i, ctypes.c_double]),
+            "oi_pair_name": (ctypes.c_char_p, []), "oi_pair_free": (None, [_vp]), **changes}
+    table = {"fixture.h": sigs, "other.h": {other: (_i, [])}}
+    return types.SimpleNamespace(SIGS=table, symbols=lambda h: sorted(table[h]), PairParams=mirror,
+                                 load=lambda: types.SimpleNamespace(**{n: None for n in sigs}))
+
+
+def test_contract_helper_refuses_what_it_must():
+    check = lambda text=HEADER_FIXTURE, **changes: cabi.check_header("fixture.h", _fixture_lib(**changes), text)
+    assert check() == (["oi_pair", "oi_pair_bytes", "oi_pair_name", "oi_pair_free"], ["PairParams"])
+    pair = lambda *args: {"oi_pair": (_i, list(args))}
+    P = ctypes.POINTER(PAIR)
+    edit = lambda old, new: dict(text=HEADER_FIXTURE.replace(old, new))
+    bad = [
+        (edit("unsigned seed,", "unsigned seed, int extra,"), "oi_pair: 6 parameters, 5 bound"),    # one argument more
+        (pair(P, _vp, _i, _u, _vp), "oi_pair: parameter 2"),                                        # long long bound as c_int
+        (pair(_vp, _vp, _ll, _u, _vp), "oi_pair: parameter 0"),                                     # a mirrored struct as void*
+        (pair(ctypes.POINTER(_mirror()), _vp, _ll, _u, _vp), "oi_pair: parameter 0"),               # another struct's pointer
+        (pair(P, _vp, _ll, _i, _vp), "oi_pair: parameter 3"),                                       # unsigned bound as c_int
+        (pair(P, _ll, _ll, _u, _vp), "oi_pair: parameter 1"),                                       # a pointer bound as an integer
+        ({"oi_pair_bytes": (_i, [_i, ctypes.c_double])}, "oi_pair_bytes: returns"),
+        ({"oi_pair_bytes": (ctypes.c_size_t, [_i, _f])}, "oi_pair_bytes: parameter 1"),             # double bound as c_float
+        ({"oi_pair_free": (_i, [_vp])}, "oi_pair_free: returns"),
+        (dict(other="oi_pair_name"), "oi_pair_name stands under fixture.h and other.h"),
+        (edit("const char* oi_pair_name(void);", ""), "oi_pair_name"),                              # bound, not declared
+        (edit("void oi_pair_free", "int oi_new(int n);\nvoid oi_pair_free"), "oi_new"),              # declared, not bound
+        (edit("int n, double scale", "int n, long scale"), "unknown type 'long'"),
+        (edit("int A, B;", "int B, A;"), "oi_pair_params: fields"),                                 # two fields swapped
+        (dict(mirror=_mirror(N=_i)), "oi_pair_params.N"),
+        (dict(mirror=_mirror(m=(_f * 8) * 16)), "oi_pair_params.m"),                                # the extents the other way round
+        (dict(mirror=_mirror(v=_i * 3)), "oi_pair_params.v"),
+        (dict(mirror=_mirror(dst=_ll)), "oi_pair_params.dst"),
+    ]
+    for kw, message in bad:
+        with pytest.raises(AssertionError, match=message):
+            check(**kw)
 
 
 def test_ops_fail_loudly_without_gpu_tensors():

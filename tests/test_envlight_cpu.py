@@ -11,11 +11,11 @@ import pytest
 import torch
 
 from conftest import ROOT
+from helpers import cabi
 from helpers import env_ref as E
 from helpers import mesh_attr_ref as A
 from helpers import trace_ref as T
 
-HEADER = os.path.join(ROOT, "include", "oi_envlight.h")
 NAMES = ["oi_env_project", "oi_env_project_partial_floats", "oi_env_shade", "oi_transfer_normal", "oi_transfer_resolve"]
 
 # at least 8 normals, +z and -z among them: the tangent frame of the sample directions switches sign between the two
@@ -23,11 +23,7 @@ NORMALS = A.unit(np.array([[0.0, 0.0, 1.0], [0.0, 0.0, -1.0], [1.0, 0.0, 0.0], [
                            [0.57, 0.58, 0.58], [-0.2, -0.9, 1e-3], [0.1, 0.05, -0.99]]))
 
 
-def _lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from oi_amd import lib
-    return lib, lib.load()
+_lib = cabi.built_lib
 
 
 def test_furnace():
@@ -172,31 +168,14 @@ def test_argument_checks():
     assert np.array_equal(rots[0], np.eye(3)) and np.abs(rots[1] - E.axis_rotation((0, 0, 1), np.pi / 2)).max() < 1e-15
 
 
-def _exports(path):
-    with open(path) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    return re.findall(r"^\s*(?:const\s+)?(?:int|size_t|void|char)\s*\*?\s*(oi_\w+)\s*\(", text, re.M)
-
-
 def test_header_library_and_binding_agree():
     lib, L = _lib()
-    names = _exports(HEADER)
-    assert sorted(names) == NAMES
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/oi_envlight.h but not exported"
-    assert set(names) == set(lib.envlight_symbols())
-    for other in (lib.declared_symbols(), lib.trace_symbols(), lib.occlusion_symbols(), lib.mesh_band_symbols(), lib.trace_batch_symbols()):
-        assert not set(names) & set(other)
-    text = open(HEADER).read()
+    names, mirrors = cabi.check_header("oi_envlight.h", lib)
+    assert sorted(names) == NAMES and mirrors == ["EnvShadeParams"]
+    text = cabi.read("oi_envlight.h")
     define = lambda name: int(re.search(r"#define %s (\d+)" % name, text).group(1))
     assert define("OI_ENV_FLOATS") == lib.ENV_FLOATS == 27 and define("OI_ENV_COEFFS") == lib.ENV_COEFFS == E.N_COEFFS == 9
     assert define("OI_ENV_MAX_ENVS") == lib.ENV_MAX_ENVS == E.MAX_ENVS == 256
-    plain = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    body = re.search(r"typedef struct oi_env_shade_params \{(.*?)\} oi_env_shade_params;", plain, re.S).group(1)
-    assert re.findall(r"(\w+)\s*;", body) == [f[0] for f in lib.EnvShadeParams._fields_]
-    for name in names:   # argument counts of the declarations against the ctypes signatures
-        decl = re.search(r"(?:int|size_t) %s\((.*?)\);" % name, plain, re.S).group(1)
-        assert len(decl.split(",")) == len(getattr(L, name).argtypes), name
     assert '"envlight.hip"' in open(os.path.join(ROOT, "object-intrinsics_amd", "build.py")).read()
     # the basis constants of the header are the rounded values of the restatement's
     k =[float(v) for v in re.findall(r"\*   y\d = (\d\.\d+)", text)]

@@ -24,9 +24,9 @@ import pytest
 import torch
 
 from conftest import ROOT
+from helpers import cabi
 from helpers import mesh_attr_ref as A
 
-HEADER = os.path.join(ROOT, "include", "oi_mesh_attr.h")
 GPU_TEST = os.path.join(ROOT, "tests", "test_gpu_mesh_attrs.py")
 KW = dict(D=8, W=128, input_ch=3, input_ch_views=3, style_dim=64)
 
@@ -131,27 +131,17 @@ def test_python_argument_checks():
 
 
 def _header_exports():
-    with open(HEADER) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    return re.findall(r"^\s*(?:const\s+)?(?:int|size_t|void|char)\s*\*?\s*(oi_\w+)\s*\(", text, re.M)
+    return list(cabi.parse(cabi.read("oi_mesh_attr.h"))[0])
 
 
-def _lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from oi_amd import lib
-    return lib, lib.load()
+_lib = cabi.built_lib
 
 
 def test_library_exports_every_mesh_attr_symbol():
     lib, L = _lib()
-    names = _header_exports()
+    names, _ = cabi.check_header("oi_mesh_attr.h", lib)
     assert sorted(names) == ["oi_mesh_attr_finalize", "oi_mesh_newton", "oi_mesh_vertex_record", "oi_mesh_vertex_world"]
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/oi_mesh_attr.h but not exported"
-    assert set(names) == set(lib.mesh_attr_symbols())
-    assert not set(names) & set(lib.declared_symbols())   # oi_hip.h's own list is unchanged
-    text = open(HEADER).read()
+    text = cabi.read("oi_mesh_attr.h")
     for macro, val in (("OI_MESH_FLAG_NONFINITE", lib.MESH_FLAG_NONFINITE), ("OI_MESH_FLAG_SMALL_GRADIENT", lib.MESH_FLAG_SMALL_GRADIENT),
                        ("OI_MESH_FLAG_LIMIT", lib.MESH_FLAG_LIMIT), ("OI_MESH_MAX_REFINE", lib.MESH_MAX_REFINE),
                        ("OI_MESH_RECORD_BYTES", lib.MESH_RECORD_BYTES)):

@@ -22,9 +22,9 @@ import torch
 
 from conftest import ROOT
 from helpers import band_ref as R
+from helpers import cabi
 from helpers import mc_numpy as M
 
-HEADER = os.path.join(ROOT, "include", "oi_mesh_band.h")
 BMIN, BMAX = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)
 GPU_LATTICES = [(512, 512, 512), (485, 510, 655)]     # tests/test_gpu_mesh_band.py imports these
 
@@ -102,28 +102,14 @@ def test_slope_guard_fires_when_the_bound_is_halved():
 # ---------------------------------------------------------------------------------------------------------------------
 # header <=> library <=> binding, refusals
 # ---------------------------------------------------------------------------------------------------------------------
-def _header_exports():
-    with open(HEADER) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    return re.findall(r"^\s*(?:const\s+)?(?:int|size_t|void|char)\s*\*?\s*(oi_\w+)\s*\(", text, re.M)
-
-
-def _lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from oi_amd import lib
-    return lib, lib.load()
+_lib = cabi.built_lib
 
 
 def test_library_exports_every_mesh_band_symbol():
     lib, L = _lib()
-    names = _header_exports()
+    names, _ = cabi.check_header("oi_mesh_band.h", lib)
     assert sorted(names) == ["oi_band_classify", "oi_band_workspace_bytes", "oi_sdf_lattice_band"]
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/oi_mesh_band.h but not exported"
-    assert set(names) == set(lib.mesh_band_symbols())
-    assert not set(names) & set(lib.declared_symbols())   # oi_hip.h's own list is unchanged
-    text = open(HEADER).read()
+    text = cabi.read("oi_mesh_band.h")
     assert int(re.search(r"#define OI_BAND_MIN_RES (\d+)", text).group(1)) == lib.BAND_MIN_RES
     assert int(re.search(r"#define OI_BAND_MAX_RES (\d+)", text).group(1)) == lib.BAND_MAX_RES
     assert '"mesh_band.hip"' in open(os.path.join(ROOT, "object-intrinsics_amd", "build.py")).read()

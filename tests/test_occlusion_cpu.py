@@ -19,50 +19,26 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from helpers import cabi
 from helpers import occlusion_ref as R
 from helpers import trace_ref as T
 
-HEADER = os.path.join(ROOT, "include", "oi_occlusion.h")
-TRACE_HEADER = os.path.join(ROOT, "include", "oi_trace.h")
 
-
-def _exports(path):
-    with open(path) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    return re.findall(r"^\s*(?:const\s+)?(?:int|size_t|void|char)\s*\*?\s*(oi_\w+)\s*\(", text, re.M)
-
-
-def _lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from oi_amd import lib
-    return lib, lib.load()
+_lib = cabi.built_lib
 
 
 def test_header_library_binding_and_helper_agree():
     lib, L = _lib()
-    names = _exports(HEADER)
+    names, mirrors = cabi.check_header("oi_occlusion.h", lib)
     assert sorted(names) == ["oi_occlusion_ambient_begin", "oi_occlusion_light_begin", "oi_occlusion_resolve", "oi_occlusion_step",
                              "oi_surface_shade_ao"]
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/oi_occlusion.h but not exported"
-    assert set(names) == set(lib.occlusion_symbols())
-    # the lists the earlier headers pin are unchanged
-    assert sorted(_exports(TRACE_HEADER)) == ["oi_surface_shade", "oi_trace_begin", "oi_trace_finish", "oi_trace_shadow_begin",
-                                              "oi_trace_step", "oi_trace_visibility"] == lib.trace_symbols()
-    assert not set(names) & set(lib.declared_symbols()) and not set(names) & set(lib.trace_symbols())
-    text = open(HEADER).read()
+    assert mirrors == ["SurfaceAoParams"]
+    text = cabi.read("oi_occlusion.h")
     assert int(re.search(r"#define OI_OCCLUSION_MAX_SAMPLES (\d+)", text).group(1)) == lib.OCCLUSION_MAX_SAMPLES == R.MAX_SAMPLES == 256
-    plain = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    fields = re.findall(r"(\w+)\s*;", re.search(r"typedef struct oi_surface_ao_params \{(.*?)\} oi_surface_ao_params;", plain, re.S).group(1))
-    assert fields == [f[0] for f in lib.SurfaceAoParams._fields_]
-    assert fields[:-1] == [f[0] for f in lib.SurfaceParams._fields_] and fields[-1] == "ambient_occlusion"
-    trace_plain = re.sub(r"/\*.*?\*/", "", open(TRACE_HEADER).read(), flags=re.S)
-    body = re.search(r"typedef struct oi_surface_params \{(.*?)\} oi_surface_params;", trace_plain, re.S).group(1)
-    assert re.findall(r"(\w+)\s*;", body) == fields[:-1]
-    for name in names:   # argument counts of the declarations against the ctypes signatures
-        decl = re.search(r"int %s\((.*?)\);" % name, plain, re.S).group(1)
-        assert len(decl.split(",")) == len(getattr(L, name).argtypes), name
+    fields = cabi.parse(text)[1]["oi_surface_ao_params"]
+    assert [f for f, _ in fields] == [f[0] for f in lib.SurfaceAoParams._fields_]
+    assert fields[:-1] == cabi.parse(cabi.read("oi_trace.h"))[1]["oi_surface_params"] and fields[-1][0] == "ambient_occlusion"
+    assert lib.SurfaceAoParams._fields_[:-1] == lib.SurfaceParams._fields_
     src = open(os.path.join(ROOT, "object-intrinsics_amd", "build.py")).read()
     assert '"occlusion.hip"' in src
     from oi_amd import inference

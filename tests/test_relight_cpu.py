@@ -13,9 +13,9 @@ import torch
 
 import oi_oracle as O
 from conftest import ROOT
+from helpers import cabi
 from helpers.relight_ref import relight_ref
 
-HEADER = os.path.join(ROOT, "include", "oi_relight.h")
 GPU_TEST = os.path.join(ROOT, "tests", "test_gpu_relight.py")
 
 
@@ -130,9 +130,7 @@ def test_light_walk_schedule(axis):
 
 
 def _header_exports():
-    with open(HEADER) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    return re.findall(r"^\s*(?:const\s+)?(?:int|size_t|void|char)\s*\*?\s*(oi_\w+)\s*\(", text, re.M)
+    return list(cabi.parse(cabi.read("oi_relight.h"))[0])
 
 
 def _code_only(path):
@@ -163,29 +161,15 @@ def test_every_relight_export_has_a_guarded_case():
         assert not all(re.search(r"torch\.empty", wrappers[f]) for f in via), (n, via)
 
 
-def _lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from oi_amd import lib
-    return lib, lib.load()
+_lib = cabi.built_lib
 
 
 def test_library_exports_every_relight_symbol():
     lib, L = _lib()
-    names = _header_exports()
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/oi_relight.h but not exported"
-    assert set(names) == set(lib.relight_symbols())
-    text = open(HEADER).read()
+    assert cabi.check_header("oi_relight.h", lib) == (["oi_relight_fwd"], ["RelightParams"])
+    text = cabi.read("oi_relight.h")
     assert int(re.search(r"#define OI_RELIGHT_LIGHT_FLOATS (\d+)", text).group(1)) == lib.RELIGHT_LIGHT_FLOATS
     assert int(re.search(r"#define OI_RELIGHT_MAX_LIGHTS (\d+)", text).group(1)) == lib.RELIGHT_MAX_LIGHTS
-    body = re.search(r"typedef struct oi_relight_params \{(.*?)\} oi_relight_params;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    declared = []
-    for decl in re.findall(r"([^;]+);", body):
-        decl = re.sub(r"^\s*(const\s+)?(long\s+long|\w+)\s*", "", decl.strip())
-        declared += [x.strip().lstrip("*").strip() for x in decl.split(",")]
-    assert declared == [f for f, _ in lib.RelightParams._fields_], declared
 
 
 def test_c_abi_rejects_invalid_arguments_before_launching():

@@ -14,10 +14,10 @@ import pytest
 import torch
 
 from conftest import ROOT
+from helpers import cabi
 from helpers import scene_ref as SR
 from helpers import trace_ref as T
 
-HEADER = os.path.join(ROOT, "include", "oi_scene.h")
 ENTRIES = ["oi_scene_begin", "oi_scene_points", "oi_scene_resolve", "oi_scene_shade", "oi_scene_shadow_begin", "oi_scene_visibility",
            "oi_scene_visible"]
 R_SCENE = 16                      # the generator of the GPU tests: crop resolution 16, scene resolution 99
@@ -34,32 +34,15 @@ def fake_gen(R=R_SCENE):
                                  pose_prior=Plane([0, -1, 0], 360, [6, 3.5], 20))
 
 
-def _lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from oi_amd import lib
-    return lib, lib.load()
+_lib = cabi.built_lib
 
 
 def test_header_library_and_binding_agree():
     lib, L = _lib()
-    with open(HEADER) as fh:
-        text = fh.read()
-    bare = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = re.findall(r"^\s*int\s+(oi_\w+)\s*\(", bare, re.M)
-    assert sorted(names) == ENTRIES == lib.scene_symbols()
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/oi_scene.h but not exported"
-    for other in (lib.declared_symbols(), lib.trace_symbols(), lib.occlusion_symbols(), lib.trace_batch_symbols(), lib.envlight_symbols()):
-        assert not set(names) & set(other)                 # the lists the earlier headers pin are unchanged
+    names, mirrors = cabi.check_header("oi_scene.h", lib)
+    assert sorted(names) == ENTRIES == lib.symbols("oi_scene.h") and mirrors == ["SceneShadeParams"]
+    text = cabi.read("oi_scene.h")
     assert int(re.search(r"#define OI_SCENE_MAX_RESOLUTION (\d+)", text).group(1)) == lib.SCENE_MAX_RESOLUTION == 32768
-    body = re.search(r"typedef struct oi_scene_shade_params \{(.*?)\} oi_scene_shade_params;", bare, re.S).group(1)
-    fields = [n for decl in re.findall(r"[\w\s\*]+?([\w\s,\*]+);", body) for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
-    assert fields == [f[0] for f in lib.SceneShadeParams._fields_]
-    # argument counts of the prototypes against the bindings
-    for n in names:
-        args = re.search(r"int\s+" + n + r"\s*\((.*?)\);", bare, re.S).group(1)
-        assert len(args.split(",")) == len(lib._SCENE_SIGS[n][1]), n
     src = open(os.path.join(ROOT, "object-intrinsics_amd", "build.py")).read()
     assert '"scene.hip"' in src and "include/oi_scene.h" in src
 

@@ -20,10 +20,10 @@ import pytest
 import torch
 
 from conftest import ROOT
+from helpers import cabi
 from helpers import trace_batch_ref as B
 from helpers import trace_ref as T
 
-HEADER = os.path.join(ROOT, "include", "oi_trace_batch.h")
 KW = dict(D=8, W=128, input_ch=3, input_ch_views=3, style_dim=64)
 
 
@@ -90,33 +90,17 @@ def test_ragged_elements_and_an_element_that_ends_at_once():
     assert s.min() > 10 * 0.05
 
 
-def _header_exports():
-    with open(HEADER) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    return re.findall(r"^\s*(?:const\s+)?(?:int|size_t|void|char)\s*\*?\s*(oi_\w+)\s*\(", text, re.M)
-
-
-def _lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from oi_amd import lib
-    return lib, lib.load()
+_lib = cabi.built_lib
 
 
 def test_header_library_and_binding_agree():
     lib, L = _lib()
-    names = _header_exports()
+    names, mirrors = cabi.check_header("oi_trace_batch.h", lib)
     assert sorted(names) == ["oi_sdf_mlp_fwd_segments", "oi_trace_batch_begin", "oi_trace_batch_finish", "oi_trace_batch_gather",
                              "oi_trace_batch_step"]
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/oi_trace_batch.h but not exported"
-    assert set(names) == set(lib.trace_batch_symbols())
-    for other in (lib.declared_symbols(), lib.trace_symbols(), lib.occlusion_symbols(), lib.mesh_band_symbols()):
-        assert not set(names) & set(other)                 # the lists the earlier headers pin are unchanged
-    text = open(HEADER).read()
+    text = cabi.read("oi_trace_batch.h")
     assert int(re.search(r"#define OI_TRACE_BATCH_MAX_ELEMS (\d+)", text).group(1)) == lib.TRACE_BATCH_MAX_ELEMS == B.MAX_ELEMS == 1024
-    body = re.search(r"typedef struct oi_trace_batch \{(.*?)\} oi_trace_batch;", re.sub(r"/\*.*?\*/", "", text, flags=re.S), re.S).group(1)
-    assert re.findall(r"(\w+)\s*;", body) == [f[0] for f in lib.TraceBatch._fields_] == ["s", "E", "live"]
+    assert mirrors == ["TraceBatch"] and [f[0] for f in lib.TraceBatch._fields_] == ["s", "E", "live"]
     assert lib.TraceBatch._fields_[0][1] is lib.TraceState
     from oi_amd import trace
     assert (trace.READBACK_DENSE, trace.READBACK_SPARSE) == (B.READBACK_DENSE, B.READBACK_SPARSE)

@@ -19,9 +19,9 @@ import pytest
 import torch
 
 from conftest import ROOT
+from helpers import cabi
 from helpers import trace_ref as T
 
-HEADER = os.path.join(ROOT, "include", "oi_trace.h")
 KW = dict(D=8, W=128, input_ch=3, input_ch_views=3, style_dim=64)
 
 
@@ -77,29 +77,16 @@ def test_state_machine_on_analytic_fields():
     assert T.visibility_of([T.MISS, T.HIT, T.LIMIT, T.START_INSIDE, T.NONFINITE, T.BACKFACING]).tolist() == [1, 0, 0, 0, 0, 0]
 
 
-def _header_exports():
-    with open(HEADER) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    return re.findall(r"^\s*(?:const\s+)?(?:int|size_t|void|char)\s*\*?\s*(oi_\w+)\s*\(", text, re.M)
-
-
-def _lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from oi_amd import lib
-    return lib, lib.load()
+_lib = cabi.built_lib
 
 
 def test_header_library_binding_and_helper_agree():
     lib, L = _lib()
-    names = _header_exports()
+    names, mirrors = cabi.check_header("oi_trace.h", lib)
     assert sorted(names) == ["oi_surface_shade", "oi_trace_begin", "oi_trace_finish", "oi_trace_shadow_begin", "oi_trace_step",
                              "oi_trace_visibility"]
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/oi_trace.h but not exported"
-    assert set(names) == set(lib.trace_symbols())
-    assert not set(names) & set(lib.declared_symbols())   # oi_hip.h's own list is unchanged
-    text = open(HEADER).read()
+    assert mirrors == ["TraceState", "SurfaceParams"]   # the ctypes mirrors have the header's fields, in its order
+    text = cabi.read("oi_trace.h")
     ints = {"OI_TRACE_MISS": (lib.TRACE_MISS, T.MISS), "OI_TRACE_HIT": (lib.TRACE_HIT, T.HIT), "OI_TRACE_LIMIT": (lib.TRACE_LIMIT, T.LIMIT),
             "OI_TRACE_START_INSIDE": (lib.TRACE_START_INSIDE, T.START_INSIDE), "OI_TRACE_NONFINITE": (lib.TRACE_NONFINITE, T.NONFINITE),
             "OI_TRACE_BACKFACING": (lib.TRACE_BACKFACING, T.BACKFACING), "OI_TRACE_MARCH": (lib.TRACE_MARCH, T.MARCH),
@@ -113,11 +100,6 @@ def test_header_library_binding_and_helper_agree():
     for macro, (a, b) in floats.items():
         assert float(re.search(r"#define %s ([0-9.e+-]+)f" % macro, text).group(1)) == a == b, macro
     assert (T.TOL, T.OMEGA, T.MAX_STEPS, T.BIAS) == (1e-5, 1.0, 64, 1e-2)
-    # the ctypes mirrors have the header's fields, in its order
-    for struct, cls in (("oi_trace_state", lib.TraceState), ("oi_surface_params", lib.SurfaceParams)):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), re.sub(r"/\*.*?\*/", "", text, flags=re.S), re.S).group(1)
-        fields = re.findall(r"(\w+)\s*;", body)
-        assert fields == [f[0] for f in cls._fields_], struct
     src = open(os.path.join(ROOT, "object-intrinsics_amd", "build.py")).read()
     assert '"trace.hip"' in src
 

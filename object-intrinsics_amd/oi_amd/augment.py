@@ -83,13 +83,17 @@ class AugmentPipe(torch.nn.Module):
             self._p_cache = (key, float(self.p))
         return self._p_cache[1]
 
+    def is_stock(self):
+        """The stock pipe: this class's own `forward`, not overridden on the instance, and the 12-tap filter -- what the fused
+        augmentation kernels (csrc/disc_small.hip, the library's plans) stand in for."""
+        return type(self).forward is AugmentPipe.forward and "forward" not in self.__dict__ and self._buffers["Hz_geom"].shape[0] == 12
+
     def fast_draw_ok(self):
-        """True when a forward's parameters may be drawn inside the library from one seed (ops.DiscGraph.call_ada): the shipped
-        configuration (xint + scale only), this class's own `forward` / `sample_G_inv` (tests and the F13 replay pin
-        `debug_percentile` by overriding them on the instance), the 12-tap filter."""
-        d = self.__dict__
-        return (self._only_xint_scale and "forward" not in d and "sample_G_inv" not in d and type(self).forward is AugmentPipe.forward
-                and type(self).sample_G_inv is AugmentPipe.sample_G_inv and self.Hz_geom.shape[0] == 12)
+        """True when a forward's parameters may be drawn inside the library from one seed (ops.DiscGraph.call_ada): the stock
+        pipe in the shipped configuration (xint + scale only) with this class's own `sample_G_inv` (tests and the F13 replay
+        pin `debug_percentile` by overriding `forward` / `sample_G_inv` on the instance)."""
+        return (self.is_stock() and self._only_xint_scale and "sample_G_inv" not in self.__dict__
+                and type(self).sample_G_inv is AugmentPipe.sample_G_inv)
 
     def fast_params(self):
         """(xint * p, xint_max, scale * p, scale_std): the gate probabilities and strengths oi_ada_theta_xint_scale takes."""

@@ -339,19 +339,16 @@ class GraphedDForward:
         """Batch <= 4 of the 64 x 64 network: the library's own graph (ops.DiscGraph) -- image pointer and sampling matrices are
         node parameters, so a call is the host-side draw + ONE graph launch (no staging launch)."""
         from . import ops
-        from .augment import AugmentPipe
         d = self.disc
         aug = getattr(d, "aug", None)
         with torch.no_grad():
             ok = d._small_ok(x)
-        if not ok or os.environ.get("OI_GRAPH_D_LIBRARY", "1") == "0":
-            return None
-        if aug is not None and (type(aug).forward is not AugmentPipe.forward or "forward" in aug.__dict__ or aug.Hz_geom.shape[0] != 12):
+        if not ok or os.environ.get("OI_GRAPH_D_LIBRARY", "1") == "0" or (aug is not None and not aug.is_stock()):
             return None
         geom = aug is not None and _has_geometric(aug)
         H, W = x.shape[2:]
-        return ops.DiscGraph(tuple(x.shape), x.device, [l.weight for l in d.blocks], d.conv_out.weight, d.conv_out.bias,
-                             f12=aug.Hz_geom if geom else None, margins=aug.static_margins(H, W) if geom else None,
+        return ops.DiscGraph(tuple(x.shape), x.device, *d.live_weights(), f12=aug.Hz_geom if geom else None,
+                             margins=aug.static_margins(H, W) if geom else None,
                              launch="eager" if len(d.blocks) == 5 else None), geom   # (the 128 x 128 plan: launch by launch only)
 
     def capture(self, x):

@@ -20,6 +20,7 @@ _lib = None
 
 OI_PREC_F32, OI_PREC_BF16X3, OI_PREC_BF16, OI_PREC_BF16X6, OI_PREC_F16X3 = 0, 1, 2, 3, 4
 OI_MLP_BLOB_READY = 1
+TICKET_WORDS = 4097   # OI_TICKET_WORDS (include/oi_hip.h): device words of an arrival-counter buffer
 PRECISIONS = {"f32": OI_PREC_F32, "fp32": OI_PREC_F32, "bf16x3": OI_PREC_BF16X3, "bf16": OI_PREC_BF16,
               "bf16x6": OI_PREC_BF16X6, "f16x3": OI_PREC_F16X3}
 

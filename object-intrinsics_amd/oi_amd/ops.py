@@ -414,7 +414,7 @@ def _stats_ticket(dev):
     key = (dev, _stream().value or 0)
     t = _STATS_TICKETS.get(key)
     if t is None:
-        t = _STATS_TICKETS[key] = torch.zeros(4097, dtype=torch.int32, device=dev)   # OI_TICKET_WORDS
+        t = _STATS_TICKETS[key] = torch.zeros(_l.TICKET_WORDS, dtype=torch.int32, device=dev)
     return t
 
 
@@ -1252,6 +1252,10 @@ def upfirdn2d(x, f, upx=1, upy=1, downx=1, downy=1, padx0=0, padx1=0, pady0=0, p
 
 
 _DISC_TICKETS = {}
+# the batch <= 4 forward's C entries by the number of blocks (4: the 64 x 64 network | 5: the shipped 128 x 128 one, whose entries
+# fix the image size): (forward, workspace floats, plan creation, H and W passed)
+_DISC_SMALL = {4: ("oi_disc_fwd_small", "oi_disc_fwd_small_workspace_floats", "oi_disc_graph_create", True),
+               5: ("oi_disc_fwd_small128", "oi_disc_fwd_small128_workspace_floats", "oi_disc_graph_create128", False)}
 
 
 def disc_fwd_small(x, weights, whead, bhead, f12=None, theta_np=None, theta_dev=None, margins=(0, 0, 0, 0), slope=0.2):
@@ -1262,9 +1266,9 @@ def disc_fwd_small(x, weights, whead, bhead, f12=None, theta_np=None, theta_dev=
     x = _c(x)
     B, C, H, W = x.shape
     mx0, my0, mx1, my1 = (int(v) for v in margins)
-    big = len(weights) == 5   # the shipped 128 x 128 / five-block network (oi_disc_fwd_small128)
-    n = (L.oi_disc_fwd_small128_workspace_floats if big else L.oi_disc_fwd_small_workspace_floats)(B, C, mx0, mx1, my0, my1)
-    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+    fwd, wsf, _, hw = _DISC_SMALL[len(weights)]
+    assert hw or (H, W) == (128, 128)
+    ws = torch.empty(getattr(L, wsf)(B, C, mx0, mx1, my0, my1), dtype=torch.float32, device=x.device)
     key = (x.device, _stream().value or 0)
     ticket = _DISC_TICKETS.get(key)
     if ticket is None:
@@ -1273,7 +1277,7 @@ def disc_fwd_small(x, weights, whead, bhead, f12=None, theta_np=None, theta_dev=
             # this stream would then reuse counters that were never cleared.  Warm the entry point up before capturing.
             raise _l.OiHipError("oi_disc_fwd_small: first call on this stream is inside a stream capture; call it once eagerly "
                                 "(warm-up) before capturing")
-        ticket = _DISC_TICKETS[key] = torch.zeros(4097, dtype=torch.int32, device=x.device)   # OI_TICKET_WORDS
+        ticket = _DISC_TICKETS[key] = torch.zeros(_l.TICKET_WORDS, dtype=torch.int32, device=x.device)
     out_dim = whead.shape[0]
     logits = _new(x, B, out_dim)
     th_host = th_arr = None
@@ -1282,15 +1286,9 @@ def disc_fwd_small(x, weights, whead, bhead, f12=None, theta_np=None, theta_dev=
         assert th_arr.size == 6 * B                                             # values into the kernel arguments
         th_host = th_arr.ctypes.data_as(ctypes.c_void_p)
     ws_ = [_c(w) for w in weights]
-    if big:
-        assert (H, W) == (128, 128)
-        _l.check(L.oi_disc_fwd_small128(_p(x), th_host, _p(_c(theta_dev)), _p(_c(f12)) if f12 is not None else _p(x), mx0, mx1, my0, my1,
-                                        *[_p(w) for w in ws_], _p(_c(whead)), _p(_c(bhead)), _p(ws), _vp(ticket.data_ptr()), _p(logits),
-                                        B, C, int(ws_[4].shape[0]), int(out_dim), float(slope), _stream()), "oi_disc_fwd_small128")
-        return logits
-    _l.check(L.oi_disc_fwd_small(_p(x), th_host, _p(_c(theta_dev)), _p(_c(f12)) if f12 is not None else _p(x), mx0, mx1, my0, my1,
-                                 *[_p(w) for w in ws_], _p(_c(whead)), _p(_c(bhead)), _p(ws), _vp(ticket.data_ptr()), _p(logits),
-                                 B, C, H, W, int(ws_[3].shape[0]), int(out_dim), float(slope), _stream()), "oi_disc_fwd_small")
+    _l.check(getattr(L, fwd)(_p(x), th_host, _p(_c(theta_dev)), _p(_c(f12)) if f12 is not None else _p(x), mx0, mx1, my0, my1,
+                             *[_p(w) for w in ws_], _p(_c(whead)), _p(_c(bhead)), _p(ws), _vp(ticket.data_ptr()), _p(logits),
+                             B, C, *((H, W) if hw else ()), int(ws_[-1].shape[0]), int(out_dim), float(slope), _stream()), fwd)
     return logits
 
 
@@ -1362,28 +1360,22 @@ class DiscGraph:
         assert launch in ("eager", "graph"), launch
         self.eager = launch == "eager"
         mx0, my0, mx1, my1 = (int(v) for v in margins) if self.aug else (0, 0, 0, 0)
-        self.big = len(weights) == 5   # the shipped 128 x 128 / five-block network: launch by launch only (oi_disc_graph_create128)
+        nb = len(weights)
+        _, wsf, create, hw = _DISC_SMALL[nb]
+        self.big = not hw   # the shipped 128 x 128 / five-block network: launch by launch only
         if self.big and launch != "eager":
             raise _l.OiHipError("ops.DiscGraph: the 128 x 128 plan is launched launch by launch (launch='eager')")
-        n = (L.oi_disc_fwd_small128_workspace_floats if self.big else L.oi_disc_fwd_small_workspace_floats)(B, C, mx0, mx1, my0, my1)
-        self.ws = torch.empty(n, dtype=torch.float32, device=device)
-        self.ticket = torch.zeros(4097, dtype=torch.int32, device=device)   # OI_TICKET_WORDS, this graph's own
+        assert hw or (H, W) == (128, 128)
+        self.ws = torch.empty(getattr(L, wsf)(B, C, mx0, mx1, my0, my1), dtype=torch.float32, device=device)
+        self.ticket = torch.zeros(_l.TICKET_WORDS, dtype=torch.int32, device=device)   # this graph's own
         self.logits = torch.empty(B, whead.shape[0], dtype=torch.float32, device=device)
         # (the graph holds raw pointers: keep the tensors it was built from alive)
-        nb = len(weights)
         self.keep = [_c(w) for w in weights] + [_c(whead), _c(bhead), _c(f12) if f12 is not None else None]
         self.handle = ctypes.c_void_p()
-        if self.big:
-            assert (H, W) == (128, 128)
-            _l.check(L.oi_disc_graph_create128(ctypes.byref(self.handle), int(self.aug), _p(self.keep[nb + 2]), mx0, mx1, my0, my1,
-                                               *[_p(w) for w in self.keep[:5]], _p(self.keep[5]), _p(self.keep[6]), _p(self.ws),
-                                               _vp(self.ticket.data_ptr()), _p(self.logits), B, C, int(self.keep[4].shape[0]),
-                                               int(whead.shape[0]), float(slope)), "oi_disc_graph_create128")
-            return
-        _l.check(L.oi_disc_graph_create(ctypes.byref(self.handle), int(self.aug), _p(self.keep[6]), mx0, mx1, my0, my1,
-                                        *[_p(w) for w in self.keep[:4]], _p(self.keep[4]), _p(self.keep[5]), _p(self.ws),
-                                        _vp(self.ticket.data_ptr()), _p(self.logits), B, C, H, W, int(self.keep[3].shape[0]),
-                                        int(whead.shape[0]), float(slope)), "oi_disc_graph_create")
+        _l.check(getattr(L, create)(ctypes.byref(self.handle), int(self.aug), _p(self.keep[nb + 2]), mx0, mx1, my0, my1,
+                                    *[_p(w) for w in self.keep[:nb + 2]], _p(self.ws), _vp(self.ticket.data_ptr()), _p(self.logits),
+                                    B, C, *((H, W) if hw else ()), int(self.keep[nb - 1].shape[0]), int(whead.shape[0]),
+                                    float(slope)), create)
 
     def __call__(self, x, theta_np=None, fresh=False):
         """`fresh` (eager launches only): the result goes to a new tensor instead of the plan's own buffer."""

@@ -868,7 +868,10 @@ def test_small_batch_discriminator_forward_vs_oracle_and_general_path(monkeypatc
     scale = max(1.0, float(ref.abs().max()))
     assert d_small.shape == (B, out_dim) and torch.equal(d_small, d_again)
     assert maxdiff(d_small.cpu(), ref) < 2e-5 * scale and maxdiff(d_small, d_gen) < 2e-5 * scale
-    # (b) with the augmentation: identical numpy draws for both paths, and the oracle at a pinned percentile
+    # (b) with the augmentation: identical numpy draws for both paths (FAST_ADA off: the small plan with host matrices at the
+    # static margins | the pipe at margins fitted to the draw + the general chain), and the oracle at a pinned percentile.
+    # Measured on an MI355X against the bar of 2e-5 (scale 1: these logits are O(1e-3)): 6.0e-8 / 5.7e-8 / 3.4e-8 at B = 1 / 3 / 4
+    monkeypatch.setattr(DM, "FAST_ADA", False)
     with torch.no_grad():
         monkeypatch.setattr(DM, "SMALL_PATH", True)
         np.random.seed(3)
@@ -876,7 +879,10 @@ def test_small_batch_discriminator_forward_vs_oracle_and_general_path(monkeypatc
         monkeypatch.setattr(DM, "SMALL_PATH", False)
         np.random.seed(3)
         a_gen = D(x0.cuda())
+    monkeypatch.setattr(DM, "FAST_ADA", True)
+    print(f"small plan vs pipe + general chain, B={B}: {maxdiff(a_small, a_gen):.3e} (bar {2e-5 * scale:.1e})")
     assert maxdiff(a_small, a_gen) < 2e-5 * scale, maxdiff(a_small, a_gen)
+    assert not torch.equal(a_small, a_gen)     # really a second path
     assert maxdiff(a_small, d_small) > 1e-4    # the augmentation did something
     pct = 0.7
     p = torch.tensor(pct, dtype=torch.float64)
@@ -1060,7 +1066,6 @@ def test_ada_discriminator_eager_forward_draws_in_the_library(B, in_dim, out_dim
         assert torch.equal(a, b)
         # (d) the numpy route: switched off, or debug_percentile pinned by an instance override
         monkeypatch.setattr(DM, "FAST_ADA", False)
-        DM._FAST_ADA.pop(D, None)
         np.random.seed(8); c = D(x).clone()
         np.random.seed(8)
         th_np = D.aug.theta_for(D.aug.sample_G_inv(x, None), m, H, W)
@@ -1073,6 +1078,119 @@ def test_ada_discriminator_eager_forward_draws_in_the_library(B, in_dim, out_dim
         d = D(x).clone()
         th_p = D.aug.theta_for(orig(x, 0.7), m, H, W)
         assert torch.equal(d, D._forward_small(x, f12=D.aug.Hz_geom, theta_np=th_p, margins=m))
+
+
+def _o1_weights(D):
+    with torch.no_grad():   # variance-preserving weights: O(1) logits (the default initialisation gives 1e-3)
+        for p_ in D.parameters():
+            p_.copy_((torch.rand_like(p_) * 2 - 1) * (6.0 / (1.04 * p_[0].numel())) ** 0.5)
+    return D
+
+
+def _numpy_draw_routes(D, x, seed):
+    """From numpy's draws for `seed`: (the pipe's explicit launches at margins fitted to the draw + the general chain, the small
+    plan with the same draws' matrices at the static margins)."""
+    import oi_amd.discriminator as DM
+    import oi_amd.ops as OPS
+    B, _, H, W = x.shape
+    np.random.seed(seed)
+    G = D.aug.sample_G_inv(x, None)
+    mf, m = D.aug.margins_for(G, H, W), D.aug.static_margins(H, W)
+    xa = OPS.ada_geom_fwd(x, torch.from_numpy(D.aug.theta_for(G, mf, H, W)).cuda(), D.aug.Hz_geom, mf)
+    small = D._forward_small(x, f12=D.aug.Hz_geom, theta_np=D.aug.theta_for(G, m, H, W), margins=m).clone()
+    small_path, DM.SMALL_PATH = DM.SMALL_PATH, False
+    try:
+        return DM.DCDiscriminator.forward(D, xa).clone(), small
+    finally:
+        DM.SMALL_PATH = small_path
+
+
+@pytest.mark.parametrize("B", [1, 4])
+def test_ada_discriminator_reads_the_switches_on_every_call(B, monkeypatch):
+    """Once a library-drawn call has filled the memo (DM._FAST_ADA[D]), FAST_ADA / SMALL_PATH = False still take the next call
+    off that route -- nothing is popped by hand -- and the route answers again when the switch is set back.  FAST_ADA off: the
+    small plan with numpy's draws, bit for bit; SMALL_PATH off: the pipe + the general chain (2e-5 x scale, the bar of
+    test_small_batch_discriminator_forward_vs_oracle_and_general_path), and not the small plan's bits."""
+    import oi_amd.discriminator as DM
+    D = _o1_weights(_ada_disc(3, 7).cuda().eval())
+    H = W = 64
+    m = D.aug.static_margins(H, W)
+    x = torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(B)).cuda()
+
+    def call(seed):
+        np.random.seed(seed)
+        return D(x).clone()
+
+    with torch.no_grad():
+        a = call(5)
+        assert DM._FAST_ADA.get(D) is not None
+        np.random.seed(5)
+        assert torch.equal(a, D._forward_small(x, f12=D.aug.Hz_geom, theta_np=D.aug.theta_fast(B, H, W), margins=m))
+        general, small = _numpy_draw_routes(D, x, 5)
+        scale = max(1.0, float(general.abs().max()))
+        monkeypatch.setattr(DM, "FAST_ADA", False)
+        b = call(5)
+        assert torch.equal(b, small) and not torch.equal(b, a)
+        monkeypatch.setattr(DM, "FAST_ADA", True)
+        assert torch.equal(call(5), a) and DM._FAST_ADA.get(D) is not None
+        monkeypatch.setattr(DM, "SMALL_PATH", False)
+        c = call(5)
+        assert maxdiff(c, general) < 2e-5 * scale and not torch.equal(c, small) and not torch.equal(c, a), maxdiff(c, general)
+        monkeypatch.setattr(DM, "SMALL_PATH", True)
+        assert torch.equal(call(5), a) and DM._FAST_ADA.get(D) is not None
+
+
+def test_shipped_128_discriminator_reads_small_path_128_on_every_call(monkeypatch, tag="v_"):
+    """The same for SMALL_PATH_128 on the shipped 128 x 128 network (F14's weights) at batch 1."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import oi_amd.discriminator as DM
+    from test_gpu_backward import _f14_net
+    g = load_golden("f14_discriminator_128")
+    D, _, _ = _f14_net(g, tag, 1)
+    del D.aug.forward                        # (_f14_net pins the percentile through `forward`)
+    D = D.eval()
+    x = g[f"{tag}b1_x"].cuda()
+    with torch.no_grad():
+        np.random.seed(5); a = D(x).clone()
+        assert DM._FAST_ADA.get(D) is not None
+        general, small = _numpy_draw_routes(D, x, 5)
+        monkeypatch.setattr(DM, "SMALL_PATH_128", False)
+        np.random.seed(5); c = D(x).clone()
+        assert maxdiff(c, general) < 2e-5 * max(1.0, float(general.abs().max())), maxdiff(c, general)
+        assert not torch.equal(c, small) and not torch.equal(c, a)
+        monkeypatch.setattr(DM, "SMALL_PATH_128", True)
+        np.random.seed(5)
+        assert torch.equal(D(x), a) and DM._FAST_ADA.get(D) is not None
+
+
+def test_ada_discriminator_memo_follows_replaced_parameters():
+    """A Parameter OBJECT replaced after the memo was filled -- by assignment, then by load_state_dict(assign=True) -- is the
+    one the next call reads: bit-equal to the explicit route on the live weights, and not the old weights' answer (the memo
+    keeps no Parameter; it compares the live addresses each call)."""
+    import oi_amd.discriminator as DM
+    D = _o1_weights(_ada_disc(3, 7).cuda().eval())
+    B, H, W = 1, 64, 64
+    m = D.aug.static_margins(H, W)
+    x = torch.rand(B, 3, H, W, generator=torch.Generator().manual_seed(2)).cuda()
+
+    def both(seed):
+        np.random.seed(seed); got = D(x).clone()
+        np.random.seed(seed); th = D.aug.theta_fast(B, H, W)
+        return got, D._forward_small(x, f12=D.aug.Hz_geom, theta_np=th, margins=m)
+
+    with torch.no_grad():
+        before, want = both(9)
+        assert DM._FAST_ADA.get(D) is not None and torch.equal(before, want)
+        old = D.blocks[2].weight
+        D.blocks[2].weight = torch.nn.Parameter(0.5 * old.detach())
+        got, want = both(9)
+        assert torch.equal(got, want) and maxdiff(got, before) > 1e-4, maxdiff(got, before)
+        assert DM._FAST_ADA.get(D) is not None
+        sd2 = {k: (0.5 * v if k == "blocks.0.weight" else v).detach().clone() for k, v in D.state_dict().items()}
+        D.load_state_dict(sd2, assign=True)
+        got2, want2 = both(9)
+        assert torch.equal(got2, want2) and maxdiff(got2, got) > 1e-4, maxdiff(got2, got)
 
 
 @pytest.mark.parametrize("B,in_dim,out_dim", [(64, 3, 7), (16, 1, 1)])

@@ -134,9 +134,15 @@ conv4x4_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, con
 // ------------------------------------------------------------------------------------------
 // Large-batch form of the same convolution (M = B * Ho * Wo >= 2048 pixels: discriminator batches of 16+, e.g. the
 // B = 64 row of SURVEY.md 8d): an LDS-tiled implicit GEMM on the fp16 matrix cores with fp32 operands split into two
-// fp16 limbs (hi + lo = 22 mantissa bits, three v_mfma_f32_32x32x16_f16 per product, fp32 accumulate -- the F16X3 mode of
-// the MLP kernels; conv inputs are images / LeakyReLU activations of O(1), weights O(0.1): no scaling needed, and an
-// |x| >= 65504 would surface as inf, not as a silent error).
+// fp16 limbs (hi = fp16(v), lo = fp16(v - hi), three v_mfma_f32_32x32x16_f16 per product, fp32 accumulate -- the F16X3 mode
+// of the MLP kernels, but UNSCALED: hi + lo holds 22 mantissa bits only while lo is a normal fp16, |v| >= 2^-3; below that
+// lo is subnormal and v is held to 2^-25 absolute -- nine operands in ten of a discriminator, whose weights are 0.01-0.1).
+// Measured envelope (max error / rms of an fp64 convolution; tests/test_gpu_disc_regimes.py): 1-5e-6, the fp32
+// kernels' own level, from variance-preserving weights upwards (layer inputs of 1 ... 1e4); 4e-6 ... 1.1e-5 at nn.Conv2d's
+// default initialisation, on white-background images and on binary masks (layer inputs of 0.07-0.15): inside the
+// project's 2e-5; outside it below that, gradually: 3-5e-5 (30x fp32) once a layer's inputs have fallen to ~4e-3 (dark
+// images, weights shrunk 5x).  An input of |x| >= 65520 splits into hi = inf, lo = -inf: every output it touches is NaN, and so
+// is every logit of that image -- never a finite wrong value (the `overflow` regime holds the kernel to that).
 //   workgroup tile   64 channels x TM pixels (TM = 128, or 64 when that is what fills the chip) x 64 taps per K chunk
 //   wave (4)         32 channels x TM/2 pixels: TM/64 accumulator blocks, 3 MFMAs per block and 16-tap step
 //   LDS              both operands in MFMA-fragment order [block][k-step][lane][8 x fp16], hi plane | lo plane: every
@@ -990,8 +996,9 @@ int oi_conv4x4_fwd_arena(const float* x, const float* w, const float* bias, floa
   hipStream_t st = oi::as_stream(stream);
   const bool y_is_zero = (flags & OI_CONV_Y_IS_ZERO) != 0;
   // OI_CONV_ANY_SCALE: an operand may be a gradient (the R1 double backward feeds d loss / d image and d loss / d w through
-  // this entry): the tiled kernel's UNSCALED fp16 limbs lose precision below |v| ~ 3e-4 and flush below ~3e-8, so such
-  // calls stay on the fp32 matrix cores
+  // this entry): the tiled kernel's UNSCALED fp16 limbs hold an operand to 2^-25 absolute once |v| < 2^-3 and to nothing
+  // below 3e-8 -- measured 1e-5 (block 1) to 5e-5 (block 3) of the output's rms at inputs of ~4e-3, against 3-5e-6 on this
+  // path at any scale (tests/test_gpu_disc_regimes.py: L1_b32 against L1_b32_any) -- so such calls stay on the fp32 matrix cores
   const bool any_scale = (flags & OI_CONV_ANY_SCALE) != 0;
   // large batches: LDS-tiled F16X3 implicit GEMM, K never split
   const int K = Cin * 16;

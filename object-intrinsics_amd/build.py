@@ -20,7 +20,9 @@ SOURCES = ["mlp.hip", "mlp_fwd3.hip", "mlp_fwd3b.hip", "color_head.hip", "render
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"] + os.environ.get("OI_FLAGS", "").split()
 # per-file extra flags.  mlp_fwd3.hip pins 256 parked values to the AGPR half of the register file; hipcc's default
 # (AGPR-form MFMA accumulators) would need 32 more AGPRs than exist, the VGPR form keeps the accumulators with the VALU.
-EXTRA = {"mlp_fwd3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+# Without the SLP vectoriser: it packs the epilogues' fp32 pairs into v_pk_*_f32, which issue slower beside MFMAs than the two
+# scalar instructions (600 of them sat between the MFMAs of the f16x3 kernel; tools/isa_gaps.py, tests/test_isa_full3_gaps.py).
+EXTRA = {"mlp_fwd3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"],
          # (224 AGPRs hold the parked cosines; without the SLP vectoriser hipcc selects v_fma_mix_f32 for acc * fp16 half)
          "mlp_fwd3b.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"],
          # backward sweep + weight-gradient GEMM: same choice -- no private-memory scratch left (76 spilled dwords before),

@@ -68,21 +68,16 @@ __device__ __forceinline__ int cu_slot_id() {
   return (int)(xcc * 256 + cu);
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// Packed fp32 arithmetic of the epilogues, as 2-vectors (hipcc unpacks v_pk_*_f32 it finds in the shadow of an MFMA on gfx950)
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-  return __builtin_elementwise_fma(a, b, c);
-}
-__device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) {
-  return a * b;
-}
-// a * s with the scalar s taken from the low dword of its register for both halves
-__device__ __forceinline__ f32x2 pk_mul_s(f32x2 a, float s) {
-  return a * s;
-}
-// FiLM phase of an accumulator pair (the rows and the accumulators sit in aligned register pairs)
-__device__ __forceinline__ f32x2 film_phase2(const f32x4& a, const f32x4& b, int k, float acc0, float acc1) {
-  return pk_fma(f32x2{a[k], a[k + 1]}, f32x2{acc0, acc1}, f32x2{b[k], b[k + 1]});
+// The fp32 arithmetic of the epilogues that run between MFMAs is written per component, and the file is built without
+// the SLP vectoriser (build.py): hipcc does NOT unpack a v_pk_*_f32 it finds in the shadow of an MFMA on gfx950 (the
+// vectorised build of this file carried 600 of them there, tools/isa_gaps.py), and a packed fp32 instruction beside an
+// MFMA issues slower than the two scalar ones it replaces.
+struct Pair2 {
+  float x, y;
+};
+// FiLM phase of an accumulator pair
+__device__ __forceinline__ Pair2 film_phase2(const f32x4& a, const f32x4& b, int k, float acc0, float acc1) {
+  return Pair2{fmaf(a[k], acc0, b[k]), fmaf(a[k + 1], acc1, b[k + 1])};
 }
 // max(m, |x|, |y|) in one v_max3_f32
 __device__ __forceinline__ float max3_abs(float m, float x, float y) {
@@ -120,30 +115,39 @@ __device__ __forceinline__ void split_limbs(const float (&act)[64], Limbs& bh, L
 }
 
 struct NoTail {
-  __device__ __forceinline__ void operator()(int, int) const {}
+  __device__ __forceinline__ void operator()(int, int, int) const {}
 };
 template <class T> struct is_no_tail { static constexpr bool value = false; };
 template <> struct is_no_tail<NoTail> { static constexpr bool value = true; };
 
 // One layer product of the stream: acc = W_img . B (three fp16 MFMAs per product), output block t outer, one
-// scheduling window per k-step = 3 MFMAs + the epilogue work that hides behind them:
-//   block 0, k-steps 0..5   TAIL(3, rp): the PREVIOUS layer's block-3 epilogue pairs (8 of them, spread 2 1 1 2 1 1);
+// window per k-step = 3 MFMAs = 3 GAPS, and the epilogue work that hides behind them.  With ONE wave per SIMD nothing but
+// the wave's own independent instructions fills the matrix pipe's shadow: a 32x32x16 MFMA occupies the pipe for 32 cycles
+// and holds vector issue for 8 of them, so 24 cycles of other vector issue (six 4-cycle instructions, or one 8-cycle
+// v_sin / v_cos and four others) hide per gap and everything past that is added to the tile time.  Every epilogue pair is
+// therefore written in THREE STAGES q = 0, 1, 2, one per gap of its window (the pair's values in flight between two
+// stages live in the kernel's `st` registers), and the order is pinned by source order: a sched_barrier(0) behind every
+// gap (sched_group_barrier groups do not spread a pair -- it is one short dependent chain -- and left two gaps of
+// three nearly empty; tools/isa_gaps.py is the census).
+//   gap 0 of every window   the two A-fragment reads of the next k-step + stage 0
+//   gap 1, k-steps 0..15    DMA(i): one 1 KiB LDS-DMA piece of the next layer's image
+//   block 0, k-steps 0..6   TAIL(3, rp, q): the PREVIOUS layer's block-3 epilogue pairs (8 of them, spread 2 1 1 1 1 1 1);
 //                           they complete THIS layer's B limbs for k-steps 6 and 7 just before those are consumed
 //   after block 0           MID(): runs once, when the previous layer's output vector is complete
-//   blocks 1..3             EPI(t - 1, s): this layer's epilogue pair s of the block that has just completed
+//   blocks 1..3             EPI(t - 1, s, q): this layer's epilogue pair s of the block that has just completed
 // This layer's own block-3 pairs are left to the caller: the next layer's TAIL, or run_tail().
 // An epilogue pair (tb, rp) consumes accumulator slots 2 rp, 2 rp + 1 of block tb = act indices 16 tb + 2 rp (+1).
-// With ONE wave per SIMD nothing but the wave's own independent instructions fills a dependency stall, and an MFMA that
-// follows an MFMA waits for the matrix pipe with the whole wave behind it: sched_group_barrier pins every window to
-// MFMA, n VALU, MFMA, n VALU, MFMA, rest.
 constexpr int F3_ADIST = 1;           // A-fragment k-steps requested ahead (see stream_layer)
-constexpr int F3_VALU_PER_MFMA = 6;   // n per epilogue pair
+constexpr int F3_DMA_PIECES = 16;     // LDS-DMA pieces of the NEXT image per wave, one per window (gap 1) of blocks 0 and 1
 struct NoMid {
   __device__ __forceinline__ void operator()() const {}
 };
-template <class TAIL, class MID, class EPI>
+struct NoDma {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+template <class TAIL, class MID, class EPI, class DMA>
 __device__ __forceinline__ void stream_layer(const char* lds, const LayOff& y, const Limbs& bh, const Limbs& bl,
-                                             f32x16 (&acc)[4], TAIL&& tail, MID&& mid, EPI&& epi) {
+                                             f32x16 (&acc)[4], TAIL&& tail, MID&& mid, EPI&& epi, DMA&& dma) {
   constexpr bool HAS_TAIL = !is_no_tail<std::remove_cv_t<std::remove_reference_t<TAIL>>>::value;
   // A fragments (hi / lo limb of the image) are requested F3_ADIST k-steps ahead of their MFMAs
   constexpr int AD = F3_ADIST;
@@ -160,21 +164,19 @@ __device__ __forceinline__ void stream_layer(const char* lds, const LayOff& y, c
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const int cur = t * 8 + s, nxt = cur + AD;
-      if (nxt < 32) {
-        ah[nxt % (AD + 1)] = lds_f4(lds, nxt * 1024, y.wl);
-        al[nxt % (AD + 1)] = lds_f4(lds, nxt * 1024, y.wh);
-      }
-      int npairs = 0;
-      if (t == 0) {
-        if (HAS_TAIL && s < 6) {
-          constexpr int first[7] = {0, 2, 3, 4, 6, 7, 8};
-          for (int rp = first[s]; rp < first[s + 1]; ++rp) tail(3, rp);
-          npairs = first[s + 1] - first[s];
+      // stage q of this window's pair(s); the one window that carries two tail pairs runs them back to back, two stages per gap
+      auto gap = [&](int q) {
+        if (t == 0) {
+          if (HAS_TAIL && s == 0) {
+            tail(3, (2 * q) / 3, (2 * q) % 3);
+            tail(3, (2 * q + 1) / 3, (2 * q + 1) % 3);
+          } else if (HAS_TAIL && s < 7) {
+            tail(3, s + 1, q);
+          }
+        } else {
+          epi(t - 1, s, q);
         }
-      } else {
-        epi(t - 1, s);
-        npairs = 1;
-      }
+      };
       const int ci = cur % (AD + 1);
       const f16x8 wh = __builtin_bit_cast(f16x8, ah[ci]);
       const f16x8 wl = __builtin_bit_cast(f16x8, al[ci]);
@@ -182,18 +184,18 @@ __device__ __forceinline__ void stream_layer(const char* lds, const LayOff& y, c
       const f16x8 vh = __builtin_bit_cast(f16x8, uh);
       const f16x8 vl = __builtin_bit_cast(f16x8, ul);
       acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, vh, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, vl, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, vh, acc[t], 0, 0, 0);
-      // one k-step per scheduling window
-      if (npairs >= 1) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if (npairs <= 1) __builtin_amdgcn_sched_group_barrier(0x002, F3_VALU_PER_MFMA, 0);
-          else __builtin_amdgcn_sched_group_barrier(0x002, 2 * F3_VALU_PER_MFMA, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      if (nxt < 32) {
+        ah[nxt % (AD + 1)] = lds_f4(lds, nxt * 1024, y.wl);
+        al[nxt % (AD + 1)] = lds_f4(lds, nxt * 1024, y.wh);
       }
+      gap(0);
+      __builtin_amdgcn_sched_barrier(0);
+      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, vl, acc[t], 0, 0, 0);
+      if (cur < F3_DMA_PIECES) dma(cur);
+      gap(1);
+      __builtin_amdgcn_sched_barrier(0);
+      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, vh, acc[t], 0, 0, 0);
+      gap(2);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (t == 0) {
@@ -202,14 +204,18 @@ __device__ __forceinline__ void stream_layer(const char* lds, const LayOff& y, c
     }
   }
 }
-// block 3's epilogue with nothing to hide behind: two pairs (four independent chains) per window
+// block 3's epilogue with nothing to hide behind: two pairs (four independent chains) per window.  The assembly comments
+// mark the section as exposed for tools/isa_gaps.py (packed fp32 would be welcome here: nothing runs beside it).
 template <class EPI>
 __device__ __forceinline__ void run_tail(EPI&& epi) {
+  asm volatile("; oi-exposed-begin");
 #pragma unroll
   for (int rp = 0; rp < 8; ++rp) {
-    epi(3, rp);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) epi(3, rp, q);
     if (rp & 1) __builtin_amdgcn_sched_barrier(0);
   }
+  asm volatile("; oi-exposed-end");
 }
 
 // -DOI_F3_PROF: per-phase shader-clock accounting (tools/dbg/phase_prof3.py)
@@ -297,27 +303,38 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   // address VGPRs (global_load_lds with flat pointers kept 16 address pairs alive across the whole kernel)
   const __amdgpu_buffer_rsrc_t img_rs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(mats), 0, NMAT * LB, 0x00020000);
-  auto prefetch = [&](int pos) {
+  // Piece i (0..15) of this wave's share of ring position pos.  A wave copies 16 consecutive KiB, 4 KiB per (M0, soffset)
+  // setting: the instruction's immediate offset advances the LDS and the global address alike, so four 1 KiB copies share
+  // one M0 / soffset pair.  The layer that runs beside the copy issues one piece per k-step window (stream_layer): sixteen
+  // pieces in one burst in front of the layer's first MFMA have nothing to hide behind.
+  constexpr int F3_PIECES = LB / 1024 / F3_WAVES;
+  static_assert(F3_PIECES == F3_DMA_PIECES, "stream_layer issues every piece of a wave's share");
+  auto prefetch_piece = [&](int pos, int i) {
     const int m = pos < 7 ? pos : (pos < 12 ? 20 - pos : (pos < 14 ? pos - 12 : (pos < 16 ? 22 - pos : 14)));
-    // a wave copies 16 consecutive KiB, 4 KiB per (M0, soffset) setting: the instruction's immediate offset advances the
-    // LDS and the global address alike, so four 1 KiB copies share one M0 / soffset pair (6 instead of 16 instructions per
-    // 4 KiB; bit-identical results, -1.3 % kernel time)
-#pragma unroll
-    for (int q = 0; q < LB / 4096 / F3_WAVES; ++q) {
-      const int c = (wave * (LB / 4096 / F3_WAVES) + q) * 4096;
-      auto* dst = (__attribute__((address_space(3))) void*)(lds + F3_BLOB + (pos & 1) * LB + c);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 1024, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 2048, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 3072, 0);
+    const int c = (wave * (F3_PIECES / 4) + i / 4) * 4096;
+    auto* dst = (__attribute__((address_space(3))) void*)(lds + F3_BLOB + (pos & 1) * LB + c);
+    switch (i % 4) {
+      case 0: __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 0, 0); break;
+      case 1: __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 1024, 0); break;
+      case 2: __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 2048, 0); break;
+      default: __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rs, dst, 16, o.l16, m * LB + c, 3072, 0); break;
     }
   };
+  auto prefetch = [&](int pos) {
+#pragma unroll
+    for (int i = 0; i < F3_PIECES; ++i) prefetch_piece(pos, i);
+  };
+#define OI_DMA(POS) [&](int i) { prefetch_piece(POS, i); }
   auto lay = [&](int pos) {  // A-image lane bases of ring position pos
     LayOff y;
     y.wl = o.l16 + F3_BLOB + (pos & 1) * LB;
     y.wh = y.wl + 32768;
     y.wq = 0;
     y.f16 = 0;
+    // opaque per layer: the A-fragment addresses are "this base + immediate".  Left transparent, the ring slot's offset (past the
+    // 16-bit immediate in the odd slot) is folded into one address register per k-step, equal addresses of different layers are
+    // merged, and dozens of address registers live across the whole sweep (they end up in AGPRs and push parked values to scratch).
+    asm volatile("" : "+v"(y.wl), "+v"(y.wh));
     return y;
   };
   // lane base of FiLM layer l's rows: [A | B | G] x 128 floats (see the staging loop)
@@ -361,6 +378,7 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   } rw[2];
   f32x4 fv;
   float run = 1.f, vmax = 0.f, sdf_part = 0.f;
+  float st[6];                   // an epilogue pair's values in flight between its three stages (see stream_layer)
 
   // phi (revolutions) -> reduced phase; v_sin_f32 / v_cos_f32 take revolutions and are specified on [-256, 256]: v_fract
   // (exact) keeps any phase inside that domain.  (Feeding the unreduced phase differs by at most 1 ulp inside the
@@ -396,27 +414,34 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     }
   };
 
-  // Epilogue pair (tb, rp) of a forward FiLM layer whose rows sit at lane base FB: sin(phi) -> next limb set, reduced
-  // phase -> PARK.  NEXT: statement that requests the first group's rows of whatever epilogue follows this layer's last
-  // group (into rw[0]).
+  // Epilogue pair (tb, rp) of a forward FiLM layer whose rows sit at lane base FB, stage q: sin(phi) -> next limb set,
+  // reduced phase -> PARK.  NEXT: statement that requests the first group's rows of whatever epilogue follows this layer's
+  // last group (into rw[0]).
+  //   q = 0  phase FMAs, v_fract                     q = 1  first sine, park, row request     q = 2  second sine, limb split
 #define OI_FWD_EPI(FB, NH, NL, PARK, NEXT)                                                                 \
-  [&](int tb, int rp) {                                                                                    \
+  [&](int tb, int rp, int q) {                                                                             \
     const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);                                                    \
     Rows& R = rw[g & 1];                                                                                   \
-    if (k == 0) {                                                                                          \
-      if (g < 15) {                                                                                        \
-        rw[(g + 1) & 1].a = ROW_A(FB, g + 1);                                                              \
-        rw[(g + 1) & 1].b = ROW_B(FB, g + 1);                                                              \
-      } else {                                                                                             \
-        NEXT;                                                                                              \
+    if (q == 0) {                                                                                          \
+      const Pair2 ph = film_phase2(R.a, R.b, k, acc[tb][2 * rp], acc[tb][2 * rp + 1]);                     \
+      st[0] = reduce(ph.x);                                                                                \
+      st[1] = reduce(ph.y);                                                                                \
+    } else if (q == 1) {                                                                                   \
+      if (k == 0) {                                                                                        \
+        if (g < 15) {                                                                                      \
+          rw[(g + 1) & 1].a = ROW_A(FB, g + 1);                                                            \
+          rw[(g + 1) & 1].b = ROW_B(FB, g + 1);                                                            \
+        } else {                                                                                           \
+          NEXT;                                                                                            \
+        }                                                                                                  \
       }                                                                                                    \
+      st[2] = __builtin_amdgcn_sinf(st[0]);                                                                \
+      PARK(g, k, st[0]);                                                                                   \
+      PARK(g, k + 1, st[1]);                                                                               \
+    } else {                                                                                               \
+      split_pair(st[2], __builtin_amdgcn_sinf(st[1]), NH[2 * tb + (rp >> 2)][rp & 3],                      \
+                 NL[2 * tb + (rp >> 2)][rp & 3]);                                                          \
     }                                                                                                      \
-    const f32x2 ph = film_phase2(R.a, R.b, k, acc[tb][2 * rp], acc[tb][2 * rp + 1]);                 \
-    const float r0 = reduce(ph[0]), r1 = reduce(ph[1]);                                                    \
-    PARK(g, k, r0);                                                                                        \
-    PARK(g, k + 1, r1);                                                                                    \
-    split_pair(__builtin_amdgcn_sinf(r0), __builtin_amdgcn_sinf(r1), NH[2 * tb + (rp >> 2)][rp & 3],       \
-               NL[2 * tb + (rp >> 2)][rp & 3]);                                                            \
   }
   // Reverse sweep bookkeeping.  A reverse layer's input V_l = v_l * S_l is held as fp16 limbs with a power-of-two scale
   // S_l (run = 1 / S_l).  Its epilogue forms V_{l-1} = (W^T V_l) * G_{l-1} cos(phi_{l-1}) * sg and splits it into limbs
@@ -441,25 +466,32 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     vmax = 0.f;                                                                \
   }
   // Epilogue pair of reverse layer l: V_{l-1} -> limb set (NH, NL); r_{l-1} from BANK, the G rows of layer l-1 at FB
+  //   q = 0  both bank reads, first cosine      q = 1  second cosine, v0, row request      q = 2  v1, maximum, limb split
 #define OI_REV_EPI(FB, BANK, NH, NL, NEXT)                                                                 \
-  [&](int tb, int rp) {                                                                                    \
+  [&](int tb, int rp, int q) {                                                                             \
     const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);                                                    \
     Rows& R = rw[g & 1];                                                                                   \
-    if (k == 0) {                                                                                          \
-      if (g < 15) {                                                                                        \
-        rw[(g + 1) & 1].c = ROW_G(FB, g + 1);                                                              \
-      } else {                                                                                             \
-        NEXT;                                                                                              \
+    if (q == 0) {                                                                                          \
+      st[0] = __builtin_amdgcn_cosf(from_acc(BANK[g][k]));                                                 \
+      st[1] = from_acc(BANK[g][k + 1]);                                                                    \
+    } else if (q == 1) {                                                                                   \
+      if (k == 0) {                                                                                        \
+        if (g < 15) {                                                                                      \
+          rw[(g + 1) & 1].c = ROW_G(FB, g + 1);                                                            \
+        } else {                                                                                           \
+          NEXT;                                                                                            \
+        }                                                                                                  \
       }                                                                                                    \
+      st[2] = __builtin_amdgcn_cosf(st[1]);                                                                \
+      st[3] = (acc[tb][2 * rp] * sg) * (R.c[k] * st[0]);                                                   \
+      st[4] = acc[tb][2 * rp + 1] * sg;                                                                    \
+    } else {                                                                                               \
+      const float v1 = st[4] * (R.c[k + 1] * st[2]);                                                       \
+      vmax = max3_abs(vmax, st[3], v1);                                                                    \
+      split_pair(st[3], v1, NH[2 * tb + (rp >> 2)][rp & 3], NL[2 * tb + (rp >> 2)][rp & 3]);               \
     }                                                                                                      \
-    const f32x2 cs = {__builtin_amdgcn_cosf(from_acc(BANK[g][k])), __builtin_amdgcn_cosf(from_acc(BANK[g][k + 1]))};                     \
-    const f32x2 v = pk_mul(pk_mul_s(f32x2{acc[tb][2 * rp], acc[tb][2 * rp + 1]}, sg),                \
-                           pk_mul(f32x2{R.c[k], R.c[k + 1]}, cs));                                         \
-    vmax = max3_abs(vmax, v[0], v[1]);                                                                     \
-    split_pair(v[0], v[1], NH[2 * tb + (rp >> 2)][rp & 3], NL[2 * tb + (rp >> 2)][rp & 3]);                \
   }
 
-  const LayOff y1 = lay(0), y2 = lay(1), y3 = lay(2), y4 = lay(3), y5 = lay(4), y6 = lay(5), y7 = lay(6);
   const int F0 = film_base(0), F1 = film_base(1), F2 = film_base(2), F3 = film_base(3), F4 = film_base(4),
             F5 = film_base(5), F6 = film_base(6), F7 = film_base(7), F8 = film_base(8), F9 = film_base(9);
 #define NEXT_AB(FB) (rw[0].a = ROW_A(FB, 0), rw[0].b = ROW_B(FB, 0))
@@ -471,95 +503,94 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   F3_T(0);
   ring_sync();  // image 0 resident
   F3_T(2);
-  prefetch(1);
   auto park0 = OI_PARK(P0);
   auto park1 = OI_PARK(P1);
   auto park2 = OI_PARK(P2);
   auto park3 = OI_PARK(P3);
   auto e1 = OI_FWD_EPI(F1, BH, BL, no_park, NEXT_AB(F2));
-  stream_layer(lds, y1, AH, AL, acc, NoTail(), NoMid(), e1);
+  stream_layer(lds, lay(0), AH, AL, acc, NoTail(), NoMid(), e1, OI_DMA(1));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(2);
   auto e2 = OI_FWD_EPI(F2, AH, AL, no_park, NEXT_AB(F3));
-  stream_layer(lds, y2, BH, BL, acc, e1, NoMid(), e2);
+  stream_layer(lds, lay(1), BH, BL, acc, e1, NoMid(), e2, OI_DMA(2));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(3);
   auto e3 = OI_FWD_EPI(F3, BH, BL, park0, NEXT_AB(F4));
-  stream_layer(lds, y3, AH, AL, acc, e2, NoMid(), e3);
+  stream_layer(lds, lay(2), AH, AL, acc, e2, NoMid(), e3, OI_DMA(3));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(4);
   auto e4 = OI_FWD_EPI(F4, AH, AL, park1, NEXT_AB(F5));
-  stream_layer(lds, y4, BH, BL, acc, e3, NoMid(), e4);
+  stream_layer(lds, lay(3), BH, BL, acc, e3, NoMid(), e4, OI_DMA(4));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(5);
   auto e5 = OI_FWD_EPI(F5, BH, BL, park2, NEXT_AB(F6));
-  stream_layer(lds, y5, AH, AL, acc, e4, NoMid(), e5);
+  stream_layer(lds, lay(4), AH, AL, acc, e4, NoMid(), e5, OI_DMA(5));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(6);
   auto e6 = OI_FWD_EPI(F6, AH, AL, park3,
                        (NEXT_AB(F7), rw[0].c = ROW_A(F9, 0), rw[0].d = ROW_SIG(0)));
-  stream_layer(lds, y6, BH, BL, acc, e5, NoMid(), e6);
+  stream_layer(lds, lay(5), BH, BL, acc, e5, NoMid(), e6, OI_DMA(6));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(7);
   // layer 7: features a8 = sin(phi7) leave through the scratch slot (+ feat_out), sdf = a8 . wsig + bsig on the fly,
   // and the reverse sweep's first operand v7 = wsig * G7 * cos(phi7) is formed in place (r7 is never parked)
   // |v7| <= max|G7 w_sigma| (row 9): its fp16 scale is known before the first value exists
   pow2_for(gmax[9] * 2.0f);
   const float sg7 = sg;
-  auto e7 = [&](int tb, int rp) {
+  // (two sines and two cosines per pair: more than one 8-cycle instruction in a gap cannot be avoided here)
+  auto e7 = [&](int tb, int rp, int q) {
     const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
     Rows& R = rw[g & 1];
-    if (k == 0) {
-      if (g < 15) {
-        Rows& N = rw[(g + 1) & 1];
-        N.a = ROW_A(F7, g + 1);
-        N.b = ROW_B(F7, g + 1);
-        N.c = ROW_A(F9, g + 1);
-        N.d = ROW_SIG(g + 1);
-      } else {
-        NEXT_G(F6);
+    if (q == 0) {
+      const Pair2 ph = film_phase2(R.a, R.b, k, acc[tb][2 * rp], acc[tb][2 * rp + 1]);
+      st[0] = reduce(ph.x);
+      st[1] = reduce(ph.y);
+      st[2] = __builtin_amdgcn_sinf(st[0]);
+    } else if (q == 1) {
+      if (k == 0) {
+        if (g < 15) {
+          Rows& N = rw[(g + 1) & 1];
+          N.a = ROW_A(F7, g + 1);
+          N.b = ROW_B(F7, g + 1);
+          N.c = ROW_A(F9, g + 1);
+          N.d = ROW_SIG(g + 1);
+        } else {
+          NEXT_G(F6);
+        }
+      }
+      fv[k] = st[2];
+      sdf_part = fmaf(st[2], R.d[k], sdf_part);
+      asm volatile("" : "+v"(sdf_part));  // evaluated HERE: left alone the whole chain sinks behind the layer, its 128 sines alive
+      st[3] = (R.c[k] * sg7) * __builtin_amdgcn_cosf(st[0]);
+      st[4] = __builtin_amdgcn_sinf(st[1]);
+    } else {
+      fv[k + 1] = st[4];
+      sdf_part = fmaf(st[4], R.d[k + 1], sdf_part);
+      asm volatile("" : "+v"(sdf_part));
+      const float v1 = (R.c[k + 1] * sg7) * __builtin_amdgcn_cosf(st[1]);
+      vmax = max3_abs(vmax, st[3], v1);
+      split_pair(st[3], v1, BH[2 * tb + (rp >> 2)][rp & 3], BL[2 * tb + (rp >> 2)][rp & 3]);
+      if (k == 2) {
+        ws.store(0, g, o, fv);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, fv), feat_rs, feat_off + grp_f0(g) * 4, 0, 0);
       }
     }
-    const f32x2 ph = film_phase2(R.a, R.b, k, acc[tb][2 * rp], acc[tb][2 * rp + 1]);
-    f32x2 cs;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float r = reduce(ph[i]);
-      const float sn = __builtin_amdgcn_sinf(r);
-      fv[k + i] = sn;
-      sdf_part = fmaf(sn, R.d[k + i], sdf_part);
-      cs[i] = __builtin_amdgcn_cosf(r);
-    }
-    const f32x2 v = pk_mul(pk_mul_s(f32x2{R.c[k], R.c[k + 1]}, sg7), cs);
-    vmax = max3_abs(vmax, v[0], v[1]);
-    split_pair(v[0], v[1], BH[2 * tb + (rp >> 2)][rp & 3], BL[2 * tb + (rp >> 2)][rp & 3]);
-    if (k == 2) {
-      ws.store(0, g, o, fv);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, fv), feat_rs, feat_off + grp_f0(g) * 4, 0, 0);
-    }
   };
-  stream_layer(lds, y7, AH, AL, acc, e6, NoMid(), e7);
+  stream_layer(lds, lay(6), AH, AL, acc, e6, NoMid(), e7, OI_DMA(7));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(8);
 
   // ================= reverse, layers 7..3 =================
   // position 7..11 = transposed layers 7..3.  Every layer runs the previous layer's block-3 pairs during its own block 0.
   auto r7 = OI_REV_EPI(F6, P3, AH, AL, NEXT_G(F5));   // V6 = g7 * G6 cos(phi6)
-  stream_layer(lds, lay(7), BH, BL, acc, e7, OI_REV_MID(7), r7);
+  stream_layer(lds, lay(7), BH, BL, acc, e7, OI_REV_MID(7), r7, OI_DMA(8));
   {
     sdf_part += __shfl_xor(sdf_part, 32, 64);  // complete since e7's last pair (inside the layer above)
     const float sdf_v = sdf_part + *reinterpret_cast<const float*>(lds + F3_TABS + (H_SIG + C) * 4);
@@ -570,103 +601,117 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(9);
   auto r6 = OI_REV_EPI(F5, P2, BH, BL, NEXT_G(F4));
-  stream_layer(lds, lay(8), AH, AL, acc, r7, OI_REV_MID(6), r6);
+  stream_layer(lds, lay(8), AH, AL, acc, r7, OI_REV_MID(6), r6, OI_DMA(9));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(10);
   auto r5 = OI_REV_EPI(F4, P1, AH, AL, NEXT_G(F3));
-  stream_layer(lds, lay(9), BH, BL, acc, r6, OI_REV_MID(5), r5);
+  stream_layer(lds, lay(9), BH, BL, acc, r6, OI_REV_MID(5), r5, OI_DMA(10));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(11);
   auto r4 = OI_REV_EPI(F3, P0, BH, BL, (void)0);      // V3 = g4 * G3 cos(phi3)
-  stream_layer(lds, lay(10), AH, AL, acc, r5, OI_REV_MID(4), r4);
+  stream_layer(lds, lay(10), AH, AL, acc, r5, OI_REV_MID(4), r4, OI_DMA(11));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(12);
   // layer 3: g3 (in units of 1 / run) is parked while layers 0..2 are recomputed.  The park is an asm statement: hipcc pads
   // no MFMA-result -> reader hazard for it, so the value first passes through a VALU instruction the compiler does know
   // (a multiply by an opaque 1.0).  max|g3| for the scale of V2 is tracked on the way.
   float one = 1.0f;
   asm volatile("" : "+v"(one));
-  auto pg3 = [&](int tb, int rp) {
+  auto pg3 = [&](int tb, int rp, int q) {
     const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
-    const f32x2 a = pk_mul_s(f32x2{acc[tb][2 * rp], acc[tb][2 * rp + 1]}, one);
-    vmax = max3_abs(vmax, a[0], a[1]);
-    P0[g][k] = to_acc(a[0]);
-    P0[g][k + 1] = to_acc(a[1]);
+    if (q == 0) {
+      st[0] = acc[tb][2 * rp] * one;
+      st[1] = acc[tb][2 * rp + 1] * one;
+    } else if (q == 1) {
+      vmax = max3_abs(vmax, st[0], st[1]);
+      P0[g][k] = to_acc(st[0]);
+    } else {
+      P0[g][k + 1] = to_acc(st[1]);
+    }
   };
-  stream_layer(lds, lay(11), BH, BL, acc, r4, [&]() { vmax = 0.f; }, pg3);   // (V3's own maximum is not needed)
+  // (V3's own maximum is not needed)
+  stream_layer(lds, lay(11), BH, BL, acc, r4, [&]() { vmax = 0.f; }, pg3, OI_DMA(12));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(13);
   run_tail(pg3);
   F3_T(3);
 
   // ================= forward again, layers 0..2 =================
-  const LayOff z1 = lay(12), z2 = lay(13);
   NEXT_AB(F1);
+  {  // the point is read again here instead of living in three VGPRs through both sweeps (the register budget is full)
+    bool valid;
+    const long long pt = point_of(valid);
+    px = pts[pt * 3 + 0], py = pts[pt * 3 + 1], pz = pts[pt * 3 + 2];
+  }
   layer0(AH, AL, park1);  // r0
   F3_T(0);
   auto f1 = OI_FWD_EPI(F1, BH, BL, park2, (NEXT_AB(F2), NEXT_G(F2)));  // r1
-  stream_layer(lds, z1, AH, AL, acc, NoTail(), NoMid(), f1);
+  stream_layer(lds, lay(12), AH, AL, acc, NoTail(), NoMid(), f1, OI_DMA(13));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(14);
   // layer 2: V2 = g3 * G2 cos(phi2) * sg (the sine is not needed any more); |g3| <= its measured maximum
   pow2_for(fmaxf(vmax, __shfl_xor(vmax, 32, 64)) * gmax[2]);
   vmax = 0.f;
   const float sg2 = sg;
-  auto f2 = [&](int tb, int rp) {
+  auto f2 = [&](int tb, int rp, int q) {
     const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
     Rows& R = rw[g & 1];
-    if (k == 0) {
-      if (g < 15) {
-        Rows& N = rw[(g + 1) & 1];
-        N.a = ROW_A(F2, g + 1);
-        N.b = ROW_B(F2, g + 1);
-        N.c = ROW_G(F2, g + 1);
-      } else {
-        NEXT_G(F1);
+    if (q == 0) {
+      const Pair2 ph = film_phase2(R.a, R.b, k, acc[tb][2 * rp], acc[tb][2 * rp + 1]);
+      st[0] = reduce(ph.x);
+      st[1] = reduce(ph.y);
+    } else if (q == 1) {
+      if (k == 0) {
+        if (g < 15) {
+          Rows& N = rw[(g + 1) & 1];
+          N.a = ROW_A(F2, g + 1);
+          N.b = ROW_B(F2, g + 1);
+          N.c = ROW_G(F2, g + 1);
+        } else {
+          NEXT_G(F1);
+        }
       }
+      st[3] = (from_acc(P0[g][k]) * sg2) * (R.c[k] * __builtin_amdgcn_cosf(st[0]));
+      st[4] = from_acc(P0[g][k + 1]) * sg2;
+    } else {
+      const float v1 = st[4] * (R.c[k + 1] * __builtin_amdgcn_cosf(st[1]));
+      vmax = max3_abs(vmax, st[3], v1);
+      split_pair(st[3], v1, AH[2 * tb + (rp >> 2)][rp & 3], AL[2 * tb + (rp >> 2)][rp & 3]);
     }
-    const f32x2 ph = film_phase2(R.a, R.b, k, acc[tb][2 * rp], acc[tb][2 * rp + 1]);
-    const f32x2 cs = {__builtin_amdgcn_cosf(reduce(ph[0])), __builtin_amdgcn_cosf(reduce(ph[1]))};
-    const f32x2 v = pk_mul(pk_mul_s(f32x2{from_acc(P0[g][k]), from_acc(P0[g][k + 1])}, sg2), pk_mul(f32x2{R.c[k], R.c[k + 1]}, cs));
-    vmax = max3_abs(vmax, v[0], v[1]);
-    split_pair(v[0], v[1], AH[2 * tb + (rp >> 2)][rp & 3], AL[2 * tb + (rp >> 2)][rp & 3]);
   };
-  stream_layer(lds, z2, BH, BL, acc, f1, NoMid(), f2);
+  stream_layer(lds, lay(13), BH, BL, acc, f1, NoMid(), f2, OI_DMA(14));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(15);
 
   // ================= reverse, layers 2..0 =================
   auto r2 = OI_REV_EPI(F1, P2, BH, BL, NEXT_G(F0));   // V1 = g2 * G1 cos(phi1)
-  stream_layer(lds, lay(14), AH, AL, acc, f2, OI_REV_MID(2), r2);
+  stream_layer(lds, lay(14), AH, AL, acc, f2, OI_REV_MID(2), r2, OI_DMA(15));
   F3_T(1);
   ring_sync();
   F3_T(2);
-  prefetch(16);
   // layer 1: v0 = g1 * G0 cos(phi0) stays fp32 (layer 0's transposed product runs on the VALU)
-  auto r1 = [&](int tb, int rp) {
+  auto r1 = [&](int tb, int rp, int q) {
     const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
     Rows& R = rw[g & 1];
-    if (k == 0 && g < 15) rw[(g + 1) & 1].c = ROW_G(F0, g + 1);
-    const f32x2 cs = {__builtin_amdgcn_cosf(from_acc(P1[g][k])), __builtin_amdgcn_cosf(from_acc(P1[g][k + 1]))};
-    const f32x2 v = pk_mul(f32x2{acc[tb][2 * rp], acc[tb][2 * rp + 1]}, pk_mul(f32x2{R.c[k], R.c[k + 1]}, cs));
-    act[4 * g + k] = v[0];
-    act[4 * g + k + 1] = v[1];
+    if (q == 0) {
+      st[0] = __builtin_amdgcn_cosf(from_acc(P1[g][k]));
+      st[1] = from_acc(P1[g][k + 1]);
+    } else if (q == 1) {
+      if (k == 0 && g < 15) rw[(g + 1) & 1].c = ROW_G(F0, g + 1);
+      st[2] = __builtin_amdgcn_cosf(st[1]);
+      act[4 * g + k] = acc[tb][2 * rp] * (R.c[k] * st[0]);
+    } else {
+      act[4 * g + k + 1] = acc[tb][2 * rp + 1] * (R.c[k + 1] * st[2]);
+    }
   };
-  stream_layer(lds, lay(15), BH, BL, acc, r2, [&]() {}, r1);
+  stream_layer(lds, lay(15), BH, BL, acc, r2, [&]() {}, r1, OI_DMA(16));
   F3_T(1);
   run_tail(r1);
   F3_T(3);
@@ -710,7 +755,6 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     for (int g = 0; g < 16; ++g)
 #pragma unroll
       for (int k = 0; k < 4; ++k) act[4 * g + k] = fback[g][k];
-    const LayOff yc = lay(16);
     // the accumulators carry the image scale 2^k: bring the rank-3 gradient term to the same scale
     const float cs3 = 1.0f / hdr[H_WSCALE + 14];
     const float vx = gx * cs3, vy = gy * cs3, vz = gz * cs3;
@@ -718,30 +762,42 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
     f32x4 w0, w1, w2;
     split_limbs(act, AH, AL);
     NEXT_AB(F8);
-    auto ec = [&](int tb, int rp) {
+    f32x4 tv[2];   // the pair's two rows of the view table
+    auto ec = [&](int tb, int rp, int q) {
       const int g = tb * 4 + (rp >> 1), k = 2 * (rp & 1);
       Rows& R = rw[g & 1];
-      if (k == 0) {
-        if (g < 15) {
-          rw[(g + 1) & 1].a = ROW_A(F8, g + 1);
-          rw[(g + 1) & 1].b = ROW_B(F8, g + 1);
-        }
-        w0 = lds_f4(lds, F3_TABS + (H_RGB + 0 * C + grp_f0(g)) * 4, o.h16);
-        w1 = lds_f4(lds, F3_TABS + (H_RGB + 1 * C + grp_f0(g)) * 4, o.h16);
-        w2 = lds_f4(lds, F3_TABS + (H_RGB + 2 * C + grp_f0(g)) * 4, o.h16);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const f32x4 w = lds_f4(lds, F3_TABS + H_TABV * 4 + (grp_f0(g) + k + i) * 16, o.h64);
-        const float u = acc[tb][2 * rp + i] + fmaf(vz, w[2], fmaf(vy, w[1], vx * w[0]));
-        const float sn = __builtin_amdgcn_sinf(reduce(fmaf(R.a[k + i], u, R.b[k + i])));
+      auto inner = [&](int i) { return fmaf(vz, tv[i][2], fmaf(vy, tv[i][1], vx * tv[i][0])); };
+      auto sine = [&](int i, float in) {
+        const float u = acc[tb][2 * rp + i] + in;
+        return __builtin_amdgcn_sinf(reduce(fmaf(R.a[k + i], u, R.b[k + i])));
+      };
+      auto sum = [&](int i, float sn) {
         r0 = fmaf(sn, w0[k + i], r0);
         r1 = fmaf(sn, w1[k + i], r1);
         r2 = fmaf(sn, w2[k + i], r2);
+      };
+      if (q == 0) {
+        if (k == 0) {
+          if (g < 15) {
+            rw[(g + 1) & 1].a = ROW_A(F8, g + 1);
+            rw[(g + 1) & 1].b = ROW_B(F8, g + 1);
+          }
+          w0 = lds_f4(lds, F3_TABS + (H_RGB + 0 * C + grp_f0(g)) * 4, o.h16);
+          w1 = lds_f4(lds, F3_TABS + (H_RGB + 1 * C + grp_f0(g)) * 4, o.h16);
+          w2 = lds_f4(lds, F3_TABS + (H_RGB + 2 * C + grp_f0(g)) * 4, o.h16);
+        }
+        tv[0] = lds_f4(lds, F3_TABS + H_TABV * 4 + (grp_f0(g) + k) * 16, o.h64);
+        tv[1] = lds_f4(lds, F3_TABS + H_TABV * 4 + (grp_f0(g) + k + 1) * 16, o.h64);
+      } else if (q == 1) {
+        st[0] = sine(0, inner(0));
+        st[1] = inner(1);
+      } else {
+        sum(0, st[0]);
+        sum(1, sine(1, st[1]));
       }
     };
     F3_T(5);
-    stream_layer(lds, yc, AH, AL, acc, NoTail(), NoMid(), ec);
+    stream_layer(lds, lay(16), AH, AL, acc, NoTail(), NoMid(), ec, NoDma());
     F3_T(1);
     run_tail(ec);
     F3_T(3);
@@ -766,6 +822,7 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   }
 #endif
 #undef OI_PARK
+#undef OI_DMA
 #undef OI_FWD_EPI
 #undef OI_REV_EPI
 #undef OI_REV_MID

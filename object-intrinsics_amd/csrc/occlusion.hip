@@ -14,34 +14,6 @@ namespace {
 
 constexpr float HALF_PI = 1.57079632679489662f;
 
-// the header's sample numbers: a 32-bit mix of (pixel, seed), one stratum per sample, a 24-bit rotation
-__device__ __forceinline__ void sample_numbers(unsigned pix, unsigned seed, unsigned j, int S, float& u1, float& u2) {
-  unsigned x = pix * 0x9E3779B9u + seed;
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  u1 = ((float)j + 0.5f) / (float)S;
-  u2 = (float)((j * 2654435769u + x) >> 8) * 0x1p-24f;
-}
-
-// d = sa cos(phi) t1 + sa sin(phi) t2 + ca a in the header's frame of the unit axis a; sa == 0 returns a itself
-__device__ __forceinline__ void direction_about(float ax, float ay, float az, float sa, float ca, float u2, float& dx, float& dy,
-                                                float& dz) {
-  const float sg = copysignf(1.0f, az);
-  const float A = -1.0f / (sg + az), B = ax * ay * A;
-  const float t1x = 1.0f + sg * ax * ax * A, t1y = sg * B, t1z = -sg * ax;
-  const float t2x = B, t2y = sg + ay * ay * A, t2z = -ay;
-  float sp, cp;
-  sincospif(2.0f * u2, &sp, &cp);  // phi = 2 pi u2
-  const float e1 = sa * cp, e2 = sa * sp;
-  dx = e1 * t1x + e2 * t2x + ca * ax;
-  dy = e1 * t1y + e2 * t2y + ca * ay;
-  dz = e1 * t1z + e2 * t2z + ca * az;
-  if (sa == 0.f) dx = ax, dy = ay, dz = az;  // (the sums above give a up to the sign of a zero)
-}
-
 // AMBIENT = false: rays to L lights of angular radius radius[l].  AMBIENT = true: L = 1, the hemisphere about the normal.
 template <bool AMBIENT>
 __global__ void __launch_bounds__(TR_THREADS) occlusion_begin_kernel(const oi_trace_state s,

@@ -1,7 +1,8 @@
 // What trace.hip, occlusion.hip, trace_batch.hip and scene.hip share (include/oi_trace.h, include/oi_occlusion.h,
 // include/oi_trace_batch.h, include/oi_scene.h; DESIGN sections 4.13, 4.16, 4.17 and 4.19): the workgroup compaction, the ray
-// state machine (the full one and its any-hit form, one template), the light's direction, the shadow ray of a surface point
-// and the per-pixel shading.  Everything here has internal linkage; each source file instantiates what it exports.
+// state machine (the full one and its any-hit form, one template), the light's direction, the sample numbers and directions
+// of the secondary rays (occlusion.hip, envgloss.hip), the shadow ray of a surface point and the per-pixel shading.
+// Everything here has internal linkage; each source file instantiates what it exports.
 #ifndef OI_TRACE_COMMON_H_
 #define OI_TRACE_COMMON_H_
 
@@ -240,6 +241,34 @@ __device__ __forceinline__ float unit_sphere_exit(float ox, float oy, float oz, 
   const float b = ox * dx + oy * dy + oz * dz, c = ox * ox + oy * oy + oz * oz - 1.0f;
   const float disc = b * b - c;
   return disc > 0.f ? fmaxf(sqrtf(disc) - b, 0.f) : 0.f;
+}
+
+// include/oi_occlusion.h's sample numbers: a 32-bit mix of (pixel, seed), one stratum per sample, a 24-bit rotation
+__device__ __forceinline__ void sample_numbers(unsigned pix, unsigned seed, unsigned j, int S, float& u1, float& u2) {
+  unsigned x = pix * 0x9E3779B9u + seed;
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  u1 = ((float)j + 0.5f) / (float)S;
+  u2 = (float)((j * 2654435769u + x) >> 8) * 0x1p-24f;
+}
+
+// d = sa cos(phi) t1 + sa sin(phi) t2 + ca a in include/oi_occlusion.h's frame of the unit axis a; sa == 0 returns a itself
+__device__ __forceinline__ void direction_about(float ax, float ay, float az, float sa, float ca, float u2, float& dx, float& dy,
+                                                float& dz) {
+  const float sg = copysignf(1.0f, az);
+  const float A = -1.0f / (sg + az), B = ax * ay * A;
+  const float t1x = 1.0f + sg * ax * ax * A, t1y = sg * B, t1z = -sg * ax;
+  const float t2x = B, t2y = sg + ay * ay * A, t2z = -ay;
+  float sp, cp;
+  sincospif(2.0f * u2, &sp, &cp);  // phi = 2 pi u2
+  const float e1 = sa * cp, e2 = sa * sp;
+  dx = e1 * t1x + e2 * t2x + ca * ax;
+  dy = e1 * t1y + e2 * t2y + ca * ay;
+  dz = e1 * t1z + e2 * t2z + ca * az;
+  if (sa == 0.f) dx = ax, dy = ay, dz = az;  // (the sums above give a up to the sign of a zero)
 }
 
 // oi_trace_shadow_begin's ray of hit i under the light lt: n = g / max(|g|, 1e-6), l = the light's direction in the object

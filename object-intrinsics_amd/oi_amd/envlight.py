@@ -9,8 +9,17 @@ capture is then shaded under any number of EnvLights -- or rotations of one -- w
     cap = trace.capture_transfer(gen, z, b2w)         # one primary trace, one full MLP pass, one 64-sample occlusion trace
     out = cap.shade([env, env.rotated(R)])            # image / shading (2, 3, H, W)
 
-Only the diffuse response is modelled; glossy terms, bands above 2 and interreflection are out of scope."""
+An EnvLight carries the diffuse response only.  An EnvMap adds the Phong lobe of the learned material (include/oi_envgloss.h;
+DESIGN section 4.20): the environment map convolved with relu(cos)^shininess once, looked up along the reflected view vector,
+times a reflection-lobe visibility that capture_transfer(glossy_samples=...) traces with the view.
+
+    env = EnvMap.from_equirect(img, shininess=10)     # the SH half as above, and the prefiltered map (oi_env_prefilter)
+    cap = trace.capture_transfer(gen, z, b2w, glossy_samples=64)
+    out = cap.shade([env, env.rotated(R)])            # image / shading / specular (2, 3, H, W); nothing is prefiltered again
+
+Bands above 2 of the diffuse term and interreflection are out of scope."""
 import math
+import warnings
 
 import numpy as np
 import torch
@@ -102,11 +111,7 @@ class EnvLight:
         """An equirectangular radiance map (3, He, We) or (He, We, 3), numpy or tensor: row r at polar angle
         pi (r + 1/2) / He from +z, column c at azimuth 2 pi (c + 1/2) / We.  Projected on the GPU (oi_env_project)."""
         from . import ops
-        t = img if torch.is_tensor(img) else torch.as_tensor(np.asarray(img))
-        if t.dim() != 3 or (t.shape[0] != 3 and t.shape[-1] != 3):
-            raise ValueError(f"EnvLight.from_equirect: image of shape {tuple(t.shape)} (expected (3, He, We) or (He, We, 3))")
-        if t.shape[0] != 3:
-            t = t.permute(2, 0, 1)
+        t = _equirect_tensor(img, "EnvLight.from_equirect")
         t = t.to(device=device if not t.is_cuda else t.device, dtype=torch.float32).contiguous()
         return cls(ops.env_project(t[None])[0])
 
@@ -115,7 +120,7 @@ class EnvLight:
         """The diffuse and ambient terms of directional lights (oi_amd.relight.Light objects) as one environment:
         L_c = pi diffuse y_c(direction / |direction|), plus 2 sqrt(pi) ambient on c = 0.  Band-limited: with the unshadowed
         transfer a light's max(n . l, 0) becomes 1/4 + cos / 2 + (5 / 32) (3 cos^2 - 1), at most 0.094 off.  The specular
-        term has no diffuse counterpart and is DROPPED."""
+        term has no diffuse counterpart and is DROPPED here; an EnvMap carries it."""
         from .relight import Light
         lights = [lights] if isinstance(lights, Light) else list(lights)
         c = np.zeros((N_COEFFS, 3))
@@ -137,6 +142,114 @@ class EnvLight:
 
     def __repr__(self):
         return f"EnvLight(L0={self.coeffs[0].tolist()})"
+
+
+class EnvMap:
+    """An environment for a glossy surface: `sh`, the EnvLight of its diffuse half; `map`, the radiance convolved with the
+    Phong lobe of `shininess`, G_s(d) = (1 / pi) integral of L(w) relu(w . d)^s dw, float32 (3, Hp, Wp) on the header's
+    equirectangular grid; `rotation`, the world rotation R (3, 3) float64 the environment has been turned by since the map
+    was made: G'(d) = G(R^T d), so rotated() shares the map and composes R."""
+
+    def __init__(self, sh, glossy_map, shininess, rotation=None):
+        from . import ops
+        if not isinstance(sh, EnvLight):
+            raise TypeError(f"EnvMap: expected an EnvLight for the diffuse half, got {type(sh).__name__}")
+        if not torch.is_tensor(glossy_map) or glossy_map.dim() != 3 or glossy_map.shape[0] != 3 or glossy_map.dtype != torch.float32:
+            raise ValueError("EnvMap: the prefiltered map is a float32 tensor (3, Hp, Wp)")
+        self.sh, self.map, self.shininess = sh, glossy_map, ops.check_shininess(shininess, "EnvMap")
+        self.rotation = np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64)
+        self._host = None
+
+    @classmethod
+    def from_equirect(cls, img, shininess, size=(64, 128), device="cuda"):
+        """EnvLight.from_equirect's image, projected (oi_env_project) and prefiltered to size = (Hp, Wp) (oi_env_prefilter) on
+        the GPU.  The sum over the He x We pixels is a midpoint rule: it resolves the lobe only while a pixel is narrower
+        than the lobe, and a warning is issued when He < 2 sqrt(shininess) (a constant 16 x 32 map at shininess 200 comes
+        out 24 % off).  The warning speaks for directions away from the poles.  A lobe that reaches a pole needs a finer map than
+        it implies, because the first band's midpoint cannot stand for the band: a constant 32 x 64 map at shininess 200 passes
+        the rule (28.3 rows) and is within 4e-4 elsewhere, but the texels within 0.4 rad of a pole come out up to 9 % off (2 % at
+        shininess 50); DESIGN section 4.20 has the figures."""
+        from . import ops
+        s = ops.check_shininess(shininess, "EnvMap.from_equirect")
+        t = _equirect_tensor(img, "EnvMap.from_equirect")
+        if t.shape[1] < 2.0 * math.sqrt(s):
+            warnings.warn(f"EnvMap.from_equirect: a map of {t.shape[1]} rows is too coarse a quadrature for shininess {s:g} "
+                          f"(He >= 2 sqrt(shininess) = {2.0 * math.sqrt(s):.1f}): the lobe falls between the pixels")
+        t = t.to(device=device if not t.is_cuda else t.device, dtype=torch.float32).contiguous()
+        sh = EnvLight(ops.env_project(t[None])[0])
+        return cls(sh, ops.env_prefilter(t[None], s, size)[0], s)
+
+    @classmethod
+    def constant(cls, rgb, shininess):
+        """Radiance `rgb` from every direction: the closed form G_s = rgb 2 / (s + 1) in a 1 x 1 map (host memory until a
+        capture is shaded)."""
+        from . import ops
+        s = ops.check_shininess(shininess, "EnvMap.constant")
+        g = np.broadcast_to(np.asarray(rgb, dtype=np.float64), (3,)) * 2.0 / (s + 1.0)
+        return cls(EnvLight.constant(rgb), torch.tensor(g, dtype=torch.float32).view(3, 1, 1), s)
+
+    def rotated(self, R):
+        """The environment turned by the world rotation R: the SH half as EnvLight.rotated, the map shared, R composed."""
+        M = sh_rotation(R)   # (checks R)
+        R = np.asarray(R.detach().cpu().numpy() if torch.is_tensor(R) else R, dtype=np.float64)
+        out = EnvMap(EnvLight(M @ self.sh.coeffs), self.map, self.shininess, R @ self.rotation)
+        out._host = self._host
+        return out
+
+    def glossy(self, d):
+        """G_s towards unit world vectors d (..., 3) -> (..., 3): oi_env_shade_glossy's lookup in float64 on the host."""
+        if self._host is None:
+            self._host = self.map.detach().cpu().numpy().astype(np.float64)
+        g = self._host
+        Hp, Wp = g.shape[1:]
+        d = np.asarray(d, dtype=np.float64) @ self.rotation          # row k: R^T d_k
+        theta = np.arccos(np.clip(d[..., 2], -1.0, 1.0))
+        phi = np.arctan2(d[..., 1], d[..., 0])
+        phi = np.where(phi < 0, phi + 2.0 * math.pi, phi)
+        u, v = theta / math.pi * Hp - 0.5, phi / (2.0 * math.pi) * Wp - 0.5
+        i0, j0 = np.floor(u), np.floor(v)
+        fu, fv = (u - i0)[..., None], (v - j0)[..., None]
+        i1 = np.clip(i0 + 1, 0, Hp - 1).astype(int)
+        i0 = np.clip(i0, 0, Hp - 1).astype(int)
+        j0 = np.mod(j0.astype(int), Wp)
+        j1 = np.mod(j0 + 1, Wp)
+        at = lambda i, j: np.moveaxis(g[:, i, j], 0, -1)
+        top = at(i0, j0) + fv * (at(i0, j1) - at(i0, j0))
+        bot = at(i1, j0) + fv * (at(i1, j1) - at(i1, j0))
+        return top + fu * (bot - top)
+
+    def __repr__(self):
+        return f"EnvMap(shininess={self.shininess:g}, map={tuple(self.map.shape[1:])}, L0={self.sh.coeffs[0].tolist()})"
+
+
+def _equirect_tensor(img, what):
+    """An equirectangular image (3, He, We) or (He, We, 3), numpy or tensor -> a (3, He, We) tensor."""
+    t = img if torch.is_tensor(img) else torch.as_tensor(np.asarray(img))
+    if t.dim() != 3 or (t.shape[0] != 3 and t.shape[-1] != 3):
+        raise ValueError(f"{what}: image of shape {tuple(t.shape)} (expected (3, He, We) or (He, We, 3))")
+    return t if t.shape[0] == 3 else t.permute(2, 0, 1)
+
+
+def stack_maps(envs, device="cuda"):
+    """EnvMaps -> what oi_env_shade_glossy reads: the SH halves (F, 9, 3), the DISTINCT maps stacked (M, 3, Hp, Wp) --
+    rotations of one map share one entry --, the F map indices (host integers) and the rotations (F, 3, 3), float32 on
+    `device`; and the common shininess."""
+    envs = [envs] if isinstance(envs, EnvMap) else list(envs)
+    if not envs or not all(isinstance(e, EnvMap) for e in envs):
+        raise TypeError("stack_maps: expected one or more EnvMap objects")
+    if any(e.shininess != envs[0].shininess for e in envs):
+        raise ValueError(f"stack_maps: the maps were prefiltered for different shininess values "
+                         f"{sorted({e.shininess for e in envs})}; one launch has one")
+    maps, index = {}, []
+    for e in envs:
+        index.append(maps.setdefault(id(e.map), (len(maps), e.map))[0])
+    tensors = [m for _, m in maps.values()]
+    if any(m.shape != tensors[0].shape for m in tensors):
+        raise ValueError(f"stack_maps: maps of different sizes {sorted({tuple(m.shape[1:]) for m in tensors})} in one call")
+    # (one map, the case of a rotation walk: a view of it, nothing is copied when it is on the device already)
+    stack = tensors[0].to(device)[None] if len(tensors) == 1 else torch.stack([m.to(device) for m in tensors])
+    rot = torch.tensor(np.stack([e.rotation for e in envs]), dtype=torch.float32, device=device)
+    return stack_envs([e.sh for e in envs], device), stack, index, rot, envs[0].shininess
 
 
 def stack_envs(envs, device="cuda"):

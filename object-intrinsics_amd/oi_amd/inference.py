@@ -293,22 +293,29 @@ def env_walk_rotations(n_frames, axis=(0.0, 0.0, 1.0)):
 
 
 @torch.no_grad()
-def env_walk(gen, z, b2w, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64, seed=0, bg=None, bias=None, **kw):
-    """The environment `env` (oi_amd.envlight.EnvLight) turning through 360 degrees about the world `axis` while the view
-    stays: ONE capture (oi_amd.trace.capture_transfer: the primary trace, the full MLP pass at its hits and transfer_samples
+def env_walk(gen, z, b2w, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64, seed=0, bg=None, bias=None,
+             glossy_samples=None, shininess=None, specular=None, **kw):
+    """The environment `env` (oi_amd.envlight.EnvLight or EnvMap) turning through 360 degrees about the world `axis` while the
+    view stays: ONE capture (oi_amd.trace.capture_transfer: the primary trace, the full MLP pass at its hits and transfer_samples
     secondary rays per visible point), then n_frames rotations of the 9 x 3 coefficients on the host and one shade launch per
     256 frames.  Frame 0 is `env` itself.  -> {"image", "shading": (n_frames, 3, H, W), "transfer": (1, 9, H, W), "mask" /
-    "depth" (1, 1, H, W), "stats"}.  Keyword arguments: capture_transfer's (tol, omega, max_steps, readback)."""
+    "depth" (1, 1, H, W), "stats"}.  An EnvMap takes the glossy path (glossy_samples, shininess: capture_transfer's; specular:
+    shade's): the map is prefiltered once, when it is made, and every frame only rotates the lookup; the result also holds
+    "specular" (n_frames, 3, H, W) and "spec_visibility".  Keyword arguments: capture_transfer's (tol, omega, max_steps,
+    readback)."""
     from . import trace
-    from .envlight import EnvLight
-    if not isinstance(env, EnvLight):
-        raise TypeError(f"env_walk: expected an EnvLight, got {type(env).__name__}")
+    from .envlight import EnvLight, EnvMap
+    if not isinstance(env, (EnvLight, EnvMap)):
+        raise TypeError(f"env_walk: expected an EnvLight or an EnvMap, got {type(env).__name__}")
     rots = env_walk_rotations(n_frames, axis)
     gen.eval()
     gen.renderer.pack.check()
-    cap = trace.capture_transfer(gen, z, b2w, transfer_samples, seed, trace.DEFAULT_BIAS if bias is None else bias, **kw)
-    res = cap.shade([env.rotated(R) for R in rots], bg)
+    cap = trace.capture_transfer(gen, z, b2w, transfer_samples, seed, trace.DEFAULT_BIAS if bias is None else bias, glossy_samples,
+                                 shininess, **kw)
+    res = cap.shade([env.rotated(R) for R in rots], bg, specular)
     res.update(transfer=cap.transfer, mask=cap.maps["mask"], depth=cap.maps["depth"], stats=cap.stats())
+    if cap.glossy_samples is not None:
+        res["spec_visibility"] = cap.spec_visibility
     return res
 
 

@@ -128,6 +128,9 @@ class EnvShadeParams(ctypes.Structure):
                 [(n, _vp) for n in ("status", "hit_slot", "rgb", "transfer", "envs", "bg", "shading", "image")])
 
 
+# include/oi_envgloss.h
+ENVGLOSS_MIN_SHININESS, ENVGLOSS_MAX_SHININESS, ENVGLOSS_CHUNK = 1, 4096, 2048
+
 # include/oi_scene.h
 SCENE_MAX_RESOLUTION = 32768
 
@@ -304,6 +307,13 @@ SIGS = {
         "oi_scene_points": (_i, [_P(TraceBatch), _vp, _vp, _ll, _vp, _ll] + [_vp] * 6),
         "oi_scene_shadow_begin": (_i, [_P(TraceBatch), _vp, _vp, _ll, _vp, _vp, _vp, _vp, _ll, _vp, _i, _vp, _f, _vp]),
         "oi_scene_visibility": (_i, [_vp] * 5 + [_i, _ll, _i, _ll, _i, _vp, _vp]),
+    },
+    # include/oi_envgloss.h: the Phong lobe under an environment map (an addition to oi_envlight.h; no struct of its own)
+    "oi_envgloss.h": {
+        "oi_env_prefilter_partial_floats": (_sz, [_i] * 5),
+        "oi_env_prefilter": (_i, [_vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp]),
+        "oi_occlusion_lobe_begin": (_i, [_P(TraceState), _vp, _vp, _vp, _vp, _ll, _i, _f, _f, _u, _vp]),
+        "oi_env_shade_glossy": (_i, [_P(EnvShadeParams)] + [_vp] * 6 + [_i, _i, _i, _P(_i), _vp, _vp, _vp, _vp]),
     },
 }
 

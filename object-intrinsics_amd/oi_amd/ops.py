@@ -966,6 +966,98 @@ def env_shade(status, hit_slot, rgb, n_hit, transfer, envs, bg=None, outputs=ENV
 
 
 # ------------------------------------------------------------------------------------------
+# glossy environment lighting on the traced surface (include/oi_envgloss.h)
+# ------------------------------------------------------------------------------------------
+
+def check_shininess(shininess, what):
+    """include/oi_envgloss.h's range of a shininess -> float."""
+    try:
+        s = float(shininess)
+    except (TypeError, ValueError):
+        s = float("nan")
+    if isinstance(shininess, bool) or not _l.ENVGLOSS_MIN_SHININESS <= s <= _l.ENVGLOSS_MAX_SHININESS:
+        raise ValueError(f"{what}: shininess={shininess!r} ({_l.ENVGLOSS_MIN_SHININESS} <= shininess <= "
+                         f"{_l.ENVGLOSS_MAX_SHININESS}, finite)")
+    return s
+
+
+def env_prefilter(radiance, shininess, size):
+    """Equirectangular maps (E, 3, He, We) float32 on the device -> their Phong-lobe convolutions (E, 3, Hp, Wp) at one
+    shininess, size = (Hp, Wp) (oi_env_prefilter)."""
+    if not torch.is_tensor(radiance) or radiance.dim() != 4 or radiance.shape[1] != 3:
+        raise ValueError(f"env_prefilter: radiance {tuple(getattr(radiance, 'shape', ()))}, expected (E, 3, He, We)")
+    s = check_shininess(shininess, "env_prefilter")
+    E, _, He, We = radiance.shape
+    Hp, Wp = (int(v) for v in size)
+    L = _l.load()
+    nf = L.oi_env_prefilter_partial_floats(E, He, We, Hp, Wp) if min(E, He, We, Hp, Wp) >= 1 else 0
+    if nf == 0:
+        raise ValueError(f"env_prefilter: E={E}, He={He}, We={We}, size={(Hp, Wp)} (1 <= E <= {_l.ENV_MAX_ENVS}, sizes >= 1, "
+                         f"E * He * We and E * 3 * Hp * Wp below 2^31, E * ceil(He * We / {_l.ENVGLOSS_CHUNK}) * "
+                         "ceil(Hp * Wp / 256) workgroups at most 2^23)")
+    radiance = _c(radiance)
+    partial = _new(radiance, nf)
+    glossy = _new(radiance, E, 3, Hp, Wp)
+    _l.check(L.oi_env_prefilter(_p(radiance), E, He, We, s, Hp, Wp, _p(partial), _p(glossy), _stream()), "oi_env_prefilter")
+    return glossy
+
+
+def occlusion_lobe_begin(st, rays_o, hit_points, grad, hit_index, n_hit, samples, shininess, bias, seed=0):
+    """S = samples reflection-lobe rays per hit into the TraceState st of S * n_hit rays; rays_o (N, 3): the primary eyes."""
+    _l.check(_l.load().oi_occlusion_lobe_begin(ctypes.byref(st.c), _p(rays_o), _p(hit_points), _p(grad), _ip(hit_index), int(n_hit),
+                                               int(samples), float(shininess), float(bias), int(seed), _stream()),
+             "oi_occlusion_lobe_begin")
+
+
+ENV_GLOSSY_OUT = ENV_SHADE_OUT + ("specular",)
+
+
+def env_shade_glossy(status, hit_slot, rgb, n_hit, transfer, envs, rays_o, hit_points, grad, w2b, spec_vis, glossy, map_index,
+                     rot, k_s, bg=None, outputs=ENV_GLOSSY_OUT, out=None):
+    """env_shade plus the glossy term (oi_env_shade_glossy): envs (F, 9, 3) the SH halves, glossy (M, 3, Hp, Wp) the
+    prefiltered maps, map_index F host integers in [0, M) (checked here, before anything is uploaded), rot (F, 3, 3) world
+    rotations, k_s (3,), spec_vis (N,) or None (= 1).  -> {name: (F, 3, N)} for the names of ENV_GLOSSY_OUT in `outputs`."""
+    N = transfer.shape[1]
+    F = envs.shape[0] if torch.is_tensor(envs) and envs.dim() == 3 else 0
+    if not 1 <= F <= _l.ENV_MAX_ENVS or tuple(envs.shape[1:]) != (_l.ENV_COEFFS, 3):
+        raise ValueError(f"env_shade_glossy: envs {tuple(getattr(envs, 'shape', ()))}, expected (F, {_l.ENV_COEFFS}, 3) with "
+                         f"1 <= F <= {_l.ENV_MAX_ENVS}")
+    if tuple(transfer.shape) != (_l.ENV_COEFFS, N) or not outputs:
+        raise ValueError(f"env_shade_glossy: transfer {tuple(transfer.shape)}, expected ({_l.ENV_COEFFS}, N); outputs {outputs!r}")
+    if not torch.is_tensor(glossy) or glossy.dim() != 4 or glossy.shape[1] != 3 or not 1 <= glossy.shape[0] <= _l.ENV_MAX_ENVS:
+        raise ValueError(f"env_shade_glossy: glossy {tuple(getattr(glossy, 'shape', ()))}, expected (M, 3, Hp, Wp) with "
+                         f"1 <= M <= {_l.ENV_MAX_ENVS}")
+    M, _, Hp, Wp = glossy.shape
+    idx = [int(v) for v in map_index]
+    if len(idx) != F or any(not 0 <= v < M for v in idx):
+        raise ValueError(f"env_shade_glossy: map_index {idx} (F = {F} integers, 0 <= map_index < M = {M})")
+    if tuple(rot.shape) != (F, 3, 3) or tuple(k_s.shape) != (3,) or (spec_vis is not None and tuple(spec_vis.shape) != (N,)):
+        raise ValueError(f"env_shade_glossy: rot {tuple(rot.shape)}, k_s {tuple(k_s.shape)}, expected {(F, 3, 3)} and (3,); "
+                         f"spec_vis (N,) = {(N,)} or None")
+    res = {}
+    for name in outputs:
+        if name not in ENV_GLOSSY_OUT:
+            raise ValueError(f"env_shade_glossy: unknown output {name!r} (one of {ENV_GLOSSY_OUT})")
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = _new(transfer, F, 3, N)
+        elif tuple(t.shape) != (F, 3, N) or not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"env_shade_glossy: out[{name!r}] must be a contiguous float32 {(F, 3, N)} tensor")
+        res[name] = t
+    P = _l.EnvShadeParams()
+    P.N, P.n_hit, P.F = N, int(n_hit), F
+    keep = [_c(x) for x in (rgb if n_hit else None, transfer, envs, bg, rays_o, hit_points if n_hit else None,
+                            grad if n_hit else None, w2b, spec_vis, glossy, rot, k_s)]
+    P.rgb, P.transfer, P.envs, P.bg = (_p(x) for x in keep[:4])
+    P.status, P.hit_slot = _p(status), _ip(hit_slot)
+    P.shading, P.image = _p(res.get("shading")), _p(res.get("image"))
+    ro, hp, g, wb, sv, gl, rt, ks = (_p(x) for x in keep[4:])
+    _l.check(_l.load().oi_env_shade_glossy(ctypes.byref(P), ro, hp, g, wb, sv, gl, M, Hp, Wp, (ctypes.c_int * F)(*idx), rt, ks,
+                                           _p(res.get("specular")), _stream()), "oi_env_shade_glossy")
+    return res
+
+
+# ------------------------------------------------------------------------------------------
 # discriminator side
 # ------------------------------------------------------------------------------------------
 

@@ -12,7 +12,9 @@
                      over the hemisphere of each visible point; include/oi_occlusion.h)
     capture_transfer one view's secondary rays traced ONCE into a per-pixel SH transfer map; the TransferCapture is then shaded
                      under any number of environment lights (oi_amd.envlight.EnvLight), 256 per launch
-                     (include/oi_envlight.h)
+                     (include/oi_envlight.h); with glossy_samples it also traces a reflection-lobe
+                     visibility, and the capture is shaded under oi_amd.envlight.EnvMap objects with the learned Phong lobe
+                     (include/oi_envgloss.h)
     render_surface_env  capture_transfer + shade in one call
 
 The loop runs on the host: oi_trace_begin, then per step the library's sdf-only MLP pass (unchanged) on the rays still in
@@ -265,8 +267,8 @@ class _Surface:
         self.kw, self.bias, self.field = kw, bias, field
         self.ro, self.rd, self.w2b, self.N, self.H = ro, rd, w2b, ro.shape[0], H
         self.res, self.n_hit, self.grad, self.rgb = res, res.hit_index.shape[0], grad, rgb
-        self.shadow_evals = self.ao_evals = self.transfer_evals = 0
-        self.shadow = self.ao = self.transfer_state = None
+        self.shadow_evals = self.ao_evals = self.transfer_evals = self.glossy_evals = 0
+        self.shadow = self.ao = self.transfer_state = self.glossy_state = None
 
     @classmethod
     def from_batch(cls, field, kw, bias, ro, rd, w2b, H, res, grad, rgb):
@@ -329,6 +331,19 @@ class _Surface:
         self.transfer_evals += self._secondary(st)
         self.transfer_state = st
         return ops.transfer_resolve(st.status, st.rays_d, self.res.hit_slot, self.N, self.n_hit, samples, self.w2b)
+
+    def lobe_visibility(self, samples, shininess, seed=0):
+        """(N,) reflection-lobe visibility V_spec (include/oi_envgloss.h): the share of `samples` rays per visible point,
+        distributed as cos^shininess about the reflected view vector, that are above the point's horizon and leave the scene;
+        1 off the mask."""
+        if self.n_hit == 0:
+            return torch.ones(self.N, device=self.ro.device)
+        st = ops.TraceState(samples * self.n_hit, ref=self.ro)
+        ops.occlusion_lobe_begin(st, self.ro, self.res.hit_points, self.grad, self.res.hit_index, self.n_hit, samples, shininess,
+                                 self.bias, seed)
+        self.glossy_evals += self._secondary(st)
+        self.glossy_state = st
+        return ops.occlusion_resolve(st.status, self.res.hit_slot, self.N, self.n_hit, 1, samples).view(self.N)
 
     def shade(self, lights, bg, visibility=None, outputs=tuple(ops.SURFACE_OUT) + ("image",), image_out=None,
               ambient_occlusion=None):
@@ -509,61 +524,130 @@ def _check_transfer(transfer_samples, seed, what):
 class TransferCapture:
     """One traced view and its SH transfer map: everything shade() needs, none of which depends on the light.
     surface: the _Surface (primary trace, gradients and albedo at the hits); transfer (1, 9, H, W); maps: render_surface's
-    G-buffer maps (depth, position, normal_map, normal_object, albedo, mask)."""
+    G-buffer maps (depth, position, normal_map, normal_object, albedo, mask).  A capture made with glossy_samples > 0 also
+    holds spec_visibility (1, 1, H, W), the reflection-lobe visibility, and the shininess it was traced for."""
 
-    def __init__(self, surface, transfer, maps, samples):
+    def __init__(self, surface, transfer, maps, samples, glossy_samples=None, shininess=None, spec_vis=None, specular=None):
         self.surface, self.samples, self.maps = surface, samples, maps
         self._transfer = transfer                       # (9, N), planar: what oi_env_shade reads
         self.H = self.W = surface.H
         self.transfer = transfer.view(1, _l.ENV_COEFFS, self.H, self.W)
+        # glossy_samples: None = never mentioned (a glossy shade is refused), 0 = no lobe trace on purpose (V_spec = 1)
+        self.glossy_samples, self.shininess, self.specular = glossy_samples, shininess, specular
+        self._spec_vis = spec_vis                       # (N,) or None
+        self.spec_visibility = None if spec_vis is None else spec_vis.view(1, 1, self.H, self.W)
 
-    def shade(self, envs, bg=None):
-        """The view under each of `envs` (an EnvLight or a sequence of them; any number: launches of ENV_MAX_ENVS).
-        -> {"image": (F, 3, H, W) = max(shading, 0) albedo on the mask, bg off it; "shading": (F, 3, H, W), not clamped}."""
-        from .envlight import stack_envs
+    def shade(self, envs, bg=None, specular=None):
+        """The view under each of `envs` (any number: launches of ENV_MAX_ENVS).
+        EnvLight objects: -> {"image": (F, 3, H, W) = max(shading, 0) albedo on the mask, bg off it; "shading": (F, 3, H, W),
+        not clamped}.
+        EnvMap objects (every element; a mixed list is refused): the glossy path, image = max(shading, 0) albedo + specular
+        and "specular": (F, 3, H, W) = k_s V_spec G_s(reflected view vector).  k_s = `specular`: None takes the generator's
+        learned specular colour, a scalar or an RGB triple overrides it.  The maps' shininess must be the capture's.  A capture
+        made with glossy_samples = 0 has V_spec = 1: the point's own horizon and every occluder are ignored."""
+        from .envlight import EnvLight, EnvMap, stack_envs, stack_maps
         s = self.surface
         dev = s.ro.device
-        ev = stack_envs(envs, dev)
-        F, N = ev.shape[0], s.N
-        out = {k: ops._new(s.ro, F, 3, N) for k in ops.ENV_SHADE_OUT}
+        seq = [envs] if isinstance(envs, (EnvLight, EnvMap)) else list(envs)
+        glossy = any(isinstance(e, EnvMap) for e in seq)
+        if glossy and not all(isinstance(e, EnvMap) for e in seq):
+            raise ValueError("shade: EnvMap and EnvLight objects in one list (shade them in two calls)")
         bgv = _bg(bg, dev)
+        if not glossy:
+            if specular is not None:
+                raise ValueError("shade: specular= needs EnvMap environments (an EnvLight has no glossy half)")
+            ev = stack_envs(seq, dev)
+            F, N = ev.shape[0], s.N
+            out = {k: ops._new(s.ro, F, 3, N) for k in ops.ENV_SHADE_OUT}
+            for a in range(0, F, ENV_MAX_ENVS):
+                b = min(F, a + ENV_MAX_ENVS)
+                ops.env_shade(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, ev[a:b], bgv,
+                              out={k: v[a:b] for k, v in out.items()})
+            return {k: v.view(F, 3, self.H, self.W) for k, v in out.items()}
+        if self.glossy_samples is None:
+            raise ValueError("shade: this capture has no reflection-lobe trace; capture_transfer(glossy_samples=S) traces one, "
+                             "glossy_samples=0 with a shininess states that V_spec = 1 is meant")
+        if any(e.shininess != self.shininess for e in seq):
+            raise ValueError(f"shade: maps prefiltered for shininess {sorted({e.shininess for e in seq})}, the capture's lobe is "
+                             f"{self.shininess:g}")
+        ks = self.specular if specular is None else specular
+        ks = torch.as_tensor(np.broadcast_to(np.asarray(ks, dtype=np.float32), (3,)).copy()).to(dev)
+        F, N = len(seq), s.N
+        out = {k: ops._new(s.ro, F, 3, N) for k in ops.ENV_GLOSSY_OUT}
         for a in range(0, F, ENV_MAX_ENVS):
             b = min(F, a + ENV_MAX_ENVS)
-            ops.env_shade(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, ev[a:b], bgv,
-                          out={k: v[a:b] for k, v in out.items()})
+            ev, maps, index, rot, _ = stack_maps(seq[a:b], dev)
+            ops.env_shade_glossy(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, ev, s.ro,
+                                 s.res.hit_points if s.n_hit else None, s.grad, s.w2b, self._spec_vis, maps, index, rot, ks, bgv,
+                                 out={k: v[a:b] for k, v in out.items()})
         return {k: v.view(F, 3, self.H, self.W) for k, v in out.items()}
 
     def stats(self):
         st = self.surface.stats()
         st["transfer_evals"] = self.surface.transfer_evals
+        st["glossy_evals"] = self.surface.glossy_evals
         return st
 
 
+def _check_glossy(gen, glossy_samples, shininess, what):
+    """-> (glossy_samples or None, shininess or None, the learned specular colour or None), checked without touching `gen`
+    unless a glossy capture is asked for and leaves a value to it."""
+    if glossy_samples is None and shininess is None:
+        return None, None, None
+    if glossy_samples is None:
+        raise ValueError(f"{what}: shininess={shininess!r} without glossy_samples (give glossy_samples=S for a lobe trace, or "
+                         "glossy_samples=0 to state that V_spec = 1 is meant)")
+    g = glossy_samples
+    if not _is_count(g, 0):
+        raise ValueError(f"{what}: glossy_samples={glossy_samples!r} (an integer, 0 <= glossy_samples <= {_l.OCCLUSION_MAX_SAMPLES})")
+    from .relight import Light
+    learned = None
+    if shininess is None:
+        learned = Light.from_module(gen.light)
+        shininess = learned.shininess
+    s = ops.check_shininess(shininess, what)
+    return int(g), s, (learned or Light.from_module(gen.light)).specular
+
+
 @torch.no_grad()
-def capture_transfer(gen, z, b2w, transfer_samples=64, seed=0, bias=DEFAULT_BIAS, **trace_kw):
+def capture_transfer(gen, z, b2w, transfer_samples=64, seed=0, bias=DEFAULT_BIAS, glossy_samples=None, shininess=None,
+                     **trace_kw):
     """One view of `gen` (latent z, pose b2w: render_surface's) prepared for environment lighting: the primary trace, the full
     MLP pass at its hits, and `transfer_samples` (0 .. 256) cosine-weighted rays per visible point -- render_surface's ambient-
     occlusion rays for the same seed, followed to the exit of the unit sphere -- resolved into a 9-coefficient transfer vector
-    per pixel.  transfer_samples == 0: the unshadowed closed form of the normal, nothing traced.  trace_kw: tol, omega,
-    max_steps, readback of sphere_trace.  -> TransferCapture."""
+    per pixel.  transfer_samples == 0: the unshadowed closed form of the normal, nothing traced.
+    Glossy environments (oi_amd.envlight.EnvMap): glossy_samples in 1 .. 256 also traces that many rays per visible point
+    about the reflected view vector, distributed as cos^shininess, into spec_visibility; shininess None takes the generator's
+    learned value.  glossy_samples = 0 prepares a glossy capture without that trace (V_spec = 1: no horizon, no occluder);
+    it has to be given: a shininess without glossy_samples is refused.
+    With both left at None the launches and outputs are those of a call without them, and the capture shades EnvLights only.
+    trace_kw: tol, omega, max_steps, readback of sphere_trace.  -> TransferCapture."""
     samples, seed = _check_transfer(transfer_samples, seed, "capture_transfer")
+    g_samples, shin, spec = _check_glossy(gen, glossy_samples, shininess, "capture_transfer")
     dev = gen.it.device
     s = _Surface(gen, z.to(dev).reshape(1, -1), b2w, bias, trace_kw)
     transfer = s.transfer(samples, seed)
     g = s.shade(None, None, outputs=tuple(ops.SURFACE_OUT))
     maps = {_MAP_NAMES[k]: v for k, v in _maps(g, s.H, s.H).items()}
-    return TransferCapture(s, transfer, maps, samples)
+    vis = s.lobe_visibility(g_samples, shin, seed) if g_samples else None
+    return TransferCapture(s, transfer, maps, samples, g_samples, shin, vis, spec)
 
 
 @torch.no_grad()
-def render_surface_env(gen, z, b2w, envs, transfer_samples=64, seed=0, bg=None, bias=DEFAULT_BIAS, **trace_kw):
-    """capture_transfer + shade: one view of `gen` under the environment lights `envs` (oi_amd.envlight.EnvLight objects).
+def render_surface_env(gen, z, b2w, envs, transfer_samples=64, seed=0, bg=None, bias=DEFAULT_BIAS, glossy_samples=None,
+                       shininess=None, specular=None, **trace_kw):
+    """capture_transfer + shade: one view of `gen` under the environment lights `envs` (oi_amd.envlight.EnvLight objects, or
+    EnvMap objects with glossy_samples given: capture_transfer's and shade's keywords pass through).
     -> render_surface's G-buffer keys (depth, position, normal_map, normal_object, albedo, mask), image (F, 3, H, W), shading
     (F, 3, H, W) (not clamped), transfer (1, 9, H, W), stats (with transfer_evals), trace (the primary TraceResult) and
-    transfer_trace (ops.TraceState of the transfer_samples x n_hit rays, ray j * n_hit + i, or None)."""
-    cap = capture_transfer(gen, z, b2w, transfer_samples, seed, bias, **trace_kw)
+    transfer_trace (ops.TraceState of the transfer_samples x n_hit rays, ray j * n_hit + i, or None); on the glossy path also
+    specular (F, 3, H, W), spec_visibility (1, 1, H, W) or None and glossy_trace (the state of the lobe rays, or None)."""
+    cap = capture_transfer(gen, z, b2w, transfer_samples, seed, bias, glossy_samples, shininess, **trace_kw)
     res = dict(cap.maps)
-    res.update(cap.shade(envs, bg))
+    res.update(cap.shade(envs, bg, specular))
+    if cap.glossy_samples is not None:
+        res["spec_visibility"] = cap.spec_visibility
+        res["glossy_trace"] = cap.surface.glossy_state
     res["transfer"] = cap.transfer
     res["transfer_trace"] = cap.surface.transfer_state
     res["stats"] = cap.stats()

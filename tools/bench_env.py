@@ -9,7 +9,15 @@
   project_ms            EnvLight.from_equirect of a --map He x We radiance map (the kernel, the upload and the read-back)
   light_walk_ms         for comparison, the existing inference.surface_light_walk(shadows=False, ao_samples=S) at
                         --walk-frames frames, per frame, same session: a directional light per frame, scalar ambient occlusion
-  env_walk_ms           inference.env_walk at the same S and frame count, per frame (the capture included)"""
+  env_walk_ms           inference.env_walk at the same S and frame count, per frame (the capture included)
+
+With --glossy only the glossy path is timed:
+
+  prefilter_ms          oi_amd.ops.env_prefilter of a --map He x We radiance map to --glossy-size at --shininess (the two
+                        kernels, the map already on the device), and EnvMap.from_equirect (projection and upload included)
+  capture_ms            capture_transfer(transfer_samples=64, glossy_samples=G) at G of --glossy-samples; glossy_evals: the sdf
+                        evaluations of the reflection-lobe trace
+  shade_ms              TransferCapture.shade under F rotations of one EnvMap at each F of --envs: per launch and per frame"""
 import argparse
 import json
 import os
@@ -23,7 +31,7 @@ import torch  # noqa: E402
 
 from bench import build_models  # noqa: E402
 from oi_amd import inference, trace  # noqa: E402
-from oi_amd.envlight import EnvLight  # noqa: E402
+from oi_amd.envlight import EnvLight, EnvMap  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--res", type=int, default=128)
@@ -34,6 +42,10 @@ ap.add_argument("--map", default="256x512")
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--precision", default="f16x3")
+ap.add_argument("--glossy", action="store_true")
+ap.add_argument("--glossy-size", default="64x128")
+ap.add_argument("--glossy-samples", default="16,64")
+ap.add_argument("--shininess", type=float, default=10.0)
 args = ap.parse_args()
 
 
@@ -64,6 +76,31 @@ He, We = (int(v) for v in args.map.split("x"))
 
 out = {"tool": "bench_env", "precision": args.precision, "res": args.res, "iters": args.iters, "warmup": args.warmup,
        "capture": {}, "shade": {}, "walk": {}}
+if args.glossy:
+    from oi_amd import ops
+    size = tuple(int(v) for v in args.glossy_size.split("x"))
+    out.update(glossy=True, shininess=args.shininess)
+    del out["walk"]
+    with torch.no_grad():
+        img = torch.rand(3, He, We, generator=torch.Generator().manual_seed(1))
+        dev_img = img.cuda()[None].contiguous()
+        out["prefilter"] = {"map": args.map, "size": args.glossy_size,
+                            "prefilter_ms": median_ms(lambda: ops.env_prefilter(dev_img, args.shininess, size)),
+                            "from_equirect_ms": median_ms(lambda: EnvMap.from_equirect(img, args.shininess, size))}
+        emap = EnvMap.from_equirect(img, args.shininess, size)
+        cap = None
+        for G in (int(g) for g in args.glossy_samples.split(",")):
+            kw = dict(transfer_samples=64, glossy_samples=G, shininess=args.shininess)
+            cap = trace.capture_transfer(gen, z, b2w, **kw)
+            st = cap.stats()
+            out["capture"][str(G)] = {"capture_ms": median_ms(lambda: trace.capture_transfer(gen, z, b2w, **kw)), "hits": st["hit"],
+                                      "rays": G * st["hit"], "glossy_evals": st["glossy_evals"], "transfer_evals": st["transfer_evals"]}
+        for F in n_envs:
+            envs = [emap.rotated(R) for R in inference.env_walk_rotations(F)]
+            ms = median_ms(lambda: cap.shade(envs, specular=0.3))
+            out["shade"][str(F)] = {"shade_ms": ms, "per_frame_ms": ms / F}
+    print(json.dumps(out))
+    sys.exit(0)
 with torch.no_grad():
     cap = None
     for S in samples:

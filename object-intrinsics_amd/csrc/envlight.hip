@@ -18,26 +18,6 @@ constexpr int ES_THREADS = 64;               // oi_env_shade: one wave per workg
 static_assert(EP_CHUNK == 8192, "the header states the chunk");
 static_assert((long long)EP_INNER * EP_INNER * EP_THREADS * EP_CHUNK >= (1ll << 31), "the final pass covers E * He * We < 2^31");
 
-// the header's basis of a unit vector
-__device__ __forceinline__ void sh9(float x, float y, float z, float* __restrict__ o) {
-  o[0] = 0.28209479177387814f;
-  o[1] = 0.4886025119029199f * y;
-  o[2] = 0.4886025119029199f * z;
-  o[3] = 0.4886025119029199f * x;
-  o[4] = 1.0925484305920792f * (x * y);
-  o[5] = 1.0925484305920792f * (y * z);
-  o[6] = 0.31539156525252005f * (3.0f * (z * z) - 1.0f);
-  o[7] = 1.0925484305920792f * (x * z);
-  o[8] = 0.5462742152960396f * (x * x - y * y);
-}
-
-// v = w2b[:3,:3]^T d (surface_shade_pixel's rotation of the normal)
-__device__ __forceinline__ void to_world(const float* __restrict__ Wb, float dx, float dy, float dz, float& x, float& y, float& z) {
-  x = Wb[0] * dx + Wb[4] * dy + Wb[8] * dz;
-  y = Wb[1] * dx + Wb[5] * dy + Wb[9] * dz;
-  z = Wb[2] * dx + Wb[6] * dy + Wb[10] * dz;
-}
-
 // Sum of v over the workgroup's EP_THREADS threads in one fixed tree (6 butterfly levels in the wave, then the 4 waves as
 // (w0 + w1) + (w2 + w3)); valid in thread 0.  Every thread calls it.  lds: 4 words.
 __device__ __forceinline__ float wg_tree_sum(float v, float* lds) {

@@ -12,8 +12,6 @@
 
 namespace {
 
-constexpr float HALF_PI = 1.57079632679489662f;
-
 // AMBIENT = false: rays to L lights of angular radius radius[l].  AMBIENT = true: L = 1, the hemisphere about the normal.
 template <bool AMBIENT>
 __global__ void __launch_bounds__(TR_THREADS) occlusion_begin_kernel(const oi_trace_state s,
@@ -35,23 +33,9 @@ __global__ void __launch_bounds__(TR_THREADS) occlusion_begin_kernel(const oi_tr
     const float gx = grad[i * 3 + 0], gy = grad[i * 3 + 1], gz = grad[i * 3 + 2];
     const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
     const float nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
-    float u1, u2;
-    sample_numbers((unsigned)hit_index[i], seed, j, S, u1, u2);
-    float ax, ay, az, sa, ca;
-    if (AMBIENT) {
-      ax = nx, ay = ny, az = nz;
-      ca = sqrtf(1.0f - u1);
-      sa = sqrtf(u1);
-    } else {
-      light_dir(lights + l * OI_RELIGHT_LIGHT_FLOATS, w2b, ax, ay, az);
-      const float rad = fminf(fmaxf(radius[l], 0.f), HALF_PI);  // (fmaxf drops a NaN)
-      const float m = u1 * (1.0f - cosf(rad));
-      ca = 1.0f - m;
-      sa = sqrtf(fmaxf(m * (2.0f - m), 0.f));  // sqrt(1 - ca^2) without the cancellation
-    }
     float dx, dy, dz;
-    direction_about(ax, ay, az, sa, ca, u2, dx, dy, dz);
-    traced = nx * dx + ny * dy + nz * dz > 0.f;
+    traced = occlusion_direction<AMBIENT>(nx, ny, nz, (unsigned)hit_index[i], seed, j, S, lights + l * OI_RELIGHT_LIGHT_FLOATS, radius,
+                                          l, w2b, dx, dy, dz);
     ox = __fmaf_rn(bias, nx, hit_points[i * 3 + 0]);
     oy = __fmaf_rn(bias, ny, hit_points[i * 3 + 1]);
     oz = __fmaf_rn(bias, nz, hit_points[i * 3 + 2]);

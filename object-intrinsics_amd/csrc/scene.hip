@@ -13,73 +13,9 @@
 // one integer atomicAdd and one atomicMax per workgroup; resolve and visibility loop over the elements in a fixed order and
 // use no atomics.  No LDS beyond the compaction's counter words, no scratch.
 #include "ray_common.h"
-#include "trace_common.h"
-
-#include "../../include/oi_scene.h"
+#include "scene_common.h"
 
 namespace {
-
-// The unit sphere's chord on the ray (o, d): false when the ray passes at 1 or more from the centre or the sphere lies wholly
-// behind the origin; otherwise near_ = max(mid - h, 0), far_ = mid + h.  Contraction off: tests/helpers/scene_ref.py restates
-// these expressions.
-__device__ __forceinline__ bool unit_sphere_chord(const float* o, const float* d, float& near_, float& far_) {
-#pragma clang fp contract(off)
-  const float dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-  const float od = o[0] * d[0] + o[1] * d[1] + o[2] * d[2];
-  const float mid = -od / dd;
-  const float cx = o[0] + mid * d[0], cy = o[1] + mid * d[1], cz = o[2] + mid * d[2];
-  const float c2 = cx * cx + cy * cy + cz * cz;
-  if (!(c2 < 1.0f)) return false;
-  const float h = sqrtf((1.0f - c2) / dd);
-  far_ = mid + h;
-  near_ = fmaxf(mid - h, 0.f);
-  return far_ > 0.f;
-}
-
-// M (4x4, rigid) applied to the point v: three products and three sums per component, contraction off
-__device__ __forceinline__ void transform_point(const float* __restrict__ M, const float* v, float* out) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int a = 0; a < 3; ++a) out[a] = M[a * 4 + 0] * v[0] + M[a * 4 + 1] * v[1] + M[a * 4 + 2] * v[2] + M[a * 4 + 3];
-}
-
-// every counter of every element and of live, and points = the coordinate origin: the slots behind an element's entered rays
-// are input of the first MLP passes (the bound is the largest count of any element)
-__global__ void __launch_bounds__(TR_THREADS) scene_clear_kernel(const oi_trace_state s, int* __restrict__ live) {
-  if (blockIdx.x == 0 && blockIdx.y == 0)
-    for (int i = threadIdx.x; i < OI_TRACE_COUNT_WORDS; i += TR_THREADS) live[i] = 0;
-  const oi_trace_state v = element_view(s, blockIdx.y);
-  clear_counts(v.counts, 0);
-  const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  if (r < s.N) v.points[r * 3 + 0] = v.points[r * 3 + 1] = v.points[r * 3 + 2] = 0.f;
-}
-
-// ray r of the view v: everything oi_trace_batch_begin writes, for an entered ray (near_ .. far_) or a culled one
-__device__ __forceinline__ void write_ray(const oi_trace_state& v, long long r, const float* o, const float* d, float near_,
-                                          float far_, unsigned status) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) v.rays_o[r * 3 + a] = o[a], v.rays_d[r * 3 + a] = d[a];
-  v.near_[r] = near_;
-  v.far_[r] = far_;
-  v.t[r] = near_;
-  v.status[r] = (uint8_t)status;
-  v.steps[r] = 0;
-  v.side[r] = 0;
-  v.bracket[r * 4 + 0] = near_;
-  v.bracket[r * 4 + 1] = 0.f;
-  v.bracket[r * 4 + 2] = near_;
-  v.bracket[r * 4 + 3] = 0.f;
-}
-
-// the entered rays of this workgroup, compacted behind the element's counter: active list and first sample points
-__device__ __forceinline__ void enter_rays(const oi_trace_state& v, long long r, bool entered, float near_, int* live,
-                                           unsigned* lds) {
-  const long long slot = wg_slot(entered, v.counts, lds, live);
-  if (entered) {
-    v.active[slot] = (int)r;
-    point_at(v.rays_o, v.rays_d, r, near_, v.points + slot * 3);
-  }
-}
 
 __global__ void __launch_bounds__(TR_THREADS) scene_begin_kernel(const oi_trace_state s, int* __restrict__ live,
                                                                  const float* __restrict__ c2b, const float* __restrict__ kinv,
@@ -148,38 +84,7 @@ __global__ void __launch_bounds__(TR_THREADS) scene_visible_kernel(const oi_trac
   if (mine) vis_index[base + slot] = (int)r;
 }
 
-// oi_surface_params' fields for one element of the scene (surface_shade_at's P)
-struct ElementSurface {
-  int L;
-  const float *rays_o, *rays_d, *t;
-  const int* hit_slot;
-  const float *hit_points, *grad, *rgb, *w2b, *lights, *bg, *visibility;
-  float *depth, *position, *normal, *normal_world, *albedo, *mask, *image;
-};
-
-__global__ void __launch_bounds__(TR_THREADS) scene_shade_kernel(const oi_scene_shade_params p) {
-  const long long M = (long long)p.S * p.S, N = (long long)p.W * p.W;
-  const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  if (q >= M) return;
-  const int e = p.owner[q];
-  const bool hit = e >= 0 && e < p.E && p.n_pad > 0;
-  const long long eo = hit ? e : 0, r = hit ? p.owner_ray[q] : 0;
-  ElementSurface v;
-  v.L = p.L;
-  v.rays_o = p.rays_o + eo * N * 3, v.rays_d = p.rays_d + eo * N * 3, v.t = p.t + eo * N;
-  v.hit_slot = p.vis_slot + eo * N;
-  v.hit_points = p.hit_points + eo * p.n_pad * 3, v.grad = p.grad + eo * p.n_pad * 3, v.rgb = p.rgb + eo * p.n_pad * 3;
-  v.w2b = p.w2b + eo * 16, v.lights = p.lights, v.bg = p.bg, v.visibility = p.visibility;
-  v.depth = p.depth, v.position = nullptr, v.normal = p.normal, v.normal_world = p.normal_world, v.albedo = p.albedo;
-  v.mask = p.mask, v.image = p.image;
-  if (p.instance) p.instance[q] = hit ? e : -1;
-  if (p.position) {
-    float w[3] = {0.f, 0.f, 0.f};
-    if (hit) transform_point(p.b2w + eo * 16, v.hit_points + (long long)v.hit_slot[r] * 3, w);
-    p.position[q * 3 + 0] = w[0], p.position[q * 3 + 1] = w[1], p.position[q * 3 + 2] = w[2];
-  }
-  surface_shade_at(v, nullptr, r, hit, q, M);
-}
+__global__ void __launch_bounds__(TR_THREADS) scene_shade_kernel(const oi_scene_shade_params p) { scene_shade_pixel(p, nullptr); }
 
 __global__ void __launch_bounds__(TR_THREADS) scene_points_kernel(const int* __restrict__ counts,
                                                                   const float* __restrict__ hit_points,
@@ -319,19 +224,8 @@ int oi_scene_visible(const oi_trace_batch* b, const int* owner, const int* windo
 
 int oi_scene_shade(const oi_scene_shade_params* p, oi_stream_t stream) {
   const char* what = "oi_scene_shade";
-  OI_REQUIRE(p != nullptr, "%s: null params", what);
-  OI_REQUIRE(p->E >= 1 && p->E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, p->E, OI_TRACE_BATCH_MAX_ELEMS);
-  OI_REQUIRE(p->W >= 1 && (long long)p->E * p->W * p->W < (1ll << 31), "%s: E=%d, W=%d (W >= 1, E * W * W < 2^31)", what, p->E,
-             p->W);
-  OI_REQUIRE(p->S >= 1 && p->S <= OI_SCENE_MAX_RESOLUTION, "%s: S=%d (1 .. %d)", what, p->S, OI_SCENE_MAX_RESOLUTION);
-  OI_REQUIRE(p->n_pad >= 0 && p->n_pad <= (long long)p->W * p->W, "%s: n_pad=%lld (0 <= n_pad <= W * W = %lld)", what, p->n_pad,
-             (long long)p->W * p->W);
-  OI_REQUIRE(p->image ? (p->L >= 1 && p->L <= OI_RELIGHT_MAX_LIGHTS && p->lights) : p->L >= 0,
-             "%s: L=%d (1 .. %d lights with an image)", what, p->L, OI_RELIGHT_MAX_LIGHTS);
-  OI_REQUIRE(p->owner && p->owner_ray, "%s: null owner map", what);
-  OI_REQUIRE(p->n_pad == 0 || (p->rays_o && p->rays_d && p->t && p->vis_slot && p->hit_points && p->grad && p->rgb &&
-                               p->w2b && p->b2w),
-             "%s: null input pointer with n_pad=%lld", what, p->n_pad);
+  int rc = check_scene_shade(p, what);
+  if (rc != OI_OK) return rc;
   hipLaunchKernelGGL(scene_shade_kernel, dim3(n_blocks((long long)p->S * p->S)), dim3(TR_THREADS), 0, oi::as_stream(stream), *p);
   return oi::check_launch(what);
 }

@@ -1,5 +1,6 @@
-// What trace.hip, occlusion.hip, trace_batch.hip and scene.hip share (include/oi_trace.h, include/oi_occlusion.h,
-// include/oi_trace_batch.h, include/oi_scene.h; DESIGN sections 4.13, 4.16, 4.17 and 4.19): the workgroup compaction, the ray
+// What trace.hip, occlusion.hip, trace_batch.hip, envlight.hip, scene.hip and scene_light.hip share (include/oi_trace.h,
+// include/oi_occlusion.h, include/oi_trace_batch.h, include/oi_envlight.h, include/oi_scene.h, include/oi_scene_light.h;
+// DESIGN sections 4.13, 4.16 - 4.19 and 4.21): the workgroup compaction, the ray
 // state machine (the full one and its any-hit form, one template), the light's direction, the sample numbers and directions
 // of the secondary rays (occlusion.hip, envgloss.hip), the shadow ray of a surface point and the per-pixel shading.
 // Everything here has internal linkage; each source file instantiates what it exports.
@@ -271,6 +272,54 @@ __device__ __forceinline__ void direction_about(float ax, float ay, float az, fl
   if (sa == 0.f) dx = ax, dy = ay, dz = az;  // (the sums above give a up to the sign of a zero)
 }
 
+constexpr float HALF_PI = 1.57079632679489662f;
+
+// Sample j of S at the pixel `pix` of a point with the unit normal n (include/oi_occlusion.h): AMBIENT = false: uniform in
+// solid angle over the cap of angular radius radius[l] (clamped) about light lt's direction in the frame w2b; AMBIENT =
+// true: cosine-weighted over the hemisphere about n (lt, radius, w2b are not read).  -> the direction; traced: n . d > 0.
+// occlusion.hip's begin kernel and scene_light.hip's draw their directions here.
+template <bool AMBIENT>
+__device__ __forceinline__ bool occlusion_direction(float nx, float ny, float nz, unsigned pix, unsigned seed, unsigned j, int S,
+                                                    const float* __restrict__ lt, const float* __restrict__ radius, long long l,
+                                                    const float* __restrict__ w2b, float& dx, float& dy, float& dz) {
+  float u1, u2;
+  sample_numbers(pix, seed, j, S, u1, u2);
+  float ax, ay, az, sa, ca;
+  if (AMBIENT) {
+    ax = nx, ay = ny, az = nz;
+    ca = sqrtf(1.0f - u1);
+    sa = sqrtf(u1);
+  } else {
+    light_dir(lt, w2b, ax, ay, az);
+    const float rad = fminf(fmaxf(radius[l], 0.f), HALF_PI);  // (fmaxf drops a NaN)
+    const float m = u1 * (1.0f - cosf(rad));
+    ca = 1.0f - m;
+    sa = sqrtf(fmaxf(m * (2.0f - m), 0.f));  // sqrt(1 - ca^2) without the cancellation
+  }
+  direction_about(ax, ay, az, sa, ca, u2, dx, dy, dz);
+  return nx * dx + ny * dy + nz * dz > 0.f;
+}
+
+// include/oi_envlight.h's basis of a unit vector
+__device__ __forceinline__ void sh9(float x, float y, float z, float* __restrict__ o) {
+  o[0] = 0.28209479177387814f;
+  o[1] = 0.4886025119029199f * y;
+  o[2] = 0.4886025119029199f * z;
+  o[3] = 0.4886025119029199f * x;
+  o[4] = 1.0925484305920792f * (x * y);
+  o[5] = 1.0925484305920792f * (y * z);
+  o[6] = 0.31539156525252005f * (3.0f * (z * z) - 1.0f);
+  o[7] = 1.0925484305920792f * (x * z);
+  o[8] = 0.5462742152960396f * (x * x - y * y);
+}
+
+// v = w2b[:3,:3]^T d (surface_shade_pixel's rotation of the normal)
+__device__ __forceinline__ void to_world(const float* __restrict__ Wb, float dx, float dy, float dz, float& x, float& y, float& z) {
+  x = Wb[0] * dx + Wb[4] * dy + Wb[8] * dz;
+  y = Wb[1] * dx + Wb[5] * dy + Wb[9] * dz;
+  z = Wb[2] * dx + Wb[6] * dy + Wb[10] * dz;
+}
+
 // oi_trace_shadow_begin's ray of hit i under the light lt: n = g / max(|g|, 1e-6), l = the light's direction in the object
 // frame; origin = point + bias n, direction = l, far = the exit of the unit sphere; traced: n . l > 0.
 struct ShadowRay {
@@ -292,8 +341,8 @@ __device__ __forceinline__ ShadowRay shadow_ray(const float* __restrict__ hit_po
   return r;
 }
 
-// One pixel of the G-buffer and of the Phong image.  P: oi_surface_params or a struct with the same fields; ao: [N] ambient
-// occlusion or nullptr (the ambient term as it is).  The inputs are read at ray r of p (only where `hit`), the outputs
+// One pixel of the G-buffer and of the Phong image.  P: oi_surface_params or a struct with the same fields; ao: ambient occlusion
+// per output pixel (read at q) or nullptr (the ambient term as it is).  The inputs are read at ray r of p (only where `hit`), the outputs
 // written at pixel q of planes of M pixels (p.visibility is read there too): r == q and M == p.N for a single view; a scene
 // (scene.hip) reads the owner's ray and writes the scene's pixel.
 template <class P>
@@ -328,7 +377,7 @@ __device__ __forceinline__ void surface_shade_at(const P& p, const float* __rest
   }
   if (!p.image) return;
   const bool occluded = ao != nullptr;
-  const float aov = occluded && hit ? ao[r] : 1.0f;
+  const float aov = occluded && hit ? ao[q] : 1.0f;
   for (int l = 0; l < p.L; ++l) {
     float* img = p.image + (long long)l * 3 * M + q;
     if (!hit) {

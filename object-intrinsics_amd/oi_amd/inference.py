@@ -243,14 +243,17 @@ def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True,
 
 @torch.no_grad()
 def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True, bg=None, bias=None, window=None,
-                     max_shadow_rays=None, **kw):
+                     max_shadow_rays=None, shadow_samples=1, light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0, **kw):
     """surface_light_walk on a scene of K instances (oi_amd.scene): the scene is traced ONCE -- one batched
     march, one depth resolve, one full MLP pass at the visible hits -- and shaded under the walk of lights, each instance
     shadowing itself and the others.  Frame 0 is the trained light.  The lights are split so that one shadow batch holds at
     most max_shadow_rays rays (default oi_amd.scene.MAX_SHADOW_RAYS), counted as K * lights * visible points, and at most 256
     lights; the frames do not depend on the split (rays are independent).  -> {"image": (n_frames, 3, S, S), "visibility":
-    (n_frames, 1, S, S) when shadows, "mask" / "depth" / "instance" (1, 1, S, S), "stats"}.  kw: tol, omega, max_steps,
-    readback of sphere_trace."""
+    (n_frames, 1, S, S) when shadows, "mask" / "depth" / "instance" (1, 1, S, S), "stats"}.
+    shadow_samples, light_radius (a scalar or one value per frame), ao_samples, ao_distance, seed: SceneSurface.shade's soft
+    shadows and ambient occlusion between the instances; a light whose samples do not fit one batch is
+    traced in chunks of samples.  Ambient occlusion does not depend on the light: ONE trace for the walk, returned as
+    "ambient_occlusion" (1, 1, S, S).  kw: tol, omega, max_steps, readback of sphere_trace."""
     from . import lib, scene, trace
     from .relight import Light, stack_lights
     base = Light.from_module(gen.light)
@@ -259,6 +262,7 @@ def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True,
     lt = stack_lights([base] + [base.replace(direction=tuple(d)) for d in dirs[1:]], dev)
     gen.eval()
     gen.renderer.pack.check()
+    radii = trace._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_frames, "scene_light_walk")
     limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
     s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, **kw)
     S, M = s.S, s.S * s.S
@@ -266,20 +270,24 @@ def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True,
     vis_all = torch.empty(n_frames, M, device=dev) if shadows else None
     step = lib.RELIGHT_MAX_LIGHTS
     if shadows:   # (one light above the limit: SceneSurface.visibility refuses it, naming the count)
-        step = max(1, min(step, limit // max(1, s.E * sum(s.n_vis))))
+        per_light = s.E * sum(s.n_vis) * (int(shadow_samples) if radii is not None else 1)
+        step = max(1, min(step, limit // max(1, per_light)))
+    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples else None
     maps = None
     for a in range(0, n_frames, step):
         b = min(n_frames, a + step)
-        vis = s.visibility(lt[a:b], limit) if shadows else None
+        vis = s.visibility(lt[a:b], None if radii is None else radii[a:b], int(shadow_samples), int(seed), limit) if shadows else None
         if shadows:
             vis_all[a:b] = vis
         out = s._shade(lt[a:b], trace._bg(bg, dev), vis, ("image",) if maps is not None else ("depth", "mask", "instance", "image"),
-                       image[a:b])
+                       image[a:b], ao)
         maps = maps or out
     res = {"image": image.view(n_frames, 3, S, S), "stats": s.stats()}
     res.update({k: maps[k].view(1, 1, S, S) for k in ("mask", "depth", "instance")})
     if shadows:
         res["visibility"] = vis_all.view(n_frames, 1, S, S)
+    if ao_samples:
+        res["ambient_occlusion"] = ao.view(1, 1, S, S)
     return res
 
 
@@ -316,6 +324,31 @@ def env_walk(gen, z, b2w, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64
     res.update(transfer=cap.transfer, mask=cap.maps["mask"], depth=cap.maps["depth"], stats=cap.stats())
     if cap.glossy_samples is not None:
         res["spec_visibility"] = cap.spec_visibility
+    return res
+
+
+@torch.no_grad()
+def scene_env_walk(gen, zs, b2ws, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64, seed=0, bg=None, bias=None, window=None,
+                   max_shadow_rays=None, **kw):
+    """env_walk on a scene of K instances (oi_amd.scene): ONE scene trace and ONE capture
+    (SceneSurface.capture_transfer: transfer_samples secondary rays per visible point, each tested against every instance),
+    then n_frames rotations of the 9 x 3 coefficients on the host and one shade launch per 256 frames.  Frame 0 is `env`
+    itself.  -> {"image", "shading": (n_frames, 3, S, S), "transfer": (1, 9, S, S), "mask" / "depth" / "instance" (1, 1, S, S),
+    "stats"}.  kw: tol, omega, max_steps, readback of sphere_trace."""
+    from . import scene, trace
+    from .envlight import EnvLight
+    if not isinstance(env, EnvLight):
+        raise TypeError(f"scene_env_walk: expected an EnvLight, got {type(env).__name__}")
+    rots = env_walk_rotations(n_frames, axis)
+    trace._check_transfer(transfer_samples, seed, "scene_env_walk")
+    gen.eval()
+    gen.renderer.pack.check()
+    limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
+    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, **kw)
+    cap = s.capture_transfer(transfer_samples, seed, limit)
+    out = cap.shade([env.rotated(R) for R in rots], bg)
+    res = {k: out[k] for k in ("image", "shading", "mask", "depth", "instance")}
+    res.update(transfer=cap.transfer, stats=cap.scene.stats())
     return res
 
 

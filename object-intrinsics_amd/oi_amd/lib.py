@@ -315,6 +315,19 @@ SIGS = {
         "oi_occlusion_lobe_begin": (_i, [_P(TraceState), _vp, _vp, _vp, _vp, _ll, _i, _f, _f, _u, _vp]),
         "oi_env_shade_glossy": (_i, [_P(EnvShadeParams)] + [_vp] * 6 + [_i, _i, _i, _P(_i), _vp, _vp, _vp, _vp]),
     },
+    # include/oi_scene_light.h: sampled secondary rays between the instances of a scene (an addition to oi_scene.h,
+    # oi_occlusion.h and oi_envlight.h).  Its two parameter structs are bound as plain pointers: their mirrors stand in
+    # oi_amd.ops next to their only users (SceneOcclusionParams, SceneShadeAoParams), held against the header field by field
+    # by tests/test_scene_light_cpu.py
+    "oi_scene_light.h": {
+        "oi_scene_point_pixels": (_i, [_P(TraceBatch), _vp, _vp, _i, _i, _vp, _ll, _vp, _vp]),
+        "oi_scene_occlusion_begin": (_i, [_P(TraceBatch), _vp, _vp]),
+        "oi_trace_batch_step_anyhit": (_i, [_P(TraceBatch), _vp, _ll, _i, _f, _f, _vp]),
+        "oi_scene_occlusion_resolve": (_i, [_vp] * 5 + [_i, _ll, _i, _i, _i, _i, _ll, _i, _i, _vp, _vp, _vp]),
+        "oi_scene_transfer_resolve": (_i, [_vp] * 7 + [_i, _ll, _i, _i, _i, _ll, _i, _i, _vp, _vp]),
+        "oi_scene_transfer_normal": (_i, [_vp, _ll] + [_vp] * 4 + [_i, _ll, _i, _vp, _vp]),
+        "oi_scene_shade_ao": (_i, [_vp, _vp]),
+    },
 }
 
 

@@ -815,14 +815,22 @@ def scene_shade(st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_p
     0).  -> {name: (S * S,) or (S * S, 3)} for the names of SCENE_OUT in `outputs` ("instance": int32), and "image" (L, 3,
     S * S) (written into `image_out` when given)."""
     P = _l.SceneShadeParams()
-    res = _shade_planes("scene_shade", SCENE_OUT, P, S * S, st.t, outputs, lights, visibility, image_out)
+    res, _keep = _scene_shade("scene_shade", P, st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_pad, w2b, b2w, lights,
+                              bg, visibility, outputs, image_out)
+    _l.check(_l.load().oi_scene_shade(ctypes.byref(P), _stream()), "oi_scene_shade")
+    return res
+
+
+def _scene_shade(what, P, st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_pad, w2b, b2w, lights, bg, visibility,
+                 outputs, image_out):
+    """The arguments scene_shade and scene_shade_ao share, filled into the struct P.  -> (outputs, tensors to keep)."""
+    res = _shade_planes(what, SCENE_OUT, P, S * S, st.t, outputs, lights, visibility, image_out)
     P.E, P.W, P.S, P.n_pad = st.E, int(W), int(S), int(n_pad)
     keep = [_c(x) for x in (hit_points, grad, rgb, w2b, b2w, lights, bg, visibility)]
     P.hit_points, P.grad, P.rgb, P.w2b, P.b2w, P.lights, P.bg, P.visibility = (_p(x) for x in keep)
     P.rays_o, P.rays_d, P.t = _p(st.rays_o), _p(st.rays_d), _p(st.t)
     P.owner, P.owner_ray, P.vis_slot = _ip(owner), _ip(owner_ray), _ip(vis_slot)
-    _l.check(_l.load().oi_scene_shade(ctypes.byref(P), _stream()), "oi_scene_shade")
-    return res
+    return res, keep
 
 
 def scene_points(st, hit_points, grad, n_pad, offset, n_vis, b2w, w2b):
@@ -847,6 +855,96 @@ def scene_visibility(shadow_status, owner, owner_ray, vis_slot, offset, E, N, L,
     _l.check(_l.load().oi_scene_visibility(_p(shadow_status), _ip(owner), _ip(owner_ray), _ip(vis_slot), _ip(offset), int(E), int(N),
                                            int(L), int(n_vis), int(S), _p(vis), _stream()), "oi_scene_visibility")
     return vis
+
+
+# ------------------------------------------------------------------------------------------
+# sampled secondary rays between the instances of a scene (include/oi_scene_light.h); oi_amd.scene sequences these
+# ------------------------------------------------------------------------------------------
+
+class SceneOcclusionParams(ctypes.Structure):
+    """Mirror of `oi_scene_occlusion_params` (include/oi_scene_light.h)."""
+    _fields_ = ([(n, ctypes.c_int) for n in ("L", "S", "j0", "Sc", "ambient")] +
+                [("seed", ctypes.c_uint), ("bias", ctypes.c_float), ("distance", ctypes.c_float), ("n_pad", ctypes.c_longlong),
+                 ("n_vis", ctypes.c_longlong)] +
+                [(n, _vp) for n in ("hit_points", "grad", "offset", "elem", "pixel", "position", "normal", "lights", "radius", "w2b")])
+
+
+class SceneShadeAoParams(ctypes.Structure):
+    """Mirror of `oi_scene_shade_ao_params` (include/oi_scene_light.h): the scene's shade parameters, then the occlusion
+    factor."""
+    _fields_ = [("s", _l.SceneShadeParams), ("ambient_occlusion", _vp)]
+
+
+def scene_point_pixels(st, vis_index, window, W, S, offset, n_vis):
+    """-> pixel (n_vis,) int32: the scene pixel Y * S + X of visible point offset[e] + slot."""
+    pixel = _new(st.t, n_vis).view(torch.int32)
+    _l.check(_l.load().oi_scene_point_pixels(ctypes.byref(st.c), _ip(vis_index), _ip(window), int(W), int(S), _ip(offset), int(n_vis),
+                                             _ip(pixel), _stream()), "oi_scene_point_pixels")
+    return pixel
+
+
+def scene_occlusion_begin(sb, hit_points, grad, n_pad, offset, elem, pixel, position, normal, n_vis, w2b, bias, samples, j0, chunk,
+                          seed=0, lights=None, radius=None, distance=None):
+    """sb: TraceBatchState of E occluder elements x L * chunk * n_vis rays (trace_batch_state_empty): the samples [j0, j0 +
+    chunk) of `samples` strata.  lights (L, 16) and radius (L,) float32: caps about the lights; distance (a float, inf
+    allowed) instead: the hemisphere about the normal."""
+    ambient = lights is None
+    if ambient == (distance is None) or (not ambient and radius is None):
+        raise ValueError("scene_occlusion_begin: give lights and radius, or distance (the ambient form)")
+    if not ambient and (not torch.is_tensor(radius) or radius.dtype != torch.float32 or tuple(radius.shape) != (lights.shape[0],)):
+        raise ValueError(f"scene_occlusion_begin: radius must be a float32 tensor of shape ({lights.shape[0]},), one per light")
+    P = SceneOcclusionParams()
+    P.L, P.S, P.j0, P.Sc, P.ambient = 1 if ambient else lights.shape[0], int(samples), int(j0), int(chunk), int(ambient)
+    P.seed, P.bias, P.distance, P.n_pad, P.n_vis = int(seed), float(bias), float(distance) if ambient else 0.0, int(n_pad), int(n_vis)
+    keep = [_c(x) for x in (hit_points, grad, position, normal, lights, radius, w2b)]
+    P.hit_points, P.grad, P.position, P.normal, P.lights, P.radius, P.w2b = (_p(x) for x in keep)
+    P.offset, P.elem, P.pixel = _ip(offset), _ip(elem), _ip(pixel)
+    _l.check(_l.load().oi_scene_occlusion_begin(ctypes.byref(sb.c), ctypes.byref(P), _stream()), "oi_scene_occlusion_begin")
+
+
+def trace_batch_step_anyhit(st, sdf, bound, k, tol, omega):
+    _l.check(_l.load().oi_trace_batch_step_anyhit(ctypes.byref(st.c), _p(sdf), int(bound), int(k), float(tol), float(omega),
+                                                  _stream()), "oi_trace_batch_step_anyhit")
+
+
+def scene_occlusion_resolve(status, owner, owner_ray, vis_slot, offset, E, N, L, samples, j0, chunk, n_vis, S, count, out, last):
+    """Adds the chunk's escaped samples to count (L, S * S) int32 (overwritten at j0 == 0); last: out (L, S * S) = count /
+    samples on the mask, 1 off it."""
+    _l.check(_l.load().oi_scene_occlusion_resolve(_p(status), _ip(owner), _ip(owner_ray), _ip(vis_slot), _ip(offset), int(E), int(N),
+                                                  int(L), int(samples), int(j0), int(chunk), int(n_vis), int(S), int(bool(last)),
+                                                  _ip(count), _p(out), _stream()), "oi_scene_occlusion_resolve")
+
+
+def scene_transfer_resolve(status, rays_d, owner, owner_ray, vis_slot, offset, w2b, E, N, samples, j0, chunk, n_vis, S, transfer,
+                           last):
+    """Adds the chunk's escaped samples' SH basis (world frame) to transfer (9, S * S) (overwritten at j0 == 0); last:
+    divided by samples."""
+    _l.check(_l.load().oi_scene_transfer_resolve(_p(status), _p(rays_d), _ip(owner), _ip(owner_ray), _ip(vis_slot), _ip(offset),
+                                                 _p(_c(w2b)), int(E), int(N), int(samples), int(j0), int(chunk), int(n_vis), int(S),
+                                                 int(bool(last)), _p(transfer), _stream()), "oi_scene_transfer_resolve")
+
+
+def scene_transfer_normal(grad, n_pad, owner, owner_ray, vis_slot, w2b, E, N, S):
+    """-> the unshadowed transfer map (9, S * S): A_band y_c(world normal) on the mask, zeros off it."""
+    out = _new(grad, _l.ENV_COEFFS, S * S)
+    _l.check(_l.load().oi_scene_transfer_normal(_p(grad), int(n_pad), _ip(owner), _ip(owner_ray), _ip(vis_slot), _p(_c(w2b)), int(E),
+                                                int(N), int(S), _p(out), _stream()), "oi_scene_transfer_normal")
+    return out
+
+
+def scene_shade_ao(st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_pad, w2b, b2w, lights=None, bg=None,
+                   visibility=None, ambient_occlusion=None, outputs=tuple(SCENE_OUT) + ("image",), image_out=None):
+    """scene_shade with an occlusion factor (S * S,) in [0, 1] on the ambient term (oi_scene_shade_ao); None: scene_shade's
+    bytes."""
+    if ambient_occlusion is not None and tuple(ambient_occlusion.shape) != (S * S,):
+        raise ValueError(f"scene_shade_ao: ambient_occlusion {tuple(ambient_occlusion.shape)}, expected {(S * S,)}")
+    A = SceneShadeAoParams()
+    res, _keep = _scene_shade("scene_shade_ao", A.s, st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_pad, w2b, b2w,
+                              lights, bg, visibility, outputs, image_out)
+    ao = _c(ambient_occlusion)
+    A.ambient_occlusion = _p(ao)
+    _l.check(_l.load().oi_scene_shade_ao(ctypes.byref(A), _stream()), "oi_scene_shade_ao")
+    return res
 
 
 # ------------------------------------------------------------------------------------------

@@ -1,14 +1,20 @@
 """A scene of many instances: K latents at K rigid poses in ONE scene image of the generator's own camera -- the picture
 the model was trained from -- with occlusion between the instances and the shadows they cast on each other
-(include/oi_scene.h).
+(include/oi_scene.h), and with sampled secondary rays between them: soft shadows, ambient occlusion
+and environment lighting (include/oi_scene_light.h).
 
     sample_scene   K latents and K poses from the generator's latent distribution and pose prior
     trace_scene    the light-independent half: windowed scene rays with a bounding-sphere cull, ONE batched march for all
                    instances (oi_amd.trace's, unchanged), the depth resolve across instances, the full MLP pass at the
                    VISIBLE hits only -> SceneSurface
     SceneSurface.shade  the scene under L lights, optionally with one shadow ray per light and visible point tested against
-                   EVERY instance
+                   EVERY instance -- or `shadow_samples` rays towards a light of angular radius `light_radius` (penumbrae) --
+                   and ambient occlusion (`ao_samples` rays over the hemisphere of each visible point), all of them tested
+                   against every instance: contact shadows between objects
     render_scene   both
+    SceneSurface.capture_transfer  the secondary rays traced ONCE into a per-pixel SH transfer map of the whole scene ->
+                   SceneTransfer, shaded under any number of environment lights (oi_amd.envlight.EnvLight)
+    render_scene_env  trace_scene + capture_transfer + shade
 
 The union of K surfaces is traced exactly by tracing each instance in its own box frame and keeping the nearest hit per
 pixel: the camera is shared and the poses are rigid, so the ray parameter of one scene pixel is comparable between
@@ -112,10 +118,10 @@ class SceneSurface:
         self.window = torch.from_numpy(origin.astype(np.int32)).to(dev)
         st = self.state = ops.trace_batch_state_empty(E, self.N, self.b2w)
         ops.scene_begin(st, prior["c2b"].contiguous(), gen._kinv(dev), self.window, W, S)
-        self.n_evals = self.n_steps = self.shadow_evals = self.n_pad = 0
+        self.n_evals = self.n_steps = self.shadow_evals = self.occlusion_evals = self.transfer_evals = self.n_pad = 0
         self.n_hit = self.n_vis = [0] * E
         self.owner = self.owner_ray = self.vis_slot = self.offset = self.points = self.grad = self.rgb = None
-        self._world = self.shadow = None
+        self._world = self._pixel = self.vis_index = self.shadow = self.ao = self.transfer_state = None
         bound = int(st.live[0].item())
         self.n_entered = st.counts[:, 0].tolist()
         if bound == 0:      # nothing enters a window: every ray is a MISS already
@@ -128,6 +134,7 @@ class SceneSurface:
         self.n_hit = st.counts[:, -1].tolist()
         self.owner, self.owner_ray = ops.scene_resolve(st, self.window, W, S)
         vis_index, self.vis_slot = ops.scene_visible(st, self.owner, self.window, W, S)
+        self.vis_index = vis_index
         self.n_pad = int(st.live[-1].item())
         self.n_vis = st.counts[:, -1].tolist()
         self.points = ops.trace_batch_gather(st, vis_index, self.n_pad)
@@ -143,12 +150,61 @@ class SceneSurface:
                                            self.w2b)
         return self._world
 
-    def visibility(self, lights, max_shadow_rays=MAX_SHADOW_RAYS):
-        """(L, S * S) visibility of `lights` (L, 16): one shadow ray per light and visible point, marched against EVERY
-        instance in one batch of E occluder elements; a pixel is lit when its ray missed them all."""
+    def point_pixels(self):
+        """(n_vis,) int32: the scene pixel of every visible point, the key of its sample sequence; computed once."""
+        if self._pixel is None:
+            self._pixel = ops.scene_point_pixels(self.state, self.vis_index, self.window, self.W, self.S, self.offset,
+                                                 sum(self.n_vis))
+        return self._pixel
+
+    def _sampled(self, what, samples, seed, max_shadow_rays, resolve, lights=None, radius=None, distance=None):
+        """The sampled any-hit trace against every instance, in chunks of the samples: a chunk holds E * L * Sc * n_vis rays, Sc
+        the largest number for which that stays within max_shadow_rays and below 2^31.  resolve(sb, j0, Sc, last) accumulates
+        each finished chunk.  -> (sdf evaluations per element, the last chunk's state)."""
+        L, n_vis = 1 if lights is None else lights.shape[0], sum(self.n_vis)
+        per = self.E * L * n_vis
+        chunk = min(int(samples), min(int(max_shadow_rays), (1 << 31) - 1) // per)
+        if chunk < 1:
+            raise ValueError(f"{what}: {self.E} instances x {L} lights x {n_vis} visible points = {per} rays per sample (at most "
+                             f"max_shadow_rays={max_shadow_rays} and below 2^31; inference.scene_light_walk splits the lights)")
+        pos, nrm, elem = self.world_points()
+        pixel = self.point_pixels()
+        evals, sb = 0, None
+        for j0 in range(0, int(samples), chunk):
+            c = min(chunk, int(samples) - j0)
+            sb = ops.trace_batch_state_empty(self.E, L * c * n_vis, pos)
+            ops.scene_occlusion_begin(sb, self.points, self.grad, self.n_pad, self.offset, elem, pixel, pos, nrm, n_vis, self.w2b,
+                                      self.bias, samples, j0, c, seed, lights, radius, distance)
+            bound = int(sb.live[0].item())
+            if bound:
+                total, _ = _t._march_batch(self.field, sb, *self.kw, bound=bound, anyhit=True)
+                evals += total
+                ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
+            resolve(sb, j0, c, j0 + c == int(samples))
+        return evals, sb
+
+    def visibility(self, lights, radius=None, samples=1, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """(L, S * S) visibility of `lights` (L, 16).  radius None (or all zero) and one sample: one shadow ray per light and
+        visible point, marched against EVERY instance in one batch of E occluder elements; a pixel is lit (1) when its ray
+        missed them all, else 0.  Otherwise radius (L,) holds the lights' angular radii and `samples` rays per light and
+        visible point sample each light's cap, every ray tested against every instance in its any-hit form: the share in
+        [0, 1] of a pixel's samples that reach the light.  Split into chunks of samples above max_shadow_rays."""
         L, n_vis = lights.shape[0], sum(self.n_vis)
         if n_vis == 0:
             return torch.ones(L, self.S * self.S, device=lights.device)
+        if radius is not None:
+            radius = torch.as_tensor(radius, dtype=torch.float32).reshape(-1).to(lights.device)
+        if int(samples) != 1 or (radius is not None and bool((radius != 0).any())):
+            if radius is None:
+                radius = torch.zeros(L, device=lights.device)
+            M = self.S * self.S
+            count, out = ops._new(lights, L, M).view(torch.int32), ops._new(lights, L, M)
+            resolve = lambda sb, j0, c, last: ops.scene_occlusion_resolve(
+                sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, L, samples, j0, c, n_vis, self.S,
+                count, out, last)
+            evals, self.shadow = self._sampled("SceneSurface.shade", samples, seed, max_shadow_rays, resolve, lights, radius)
+            self.shadow_evals += evals
+            return out
         rays = self.E * L * n_vis
         if rays > max_shadow_rays or rays >= 1 << 31:
             raise ValueError(f"SceneSurface.shade: {self.E} instances x {L} lights x {n_vis} visible points = {rays} shadow rays "
@@ -164,12 +220,56 @@ class SceneSurface:
         self.shadow = sb
         return ops.scene_visibility(sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, L, n_vis, self.S)
 
-    def _shade(self, lt, bg, vis, outputs, image_out=None):
-        """ops.scene_shade on this scene; without a visible hit nothing is launched and every map is its off-mask value."""
+    def ambient(self, samples, distance, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """(S * S,) ambient occlusion: the share of `samples` cosine-weighted hemisphere rays per visible point that meet no
+        instance -- the point's own or any other -- within `distance` (world units; inf allowed); 1 off the mask."""
+        M, n_vis, dev = self.S * self.S, sum(self.n_vis), self.b2w.device
+        if n_vis == 0:
+            return torch.ones(M, device=dev)
+        count, out = ops._new(self.b2w, 1, M).view(torch.int32), ops._new(self.b2w, 1, M)
+        resolve = lambda sb, j0, c, last: ops.scene_occlusion_resolve(
+            sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, 1, samples, j0, c, n_vis, self.S, count,
+            out, last)
+        evals, self.ao = self._sampled("SceneSurface.ambient", samples, seed, max_shadow_rays, resolve, distance=float(distance))
+        self.occlusion_evals += evals
+        return out.view(M)
+
+    def transfer(self, samples, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """(9, S * S) SH transfer map of the scene in the WORLD frame (include/oi_scene_light.h): ambient()'s rays without a
+        distance limit, resolved into the mean of [escaped every instance] y_c(world direction) per pixel; samples == 0: the
+        unshadowed closed form, nothing traced.  Zeros off the mask."""
+        M, n_vis = self.S * self.S, sum(self.n_vis)
+        if n_vis == 0:
+            return torch.zeros(_l.ENV_COEFFS, M, device=self.b2w.device)
+        if samples == 0:
+            return ops.scene_transfer_normal(self.grad, self.n_pad, self.owner, self.owner_ray, self.vis_slot, self.w2b, self.E, self.N,
+                                             self.S)
+        out = ops._new(self.b2w, _l.ENV_COEFFS, M)
+        resolve = lambda sb, j0, c, last: ops.scene_transfer_resolve(
+            sb.status, sb.rays_d, self.owner, self.owner_ray, self.vis_slot, self.offset, self.w2b, self.E, self.N, samples, j0, c,
+            n_vis, self.S, out, last)
+        evals, self.transfer_state = self._sampled("SceneSurface.capture_transfer", samples, seed, max_shadow_rays, resolve,
+                                                   distance=math.inf)
+        self.transfer_evals += evals
+        return out
+
+    def capture_transfer(self, transfer_samples=64, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """The scene prepared for environment lighting: `transfer_samples` (0 .. 256) cosine-weighted rays per visible point,
+        each tested against EVERY instance, resolved into a 9-coefficient world-frame transfer vector per scene pixel (0: the
+        unshadowed closed form, nothing traced).  -> SceneTransfer."""
+        samples, seed = _t._check_transfer(transfer_samples, seed, "SceneSurface.capture_transfer")
+        transfer = self.transfer(samples, seed, max_shadow_rays)
+        out = self._shade(None, None, None, ("depth", "position", "normal_world", "albedo", "mask", "instance"))
+        return SceneTransfer(self, transfer, out, samples)
+
+    def _shade(self, lt, bg, vis, outputs, image_out=None, ao=None):
+        """ops.scene_shade on this scene (ao: ops.scene_shade_ao, the occlusion factor (S * S,) on the ambient term); without a
+        visible hit nothing is launched and every map is its off-mask value."""
         M, dev = self.S * self.S, lt.device if lt is not None else self.b2w.device
         if self.n_pad:
-            return ops.scene_shade(self.state, self.W, self.S, self.owner, self.owner_ray, self.vis_slot, self.points, self.grad,
-                                   self.rgb, self.n_pad, self.w2b, self.b2w, lt, bg, vis, outputs, image_out)
+            args = (self.state, self.W, self.S, self.owner, self.owner_ray, self.vis_slot, self.points, self.grad, self.rgb, self.n_pad,
+                    self.w2b, self.b2w, lt, bg, vis)
+            return ops.scene_shade(*args, outputs, image_out) if ao is None else ops.scene_shade_ao(*args, ao, outputs, image_out)
         res = {}
         for k in outputs:
             if k == "image":
@@ -183,40 +283,101 @@ class SceneSurface:
                 res[k] = torch.zeros((M,) if ops.SCENE_OUT[k] == (1,) else (M, 3), device=dev)
         return res
 
-    def shade(self, lights=None, shadows=False, bg=None, max_shadow_rays=MAX_SHADOW_RAYS):
+    def shade(self, lights=None, shadows=False, bg=None, max_shadow_rays=MAX_SHADOW_RAYS, shadow_samples=1, light_radius=0.0,
+              ao_samples=0, ao_distance=0.5, seed=0):
         """The scene under `lights` (oi_amd.relight.Light objects in the WORLD frame; default the generator's trained light; at
         most RELIGHT_MAX_LIGHTS).  -> dict of image (L, 3, S, S); depth (the ray parameter; NaN off the mask), mask, instance
         (int32, -1 off the mask) (1, 1, S, S); position (world frame), normal_map (world frame), albedo (1, 3, S, S);
         visibility (L, 1, S, S) when `shadows` (refused above max_shadow_rays = E * L * n_vis rays); stats.  bg: (3,)
-        background colour (black when None)."""
+        background colour (black when None).
+        Soft shadows: light_radius (radians; a scalar or one value per light) and shadow_samples (1 .. 256), as
+        oi_amd.trace.render_surface takes them: `visibility` is the share in [0, 1] of the samples that reach the light past
+        EVERY instance.  Ambient occlusion: ao_samples > 0 rays over each visible point's hemisphere as far as ao_distance (world
+        units), tested against every instance; the share that escapes multiplies the ambient term and is returned as
+        ambient_occlusion (1, 1, S, S).  The samples are a function of scene pixel, sample number and `seed` alone; traces
+        above max_shadow_rays are split into chunks of samples, which changes no byte.  At the defaults the launches and the
+        bytes are those of a call without these arguments."""
         dev = self.b2w.device
         lt = _t._stack_lights(self.gen, lights, dev, "SceneSurface.shade", "; inference.scene_light_walk splits larger sets")
-        vis = self.visibility(lt, max_shadow_rays) if shadows else None
-        out = self._shade(lt, _t._bg(bg, dev), vis, ("depth", "position", "normal_world", "albedo", "mask", "instance", "image"))
+        radii = _t._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0],
+                                    "SceneSurface.shade")
+        vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays) if shadows else None
+        ao = self.ambient(int(ao_samples), float(ao_distance), int(seed), max_shadow_rays) if ao_samples else None
+        out = self._shade(lt, _t._bg(bg, dev), vis, ("depth", "position", "normal_world", "albedo", "mask", "instance", "image"), ao=ao)
         S = self.S
         res = {_MAP_NAMES[k]: v for k, v in _t._maps({k: v for k, v in out.items() if k != "image"}, S, S).items()}
         res["image"] = out["image"].view(-1, 3, S, S)
         if shadows:
             res["visibility"] = vis.view(-1, 1, S, S)
+        if ao_samples:
+            res["ambient_occlusion"] = ao.view(1, 1, S, S)
         res["stats"] = self.stats()
         return res
 
     def stats(self):
         """Per instance: rays entered and culled, rays per status (culled rays are misses), hits, visible hits; sdf
-        evaluations of the primary march and of the shadow marches so far (every instance carries the batch's bound)."""
+        evaluations of the primary march and of the shadow, ambient-occlusion and transfer marches so far (every instance carries
+        the batch's bound)."""
         st = self.state
         per = torch.stack([torch.bincount(st.status[e].long(), minlength=6)[:6] for e in range(self.E)]).tolist()
         out = []
         for e in range(self.E):
             s = {name: int(per[e][code]) for code, name in _l.TRACE_STATUS_NAMES.items()}
             s.update(n_rays=self.N, entered=int(self.n_entered[e]), culled=self.N - int(self.n_entered[e]), hits=int(self.n_hit[e]),
-                     visible=int(self.n_vis[e]), n_evals=self.n_evals, n_steps=self.n_steps, shadow_evals=self.shadow_evals)
+                     visible=int(self.n_vis[e]), n_evals=self.n_evals, n_steps=self.n_steps, shadow_evals=self.shadow_evals,
+                     occlusion_evals=self.occlusion_evals, transfer_evals=self.transfer_evals)
             out.append(s)
         return out
 
 
 _MAP_NAMES = {"depth": "depth", "position": "position", "normal_world": "normal_map", "albedo": "albedo", "mask": "mask",
               "instance": "instance"}
+
+
+class SceneTransfer:
+    """One traced scene and its SH transfer map: everything shade() needs, none of which depends on the light.
+    scene: the SceneSurface; transfer (1, 9, S, S), world frame; maps: SceneSurface.shade's G-buffer maps (depth, position,
+    normal_map, albedo, mask, instance); samples: the rays per visible point (0: the closed form)."""
+
+    def __init__(self, scene, transfer, planes, samples):
+        S = scene.S
+        self.scene, self.samples, self.S = scene, samples, S
+        self._transfer = transfer                       # (9, S * S), planar: what oi_env_shade reads
+        self.transfer = transfer.view(1, _l.ENV_COEFFS, S, S)
+        self.maps = {_MAP_NAMES[k]: v for k, v in _t._maps(planes, S, S).items()}
+        # oi_env_shade's view of the scene's planes: every scene pixel is a ray, the owned ones are hits at their own index
+        M, dev = S * S, transfer.device
+        on = planes["instance"] >= 0
+        self._status = on.to(torch.uint8) * _l.TRACE_HIT
+        self._hit_slot = torch.where(on, torch.arange(M, dtype=torch.int32, device=dev), torch.full((M,), -1, dtype=torch.int32, device=dev))
+        self._rgb = planes["albedo"]
+
+    def shade(self, envs, bg=None):
+        """The scene under each of `envs` (oi_amd.envlight.EnvLight objects, any number: launches of ENV_MAX_ENVS).  ->
+        {"image": (F, 3, S, S) = max(shading, 0) albedo on the mask, bg off it; "shading": (F, 3, S, S), not clamped; the
+        G-buffer maps; "stats"}.  The glossy lobe (EnvMap) is not available in scenes."""
+        from .envlight import EnvLight, stack_envs
+        seq = [envs] if isinstance(envs, EnvLight) else list(envs)
+        if not seq or not all(isinstance(e, EnvLight) for e in seq):
+            raise ValueError("SceneTransfer.shade: EnvLight objects only (the glossy lobe of an EnvMap is not available in scenes)")
+        s, S = self.scene, self.S
+        dev, M = self._transfer.device, S * S
+        ev = stack_envs(seq, dev)
+        F = ev.shape[0]
+        bgv = _t._bg(bg, dev)
+        out = {k: ops._new(self._transfer, F, 3, M) for k in ops.ENV_SHADE_OUT}
+        if s.n_pad == 0:   # no hit at all: nothing is launched
+            out["shading"].zero_()
+            out["image"].copy_((torch.zeros(3, device=dev) if bgv is None else bgv).view(1, 3, 1).expand(F, 3, M))
+        else:
+            for a in range(0, F, _t.ENV_MAX_ENVS):
+                b = min(F, a + _t.ENV_MAX_ENVS)
+                ops.env_shade(self._status, self._hit_slot, self._rgb, M, self._transfer, ev[a:b], bgv,
+                              out={k: v[a:b] for k, v in out.items()})
+        res = {k: v.view(F, 3, S, S) for k, v in out.items()}
+        res.update(self.maps)
+        res["stats"] = s.stats()
+        return res
 
 
 @torch.no_grad()
@@ -232,11 +393,31 @@ def trace_scene(gen, zs, b2ws, window=None, bias=DEFAULT_BIAS, **trace_kw):
 
 @torch.no_grad()
 def render_scene(gen, zs, b2ws, lights=None, shadows=False, bg=None, window=None, bias=DEFAULT_BIAS,
-                 max_shadow_rays=MAX_SHADOW_RAYS, **trace_kw):
+                 max_shadow_rays=MAX_SHADOW_RAYS, shadow_samples=1, light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0,
+                 **trace_kw):
     """trace_scene + SceneSurface.shade: K instances in one scene image, nearer instances hiding farther ones and, with
-    `shadows`, every instance throwing its shadow on itself and on the others.  -> SceneSurface.shade's dict, with "scene" (the
-    SceneSurface)."""
+    `shadows`, every instance throwing its shadow on itself and on the others; shadow_samples, light_radius, ao_samples,
+    ao_distance, seed: shade's soft shadows and ambient occlusion between the instances.  -> SceneSurface.shade's dict, with
+    "scene" (the SceneSurface)."""
+    rad = light_radius.detach().cpu() if torch.is_tensor(light_radius) else light_radius
+    # (before the trace; shade checks a radius per light against the lights it stacks)
+    _t._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, np.size(rad) if np.ndim(rad) == 1 else 1,
+                        "render_scene")
     s = trace_scene(gen, zs, b2ws, window, bias, **trace_kw)
-    res = s.shade(lights, shadows, bg, max_shadow_rays)
+    res = s.shade(lights, shadows, bg, max_shadow_rays, shadow_samples, light_radius, ao_samples, ao_distance, seed)
     res["scene"] = s
+    return res
+
+
+@torch.no_grad()
+def render_scene_env(gen, zs, b2ws, envs, transfer_samples=64, seed=0, bg=None, window=None, bias=DEFAULT_BIAS,
+                     max_shadow_rays=MAX_SHADOW_RAYS, **trace_kw):
+    """trace_scene + capture_transfer + shade: K instances in one scene image under the environment lights `envs`
+    (oi_amd.envlight.EnvLight objects), every instance occluding the sky for itself and for the others.  ->
+    SceneTransfer.shade's dict, with "transfer" (1, 9, S, S), "scene" (the SceneSurface) and "capture" (the SceneTransfer)."""
+    _t._check_transfer(transfer_samples, seed, "render_scene_env")
+    s = trace_scene(gen, zs, b2ws, window, bias, **trace_kw)
+    cap = s.capture_transfer(transfer_samples, seed, max_shadow_rays)
+    res = cap.shade(envs, bg)
+    res.update(transfer=cap.transfer, scene=s, capture=cap)
     return res

@@ -78,7 +78,7 @@ def _march(field, st, bound, tol, omega, max_steps, readback, anyhit=False):
     """The one march loop, on a state that a begin entry has filled.  -> (sum of the bounds = points evaluated, per element
     of a batch; steps run).  An ops.TraceState steps with oi_trace_step -- anyhit: oi_occlusion_step, a ray ends at its first
     occluder -- after oi_sdf_mlp_fwd with B = 1 on the first `bound` points, and reads counts[k]; an ops.TraceBatchState steps
-    with oi_trace_batch_step after oi_sdf_mlp_fwd_segments on the first `bound` points of each of its E segments of N, and
+    with oi_trace_batch_step (anyhit: oi_trace_batch_step_anyhit) after oi_sdf_mlp_fwd_segments on the first `bound` points of each of its E segments of N, and
     reads live[k], the largest count of any element.  Two launches per step through the C ABI directly, the pointers converted
     and these differences bound once, before the loop: its tail is a handful of rays per step, where the host's time per
     launch is the frame's time."""
@@ -87,7 +87,7 @@ def _march(field, st, bound, tol, omega, max_steps, readback, anyhit=False):
     pts_p, sdf_p, state_p, stream = ops._p(st.points), ops._p(sdf), ctypes.byref(st.c), ops._stream()
     mlp_args = [pts_p, ops._p(field.packed), ops._p(field.gamma), ops._p(field.beta), sdf_p]
     if isinstance(st, ops.TraceBatchState):
-        mlp_name, step_name, counter = "oi_sdf_mlp_fwd_segments", "oi_trace_batch_step", st.live
+        mlp_name, step_name, counter = "oi_sdf_mlp_fwd_segments", "oi_trace_batch_step_anyhit" if anyhit else "oi_trace_batch_step", st.live
         mlp_args, at = mlp_args + [st.E, bound, st.N, field.prec, field.fast, stream], 6       # at: where the bound goes
     else:
         mlp_name, step_name, counter = "oi_sdf_mlp_fwd", "oi_occlusion_step" if anyhit else "oi_trace_step", st.counts
@@ -163,10 +163,10 @@ class TraceResults(list):
     n_hit = ()
 
 
-def _march_batch(field, st, tol, omega, max_steps, readback, bound=None):
+def _march_batch(field, st, tol, omega, max_steps, readback, bound=None, anyhit=False):
     """_march on an ops.TraceBatchState.  bound: live[0] where a begin kernel enters only some of the rays (oi_amd.scene),
-    else N."""
-    return _march(field, st, st.N if bound is None else int(bound), tol, omega, max_steps, readback)
+    else N.  anyhit: the sampled secondary rays of a scene, which end at their first occluder (oi_trace_batch_step_anyhit)."""
+    return _march(field, st, st.N if bound is None else int(bound), tol, omega, max_steps, readback, anyhit=anyhit)
 
 
 @torch.no_grad()

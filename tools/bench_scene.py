@@ -8,7 +8,13 @@ calls, golden SDF weights, f16x3 by default, K instances from oi_amd.scene.sampl
   crops_ms / crops_shadows_ms    for comparison, the parent's way of getting the same instances: K calls of
                                  oi_amd.trace.render_surface, each on its own crop of W x W pixels of the same scene image (W: the
                                  scene's window) -- which gives neither occlusion between instances nor mutual shadows
-No ratio is promised: the two do different work (the scene tests every shadow ray against all K instances)."""
+With --shadow-samples / --light-radius / --ao-samples the shadowed rows are the sampled ones of DESIGN section 4.21 (soft shadows
+and ambient occlusion between the instances; the crops trace theirs against their own instance alone), and --env adds
+
+  scene_env_ms                   oi_amd.scene.render_scene_env with --transfer-samples rays per visible point, every ray tested
+                                 against all K instances, under one constant environment
+  crops_env_ms                   K calls of oi_amd.trace.render_surface_env on the crops
+No ratio is promised: the two do different work (the scene tests every secondary ray against all K instances)."""
 import argparse
 import copy
 import json
@@ -22,6 +28,7 @@ import torch  # noqa: E402
 
 from bench import build_models  # noqa: E402
 from oi_amd import scene, trace  # noqa: E402
+from oi_amd.envlight import EnvLight  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--res", type=int, default=64, help="crop resolution of the generator; the scene image is res * 1588 / 256")
@@ -30,6 +37,11 @@ ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--precision", default="f16x3")
+ap.add_argument("--shadow-samples", type=int, default=1, help="rays per light and visible point of the shadowed rows")
+ap.add_argument("--light-radius", type=float, default=0.0, help="angular radius of the light in radians")
+ap.add_argument("--ao-samples", type=int, default=0, help="ambient-occlusion rays per visible point of the shadowed rows")
+ap.add_argument("--env", action="store_true", help="also time environment lighting (scene_env_ms / crops_env_ms)")
+ap.add_argument("--transfer-samples", type=int, default=64)
 args = ap.parse_args()
 
 
@@ -51,7 +63,10 @@ def median_ms(fn):
 gen, _ = build_models(args.res, 256, 64, 1, args.precision, "cuda")
 gen.eval()
 out = {"tool": "bench_scene", "precision": args.precision, "res": args.res, "scene_resolution": gen.scene_resolution,
-       "iters": args.iters, "warmup": args.warmup, "instances": {}}
+       "iters": args.iters, "warmup": args.warmup, "shadow_samples": args.shadow_samples, "light_radius": args.light_radius,
+       "ao_samples": args.ao_samples, "transfer_samples": args.transfer_samples if args.env else None, "instances": {}}
+soft = dict(shadow_samples=args.shadow_samples, light_radius=args.light_radius, ao_samples=args.ao_samples)
+envs = [EnvLight.constant(1.0)]
 with torch.no_grad():
     for K in (int(k) for k in args.instances.split(",")):
         zs, b2ws = scene.sample_scene(gen, K, args.seed)
@@ -61,11 +76,19 @@ with torch.no_grad():
 
         def crops(shadows):
             for z, b2w in zip(zs, b2ws):
-                trace.render_surface(crop, z, b2w, shadows=shadows)
+                trace.render_surface(crop, z, b2w, shadows=shadows, **(soft if shadows else {}))
+
+        def crops_env():
+            for z, b2w in zip(zs, b2ws):
+                trace.render_surface_env(crop, z, b2w, envs, transfer_samples=args.transfer_samples)
 
         row = {"window": s.W, "rays": K * s.N, "entered": sum(s.n_entered), "hits": sum(s.n_hit), "visible": sum(s.n_vis)}
         for name, shadows in (("", False), ("_shadows", True)):
-            row["scene" + name + "_ms"] = median_ms(lambda: scene.render_scene(gen, zs, b2ws, shadows=shadows))
+            kw = soft if shadows else {}
+            row["scene" + name + "_ms"] = median_ms(lambda: scene.render_scene(gen, zs, b2ws, shadows=shadows, **kw))
             row["crops" + name + "_ms"] = median_ms(lambda: crops(shadows))
+        if args.env:
+            row["scene_env_ms"] = median_ms(lambda: scene.render_scene_env(gen, zs, b2ws, envs, transfer_samples=args.transfer_samples))
+            row["crops_env_ms"] = median_ms(crops_env)
         out["instances"][str(K)] = row
 print(json.dumps(out))

@@ -1,6 +1,6 @@
-// What trace.hip, occlusion.hip, trace_batch.hip, envlight.hip, scene.hip and scene_light.hip share (include/oi_trace.h,
-// include/oi_occlusion.h, include/oi_trace_batch.h, include/oi_envlight.h, include/oi_scene.h, include/oi_scene_light.h;
-// DESIGN sections 4.13, 4.16 - 4.19 and 4.21): the workgroup compaction, the ray
+// What trace.hip, occlusion.hip, trace_batch.hip, envlight.hip, scene.hip, scene_light.hip and envbounce.hip share
+// (include/oi_trace.h, include/oi_occlusion.h, include/oi_trace_batch.h, include/oi_envlight.h, include/oi_scene.h,
+// include/oi_scene_light.h, include/oi_envbounce.h; DESIGN sections 4.13, 4.16 - 4.19, 4.21 and 4.22): the workgroup compaction, the ray
 // state machine (the full one and its any-hit form, one template), the light's direction, the sample numbers and directions
 // of the secondary rays (occlusion.hip, envgloss.hip), the shadow ray of a surface point and the per-pixel shading.
 // Everything here has internal linkage; each source file instantiates what it exports.

@@ -17,7 +17,10 @@ times a reflection-lobe visibility that capture_transfer(glossy_samples=...) tra
     cap = trace.capture_transfer(gen, z, b2w, glossy_samples=64)
     out = cap.shade([env, env.rotated(R)])            # image / shading / specular (2, 3, H, W); nothing is prefiltered again
 
-Bands above 2 of the diffuse term and interreflection are out of scope."""
+capture_transfer(bounces=1) folds one diffuse interreflection bounce into a per-channel transfer (include/oi_envbounce.h;
+DESIGN section 4.22): an EnvLight capture then also returns the indirect part of the shading.
+
+Bands above 2 of the diffuse term, more than one bounce and the bounce under an EnvMap are out of scope."""
 import math
 import warnings
 

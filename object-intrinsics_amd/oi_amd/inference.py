@@ -302,14 +302,16 @@ def env_walk_rotations(n_frames, axis=(0.0, 0.0, 1.0)):
 
 @torch.no_grad()
 def env_walk(gen, z, b2w, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64, seed=0, bg=None, bias=None,
-             glossy_samples=None, shininess=None, specular=None, **kw):
+             glossy_samples=None, shininess=None, specular=None, bounces=0, **kw):
     """The environment `env` (oi_amd.envlight.EnvLight or EnvMap) turning through 360 degrees about the world `axis` while the
     view stays: ONE capture (oi_amd.trace.capture_transfer: the primary trace, the full MLP pass at its hits and transfer_samples
     secondary rays per visible point), then n_frames rotations of the 9 x 3 coefficients on the host and one shade launch per
     256 frames.  Frame 0 is `env` itself.  -> {"image", "shading": (n_frames, 3, H, W), "transfer": (1, 9, H, W), "mask" /
     "depth" (1, 1, H, W), "stats"}.  An EnvMap takes the glossy path (glossy_samples, shininess: capture_transfer's; specular:
     shade's): the map is prefiltered once, when it is made, and every frame only rotates the lookup; the result also holds
-    "specular" (n_frames, 3, H, W) and "spec_visibility".  Keyword arguments: capture_transfer's (tol, omega, max_steps,
+    "specular" (n_frames, 3, H, W) and "spec_visibility".  bounces=1 (an EnvLight only): capture_transfer's one diffuse
+    interreflection bounce; the result also holds "indirect" (n_frames, 3, H, W) and "bounce" (1, 3, 9, H, W), and a frame
+    costs one dot product more per channel.  Keyword arguments: capture_transfer's (tol, omega, max_steps,
     readback)."""
     from . import trace
     from .envlight import EnvLight, EnvMap
@@ -319,9 +321,11 @@ def env_walk(gen, z, b2w, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64
     gen.eval()
     gen.renderer.pack.check()
     cap = trace.capture_transfer(gen, z, b2w, transfer_samples, seed, trace.DEFAULT_BIAS if bias is None else bias, glossy_samples,
-                                 shininess, **kw)
+                                 shininess, bounces, **kw)
     res = cap.shade([env.rotated(R) for R in rots], bg, specular)
     res.update(transfer=cap.transfer, mask=cap.maps["mask"], depth=cap.maps["depth"], stats=cap.stats())
+    if cap.bounce is not None:
+        res["bounce"] = cap.bounce
     if cap.glossy_samples is not None:
         res["spec_visibility"] = cap.spec_visibility
     return res

@@ -128,6 +128,10 @@ class EnvShadeParams(ctypes.Structure):
                 [(n, _vp) for n in ("status", "hit_slot", "rgb", "transfer", "envs", "bg", "shading", "image")])
 
 
+# include/oi_envbounce.h
+BOUNCE_FLOATS = 27
+
+
 # include/oi_envgloss.h
 ENVGLOSS_MIN_SHININESS, ENVGLOSS_MAX_SHININESS, ENVGLOSS_CHUNK = 1, 4096, 2048
 
@@ -327,6 +331,13 @@ SIGS = {
         "oi_scene_transfer_resolve": (_i, [_vp] * 7 + [_i, _ll, _i, _i, _i, _ll, _i, _i, _vp, _vp]),
         "oi_scene_transfer_normal": (_i, [_vp, _ll] + [_vp] * 4 + [_i, _ll, _i, _vp, _vp]),
         "oi_scene_shade_ao": (_i, [_vp, _vp]),
+    },
+    # include/oi_envbounce.h: one diffuse interreflection bounce in the transfer of a captured view (an addition to
+    # oi_envlight.h).  Its parameter struct is bound as a plain pointer: the mirror stands in oi_amd.ops next to its only user
+    # (EnvShadeBounceParams), held against the header field by field by tests/test_envbounce_cpu.py
+    "oi_envbounce.h": {
+        "oi_bounce_resolve": (_i, [_vp] * 6 + [_ll, _ll, _ll, _i, _vp, _vp, _vp]),
+        "oi_env_shade_bounce": (_i, [_vp, _vp]),
     },
 }
 

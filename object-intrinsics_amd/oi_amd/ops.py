@@ -1064,6 +1064,63 @@ def env_shade(status, hit_slot, rgb, n_hit, transfer, envs, bg=None, outputs=ENV
 
 
 # ------------------------------------------------------------------------------------------
+# one diffuse interreflection bounce under environment lighting (include/oi_envbounce.h)
+# ------------------------------------------------------------------------------------------
+
+def bounce_resolve(status, rays_d, hit_slot2, grad2, rgb2, n_hit2, hit_slot, N, n_hit, samples, w2b):
+    """The finished states (S * n_hit,) uint8, directions (S * n_hit, 3) and secondary hit slots (S * n_hit,) int32 of a
+    closest-hit trace of the transfer rays, the gradients and albedo (n_hit2, 3) at its hits (None when n_hit2 == 0) -> the
+    bounce transfer (3, 9, N) float32: per pixel and channel the mean over its `samples` rays of [front-facing hit] albedo
+    A_band y_c(world normal at the hit); zeros off the mask."""
+    out = _new(hit_slot, 3, _l.ENV_COEFFS, N)
+    g2, c2 = (_c(grad2), _c(rgb2)) if n_hit2 else (None, None)
+    _l.check(_l.load().oi_bounce_resolve(_p(status), _p(rays_d), _ip(hit_slot2), _p(g2), _p(c2), _ip(hit_slot), int(N),
+                                         int(n_hit), int(n_hit2), int(samples), _p(w2b), _p(out), _stream()), "oi_bounce_resolve")
+    return out
+
+
+class EnvShadeBounceParams(ctypes.Structure):
+    """Mirror of `oi_env_shade_bounce_params` (include/oi_envbounce.h): EnvShadeParams' fields, then the bounce transfer and
+    its output."""
+    _fields_ = _l.EnvShadeParams._fields_ + [("bounce", _vp), ("indirect", _vp)]
+
+
+ENV_BOUNCE_OUT = ENV_SHADE_OUT + ("indirect",)
+
+
+def env_shade_bounce(status, hit_slot, rgb, n_hit, transfer, bounce, envs, bg=None, outputs=ENV_BOUNCE_OUT, out=None):
+    """env_shade with the bounce transfer (3, 9, N) of bounce_resolve (oi_env_shade_bounce).  -> {name: (F, 3, N)} for the names
+    of ENV_BOUNCE_OUT in `outputs` (written into out[name] when given): shading = direct + indirect."""
+    N = transfer.shape[1]
+    F = envs.shape[0] if torch.is_tensor(envs) and envs.dim() == 3 else 0
+    if not 1 <= F <= _l.ENV_MAX_ENVS or tuple(envs.shape[1:]) != (_l.ENV_COEFFS, 3):
+        raise ValueError(f"env_shade_bounce: envs {tuple(getattr(envs, 'shape', ()))}, expected (F, {_l.ENV_COEFFS}, 3) with "
+                         f"1 <= F <= {_l.ENV_MAX_ENVS}")
+    if tuple(transfer.shape) != (_l.ENV_COEFFS, N) or not outputs:
+        raise ValueError(f"env_shade_bounce: transfer {tuple(transfer.shape)}, expected ({_l.ENV_COEFFS}, N); outputs {outputs!r}")
+    if not torch.is_tensor(bounce) or tuple(bounce.shape) != (3, _l.ENV_COEFFS, N):
+        raise ValueError(f"env_shade_bounce: bounce {tuple(getattr(bounce, 'shape', ()))}, expected (3, {_l.ENV_COEFFS}, {N})")
+    res = {}
+    for name in outputs:
+        if name not in ENV_BOUNCE_OUT:
+            raise ValueError(f"env_shade_bounce: unknown output {name!r} (one of {ENV_BOUNCE_OUT})")
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = _new(transfer, F, 3, N)
+        elif tuple(t.shape) != (F, 3, N) or not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f"env_shade_bounce: out[{name!r}] must be a contiguous float32 {(F, 3, N)} tensor")
+        res[name] = t
+    P = EnvShadeBounceParams()
+    P.N, P.n_hit, P.F = N, int(n_hit), F
+    keep = [_c(x) for x in (rgb if n_hit else None, transfer, envs, bg, bounce)]
+    P.rgb, P.transfer, P.envs, P.bg, P.bounce = (_p(x) for x in keep)
+    P.status, P.hit_slot = _p(status), _ip(hit_slot)
+    P.shading, P.image, P.indirect = _p(res.get("shading")), _p(res.get("image")), _p(res.get("indirect"))
+    _l.check(_l.load().oi_env_shade_bounce(ctypes.byref(P), _stream()), "oi_env_shade_bounce")
+    return res
+
+
+# ------------------------------------------------------------------------------------------
 # glossy environment lighting on the traced surface (include/oi_envgloss.h)
 # ------------------------------------------------------------------------------------------
 

@@ -14,7 +14,9 @@
                      under any number of environment lights (oi_amd.envlight.EnvLight), 256 per launch
                      (include/oi_envlight.h); with glossy_samples it also traces a reflection-lobe
                      visibility, and the capture is shaded under oi_amd.envlight.EnvMap objects with the learned Phong lobe
-                     (include/oi_envgloss.h)
+                     (include/oi_envgloss.h); with bounces=1 the transfer rays are followed to their
+                     nearest intersection and one diffuse interreflection bounce is folded into a per-channel transfer
+                     (include/oi_envbounce.h)
     render_surface_env  capture_transfer + shade in one call
 
 The loop runs on the host: oi_trace_begin, then per step the library's sdf-only MLP pass (unchanged) on the rays still in
@@ -267,8 +269,8 @@ class _Surface:
         self.kw, self.bias, self.field = kw, bias, field
         self.ro, self.rd, self.w2b, self.N, self.H = ro, rd, w2b, ro.shape[0], H
         self.res, self.n_hit, self.grad, self.rgb = res, res.hit_index.shape[0], grad, rgb
-        self.shadow_evals = self.ao_evals = self.transfer_evals = self.glossy_evals = 0
-        self.shadow = self.ao = self.transfer_state = self.glossy_state = None
+        self.shadow_evals = self.ao_evals = self.transfer_evals = self.glossy_evals = self.bounce_points = 0
+        self.shadow = self.ao = self.transfer_state = self.glossy_state = self.bounce_hits = None
 
     @classmethod
     def from_batch(cls, field, kw, bias, ro, rd, w2b, H, res, grad, rgb):
@@ -331,6 +333,34 @@ class _Surface:
         self.transfer_evals += self._secondary(st)
         self.transfer_state = st
         return ops.transfer_resolve(st.status, st.rays_d, self.res.hit_slot, self.N, self.n_hit, samples, self.w2b)
+
+    def transfer_bounce(self, samples, seed=0):
+        """transfer()'s (9, N) map and the bounce transfer (3, 9, N) of the same rays (include/oi_envbounce.h).  The rays are
+        transfer()'s, marched with the closest-hit step (oi_trace_step): the ones that end MISS are the same, the others are
+        refined to their nearest intersection; one full MLP pass there gives the normals and the albedo that
+        oi_bounce_resolve folds into a per-channel transfer.  samples >= 1."""
+        dev = self.ro.device
+        if self.n_hit == 0:
+            return torch.zeros(_l.ENV_COEFFS, self.N, device=dev), torch.zeros(3, _l.ENV_COEFFS, self.N, device=dev)
+        st = ops.TraceState(samples * self.n_hit, ref=self.ro)
+        ops.occlusion_ambient_begin(st, self.res.hit_points, self.grad, self.res.hit_index, self.n_hit, samples, self.bias,
+                                    TRANSFER_DISTANCE, seed)
+        n_evals, _ = _march(self.field, st, int(st.counts[0].item()), *self.kw, anyhit=False)
+        hit_index2, hit_points2, hit_slot2 = ops.trace_finish(st)     # rays in flight at the end -> LIMIT
+        n_hit2 = int(st.counts[-1].item())
+        grad2 = rgb2 = None
+        if n_hit2:
+            _, grad2, rgb2 = self.field.full(hit_points2[:n_hit2])
+        self.transfer_evals += n_evals
+        self.bounce_points += n_hit2
+        self.transfer_state = st
+        # what oi_bounce_resolve read: the secondary hits of the state (ray q = j * n_hit + i)
+        self.bounce_hits = dict(hit_index=hit_index2[:n_hit2], hit_points=hit_points2[:n_hit2], hit_slot=hit_slot2, grad=grad2,
+                                rgb=rgb2, n_hit=n_hit2)
+        direct = ops.transfer_resolve(st.status, st.rays_d, self.res.hit_slot, self.N, self.n_hit, samples, self.w2b)
+        bounce = ops.bounce_resolve(st.status, st.rays_d, hit_slot2, grad2, rgb2, n_hit2, self.res.hit_slot, self.N, self.n_hit,
+                                    samples, self.w2b)
+        return direct, bounce
 
     def lobe_visibility(self, samples, shininess, seed=0):
         """(N,) reflection-lobe visibility V_spec (include/oi_envgloss.h): the share of `samples` rays per visible point,
@@ -521,17 +551,33 @@ def _check_transfer(transfer_samples, seed, what):
     return int(v), int(seed)
 
 
+def _check_bounces(bounces, samples, glossy_samples, shininess, what):
+    """bounces: the integer 0 or 1 (no bool); a bounce follows the transfer rays, and the glossy shade does not read one."""
+    if not _is_count(bounces, 0, 1):
+        raise ValueError(f"{what}: bounces={bounces!r} (the integer 0 or 1: one diffuse interreflection bounce at the most)")
+    if bounces and samples == 0:
+        raise ValueError(f"{what}: bounces=1 with transfer_samples=0 (the bounce follows the transfer rays, and there are none)")
+    if bounces and (glossy_samples is not None or shininess is not None):
+        raise ValueError(f"{what}: bounces=1 with glossy_samples / shininess (the glossy shade has no bounce input yet)")
+    return int(bounces)
+
+
 class TransferCapture:
     """One traced view and its SH transfer map: everything shade() needs, none of which depends on the light.
     surface: the _Surface (primary trace, gradients and albedo at the hits); transfer (1, 9, H, W); maps: render_surface's
-    G-buffer maps (depth, position, normal_map, normal_object, albedo, mask).  A capture made with glossy_samples > 0 also
+    G-buffer maps (depth, position, normal_map, normal_object, albedo, mask).  A capture made with bounces=1 also holds bounce
+    (1, 3, 9, H, W), the per-channel transfer of one diffuse interreflection bounce (None otherwise; include/oi_envbounce.h).
+    A capture made with glossy_samples > 0 also
     holds spec_visibility (1, 1, H, W), the reflection-lobe visibility, and the shininess it was traced for."""
 
-    def __init__(self, surface, transfer, maps, samples, glossy_samples=None, shininess=None, spec_vis=None, specular=None):
+    def __init__(self, surface, transfer, maps, samples, glossy_samples=None, shininess=None, spec_vis=None, specular=None,
+                 bounce=None):
         self.surface, self.samples, self.maps = surface, samples, maps
         self._transfer = transfer                       # (9, N), planar: what oi_env_shade reads
         self.H = self.W = surface.H
         self.transfer = transfer.view(1, _l.ENV_COEFFS, self.H, self.W)
+        self._bounce = bounce                           # (3, 9, N), planar, or None: what oi_env_shade_bounce reads
+        self.bounce = None if bounce is None else bounce.view(1, 3, _l.ENV_COEFFS, self.H, self.W)
         # glossy_samples: None = never mentioned (a glossy shade is refused), 0 = no lobe trace on purpose (V_spec = 1)
         self.glossy_samples, self.shininess, self.specular = glossy_samples, shininess, specular
         self._spec_vis = spec_vis                       # (N,) or None
@@ -540,7 +586,8 @@ class TransferCapture:
     def shade(self, envs, bg=None, specular=None):
         """The view under each of `envs` (any number: launches of ENV_MAX_ENVS).
         EnvLight objects: -> {"image": (F, 3, H, W) = max(shading, 0) albedo on the mask, bg off it; "shading": (F, 3, H, W),
-        not clamped}.
+        not clamped}.  On a capture made with bounces=1 (oi_env_shade_bounce) shading = direct + indirect, and "indirect":
+        (F, 3, H, W), the part that reached the point by way of the object itself, is returned too.
         EnvMap objects (every element; a mixed list is refused): the glossy path, image = max(shading, 0) albedo + specular
         and "specular": (F, 3, H, W) = k_s V_spec G_s(reflected view vector).  k_s = `specular`: None takes the generator's
         learned specular colour, a scalar or an RGB triple overrides it.  The maps' shininess must be the capture's.  A capture
@@ -558,11 +605,15 @@ class TransferCapture:
                 raise ValueError("shade: specular= needs EnvMap environments (an EnvLight has no glossy half)")
             ev = stack_envs(seq, dev)
             F, N = ev.shape[0], s.N
-            out = {k: ops._new(s.ro, F, 3, N) for k in ops.ENV_SHADE_OUT}
+            out = {k: ops._new(s.ro, F, 3, N) for k in (ops.ENV_SHADE_OUT if self._bounce is None else ops.ENV_BOUNCE_OUT)}
             for a in range(0, F, ENV_MAX_ENVS):
                 b = min(F, a + ENV_MAX_ENVS)
-                ops.env_shade(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, ev[a:b], bgv,
-                              out={k: v[a:b] for k, v in out.items()})
+                if self._bounce is None:
+                    ops.env_shade(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, ev[a:b], bgv,
+                                  out={k: v[a:b] for k, v in out.items()})
+                else:
+                    ops.env_shade_bounce(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, self._bounce, ev[a:b], bgv,
+                                         out={k: v[a:b] for k, v in out.items()})
             return {k: v.view(F, 3, self.H, self.W) for k, v in out.items()}
         if self.glossy_samples is None:
             raise ValueError("shade: this capture has no reflection-lobe trace; capture_transfer(glossy_samples=S) traces one, "
@@ -586,6 +637,7 @@ class TransferCapture:
         st = self.surface.stats()
         st["transfer_evals"] = self.surface.transfer_evals
         st["glossy_evals"] = self.surface.glossy_evals
+        st["bounce_points"] = self.surface.bounce_points
         return st
 
 
@@ -611,7 +663,7 @@ def _check_glossy(gen, glossy_samples, shininess, what):
 
 @torch.no_grad()
 def capture_transfer(gen, z, b2w, transfer_samples=64, seed=0, bias=DEFAULT_BIAS, glossy_samples=None, shininess=None,
-                     **trace_kw):
+                     bounces=0, **trace_kw):
     """One view of `gen` (latent z, pose b2w: render_surface's) prepared for environment lighting: the primary trace, the full
     MLP pass at its hits, and `transfer_samples` (0 .. 256) cosine-weighted rays per visible point -- render_surface's ambient-
     occlusion rays for the same seed, followed to the exit of the unit sphere -- resolved into a 9-coefficient transfer vector
@@ -621,34 +673,43 @@ def capture_transfer(gen, z, b2w, transfer_samples=64, seed=0, bias=DEFAULT_BIAS
     learned value.  glossy_samples = 0 prepares a glossy capture without that trace (V_spec = 1: no horizon, no occluder);
     it has to be given: a shininess without glossy_samples is refused.
     With both left at None the launches and outputs are those of a call without them, and the capture shades EnvLights only.
+    bounces = 1 (the integer; with transfer_samples >= 1, not with the glossy keywords) follows the transfer rays to their
+    nearest intersection with the object instead of to their first occluder, evaluates the normal and the albedo there in one
+    more full MLP pass and folds ONE DIFFUSE interreflection bounce into a per-channel transfer, TransferCapture.bounce
+    (include/oi_envbounce.h has the estimator and its approximations); the direct transfer is bit for bit that of bounces = 0,
+    whose launches and outputs are those of a call without the keyword.
     trace_kw: tol, omega, max_steps, readback of sphere_trace.  -> TransferCapture."""
     samples, seed = _check_transfer(transfer_samples, seed, "capture_transfer")
+    bounces = _check_bounces(bounces, samples, glossy_samples, shininess, "capture_transfer")
     g_samples, shin, spec = _check_glossy(gen, glossy_samples, shininess, "capture_transfer")
     dev = gen.it.device
     s = _Surface(gen, z.to(dev).reshape(1, -1), b2w, bias, trace_kw)
-    transfer = s.transfer(samples, seed)
+    transfer, bounce = s.transfer_bounce(samples, seed) if bounces else (s.transfer(samples, seed), None)
     g = s.shade(None, None, outputs=tuple(ops.SURFACE_OUT))
     maps = {_MAP_NAMES[k]: v for k, v in _maps(g, s.H, s.H).items()}
     vis = s.lobe_visibility(g_samples, shin, seed) if g_samples else None
-    return TransferCapture(s, transfer, maps, samples, g_samples, shin, vis, spec)
+    return TransferCapture(s, transfer, maps, samples, g_samples, shin, vis, spec, bounce)
 
 
 @torch.no_grad()
 def render_surface_env(gen, z, b2w, envs, transfer_samples=64, seed=0, bg=None, bias=DEFAULT_BIAS, glossy_samples=None,
-                       shininess=None, specular=None, **trace_kw):
+                       shininess=None, specular=None, bounces=0, **trace_kw):
     """capture_transfer + shade: one view of `gen` under the environment lights `envs` (oi_amd.envlight.EnvLight objects, or
     EnvMap objects with glossy_samples given: capture_transfer's and shade's keywords pass through).
     -> render_surface's G-buffer keys (depth, position, normal_map, normal_object, albedo, mask), image (F, 3, H, W), shading
     (F, 3, H, W) (not clamped), transfer (1, 9, H, W), stats (with transfer_evals), trace (the primary TraceResult) and
     transfer_trace (ops.TraceState of the transfer_samples x n_hit rays, ray j * n_hit + i, or None); on the glossy path also
-    specular (F, 3, H, W), spec_visibility (1, 1, H, W) or None and glossy_trace (the state of the lobe rays, or None)."""
-    cap = capture_transfer(gen, z, b2w, transfer_samples, seed, bias, glossy_samples, shininess, **trace_kw)
+    specular (F, 3, H, W), spec_visibility (1, 1, H, W) or None and glossy_trace (the state of the lobe rays, or None); with
+    bounces=1 also indirect (F, 3, H, W) and bounce (1, 3, 9, H, W)."""
+    cap = capture_transfer(gen, z, b2w, transfer_samples, seed, bias, glossy_samples, shininess, bounces, **trace_kw)
     res = dict(cap.maps)
     res.update(cap.shade(envs, bg, specular))
     if cap.glossy_samples is not None:
         res["spec_visibility"] = cap.spec_visibility
         res["glossy_trace"] = cap.surface.glossy_state
     res["transfer"] = cap.transfer
+    if cap.bounce is not None:
+        res["bounce"] = cap.bounce
     res["transfer_trace"] = cap.surface.transfer_state
     res["stats"] = cap.stats()
     res["trace"] = cap.surface.res

@@ -17,7 +17,14 @@ With --glossy only the glossy path is timed:
                         kernels, the map already on the device), and EnvMap.from_equirect (projection and upload included)
   capture_ms            capture_transfer(transfer_samples=64, glossy_samples=G) at G of --glossy-samples; glossy_evals: the sdf
                         evaluations of the reflection-lobe trace
-  shade_ms              TransferCapture.shade under F rotations of one EnvMap at each F of --envs: per launch and per frame"""
+  shade_ms              TransferCapture.shade under F rotations of one EnvMap at each F of --envs: per launch and per frame
+
+With --bounce only the interreflection bounce is timed, each figure beside its counterpart without:
+
+  capture_ms            capture_transfer at each S of --samples with bounces=0 and with bounces=1 (the closest-hit march of the
+                        transfer rays, the full MLP pass at their hits, oi_bounce_resolve); bounce_points: those hits
+  shade_ms              TransferCapture.shade at each F of --envs on a plain capture (oi_env_shade) and on a bounce capture
+                        (oi_env_shade_bounce) at the last S: per launch and per frame"""
 import argparse
 import json
 import os
@@ -46,6 +53,7 @@ ap.add_argument("--glossy", action="store_true")
 ap.add_argument("--glossy-size", default="64x128")
 ap.add_argument("--glossy-samples", default="16,64")
 ap.add_argument("--shininess", type=float, default=10.0)
+ap.add_argument("--bounce", action="store_true")
 args = ap.parse_args()
 
 
@@ -99,6 +107,30 @@ if args.glossy:
             envs = [emap.rotated(R) for R in inference.env_walk_rotations(F)]
             ms = median_ms(lambda: cap.shade(envs, specular=0.3))
             out["shade"][str(F)] = {"shade_ms": ms, "per_frame_ms": ms / F}
+    print(json.dumps(out))
+    sys.exit(0)
+if args.bounce:
+    out.update(bounce=True)
+    del out["walk"]
+    with torch.no_grad():
+        caps = {}
+        for S in samples:
+            row = {}
+            for nb in (0, 1):
+                caps[nb] = trace.capture_transfer(gen, z, b2w, transfer_samples=S, bounces=nb)
+                st = caps[nb].stats()
+                row["bounces=%d" % nb] = {
+                    "capture_ms": median_ms(lambda: trace.capture_transfer(gen, z, b2w, transfer_samples=S, bounces=nb)),
+                    "hits": st["hit"], "rays": S * st["hit"], "transfer_evals": st["transfer_evals"],
+                    "bounce_points": st["bounce_points"]}
+            out["capture"][str(S)] = row
+        for F in n_envs:
+            envs = [env.rotated(R) for R in inference.env_walk_rotations(F)]
+            row = {}
+            for nb in (0, 1):
+                ms = median_ms(lambda: caps[nb].shade(envs))
+                row["bounces=%d" % nb] = {"shade_ms": ms, "per_frame_ms": ms / F}
+            out["shade"][str(F)] = row
     print(json.dumps(out))
     sys.exit(0)
 with torch.no_grad():

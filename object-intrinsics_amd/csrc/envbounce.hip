@@ -2,14 +2,13 @@
 //   bounce_resolve        the final states of a closest-hit trace of the transfer rays, the normals and albedo at their hits
 //                         -> the per-channel bounce transfer [3][9][N], one thread per pixel, 27 sums in registers
 //   env_shade_bounce      (transfer + bounce[ch]) . coefficients for F environments, one thread per pixel, its 36 values read once
+//                         (env_shade_common.h's pixel with the BOUNCE term)
 // No atomics at all, no LDS, no scratch; every sum has one fixed order.
-#include "trace_common.h"
+#include "env_shade_common.h"
 #include "../../include/oi_envbounce.h"
 
 namespace {
 
-constexpr int NC = OI_ENV_COEFFS;
-constexpr int ESB_THREADS = 64;  // oi_env_shade_bounce: one wave per workgroup, as env_shade_kernel
 static_assert(OI_BOUNCE_FLOATS == 3 * NC, "[3][9] per pixel");
 
 __global__ void __launch_bounds__(TR_THREADS) bounce_resolve_kernel(const uint8_t* __restrict__ status,
@@ -32,17 +31,10 @@ __global__ void __launch_bounds__(TR_THREADS) bounce_resolve_kernel(const uint8_
       if (status[q] != OI_TRACE_HIT) continue;
       const long long k = hit_slot2[q];
       if (k < 0 || k >= n_hit2) continue;  // (a finished state lists every HIT; nothing is read outside grad2 / rgb2 whatever it holds)
-      const float gx = grad2[k * 3 + 0], gy = grad2[k * 3 + 1], gz = grad2[k * 3 + 2];
-      const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);  // transfer_normal_kernel's normal
-      const float nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
+      float nx, ny, nz, t[NC];
+      unit_normal(grad2, k, nx, ny, nz);
       if (!(nx * rays_d[q * 3 + 0] + ny * rays_d[q * 3 + 1] + nz * rays_d[q * 3 + 2] < 0.f)) continue;  // a back face
-      float x, y, z, t[NC];
-      to_world(w2b, nx, ny, nz, x, y, z);
-      sh9(x, y, z, t);
-#pragma unroll
-      for (int c = 1; c < 4; ++c) t[c] *= 2.0f / 3.0f;
-#pragma unroll
-      for (int c = 4; c < NC; ++c) t[c] *= 0.25f;
+      normal_transfer(w2b, nx, ny, nz, t);  // transfer_normal_kernel's closed form at the secondary hit
       const float r0 = rgb2[k * 3 + 0], r1 = rgb2[k * 3 + 1], r2 = rgb2[k * 3 + 2];
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
@@ -61,38 +53,8 @@ __global__ void __launch_bounds__(TR_THREADS) bounce_resolve_kernel(const uint8_
     for (int c = 0; c < NC; ++c) bounce[((long long)ch * NC + c) * N + i] = acc[ch][c];
 }
 
-__global__ void __launch_bounds__(ESB_THREADS) env_shade_bounce_kernel(const oi_env_shade_bounce_params p) {
-  const long long i = (long long)blockIdx.x * ESB_THREADS + threadIdx.x;
-  if (i >= p.N) return;
-  const bool hit = p.status[i] == OI_TRACE_HIT;
-  float t[NC], b[3][NC], alb[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < NC; ++c) t[c] = p.transfer[c * p.N + i];
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) b[ch][c] = p.bounce[((long long)ch * NC + c) * p.N + i];
-  if (hit && p.image) {
-    const long long k = p.hit_slot[i];
-    alb[0] = p.rgb[k * 3 + 0], alb[1] = p.rgb[k * 3 + 1], alb[2] = p.rgb[k * 3 + 2];
-  }
-  const float b3[3] = {p.bg ? p.bg[0] : 0.f, p.bg ? p.bg[1] : 0.f, p.bg ? p.bg[2] : 0.f};
-  for (int f = 0; f < p.F; ++f) {
-    const float* __restrict__ env = p.envs + (long long)f * OI_ENV_FLOATS;  // the same for every lane
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      float d = 0.f, in = 0.f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) d = __fmaf_rn(t[c], env[c * 3 + ch], d);  // env_shade_kernel's chain
-#pragma unroll
-      for (int c = 0; c < NC; ++c) in = __fmaf_rn(b[ch][c], env[c * 3 + ch], in);
-      const float s = __fadd_rn(d, in);
-      const long long o = ((long long)f * 3 + ch) * p.N + i;
-      if (p.shading) p.shading[o] = hit ? s : 0.f;
-      if (p.indirect) p.indirect[o] = hit ? in : 0.f;
-      if (p.image) p.image[o] = hit ? __fmul_rn(fmaxf(s, 0.f), alb[ch]) : b3[ch];
-    }
-  }
+__global__ void __launch_bounds__(ES_THREADS) env_shade_bounce_kernel(const oi_env_shade_bounce_params p) {
+  env_shade_pixel<EnvTerm::BOUNCE>(p);
 }
 
 }  // namespace
@@ -114,17 +76,13 @@ int oi_bounce_resolve(const uint8_t* status, const float* rays_d, const int* hit
 }
 
 int oi_env_shade_bounce(const oi_env_shade_bounce_params* p, oi_stream_t stream) {
-  OI_REQUIRE(p != nullptr, "oi_env_shade_bounce: null params");
-  OI_REQUIRE(p->N >= 1 && p->N < (1ll << 31) && p->n_hit >= 0 && p->n_hit <= p->N, "oi_env_shade_bounce: N=%lld, n_hit=%lld", p->N,
-             p->n_hit);
-  OI_REQUIRE(p->F >= 1 && p->F <= OI_ENV_MAX_ENVS, "oi_env_shade_bounce: F=%d (1 .. %d environments)", p->F, OI_ENV_MAX_ENVS);
-  OI_REQUIRE(p->status && p->hit_slot && p->transfer && p->envs, "oi_env_shade_bounce: null input pointer");
-  OI_REQUIRE(p->bounce != nullptr, "oi_env_shade_bounce: null bounce (oi_env_shade shades a capture without one)");
-  OI_REQUIRE(p->shading || p->image || p->indirect, "oi_env_shade_bounce: no output (shading, image and indirect are all null)");
-  OI_REQUIRE(p->rgb || p->n_hit == 0 || !p->image, "oi_env_shade_bounce: null rgb with n_hit=%lld and an image", p->n_hit);
-  hipLaunchKernelGGL(env_shade_bounce_kernel, dim3((unsigned)((p->N + ESB_THREADS - 1) / ESB_THREADS)), dim3(ESB_THREADS), 0,
+  const char* what = "oi_env_shade_bounce";
+  int rc = check_env_shade(what, p, p && (p->shading || p->image || p->indirect), "shading, image and indirect are all null");
+  if (rc != OI_OK) return rc;
+  OI_REQUIRE(p->bounce != nullptr, "%s: null bounce (oi_env_shade shades a capture without one)", what);
+  hipLaunchKernelGGL(env_shade_bounce_kernel, dim3((unsigned)((p->N + ES_THREADS - 1) / ES_THREADS)), dim3(ES_THREADS), 0,
                      oi::as_stream(stream), *p);
-  return oi::check_launch("oi_env_shade_bounce");
+  return oi::check_launch(what);
 }
 
 }  // extern "C"

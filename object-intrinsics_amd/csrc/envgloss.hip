@@ -4,25 +4,21 @@
 //   occlusion_lobe_begin  S rays per visible point distributed as cos^s about the reflected view vector, compacted like
 //                         occlusion.hip's begin kernels; the march and the resolve are occlusion.hip's
 //   env_shade_glossy      envlight.hip's shading plus k_s V_spec G_s(R_f^T r_world): rotated bilinear lookups, F per thread
+//                         (env_shade_common.h's pixel with the GLOSSY term)
 // No float atomics, no scratch; every sum has one fixed order.  The only atomics are the compaction's integer counters.
-#include "trace_common.h"
-#include "../../include/oi_envgloss.h"
+#include "env_shade_common.h"
 
 namespace {
 
-constexpr int NC = OI_ENV_COEFFS;
 constexpr int PF_THREADS = 256;            // oi_env_prefilter: output texels per workgroup, one per thread
 constexpr int PF_CHUNK = OI_ENVGLOSS_CHUNK;  // input pixels per workgroup
 constexpr int PF_BATCH = PF_THREADS;       // records in LDS at a time: each thread forms one
 constexpr int PF_INNER = 32;               // terms a thread sums in one chain
 constexpr int PF_FINAL = 32;               // stage 2: chains of 32 partials, nested four times (32^4 = 2^20 chunks)
 constexpr long long PF_MAX_WORKGROUPS = 1ll << 23;  // the header's limit on E * chunks * tiles
-constexpr int GS_THREADS = 64;             // oi_env_shade_glossy: envlight.hip's one wave per workgroup
 static_assert(PF_CHUNK % PF_BATCH == 0 && PF_BATCH % PF_INNER == 0, "whole batches, whole chains");
 static_assert(PF_INNER + PF_BATCH / PF_INNER + PF_CHUNK / PF_BATCH + 4 * PF_FINAL == 176, "the header states the additions");
 static_assert((long long)PF_FINAL * PF_FINAL * PF_FINAL * PF_FINAL * PF_CHUNK >= (1ll << 31), "stage 2 covers E * He * We < 2^31");
-
-constexpr float kPiF = 3.14159265358979323846f;
 
 // the unit direction of pixel (r, c) of an H x W equirectangular map and sin(theta): envlight.hip's expressions
 __device__ __forceinline__ void texel_dir(long long r, long long c, int H, int W, float& x, float& y, float& z, float& st) {
@@ -112,18 +108,6 @@ __global__ void __launch_bounds__(PF_THREADS) env_prefilter_final_kernel(const f
   glossy[i] = s3;
 }
 
-// n = g / max(|g|, 1e-6), v = (eye - point) / max(|.|, 1e-6) (surface_shade_at's), r = 2 ((n . v) n) - v
-__device__ __forceinline__ void reflect_view(const float* __restrict__ grad, const float* __restrict__ hit_points, long long k,
-                                             const float* __restrict__ eye, float* n, float* r) {
-  const float gx = grad[k * 3 + 0], gy = grad[k * 3 + 1], gz = grad[k * 3 + 2];
-  const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
-  n[0] = gx / gnc, n[1] = gy / gnc, n[2] = gz / gnc;
-  float vx = eye[0] - hit_points[k * 3 + 0], vy = eye[1] - hit_points[k * 3 + 1], vz = eye[2] - hit_points[k * 3 + 2];
-  normalize3(vx, vy, vz, 1e-6f);
-  const float ndv = n[0] * vx + n[1] * vy + n[2] * vz;
-  r[0] = 2.0f * (ndv * n[0]) - vx, r[1] = 2.0f * (ndv * n[1]) - vy, r[2] = 2.0f * (ndv * n[2]) - vz;
-}
-
 // occlusion.hip's begin kernel with the lobe about r in place of the hemisphere about n
 __global__ void __launch_bounds__(TR_THREADS) occlusion_lobe_begin_kernel(const oi_trace_state s, const float* __restrict__ rays_o,
                                                                           const float* __restrict__ hit_points,
@@ -166,92 +150,9 @@ __global__ void __launch_bounds__(TR_THREADS) occlusion_lobe_begin_kernel(const 
   }
 }
 
-// what travels in the kernel's arguments: the checked map of every environment
-struct MapIndex {
-  uint8_t v[OI_ENV_MAX_ENVS];
-};
-static_assert(OI_ENV_MAX_ENVS <= 256, "a map index fits a byte");
-
-struct GlossArgs {
-  const float* rays_o;
-  const float* hit_points;
-  const float* grad;
-  const float* w2b;
-  const float* spec_vis;
-  const float* glossy;
-  const float* rot;
-  const float* k_s;
-  float* specular;
-  int Hp, Wp;
-};
-
-__device__ __forceinline__ float lerp_(float a, float b, float f) { return __fmaf_rn(f, b - a, a); }
-
-__global__ void __launch_bounds__(GS_THREADS) env_shade_glossy_kernel(const oi_env_shade_params p, const GlossArgs g,
+__global__ void __launch_bounds__(ES_THREADS) env_shade_glossy_kernel(const oi_env_shade_params p, const GlossArgs g,
                                                                       const MapIndex mi) {
-  const long long i = (long long)blockIdx.x * GS_THREADS + threadIdx.x;
-  if (i >= p.N) return;
-  const bool hit = p.status[i] == OI_TRACE_HIT;
-  float t[NC], alb[3] = {0.f, 0.f, 0.f}, rw[3] = {0.f, 0.f, 0.f}, kv[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < NC; ++c) t[c] = p.transfer[c * p.N + i];
-  if (hit) {
-    const long long k = p.hit_slot[i];
-    if (p.image) alb[0] = p.rgb[k * 3 + 0], alb[1] = p.rgb[k * 3 + 1], alb[2] = p.rgb[k * 3 + 2];
-    float n[3], r[3];
-    reflect_view(g.grad, g.hit_points, k, g.rays_o + i * 3, n, r);
-    const float* Wb = g.w2b;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) rw[a] = Wb[0 + a] * r[0] + Wb[4 + a] * r[1] + Wb[8 + a] * r[2];  // w2b[:3,:3]^T r
-    const float vis = g.spec_vis ? g.spec_vis[i] : 1.0f;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) kv[ch] = __fmul_rn(g.k_s[ch], vis);
-  }
-  const float b3[3] = {p.bg ? p.bg[0] : 0.f, p.bg ? p.bg[1] : 0.f, p.bg ? p.bg[2] : 0.f};
-  const int Hp = g.Hp, Wp = g.Wp;
-  const long long O = (long long)Hp * Wp;
-  for (int f = 0; f < p.F; ++f) {
-    const float* __restrict__ env = p.envs + (long long)f * OI_ENV_FLOATS;  // the same for every lane
-    float spec[3] = {0.f, 0.f, 0.f};
-    if (hit) {
-      const float* __restrict__ R = g.rot + (long long)f * 9;
-      const float dx = R[0] * rw[0] + R[3] * rw[1] + R[6] * rw[2];  // R_f^T r_w
-      const float dy = R[1] * rw[0] + R[4] * rw[1] + R[7] * rw[2];
-      const float dz = R[2] * rw[0] + R[5] * rw[1] + R[8] * rw[2];
-      const float theta = acosf(fminf(fmaxf(dz, -1.0f), 1.0f));
-      float phi = atan2f(dy, dx);
-      if (phi < 0.f) phi += 2.0f * kPiF;
-      const float u = theta / kPiF * (float)Hp - 0.5f, v = phi / (2.0f * kPiF) * (float)Wp - 0.5f;
-      const float fi = floorf(u), fj = floorf(v);
-      const float fu = u - fi, fv = v - fj;
-      // (a NaN direction lands on row 0, column 0: min / max drop it, and the remainder of 0 is 0)
-      const int i0 = (int)fminf(fmaxf(fi, 0.f), (float)(Hp - 1)), i1 = (int)fminf(fmaxf(fi + 1.0f, 0.f), (float)(Hp - 1));
-      int j0 = (int)fminf(fmaxf(fj, -1.0f), (float)Wp) % Wp;
-      if (j0 < 0) j0 += Wp;
-      const int j1 = j0 + 1 == Wp ? 0 : j0 + 1;
-      const float* __restrict__ map = g.glossy + (long long)mi.v[f] * 3 * O;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float* __restrict__ m = map + ch * O;
-        const float top = lerp_(m[(long long)i0 * Wp + j0], m[(long long)i0 * Wp + j1], fv);
-        const float bot = lerp_(m[(long long)i1 * Wp + j0], m[(long long)i1 * Wp + j1], fv);
-        spec[ch] = __fmul_rn(kv[ch], lerp_(top, bot, fu));
-      }
-    }
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) s = __fmaf_rn(t[c], env[c * 3 + ch], s);
-      const long long o = ((long long)f * 3 + ch) * p.N + i;
-      if (p.shading) p.shading[o] = hit ? s : 0.f;
-      if (g.specular) g.specular[o] = spec[ch];
-      if (p.image) {
-        const float base = __fmul_rn(fmaxf(s, 0.f), alb[ch]);  // oi_env_shade's pixel
-        p.image[o] = hit ? (spec[ch] != 0.f ? __fadd_rn(base, spec[ch]) : base) : b3[ch];
-      }
-    }
-  }
+  env_shade_pixel<EnvTerm::GLOSSY>(p, g, mi);
 }
 
 long long prefilter_chunks(int He, int We) { return ((long long)He * We + PF_CHUNK - 1) / PF_CHUNK; }
@@ -320,23 +221,19 @@ int oi_env_shade_glossy(const oi_env_shade_params* p, const float* rays_o, const
                         const float* w2b, const float* spec_vis, const float* glossy, int M, int Hp, int Wp,
                         const int* map_index, const float* rot, const float* k_s, float* specular, oi_stream_t stream) {
   const char* what = "oi_env_shade_glossy";
-  OI_REQUIRE(p != nullptr, "%s: null params", what);
-  OI_REQUIRE(p->N >= 1 && p->N < (1ll << 31) && p->n_hit >= 0 && p->n_hit <= p->N, "%s: N=%lld, n_hit=%lld", what, p->N, p->n_hit);
-  OI_REQUIRE(p->F >= 1 && p->F <= OI_ENV_MAX_ENVS, "%s: F=%d (1 .. %d environments)", what, p->F, OI_ENV_MAX_ENVS);
+  int rc = check_env_shade(what, p, p && (p->shading || p->image || specular), "shading, image and specular are all null");
+  if (rc != OI_OK) return rc;
   OI_REQUIRE(M >= 1 && M <= OI_ENV_MAX_ENVS && Hp >= 1 && Wp >= 1 && (long long)M * 3 * Hp * Wp < (1ll << 31),
              "%s: M=%d, Hp=%d, Wp=%d (1 <= M <= %d, sizes >= 1, M * 3 * Hp * Wp < 2^31)", what, M, Hp, Wp, OI_ENV_MAX_ENVS);
-  OI_REQUIRE(p->status && p->hit_slot && p->transfer && p->envs, "%s: null input pointer", what);
   OI_REQUIRE(rays_o && w2b && glossy && map_index && rot && k_s, "%s: null glossy input pointer", what);
   OI_REQUIRE(p->n_hit == 0 || (hit_points && grad), "%s: null hit arrays with n_hit=%lld", what, p->n_hit);
-  OI_REQUIRE(p->shading || p->image || specular, "%s: no output (shading, image and specular are all null)", what);
-  OI_REQUIRE(p->rgb || p->n_hit == 0 || !p->image, "%s: null rgb with n_hit=%lld and an image", what, p->n_hit);
   MapIndex mi = {};
   for (int f = 0; f < p->F; ++f) {
     OI_REQUIRE(map_index[f] >= 0 && map_index[f] < M, "%s: map_index[%d]=%d (0 <= map_index < M=%d)", what, f, map_index[f], M);
     mi.v[f] = (uint8_t)map_index[f];
   }
   const GlossArgs g = {rays_o, hit_points, grad, w2b, spec_vis, glossy, rot, k_s, specular, Hp, Wp};
-  hipLaunchKernelGGL(env_shade_glossy_kernel, dim3((unsigned)((p->N + GS_THREADS - 1) / GS_THREADS)), dim3(GS_THREADS), 0,
+  hipLaunchKernelGGL(env_shade_glossy_kernel, dim3((unsigned)((p->N + ES_THREADS - 1) / ES_THREADS)), dim3(ES_THREADS), 0,
                      oi::as_stream(stream), *p, g, mi);
   return oi::check_launch(what);
 }

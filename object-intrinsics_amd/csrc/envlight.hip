@@ -3,18 +3,16 @@
 //   transfer_resolve      the final states and directions of an ambient-occlusion trace -> the transfer map, one thread per pixel
 //   transfer_normal       the unshadowed closed form
 //   env_shade             transfer . coefficients for F environments, one thread per pixel, its transfer read once
+//                         (env_shade_common.h's pixel without a further term)
 // No atomics at all, no scratch; every sum has one fixed order.
-#include "trace_common.h"
-#include "../../include/oi_envlight.h"
+#include "env_shade_common.h"
 
 namespace {
 
-constexpr int NC = OI_ENV_COEFFS;
 constexpr int EP_THREADS = 256;              // oi_env_project's workgroup
 constexpr int EP_PER_THREAD = 32;            // pixels a thread sums in sequence
 constexpr int EP_CHUNK = EP_THREADS * EP_PER_THREAD;  // pixels per workgroup: the 8192 of the header
 constexpr int EP_INNER = 32;                 // the final pass: chains of 32 partials, nested twice (32 x 32 x 256 = 2^18 partials)
-constexpr int ES_THREADS = 64;               // oi_env_shade: one wave per workgroup, so a 128 x 128 view still covers every CU
 static_assert(EP_CHUNK == 8192, "the header states the chunk");
 static_assert((long long)EP_INNER * EP_INNER * EP_THREADS * EP_CHUNK >= (1ll << 31), "the final pass covers E * He * We < 2^31");
 
@@ -133,44 +131,16 @@ __global__ void __launch_bounds__(TR_THREADS) transfer_normal_kernel(const float
 #pragma unroll
   for (int c = 0; c < NC; ++c) t[c] = 0.f;
   if (k >= 0) {
-    const float gx = grad[k * 3 + 0], gy = grad[k * 3 + 1], gz = grad[k * 3 + 2];
-    const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);  // surface_shade_pixel's normal
-    float x, y, z;
-    to_world(w2b, gx / gnc, gy / gnc, gz / gnc, x, y, z);
-    sh9(x, y, z, t);
-#pragma unroll
-    for (int c = 1; c < 4; ++c) t[c] *= 2.0f / 3.0f;
-#pragma unroll
-    for (int c = 4; c < NC; ++c) t[c] *= 0.25f;
+    float nx, ny, nz;
+    unit_normal(grad, k, nx, ny, nz);
+    normal_transfer(w2b, nx, ny, nz, t);
   }
 #pragma unroll
   for (int c = 0; c < NC; ++c) transfer[c * N + i] = t[c];
 }
 
 __global__ void __launch_bounds__(ES_THREADS) env_shade_kernel(const oi_env_shade_params p) {
-  const long long i = (long long)blockIdx.x * ES_THREADS + threadIdx.x;
-  if (i >= p.N) return;
-  const bool hit = p.status[i] == OI_TRACE_HIT;
-  float t[NC], alb[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < NC; ++c) t[c] = p.transfer[c * p.N + i];
-  if (hit && p.image) {
-    const long long k = p.hit_slot[i];
-    alb[0] = p.rgb[k * 3 + 0], alb[1] = p.rgb[k * 3 + 1], alb[2] = p.rgb[k * 3 + 2];
-  }
-  const float b3[3] = {p.bg ? p.bg[0] : 0.f, p.bg ? p.bg[1] : 0.f, p.bg ? p.bg[2] : 0.f};
-  for (int f = 0; f < p.F; ++f) {
-    const float* __restrict__ env = p.envs + (long long)f * OI_ENV_FLOATS;  // the same for every lane
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) s = __fmaf_rn(t[c], env[c * 3 + ch], s);
-      const long long o = ((long long)f * 3 + ch) * p.N + i;
-      if (p.shading) p.shading[o] = hit ? s : 0.f;
-      if (p.image) p.image[o] = hit ? __fmul_rn(fmaxf(s, 0.f), alb[ch]) : b3[ch];
-    }
-  }
+  env_shade_pixel<EnvTerm::NONE>(p);
 }
 
 long long project_blocks(int He, int We) { return ((long long)He * We + EP_CHUNK - 1) / EP_CHUNK; }
@@ -222,13 +192,8 @@ int oi_transfer_normal(const float* grad, const int* hit_slot, long long N, long
 }
 
 int oi_env_shade(const oi_env_shade_params* p, oi_stream_t stream) {
-  OI_REQUIRE(p != nullptr, "oi_env_shade: null params");
-  OI_REQUIRE(p->N >= 1 && p->N < (1ll << 31) && p->n_hit >= 0 && p->n_hit <= p->N, "oi_env_shade: N=%lld, n_hit=%lld", p->N,
-             p->n_hit);
-  OI_REQUIRE(p->F >= 1 && p->F <= OI_ENV_MAX_ENVS, "oi_env_shade: F=%d (1 .. %d environments)", p->F, OI_ENV_MAX_ENVS);
-  OI_REQUIRE(p->status && p->hit_slot && p->transfer && p->envs, "oi_env_shade: null input pointer");
-  OI_REQUIRE(p->shading || p->image, "oi_env_shade: no output (shading and image are both null)");
-  OI_REQUIRE(p->rgb || p->n_hit == 0 || !p->image, "oi_env_shade: null rgb with n_hit=%lld and an image", p->n_hit);
+  int rc = check_env_shade("oi_env_shade", p, p && (p->shading || p->image), "shading and image are both null");
+  if (rc != OI_OK) return rc;
   hipLaunchKernelGGL(env_shade_kernel, dim3((unsigned)((p->N + ES_THREADS - 1) / ES_THREADS)), dim3(ES_THREADS), 0,
                      oi::as_stream(stream), *p);
   return oi::check_launch("oi_env_shade");

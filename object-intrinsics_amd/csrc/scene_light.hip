@@ -200,15 +200,9 @@ __global__ void __launch_bounds__(TR_THREADS) scene_transfer_normal_kernel(const
   for (int c = 0; c < NC; ++c) t[c] = 0.f;
   if (e >= 0) {
     const long long k = (long long)e * n_pad + vis_slot[(long long)e * N + owner_ray[q]];
-    const float gx = grad[k * 3 + 0], gy = grad[k * 3 + 1], gz = grad[k * 3 + 2];
-    const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);  // surface_shade_at's normal
-    float x, y, z;
-    to_world(w2b + (long long)e * 16, gx / gnc, gy / gnc, gz / gnc, x, y, z);
-    sh9(x, y, z, t);
-#pragma unroll
-    for (int c = 1; c < 4; ++c) t[c] *= 2.0f / 3.0f;
-#pragma unroll
-    for (int c = 4; c < NC; ++c) t[c] *= 0.25f;
+    float nx, ny, nz;
+    unit_normal(grad, k, nx, ny, nz);
+    normal_transfer(w2b + (long long)e * 16, nx, ny, nz, t);
   }
 #pragma unroll
   for (int c = 0; c < NC; ++c) transfer[c * M + q] = t[c];

@@ -2,7 +2,8 @@
 // (include/oi_trace.h, include/oi_occlusion.h, include/oi_trace_batch.h, include/oi_envlight.h, include/oi_scene.h,
 // include/oi_scene_light.h, include/oi_envbounce.h; DESIGN sections 4.13, 4.16 - 4.19, 4.21 and 4.22): the workgroup compaction, the ray
 // state machine (the full one and its any-hit form, one template), the light's direction, the sample numbers and directions
-// of the secondary rays (occlusion.hip, envgloss.hip), the shadow ray of a surface point and the per-pixel shading.
+// of the secondary rays (occlusion.hip, envgloss.hip), the SH basis and the closed-form transfer of a normal, the shadow ray
+// of a surface point and the per-pixel shading.  (The environment shade's pixel is env_shade_common.h's.)
 // Everything here has internal linkage; each source file instantiates what it exports.
 #ifndef OI_TRACE_COMMON_H_
 #define OI_TRACE_COMMON_H_
@@ -318,6 +319,25 @@ __device__ __forceinline__ void to_world(const float* __restrict__ Wb, float dx,
   x = Wb[0] * dx + Wb[4] * dy + Wb[8] * dz;
   y = Wb[1] * dx + Wb[5] * dy + Wb[9] * dz;
   z = Wb[2] * dx + Wb[6] * dy + Wb[10] * dz;
+}
+
+// n = g / max(|g|, 1e-6) of gradient row k (surface_shade_at's normal)
+__device__ __forceinline__ void unit_normal(const float* __restrict__ grad, long long k, float& nx, float& ny, float& nz) {
+  const float gx = grad[k * 3 + 0], gy = grad[k * 3 + 1], gz = grad[k * 3 + 2];
+  const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
+  nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
+}
+
+// The unshadowed transfer of a point with the unit normal n in the frame w2b (include/oi_envlight.h's closed form):
+// t[c] = A_band y_c(world normal), the clamped cosine's A = 1, 2/3, 1/4 for the bands 0, 1, 2
+__device__ __forceinline__ void normal_transfer(const float* __restrict__ Wb, float nx, float ny, float nz, float* __restrict__ t) {
+  float x, y, z;
+  to_world(Wb, nx, ny, nz, x, y, z);
+  sh9(x, y, z, t);
+#pragma unroll
+  for (int c = 1; c < 4; ++c) t[c] *= 2.0f / 3.0f;
+#pragma unroll
+  for (int c = 4; c < 9; ++c) t[c] *= 0.25f;
 }
 
 // oi_trace_shadow_begin's ray of hit i under the light lt: n = g / max(|g|, 1e-6), l = the light's direction in the object

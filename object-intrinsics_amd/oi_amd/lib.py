@@ -3,7 +3,9 @@
 SIGS is the one binding table, header file name -> {entry: (restype, argtypes)}, in the order the headers were added;
 symbols(header) lists a header's entries.  The table is the reviewed statement of the ABI on the Python side (the headers
 are not part of the installed package); tests/helpers/cabi.py holds it against the headers prototype by prototype,
-argument by argument, and the struct mirrors below field by field.
+argument by argument, and the struct mirrors below field by field.  Every ctypes.Structure of the package stands in this
+module, and an entry that takes one binds it as POINTER of the mirror, never as a plain pointer: that is what lets the
+helper find it (tests/test_cabi_cpu.py pins both).
 
 The library handle is module-global (never stored on nn.Module instances, so modules stay
 deepcopy-able for the EMA copies the reference trainer makes, src/utils/ema.py:11-12).
@@ -132,6 +134,12 @@ class EnvShadeParams(ctypes.Structure):
 BOUNCE_FLOATS = 27
 
 
+class EnvShadeBounceParams(ctypes.Structure):
+    """Mirror of `oi_env_shade_bounce_params` (include/oi_envbounce.h): EnvShadeParams' fields, then the bounce transfer and
+    its output."""
+    _fields_ = EnvShadeParams._fields_ + [("bounce", _vp), ("indirect", _vp)]
+
+
 # include/oi_envgloss.h
 ENVGLOSS_MIN_SHININESS, ENVGLOSS_MAX_SHININESS, ENVGLOSS_CHUNK = 1, 4096, 2048
 
@@ -145,6 +153,20 @@ class SceneShadeParams(ctypes.Structure):
                 [(n, _vp) for n in ("owner", "owner_ray", "rays_o", "rays_d", "t", "vis_slot", "hit_points", "grad", "rgb", "w2b",
                                     "b2w", "lights", "bg", "visibility", "depth", "position", "normal", "normal_world", "albedo",
                                     "mask", "instance", "image")])
+
+
+# include/oi_scene_light.h
+class SceneShadeAoParams(ctypes.Structure):
+    """Mirror of `oi_scene_shade_ao_params` (include/oi_scene_light.h): the scene's shade parameters, then the occlusion
+    factor."""
+    _fields_ = [("s", SceneShadeParams), ("ambient_occlusion", _vp)]
+
+
+class SceneOcclusionParams(ctypes.Structure):
+    """Mirror of `oi_scene_occlusion_params` (include/oi_scene_light.h)."""
+    _fields_ = ([(n, _i) for n in ("L", "S", "j0", "Sc", "ambient")] +
+                [("seed", _u), ("bias", _f), ("distance", _f), ("n_pad", _ll), ("n_vis", _ll)] +
+                [(n, _vp) for n in ("hit_points", "grad", "offset", "elem", "pixel", "position", "normal", "lights", "radius", "w2b")])
 
 
 SIGS = {
@@ -320,24 +342,21 @@ SIGS = {
         "oi_env_shade_glossy": (_i, [_P(EnvShadeParams)] + [_vp] * 6 + [_i, _i, _i, _P(_i), _vp, _vp, _vp, _vp]),
     },
     # include/oi_scene_light.h: sampled secondary rays between the instances of a scene (an addition to oi_scene.h,
-    # oi_occlusion.h and oi_envlight.h).  Its two parameter structs are bound as plain pointers: their mirrors stand in
-    # oi_amd.ops next to their only users (SceneOcclusionParams, SceneShadeAoParams), held against the header field by field
-    # by tests/test_scene_light_cpu.py
+    # oi_occlusion.h and oi_envlight.h)
     "oi_scene_light.h": {
         "oi_scene_point_pixels": (_i, [_P(TraceBatch), _vp, _vp, _i, _i, _vp, _ll, _vp, _vp]),
-        "oi_scene_occlusion_begin": (_i, [_P(TraceBatch), _vp, _vp]),
+        "oi_scene_occlusion_begin": (_i, [_P(TraceBatch), _P(SceneOcclusionParams), _vp]),
         "oi_trace_batch_step_anyhit": (_i, [_P(TraceBatch), _vp, _ll, _i, _f, _f, _vp]),
         "oi_scene_occlusion_resolve": (_i, [_vp] * 5 + [_i, _ll, _i, _i, _i, _i, _ll, _i, _i, _vp, _vp, _vp]),
         "oi_scene_transfer_resolve": (_i, [_vp] * 7 + [_i, _ll, _i, _i, _i, _ll, _i, _i, _vp, _vp]),
         "oi_scene_transfer_normal": (_i, [_vp, _ll] + [_vp] * 4 + [_i, _ll, _i, _vp, _vp]),
-        "oi_scene_shade_ao": (_i, [_vp, _vp]),
+        "oi_scene_shade_ao": (_i, [_P(SceneShadeAoParams), _vp]),
     },
     # include/oi_envbounce.h: one diffuse interreflection bounce in the transfer of a captured view (an addition to
-    # oi_envlight.h).  Its parameter struct is bound as a plain pointer: the mirror stands in oi_amd.ops next to its only user
-    # (EnvShadeBounceParams), held against the header field by field by tests/test_envbounce_cpu.py
+    # oi_envlight.h)
     "oi_envbounce.h": {
         "oi_bounce_resolve": (_i, [_vp] * 6 + [_ll, _ll, _ll, _i, _vp, _vp, _vp]),
-        "oi_env_shade_bounce": (_i, [_vp, _vp]),
+        "oi_env_shade_bounce": (_i, [_P(EnvShadeBounceParams), _vp]),
     },
 }
 

@@ -861,20 +861,6 @@ def scene_visibility(shadow_status, owner, owner_ray, vis_slot, offset, E, N, L,
 # sampled secondary rays between the instances of a scene (include/oi_scene_light.h); oi_amd.scene sequences these
 # ------------------------------------------------------------------------------------------
 
-class SceneOcclusionParams(ctypes.Structure):
-    """Mirror of `oi_scene_occlusion_params` (include/oi_scene_light.h)."""
-    _fields_ = ([(n, ctypes.c_int) for n in ("L", "S", "j0", "Sc", "ambient")] +
-                [("seed", ctypes.c_uint), ("bias", ctypes.c_float), ("distance", ctypes.c_float), ("n_pad", ctypes.c_longlong),
-                 ("n_vis", ctypes.c_longlong)] +
-                [(n, _vp) for n in ("hit_points", "grad", "offset", "elem", "pixel", "position", "normal", "lights", "radius", "w2b")])
-
-
-class SceneShadeAoParams(ctypes.Structure):
-    """Mirror of `oi_scene_shade_ao_params` (include/oi_scene_light.h): the scene's shade parameters, then the occlusion
-    factor."""
-    _fields_ = [("s", _l.SceneShadeParams), ("ambient_occlusion", _vp)]
-
-
 def scene_point_pixels(st, vis_index, window, W, S, offset, n_vis):
     """-> pixel (n_vis,) int32: the scene pixel Y * S + X of visible point offset[e] + slot."""
     pixel = _new(st.t, n_vis).view(torch.int32)
@@ -893,7 +879,7 @@ def scene_occlusion_begin(sb, hit_points, grad, n_pad, offset, elem, pixel, posi
         raise ValueError("scene_occlusion_begin: give lights and radius, or distance (the ambient form)")
     if not ambient and (not torch.is_tensor(radius) or radius.dtype != torch.float32 or tuple(radius.shape) != (lights.shape[0],)):
         raise ValueError(f"scene_occlusion_begin: radius must be a float32 tensor of shape ({lights.shape[0]},), one per light")
-    P = SceneOcclusionParams()
+    P = _l.SceneOcclusionParams()
     P.L, P.S, P.j0, P.Sc, P.ambient = 1 if ambient else lights.shape[0], int(samples), int(j0), int(chunk), int(ambient)
     P.seed, P.bias, P.distance, P.n_pad, P.n_vis = int(seed), float(bias), float(distance) if ambient else 0.0, int(n_pad), int(n_vis)
     keep = [_c(x) for x in (hit_points, grad, position, normal, lights, radius, w2b)]
@@ -938,7 +924,7 @@ def scene_shade_ao(st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, 
     bytes."""
     if ambient_occlusion is not None and tuple(ambient_occlusion.shape) != (S * S,):
         raise ValueError(f"scene_shade_ao: ambient_occlusion {tuple(ambient_occlusion.shape)}, expected {(S * S,)}")
-    A = SceneShadeAoParams()
+    A = _l.SceneShadeAoParams()
     res, _keep = _scene_shade("scene_shade_ao", A.s, st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_pad, w2b, b2w,
                               lights, bg, visibility, outputs, image_out)
     ao = _c(ambient_occlusion)
@@ -1033,32 +1019,41 @@ def transfer_normal(grad, hit_slot, N, n_hit, w2b):
 ENV_SHADE_OUT = ("shading", "image")
 
 
-def env_shade(status, hit_slot, rgb, n_hit, transfer, envs, bg=None, outputs=ENV_SHADE_OUT, out=None):
-    """One captured view under the environments envs (F, 9, 3) (oi_env_shade).  -> {name: (F, 3, N)} for the names of
-    ENV_SHADE_OUT in `outputs` (written into out[name] when given)."""
+def _env_shade(what, table, P, status, hit_slot, rgb, n_hit, transfer, envs, bg, outputs, out, own=None):
+    """What env_shade, env_shade_bounce and env_shade_glossy share, for the output table `table`: the checks of envs, transfer
+    and `outputs`, then the caller's own checks own(N, F), the output planes (F, 3, N) (out[name] when given) and the fields
+    of EnvShadeParams in the struct P.  -> ({name: plane}, tensors to keep, what own returned)."""
     N = transfer.shape[1]
     F = envs.shape[0] if torch.is_tensor(envs) and envs.dim() == 3 else 0
     if not 1 <= F <= _l.ENV_MAX_ENVS or tuple(envs.shape[1:]) != (_l.ENV_COEFFS, 3):
-        raise ValueError(f"env_shade: envs {tuple(getattr(envs, 'shape', ()))}, expected (F, {_l.ENV_COEFFS}, 3) with "
+        raise ValueError(f"{what}: envs {tuple(getattr(envs, 'shape', ()))}, expected (F, {_l.ENV_COEFFS}, 3) with "
                          f"1 <= F <= {_l.ENV_MAX_ENVS}")
     if tuple(transfer.shape) != (_l.ENV_COEFFS, N) or not outputs:
-        raise ValueError(f"env_shade: transfer {tuple(transfer.shape)}, expected ({_l.ENV_COEFFS}, N); outputs {outputs!r}")
+        raise ValueError(f"{what}: transfer {tuple(transfer.shape)}, expected ({_l.ENV_COEFFS}, N); outputs {outputs!r}")
+    extra = own(N, F) if own else None
     res = {}
     for name in outputs:
-        if name not in ENV_SHADE_OUT:
-            raise ValueError(f"env_shade: unknown output {name!r} (one of {ENV_SHADE_OUT})")
+        if name not in table:
+            raise ValueError(f"{what}: unknown output {name!r} (one of {table})")
         t = None if out is None else out.get(name)
         if t is None:
             t = _new(transfer, F, 3, N)
         elif tuple(t.shape) != (F, 3, N) or not t.is_contiguous() or t.dtype != torch.float32:
-            raise ValueError(f"env_shade: out[{name!r}] must be a contiguous float32 {(F, 3, N)} tensor")
+            raise ValueError(f"{what}: out[{name!r}] must be a contiguous float32 {(F, 3, N)} tensor")
         res[name] = t
-    P = _l.EnvShadeParams()
     P.N, P.n_hit, P.F = N, int(n_hit), F
     keep = [_c(x) for x in (rgb if n_hit else None, transfer, envs, bg)]
     P.rgb, P.transfer, P.envs, P.bg = (_p(x) for x in keep)
     P.status, P.hit_slot = _p(status), _ip(hit_slot)
     P.shading, P.image = _p(res.get("shading")), _p(res.get("image"))
+    return res, keep, extra
+
+
+def env_shade(status, hit_slot, rgb, n_hit, transfer, envs, bg=None, outputs=ENV_SHADE_OUT, out=None):
+    """One captured view under the environments envs (F, 9, 3) (oi_env_shade).  -> {name: (F, 3, N)} for the names of
+    ENV_SHADE_OUT in `outputs` (written into out[name] when given)."""
+    P = _l.EnvShadeParams()
+    res, _keep, _ = _env_shade("env_shade", ENV_SHADE_OUT, P, status, hit_slot, rgb, n_hit, transfer, envs, bg, outputs, out)
     _l.check(_l.load().oi_env_shade(ctypes.byref(P), _stream()), "oi_env_shade")
     return res
 
@@ -1079,43 +1074,21 @@ def bounce_resolve(status, rays_d, hit_slot2, grad2, rgb2, n_hit2, hit_slot, N, 
     return out
 
 
-class EnvShadeBounceParams(ctypes.Structure):
-    """Mirror of `oi_env_shade_bounce_params` (include/oi_envbounce.h): EnvShadeParams' fields, then the bounce transfer and
-    its output."""
-    _fields_ = _l.EnvShadeParams._fields_ + [("bounce", _vp), ("indirect", _vp)]
-
-
 ENV_BOUNCE_OUT = ENV_SHADE_OUT + ("indirect",)
 
 
 def env_shade_bounce(status, hit_slot, rgb, n_hit, transfer, bounce, envs, bg=None, outputs=ENV_BOUNCE_OUT, out=None):
     """env_shade with the bounce transfer (3, 9, N) of bounce_resolve (oi_env_shade_bounce).  -> {name: (F, 3, N)} for the names
     of ENV_BOUNCE_OUT in `outputs` (written into out[name] when given): shading = direct + indirect."""
-    N = transfer.shape[1]
-    F = envs.shape[0] if torch.is_tensor(envs) and envs.dim() == 3 else 0
-    if not 1 <= F <= _l.ENV_MAX_ENVS or tuple(envs.shape[1:]) != (_l.ENV_COEFFS, 3):
-        raise ValueError(f"env_shade_bounce: envs {tuple(getattr(envs, 'shape', ()))}, expected (F, {_l.ENV_COEFFS}, 3) with "
-                         f"1 <= F <= {_l.ENV_MAX_ENVS}")
-    if tuple(transfer.shape) != (_l.ENV_COEFFS, N) or not outputs:
-        raise ValueError(f"env_shade_bounce: transfer {tuple(transfer.shape)}, expected ({_l.ENV_COEFFS}, N); outputs {outputs!r}")
-    if not torch.is_tensor(bounce) or tuple(bounce.shape) != (3, _l.ENV_COEFFS, N):
-        raise ValueError(f"env_shade_bounce: bounce {tuple(getattr(bounce, 'shape', ()))}, expected (3, {_l.ENV_COEFFS}, {N})")
-    res = {}
-    for name in outputs:
-        if name not in ENV_BOUNCE_OUT:
-            raise ValueError(f"env_shade_bounce: unknown output {name!r} (one of {ENV_BOUNCE_OUT})")
-        t = None if out is None else out.get(name)
-        if t is None:
-            t = _new(transfer, F, 3, N)
-        elif tuple(t.shape) != (F, 3, N) or not t.is_contiguous() or t.dtype != torch.float32:
-            raise ValueError(f"env_shade_bounce: out[{name!r}] must be a contiguous float32 {(F, 3, N)} tensor")
-        res[name] = t
-    P = EnvShadeBounceParams()
-    P.N, P.n_hit, P.F = N, int(n_hit), F
-    keep = [_c(x) for x in (rgb if n_hit else None, transfer, envs, bg, bounce)]
-    P.rgb, P.transfer, P.envs, P.bg, P.bounce = (_p(x) for x in keep)
-    P.status, P.hit_slot = _p(status), _ip(hit_slot)
-    P.shading, P.image, P.indirect = _p(res.get("shading")), _p(res.get("image")), _p(res.get("indirect"))
+    def own(N, F):
+        if not torch.is_tensor(bounce) or tuple(bounce.shape) != (3, _l.ENV_COEFFS, N):
+            raise ValueError(f"env_shade_bounce: bounce {tuple(getattr(bounce, 'shape', ()))}, expected (3, {_l.ENV_COEFFS}, {N})")
+
+    P = _l.EnvShadeBounceParams()
+    res, _keep, _ = _env_shade("env_shade_bounce", ENV_BOUNCE_OUT, P, status, hit_slot, rgb, n_hit, transfer, envs, bg, outputs, out,
+                               own)
+    bounce = _c(bounce)
+    P.bounce, P.indirect = _p(bounce), _p(res.get("indirect"))
     _l.check(_l.load().oi_env_shade_bounce(ctypes.byref(P), _stream()), "oi_env_shade_bounce")
     return res
 
@@ -1172,42 +1145,26 @@ def env_shade_glossy(status, hit_slot, rgb, n_hit, transfer, envs, rays_o, hit_p
     """env_shade plus the glossy term (oi_env_shade_glossy): envs (F, 9, 3) the SH halves, glossy (M, 3, Hp, Wp) the
     prefiltered maps, map_index F host integers in [0, M) (checked here, before anything is uploaded), rot (F, 3, 3) world
     rotations, k_s (3,), spec_vis (N,) or None (= 1).  -> {name: (F, 3, N)} for the names of ENV_GLOSSY_OUT in `outputs`."""
-    N = transfer.shape[1]
-    F = envs.shape[0] if torch.is_tensor(envs) and envs.dim() == 3 else 0
-    if not 1 <= F <= _l.ENV_MAX_ENVS or tuple(envs.shape[1:]) != (_l.ENV_COEFFS, 3):
-        raise ValueError(f"env_shade_glossy: envs {tuple(getattr(envs, 'shape', ()))}, expected (F, {_l.ENV_COEFFS}, 3) with "
-                         f"1 <= F <= {_l.ENV_MAX_ENVS}")
-    if tuple(transfer.shape) != (_l.ENV_COEFFS, N) or not outputs:
-        raise ValueError(f"env_shade_glossy: transfer {tuple(transfer.shape)}, expected ({_l.ENV_COEFFS}, N); outputs {outputs!r}")
-    if not torch.is_tensor(glossy) or glossy.dim() != 4 or glossy.shape[1] != 3 or not 1 <= glossy.shape[0] <= _l.ENV_MAX_ENVS:
-        raise ValueError(f"env_shade_glossy: glossy {tuple(getattr(glossy, 'shape', ()))}, expected (M, 3, Hp, Wp) with "
-                         f"1 <= M <= {_l.ENV_MAX_ENVS}")
-    M, _, Hp, Wp = glossy.shape
-    idx = [int(v) for v in map_index]
-    if len(idx) != F or any(not 0 <= v < M for v in idx):
-        raise ValueError(f"env_shade_glossy: map_index {idx} (F = {F} integers, 0 <= map_index < M = {M})")
-    if tuple(rot.shape) != (F, 3, 3) or tuple(k_s.shape) != (3,) or (spec_vis is not None and tuple(spec_vis.shape) != (N,)):
-        raise ValueError(f"env_shade_glossy: rot {tuple(rot.shape)}, k_s {tuple(k_s.shape)}, expected {(F, 3, 3)} and (3,); "
-                         f"spec_vis (N,) = {(N,)} or None")
-    res = {}
-    for name in outputs:
-        if name not in ENV_GLOSSY_OUT:
-            raise ValueError(f"env_shade_glossy: unknown output {name!r} (one of {ENV_GLOSSY_OUT})")
-        t = None if out is None else out.get(name)
-        if t is None:
-            t = _new(transfer, F, 3, N)
-        elif tuple(t.shape) != (F, 3, N) or not t.is_contiguous() or t.dtype != torch.float32:
-            raise ValueError(f"env_shade_glossy: out[{name!r}] must be a contiguous float32 {(F, 3, N)} tensor")
-        res[name] = t
+    def own(N, F):
+        if not torch.is_tensor(glossy) or glossy.dim() != 4 or glossy.shape[1] != 3 or not 1 <= glossy.shape[0] <= _l.ENV_MAX_ENVS:
+            raise ValueError(f"env_shade_glossy: glossy {tuple(getattr(glossy, 'shape', ()))}, expected (M, 3, Hp, Wp) with "
+                             f"1 <= M <= {_l.ENV_MAX_ENVS}")
+        M = glossy.shape[0]
+        idx = [int(v) for v in map_index]
+        if len(idx) != F or any(not 0 <= v < M for v in idx):
+            raise ValueError(f"env_shade_glossy: map_index {idx} (F = {F} integers, 0 <= map_index < M = {M})")
+        if tuple(rot.shape) != (F, 3, 3) or tuple(k_s.shape) != (3,) or (spec_vis is not None and tuple(spec_vis.shape) != (N,)):
+            raise ValueError(f"env_shade_glossy: rot {tuple(rot.shape)}, k_s {tuple(k_s.shape)}, expected {(F, 3, 3)} and (3,); "
+                             f"spec_vis (N,) = {(N,)} or None")
+        return (ctypes.c_int * F)(*idx)
+
     P = _l.EnvShadeParams()
-    P.N, P.n_hit, P.F = N, int(n_hit), F
-    keep = [_c(x) for x in (rgb if n_hit else None, transfer, envs, bg, rays_o, hit_points if n_hit else None,
-                            grad if n_hit else None, w2b, spec_vis, glossy, rot, k_s)]
-    P.rgb, P.transfer, P.envs, P.bg = (_p(x) for x in keep[:4])
-    P.status, P.hit_slot = _p(status), _ip(hit_slot)
-    P.shading, P.image = _p(res.get("shading")), _p(res.get("image"))
-    ro, hp, g, wb, sv, gl, rt, ks = (_p(x) for x in keep[4:])
-    _l.check(_l.load().oi_env_shade_glossy(ctypes.byref(P), ro, hp, g, wb, sv, gl, M, Hp, Wp, (ctypes.c_int * F)(*idx), rt, ks,
+    res, _keep, index = _env_shade("env_shade_glossy", ENV_GLOSSY_OUT, P, status, hit_slot, rgb, n_hit, transfer, envs, bg, outputs,
+                                   out, own)
+    M, _, Hp, Wp = glossy.shape
+    more = [_c(x) for x in (rays_o, hit_points if n_hit else None, grad if n_hit else None, w2b, spec_vis, glossy, rot, k_s)]
+    ro, hp, g, wb, sv, gl, rt, ks = (_p(x) for x in more)
+    _l.check(_l.load().oi_env_shade_glossy(ctypes.byref(P), ro, hp, g, wb, sv, gl, M, Hp, Wp, index, rt, ks,
                                            _p(res.get("specular")), _stream()), "oi_env_shade_glossy")
     return res
 

@@ -365,15 +365,13 @@ class SceneTransfer:
         ev = stack_envs(seq, dev)
         F = ev.shape[0]
         bgv = _t._bg(bg, dev)
-        out = {k: ops._new(self._transfer, F, 3, M) for k in ops.ENV_SHADE_OUT}
         if s.n_pad == 0:   # no hit at all: nothing is launched
+            out = {k: ops._new(self._transfer, F, 3, M) for k in ops.ENV_SHADE_OUT}
             out["shading"].zero_()
             out["image"].copy_((torch.zeros(3, device=dev) if bgv is None else bgv).view(1, 3, 1).expand(F, 3, M))
         else:
-            for a in range(0, F, _t.ENV_MAX_ENVS):
-                b = min(F, a + _t.ENV_MAX_ENVS)
-                ops.env_shade(self._status, self._hit_slot, self._rgb, M, self._transfer, ev[a:b], bgv,
-                              out={k: v[a:b] for k, v in out.items()})
+            out = _t._shade_chunks(self._transfer, ops.ENV_SHADE_OUT, F, M, lambda a, b, out: ops.env_shade(
+                self._status, self._hit_slot, self._rgb, M, self._transfer, ev[a:b], bgv, out=out))
         res = {k: v.view(F, 3, S, S) for k, v in out.items()}
         res.update(self.maps)
         res["stats"] = s.stats()

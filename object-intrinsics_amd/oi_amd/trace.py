@@ -562,6 +562,16 @@ def _check_bounces(bounces, samples, glossy_samples, shininess, what):
     return int(bounces)
 
 
+def _shade_chunks(like, names, F, N, launch):
+    """-> {name: (F, 3, N) plane} for `names`, filled by launch(a, b, out) for the environments [a, b) in steps of ENV_MAX_ENVS;
+    out: the planes' rows [a, b)."""
+    planes = {k: ops._new(like, F, 3, N) for k in names}
+    for a in range(0, F, ENV_MAX_ENVS):
+        b = min(F, a + ENV_MAX_ENVS)
+        launch(a, b, {k: v[a:b] for k, v in planes.items()})
+    return planes
+
+
 class TransferCapture:
     """One traced view and its SH transfer map: everything shade() needs, none of which depends on the light.
     surface: the _Surface (primary trace, gradients and albedo at the hits); transfer (1, 9, H, W); maps: render_surface's
@@ -604,16 +614,12 @@ class TransferCapture:
             if specular is not None:
                 raise ValueError("shade: specular= needs EnvMap environments (an EnvLight has no glossy half)")
             ev = stack_envs(seq, dev)
-            F, N = ev.shape[0], s.N
-            out = {k: ops._new(s.ro, F, 3, N) for k in (ops.ENV_SHADE_OUT if self._bounce is None else ops.ENV_BOUNCE_OUT)}
-            for a in range(0, F, ENV_MAX_ENVS):
-                b = min(F, a + ENV_MAX_ENVS)
-                if self._bounce is None:
-                    ops.env_shade(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, ev[a:b], bgv,
-                                  out={k: v[a:b] for k, v in out.items()})
-                else:
-                    ops.env_shade_bounce(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, self._bounce, ev[a:b], bgv,
-                                         out={k: v[a:b] for k, v in out.items()})
+            F, view = ev.shape[0], (s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer)
+            if self._bounce is None:
+                names, launch = ops.ENV_SHADE_OUT, lambda a, b, out: ops.env_shade(*view, ev[a:b], bgv, out=out)
+            else:
+                names, launch = ops.ENV_BOUNCE_OUT, lambda a, b, out: ops.env_shade_bounce(*view, self._bounce, ev[a:b], bgv, out=out)
+            out = _shade_chunks(s.ro, names, F, s.N, launch)
             return {k: v.view(F, 3, self.H, self.W) for k, v in out.items()}
         if self.glossy_samples is None:
             raise ValueError("shade: this capture has no reflection-lobe trace; capture_transfer(glossy_samples=S) traces one, "
@@ -623,14 +629,14 @@ class TransferCapture:
                              f"{self.shininess:g}")
         ks = self.specular if specular is None else specular
         ks = torch.as_tensor(np.broadcast_to(np.asarray(ks, dtype=np.float32), (3,)).copy()).to(dev)
-        F, N = len(seq), s.N
-        out = {k: ops._new(s.ro, F, 3, N) for k in ops.ENV_GLOSSY_OUT}
-        for a in range(0, F, ENV_MAX_ENVS):
-            b = min(F, a + ENV_MAX_ENVS)
+        F = len(seq)
+
+        def launch(a, b, out):
             ev, maps, index, rot, _ = stack_maps(seq[a:b], dev)
             ops.env_shade_glossy(s.res.status, s.res.hit_slot, s.rgb, s.n_hit, self._transfer, ev, s.ro,
                                  s.res.hit_points if s.n_hit else None, s.grad, s.w2b, self._spec_vis, maps, index, rot, ks, bgv,
-                                 out={k: v[a:b] for k, v in out.items()})
+                                 out=out)
+        out = _shade_chunks(s.ro, ops.ENV_GLOSSY_OUT, F, s.N, launch)
         return {k: v.view(F, 3, self.H, self.W) for k, v in out.items()}
 
     def stats(self):

@@ -25,8 +25,24 @@ def test_every_mirror_is_checked_against_its_header():
     lib, _ = cabi.built_lib()
     checked = [m for h in lib.SIGS for m in cabi.check_header(h, lib)[1]]
     assert sorted(checked) == sorted(n for n, c in vars(lib).items() if isinstance(c, type) and issubclass(c, ctypes.Structure))
-    assert sorted(checked) == ["CompositeGrads", "CompositeParams", "EnvShadeParams", "PrepParams", "RelightParams",
-                               "SceneShadeParams", "SurfaceAoParams", "SurfaceParams", "TraceBatch", "TraceState"]
+    assert sorted(checked) == ["CompositeGrads", "CompositeParams", "EnvShadeBounceParams", "EnvShadeParams", "PrepParams",
+                               "RelightParams", "SceneOcclusionParams", "SceneShadeAoParams", "SceneShadeParams", "SurfaceAoParams",
+                               "SurfaceParams", "TraceBatch", "TraceState"]
+
+
+def test_no_struct_mirror_outside_lib():
+    """Every ctypes.Structure of the package stands in oi_amd.lib, where the test above finds it, and under no second name
+    elsewhere: a mirror in another module would be bound as a plain pointer and held against no header."""
+    import importlib
+    import os
+    cabi.built_lib()
+    import oi_amd
+    names = sorted("oi_amd." + f[:-3] for f in os.listdir(os.path.dirname(oi_amd.__file__)) if f.endswith(".py") and f != "__init__.py")
+    assert "oi_amd.lib" in names and "oi_amd.ops" in names and len(names) >= 10
+    for name in names:
+        mod = importlib.import_module(name)
+        found = sorted(n for n, c in vars(mod).items() if isinstance(c, type) and issubclass(c, ctypes.Structure))
+        assert found == [] or name == "oi_amd.lib", f"{name} holds the struct mirrors {found}: they belong in oi_amd.lib alone"
 
 
 HEADER_FIXTURE = """

@@ -143,8 +143,8 @@ def test_bounce_resolve(N, S):
 # oi_env_shade_bounce
 # ---------------------------------------------------------------------------------------------------------------------
 def _shade(L, st, N, n_hit, F, status, slot, rgb, transfer, bounce, envs, bg, want=("shading", "image", "indirect")):
-    from oi_amd import ops
-    P = ops.EnvShadeBounceParams()
+    from oi_amd import lib
+    P = lib.EnvShadeBounceParams()
     P.N, P.n_hit, P.F = N, n_hit, F
     out = {k: guarded_empty((F, 3, N), what=k) for k in want}
     for k_, v_ in dict(status=status, hit_slot=slot, rgb=rgb, transfer=transfer, envs=envs, bg=bg, bounce=bounce,

@@ -451,9 +451,14 @@ sdf_mlp_full3_kernel(const float* __restrict__ pts, const char* __restrict__ pac
   // so the slack of the bound (a few bits) does not compound from layer to layer: hi limb 11 bits, lo limb down to 2^-24
   // absolute = 2^-33 of the vector's maximum.
   float sg = 1.f;
+  // sg multiplies the ACCUMULATOR (|W^T V_l| <= 2^21 * 2^16) before G cos does: where max|G_{l-1}| is 0 or tiny (a FiLM
+  // layer whose gamma is 0 for this element) U says nothing about it, and sg = 2^126 made acc * sg infinite and
+  // inf * (G cos = 0) a NaN gradient for every point of the element.  U below 2^-63 is therefore treated as 2^-63:
+  // sg <= 2^77, acc * sg <= 2^114, and the result U * sg < 2^14 is as exact as before (tests/test_gpu_mlp_regimes.py,
+  // cell dead_layer).
   auto pow2_for = [&](float U) {  // -> sg with U * sg in [2^14, 2^15); run *= 1 / sg
     int eb = (__builtin_bit_cast(int, U) >> 23) & 0xff;
-    eb = eb < 15 ? 15 : (eb > 253 ? 253 : eb);
+    eb = eb < 64 ? 64 : (eb > 253 ? 253 : eb);
     run *= __builtin_bit_cast(float, (eb - 14) << 23);
     sg = __builtin_bit_cast(float, (268 - eb) << 23);
   };

@@ -283,6 +283,7 @@ static void launch_dgrad(const DgradArgs& A, int stride, hipStream_t st) {
   else hipLaunchKernelGGL((conv4x4_dgrad_kernel<1, false>), grid, blk, 0, st, A);
 }
 
+// (restated in Python as dgrad_plan of tests/helpers/disc_bwd_regimes.py, which names the routes of every k_splits class: they move together)
 static int make_dgrad(DgradArgs& A, const float* g, const float* ref, float slope, const float* w, float* gx, int B, int Cin,
                       int H, int W, int Cout, int stride, int pad, const float* out_ref = nullptr, float out_slope = 1.f) {
   OI_REQUIRE(g && w && gx, "oi_conv4x4_dgrad: null pointer");
@@ -302,6 +303,7 @@ static int make_dgrad(DgradArgs& A, const float* g, const float* ref, float slop
   return OI_OK;
 }
 
+// (restated in Python as wgrad_plan of tests/helpers/disc_bwd_regimes.py: they move together)
 static int make_wgrad(WgradArgs& A, const float* g, const float* ref, float slope, const float* x, float* gw, int accumulate,
                       int B, int Cin, int H, int W, int Cout, int stride, int pad, float x_slope = 1.f) {
   OI_REQUIRE(g && x && gw, "oi_conv4x4_wgrad: null pointer");

@@ -196,14 +196,32 @@ def ref32(wsd, x):
     return chain(wsd, x, torch.float32)
 
 
-def grad32(wsd, us32):
-    """d (logit 0 summed over the images) / d image along the float32 chain, in float32 throughout."""
+def head_t32(cot, w):
+    """The data gradient of the head (4 x 4 window, stride 1, no padding) for a cotangent (B, out_dim) on the logits: every
+    product rounded once, the logits added in a plain float32 loop, in order."""
+    p = (cot.double()[:, :, None, None, None] * w.double()[None]).float()   # (B, out_dim, C, 4, 4)
+    acc = p[:, 0].clone()
+    for o in range(1, p.shape[1]):
+        acc += p[:, o]
+    return acc
+
+
+def grad32(wsd, us32, cot=None, per_layer=False):
+    """d (logit 0 summed over the images) / d image along the float32 chain, in float32 throughout.  `cot`: a cotangent
+    (B, out_dim) on the logits in place of the selection of logit 0.  `per_layer`: the gradient with respect to every
+    layer's pre-activation instead, [d / d u_0, ..., d / d logits] (tests/helpers/disc_bwd_regimes.py)."""
     L = _layers(wsd)
-    g = L[-1][0][0][None].expand(us32[0].shape[0], -1, -1, -1)   # through the head: its weights of logit 0
+    B = us32[0].shape[0]
+    if cot is None:
+        g = L[-1][0][0][None].expand(B, -1, -1, -1)   # through the head: its weights of logit 0
+    else:
+        g = head_t32(cot, L[-1][0])
+    gs = [None if cot is None else cot.float().reshape(B, -1, 1, 1)]
     for l in range(len(L) - 2, -1, -1):
         g = g * torch.where(us32[l] > 0, 1.0, SLOPE)
+        gs.append(g)
         g = conv_t32(g, L[l][0])
-    return g
+    return gs[::-1] if per_layer else g
 
 
 def _trunc16(t):

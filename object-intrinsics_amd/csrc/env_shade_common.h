@@ -16,14 +16,12 @@ constexpr float kPiF = 3.14159265358979323846f;
 
 enum class EnvTerm { NONE, BOUNCE, GLOSSY };  // beside transfer . coefficients: nothing, bounce[ch] . coefficients, the lobe's map
 
-// n = g / max(|g|, 1e-6), v = (eye - point) / max(|.|, 1e-6) (surface_shade_at's), r = 2 ((n . v) n) - v
+// n = the unit normal of hit k, v = its unit view vector from `eye`, r = 2 ((n . v) n) - v
 __device__ __forceinline__ void reflect_view(const float* __restrict__ grad, const float* __restrict__ hit_points, long long k,
                                              const float* __restrict__ eye, float* n, float* r) {
-  const float gx = grad[k * 3 + 0], gy = grad[k * 3 + 1], gz = grad[k * 3 + 2];
-  const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
-  n[0] = gx / gnc, n[1] = gy / gnc, n[2] = gz / gnc;
-  float vx = eye[0] - hit_points[k * 3 + 0], vy = eye[1] - hit_points[k * 3 + 1], vz = eye[2] - hit_points[k * 3 + 2];
-  normalize3(vx, vy, vz, 1e-6f);
+  unit_normal(grad, k, n[0], n[1], n[2]);
+  float vx, vy, vz;
+  unit_view(eye[0], eye[1], eye[2], hit_points[k * 3 + 0], hit_points[k * 3 + 1], hit_points[k * 3 + 2], vx, vy, vz);
   const float ndv = n[0] * vx + n[1] * vy + n[2] * vz;
   r[0] = 2.0f * (ndv * n[0]) - vx, r[1] = 2.0f * (ndv * n[1]) - vy, r[2] = 2.0f * (ndv * n[2]) - vz;
 }

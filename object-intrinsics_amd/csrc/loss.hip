@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "oi_common.h"
+#include "shade_common.h"
 
 namespace {
 
@@ -123,13 +124,13 @@ __global__ void render_scalars_bwd_kernel(const float* __restrict__ r4, const fl
 __global__ void scalar_glue_kernel(const float* __restrict__ variance, const float* __restrict__ ambient,
                                    const float* __restrict__ specular, const float* __restrict__ shininess,
                                    float* __restrict__ out5, float* __restrict__ packed3) {
-  const float inv_s = fminf(fmaxf(expf(variance[0] * 10.0f), 1e-6f), 1e6f);   // renderer.py:404
-  const float amb = 1.0f / (1.0f + expf(-ambient[0]));                          // lighting.py:50-60
+  const float inv_s = inv_s_of(variance[0]).v;
+  const LightTerms lt = light_terms(ambient[0], specular[0], shininess[0]);
   out5[0] = inv_s;
   out5[1] = 1.0f / inv_s;
-  out5[2] = amb;
-  out5[3] = 1.0f - amb;
-  out5[4] = fmaxf(specular[0], 0.f);
+  out5[2] = lt.amb;
+  out5[3] = lt.dif;
+  out5[4] = lt.spec;
   packed3[0] = ambient[0];
   packed3[1] = specular[0];
   packed3[2] = shininess[0];

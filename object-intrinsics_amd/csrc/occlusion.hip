@@ -30,10 +30,8 @@ __global__ void __launch_bounds__(TR_THREADS) occlusion_begin_kernel(const oi_tr
     const long long lj = q / n_hit, i = q - lj * n_hit;
     const long long l = lj / S;
     const unsigned j = (unsigned)(lj - l * S);
-    const float gx = grad[i * 3 + 0], gy = grad[i * 3 + 1], gz = grad[i * 3 + 2];
-    const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
-    const float nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
-    float dx, dy, dz;
+    float nx, ny, nz, dx, dy, dz;
+    unit_normal(grad, i, nx, ny, nz);
     traced = occlusion_direction<AMBIENT>(nx, ny, nz, (unsigned)hit_index[i], seed, j, S, lights + l * OI_RELIGHT_LIGHT_FLOATS, radius,
                                           l, w2b, dx, dy, dz);
     ox = __fmaf_rn(bias, nx, hit_points[i * 3 + 0]);

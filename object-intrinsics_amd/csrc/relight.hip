@@ -11,7 +11,7 @@
 //
 // Rays whose samples do not fit the LDS budget (T > 1600) take the same code with the staging replaced by the global
 // loads of each group (identical values, identical order).
-#include "oi_common.h"
+#include "shade_common.h"
 #include "../../include/oi_relight.h"
 
 namespace {
@@ -23,19 +23,11 @@ constexpr int STAGE_FLOATS = 10;   // per staged sample: n (3), v (3), w, albedo
 constexpr int G = 4;                // lights per group: 121 VGPRs image-only, 159 with the three extra maps, no scratch
                                    // (8 lights per group: 219, two waves per SIMD)
 
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z, float eps) {
-  // F.normalize(v, eps): v / max(|v|, eps)   (render.hip's helper)
-  const float n = fmaxf(sqrtf(x * x + y * y + z * z), eps);
-  x /= n;
-  y /= n;
-  z /= n;
-}
-
 struct Sample {
   float nx, ny, nz, vx, vy, vz, w, c_r, c_g, c_b;
 };
 
-// The light-independent terms of sample k of ray (o, d): composite_fwd_kernel's expressions (render.hip).
+// The light-independent terms of sample k of ray (o, d).
 __device__ __forceinline__ Sample load_sample(const oi_relight_params& p, long long k, float ox, float oy, float oz, float dx,
                                               float dy, float dz) {
   Sample s;
@@ -46,16 +38,8 @@ __device__ __forceinline__ Sample load_sample(const oi_relight_params& p, long l
   s.c_g = p.rgb[k * 3 + 1];
   s.c_b = p.rgb[k * 3 + 2];
   const float px = ox + dx * mz, py = oy + dy * mz, pz = oz + dz * mz;
-  const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
-  const float gnc = fmaxf(gn, 1e-6f);
-  s.nx = gx / gnc;
-  s.ny = gy / gnc;
-  s.nz = gz / gnc;
-  float vx = ox - px, vy = oy - py, vz = oz - pz;
-  normalize3(vx, vy, vz, 1e-6f);
-  s.vx = vx;
-  s.vy = vy;
-  s.vz = vz;
+  unit_normal(gx, gy, gz, s.nx, s.ny, s.nz);
+  unit_view(ox, oy, oz, px, py, pz, s.vx, s.vy, s.vz);
   return s;
 }
 
@@ -101,18 +85,12 @@ __global__ void __launch_bounds__(256) relight_kernel(const oi_relight_params p,
   float wsum = 0.f;  // sum w (light independent): formed during the first group, in the same per-lane order
   for (int g0 = 0; g0 < p.L; g0 += G) {
     const int gn = min(G, p.L - g0);
-    // light terms of the group.  The direction in this element's box frame: gen_rays_kernel's expression for the
-    // generator's light (render.hip), then composite_fwd_kernel's normalisation.
+    // light terms of the group, the direction in this element's box frame
     float lx[G], ly[G], lz[G], ca[G][3], cd[G][3], cs[G][3], sh[G];
 #pragma unroll
     for (int j = 0; j < G; ++j) {
       const float* lt = p.lights + (size_t)(g0 + (j < gn ? j : 0)) * OI_RELIGHT_LIGHT_FLOATS;
-      const float l0 = lt[0], l1 = lt[1], l2 = lt[2];
-      const float ln = sqrtf(l0 * l0 + l1 * l1 + l2 * l2);
-      lx[j] = Wb[0] * (l0 / ln) + Wb[1] * (l1 / ln) + Wb[2] * (l2 / ln);
-      ly[j] = Wb[4] * (l0 / ln) + Wb[5] * (l1 / ln) + Wb[6] * (l2 / ln);
-      lz[j] = Wb[8] * (l0 / ln) + Wb[9] * (l1 / ln) + Wb[10] * (l2 / ln);
-      normalize3(lx[j], ly[j], lz[j], 1e-6f);
+      light_dir(lt, Wb, lx[j], ly[j], lz[j]);
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         ca[j][c] = lt[4 + c];
@@ -152,12 +130,9 @@ __global__ void __launch_bounds__(256) relight_kernel(const oi_relight_params p,
 #pragma unroll
       for (int j = 0; j < G; ++j) {
         if (j >= gn) break;
-        // Phong terms (lighting.py:167-170, 212-225; generator.py:128-152), composite_fwd_kernel's expressions per channel
-        const float ndl = s.nx * lx[j] + s.ny * ly[j] + s.nz * lz[j];
-        const float rl = fmaxf(ndl, 0.f);
-        const float rx = -lx[j] + 2.0f * (ndl * s.nx), ry = -ly[j] + 2.0f * (ndl * s.ny), rz = -lz[j] + 2.0f * (ndl * s.nz);
-        const float al = fmaxf(s.vx * rx + s.vy * ry + s.vz * rz, 0.f) * (ndl > 0.f ? 1.f : 0.f);
-        const float pw = powf(al, sh[j]);
+        const PhongGeometry ph = phong_geometry(s.nx, s.ny, s.nz, lx[j], ly[j], lz[j], s.vx, s.vy, s.vz);
+        const float rl = fmaxf(ph.ndl, 0.f);
+        const float pw = powf(ph.al, sh[j]);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           const float diff = cd[j][c] * rl;

@@ -14,6 +14,7 @@
 #include "oi_common.h"
 #include "f3_blob.h"
 #include "ray_common.h"
+#include "shade_common.h"
 
 namespace {
 
@@ -173,7 +174,7 @@ __global__ void __launch_bounds__(256) prep_render_kernel(const oi_prep_params p
     }
   }
   const long long r0 = (long long)rb * PREP_RAYS;
-  if (t < PREP_RAYS && r0 + t < n) {  // gen_rays_kernel's expressions
+  if (t < PREP_RAYS && r0 + t < n) {  // this workgroup's rays
     const long long idx = r0 + t;
     const int x = idx % R, y = (idx / R) % R, b = idx / ((long long)R * R);
     const RayOD ry = make_ray(p.c2b[b], p.kinv, p.offs[b][0], p.offs[b][1], R, x, y);
@@ -428,14 +429,6 @@ merge_sorted_kernel(const float* __restrict__ z, const float* __restrict__ sdf, 
 // ------------------------------------------------------------------------------------------
 // a12 (tail) + a15: alpha compositing + Phong shading + maps, one wavefront per ray
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z, float eps) {
-  // F.normalize(v, eps): v / max(|v|, eps)
-  const float n = fmaxf(sqrtf(x * x + y * y + z * z), eps);
-  x /= n;
-  y /= n;
-  z /= n;
-}
-
 // Sums the per-block partials of composite_fwd_kernel in a fixed order (256 threads: block-strided partial sums, wave sums,
 // four waves) and derives the scalars the reference gets from ~8 tiny tensor launches:  out[0..3] = reduce4 totals,
 // out[4..7] = ray sums, out[8] = gradient_error = out[0] / (out[1] + 1e-5), out[9] = surface_loss = out[2] / (N T),
@@ -507,10 +500,9 @@ composite_fwd_kernel(const oi_composite_params p) {
   const float dx = p.rays_d[r * 3 + 0], dy = p.rays_d[r * 3 + 1], dz = p.rays_d[r * 3 + 2];
   float lx = p.light_dir[e * 3 + 0], ly = p.light_dir[e * 3 + 1], lz = p.light_dir[e * 3 + 2];
   normalize3(lx, ly, lz, 1e-6f);
-  // SingleVarianceNetwork + clip (neus/models/fields.py:267-268; renderer.py:266)
-  const float inv_s = fminf(fmaxf(expf(p.variance[0] * 10.0f), 1e-6f), 1e6f);
+  const float inv_s = inv_s_of(p.variance[0]).v;
   const float car = p.cos_anneal_ratio;
-  const float l_amb = sigmoidf_(p.light[0]), l_dif = 1.0f - l_amb, l_spec = fmaxf(p.light[1], 0.f), l_shin = p.light[2];
+  const LightTerms lt = light_terms(p.light[0], p.light[1], p.light[2]);
 
   float carry = 1.0f;
   float a_wsum = 0.f, a_wmax = 0.f, a_c0 = 0.f, a_c1 = 0.f, a_c2 = 0.f, a_i0 = 0.f, a_i1 = 0.f, a_i2 = 0.f;
@@ -525,37 +517,23 @@ composite_fwd_kernel(const oi_composite_params p) {
     const float gx = p.grad[k * 3 + 0], gy = p.grad[k * 3 + 1], gz = p.grad[k * 3 + 2];
     const float c_r = p.rgb[k * 3 + 0], c_g = p.rgb[k * 3 + 1], c_b = p.rgb[k * 3 + 2];
 
-    // renderer.py:269-286
-    const float true_cos = dx * gx + dy * gy + dz * gz;
-    const float iter_cos = -(fmaxf(-true_cos * 0.5f + 0.5f, 0.f) * (1.0f - car) + fmaxf(-true_cos, 0.f) * car);
-    const float prev_cdf = sigmoidf_((sdf - iter_cos * dist * 0.5f) * inv_s);
-    const float next_cdf = sigmoidf_((sdf + iter_cos * dist * 0.5f) * inv_s);
-    float alpha = (prev_cdf - next_cdf + 1e-5f) / (prev_cdf + 1e-5f);
-    alpha = fminf(fmaxf(alpha, 0.f), 1.f);
+    const NeusAlpha na = neus_alpha(dx * gx + dy * gy + dz * gz, sdf, dist, car, inv_s);
+    const float prev_cdf = na.prev_cdf;
+    float alpha = na.alpha;
     if (!on) alpha = 0.f;
-
-    // weights = alpha * cumprod([1, 1 - alpha + 1e-7])[:-1]   (renderer.py:300): wavefront product scan
-    const float incl = wave_scan_mul(on ? 1.0f - alpha + 1e-7f : 1.0f, lane);
-    float excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 1.0f;
-    const float w = alpha * (excl * carry);
-    carry *= __shfl(incl, 63, 64);
+    const float w = alpha * transmittance_step(on ? 1.0f - alpha + 1e-7f : 1.0f, lane, carry);
 
     const float px = ox + dx * mz, py = oy + dy * mz, pz = oz + dz * mz;
     const float pn = sqrtf(px * px + py * py + pz * pz);
     const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
 
-    // Phong terms (lighting.py:167-170, 212-225; generator.py:128-152)
-    const float gnc = fmaxf(gn, 1e-6f);
-    const float nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
-    const float ndl = nx * lx + ny * ly + nz * lz;
-    const float diff = l_dif * fmaxf(ndl, 0.f);
-    float vx = ox - px, vy = oy - py, vz = oz - pz;
-    normalize3(vx, vy, vz, 1e-6f);
-    const float rx = -lx + 2.0f * (ndl * nx), ry = -ly + 2.0f * (ndl * ny), rz = -lz + 2.0f * (ndl * nz);
-    const float al = fmaxf(vx * rx + vy * ry + vz * rz, 0.f) * (ndl > 0.f ? 1.f : 0.f);
-    const float spec = l_spec * powf(al, l_shin);
-    const float shade = l_amb + diff;
+    float nx, ny, nz, vx, vy, vz;
+    unit_normal(gx, gy, gz, gn, nx, ny, nz);
+    unit_view(ox, oy, oz, px, py, pz, vx, vy, vz);
+    const PhongGeometry ph = phong_geometry(nx, ny, nz, lx, ly, lz, vx, vy, vz);
+    const float diff = lt.dif * fmaxf(ph.ndl, 0.f);
+    const float spec = lt.spec * powf(ph.al, lt.shin);
+    const float shade = lt.amb + diff;
 
     if (c0 == 0) cdf_first = __shfl(prev_cdf, 0, 64);
     if (on && live) {

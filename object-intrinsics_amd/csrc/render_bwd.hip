@@ -7,11 +7,11 @@
 // (product scan) and emits every gradient that does not depend on later samples; pass 2 walks the
 // samples backwards with a suffix-sum scan for d w_j / d alpha_i (j > i).
 #include "oi_common.h"
+#include "shade_common.h"
 
 namespace {
 
 using oi::sigmoidf_;
-using oi::wave_scan_mul;
 using oi::wave_sum;
 
 constexpr int RAYS_PER_BLOCK = 4;
@@ -45,15 +45,11 @@ composite_bwd_kernel(const oi_composite_params p, const oi_composite_grads q) {
   const float ox = p.rays_o[r * 3 + 0], oy = p.rays_o[r * 3 + 1], oz = p.rays_o[r * 3 + 2];
   const float dx = p.rays_d[r * 3 + 0], dy = p.rays_d[r * 3 + 1], dz = p.rays_d[r * 3 + 2];
   float lx = p.light_dir[e * 3 + 0], ly = p.light_dir[e * 3 + 1], lz = p.light_dir[e * 3 + 2];
-  {
-    const float n = fmaxf(sqrtf(lx * lx + ly * ly + lz * lz), 1e-6f);
-    lx /= n; ly /= n; lz /= n;
-  }
-  const float inv_s_raw = expf(p.variance[0] * 10.0f);
-  const float inv_s = fminf(fmaxf(inv_s_raw, 1e-6f), 1e6f);
-  const bool inv_s_free = inv_s_raw > 1e-6f && inv_s_raw < 1e6f;
+  normalize3(lx, ly, lz, 1e-6f);
+  const InvS var = inv_s_of(p.variance[0]);
+  const float inv_s = var.v;
   const float car = p.cos_anneal_ratio;
-  const float l_amb = sigmoidf_(p.light[0]), l_dif = 1.0f - l_amb, l_spec = fmaxf(p.light[1], 0.f), l_shin = p.light[2];
+  const LightTerms lt = light_terms(p.light[0], p.light[1], p.light[2]);
 
   // ---- upstream per-ray gradients
   float W = 0.f;
@@ -65,15 +61,10 @@ composite_bwd_kernel(const oi_composite_params p, const oi_composite_grads q) {
       const long long k = r * T + (on ? i : T - 1);
       const float sdf = p.sdf[k], dist = p.dists[k];
       const float tc = dx * p.grad[k * 3] + dy * p.grad[k * 3 + 1] + dz * p.grad[k * 3 + 2];
-      const float ic = -(fmaxf(-tc * 0.5f + 0.5f, 0.f) * (1.0f - car) + fmaxf(-tc, 0.f) * car);
-      const float P = sigmoidf_((sdf - ic * dist * 0.5f) * inv_s), Nn = sigmoidf_((sdf + ic * dist * 0.5f) * inv_s);
-      float alpha = fminf(fmaxf((P - Nn + 1e-5f) / (P + 1e-5f), 0.f), 1.f);
+      float alpha = neus_alpha(tc, sdf, dist, car, inv_s).alpha;
       if (!on) alpha = 0.f;
-      const float incl = wave_scan_mul(on ? 1.0f - alpha + 1e-7f : 1.0f, lane);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.0f;
-      W += wave_sum(on ? alpha * (excl * carry) : 0.f);
-      carry *= __shfl(incl, 63, 64);
+      const float Ti = transmittance_step(on ? 1.0f - alpha + 1e-7f : 1.0f, lane, carry);
+      W += wave_sum(on ? alpha * Ti : 0.f);
     }
   }
   // d image: [N][3], or the [B][3][N / B] map layout the forward wrote (p.image_planar)
@@ -100,38 +91,25 @@ composite_bwd_kernel(const oi_composite_params p, const oi_composite_grads q) {
     const float sdf = p.sdf[k], dist = p.dists[k], mz = p.mid_z[k];
     const float gx = p.grad[k * 3], gy = p.grad[k * 3 + 1], gzz = p.grad[k * 3 + 2];
     const float c_r = p.rgb[k * 3], c_g = p.rgb[k * 3 + 1], c_b = p.rgb[k * 3 + 2];
-    const float tc = dx * gx + dy * gy + dz * gzz;
-    const float ic = -(fmaxf(-tc * 0.5f + 0.5f, 0.f) * (1.0f - car) + fmaxf(-tc, 0.f) * car);
-    const float P = sigmoidf_((sdf - ic * dist * 0.5f) * inv_s), Nn = sigmoidf_((sdf + ic * dist * 0.5f) * inv_s);
-    float alpha = fminf(fmaxf((P - Nn + 1e-5f) / (P + 1e-5f), 0.f), 1.f);
+    float alpha = neus_alpha(dx * gx + dy * gy + dz * gzz, sdf, dist, car, inv_s).alpha;
     if (!on) alpha = 0.f;
     const float om = on ? 1.0f - alpha + 1e-7f : 1.0f;
-    const float incl = wave_scan_mul(om, lane);
-    float excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 1.0f;
-    const float Ti = excl * carry;
+    const float Ti = transmittance_step(om, lane, carry);
     const float w = alpha * Ti;
-    carry *= __shfl(incl, 63, 64);
 
     const float px = ox + dx * mz, py = oy + dy * mz, pz = oz + dz * mz;
     const float pn = sqrtf(px * px + py * py + pz * pz);
     const float gn = sqrtf(gx * gx + gy * gy + gzz * gzz);
-    const float gnc = fmaxf(gn, 1e-6f);
-    const float nx = gx / gnc, ny = gy / gnc, nz = gzz / gnc;
-    const float ndl = nx * lx + ny * ly + nz * lz;
+    float nx, ny, nz, vx, vy, vz;
+    unit_normal(gx, gy, gzz, gn, nx, ny, nz);
+    unit_view(ox, oy, oz, px, py, pz, vx, vy, vz);
+    const PhongGeometry ph = phong_geometry(nx, ny, nz, lx, ly, lz, vx, vy, vz);
+    const float ndl = ph.ndl, vr = ph.vr, al = ph.al;
     const float rndl = fmaxf(ndl, 0.f);
-    const float diff = l_dif * rndl;
-    float vx = ox - px, vy = oy - py, vz = oz - pz;
-    {
-      const float n = fmaxf(sqrtf(vx * vx + vy * vy + vz * vz), 1e-6f);
-      vx /= n; vy /= n; vz /= n;
-    }
-    const float rx = -lx + 2.0f * (ndl * nx), ry = -ly + 2.0f * (ndl * ny), rz = -lz + 2.0f * (ndl * nz);
-    const float vr = vx * rx + vy * ry + vz * rz;
-    const float al = fmaxf(vr, 0.f) * (ndl > 0.f ? 1.f : 0.f);
-    const float al_h = powf(al, l_shin);
-    const float spec = l_spec * al_h;
-    const float shade = l_amb + diff;
+    const float diff = lt.dif * rndl;
+    const float al_h = powf(al, lt.shin);
+    const float spec = lt.spec * al_h;
+    const float shade = lt.amb + diff;
 
     // A_i = dL/dw_i
     const float gwi = (q.g_weights && on) ? q.g_weights[k] : 0.f;
@@ -153,10 +131,10 @@ composite_bwd_kernel(const oi_composite_params p, const oi_composite_grads q) {
       acc_cs += d_spec * al_h;
       float d_al = 0.f;
       if (al > 0.f) {
-        acc_sh += d_spec * l_spec * al_h * logf(al);
-        d_al = d_spec * l_spec * l_shin * powf(al, l_shin - 1.0f);
+        acc_sh += d_spec * lt.spec * al_h * logf(al);
+        d_al = d_spec * lt.spec * lt.shin * powf(al, lt.shin - 1.0f);
       }
-      float d_ndl = d_diff * l_dif * (ndl > 0.f ? 1.f : 0.f);
+      float d_ndl = d_diff * lt.dif * (ndl > 0.f ? 1.f : 0.f);
       const float d_vr = d_al * ((vr > 0.f && ndl > 0.f) ? 1.f : 0.f);
       const float drx = d_vr * vx, dry = d_vr * vy, drz = d_vr * vz;  // d rho
       d_ndl += 2.0f * (drx * nx + dry * ny + drz * nz);
@@ -204,7 +182,7 @@ composite_bwd_kernel(const oi_composite_params p, const oi_composite_grads q) {
     const float sdf = p.sdf[k], dist = p.dists[k];
     const float gx = p.grad[k * 3], gy = p.grad[k * 3 + 1], gzz = p.grad[k * 3 + 2];
     const float tc = dx * gx + dy * gy + dz * gzz;
-    const float ic = -(fmaxf(-tc * 0.5f + 0.5f, 0.f) * (1.0f - car) + fmaxf(-tc, 0.f) * car);
+    const float ic = anneal_cos(tc, car);
     const float eh = ic * dist * 0.5f;
     const float P = sigmoidf_((sdf - eh) * inv_s), Nn = sigmoidf_((sdf + eh) * inv_s);
     const float raw = (P - Nn + 1e-5f) / (P + 1e-5f);
@@ -257,11 +235,11 @@ composite_bwd_kernel(const oi_composite_params p, const oi_composite_grads q) {
       for (int t = 0; t < 8; ++t) s[t] += red[wv][t];
     if (q.d_light) {
       // ambient = sigmoid(a); diffuse = 1 - ambient; specular = max(s, 0); shininess
-      atomicAdd(q.d_light + 0, (s[0] - s[1]) * l_amb * (1.0f - l_amb));
+      atomicAdd(q.d_light + 0, (s[0] - s[1]) * lt.amb * (1.0f - lt.amb));
       atomicAdd(q.d_light + 1, p.light[1] > 0.f ? s[2] : 0.f);
       atomicAdd(q.d_light + 2, s[3]);
     }
-    if (q.d_variance && inv_s_free) atomicAdd(q.d_variance, s[7] * inv_s * 10.0f);
+    if (q.d_variance && var.unclamped()) atomicAdd(q.d_variance, s[7] * inv_s * 10.0f);
   }
 }
 
@@ -300,8 +278,8 @@ composite_bwd_reduce_kernel(const oi_composite_params p, const oi_composite_grad
     atomicAdd(q.d_light + 1, p.light[1] > 0.f ? s[2] : 0.f);
     atomicAdd(q.d_light + 2, s[3]);
   }
-  const float inv_s_raw = expf(p.variance[0] * 10.0f);
-  if (q.d_variance && inv_s_raw > 1e-6f && inv_s_raw < 1e6f) atomicAdd(q.d_variance, s[7] * inv_s_raw * 10.0f);
+  const InvS inv_s = inv_s_of(p.variance[0]);
+  if (q.d_variance && inv_s.unclamped()) atomicAdd(q.d_variance, s[7] * inv_s.raw * 10.0f);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -319,9 +297,9 @@ __global__ void light_dir_fwd_kernel(const float* __restrict__ d, const float* _
   float v[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) v[i] = R[4 * i] * u[0] + R[4 * i + 1] * u[1] + R[4 * i + 2] * u[2];
-  const float nv = fmaxf(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), 1e-6f);
+  normalize3(v[0], v[1], v[2], 1e-6f);
 #pragma unroll
-  for (int i = 0; i < 3; ++i) n[b * 3 + i] = v[i] / nv;
+  for (int i = 0; i < 3; ++i) n[b * 3 + i] = v[i];
 }
 
 __global__ void __launch_bounds__(64)

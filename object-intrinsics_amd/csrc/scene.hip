@@ -100,9 +100,8 @@ __global__ void __launch_bounds__(TR_THREADS) scene_points_kernel(const int* __r
   if (g >= n_vis) return;  // (offsets that do not belong to these counts: nothing is written outside the lists)
   float w[3];
   transform_point(b2w + (long long)e * 16, hit_points + k * 3, w);
-  const float gx = grad[k * 3 + 0], gy = grad[k * 3 + 1], gz = grad[k * 3 + 2];
-  const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);  // surface_shade_at's normal
-  const float n[3] = {gx / gnc, gy / gnc, gz / gnc};
+  float n[3];
+  unit_normal(grad, k, n[0], n[1], n[2]);
   const float* Wb = w2b + (long long)e * 16;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {

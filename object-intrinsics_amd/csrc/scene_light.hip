@@ -68,10 +68,8 @@ __global__ void __launch_bounds__(TR_THREADS) scene_occlusion_begin_kernel(const
     const int e = p.elem[g];  // the point's owner
     const long long k = (long long)e * p.n_pad + (g - p.offset[e]);
     const float* We = p.w2b + (long long)e * 16;
-    const float gx = p.grad[k * 3 + 0], gy = p.grad[k * 3 + 1], gz = p.grad[k * 3 + 2];
-    const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
-    const float nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
-    float d[3];
+    float nx, ny, nz, d[3];
+    unit_normal(p.grad, k, nx, ny, nz);
     const bool traced = occlusion_direction<AMBIENT>(nx, ny, nz, (unsigned)p.pixel[g], p.seed, j, p.S,
                                                      p.lights + l * OI_RELIGHT_LIGHT_FLOATS, p.radius, l, We, d[0], d[1], d[2]);
     float o[3] = {__fmaf_rn(p.bias, nx, p.hit_points[k * 3 + 0]), __fmaf_rn(p.bias, ny, p.hit_points[k * 3 + 1]),

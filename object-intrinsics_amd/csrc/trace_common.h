@@ -1,14 +1,15 @@
 // What trace.hip, occlusion.hip, trace_batch.hip, envlight.hip, scene.hip, scene_light.hip and envbounce.hip share
 // (include/oi_trace.h, include/oi_occlusion.h, include/oi_trace_batch.h, include/oi_envlight.h, include/oi_scene.h,
 // include/oi_scene_light.h, include/oi_envbounce.h; DESIGN sections 4.13, 4.16 - 4.19, 4.21 and 4.22): the workgroup compaction, the ray
-// state machine (the full one and its any-hit form, one template), the light's direction, the sample numbers and directions
-// of the secondary rays (occlusion.hip, envgloss.hip), the SH basis and the closed-form transfer of a normal, the shadow ray
-// of a surface point and the per-pixel shading.  (The environment shade's pixel is env_shade_common.h's.)
+// state machine (the full one and its any-hit form, one template), the sample numbers and directions of the secondary rays
+// (occlusion.hip, envgloss.hip), the SH basis and the closed-form transfer of a normal, the shadow ray of a surface point and
+// the per-pixel shading.  (The environment shade's pixel is env_shade_common.h's; the unit normal, the view vector, the
+// light's direction and the Phong geometry are shade_common.h's, shared with the compositing kernels.)
 // Everything here has internal linkage; each source file instantiates what it exports.
 #ifndef OI_TRACE_COMMON_H_
 #define OI_TRACE_COMMON_H_
 
-#include "oi_common.h"
+#include "shade_common.h"
 #include "../../include/oi_trace_batch.h"
 
 namespace {
@@ -19,14 +20,6 @@ constexpr int N_HIT_WORD = OI_TRACE_COUNT_WORDS - 1;
 static_assert(OI_TRACE_COUNT_WORDS == OI_TRACE_MAX_STEPS + 2, "counts[0 .. MAX_STEPS] and the hit count");
 
 __device__ __forceinline__ bool finite_(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z, float eps) {
-  // F.normalize(v, eps): v / max(|v|, eps)   (relight.hip's helper)
-  const float n = fmaxf(sqrtf(x * x + y * y + z * z), eps);
-  x /= n;
-  y /= n;
-  z /= n;
-}
 
 // the sample point of ray (o, d) at t: the one expression every kernel here uses, so a hit's position is bit-equal to the
 // point the MLP was given
@@ -227,17 +220,6 @@ __device__ __forceinline__ void trace_finish_rays(const oi_trace_state& s, int* 
   }
 }
 
-// light l's unit direction in the object frame: relight.hip's expressions
-__device__ __forceinline__ void light_dir(const float* __restrict__ lt, const float* __restrict__ Wb, float& lx, float& ly,
-                                          float& lz) {
-  const float l0 = lt[0], l1 = lt[1], l2 = lt[2];
-  const float ln = sqrtf(l0 * l0 + l1 * l1 + l2 * l2);
-  lx = Wb[0] * (l0 / ln) + Wb[1] * (l1 / ln) + Wb[2] * (l2 / ln);
-  ly = Wb[4] * (l0 / ln) + Wb[5] * (l1 / ln) + Wb[6] * (l2 / ln);
-  lz = Wb[8] * (l0 / ln) + Wb[9] * (l1 / ln) + Wb[10] * (l2 / ln);
-  normalize3(lx, ly, lz, 1e-6f);
-}
-
 // The exit of the unit sphere along (o, d), |o + t d| = 1: 0 when the origin is outside and the ray leaves it.
 __device__ __forceinline__ float unit_sphere_exit(float ox, float oy, float oz, float dx, float dy, float dz) {
   const float b = ox * dx + oy * dy + oz * dz, c = ox * ox + oy * oy + oz * oz - 1.0f;
@@ -321,11 +303,9 @@ __device__ __forceinline__ void to_world(const float* __restrict__ Wb, float dx,
   z = Wb[2] * dx + Wb[6] * dy + Wb[10] * dz;
 }
 
-// n = g / max(|g|, 1e-6) of gradient row k (surface_shade_at's normal)
+// the unit normal of gradient row k
 __device__ __forceinline__ void unit_normal(const float* __restrict__ grad, long long k, float& nx, float& ny, float& nz) {
-  const float gx = grad[k * 3 + 0], gy = grad[k * 3 + 1], gz = grad[k * 3 + 2];
-  const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
-  nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
+  unit_normal(grad[k * 3 + 0], grad[k * 3 + 1], grad[k * 3 + 2], nx, ny, nz);
 }
 
 // The unshadowed transfer of a point with the unit normal n in the frame w2b (include/oi_envlight.h's closed form):
@@ -340,7 +320,7 @@ __device__ __forceinline__ void normal_transfer(const float* __restrict__ Wb, fl
   for (int c = 4; c < 9; ++c) t[c] *= 0.25f;
 }
 
-// oi_trace_shadow_begin's ray of hit i under the light lt: n = g / max(|g|, 1e-6), l = the light's direction in the object
+// oi_trace_shadow_begin's ray of hit i under the light lt: n = the unit normal, l = the light's direction in the object
 // frame; origin = point + bias n, direction = l, far = the exit of the unit sphere; traced: n . l > 0.
 struct ShadowRay {
   float o[3], l[3], far_;
@@ -350,9 +330,8 @@ __device__ __forceinline__ ShadowRay shadow_ray(const float* __restrict__ hit_po
                                                 const float* __restrict__ lt, const float* __restrict__ w2b, float bias) {
   ShadowRay r;
   light_dir(lt, w2b, r.l[0], r.l[1], r.l[2]);
-  const float gx = grad[i * 3 + 0], gy = grad[i * 3 + 1], gz = grad[i * 3 + 2];
-  const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);
-  const float nx = gx / gnc, ny = gy / gnc, nz = gz / gnc;
+  float nx, ny, nz;
+  unit_normal(grad, i, nx, ny, nz);
   r.traced = nx * r.l[0] + ny * r.l[1] + nz * r.l[2] > 0.f;
   r.o[0] = __fmaf_rn(bias, nx, hit_points[i * 3 + 0]);
   r.o[1] = __fmaf_rn(bias, ny, hit_points[i * 3 + 1]);
@@ -374,17 +353,14 @@ __device__ __forceinline__ void surface_shade_at(const P& p, const float* __rest
   const float* Wb = p.w2b;
   if (hit) {
     const long long k = p.hit_slot[r];
-    const float gx = p.grad[k * 3 + 0], gy = p.grad[k * 3 + 1], gz = p.grad[k * 3 + 2];
-    const float gnc = fmaxf(sqrtf(gx * gx + gy * gy + gz * gz), 1e-6f);  // relight.hip's normal
-    n[0] = gx / gnc, n[1] = gy / gnc, n[2] = gz / gnc;
+    unit_normal(p.grad, k, n[0], n[1], n[2]);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       pos[a] = p.hit_points[k * 3 + a];
       alb[a] = p.rgb[k * 3 + a];
       nw[a] = Wb[0 + a] * n[0] + Wb[4 + a] * n[1] + Wb[8 + a] * n[2];  // w2b[:3,:3]^T n
     }
-    vx = p.rays_o[r * 3 + 0] - pos[0], vy = p.rays_o[r * 3 + 1] - pos[1], vz = p.rays_o[r * 3 + 2] - pos[2];
-    normalize3(vx, vy, vz, 1e-6f);
+    unit_view(p.rays_o[r * 3 + 0], p.rays_o[r * 3 + 1], p.rays_o[r * 3 + 2], pos[0], pos[1], pos[2], vx, vy, vz);
   }
   if (p.depth) p.depth[q] = hit ? p.t[r] : __uint_as_float(0x7fc00000u);
   if (p.mask) p.mask[q] = hit ? 1.0f : 0.0f;
@@ -407,12 +383,9 @@ __device__ __forceinline__ void surface_shade_at(const P& p, const float* __rest
     const float* lt = p.lights + (long long)l * OI_RELIGHT_LIGHT_FLOATS;
     float lx, ly, lz;
     light_dir(lt, Wb, lx, ly, lz);
-    // Phong terms: relight_kernel's expressions at weight 1 (relight.hip)
-    const float ndl = n[0] * lx + n[1] * ly + n[2] * lz;
-    const float rl = fmaxf(ndl, 0.f);
-    const float rx = -lx + 2.0f * (ndl * n[0]), ry = -ly + 2.0f * (ndl * n[1]), rz = -lz + 2.0f * (ndl * n[2]);
-    const float al = fmaxf(vx * rx + vy * ry + vz * rz, 0.f) * (ndl > 0.f ? 1.f : 0.f);
-    const float pw = powf(al, lt[15]);
+    const PhongGeometry ph = phong_geometry(n[0], n[1], n[2], lx, ly, lz, vx, vy, vz);
+    const float rl = fmaxf(ph.ndl, 0.f);
+    const float pw = powf(ph.al, lt[15]);
     const bool shadowed = p.visibility != nullptr;
     const float vis = shadowed ? p.visibility[(long long)l * M + q] : 1.0f;
 #pragma unroll

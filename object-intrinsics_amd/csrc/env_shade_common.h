@@ -100,9 +100,7 @@ __device__ __forceinline__ void env_shade_pixel(const P& p, const GlossArgs& g =
     if constexpr (X == EnvTerm::GLOSSY) {
       float n[3], r[3];
       reflect_view(g.grad, g.hit_points, k, g.rays_o + i * 3, n, r);
-      const float* Wb = g.w2b;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) rw[a] = Wb[0 + a] * r[0] + Wb[4 + a] * r[1] + Wb[8 + a] * r[2];  // w2b[:3,:3]^T r
+      to_world(g.w2b, r[0], r[1], r[2], rw[0], rw[1], rw[2]);
       const float vis = g.spec_vis ? g.spec_vis[i] : 1.0f;
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) kv[ch] = __fmul_rn(g.k_s[ch], vis);
@@ -149,7 +147,7 @@ __device__ __forceinline__ void env_shade_pixel(const P& p, const GlossArgs& g =
 template <class P>
 inline int check_env_shade(const char* what, const P* p, bool has_output, const char* outputs) {
   OI_REQUIRE(p != nullptr, "%s: null params", what);
-  OI_REQUIRE(p->N >= 1 && p->N < (1ll << 31) && p->n_hit >= 0 && p->n_hit <= p->N, "%s: N=%lld, n_hit=%lld", what, p->N, p->n_hit);
+  OI_TRY(check_pixels(what, p->N, p->n_hit));
   OI_REQUIRE(p->F >= 1 && p->F <= OI_ENV_MAX_ENVS, "%s: F=%d (1 .. %d environments)", what, p->F, OI_ENV_MAX_ENVS);
   OI_REQUIRE(p->status && p->hit_slot && p->transfer && p->envs, "%s: null input pointer", what);
   OI_REQUIRE(has_output, "%s: no output (%s)", what, outputs);

@@ -3,6 +3,7 @@
 //                         -> the per-channel bounce transfer [3][9][N], one thread per pixel, 27 sums in registers
 //   env_shade_bounce      (transfer + bounce[ch]) . coefficients for F environments, one thread per pixel, its 36 values read once
 //                         (env_shade_common.h's pixel with the BOUNCE term)
+// The pixel shape and the sample count are checked by trace_common.h's check_pixels and check_samples, as envlight.hip's.
 // No atomics at all, no LDS, no scratch; every sum has one fixed order.
 #include "env_shade_common.h"
 #include "../../include/oi_envbounce.h"
@@ -64,8 +65,8 @@ extern "C" {
 int oi_bounce_resolve(const uint8_t* status, const float* rays_d, const int* hit_slot2, const float* grad2, const float* rgb2,
                       const int* hit_slot, long long N, long long n_hit, long long n_hit2, int S, const float* w2b, float* bounce,
                       oi_stream_t stream) {
-  OI_REQUIRE(N >= 1 && N < (1ll << 31) && n_hit >= 0 && n_hit <= N, "oi_bounce_resolve: N=%lld, n_hit=%lld", N, n_hit);
-  OI_REQUIRE(S >= 1 && S <= OI_OCCLUSION_MAX_SAMPLES, "oi_bounce_resolve: S=%d (1 .. %d samples)", S, OI_OCCLUSION_MAX_SAMPLES);
+  OI_TRY(check_pixels("oi_bounce_resolve", N, n_hit));
+  OI_TRY(check_samples("oi_bounce_resolve", S));
   OI_REQUIRE(n_hit * S < (1ll << 31), "oi_bounce_resolve: S * n_hit = %lld rays (below 2^31)", n_hit * S);
   OI_REQUIRE(n_hit2 >= 0 && n_hit2 <= n_hit * S, "oi_bounce_resolve: n_hit2=%lld secondary hits of %lld rays", n_hit2, n_hit * S);
   OI_REQUIRE(hit_slot && w2b && bounce && ((status && rays_d && hit_slot2) || n_hit == 0), "oi_bounce_resolve: null pointer");
@@ -77,8 +78,7 @@ int oi_bounce_resolve(const uint8_t* status, const float* rays_d, const int* hit
 
 int oi_env_shade_bounce(const oi_env_shade_bounce_params* p, oi_stream_t stream) {
   const char* what = "oi_env_shade_bounce";
-  int rc = check_env_shade(what, p, p && (p->shading || p->image || p->indirect), "shading, image and indirect are all null");
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_env_shade(what, p, p && (p->shading || p->image || p->indirect), "shading, image and indirect are all null"));
   OI_REQUIRE(p->bounce != nullptr, "%s: null bounce (oi_env_shade shades a capture without one)", what);
   hipLaunchKernelGGL(env_shade_bounce_kernel, dim3((unsigned)((p->N + ES_THREADS - 1) / ES_THREADS)), dim3(ES_THREADS), 0,
                      oi::as_stream(stream), *p);

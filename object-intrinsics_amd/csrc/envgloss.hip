@@ -1,8 +1,9 @@
 // Glossy environment lighting on the sphere-traced surface (include/oi_envgloss.h), gfx950.
 //   env_prefilter         equirectangular maps -> the Phong-lobe convolution G_s on an equirectangular grid: a dense sphere-to-
 //                         sphere sum, per-chunk partials, then one thread per output value
-//   occlusion_lobe_begin  S rays per visible point distributed as cos^s about the reflected view vector, compacted like
-//                         occlusion.hip's begin kernels; the march and the resolve are occlusion.hip's
+//   occlusion_lobe_begin  S rays per visible point distributed as cos^s about the reflected view vector, written and compacted
+//                         by trace_common.h's write_ray and enter_rays as occlusion.hip's begin kernels; the march and the
+//                         resolve are occlusion.hip's
 //   env_shade_glossy      envlight.hip's shading plus k_s V_spec G_s(R_f^T r_world): rotated bilinear lookups, F per thread
 //                         (env_shade_common.h's pixel with the GLOSSY term)
 // No float atomics, no scratch; every sum has one fixed order.  The only atomics are the compaction's integer counters.
@@ -130,24 +131,11 @@ __global__ void __launch_bounds__(TR_THREADS) occlusion_lobe_begin_kernel(const 
     float dx, dy, dz;
     direction_about(a[0], a[1], a[2], sa, ca, u2, dx, dy, dz);
     traced = n[0] * dx + n[1] * dy + n[2] * dz > 0.f;
-    ox = __fmaf_rn(bias, n[0], hit_points[i * 3 + 0]);
-    oy = __fmaf_rn(bias, n[1], hit_points[i * 3 + 1]);
-    oz = __fmaf_rn(bias, n[2], hit_points[i * 3 + 2]);
-    s.rays_o[q * 3 + 0] = ox, s.rays_o[q * 3 + 1] = oy, s.rays_o[q * 3 + 2] = oz;
-    s.rays_d[q * 3 + 0] = dx, s.rays_d[q * 3 + 1] = dy, s.rays_d[q * 3 + 2] = dz;
-    s.near_[q] = 0.f;
-    s.far_[q] = unit_sphere_exit(ox, oy, oz, dx, dy, dz);
-    s.t[q] = 0.f;
-    s.status[q] = traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING;
-    s.steps[q] = 0;
-    s.side[q] = 0;
-    s.bracket[q * 4 + 0] = s.bracket[q * 4 + 1] = s.bracket[q * 4 + 2] = s.bracket[q * 4 + 3] = 0.f;
+    offset_origin(hit_points + i * 3, bias, n[0], n[1], n[2], ox, oy, oz);
+    const float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz};
+    write_ray(s, q, o, d, 0.f, unit_sphere_exit(ox, oy, oz, dx, dy, dz), traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING);
   }
-  const long long slot = wg_slot(traced, s.counts, lds);
-  if (traced) {
-    s.active[slot] = (int)q;
-    s.points[slot * 3 + 0] = ox, s.points[slot * 3 + 1] = oy, s.points[slot * 3 + 2] = oz;  // o + 0 d
-  }
+  enter_rays(s, q, traced, ox, oy, oz, lds);
 }
 
 __global__ void __launch_bounds__(ES_THREADS) env_shade_glossy_kernel(const oi_env_shade_params p, const GlossArgs g,
@@ -201,28 +189,23 @@ int oi_occlusion_lobe_begin(const oi_trace_state* s, const float* rays_o, const 
                             const int* hit_index, long long n_hit, int S, float shininess, float bias, unsigned seed,
                             oi_stream_t stream) {
   const char* what = "oi_occlusion_lobe_begin";
-  int rc = check_state(s, what);
-  if (rc != OI_OK) return rc;
-  OI_REQUIRE(S >= 1 && S <= OI_OCCLUSION_MAX_SAMPLES, "%s: S=%d (1 .. %d samples)", what, S, OI_OCCLUSION_MAX_SAMPLES);
+  OI_TRY(check_state(s, what));
+  OI_TRY(check_samples(what, S));
   OI_REQUIRE(n_hit >= 1 && n_hit < (1ll << 31) && n_hit * S == s->N, "%s: n_hit=%lld, S=%d, N=%lld (N must be S * n_hit, below 2^31)",
              what, n_hit, S, s->N);
   OI_REQUIRE(shininess_ok(shininess), "%s: shininess %g (%d .. %d, finite)", what, (double)shininess, OI_ENVGLOSS_MIN_SHININESS,
              OI_ENVGLOSS_MAX_SHININESS);
-  OI_REQUIRE(bias >= 0.f && bias < INFINITY, "%s: bias %g (>= 0, finite)", what, (double)bias);
+  OI_TRY(check_bias(what, bias));
   OI_REQUIRE(rays_o && hit_points && grad && hit_index, "%s: null input pointer", what);
-  const hipStream_t st = oi::as_stream(stream);
-  hipLaunchKernelGGL(trace_clear_counts_kernel, dim3(1), dim3(TR_THREADS), 0, st, s->counts);
-  hipLaunchKernelGGL(occlusion_lobe_begin_kernel, dim3(n_blocks(s->N)), dim3(TR_THREADS), 0, st, *s, rays_o, hit_points, grad,
-                     hit_index, n_hit, S, 1.0f / (shininess + 1.0f), bias, seed);
-  return oi::check_launch(what);
+  return launch_begin(what, s, stream, occlusion_lobe_begin_kernel, rays_o, hit_points, grad, hit_index, n_hit, S,
+                      1.0f / (shininess + 1.0f), bias, seed);
 }
 
 int oi_env_shade_glossy(const oi_env_shade_params* p, const float* rays_o, const float* hit_points, const float* grad,
                         const float* w2b, const float* spec_vis, const float* glossy, int M, int Hp, int Wp,
                         const int* map_index, const float* rot, const float* k_s, float* specular, oi_stream_t stream) {
   const char* what = "oi_env_shade_glossy";
-  int rc = check_env_shade(what, p, p && (p->shading || p->image || specular), "shading, image and specular are all null");
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_env_shade(what, p, p && (p->shading || p->image || specular), "shading, image and specular are all null"));
   OI_REQUIRE(M >= 1 && M <= OI_ENV_MAX_ENVS && Hp >= 1 && Wp >= 1 && (long long)M * 3 * Hp * Wp < (1ll << 31),
              "%s: M=%d, Hp=%d, Wp=%d (1 <= M <= %d, sizes >= 1, M * 3 * Hp * Wp < 2^31)", what, M, Hp, Wp, OI_ENV_MAX_ENVS);
   OI_REQUIRE(rays_o && w2b && glossy && map_index && rot && k_s, "%s: null glossy input pointer", what);

@@ -4,6 +4,7 @@
 //   transfer_normal       the unshadowed closed form
 //   env_shade             transfer . coefficients for F environments, one thread per pixel, its transfer read once
 //                         (env_shade_common.h's pixel without a further term)
+// The pixel shape and the sample count are checked by trace_common.h's check_pixels and check_samples, as occlusion.hip's.
 // No atomics at all, no scratch; every sum has one fixed order.
 #include "env_shade_common.h"
 
@@ -173,8 +174,8 @@ int oi_env_project(const float* radiance, int E, int He, int We, float* partial,
 
 int oi_transfer_resolve(const uint8_t* status, const float* rays_d, const int* hit_slot, long long N, long long n_hit, int S,
                         const float* w2b, float* transfer, oi_stream_t stream) {
-  OI_REQUIRE(N >= 1 && N < (1ll << 31) && n_hit >= 0 && n_hit <= N, "oi_transfer_resolve: N=%lld, n_hit=%lld", N, n_hit);
-  OI_REQUIRE(S >= 1 && S <= OI_OCCLUSION_MAX_SAMPLES, "oi_transfer_resolve: S=%d (1 .. %d samples)", S, OI_OCCLUSION_MAX_SAMPLES);
+  OI_TRY(check_pixels("oi_transfer_resolve", N, n_hit));
+  OI_TRY(check_samples("oi_transfer_resolve", S));
   OI_REQUIRE(n_hit * S < (1ll << 31), "oi_transfer_resolve: S * n_hit = %lld rays (below 2^31)", n_hit * S);
   OI_REQUIRE(hit_slot && w2b && transfer && ((status && rays_d) || n_hit == 0), "oi_transfer_resolve: null pointer");
   hipLaunchKernelGGL(transfer_resolve_kernel, dim3(n_blocks(N)), dim3(TR_THREADS), 0, oi::as_stream(stream), status, rays_d, hit_slot,
@@ -184,7 +185,7 @@ int oi_transfer_resolve(const uint8_t* status, const float* rays_d, const int* h
 
 int oi_transfer_normal(const float* grad, const int* hit_slot, long long N, long long n_hit, const float* w2b, float* transfer,
                        oi_stream_t stream) {
-  OI_REQUIRE(N >= 1 && N < (1ll << 31) && n_hit >= 0 && n_hit <= N, "oi_transfer_normal: N=%lld, n_hit=%lld", N, n_hit);
+  OI_TRY(check_pixels("oi_transfer_normal", N, n_hit));
   OI_REQUIRE(hit_slot && w2b && transfer && (grad || n_hit == 0), "oi_transfer_normal: null pointer");
   hipLaunchKernelGGL(transfer_normal_kernel, dim3(n_blocks(N)), dim3(TR_THREADS), 0, oi::as_stream(stream), grad, hit_slot, N, w2b,
                      transfer);
@@ -192,8 +193,7 @@ int oi_transfer_normal(const float* grad, const int* hit_slot, long long N, long
 }
 
 int oi_env_shade(const oi_env_shade_params* p, oi_stream_t stream) {
-  int rc = check_env_shade("oi_env_shade", p, p && (p->shading || p->image), "shading and image are both null");
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_env_shade("oi_env_shade", p, p && (p->shading || p->image), "shading and image are both null"));
   hipLaunchKernelGGL(env_shade_kernel, dim3((unsigned)((p->N + ES_THREADS - 1) / ES_THREADS)), dim3(ES_THREADS), 0,
                      oi::as_stream(stream), *p);
   return oi::check_launch("oi_env_shade");

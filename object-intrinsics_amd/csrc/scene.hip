@@ -8,9 +8,10 @@
 //   points         the visible points of all instances as one world-frame list
 //   shadow_begin   per occluder instance one shadow ray per (light, visible point): the owner's own ray by trace.hip's
 //                  expressions, any other instance's moved into its box frame and culled against its unit sphere
-//   visibility     a pixel is lit when its shadow ray missed every instance
-// The march, the finish, the gather and both MLP passes are the library's own.  The compaction is trace_common.h's wg_slot:
-// one integer atomicAdd and one atomicMax per workgroup; resolve and visibility loop over the elements in a fixed order and
+//   visibility     a pixel is lit when its shadow ray missed every instance (scene_common.h's escaped_everywhere)
+// The march, the finish, the gather and both MLP passes are the library's own.  The begin kernels store a ray through
+// trace_common.h's write_ray and compact through its enter_rays, the first sample point passed from registers (wg_slot:
+// one integer atomicAdd and one atomicMax per workgroup); resolve and visibility loop over the elements in a fixed order and
 // use no atomics.  No LDS beyond the compaction's counter words, no scratch.
 #include "ray_common.h"
 #include "scene_common.h"
@@ -25,19 +26,20 @@ __global__ void __launch_bounds__(TR_THREADS) scene_begin_kernel(const oi_trace_
   const oi_trace_state v = element_view(s, e);
   const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
   bool entered = false;
-  float near_ = 0.f;
+  float px = 0.f, py = 0.f, pz = 0.f;
   if (r < s.N) {
     const int j = (int)(r / W), i = (int)(r - (long long)j * W);
     const long long X = (long long)window[e * 2 + 0] + i, Y = (long long)window[e * 2 + 1] + j;
     const bool inside = X >= 0 && X < S && Y >= 0 && Y < S;
     // (a pixel outside the image has no ray: its slot holds pixel (0, 0)'s, never traced)
     const RayOD ry = make_ray(c2b + (long long)e * 16, kinv, 0.f, 0.f, S, inside ? (int)X : 0, inside ? (int)Y : 0);
-    float far_ = 0.f;
+    float near_ = 0.f, far_ = 0.f;
     entered = unit_sphere_chord(ry.o, ry.d, near_, far_) && inside;
     if (!entered) near_ = far_ = 0.f;
     write_ray(v, r, ry.o, ry.d, near_, far_, entered ? OI_TRACE_MARCH : OI_TRACE_MISS);
+    px = __fmaf_rn(near_, ry.d[0], ry.o[0]), py = __fmaf_rn(near_, ry.d[1], ry.o[1]), pz = __fmaf_rn(near_, ry.d[2], ry.o[2]);
   }
-  enter_rays(v, r, entered, near_, live, lds);
+  enter_rays(v, r, entered, px, py, pz, lds, live);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) scene_resolve_kernel(const oi_trace_state s, int E, const int* __restrict__ window,
@@ -102,12 +104,8 @@ __global__ void __launch_bounds__(TR_THREADS) scene_points_kernel(const int* __r
   transform_point(b2w + (long long)e * 16, hit_points + k * 3, w);
   float n[3];
   unit_normal(grad, k, n[0], n[1], n[2]);
-  const float* Wb = w2b + (long long)e * 16;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    position[g * 3 + a] = w[a];
-    normal[g * 3 + a] = Wb[0 + a] * n[0] + Wb[4 + a] * n[1] + Wb[8 + a] * n[2];  // w2b[:3,:3]^T n
-  }
+  to_world(w2b + (long long)e * 16, n[0], n[1], n[2], normal[g * 3 + 0], normal[g * 3 + 1], normal[g * 3 + 2]);
+  position[g * 3 + 0] = w[0], position[g * 3 + 1] = w[1], position[g * 3 + 2] = w[2];
   elem[g] = e;
 }
 
@@ -125,14 +123,14 @@ __global__ void __launch_bounds__(TR_THREADS) scene_shadow_begin_kernel(const oi
   const oi_trace_state v = element_view(s, eo);
   const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
   bool entered = false;
-  float near_ = 0.f;
+  float px = 0.f, py = 0.f, pz = 0.f;
   if (q < s.N) {
     const long long l = q / n_vis, g = q - l * n_vis;
     const int e = elem[g];  // the point's owner
     const float* lt = lights + l * OI_RELIGHT_LIGHT_FLOATS;
     const ShadowRay own = shadow_ray(hit_points + (long long)e * n_pad * 3, grad + (long long)e * n_pad * 3, g - offset[e], lt,
                                      w2b + (long long)e * 16, bias);
-    float o[3] = {own.o[0], own.o[1], own.o[2]}, d[3] = {own.l[0], own.l[1], own.l[2]}, far_ = own.far_;
+    float o[3] = {own.o[0], own.o[1], own.o[2]}, d[3] = {own.l[0], own.l[1], own.l[2]}, near_ = 0.f, far_ = own.far_;
     unsigned status = OI_TRACE_BACKFACING;
     if (own.traced && e == eo) {
       entered = true;
@@ -140,8 +138,7 @@ __global__ void __launch_bounds__(TR_THREADS) scene_shadow_begin_kernel(const oi
     } else if (own.traced) {
       const float* Wb = w2b + (long long)eo * 16;
       float ow[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) ow[a] = __fmaf_rn(bias, normal[g * 3 + a], position[g * 3 + a]);
+      offset_origin(position + g * 3, bias, normal[g * 3 + 0], normal[g * 3 + 1], normal[g * 3 + 2], ow[0], ow[1], ow[2]);
       transform_point(Wb, ow, o);
       light_dir(lt, Wb, d[0], d[1], d[2]);
       entered = unit_sphere_chord(o, d, near_, far_);
@@ -149,8 +146,9 @@ __global__ void __launch_bounds__(TR_THREADS) scene_shadow_begin_kernel(const oi
     }
     if (!entered) near_ = far_ = 0.f;
     write_ray(v, q, o, d, near_, far_, status);
+    px = __fmaf_rn(near_, d[0], o[0]), py = __fmaf_rn(near_, d[1], o[1]), pz = __fmaf_rn(near_, d[2], o[2]);
   }
-  enter_rays(v, q, entered, near_, live, lds);
+  enter_rays(v, q, entered, px, py, pz, lds, live);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) scene_visibility_kernel(const uint8_t* __restrict__ status,
@@ -166,18 +164,15 @@ __global__ void __launch_bounds__(TR_THREADS) scene_visibility_kernel(const uint
   float out = 1.0f;
   if (e >= 0) {
     const long long g = (long long)offset[e] + vis_slot[(long long)e * N + owner_ray[q]];
-    for (int eo = 0; eo < E; ++eo)
-      if (status[((long long)eo * L + l) * n_vis + g] != OI_TRACE_MISS) out = 0.0f;
+    out = escaped_everywhere(status, E, (long long)L * n_vis, l * n_vis + g) ? 1.0f : 0.0f;
   }
   vis[i] = out;
 }
 
 inline int check_scene(const oi_trace_batch* b, int W, int S, const char* what) {
-  int rc = check_batch(b, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_batch(b, what));
   OI_REQUIRE(W >= 1 && (long long)W * W == b->s.N, "%s: W=%d, N=%lld rays per element (N must be W * W)", what, W, b->s.N);
-  OI_REQUIRE(S >= 1 && S <= OI_SCENE_MAX_RESOLUTION, "%s: S=%d (1 .. %d)", what, S, OI_SCENE_MAX_RESOLUTION);
-  return OI_OK;
+  return check_resolution(what, "S", S);
 }
 
 }  // namespace
@@ -187,8 +182,7 @@ extern "C" {
 int oi_scene_begin(const oi_trace_batch* b, const float* c2b, const float* kinv, const int* window, int W, int S,
                    oi_stream_t stream) {
   const char* what = "oi_scene_begin";
-  int rc = check_scene(b, W, S, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_scene(b, W, S, what));
   OI_REQUIRE(c2b && kinv && window, "%s: null input pointer", what);
   const hipStream_t st = oi::as_stream(stream);
   const dim3 grid(n_blocks(b->s.N), b->E);
@@ -200,8 +194,7 @@ int oi_scene_begin(const oi_trace_batch* b, const float* c2b, const float* kinv,
 int oi_scene_resolve(const oi_trace_batch* b, const int* window, int W, int S, int* owner, int* owner_ray,
                      oi_stream_t stream) {
   const char* what = "oi_scene_resolve";
-  int rc = check_scene(b, W, S, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_scene(b, W, S, what));
   OI_REQUIRE(window && owner && owner_ray, "%s: null pointer", what);
   hipLaunchKernelGGL(scene_resolve_kernel, dim3(n_blocks((long long)S * S)), dim3(TR_THREADS), 0, oi::as_stream(stream), b->s,
                      b->E, window, W, S, owner, owner_ray);
@@ -211,8 +204,7 @@ int oi_scene_resolve(const oi_trace_batch* b, const int* window, int W, int S, i
 int oi_scene_visible(const oi_trace_batch* b, const int* owner, const int* window, int W, int S, int* vis_index,
                      int* vis_slot, oi_stream_t stream) {
   const char* what = "oi_scene_visible";
-  int rc = check_scene(b, W, S, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_scene(b, W, S, what));
   OI_REQUIRE(owner && window && vis_index && vis_slot, "%s: null pointer", what);
   const hipStream_t st = oi::as_stream(stream);
   hipLaunchKernelGGL(scene_clear_hits_kernel, dim3(n_blocks(b->E)), dim3(TR_THREADS), 0, st, b->s.counts, b->live, b->E);
@@ -223,8 +215,7 @@ int oi_scene_visible(const oi_trace_batch* b, const int* owner, const int* windo
 
 int oi_scene_shade(const oi_scene_shade_params* p, oi_stream_t stream) {
   const char* what = "oi_scene_shade";
-  int rc = check_scene_shade(p, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_scene_shade(p, what));
   hipLaunchKernelGGL(scene_shade_kernel, dim3(n_blocks((long long)p->S * p->S)), dim3(TR_THREADS), 0, oi::as_stream(stream), *p);
   return oi::check_launch(what);
 }
@@ -233,8 +224,7 @@ int oi_scene_points(const oi_trace_batch* b, const float* hit_points, const floa
                     long long n_vis, const float* b2w, const float* w2b, float* position, float* normal, int* elem,
                     oi_stream_t stream) {
   const char* what = "oi_scene_points";
-  int rc = check_batch(b, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_batch(b, what));
   OI_REQUIRE(n_pad >= 1 && n_pad <= b->s.N, "%s: n_pad=%lld (1 <= n_pad <= N=%lld)", what, n_pad, b->s.N);
   OI_REQUIRE(n_vis >= 1 && n_vis <= b->E * n_pad, "%s: n_vis=%lld (1 <= n_vis <= E * n_pad = %lld)", what, n_vis, b->E * n_pad);
   OI_REQUIRE(hit_points && grad && offset && b2w && w2b && position && normal && elem, "%s: null pointer", what);
@@ -247,13 +237,12 @@ int oi_scene_shadow_begin(const oi_trace_batch* sb, const float* hit_points, con
                           const int* offset, const int* elem, const float* position, const float* normal, long long n_vis,
                           const float* lights, int L, const float* w2b, float bias, oi_stream_t stream) {
   const char* what = "oi_scene_shadow_begin";
-  int rc = check_batch(sb, what);
-  if (rc != OI_OK) return rc;
-  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "%s: L=%d (1 .. %d lights)", what, L, OI_RELIGHT_MAX_LIGHTS);
+  OI_TRY(check_batch(sb, what));
+  OI_TRY(check_lights(what, L));
   OI_REQUIRE(n_vis >= 1 && n_vis * L == sb->s.N, "%s: n_vis=%lld, L=%d, N=%lld (N must be L * n_vis)", what, n_vis, L, sb->s.N);
   OI_REQUIRE(n_pad >= 1 && n_vis <= sb->E * n_pad, "%s: n_pad=%lld, n_vis=%lld (n_pad >= 1, n_vis <= E * n_pad)", what, n_pad,
              n_vis);
-  OI_REQUIRE(bias >= 0.f && bias < INFINITY, "%s: bias %g (>= 0, finite)", what, (double)bias);
+  OI_TRY(check_bias(what, bias));
   OI_REQUIRE(hit_points && grad && offset && elem && position && normal && lights && w2b, "%s: null input pointer", what);
   const hipStream_t st = oi::as_stream(stream);
   const dim3 grid(n_blocks(sb->s.N), sb->E);
@@ -267,10 +256,9 @@ int oi_scene_visibility(const uint8_t* shadow_status, const int* owner, const in
                         const int* offset, int E, long long N, int L, long long n_vis, int S, float* visibility,
                         oi_stream_t stream) {
   const char* what = "oi_scene_visibility";
-  OI_REQUIRE(E >= 1 && E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, E, OI_TRACE_BATCH_MAX_ELEMS);
-  OI_REQUIRE(N >= 1 && E * N < (1ll << 31), "%s: E=%d x N=%lld rays (N >= 1, E * N < 2^31)", what, E, N);
-  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "%s: L=%d (1 .. %d lights)", what, L, OI_RELIGHT_MAX_LIGHTS);
-  OI_REQUIRE(S >= 1 && S <= OI_SCENE_MAX_RESOLUTION, "%s: S=%d (1 .. %d)", what, S, OI_SCENE_MAX_RESOLUTION);
+  OI_TRY(check_scene_rays(what, E, N));
+  OI_TRY(check_lights(what, L));
+  OI_TRY(check_resolution(what, "S", S));
   OI_REQUIRE(n_vis >= 0 && n_vis <= E * N && (long long)E * L * n_vis < (1ll << 31),
              "%s: n_vis=%lld (0 <= n_vis <= E * N, E * L * n_vis < 2^31)", what, n_vis);
   OI_REQUIRE(owner && owner_ray && visibility && (n_vis == 0 || (shadow_status && vis_slot && offset)), "%s: null pointer", what);

@@ -1,6 +1,7 @@
 // What scene.hip and scene_light.hip share (include/oi_scene.h, include/oi_scene_light.h; DESIGN sections 4.19 and 4.21): the
-// unit sphere's chord, the rigid transform, the state of a ray that a begin kernel writes, the compaction of the entered
-// rays, the per-pixel shading on the owner's slices and the checks of its arguments.  Internal linkage, as trace_common.h.
+// unit sphere's chord, the rigid transform, "missed every instance", the per-pixel shading on the owner's slices and the
+// checks of its arguments.  (What a begin kernel stores and the compaction of the entered rays are trace_common.h's write_ray
+// and enter_rays.)  Internal linkage, as trace_common.h.
 #ifndef OI_SCENE_COMMON_H_
 #define OI_SCENE_COMMON_H_
 
@@ -45,31 +46,12 @@ __global__ void __launch_bounds__(TR_THREADS) scene_clear_kernel(const oi_trace_
   if (r < s.N) v.points[r * 3 + 0] = v.points[r * 3 + 1] = v.points[r * 3 + 2] = 0.f;
 }
 
-// ray r of the view v: everything oi_trace_batch_begin writes, for an entered ray (near_ .. far_) or a culled one
-__device__ __forceinline__ void write_ray(const oi_trace_state& v, long long r, const float* o, const float* d, float near_,
-                                          float far_, unsigned status) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) v.rays_o[r * 3 + a] = o[a], v.rays_d[r * 3 + a] = d[a];
-  v.near_[r] = near_;
-  v.far_[r] = far_;
-  v.t[r] = near_;
-  v.status[r] = (uint8_t)status;
-  v.steps[r] = 0;
-  v.side[r] = 0;
-  v.bracket[r * 4 + 0] = near_;
-  v.bracket[r * 4 + 1] = 0.f;
-  v.bracket[r * 4 + 2] = near_;
-  v.bracket[r * 4 + 3] = 0.f;
-}
-
-// the entered rays of this workgroup, compacted behind the element's counter: active list and first sample points
-__device__ __forceinline__ void enter_rays(const oi_trace_state& v, long long r, bool entered, float near_, int* live,
-                                           unsigned* lds) {
-  const long long slot = wg_slot(entered, v.counts, lds, live);
-  if (entered) {
-    v.active[slot] = (int)r;
-    point_at(v.rays_o, v.rays_d, r, near_, v.points + slot * 3);
-  }
+// did ray `ray` (of `rays` per element) end OI_TRACE_MISS in every element?  A fixed-order loop, no early exit.
+__device__ __forceinline__ bool escaped_everywhere(const uint8_t* __restrict__ status, int E, long long rays, long long ray) {
+  bool free_ = true;
+  for (int eo = 0; eo < E; ++eo)
+    if (status[(long long)eo * rays + ray] != OI_TRACE_MISS) free_ = false;
+  return free_;
 }
 
 // oi_surface_params' fields for one element of the scene (surface_shade_at's P)
@@ -106,13 +88,19 @@ __device__ __forceinline__ void scene_shade_pixel(const oi_scene_shade_params& p
   surface_shade_at(v, ao, r, hit, q, M);
 }
 
+// the scene's resolution; name: how the entry's message calls it ("S", or "scene S" where S counts samples)
+inline int check_resolution(const char* what, const char* name, int S) {
+  OI_REQUIRE(S >= 1 && S <= OI_SCENE_MAX_RESOLUTION, "%s: %s=%d (1 .. %d)", what, name, S, OI_SCENE_MAX_RESOLUTION);
+  return OI_OK;
+}
+
 // Arguments of oi_scene_shade and oi_scene_shade_ao.
 inline int check_scene_shade(const oi_scene_shade_params* p, const char* what) {
   OI_REQUIRE(p != nullptr, "%s: null params", what);
-  OI_REQUIRE(p->E >= 1 && p->E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, p->E, OI_TRACE_BATCH_MAX_ELEMS);
+  OI_TRY(check_elements(what, p->E));
   OI_REQUIRE(p->W >= 1 && (long long)p->E * p->W * p->W < (1ll << 31), "%s: E=%d, W=%d (W >= 1, E * W * W < 2^31)", what, p->E,
              p->W);
-  OI_REQUIRE(p->S >= 1 && p->S <= OI_SCENE_MAX_RESOLUTION, "%s: S=%d (1 .. %d)", what, p->S, OI_SCENE_MAX_RESOLUTION);
+  OI_TRY(check_resolution(what, "S", p->S));
   OI_REQUIRE(p->n_pad >= 0 && p->n_pad <= (long long)p->W * p->W, "%s: n_pad=%lld (0 <= n_pad <= W * W = %lld)", what, p->n_pad,
              (long long)p->W * p->W);
   OI_REQUIRE(p->image ? (p->L >= 1 && p->L <= OI_RELIGHT_MAX_LIGHTS && p->lights) : p->L >= 0,

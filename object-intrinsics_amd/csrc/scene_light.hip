@@ -5,9 +5,11 @@
 //   occlusion_begin     per occluder instance Sc sampled rays per (light, visible point): the direction drawn once in the
 //                       owner's frame (trace_common.h's occlusion_direction, occlusion.hip's own), the owner's ray by
 //                       occlusion.hip's expressions, any other instance's moved into its box frame and culled against its
-//                       unit sphere (and against `distance` when ambient)
+//                       unit sphere (and against `distance` when ambient); both origins are trace_common.h's
+//                       offset_origin, the stores and the compaction its write_ray and enter_rays
 //   step_anyhit         trace_common.h's state machine in its any-hit form on an element's view of the batched state
-//   occlusion_resolve   per scene pixel the number of samples that missed every instance, accumulated across chunks as integers
+//   occlusion_resolve   per scene pixel the number of samples that missed every instance (scene_common.h's
+//                       escaped_everywhere), accumulated across chunks as integers
 //   transfer_resolve    per scene pixel the sum of sh9(world direction) over those samples, in sample order, the running sums
 //                       kept in the output between chunks
 //   transfer_normal     the unshadowed closed form on the owner's slices
@@ -45,7 +47,9 @@ __device__ __forceinline__ void rotate(const float* __restrict__ M, const float*
   for (int a = 0; a < 3; ++a) out[a] = M[a * 4 + 0] * v[0] + M[a * 4 + 1] * v[1] + M[a * 4 + 2] * v[2];
 }
 
-// ... and its transpose: w2b[:3,:3]^T v, a box-frame direction in the world
+// ... and its transpose: w2b[:3,:3]^T v, a box-frame direction in the world.  trace_common.h's to_world is the same sum
+// under the default contraction (fused multiply-adds); this one rounds every product, as scene_light_ref.py does, so the two
+// stay apart.
 __device__ __forceinline__ void rotate_t(const float* __restrict__ M, const float* v, float* out) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -60,7 +64,7 @@ __global__ void __launch_bounds__(TR_THREADS) scene_occlusion_begin_kernel(const
   const oi_trace_state v = element_view(s, eo);
   const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
   bool entered = false;
-  float near_ = 0.f;
+  float px = 0.f, py = 0.f, pz = 0.f;
   if (q < s.N) {
     const long long lj = q / p.n_vis, g = q - lj * p.n_vis;
     const long long l = lj / p.Sc;
@@ -68,13 +72,12 @@ __global__ void __launch_bounds__(TR_THREADS) scene_occlusion_begin_kernel(const
     const int e = p.elem[g];  // the point's owner
     const long long k = (long long)e * p.n_pad + (g - p.offset[e]);
     const float* We = p.w2b + (long long)e * 16;
-    float nx, ny, nz, d[3];
+    float nx, ny, nz, d[3], o[3];
     unit_normal(p.grad, k, nx, ny, nz);
     const bool traced = occlusion_direction<AMBIENT>(nx, ny, nz, (unsigned)p.pixel[g], p.seed, j, p.S,
                                                      p.lights + l * OI_RELIGHT_LIGHT_FLOATS, p.radius, l, We, d[0], d[1], d[2]);
-    float o[3] = {__fmaf_rn(p.bias, nx, p.hit_points[k * 3 + 0]), __fmaf_rn(p.bias, ny, p.hit_points[k * 3 + 1]),
-                  __fmaf_rn(p.bias, nz, p.hit_points[k * 3 + 2])};
-    float far_ = 0.f;
+    offset_origin(p.hit_points + k * 3, p.bias, nx, ny, nz, o[0], o[1], o[2]);
+    float near_ = 0.f, far_ = 0.f;
     unsigned status = OI_TRACE_BACKFACING;
     if (traced && e == eo) {
       far_ = unit_sphere_exit(o[0], o[1], o[2], d[0], d[1], d[2]);
@@ -84,8 +87,7 @@ __global__ void __launch_bounds__(TR_THREADS) scene_occlusion_begin_kernel(const
     } else if (traced) {
       const float* Wb = p.w2b + (long long)eo * 16;
       float ow[3], dw[3], dd[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) ow[a] = __fmaf_rn(p.bias, p.normal[g * 3 + a], p.position[g * 3 + a]);
+      offset_origin(p.position + g * 3, p.bias, p.normal[g * 3 + 0], p.normal[g * 3 + 1], p.normal[g * 3 + 2], ow[0], ow[1], ow[2]);
       transform_point(Wb, ow, o);
       rotate_t(We, d, dw);
       rotate(Wb, dw, dd);
@@ -99,8 +101,9 @@ __global__ void __launch_bounds__(TR_THREADS) scene_occlusion_begin_kernel(const
     }
     if (!entered) near_ = far_ = 0.f;
     write_ray(v, q, o, d, near_, far_, status);
+    px = __fmaf_rn(near_, d[0], o[0]), py = __fmaf_rn(near_, d[1], o[1]), pz = __fmaf_rn(near_, d[2], o[2]);
   }
-  enter_rays(v, q, entered, near_, live, lds);
+  enter_rays(v, q, entered, px, py, pz, lds, live);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) trace_batch_step_anyhit_kernel(const oi_trace_state s, int* __restrict__ live,
@@ -108,14 +111,6 @@ __global__ void __launch_bounds__(TR_THREADS) trace_batch_step_anyhit_kernel(con
                                                                              int k, float tol, float omega) {
   __shared__ unsigned lds[TR_WAVES + 1];
   trace_step_rays<true>(element_view(s, blockIdx.y), sdf + (long long)blockIdx.y * s.N, bound, k, tol, omega, lds, live + k + 1);
-}
-
-// did ray `ray` (of L * Sc * n_vis per element) end OI_TRACE_MISS in every element?  A fixed-order loop, no early exit.
-__device__ __forceinline__ bool escaped_everywhere(const uint8_t* __restrict__ status, int E, long long rays, long long ray) {
-  bool free_ = true;
-  for (int eo = 0; eo < E; ++eo)
-    if (status[(long long)eo * rays + ray] != OI_TRACE_MISS) free_ = false;
-  return free_;
 }
 
 __global__ void __launch_bounds__(TR_THREADS) scene_occlusion_resolve_kernel(const uint8_t* __restrict__ status,
@@ -212,8 +207,8 @@ __global__ void __launch_bounds__(TR_THREADS) scene_shade_ao_kernel(const oi_sce
 
 // the strata and the chunk of a sampled trace
 inline int check_chunk(const char* what, int L, int S, int j0, int Sc) {
-  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "%s: L=%d (1 .. %d lights)", what, L, OI_RELIGHT_MAX_LIGHTS);
-  OI_REQUIRE(S >= 1 && S <= OI_OCCLUSION_MAX_SAMPLES, "%s: S=%d (1 .. %d samples)", what, S, OI_OCCLUSION_MAX_SAMPLES);
+  OI_TRY(check_lights(what, L));
+  OI_TRY(check_samples(what, S));
   OI_REQUIRE(j0 >= 0 && Sc >= 1 && j0 <= S - Sc, "%s: j0=%d, Sc=%d, S=%d (the chunk [j0, j0 + Sc) within [0, S), Sc >= 1)", what,
              j0, Sc, S);
   return OI_OK;
@@ -221,10 +216,8 @@ inline int check_chunk(const char* what, int L, int S, int j0, int Sc) {
 
 // what the resolves share: the scene's shape and the size of the chunk's trace
 inline int check_resolve(const char* what, int E, long long N, int L, int Sc, long long n_vis, int scene_S) {
-  OI_REQUIRE(E >= 1 && E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, E, OI_TRACE_BATCH_MAX_ELEMS);
-  OI_REQUIRE(N >= 1 && E * N < (1ll << 31), "%s: E=%d x N=%lld rays (N >= 1, E * N < 2^31)", what, E, N);
-  OI_REQUIRE(scene_S >= 1 && scene_S <= OI_SCENE_MAX_RESOLUTION, "%s: scene S=%d (1 .. %d)", what, scene_S,
-             OI_SCENE_MAX_RESOLUTION);
+  OI_TRY(check_scene_rays(what, E, N));
+  OI_TRY(check_resolution(what, "scene S", scene_S));
   OI_REQUIRE(n_vis >= 1 && n_vis <= E * N && (long long)E * L * Sc * n_vis < (1ll << 31),
              "%s: n_vis=%lld (1 <= n_vis <= E * N, E * L * Sc * n_vis < 2^31)", what, n_vis);
   return OI_OK;
@@ -237,10 +230,9 @@ extern "C" {
 int oi_scene_point_pixels(const oi_trace_batch* b, const int* vis_index, const int* window, int W, int S, const int* offset,
                           long long n_vis, int* pixel, oi_stream_t stream) {
   const char* what = "oi_scene_point_pixels";
-  int rc = check_batch(b, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_batch(b, what));
   OI_REQUIRE(W >= 1 && (long long)W * W == b->s.N, "%s: W=%d, N=%lld rays per element (N must be W * W)", what, W, b->s.N);
-  OI_REQUIRE(S >= 1 && S <= OI_SCENE_MAX_RESOLUTION, "%s: S=%d (1 .. %d)", what, S, OI_SCENE_MAX_RESOLUTION);
+  OI_TRY(check_resolution(what, "S", S));
   OI_REQUIRE(n_vis >= 1 && n_vis <= b->E * b->s.N, "%s: n_vis=%lld (1 <= n_vis <= E * N = %lld)", what, n_vis, b->E * b->s.N);
   OI_REQUIRE(vis_index && window && offset && pixel, "%s: null pointer", what);
   hipLaunchKernelGGL(scene_point_pixels_kernel, dim3(n_blocks(b->s.N), b->E), dim3(TR_THREADS), 0, oi::as_stream(stream),
@@ -250,17 +242,15 @@ int oi_scene_point_pixels(const oi_trace_batch* b, const int* vis_index, const i
 
 int oi_scene_occlusion_begin(const oi_trace_batch* sb, const oi_scene_occlusion_params* p, oi_stream_t stream) {
   const char* what = "oi_scene_occlusion_begin";
-  int rc = check_batch(sb, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_batch(sb, what));
   OI_REQUIRE(p != nullptr, "%s: null params", what);
-  rc = check_chunk(what, p->L, p->S, p->j0, p->Sc);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_chunk(what, p->L, p->S, p->j0, p->Sc));
   OI_REQUIRE(!p->ambient || p->L == 1, "%s: L=%d with ambient (the hemisphere is one set of rays: L must be 1)", what, p->L);
   OI_REQUIRE(p->n_pad >= 1 && p->n_vis >= 1 && p->n_vis <= sb->E * p->n_pad,
              "%s: n_pad=%lld, n_vis=%lld (n_pad >= 1, 1 <= n_vis <= E * n_pad)", what, p->n_pad, p->n_vis);
   OI_REQUIRE((long long)p->L * p->Sc * p->n_vis == sb->s.N, "%s: L=%d, Sc=%d, n_vis=%lld, N=%lld (N must be L * Sc * n_vis)", what,
              p->L, p->Sc, p->n_vis, sb->s.N);
-  OI_REQUIRE(p->bias >= 0.f && p->bias < INFINITY, "%s: bias %g (>= 0, finite)", what, (double)p->bias);
+  OI_TRY(check_bias(what, p->bias));
   OI_REQUIRE(!p->ambient || p->distance > 0.f, "%s: distance %g (> 0; INFINITY is allowed)", what, (double)p->distance);
   OI_REQUIRE(p->hit_points && p->grad && p->offset && p->elem && p->pixel && p->position && p->normal && p->w2b &&
                  (p->ambient || (p->lights && p->radius)),
@@ -278,8 +268,7 @@ int oi_scene_occlusion_begin(const oi_trace_batch* sb, const oi_scene_occlusion_
 int oi_trace_batch_step_anyhit(const oi_trace_batch* b, const float* sdf, long long bound, int k, float tol, float omega,
                                oi_stream_t stream) {
   const char* what = "oi_trace_batch_step_anyhit";
-  int rc = check_batch(b, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_batch(b, what));
   OI_REQUIRE(k >= 0 && k < OI_TRACE_MAX_STEPS, "%s: step k=%d (0 <= k < %d)", what, k, OI_TRACE_MAX_STEPS);
   OI_REQUIRE(bound >= 0 && bound <= b->s.N, "%s: bound=%lld (0 <= bound <= N=%lld)", what, bound, b->s.N);
   OI_REQUIRE(tol > 0.f && omega > 0.f && tol < INFINITY && omega < INFINITY, "%s: tol %g, omega %g (both > 0, finite)", what,
@@ -295,10 +284,8 @@ int oi_scene_occlusion_resolve(const uint8_t* status, const int* owner, const in
                                const int* offset, int E, long long N, int L, int S, int j0, int Sc, long long n_vis,
                                int scene_S, int last, int* count, float* out, oi_stream_t stream) {
   const char* what = "oi_scene_occlusion_resolve";
-  int rc = check_chunk(what, L, S, j0, Sc);
-  if (rc != OI_OK) return rc;
-  rc = check_resolve(what, E, N, L, Sc, n_vis, scene_S);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_chunk(what, L, S, j0, Sc));
+  OI_TRY(check_resolve(what, E, N, L, Sc, n_vis, scene_S));
   OI_REQUIRE(status && owner && owner_ray && vis_slot && offset && count && (out || !last), "%s: null pointer", what);
   const long long M = (long long)scene_S * scene_S;
   hipLaunchKernelGGL(scene_occlusion_resolve_kernel, dim3(n_blocks(M * L)), dim3(TR_THREADS), 0, oi::as_stream(stream), status, owner,
@@ -310,10 +297,8 @@ int oi_scene_transfer_resolve(const uint8_t* status, const float* rays_d, const 
                               const int* vis_slot, const int* offset, const float* w2b, int E, long long N, int S, int j0,
                               int Sc, long long n_vis, int scene_S, int last, float* transfer, oi_stream_t stream) {
   const char* what = "oi_scene_transfer_resolve";
-  int rc = check_chunk(what, 1, S, j0, Sc);
-  if (rc != OI_OK) return rc;
-  rc = check_resolve(what, E, N, 1, Sc, n_vis, scene_S);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_chunk(what, 1, S, j0, Sc));
+  OI_TRY(check_resolve(what, E, N, 1, Sc, n_vis, scene_S));
   OI_REQUIRE(status && rays_d && owner && owner_ray && vis_slot && offset && w2b && transfer, "%s: null pointer", what);
   const long long M = (long long)scene_S * scene_S;
   hipLaunchKernelGGL(scene_transfer_resolve_kernel, dim3(n_blocks(M)), dim3(TR_THREADS), 0, oi::as_stream(stream), status, rays_d,
@@ -324,11 +309,9 @@ int oi_scene_transfer_resolve(const uint8_t* status, const float* rays_d, const 
 int oi_scene_transfer_normal(const float* grad, long long n_pad, const int* owner, const int* owner_ray, const int* vis_slot,
                              const float* w2b, int E, long long N, int scene_S, float* transfer, oi_stream_t stream) {
   const char* what = "oi_scene_transfer_normal";
-  OI_REQUIRE(E >= 1 && E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, E, OI_TRACE_BATCH_MAX_ELEMS);
-  OI_REQUIRE(N >= 1 && E * N < (1ll << 31), "%s: E=%d x N=%lld rays (N >= 1, E * N < 2^31)", what, E, N);
+  OI_TRY(check_scene_rays(what, E, N));
   OI_REQUIRE(n_pad >= 1 && n_pad <= N, "%s: n_pad=%lld (1 <= n_pad <= N=%lld)", what, n_pad, N);
-  OI_REQUIRE(scene_S >= 1 && scene_S <= OI_SCENE_MAX_RESOLUTION, "%s: scene S=%d (1 .. %d)", what, scene_S,
-             OI_SCENE_MAX_RESOLUTION);
+  OI_TRY(check_resolution(what, "scene S", scene_S));
   OI_REQUIRE(grad && owner && owner_ray && vis_slot && w2b && transfer, "%s: null pointer", what);
   const long long M = (long long)scene_S * scene_S;
   hipLaunchKernelGGL(scene_transfer_normal_kernel, dim3(n_blocks(M)), dim3(TR_THREADS), 0, oi::as_stream(stream), grad, n_pad, owner,
@@ -339,8 +322,7 @@ int oi_scene_transfer_normal(const float* grad, long long n_pad, const int* owne
 int oi_scene_shade_ao(const oi_scene_shade_ao_params* p, oi_stream_t stream) {
   const char* what = "oi_scene_shade_ao";
   OI_REQUIRE(p != nullptr, "%s: null params", what);
-  int rc = check_scene_shade(&p->s, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_scene_shade(&p->s, what));
   hipLaunchKernelGGL(scene_shade_ao_kernel, dim3(n_blocks((long long)p->s.S * p->s.S)), dim3(TR_THREADS), 0, oi::as_stream(stream),
                      *p);
   return oi::check_launch(what);

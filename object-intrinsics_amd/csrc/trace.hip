@@ -7,8 +7,9 @@
 //   shadow_begin   one shadow ray per (light, hit) facing the light, offset along the normal, compacted like a step
 //   visibility     shadow-ray states -> the (L, N) visibility map
 //   shade          G-buffer (depth, position, normals, albedo, mask) and the Phong image under L lights
-// The per-ray work of begin, step and finish, the compaction and the shading live in trace_common.h, which occlusion.hip and
-// trace_batch.hip share.
+// The per-ray work of begin, step and finish, the compaction, the state a begin kernel writes (write_ray, enter_rays), the
+// lit share that visibility is at S = 1, the shading and the shared argument checks live in trace_common.h, which
+// occlusion.hip, trace_batch.hip, envgloss.hip and the scene sources share.
 // Compaction inside a workgroup: one 64-bit ballot per wave (popcount on the lower lanes) and an LDS scan over the waves,
 // as mesh.hip; across workgroups one integer atomicAdd per workgroup on the step's counter.  No float atomics, no scratch.
 #include "trace_common.h"
@@ -31,38 +32,19 @@ __global__ void __launch_bounds__(TR_THREADS) trace_shadow_begin_kernel(const oi
                                                                         const float* __restrict__ w2b, float bias) {
   __shared__ unsigned lds[TR_WAVES + 1];
   const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  bool traced = false;
-  float ox = 0.f, oy = 0.f, oz = 0.f;
+  ShadowRay ry = {};
   if (q < s.N) {
     const long long l = q / n_hit, i = q - l * n_hit;
-    const ShadowRay ry = shadow_ray(hit_points, grad, i, lights + l * OI_RELIGHT_LIGHT_FLOATS, w2b, bias);
-    traced = ry.traced;
-    ox = ry.o[0], oy = ry.o[1], oz = ry.o[2];
-    s.rays_o[q * 3 + 0] = ox, s.rays_o[q * 3 + 1] = oy, s.rays_o[q * 3 + 2] = oz;
-    s.rays_d[q * 3 + 0] = ry.l[0], s.rays_d[q * 3 + 1] = ry.l[1], s.rays_d[q * 3 + 2] = ry.l[2];
-    s.near_[q] = 0.f;
-    s.far_[q] = ry.far_;
-    s.t[q] = 0.f;
-    s.status[q] = traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING;
-    s.steps[q] = 0;
-    s.side[q] = 0;
-    s.bracket[q * 4 + 0] = s.bracket[q * 4 + 1] = s.bracket[q * 4 + 2] = s.bracket[q * 4 + 3] = 0.f;
+    ry = shadow_ray(hit_points, grad, i, lights + l * OI_RELIGHT_LIGHT_FLOATS, w2b, bias);
+    write_ray(s, q, ry.o, ry.l, 0.f, ry.far_, ry.traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING);
   }
-  const long long slot = wg_slot(traced, s.counts, lds);
-  if (traced) {
-    s.active[slot] = (int)q;
-    s.points[slot * 3 + 0] = ox, s.points[slot * 3 + 1] = oy, s.points[slot * 3 + 2] = oz;  // o + 0 d
-  }
+  enter_rays(s, q, ry.traced, ry.o[0], ry.o[1], ry.o[2], lds);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) trace_visibility_kernel(const uint8_t* __restrict__ status,
                                                                       const int* __restrict__ hit_slot, long long N,
                                                                       long long n_hit, int L, float* __restrict__ vis) {
-  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  if (i >= N * L) return;
-  const long long l = i / N, px = i - l * N;
-  const int slot = hit_slot[px];
-  vis[i] = slot < 0 ? 1.0f : (status[l * n_hit + slot] == OI_TRACE_MISS ? 1.0f : 0.0f);
+  lit_share(status, hit_slot, N, n_hit, L, 1, vis);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) surface_shade_kernel(const oi_surface_params p) { surface_shade_pixel(p, nullptr); }
@@ -72,8 +54,7 @@ __global__ void __launch_bounds__(TR_THREADS) surface_shade_kernel(const oi_surf
 extern "C" {
 
 int oi_trace_begin(const oi_trace_state* s, oi_stream_t stream) {
-  int rc = check_state(s, "oi_trace_begin");
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_state(s, "oi_trace_begin"));
   hipLaunchKernelGGL(trace_begin_kernel, dim3(n_blocks(s->N)), dim3(TR_THREADS), 0, oi::as_stream(stream), *s);
   return oi::check_launch("oi_trace_begin");
 }
@@ -84,8 +65,7 @@ int oi_trace_step(const oi_trace_state* s, const float* sdf, long long bound, in
 }
 
 int oi_trace_finish(const oi_trace_state* s, int* hit_index, float* hit_points, int* hit_slot, oi_stream_t stream) {
-  int rc = check_state(s, "oi_trace_finish");
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_state(s, "oi_trace_finish"));
   OI_REQUIRE(hit_index && hit_points && hit_slot, "oi_trace_finish: null output pointer");
   hipLaunchKernelGGL(trace_finish_kernel, dim3(n_blocks(s->N)), dim3(TR_THREADS), 0, oi::as_stream(stream), *s, hit_index,
                      hit_points, hit_slot);
@@ -94,24 +74,19 @@ int oi_trace_finish(const oi_trace_state* s, int* hit_index, float* hit_points, 
 
 int oi_trace_shadow_begin(const oi_trace_state* s, const float* hit_points, const float* grad, long long n_hit,
                           const float* lights, int L, const float* w2b, float bias, oi_stream_t stream) {
-  int rc = check_state(s, "oi_trace_shadow_begin");
-  if (rc != OI_OK) return rc;
-  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "oi_trace_shadow_begin: L=%d (1 .. %d lights)", L, OI_RELIGHT_MAX_LIGHTS);
-  OI_REQUIRE(n_hit >= 1 && n_hit * L == s->N, "oi_trace_shadow_begin: n_hit=%lld, L=%d, N=%lld (N must be L * n_hit)", n_hit, L,
-             s->N);
-  OI_REQUIRE(bias >= 0.f && bias < INFINITY, "oi_trace_shadow_begin: bias %g (>= 0, finite)", (double)bias);
-  OI_REQUIRE(hit_points && grad && lights && w2b, "oi_trace_shadow_begin: null input pointer");
-  const hipStream_t st = oi::as_stream(stream);
-  hipLaunchKernelGGL(trace_clear_counts_kernel, dim3(1), dim3(TR_THREADS), 0, st, s->counts);
-  hipLaunchKernelGGL(trace_shadow_begin_kernel, dim3(n_blocks(s->N)), dim3(TR_THREADS), 0, st, *s, hit_points, grad, n_hit, lights,
-                     w2b, bias);
-  return oi::check_launch("oi_trace_shadow_begin");
+  const char* what = "oi_trace_shadow_begin";
+  OI_TRY(check_state(s, what));
+  OI_TRY(check_lights(what, L));
+  OI_REQUIRE(n_hit >= 1 && n_hit * L == s->N, "%s: n_hit=%lld, L=%d, N=%lld (N must be L * n_hit)", what, n_hit, L, s->N);
+  OI_TRY(check_bias(what, bias));
+  OI_REQUIRE(hit_points && grad && lights && w2b, "%s: null input pointer", what);
+  return launch_begin(what, s, stream, trace_shadow_begin_kernel, hit_points, grad, n_hit, lights, w2b, bias);
 }
 
 int oi_trace_visibility(const uint8_t* shadow_status, const int* hit_slot, long long N, long long n_hit, int L,
                         float* visibility, oi_stream_t stream) {
-  OI_REQUIRE(N >= 1 && N < (1ll << 31) && n_hit >= 0 && n_hit <= N, "oi_trace_visibility: N=%lld, n_hit=%lld", N, n_hit);
-  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "oi_trace_visibility: L=%d (1 .. %d lights)", L, OI_RELIGHT_MAX_LIGHTS);
+  OI_TRY(check_pixels("oi_trace_visibility", N, n_hit));
+  OI_TRY(check_lights("oi_trace_visibility", L));
   OI_REQUIRE(hit_slot && visibility && (shadow_status || n_hit == 0), "oi_trace_visibility: null pointer");
   hipLaunchKernelGGL(trace_visibility_kernel, dim3(n_blocks(N * L)), dim3(TR_THREADS), 0, oi::as_stream(stream), shadow_status,
                      hit_slot, N, n_hit, L, visibility);
@@ -119,8 +94,7 @@ int oi_trace_visibility(const uint8_t* shadow_status, const int* hit_slot, long 
 }
 
 int oi_surface_shade(const oi_surface_params* p, oi_stream_t stream) {
-  int rc = check_surface("oi_surface_shade", p);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_surface("oi_surface_shade", p));
   hipLaunchKernelGGL(surface_shade_kernel, dim3(n_blocks(p->N)), dim3(TR_THREADS), 0, oi::as_stream(stream), *p);
   return oi::check_launch("oi_surface_shade");
 }

@@ -1,15 +1,18 @@
-// What trace.hip, occlusion.hip, trace_batch.hip, envlight.hip, scene.hip, scene_light.hip and envbounce.hip share
+// What trace.hip, occlusion.hip, trace_batch.hip, envlight.hip, envgloss.hip, scene.hip, scene_light.hip and envbounce.hip share
 // (include/oi_trace.h, include/oi_occlusion.h, include/oi_trace_batch.h, include/oi_envlight.h, include/oi_scene.h,
-// include/oi_scene_light.h, include/oi_envbounce.h; DESIGN sections 4.13, 4.16 - 4.19, 4.21 and 4.22): the workgroup compaction, the ray
-// state machine (the full one and its any-hit form, one template), the sample numbers and directions of the secondary rays
-// (occlusion.hip, envgloss.hip), the SH basis and the closed-form transfer of a normal, the shadow ray of a surface point and
-// the per-pixel shading.  (The environment shade's pixel is env_shade_common.h's; the unit normal, the view vector, the
-// light's direction and the Phong geometry are shade_common.h's, shared with the compositing kernels.)
+// include/oi_scene_light.h, include/oi_envbounce.h; DESIGN sections 4.13, 4.16 - 4.22): the workgroup compaction, the state of
+// a ray that starts (write_ray) and the compaction of the started rays (enter_rays): every begin kernel's, the ray state
+// machine (the full one and its any-hit form, one template), the offset origin, the sample numbers and directions of the
+// secondary rays (occlusion.hip, envgloss.hip), the lit share of a pixel's rays, the SH basis and the closed-form transfer of a
+// normal, the shadow ray of a surface point, the per-pixel shading, and the argument checks the C entries repeat (check_*).
+// (The environment shade's pixel is env_shade_common.h's; the unit normal, the view vector, the light's direction and the
+// Phong geometry are shade_common.h's, shared with the compositing kernels.)
 // Everything here has internal linkage; each source file instantiates what it exports.
 #ifndef OI_TRACE_COMMON_H_
 #define OI_TRACE_COMMON_H_
 
 #include "shade_common.h"
+#include "../../include/oi_occlusion.h"
 #include "../../include/oi_trace_batch.h"
 
 namespace {
@@ -28,6 +31,14 @@ __device__ __forceinline__ void point_at(const float* __restrict__ o, const floa
   dst[0] = __fmaf_rn(t, d[r * 3 + 0], o[r * 3 + 0]);
   dst[1] = __fmaf_rn(t, d[r * 3 + 1], o[r * 3 + 1]);
   dst[2] = __fmaf_rn(t, d[r * 3 + 2], o[r * 3 + 2]);
+}
+
+// p + bias n: the origin of a secondary ray, off the surface along the normal (the owner's frame or the world's)
+__device__ __forceinline__ void offset_origin(const float* __restrict__ p, float bias, float nx, float ny, float nz, float& ox, float& oy,
+                                              float& oz) {
+  ox = __fmaf_rn(bias, nx, p[0]);
+  oy = __fmaf_rn(bias, ny, p[1]);
+  oz = __fmaf_rn(bias, nz, p[2]);
 }
 
 // Dense output slot of this thread (meaningful where `keep`), the workgroup's kept threads in thread order behind
@@ -81,6 +92,41 @@ __device__ __forceinline__ void clear_counts(int* counts, int first) {
 }
 
 __global__ void __launch_bounds__(TR_THREADS) trace_clear_counts_kernel(int* counts) { clear_counts(counts, 0); }
+
+// ray r of v starts at near_: what every begin kernel writes besides the ray itself
+__device__ __forceinline__ void restart_ray(const oi_trace_state& v, long long r, float near_, unsigned status) {
+  v.t[r] = near_;
+  v.status[r] = (uint8_t)status;
+  v.steps[r] = 0;
+  v.side[r] = 0;
+  v.bracket[r * 4 + 0] = near_;
+  v.bracket[r * 4 + 1] = 0.f;
+  v.bracket[r * 4 + 2] = near_;
+  v.bracket[r * 4 + 3] = 0.f;
+}
+
+// ray r of v, whole: (o, d) on near_ .. far_, started (MARCH) or ended before its first sample (0 .. 0 and a final status)
+__device__ __forceinline__ void write_ray(const oi_trace_state& v, long long r, const float* o, const float* d, float near_,
+                                          float far_, unsigned status) {
+  v.rays_o[r * 3 + 0] = o[0], v.rays_o[r * 3 + 1] = o[1], v.rays_o[r * 3 + 2] = o[2];  // (each triple on its own: one 12-byte store)
+  v.rays_d[r * 3 + 0] = d[0], v.rays_d[r * 3 + 1] = d[1], v.rays_d[r * 3 + 2] = d[2];
+  v.near_[r] = near_;
+  v.far_[r] = far_;
+  restart_ray(v, r, near_, status);
+}
+
+// The started rays of this workgroup, compacted behind v's counter: the active list and the first sample points.  Every
+// thread of the workgroup calls it; live: wg_slot's.  (px, py, pz): ray r's point at near_, values the caller holds in
+// registers -- the origin itself where near_ is 0 (o + 0 d would lose the sign of a zero and turn a non-finite d into NaN),
+// point_at's fmaf of the values it has just written otherwise.
+__device__ __forceinline__ void enter_rays(const oi_trace_state& v, long long r, bool entered, float px, float py, float pz,
+                                           unsigned* lds, int* live = nullptr) {
+  const long long slot = wg_slot(entered, v.counts, lds, live);
+  if (entered) {
+    v.active[slot] = (int)r;
+    v.points[slot * 3 + 0] = px, v.points[slot * 3 + 1] = py, v.points[slot * 3 + 2] = pz;
+  }
+}
 
 // One step of the ray state machine on the sdf of the last MLP pass, and the compaction of the rays still in flight.
 // ANYHIT = false: oi_trace_step (march, bracket, Illinois regula falsi).  ANYHIT = true: oi_occlusion_step, whose MARCH
@@ -183,15 +229,8 @@ __device__ __forceinline__ void trace_begin_rays(const oi_trace_state& s) {
   clear_counts(s.counts, (int)s.N);
   const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
   if (r >= s.N) return;
-  const float t = s.near_[r];
-  s.t[r] = t;
-  s.status[r] = OI_TRACE_MARCH;
-  s.steps[r] = 0;
-  s.side[r] = 0;
-  s.bracket[r * 4 + 0] = t;
-  s.bracket[r * 4 + 1] = 0.f;
-  s.bracket[r * 4 + 2] = t;
-  s.bracket[r * 4 + 3] = 0.f;
+  const float t = s.near_[r];  // (the caller's rays: nothing but restart_ray's part of write_ray is stored, and nothing is compacted)
+  restart_ray(s, r, t, OI_TRACE_MARCH);
   s.active[r] = (int)r;
   point_at(s.rays_o, s.rays_d, r, t, s.points + r * 3);
 }
@@ -296,7 +335,7 @@ __device__ __forceinline__ void sh9(float x, float y, float z, float* __restrict
   o[8] = 0.5462742152960396f * (x * x - y * y);
 }
 
-// v = w2b[:3,:3]^T d (surface_shade_pixel's rotation of the normal)
+// v = w2b[:3,:3]^T d: a box-frame direction in the world (scene_light.hip's rotate_t is this with contraction off)
 __device__ __forceinline__ void to_world(const float* __restrict__ Wb, float dx, float dy, float dz, float& x, float& y, float& z) {
   x = Wb[0] * dx + Wb[4] * dy + Wb[8] * dz;
   y = Wb[1] * dx + Wb[5] * dy + Wb[9] * dz;
@@ -333,11 +372,27 @@ __device__ __forceinline__ ShadowRay shadow_ray(const float* __restrict__ hit_po
   float nx, ny, nz;
   unit_normal(grad, i, nx, ny, nz);
   r.traced = nx * r.l[0] + ny * r.l[1] + nz * r.l[2] > 0.f;
-  r.o[0] = __fmaf_rn(bias, nx, hit_points[i * 3 + 0]);
-  r.o[1] = __fmaf_rn(bias, ny, hit_points[i * 3 + 1]);
-  r.o[2] = __fmaf_rn(bias, nz, hit_points[i * 3 + 2]);
+  offset_origin(hit_points + i * 3, bias, nx, ny, nz, r.o[0], r.o[1], r.o[2]);
   r.far_ = unit_sphere_exit(r.o[0], r.o[1], r.o[2], r.l[0], r.l[1], r.l[2]);
   return r;
+}
+
+// Value i of the (L, N) map of oi_occlusion_resolve: the share of pixel i % N's S rays under light i / N that ended MISS, 1
+// off the surface.  oi_trace_visibility's map is this at S = 1.
+__device__ __forceinline__ void lit_share(const uint8_t* __restrict__ status, const int* __restrict__ hit_slot, long long N,
+                                          long long n_hit, int L, int S, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  if (i >= N * L) return;
+  const long long l = i / N, px = i - l * N;
+  const int slot = hit_slot[px];
+  if (slot < 0) {
+    out[i] = 1.0f;
+    return;
+  }
+  const uint8_t* __restrict__ st = status + l * S * n_hit + slot;
+  int lit = 0;
+  for (int j = 0; j < S; ++j) lit += st[(long long)j * n_hit] == OI_TRACE_MISS ? 1 : 0;
+  out[i] = (float)lit / (float)S;
 }
 
 // One pixel of the G-buffer and of the Phong image.  P: oi_surface_params or a struct with the same fields; ao: ambient occlusion
@@ -355,11 +410,8 @@ __device__ __forceinline__ void surface_shade_at(const P& p, const float* __rest
     const long long k = p.hit_slot[r];
     unit_normal(p.grad, k, n[0], n[1], n[2]);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      pos[a] = p.hit_points[k * 3 + a];
-      alb[a] = p.rgb[k * 3 + a];
-      nw[a] = Wb[0 + a] * n[0] + Wb[4 + a] * n[1] + Wb[8 + a] * n[2];  // w2b[:3,:3]^T n
-    }
+    for (int a = 0; a < 3; ++a) pos[a] = p.hit_points[k * 3 + a], alb[a] = p.rgb[k * 3 + a];
+    to_world(Wb, n[0], n[1], n[2], nw[0], nw[1], nw[2]);
     unit_view(p.rays_o[r * 3 + 0], p.rays_o[r * 3 + 1], p.rays_o[r * 3 + 2], pos[0], pos[1], pos[2], vx, vy, vz);
   }
   if (p.depth) p.depth[q] = hit ? p.t[r] : __uint_as_float(0x7fc00000u);
@@ -409,6 +461,41 @@ __device__ __forceinline__ void surface_shade_pixel(const P& p, const float* __r
 
 inline unsigned n_blocks(long long n) { return (unsigned)((n + TR_THREADS - 1) / TR_THREADS); }
 
+// a check's refusal is the entry's
+#define OI_TRY(call)                  \
+  do {                                \
+    const int rc_ = (call);           \
+    if (rc_ != OI_OK) return rc_;     \
+  } while (0)
+
+// The conditions several entries refuse in the same words; `what` is the entry's name.
+inline int check_lights(const char* what, int L) {
+  OI_REQUIRE(L >= 1 && L <= OI_RELIGHT_MAX_LIGHTS, "%s: L=%d (1 .. %d lights)", what, L, OI_RELIGHT_MAX_LIGHTS);
+  return OI_OK;
+}
+inline int check_samples(const char* what, int S) {
+  OI_REQUIRE(S >= 1 && S <= OI_OCCLUSION_MAX_SAMPLES, "%s: S=%d (1 .. %d samples)", what, S, OI_OCCLUSION_MAX_SAMPLES);
+  return OI_OK;
+}
+inline int check_bias(const char* what, float bias) {
+  OI_REQUIRE(bias >= 0.f && bias < INFINITY, "%s: bias %g (>= 0, finite)", what, (double)bias);
+  return OI_OK;
+}
+inline int check_pixels(const char* what, long long N, long long n_hit) {
+  OI_REQUIRE(N >= 1 && N < (1ll << 31) && n_hit >= 0 && n_hit <= N, "%s: N=%lld, n_hit=%lld", what, N, n_hit);
+  return OI_OK;
+}
+inline int check_elements(const char* what, int E) {
+  OI_REQUIRE(E >= 1 && E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, E, OI_TRACE_BATCH_MAX_ELEMS);
+  return OI_OK;
+}
+// a scene's elements and rays per element as plain numbers
+inline int check_scene_rays(const char* what, int E, long long N) {
+  OI_TRY(check_elements(what, E));
+  OI_REQUIRE(N >= 1 && E * N < (1ll << 31), "%s: E=%d x N=%lld rays (N >= 1, E * N < 2^31)", what, E, N);
+  return OI_OK;
+}
+
 inline int check_state(const oi_trace_state* s, const char* what) {
   OI_REQUIRE(s != nullptr, "%s: null state", what);
   OI_REQUIRE(s->N >= 1 && s->N < (1ll << 31), "%s: N=%lld rays (1 <= N < 2^31)", what, s->N);
@@ -420,9 +507,8 @@ inline int check_state(const oi_trace_state* s, const char* what) {
 
 inline int check_batch(const oi_trace_batch* b, const char* what) {
   OI_REQUIRE(b != nullptr, "%s: null batch", what);
-  OI_REQUIRE(b->E >= 1 && b->E <= OI_TRACE_BATCH_MAX_ELEMS, "%s: E=%d elements (1 .. %d)", what, b->E, OI_TRACE_BATCH_MAX_ELEMS);
-  int rc = check_state(&b->s, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_elements(what, b->E));
+  OI_TRY(check_state(&b->s, what));
   OI_REQUIRE((long long)b->E * b->s.N < (1ll << 31), "%s: E=%d x N=%lld rays (E * N < 2^31)", what, b->E, b->s.N);
   OI_REQUIRE(b->live != nullptr, "%s: null live", what);
   return OI_OK;
@@ -432,8 +518,7 @@ inline int check_batch(const oi_trace_batch* b, const char* what) {
 template <bool ANYHIT>
 inline int launch_step(const char* what, const oi_trace_state* s, const float* sdf, long long bound, int k, float tol,
                        float omega, oi_stream_t stream) {
-  int rc = check_state(s, what);
-  if (rc != OI_OK) return rc;
+  OI_TRY(check_state(s, what));
   OI_REQUIRE(k >= 0 && k < OI_TRACE_MAX_STEPS, "%s: step k=%d (0 <= k < %d)", what, k, OI_TRACE_MAX_STEPS);
   OI_REQUIRE(bound >= 0 && bound <= s->N, "%s: bound=%lld (0 <= bound <= N=%lld)", what, bound, s->N);
   OI_REQUIRE(tol > 0.f && omega > 0.f && tol < INFINITY && omega < INFINITY, "%s: tol %g, omega %g (both > 0, finite)", what,
@@ -445,11 +530,20 @@ inline int launch_step(const char* what, const oi_trace_state* s, const float* s
   return oi::check_launch(what);
 }
 
+// The counters cleared, then a begin kernel on one thread per ray of s: the two launches of every single-view secondary begin.
+template <class K, class... A>
+inline int launch_begin(const char* what, const oi_trace_state* s, oi_stream_t stream, K kernel, A... args) {
+  const hipStream_t st = oi::as_stream(stream);
+  hipLaunchKernelGGL(trace_clear_counts_kernel, dim3(1), dim3(TR_THREADS), 0, st, s->counts);
+  hipLaunchKernelGGL(kernel, dim3(n_blocks(s->N)), dim3(TR_THREADS), 0, st, *s, args...);
+  return oi::check_launch(what);
+}
+
 // Arguments of oi_surface_shade and oi_surface_shade_ao (P: oi_surface_params or a struct with the same fields).
 template <class P>
 inline int check_surface(const char* what, const P* p) {
   OI_REQUIRE(p != nullptr, "%s: null params", what);
-  OI_REQUIRE(p->N >= 1 && p->N < (1ll << 31) && p->n_hit >= 0 && p->n_hit <= p->N, "%s: N=%lld, n_hit=%lld", what, p->N, p->n_hit);
+  OI_TRY(check_pixels(what, p->N, p->n_hit));
   OI_REQUIRE(p->image ? (p->L >= 1 && p->L <= OI_RELIGHT_MAX_LIGHTS && p->lights) : p->L >= 0,
              "%s: L=%d (1 .. %d lights with an image)", what, p->L, OI_RELIGHT_MAX_LIGHTS);
   OI_REQUIRE(p->rays_o && p->rays_d && p->t && p->status && p->hit_slot && p->w2b, "%s: null input pointer", what);

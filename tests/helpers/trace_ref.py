@@ -169,6 +169,21 @@ def shadow_rays(points, grad, l, bias=BIAS):
     return o, far, (n @ l) > 0
 
 
+def assert_secondary_begin_state(arr):
+    """What oi_trace_shadow_begin and the oi_occlusion_*_begin entries leave in a state (arr: its arrays as torch tensors), read
+    before the first step: the first sample point of every compacted ray is its origin bit for bit (o, not o + 0 d, which
+    would lose the sign of a zero), bracket and side of every ray are zero bits, and t == near == 0."""
+    bits = lambda t_: t_.detach().cpu().contiguous().numpy().view({1: np.uint8, 2: np.uint16, 4: np.uint32}[t_.element_size()])
+    n0 = int(arr["counts"][0].item())
+    assert 0 <= n0 <= arr["status"].numel()
+    active = arr["active"].reshape(2, -1)[0, :n0].cpu().numpy().astype(np.int64)
+    assert active.size == 0 or (active.min() >= 0 and active.max() < arr["status"].numel())
+    assert np.array_equal(bits(arr["points"].reshape(-1, 3)[:n0]), bits(arr["rays_o"].reshape(-1, 3))[active]), "points != rays_o[active]"
+    assert not bits(arr["bracket"]).any(), "bracket"
+    assert not bits(arr["side"]).any(), "side"
+    assert bool((arr["t"] == 0).all()) and bool((arr["near_"] == 0).all()), "t, near"
+
+
 def visibility_of(status):
     """1 for a shadow ray that ended MISS, 0 for every other state."""
     return (np.asarray(status) == MISS).astype(np.float64)

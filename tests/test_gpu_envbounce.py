@@ -292,6 +292,7 @@ def test_analytic_bounce_under_the_blocker():
     for tag in ("any", "closest"):
         arr, St = GE._guarded_state(S * n_hit, tag)
         assert L.oi_occlusion_ambient_begin(ctypes.byref(St), _p(hp), _p(grad), _p(hit_index), n_hit, S, T.BIAS, 4.0, R.SEED, st) == 0
+        T.assert_secondary_begin_state(arr)
         states.append((arr, St))
     (arr_a, St_a), (arr_c, St_c) = states
     assert torch.equal(_bits(arr_a["rays_d"]), _bits(arr_c["rays_d"])) and torch.equal(_bits(arr_a["rays_o"]), _bits(arr_c["rays_o"]))

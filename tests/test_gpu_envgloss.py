@@ -174,6 +174,7 @@ def test_lobe_begin(n_hit, S, s):
     for name in ("near_", "t", "bracket"):
         assert not arr[name].any(), name
     assert not arr["side"].any() and not arr["steps"].any()
+    T.assert_secondary_begin_state(arr)
     # a second launch: the same bytes; and through the wrapper
     arr2, St2 = V._guarded_state(Qn, "lobe2")
     assert L.oi_occlusion_lobe_begin(ctypes.byref(St2), _p(ro), _p(hp), _p(g_t), _p(hi), n_hit, S, float(s), bias, seed, st) == 0
@@ -206,6 +207,7 @@ def test_analytic_lobe_visibility():
     ro, hi = guarded_copy(_cuda(eyes), "rays_o"), guarded_copy(_cuda(pix, torch.int32), "hit_index")
     arr, St = V._guarded_state(S * n_hit, "lobe")
     assert L.oi_occlusion_lobe_begin(ctypes.byref(St), _p(ro), _p(hp), _p(g_t), _p(hi), n_hit, S, s, bias, R.SEED, st) == 0
+    T.assert_secondary_begin_state(arr)
     steps = V._anyhit_loop(arr, St, V._two_spheres, 256)
     status = arr["status"].cpu().numpy().reshape(S, n_hit)
     assert status.max() <= T.BACKFACING

@@ -424,6 +424,7 @@ def test_analytic_blocked_cap():
     arr, St = _guarded_state(S * n_hit, "env")
     assert L.oi_occlusion_ambient_begin(ctypes.byref(St), _p(hp), _p(grad), _p(hit_index), n_hit, S, T.BIAS, 4.0, R.SEED, st) == 0
     assert int(arr["counts"][0].item()) == S * n_hit
+    T.assert_secondary_begin_state(arr)
     steps = _anyhit_loop(arr, St, _two_spheres, 256)
     status = arr["status"].cpu().numpy().reshape(S, n_hit)
     assert status.max() <= T.NONFINITE and (status[:, 3] == T.MISS).all()         # the equator sees nothing

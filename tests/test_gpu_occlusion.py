@@ -313,6 +313,7 @@ def test_analytic_occluder_penumbra():
     arr, St = _guarded_state(S * n_hit, "an")
     assert _light_begin(St, hp, grad, hit_index, n_hit, lts, radius, 1, S, w2b, R.SEED) == 0
     assert int(arr["counts"][0].item()) == S * n_hit                               # every sample faces the light
+    T.assert_secondary_begin_state(arr)
     k = _anyhit_loop(arr, St, _two_spheres, 256)
     # the oracle: the restatement's rays through the fp64 machine
     o, d, far, traced = R.light_rays(npd(hp), npd(grad), pix, np.array(R.ANALYTIC_AXIS), R.ANALYTIC_RADIUS, S, R.SEED)
@@ -349,6 +350,7 @@ def test_analytic_ambient_occlusion():
     assert lib.load().oi_occlusion_ambient_begin(ctypes.byref(St), _p(hp), _p(grad), _p(hit_index), n_hit, S, T.BIAS, 0.5, R.SEED,
                                                  ops._stream()) == 0
     assert int(arr["counts"][0].item()) == S * n_hit
+    T.assert_secondary_begin_state(arr)
     o, d, far, _ = R.ambient_rays(pts, pts / R.R0, pix, S, R.SEED, distance=0.5)
     assert np.abs(npd(arr["rays_d"]).reshape(S, n_hit, 3) - d).max() < RAY_BAR and np.abs(npd(arr["far_"]).reshape(S, n_hit) - far).max() < FAR_BAR
     _anyhit_loop(arr, St, _two_spheres, 256)
@@ -382,6 +384,7 @@ def _shape_case(n_hit, S, L, seed, backfacing=False):
     for rep in range(2):
         arr, St = _guarded_state(L * S * n_hit, f"sh{rep}")
         assert _light_begin(St, hp, grad, hit_index, n_hit, lts, radius, L, S, w2b, seed) == 0
+        T.assert_secondary_begin_state(arr)
         s0 = arr["status"].cpu().numpy()
         assert set(np.unique(s0)) <= {T.MARCH, T.BACKFACING} and int(arr["counts"][0].item()) == int((s0 == T.MARCH).sum())
         assert not bool(arr["counts"][1:].any())
@@ -392,6 +395,7 @@ def _shape_case(n_hit, S, L, seed, backfacing=False):
         assert lib.load().oi_occlusion_ambient_begin(ctypes.byref(Sa), _p(hp), _p(grad), _p(hit_index), n_hit, S, T.BIAS, 0.3, seed,
                                                      ops._stream()) == 0
         assert int(amb["counts"][0].item()) == S * n_hit and bool((amb["status"] == T.MARCH).all())
+        T.assert_secondary_begin_state(amb)
         _anyhit_loop(amb, Sa, _two_spheres, T.MAX_STEPS, stale=rep == 1)
         ao = _resolve(amb["status"], slot, N, n_hit, 1, S)
         runs.append(dict(arr=arr, vis=vis, k=k, s0=s0, amb=amb, ao=ao))

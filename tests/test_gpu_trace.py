@@ -399,6 +399,7 @@ def _guarded_pass(N, seed):
     for k_, v_ in sh.items():
         setattr(S2, k_, p(v_))
     assert L_.oi_trace_shadow_begin(ctypes.byref(S2), p(hp), p(grad), n_hit, p(lts), Lt, p(w2b), T.BIAS, st) == 0
+    T.assert_secondary_begin_state(sh)
     bound, k = int(sh["counts"][0].item()), 0
     s0 = sh["status"].cpu().numpy()
     assert bound == int((s0 == T.MARCH).sum()) and set(np.unique(s0)) <= {T.MARCH, T.BACKFACING}

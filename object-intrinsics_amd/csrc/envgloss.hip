@@ -124,13 +124,8 @@ __global__ void __launch_bounds__(TR_THREADS) occlusion_lobe_begin_kernel(const 
     const long long pix = hit_index[i];
     float n[3], a[3];
     reflect_view(grad, hit_points, i, rays_o + pix * 3, n, a);
-    float u1, u2;
-    sample_numbers((unsigned)pix, seed, (unsigned)j, S, u1, u2);
-    const float e = logf(u1) * inv_s1;  // log(cos alpha)
-    const float ca = expf(e), sa = sqrtf(fmaxf(-expm1f(2.0f * e), 0.f));
     float dx, dy, dz;
-    direction_about(a[0], a[1], a[2], sa, ca, u2, dx, dy, dz);
-    traced = n[0] * dx + n[1] * dy + n[2] * dz > 0.f;
+    traced = lobe_direction(n, a, (unsigned)pix, seed, (unsigned)j, S, inv_s1, dx, dy, dz);
     offset_origin(hit_points + i * 3, bias, n[0], n[1], n[2], ox, oy, oz);
     const float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz};
     write_ray(s, q, o, d, 0.f, unit_sphere_exit(ox, oy, oz, dx, dy, dz), traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING);
@@ -153,8 +148,6 @@ bool prefilter_args_ok(int E, int He, int We, int Hp, int Wp) {
   // grid any other entry of the library launches, n_blocks(N) for N < 2^31
   return (long long)E * prefilter_chunks(He, We) * prefilter_tiles(Hp, Wp) <= PF_MAX_WORKGROUPS;
 }
-
-bool shininess_ok(float s) { return s >= (float)OI_ENVGLOSS_MIN_SHININESS && s <= (float)OI_ENVGLOSS_MAX_SHININESS; }
 
 }  // namespace
 
@@ -206,16 +199,12 @@ int oi_env_shade_glossy(const oi_env_shade_params* p, const float* rays_o, const
                         const int* map_index, const float* rot, const float* k_s, float* specular, oi_stream_t stream) {
   const char* what = "oi_env_shade_glossy";
   OI_TRY(check_env_shade(what, p, p && (p->shading || p->image || specular), "shading, image and specular are all null"));
-  OI_REQUIRE(M >= 1 && M <= OI_ENV_MAX_ENVS && Hp >= 1 && Wp >= 1 && (long long)M * 3 * Hp * Wp < (1ll << 31),
-             "%s: M=%d, Hp=%d, Wp=%d (1 <= M <= %d, sizes >= 1, M * 3 * Hp * Wp < 2^31)", what, M, Hp, Wp, OI_ENV_MAX_ENVS);
+  OI_TRY(check_gloss_maps(what, M, Hp, Wp));
   OI_REQUIRE(rays_o && w2b && glossy && map_index && rot && k_s, "%s: null glossy input pointer", what);
   OI_REQUIRE(p->n_hit == 0 || (hit_points && grad), "%s: null hit arrays with n_hit=%lld", what, p->n_hit);
   MapIndex mi = {};
-  for (int f = 0; f < p->F; ++f) {
-    OI_REQUIRE(map_index[f] >= 0 && map_index[f] < M, "%s: map_index[%d]=%d (0 <= map_index < M=%d)", what, f, map_index[f], M);
-    mi.v[f] = (uint8_t)map_index[f];
-  }
-  const GlossArgs g = {rays_o, hit_points, grad, w2b, spec_vis, glossy, rot, k_s, specular, Hp, Wp};
+  OI_TRY(pack_map_index(what, p->F, M, map_index, mi));
+  const GlossArgs g = {rays_o, hit_points, grad, w2b, spec_vis, glossy, rot, k_s, specular, Hp, Wp, nullptr};
   hipLaunchKernelGGL(env_shade_glossy_kernel, dim3((unsigned)((p->N + ES_THREADS - 1) / ES_THREADS)), dim3(ES_THREADS), 0,
                      oi::as_stream(stream), *p, g, mi);
   return oi::check_launch(what);

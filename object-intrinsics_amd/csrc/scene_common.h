@@ -1,13 +1,15 @@
-// What scene.hip and scene_light.hip share (include/oi_scene.h, include/oi_scene_light.h; DESIGN sections 4.19 and 4.21): the
-// unit sphere's chord, the rigid transform, "missed every instance", the per-pixel shading on the owner's slices and the
-// checks of its arguments.  (What a begin kernel stores and the compaction of the entered rays are trace_common.h's write_ray
-// and enter_rays.)  Internal linkage, as trace_common.h.
+// What scene.hip, scene_light.hip and scene_gloss.hip share (include/oi_scene.h, include/oi_scene_light.h,
+// include/oi_scene_gloss.h; DESIGN sections 4.19, 4.21 and 4.25): the unit sphere's chord, the rigid transform and its
+// rotation, the begin of a sampled ray against every instance (one body for the cap, the hemisphere and the lobe), "missed
+// every instance", the per-pixel shading on the owner's slices and the checks of its arguments.  (What a begin kernel stores and the
+// compaction of the entered rays are trace_common.h's write_ray and enter_rays.)  Internal linkage, as trace_common.h.
 #ifndef OI_SCENE_COMMON_H_
 #define OI_SCENE_COMMON_H_
 
 #include "trace_common.h"
 
 #include "../../include/oi_scene.h"
+#include "../../include/oi_scene_light.h"
 
 namespace {
 
@@ -44,6 +46,97 @@ __global__ void __launch_bounds__(TR_THREADS) scene_clear_kernel(const oi_trace_
   clear_counts(v.counts, 0);
   const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
   if (r < s.N) v.points[r * 3 + 0] = v.points[r * 3 + 1] = v.points[r * 3 + 2] = 0.f;
+}
+
+// R (the rotation of the rigid 4 x 4 M) applied to v, contraction off: tests/helpers/scene_light_ref.py restates it
+__device__ __forceinline__ void rotate(const float* __restrict__ M, const float* v, float* out) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int a = 0; a < 3; ++a) out[a] = M[a * 4 + 0] * v[0] + M[a * 4 + 1] * v[1] + M[a * 4 + 2] * v[2];
+}
+
+// ... and its transpose: w2b[:3,:3]^T v, a box-frame direction in the world.  trace_common.h's to_world is the same sum
+// under the default contraction (fused multiply-adds); this one rounds every product, as scene_light_ref.py does, so the two
+// stay apart.
+__device__ __forceinline__ void rotate_t(const float* __restrict__ M, const float* v, float* out) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int a = 0; a < 3; ++a) out[a] = M[0 + a] * v[0] + M[4 + a] * v[1] + M[8 + a] * v[2];
+}
+
+// How a scene's sampled rays are drawn in the owner's frame: uniform over the cap about a light, cosine-weighted over the
+// hemisphere about the normal (with a distance limit), or as cos^s about the reflected view vector (the hemisphere's cases
+// without a limit).
+enum class SceneSampler { CAP, HEMISPHERE, LOBE };
+
+// what the LOBE sampler reads beside oi_scene_occlusion_params (oi_scene_lobe_begin's own arguments, include/oi_scene_gloss.h)
+struct SceneLobe {
+  const float* rays_o;   // [E][N][3] the primary batch's origins
+  const int* vis_index;  // [E][N]
+  long long N;
+  float inv_s1;          // 1 / (shininess + 1)
+};
+
+// One ray of oi_scene_occlusion_begin (CAP, HEMISPHERE: scene_light.hip) and oi_scene_lobe_begin (LOBE: scene_gloss.hip): ray
+// blockIdx.x * TR_THREADS + threadIdx.x of occluder element blockIdx.y.  The direction is drawn once in the owner's frame;
+// the owner's ray starts at the biased point, any other instance's is moved into its box frame and culled against its unit
+// sphere.  Every thread of the workgroup calls it; lds: TR_WAVES + 1 words.  g: read for LOBE only.
+template <SceneSampler X>
+__device__ __forceinline__ void scene_sampled_begin(const oi_trace_state& s, int* __restrict__ live,
+                                                    const oi_scene_occlusion_params& p, const SceneLobe& g, unsigned* lds) {
+  constexpr bool LIMITED = X == SceneSampler::HEMISPHERE;  // far and the cull honour p.distance
+  const int eo = blockIdx.y;  // the occluder
+  const oi_trace_state v = element_view(s, eo);
+  const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  bool entered = false;
+  float px = 0.f, py = 0.f, pz = 0.f;
+  if (q < s.N) {
+    const long long lj = q / p.n_vis, gi = q - lj * p.n_vis;
+    const long long l = lj / p.Sc;
+    const unsigned j = (unsigned)p.j0 + (unsigned)(lj - l * p.Sc);
+    const int e = p.elem[gi];  // the point's owner
+    const long long slot = gi - p.offset[e], k = (long long)e * p.n_pad + slot;
+    const float* We = p.w2b + (long long)e * 16;
+    float n[3], d[3], o[3];
+    bool traced;
+    if constexpr (X == SceneSampler::LOBE) {
+      float r[3];
+      reflect_view(p.grad, p.hit_points, k, g.rays_o + ((long long)e * g.N + g.vis_index[(long long)e * g.N + slot]) * 3, n, r);
+      traced = lobe_direction(n, r, (unsigned)p.pixel[gi], p.seed, j, p.S, g.inv_s1, d[0], d[1], d[2]);
+    } else {
+      unit_normal(p.grad, k, n[0], n[1], n[2]);
+      traced = occlusion_direction<X == SceneSampler::HEMISPHERE>(n[0], n[1], n[2], (unsigned)p.pixel[gi], p.seed, j, p.S,
+                                                                  p.lights + l * OI_RELIGHT_LIGHT_FLOATS, p.radius, l, We, d[0],
+                                                                  d[1], d[2]);
+    }
+    offset_origin(p.hit_points + k * 3, p.bias, n[0], n[1], n[2], o[0], o[1], o[2]);
+    float near_ = 0.f, far_ = 0.f;
+    unsigned status = OI_TRACE_BACKFACING;
+    if (traced && e == eo) {
+      far_ = unit_sphere_exit(o[0], o[1], o[2], d[0], d[1], d[2]);
+      if (LIMITED) far_ = fminf(far_, p.distance);
+      entered = true;
+      status = OI_TRACE_MARCH;
+    } else if (traced) {
+      const float* Wb = p.w2b + (long long)eo * 16;
+      float ow[3], dw[3], dd[3];
+      offset_origin(p.position + gi * 3, p.bias, p.normal[gi * 3 + 0], p.normal[gi * 3 + 1], p.normal[gi * 3 + 2], ow[0], ow[1], ow[2]);
+      transform_point(Wb, ow, o);
+      rotate_t(We, d, dw);
+      rotate(Wb, dw, dd);
+      d[0] = dd[0], d[1] = dd[1], d[2] = dd[2];
+      entered = unit_sphere_chord(o, d, near_, far_);
+      if (LIMITED) {
+        entered = entered && near_ < p.distance;
+        far_ = fminf(far_, p.distance);
+      }
+      status = entered ? OI_TRACE_MARCH : OI_TRACE_MISS;
+    }
+    if (!entered) near_ = far_ = 0.f;
+    write_ray(v, q, o, d, near_, far_, status);
+    px = __fmaf_rn(near_, d[0], o[0]), py = __fmaf_rn(near_, d[1], o[1]), pz = __fmaf_rn(near_, d[2], o[2]);
+  }
+  enter_rays(v, q, entered, px, py, pz, lds, live);
 }
 
 // did ray `ray` (of `rays` per element) end OI_TRACE_MISS in every element?  A fixed-order loop, no early exit.
@@ -91,6 +184,25 @@ __device__ __forceinline__ void scene_shade_pixel(const oi_scene_shade_params& p
 // the scene's resolution; name: how the entry's message calls it ("S", or "scene S" where S counts samples)
 inline int check_resolution(const char* what, const char* name, int S) {
   OI_REQUIRE(S >= 1 && S <= OI_SCENE_MAX_RESOLUTION, "%s: %s=%d (1 .. %d)", what, name, S, OI_SCENE_MAX_RESOLUTION);
+  return OI_OK;
+}
+
+// the strata and the chunk of a sampled trace
+inline int check_chunk(const char* what, int L, int S, int j0, int Sc) {
+  OI_TRY(check_lights(what, L));
+  OI_TRY(check_samples(what, S));
+  OI_REQUIRE(j0 >= 0 && Sc >= 1 && j0 <= S - Sc, "%s: j0=%d, Sc=%d, S=%d (the chunk [j0, j0 + Sc) within [0, S), Sc >= 1)", what,
+             j0, Sc, S);
+  return OI_OK;
+}
+
+// the layout of a sampled begin's rays (sb: a checked batch) and its bias
+inline int check_sampled_rays(const char* what, const oi_trace_batch* sb, const oi_scene_occlusion_params* p) {
+  OI_REQUIRE(p->n_pad >= 1 && p->n_vis >= 1 && p->n_vis <= sb->E * p->n_pad,
+             "%s: n_pad=%lld, n_vis=%lld (n_pad >= 1, 1 <= n_vis <= E * n_pad)", what, p->n_pad, p->n_vis);
+  OI_REQUIRE((long long)p->L * p->Sc * p->n_vis == sb->s.N, "%s: L=%d, Sc=%d, n_vis=%lld, N=%lld (N must be L * Sc * n_vis)", what,
+             p->L, p->Sc, p->n_vis, sb->s.N);
+  OI_TRY(check_bias(what, p->bias));
   return OI_OK;
 }
 

@@ -5,8 +5,8 @@
 //   occlusion_begin     per occluder instance Sc sampled rays per (light, visible point): the direction drawn once in the
 //                       owner's frame (trace_common.h's occlusion_direction, occlusion.hip's own), the owner's ray by
 //                       occlusion.hip's expressions, any other instance's moved into its box frame and culled against its
-//                       unit sphere (and against `distance` when ambient); both origins are trace_common.h's
-//                       offset_origin, the stores and the compaction its write_ray and enter_rays
+//                       unit sphere (and against `distance` when ambient): scene_common.h's scene_sampled_begin, the one
+//                       body of the scene's three samplers (the lobe's entry is scene_gloss.hip's)
 //   step_anyhit         trace_common.h's state machine in its any-hit form on an element's view of the batched state
 //   occlusion_resolve   per scene pixel the number of samples that missed every instance (scene_common.h's
 //                       escaped_everywhere), accumulated across chunks as integers
@@ -40,70 +40,11 @@ __global__ void __launch_bounds__(TR_THREADS) scene_point_pixels_kernel(const in
   pixel[g] = (int)(Y * S + X);
 }
 
-// R (the rotation of the rigid 4 x 4 M) applied to v, contraction off: tests/helpers/scene_light_ref.py restates it
-__device__ __forceinline__ void rotate(const float* __restrict__ M, const float* v, float* out) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int a = 0; a < 3; ++a) out[a] = M[a * 4 + 0] * v[0] + M[a * 4 + 1] * v[1] + M[a * 4 + 2] * v[2];
-}
-
-// ... and its transpose: w2b[:3,:3]^T v, a box-frame direction in the world.  trace_common.h's to_world is the same sum
-// under the default contraction (fused multiply-adds); this one rounds every product, as scene_light_ref.py does, so the two
-// stay apart.
-__device__ __forceinline__ void rotate_t(const float* __restrict__ M, const float* v, float* out) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int a = 0; a < 3; ++a) out[a] = M[0 + a] * v[0] + M[4 + a] * v[1] + M[8 + a] * v[2];
-}
-
-template <bool AMBIENT>
+template <SceneSampler X>
 __global__ void __launch_bounds__(TR_THREADS) scene_occlusion_begin_kernel(const oi_trace_state s, int* __restrict__ live,
                                                                            const oi_scene_occlusion_params p) {
   __shared__ unsigned lds[TR_WAVES + 1];
-  const int eo = blockIdx.y;  // the occluder
-  const oi_trace_state v = element_view(s, eo);
-  const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  bool entered = false;
-  float px = 0.f, py = 0.f, pz = 0.f;
-  if (q < s.N) {
-    const long long lj = q / p.n_vis, g = q - lj * p.n_vis;
-    const long long l = lj / p.Sc;
-    const unsigned j = (unsigned)p.j0 + (unsigned)(lj - l * p.Sc);
-    const int e = p.elem[g];  // the point's owner
-    const long long k = (long long)e * p.n_pad + (g - p.offset[e]);
-    const float* We = p.w2b + (long long)e * 16;
-    float nx, ny, nz, d[3], o[3];
-    unit_normal(p.grad, k, nx, ny, nz);
-    const bool traced = occlusion_direction<AMBIENT>(nx, ny, nz, (unsigned)p.pixel[g], p.seed, j, p.S,
-                                                     p.lights + l * OI_RELIGHT_LIGHT_FLOATS, p.radius, l, We, d[0], d[1], d[2]);
-    offset_origin(p.hit_points + k * 3, p.bias, nx, ny, nz, o[0], o[1], o[2]);
-    float near_ = 0.f, far_ = 0.f;
-    unsigned status = OI_TRACE_BACKFACING;
-    if (traced && e == eo) {
-      far_ = unit_sphere_exit(o[0], o[1], o[2], d[0], d[1], d[2]);
-      if (AMBIENT) far_ = fminf(far_, p.distance);
-      entered = true;
-      status = OI_TRACE_MARCH;
-    } else if (traced) {
-      const float* Wb = p.w2b + (long long)eo * 16;
-      float ow[3], dw[3], dd[3];
-      offset_origin(p.position + g * 3, p.bias, p.normal[g * 3 + 0], p.normal[g * 3 + 1], p.normal[g * 3 + 2], ow[0], ow[1], ow[2]);
-      transform_point(Wb, ow, o);
-      rotate_t(We, d, dw);
-      rotate(Wb, dw, dd);
-      d[0] = dd[0], d[1] = dd[1], d[2] = dd[2];
-      entered = unit_sphere_chord(o, d, near_, far_);
-      if (AMBIENT) {
-        entered = entered && near_ < p.distance;
-        far_ = fminf(far_, p.distance);
-      }
-      status = entered ? OI_TRACE_MARCH : OI_TRACE_MISS;
-    }
-    if (!entered) near_ = far_ = 0.f;
-    write_ray(v, q, o, d, near_, far_, status);
-    px = __fmaf_rn(near_, d[0], o[0]), py = __fmaf_rn(near_, d[1], o[1]), pz = __fmaf_rn(near_, d[2], o[2]);
-  }
-  enter_rays(v, q, entered, px, py, pz, lds, live);
+  scene_sampled_begin<X>(s, live, p, SceneLobe{}, lds);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) trace_batch_step_anyhit_kernel(const oi_trace_state s, int* __restrict__ live,
@@ -205,15 +146,6 @@ __global__ void __launch_bounds__(TR_THREADS) scene_shade_ao_kernel(const oi_sce
   scene_shade_pixel(p.s, p.ambient_occlusion);
 }
 
-// the strata and the chunk of a sampled trace
-inline int check_chunk(const char* what, int L, int S, int j0, int Sc) {
-  OI_TRY(check_lights(what, L));
-  OI_TRY(check_samples(what, S));
-  OI_REQUIRE(j0 >= 0 && Sc >= 1 && j0 <= S - Sc, "%s: j0=%d, Sc=%d, S=%d (the chunk [j0, j0 + Sc) within [0, S), Sc >= 1)", what,
-             j0, Sc, S);
-  return OI_OK;
-}
-
 // what the resolves share: the scene's shape and the size of the chunk's trace
 inline int check_resolve(const char* what, int E, long long N, int L, int Sc, long long n_vis, int scene_S) {
   OI_TRY(check_scene_rays(what, E, N));
@@ -246,11 +178,7 @@ int oi_scene_occlusion_begin(const oi_trace_batch* sb, const oi_scene_occlusion_
   OI_REQUIRE(p != nullptr, "%s: null params", what);
   OI_TRY(check_chunk(what, p->L, p->S, p->j0, p->Sc));
   OI_REQUIRE(!p->ambient || p->L == 1, "%s: L=%d with ambient (the hemisphere is one set of rays: L must be 1)", what, p->L);
-  OI_REQUIRE(p->n_pad >= 1 && p->n_vis >= 1 && p->n_vis <= sb->E * p->n_pad,
-             "%s: n_pad=%lld, n_vis=%lld (n_pad >= 1, 1 <= n_vis <= E * n_pad)", what, p->n_pad, p->n_vis);
-  OI_REQUIRE((long long)p->L * p->Sc * p->n_vis == sb->s.N, "%s: L=%d, Sc=%d, n_vis=%lld, N=%lld (N must be L * Sc * n_vis)", what,
-             p->L, p->Sc, p->n_vis, sb->s.N);
-  OI_TRY(check_bias(what, p->bias));
+  OI_TRY(check_sampled_rays(what, sb, p));
   OI_REQUIRE(!p->ambient || p->distance > 0.f, "%s: distance %g (> 0; INFINITY is allowed)", what, (double)p->distance);
   OI_REQUIRE(p->hit_points && p->grad && p->offset && p->elem && p->pixel && p->position && p->normal && p->w2b &&
                  (p->ambient || (p->lights && p->radius)),
@@ -259,9 +187,9 @@ int oi_scene_occlusion_begin(const oi_trace_batch* sb, const oi_scene_occlusion_
   const dim3 grid(n_blocks(sb->s.N), sb->E);
   hipLaunchKernelGGL(scene_clear_kernel, grid, dim3(TR_THREADS), 0, st, sb->s, sb->live);
   if (p->ambient)
-    hipLaunchKernelGGL(scene_occlusion_begin_kernel<true>, grid, dim3(TR_THREADS), 0, st, sb->s, sb->live, *p);
+    hipLaunchKernelGGL(scene_occlusion_begin_kernel<SceneSampler::HEMISPHERE>, grid, dim3(TR_THREADS), 0, st, sb->s, sb->live, *p);
   else
-    hipLaunchKernelGGL(scene_occlusion_begin_kernel<false>, grid, dim3(TR_THREADS), 0, st, sb->s, sb->live, *p);
+    hipLaunchKernelGGL(scene_occlusion_begin_kernel<SceneSampler::CAP>, grid, dim3(TR_THREADS), 0, st, sb->s, sb->live, *p);
   return oi::check_launch(what);
 }
 

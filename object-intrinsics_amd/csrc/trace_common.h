@@ -322,6 +322,20 @@ __device__ __forceinline__ bool occlusion_direction(float nx, float ny, float nz
   return nx * dx + ny * dy + nz * dz > 0.f;
 }
 
+// Sample j of S at the pixel `pix` of the reflection lobe about the unit axis a (include/oi_envgloss.h): the polar angle has
+// density proportional to cos^s(alpha), cos(alpha) = u1^(1 / (s + 1)) evaluated as expf(logf(u1) inv_s1) with inv_s1 = 1 / (s + 1),
+// sin(alpha) = sqrt(-expm1f(2 logf(u1) inv_s1)) (1 - cos^2 without the cancellation).  -> the direction; traced: n . d > 0.
+// envgloss.hip's begin kernel and the scene's lobe rays (scene_gloss.hip) draw their directions here.
+__device__ __forceinline__ bool lobe_direction(const float* n, const float* a, unsigned pix, unsigned seed, unsigned j, int S,
+                                               float inv_s1, float& dx, float& dy, float& dz) {
+  float u1, u2;
+  sample_numbers(pix, seed, j, S, u1, u2);
+  const float e = logf(u1) * inv_s1;  // log(cos alpha)
+  const float ca = expf(e), sa = sqrtf(fmaxf(-expm1f(2.0f * e), 0.f));
+  direction_about(a[0], a[1], a[2], sa, ca, u2, dx, dy, dz);
+  return n[0] * dx + n[1] * dy + n[2] * dz > 0.f;
+}
+
 // include/oi_envlight.h's basis of a unit vector
 __device__ __forceinline__ void sh9(float x, float y, float z, float* __restrict__ o) {
   o[0] = 0.28209479177387814f;
@@ -345,6 +359,16 @@ __device__ __forceinline__ void to_world(const float* __restrict__ Wb, float dx,
 // the unit normal of gradient row k
 __device__ __forceinline__ void unit_normal(const float* __restrict__ grad, long long k, float& nx, float& ny, float& nz) {
   unit_normal(grad[k * 3 + 0], grad[k * 3 + 1], grad[k * 3 + 2], nx, ny, nz);
+}
+
+// n = the unit normal of hit k, v = its unit view vector from `eye`, r = 2 ((n . v) n) - v
+__device__ __forceinline__ void reflect_view(const float* __restrict__ grad, const float* __restrict__ hit_points, long long k,
+                                             const float* __restrict__ eye, float* n, float* r) {
+  unit_normal(grad, k, n[0], n[1], n[2]);
+  float vx, vy, vz;
+  unit_view(eye[0], eye[1], eye[2], hit_points[k * 3 + 0], hit_points[k * 3 + 1], hit_points[k * 3 + 2], vx, vy, vz);
+  const float ndv = n[0] * vx + n[1] * vy + n[2] * vz;
+  r[0] = 2.0f * (ndv * n[0]) - vx, r[1] = 2.0f * (ndv * n[1]) - vy, r[2] = 2.0f * (ndv * n[2]) - vz;
 }
 
 // The unshadowed transfer of a point with the unit normal n in the frame w2b (include/oi_envlight.h's closed form):

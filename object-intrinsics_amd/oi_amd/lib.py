@@ -358,6 +358,13 @@ SIGS = {
         "oi_bounce_resolve": (_i, [_vp] * 6 + [_ll, _ll, _ll, _i, _vp, _vp, _vp]),
         "oi_env_shade_bounce": (_i, [_P(EnvShadeBounceParams), _vp]),
     },
+    # include/oi_scene_gloss.h: the Phong lobe under an environment map in a scene of many instances (an addition to
+    # oi_scene_light.h and oi_envgloss.h; no struct of its own: the lobe's begin takes oi_scene_light.h's parameters)
+    "oi_scene_gloss.h": {
+        "oi_scene_lobe_begin": (_i, [_P(TraceBatch), _P(SceneOcclusionParams), _vp, _vp, _ll, _f, _vp]),
+        "oi_scene_reflect": (_i, [_vp, _vp, _vp, _ll] + [_vp] * 4 + [_i, _ll, _i, _vp, _vp]),
+        "oi_env_shade_glossy_dirs": (_i, [_P(EnvShadeParams), _vp, _vp, _vp, _i, _i, _i, _P(_i), _vp, _vp, _vp, _vp]),
+    },
 }
 
 

@@ -1140,32 +1140,84 @@ def occlusion_lobe_begin(st, rays_o, hit_points, grad, hit_index, n_hit, samples
 ENV_GLOSSY_OUT = ENV_SHADE_OUT + ("specular",)
 
 
+def _gloss_own(what, glossy, map_index, rot, k_s, spec_vis, dirs=None):
+    """env_shade_glossy's and env_shade_glossy_dirs' own checks for _env_shade: -> own(N, F), which returns the map indices as a
+    host array of F C integers."""
+    def own(N, F):
+        if not torch.is_tensor(glossy) or glossy.dim() != 4 or glossy.shape[1] != 3 or not 1 <= glossy.shape[0] <= _l.ENV_MAX_ENVS:
+            raise ValueError(f"{what}: glossy {tuple(getattr(glossy, 'shape', ()))}, expected (M, 3, Hp, Wp) with "
+                             f"1 <= M <= {_l.ENV_MAX_ENVS}")
+        M = glossy.shape[0]
+        idx = [int(v) for v in map_index]
+        if len(idx) != F or any(not 0 <= v < M for v in idx):
+            raise ValueError(f"{what}: map_index {idx} (F = {F} integers, 0 <= map_index < M = {M})")
+        if tuple(rot.shape) != (F, 3, 3) or tuple(k_s.shape) != (3,) or (spec_vis is not None and tuple(spec_vis.shape) != (N,)):
+            raise ValueError(f"{what}: rot {tuple(rot.shape)}, k_s {tuple(k_s.shape)}, expected {(F, 3, 3)} and (3,); "
+                             f"spec_vis (N,) = {(N,)} or None")
+        if dirs is not None and tuple(dirs.shape) != (N, 3):
+            raise ValueError(f"{what}: dirs {tuple(dirs.shape)}, expected {(N, 3)}")
+        return (ctypes.c_int * F)(*idx)
+    return own
+
+
 def env_shade_glossy(status, hit_slot, rgb, n_hit, transfer, envs, rays_o, hit_points, grad, w2b, spec_vis, glossy, map_index,
                      rot, k_s, bg=None, outputs=ENV_GLOSSY_OUT, out=None):
     """env_shade plus the glossy term (oi_env_shade_glossy): envs (F, 9, 3) the SH halves, glossy (M, 3, Hp, Wp) the
     prefiltered maps, map_index F host integers in [0, M) (checked here, before anything is uploaded), rot (F, 3, 3) world
     rotations, k_s (3,), spec_vis (N,) or None (= 1).  -> {name: (F, 3, N)} for the names of ENV_GLOSSY_OUT in `outputs`."""
-    def own(N, F):
-        if not torch.is_tensor(glossy) or glossy.dim() != 4 or glossy.shape[1] != 3 or not 1 <= glossy.shape[0] <= _l.ENV_MAX_ENVS:
-            raise ValueError(f"env_shade_glossy: glossy {tuple(getattr(glossy, 'shape', ()))}, expected (M, 3, Hp, Wp) with "
-                             f"1 <= M <= {_l.ENV_MAX_ENVS}")
-        M = glossy.shape[0]
-        idx = [int(v) for v in map_index]
-        if len(idx) != F or any(not 0 <= v < M for v in idx):
-            raise ValueError(f"env_shade_glossy: map_index {idx} (F = {F} integers, 0 <= map_index < M = {M})")
-        if tuple(rot.shape) != (F, 3, 3) or tuple(k_s.shape) != (3,) or (spec_vis is not None and tuple(spec_vis.shape) != (N,)):
-            raise ValueError(f"env_shade_glossy: rot {tuple(rot.shape)}, k_s {tuple(k_s.shape)}, expected {(F, 3, 3)} and (3,); "
-                             f"spec_vis (N,) = {(N,)} or None")
-        return (ctypes.c_int * F)(*idx)
-
     P = _l.EnvShadeParams()
     res, _keep, index = _env_shade("env_shade_glossy", ENV_GLOSSY_OUT, P, status, hit_slot, rgb, n_hit, transfer, envs, bg, outputs,
-                                   out, own)
+                                   out, _gloss_own("env_shade_glossy", glossy, map_index, rot, k_s, spec_vis))
     M, _, Hp, Wp = glossy.shape
     more = [_c(x) for x in (rays_o, hit_points if n_hit else None, grad if n_hit else None, w2b, spec_vis, glossy, rot, k_s)]
     ro, hp, g, wb, sv, gl, rt, ks = (_p(x) for x in more)
     _l.check(_l.load().oi_env_shade_glossy(ctypes.byref(P), ro, hp, g, wb, sv, gl, M, Hp, Wp, index, rt, ks,
                                            _p(res.get("specular")), _stream()), "oi_env_shade_glossy")
+    return res
+
+
+# ------------------------------------------------------------------------------------------
+# glossy environment lighting in a scene of many instances (include/oi_scene_gloss.h); oi_amd.scene sequences these
+# ------------------------------------------------------------------------------------------
+
+def scene_lobe_begin(sb, rays_o, vis_index, N, hit_points, grad, n_pad, offset, elem, pixel, position, normal, n_vis, w2b, bias,
+                     samples, j0, chunk, shininess, seed=0):
+    """sb: TraceBatchState of E occluder elements x chunk * n_vis rays (trace_batch_state_empty): the samples [j0, j0 + chunk)
+    of `samples` reflection-lobe rays per visible point, distributed as cos^shininess about the reflected view vector.  rays_o
+    (E, N, 3): the primary batch's origins; vis_index (E, N) int32."""
+    P = _l.SceneOcclusionParams()
+    P.L, P.S, P.j0, P.Sc, P.ambient = 1, int(samples), int(j0), int(chunk), 1
+    P.seed, P.bias, P.distance, P.n_pad, P.n_vis = int(seed), float(bias), float("inf"), int(n_pad), int(n_vis)
+    keep = [_c(x) for x in (hit_points, grad, position, normal, w2b, rays_o)]
+    P.hit_points, P.grad, P.position, P.normal, P.w2b, eyes = (_p(x) for x in keep)
+    P.offset, P.elem, P.pixel = _ip(offset), _ip(elem), _ip(pixel)
+    _l.check(_l.load().oi_scene_lobe_begin(ctypes.byref(sb.c), ctypes.byref(P), eyes, _ip(vis_index), int(N), float(shininess),
+                                           _stream()), "oi_scene_lobe_begin")
+
+
+def scene_reflect(rays_o, hit_points, grad, n_pad, owner, owner_ray, vis_slot, w2b, E, N, S):
+    """-> the reflected view vector of every scene pixel (S * S, 3), world frame; zeros off the mask."""
+    out = _new(grad, S * S, 3)
+    _l.check(_l.load().oi_scene_reflect(_p(_c(rays_o)), _p(_c(hit_points)), _p(_c(grad)), int(n_pad), _ip(owner), _ip(owner_ray),
+                                        _ip(vis_slot), _p(_c(w2b)), int(E), int(N), int(S), _p(out), _stream()), "oi_scene_reflect")
+    return out
+
+
+def env_shade_glossy_dirs(status, hit_slot, rgb, n_hit, transfer, envs, dirs, spec_vis, glossy, map_index, rot, k_s, bg=None,
+                          outputs=ENV_GLOSSY_OUT, out=None):
+    """env_shade_glossy with the world-frame lookup direction given per pixel, dirs (N, 3), in place of the eyes, the hits and
+    the pose (oi_env_shade_glossy_dirs): a scene's planes.  -> {name: (F, 3, N)} for the names of ENV_GLOSSY_OUT in `outputs`."""
+    what = "env_shade_glossy_dirs"
+    if not torch.is_tensor(dirs) or dirs.dim() != 2:
+        raise ValueError(f"{what}: dirs {tuple(getattr(dirs, 'shape', ()))}, expected (N, 3)")
+    P = _l.EnvShadeParams()
+    res, _keep, index = _env_shade(what, ENV_GLOSSY_OUT, P, status, hit_slot, rgb, n_hit, transfer, envs, bg, outputs, out,
+                                   _gloss_own(what, glossy, map_index, rot, k_s, spec_vis, dirs))
+    M, _, Hp, Wp = glossy.shape
+    more = [_c(x) for x in (dirs, spec_vis, glossy, rot, k_s)]
+    dr, sv, gl, rt, ks = (_p(x) for x in more)
+    _l.check(_l.load().oi_env_shade_glossy_dirs(ctypes.byref(P), dr, sv, gl, M, Hp, Wp, index, rt, ks, _p(res.get("specular")),
+                                                _stream()), "oi_env_shade_glossy_dirs")
     return res
 
 

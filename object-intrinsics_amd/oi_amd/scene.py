@@ -122,6 +122,7 @@ class SceneSurface:
         self.n_hit = self.n_vis = [0] * E
         self.owner = self.owner_ray = self.vis_slot = self.offset = self.points = self.grad = self.rgb = None
         self._world = self._pixel = self.vis_index = self.shadow = self.ao = self.transfer_state = None
+        self.glossy_evals, self.glossy_state, self._reflect = 0, None, None
         bound = int(st.live[0].item())
         self.n_entered = st.counts[:, 0].tolist()
         if bound == 0:      # nothing enters a window: every ray is a MISS already
@@ -157,10 +158,12 @@ class SceneSurface:
                                                  sum(self.n_vis))
         return self._pixel
 
-    def _sampled(self, what, samples, seed, max_shadow_rays, resolve, lights=None, radius=None, distance=None):
+    def _sampled(self, what, samples, seed, max_shadow_rays, resolve, lights=None, radius=None, distance=None, *, lobe=None):
         """The sampled any-hit trace against every instance, in chunks of the samples: a chunk holds E * L * Sc * n_vis rays, Sc
         the largest number for which that stays within max_shadow_rays and below 2^31.  resolve(sb, j0, Sc, last) accumulates
-        each finished chunk.  -> (sdf evaluations per element, the last chunk's state)."""
+        each finished chunk.  lights and radius: caps about the lights; distance: the hemisphere about the normal; lobe (a
+        shininess): the reflection lobe about the reflected view vector (include/oi_scene_gloss.h).  -> (sdf evaluations per
+        element, the last chunk's state)."""
         L, n_vis = 1 if lights is None else lights.shape[0], sum(self.n_vis)
         per = self.E * L * n_vis
         chunk = min(int(samples), min(int(max_shadow_rays), (1 << 31) - 1) // per)
@@ -173,8 +176,12 @@ class SceneSurface:
         for j0 in range(0, int(samples), chunk):
             c = min(chunk, int(samples) - j0)
             sb = ops.trace_batch_state_empty(self.E, L * c * n_vis, pos)
-            ops.scene_occlusion_begin(sb, self.points, self.grad, self.n_pad, self.offset, elem, pixel, pos, nrm, n_vis, self.w2b,
-                                      self.bias, samples, j0, c, seed, lights, radius, distance)
+            if lobe is None:
+                ops.scene_occlusion_begin(sb, self.points, self.grad, self.n_pad, self.offset, elem, pixel, pos, nrm, n_vis, self.w2b,
+                                          self.bias, samples, j0, c, seed, lights, radius, distance)
+            else:
+                ops.scene_lobe_begin(sb, self.state.rays_o, self.vis_index, self.N, self.points, self.grad, self.n_pad, self.offset,
+                                     elem, pixel, pos, nrm, n_vis, self.w2b, self.bias, samples, j0, c, lobe, seed)
             bound = int(sb.live[0].item())
             if bound:
                 total, _ = _t._march_batch(self.field, sb, *self.kw, bound=bound, anyhit=True)
@@ -253,14 +260,50 @@ class SceneSurface:
         self.transfer_evals += evals
         return out
 
-    def capture_transfer(self, transfer_samples=64, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+    def lobe_visibility(self, samples, shininess, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """(S * S,) reflection-lobe visibility V_spec (include/oi_scene_gloss.h): the share of `samples` rays per visible point,
+        distributed as cos^shininess about the reflected view vector, that are above the point's horizon and meet no instance
+        -- the point's own or any other; 1 off the mask.  Chunked as ambient()."""
+        M, n_vis = self.S * self.S, sum(self.n_vis)
+        if n_vis == 0:
+            return torch.ones(M, device=self.b2w.device)
+        count, out = ops._new(self.b2w, 1, M).view(torch.int32), ops._new(self.b2w, 1, M)
+        resolve = lambda sb, j0, c, last: ops.scene_occlusion_resolve(
+            sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, 1, samples, j0, c, n_vis, self.S, count,
+            out, last)
+        evals, self.glossy_state = self._sampled("SceneSurface.lobe_visibility", samples, seed, max_shadow_rays, resolve,
+                                                 lobe=float(shininess))
+        self.glossy_evals += evals
+        return out.view(M)
+
+    def reflection(self):
+        """(S * S, 3): the reflected view vector of every scene pixel in the world frame (the lookup direction of the glossy
+        shade), zeros off the mask; computed once."""
+        if self._reflect is None:
+            if self.n_pad == 0:
+                self._reflect = torch.zeros(self.S * self.S, 3, device=self.b2w.device)
+            else:
+                self._reflect = ops.scene_reflect(self.state.rays_o, self.points, self.grad, self.n_pad, self.owner, self.owner_ray,
+                                                  self.vis_slot, self.w2b, self.E, self.N, self.S)
+        return self._reflect
+
+    def capture_transfer(self, transfer_samples=64, seed=0, max_shadow_rays=MAX_SHADOW_RAYS, glossy_samples=None, shininess=None):
         """The scene prepared for environment lighting: `transfer_samples` (0 .. 256) cosine-weighted rays per visible point,
         each tested against EVERY instance, resolved into a 9-coefficient world-frame transfer vector per scene pixel (0: the
-        unshadowed closed form, nothing traced).  -> SceneTransfer."""
+        unshadowed closed form, nothing traced).
+        Glossy environments (oi_amd.envlight.EnvMap): glossy_samples in 1 .. 256 also traces that many rays per visible point
+        about the reflected view vector, distributed as cos^shininess and tested against every instance, into spec_visibility;
+        shininess None takes the generator's learned value; glossy_samples = 0 prepares a glossy capture without that trace
+        (V_spec = 1), and a shininess without glossy_samples is refused (oi_amd.trace.capture_transfer's rules).  With both left
+        at None the launches and outputs are those of a call without them.  -> SceneTransfer."""
         samples, seed = _t._check_transfer(transfer_samples, seed, "SceneSurface.capture_transfer")
+        g_samples, shin, spec = _t._check_glossy(getattr(self, "gen", None), glossy_samples, shininess, "SceneSurface.capture_transfer")
         transfer = self.transfer(samples, seed, max_shadow_rays)
         out = self._shade(None, None, None, ("depth", "position", "normal_world", "albedo", "mask", "instance"))
-        return SceneTransfer(self, transfer, out, samples)
+        if g_samples is None:
+            return SceneTransfer(self, transfer, out, samples)
+        vis = self.lobe_visibility(g_samples, shin, seed, max_shadow_rays) if g_samples else None
+        return SceneTransfer(self, transfer, out, samples, g_samples, shin, spec, vis, self.reflection())
 
     def _shade(self, lt, bg, vis, outputs, image_out=None, ao=None):
         """ops.scene_shade on this scene (ao: ops.scene_shade_ao, the occlusion factor (S * S,) on the ambient term); without a
@@ -316,8 +359,8 @@ class SceneSurface:
 
     def stats(self):
         """Per instance: rays entered and culled, rays per status (culled rays are misses), hits, visible hits; sdf
-        evaluations of the primary march and of the shadow, ambient-occlusion and transfer marches so far (every instance carries
-        the batch's bound)."""
+        evaluations of the primary march and of the shadow, ambient-occlusion, transfer and reflection-lobe marches so far (every
+        instance carries the batch's bound)."""
         st = self.state
         per = torch.stack([torch.bincount(st.status[e].long(), minlength=6)[:6] for e in range(self.E)]).tolist()
         out = []
@@ -325,7 +368,7 @@ class SceneSurface:
             s = {name: int(per[e][code]) for code, name in _l.TRACE_STATUS_NAMES.items()}
             s.update(n_rays=self.N, entered=int(self.n_entered[e]), culled=self.N - int(self.n_entered[e]), hits=int(self.n_hit[e]),
                      visible=int(self.n_vis[e]), n_evals=self.n_evals, n_steps=self.n_steps, shadow_evals=self.shadow_evals,
-                     occlusion_evals=self.occlusion_evals, transfer_evals=self.transfer_evals)
+                     occlusion_evals=self.occlusion_evals, transfer_evals=self.transfer_evals, glossy_evals=self.glossy_evals)
             out.append(s)
         return out
 
@@ -337,9 +380,12 @@ _MAP_NAMES = {"depth": "depth", "position": "position", "normal_world": "normal_
 class SceneTransfer:
     """One traced scene and its SH transfer map: everything shade() needs, none of which depends on the light.
     scene: the SceneSurface; transfer (1, 9, S, S), world frame; maps: SceneSurface.shade's G-buffer maps (depth, position,
-    normal_map, albedo, mask, instance); samples: the rays per visible point (0: the closed form)."""
+    normal_map, albedo, mask, instance); samples: the rays per visible point (0: the closed form).  A capture made with
+    glossy_samples also holds the shininess its lobe was traced for, specular (the learned specular colour), spec_visibility
+    (1, 1, S, S) (None with glossy_samples = 0: V_spec = 1) and reflection (1, 3, S, S), the world-frame reflected view vector."""
 
-    def __init__(self, scene, transfer, planes, samples):
+    def __init__(self, scene, transfer, planes, samples, glossy_samples=None, shininess=None, specular=None, spec_vis=None,
+                 reflection=None):
         S = scene.S
         self.scene, self.samples, self.S = scene, samples, S
         self._transfer = transfer                       # (9, S * S), planar: what oi_env_shade reads
@@ -351,27 +397,58 @@ class SceneTransfer:
         self._status = on.to(torch.uint8) * _l.TRACE_HIT
         self._hit_slot = torch.where(on, torch.arange(M, dtype=torch.int32, device=dev), torch.full((M,), -1, dtype=torch.int32, device=dev))
         self._rgb = planes["albedo"]
+        # glossy_samples: None = never mentioned (a glossy shade is refused), 0 = no lobe trace on purpose (V_spec = 1)
+        self.glossy_samples, self.shininess, self.specular = glossy_samples, shininess, specular
+        self._spec_vis, self._reflect = spec_vis, reflection     # (S * S,) or None; (S * S, 3) or None
+        self.spec_visibility = None if spec_vis is None else spec_vis.view(1, 1, S, S)
+        self.reflection = None if reflection is None else reflection.view(S, S, 3).permute(2, 0, 1)[None]
 
-    def shade(self, envs, bg=None):
-        """The scene under each of `envs` (oi_amd.envlight.EnvLight objects, any number: launches of ENV_MAX_ENVS).  ->
-        {"image": (F, 3, S, S) = max(shading, 0) albedo on the mask, bg off it; "shading": (F, 3, S, S), not clamped; the
-        G-buffer maps; "stats"}.  The glossy lobe (EnvMap) is not available in scenes."""
-        from .envlight import EnvLight, stack_envs
-        seq = [envs] if isinstance(envs, EnvLight) else list(envs)
-        if not seq or not all(isinstance(e, EnvLight) for e in seq):
-            raise ValueError("SceneTransfer.shade: EnvLight objects only (the glossy lobe of an EnvMap is not available in scenes)")
+    def shade(self, envs, bg=None, specular=None):
+        """The scene under each of `envs` (any number: launches of ENV_MAX_ENVS).
+        EnvLight objects: -> {"image": (F, 3, S, S) = max(shading, 0) albedo on the mask, bg off it; "shading": (F, 3, S, S), not
+        clamped; the G-buffer maps; "stats"}.
+        EnvMap objects (every element; a mixed list is refused), on a capture made with glossy_samples: the glossy path
+        (include/oi_scene_gloss.h), image = max(shading, 0) albedo + specular and "specular": (F, 3, S, S) = k_s V_spec
+        G_s(reflected view vector), V_spec knowing every instance.  k_s = `specular`: None takes the generator's learned specular
+        colour, a scalar or an RGB triple overrides it.  The maps' shininess must be the capture's."""
+        from .envlight import EnvLight, EnvMap, stack_envs, stack_maps
+        seq = [envs] if isinstance(envs, (EnvLight, EnvMap)) else list(envs)
+        if not seq or not all(isinstance(e, (EnvLight, EnvMap)) for e in seq):
+            raise ValueError("SceneTransfer.shade: EnvLight objects only, or EnvMap objects only")
+        glossy = any(isinstance(e, EnvMap) for e in seq)
+        if glossy and not all(isinstance(e, EnvMap) for e in seq):
+            raise ValueError("SceneTransfer.shade: EnvMap and EnvLight objects in one list (shade them in two calls)")
+        if not glossy and specular is not None:
+            raise ValueError("SceneTransfer.shade: specular= needs EnvMap environments (an EnvLight has no glossy half)")
+        if glossy and self.glossy_samples is None:
+            raise ValueError("SceneTransfer.shade: this capture has no reflection-lobe trace; capture_transfer(glossy_samples=S) "
+                             "traces one, glossy_samples=0 with a shininess states that V_spec = 1 is meant")
+        if glossy and any(e.shininess != self.shininess for e in seq):
+            raise ValueError(f"SceneTransfer.shade: maps prefiltered for shininess {sorted({e.shininess for e in seq})}, the "
+                             f"capture's lobe is {self.shininess:g}")
         s, S = self.scene, self.S
         dev, M = self._transfer.device, S * S
-        ev = stack_envs(seq, dev)
-        F = ev.shape[0]
+        F = len(seq)
         bgv = _t._bg(bg, dev)
+        names = ops.ENV_GLOSSY_OUT if glossy else ops.ENV_SHADE_OUT
+        view = (self._status, self._hit_slot, self._rgb, M, self._transfer)
         if s.n_pad == 0:   # no hit at all: nothing is launched
-            out = {k: ops._new(self._transfer, F, 3, M) for k in ops.ENV_SHADE_OUT}
-            out["shading"].zero_()
+            out = {k: ops._new(self._transfer, F, 3, M) for k in names}
+            for k in names:
+                if k != "image":
+                    out[k].zero_()
             out["image"].copy_((torch.zeros(3, device=dev) if bgv is None else bgv).view(1, 3, 1).expand(F, 3, M))
+        elif not glossy:
+            ev = stack_envs(seq, dev)
+            out = _t._shade_chunks(self._transfer, names, F, M, lambda a, b, out: ops.env_shade(*view, ev[a:b], bgv, out=out))
         else:
-            out = _t._shade_chunks(self._transfer, ops.ENV_SHADE_OUT, F, M, lambda a, b, out: ops.env_shade(
-                self._status, self._hit_slot, self._rgb, M, self._transfer, ev[a:b], bgv, out=out))
+            ks = self.specular if specular is None else specular
+            ks = torch.as_tensor(np.broadcast_to(np.asarray(ks, dtype=np.float32), (3,)).copy()).to(dev)
+
+            def launch(a, b, out):
+                ev, maps, index, rot, _ = stack_maps(seq[a:b], dev)
+                ops.env_shade_glossy_dirs(*view, ev, self._reflect, self._spec_vis, maps, index, rot, ks, bgv, out=out)
+            out = _t._shade_chunks(self._transfer, names, F, M, launch)
         res = {k: v.view(F, 3, S, S) for k, v in out.items()}
         res.update(self.maps)
         res["stats"] = s.stats()
@@ -409,13 +486,19 @@ def render_scene(gen, zs, b2ws, lights=None, shadows=False, bg=None, window=None
 
 @torch.no_grad()
 def render_scene_env(gen, zs, b2ws, envs, transfer_samples=64, seed=0, bg=None, window=None, bias=DEFAULT_BIAS,
-                     max_shadow_rays=MAX_SHADOW_RAYS, **trace_kw):
+                     max_shadow_rays=MAX_SHADOW_RAYS, glossy_samples=None, shininess=None, specular=None, **trace_kw):
     """trace_scene + capture_transfer + shade: K instances in one scene image under the environment lights `envs`
-    (oi_amd.envlight.EnvLight objects), every instance occluding the sky for itself and for the others.  ->
-    SceneTransfer.shade's dict, with "transfer" (1, 9, S, S), "scene" (the SceneSurface) and "capture" (the SceneTransfer)."""
+    (oi_amd.envlight.EnvLight objects, or EnvMap objects with glossy_samples given: capture_transfer's and shade's keywords pass
+    through), every instance occluding the sky for itself and for the others -- and, on the glossy path, standing in the
+    others' reflections.  -> SceneTransfer.shade's dict, with "transfer" (1, 9, S, S), "scene" (the SceneSurface) and "capture"
+    (the SceneTransfer); on the glossy path also "specular" (F, 3, S, S), "spec_visibility" (1, 1, S, S) or None and
+    "reflection" (1, 3, S, S)."""
     _t._check_transfer(transfer_samples, seed, "render_scene_env")
+    _t._check_glossy(gen, glossy_samples, shininess, "render_scene_env")
     s = trace_scene(gen, zs, b2ws, window, bias, **trace_kw)
-    cap = s.capture_transfer(transfer_samples, seed, max_shadow_rays)
-    res = cap.shade(envs, bg)
+    cap = s.capture_transfer(transfer_samples, seed, max_shadow_rays, glossy_samples, shininess)
+    res = cap.shade(envs, bg, specular)
     res.update(transfer=cap.transfer, scene=s, capture=cap)
+    if cap.glossy_samples is not None:
+        res.update(spec_visibility=cap.spec_visibility, reflection=cap.reflection)
     return res

@@ -14,7 +14,13 @@ and ambient occlusion between the instances; the crops trace theirs against thei
   scene_env_ms                   oi_amd.scene.render_scene_env with --transfer-samples rays per visible point, every ray tested
                                  against all K instances, under one constant environment
   crops_env_ms                   K calls of oi_amd.trace.render_surface_env on the crops
-No ratio is promised: the two do different work (the scene tests every secondary ray against all K instances)."""
+No ratio is promised: the two do different work (the scene tests every secondary ray against all K instances).
+With --env --glossy the glossy lobe of DESIGN section 4.25 is timed per K beside the diffuse rows of the same run:
+
+  scene_gloss_capture_ms         trace_scene + SceneSurface.capture_transfer with --glossy-samples reflection-lobe rays per
+                                 visible point on top of the transfer rays, every ray tested against all K instances
+  scene_gloss_shade_ms           SceneTransfer.shade of that capture under one prefiltered 64 x 128 map (one launch)
+  scene_gloss_ms                 oi_amd.scene.render_scene_env on the glossy path: the two together"""
 import argparse
 import copy
 import json
@@ -28,7 +34,7 @@ import torch  # noqa: E402
 
 from bench import build_models  # noqa: E402
 from oi_amd import scene, trace  # noqa: E402
-from oi_amd.envlight import EnvLight  # noqa: E402
+from oi_amd.envlight import EnvLight, EnvMap  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--res", type=int, default=64, help="crop resolution of the generator; the scene image is res * 1588 / 256")
@@ -42,6 +48,9 @@ ap.add_argument("--light-radius", type=float, default=0.0, help="angular radius 
 ap.add_argument("--ao-samples", type=int, default=0, help="ambient-occlusion rays per visible point of the shadowed rows")
 ap.add_argument("--env", action="store_true", help="also time environment lighting (scene_env_ms / crops_env_ms)")
 ap.add_argument("--transfer-samples", type=int, default=64)
+ap.add_argument("--glossy", action="store_true", help="with --env: also time the glossy capture and shade (scene_gloss_*_ms)")
+ap.add_argument("--glossy-samples", type=int, default=64, help="reflection-lobe rays per visible point")
+ap.add_argument("--shininess", type=float, default=10.0)
 args = ap.parse_args()
 
 
@@ -64,9 +73,16 @@ gen, _ = build_models(args.res, 256, 64, 1, args.precision, "cuda")
 gen.eval()
 out = {"tool": "bench_scene", "precision": args.precision, "res": args.res, "scene_resolution": gen.scene_resolution,
        "iters": args.iters, "warmup": args.warmup, "shadow_samples": args.shadow_samples, "light_radius": args.light_radius,
-       "ao_samples": args.ao_samples, "transfer_samples": args.transfer_samples if args.env else None, "instances": {}}
+       "ao_samples": args.ao_samples, "transfer_samples": args.transfer_samples if args.env else None,
+       "glossy_samples": args.glossy_samples if args.env and args.glossy else None, "instances": {}}
 soft = dict(shadow_samples=args.shadow_samples, light_radius=args.light_radius, ao_samples=args.ao_samples)
 envs = [EnvLight.constant(1.0)]
+if args.glossy and not args.env:
+    ap.error("--glossy needs --env")
+if args.env and args.glossy:   # a sky brighter towards +z, prefiltered once
+    rows = torch.linspace(2.0, 0.2, 64)[None, :, None].expand(3, 64, 128)
+    maps = [EnvMap.from_equirect(rows.contiguous(), args.shininess, size=(64, 128))]
+    gloss = dict(transfer_samples=args.transfer_samples, glossy_samples=args.glossy_samples, shininess=args.shininess)
 with torch.no_grad():
     for K in (int(k) for k in args.instances.split(",")):
         zs, b2ws = scene.sample_scene(gen, K, args.seed)
@@ -90,5 +106,12 @@ with torch.no_grad():
         if args.env:
             row["scene_env_ms"] = median_ms(lambda: scene.render_scene_env(gen, zs, b2ws, envs, transfer_samples=args.transfer_samples))
             row["crops_env_ms"] = median_ms(crops_env)
+        if args.env and args.glossy:
+            capture = lambda: scene.trace_scene(gen, zs, b2ws).capture_transfer(args.transfer_samples, 0, scene.MAX_SHADOW_RAYS,
+                                                                                 args.glossy_samples, args.shininess)
+            cap = capture()
+            row["scene_gloss_capture_ms"] = median_ms(capture)
+            row["scene_gloss_shade_ms"] = median_ms(lambda: cap.shade(maps))
+            row["scene_gloss_ms"] = median_ms(lambda: scene.render_scene_env(gen, zs, b2ws, maps, **gloss))
         out["instances"][str(K)] = row
 print(json.dumps(out))

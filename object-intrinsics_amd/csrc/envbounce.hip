@@ -4,13 +4,13 @@
 //   env_shade_bounce      (transfer + bounce[ch]) . coefficients for F environments, one thread per pixel, its 36 values read once
 //                         (env_shade_common.h's pixel with the BOUNCE term)
 // The pixel shape and the sample count are checked by trace_common.h's check_pixels and check_samples, as envlight.hip's.
+// The per-sample term of bounce_resolve is bounce_common.h's bounce_sample, shared with scene_bounce.hip.
 // No atomics at all, no LDS, no scratch; every sum has one fixed order.
+#include "bounce_common.h"
 #include "env_shade_common.h"
 #include "../../include/oi_envbounce.h"
 
 namespace {
-
-static_assert(OI_BOUNCE_FLOATS == 3 * NC, "[3][9] per pixel");
 
 __global__ void __launch_bounds__(TR_THREADS) bounce_resolve_kernel(const uint8_t* __restrict__ status,
                                                                     const float* __restrict__ rays_d,
@@ -23,7 +23,8 @@ __global__ void __launch_bounds__(TR_THREADS) bounce_resolve_kernel(const uint8_
   const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
   if (i >= N) return;
   const int slot = hit_slot[i];
-  float acc[3][NC];
+  BounceSums sums;
+  auto& acc = sums.v;
 #pragma unroll
   for (int c = 0; c < NC; ++c) acc[0][c] = acc[1][c] = acc[2][c] = 0.f;
   if (slot >= 0 && n_hit2 > 0) {
@@ -32,17 +33,7 @@ __global__ void __launch_bounds__(TR_THREADS) bounce_resolve_kernel(const uint8_
       if (status[q] != OI_TRACE_HIT) continue;
       const long long k = hit_slot2[q];
       if (k < 0 || k >= n_hit2) continue;  // (a finished state lists every HIT; nothing is read outside grad2 / rgb2 whatever it holds)
-      float nx, ny, nz, t[NC];
-      unit_normal(grad2, k, nx, ny, nz);
-      if (!(nx * rays_d[q * 3 + 0] + ny * rays_d[q * 3 + 1] + nz * rays_d[q * 3 + 2] < 0.f)) continue;  // a back face
-      normal_transfer(w2b, nx, ny, nz, t);  // transfer_normal_kernel's closed form at the secondary hit
-      const float r0 = rgb2[k * 3 + 0], r1 = rgb2[k * 3 + 1], r2 = rgb2[k * 3 + 2];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        acc[0][c] = __fmaf_rn(r0, t[c], acc[0][c]);
-        acc[1][c] = __fmaf_rn(r1, t[c], acc[1][c]);
-        acc[2][c] = __fmaf_rn(r2, t[c], acc[2][c]);
-      }
+      sums = bounce_sample(grad2, rgb2, k, rays_d, q, w2b, sums);  // bounce_common.h: the term scene_bounce.hip shares
     }
     const float s = (float)S;
 #pragma unroll

@@ -63,9 +63,7 @@ __global__ void __launch_bounds__(TR_THREADS) scene_resolve_kernel(const oi_trac
 }
 
 __global__ void __launch_bounds__(TR_THREADS) scene_clear_hits_kernel(int* __restrict__ counts, int* __restrict__ live, int E) {
-  const int e = blockIdx.x * TR_THREADS + threadIdx.x;
-  if (e < E) counts[(long long)e * OI_TRACE_COUNT_WORDS + N_HIT_WORD] = 0;
-  if (e == 0) live[N_HIT_WORD] = 0;
+  clear_hit_words(counts, live, E);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) scene_visible_kernel(const oi_trace_state s, int* __restrict__ live,

@@ -1,7 +1,8 @@
-// What scene.hip, scene_light.hip and scene_gloss.hip share (include/oi_scene.h, include/oi_scene_light.h,
-// include/oi_scene_gloss.h; DESIGN sections 4.19, 4.21 and 4.25): the unit sphere's chord, the rigid transform and its
-// rotation, the begin of a sampled ray against every instance (one body for the cap, the hemisphere and the lobe), "missed
-// every instance", the per-pixel shading on the owner's slices and the checks of its arguments.  (What a begin kernel stores and the
+// What scene.hip, scene_light.hip, scene_gloss.hip and scene_bounce.hip share (include/oi_scene.h, include/oi_scene_light.h,
+// include/oi_scene_gloss.h, include/oi_scene_bounce.h; DESIGN sections 4.19, 4.21, 4.25 and 4.26): the unit sphere's chord, the
+// rigid transform and its rotation, the begin of a sampled ray against every instance (one body for the cap, the hemisphere and
+// the lobe), "missed every instance", the clearing of the hit words before a compaction into them, the per-pixel shading on the
+// owner's slices and the checks of its arguments and of the resolves'.  (What a begin kernel stores and the
 // compaction of the entered rays are trace_common.h's write_ray and enter_rays.)  Internal linkage, as trace_common.h.
 #ifndef OI_SCENE_COMMON_H_
 #define OI_SCENE_COMMON_H_
@@ -46,6 +47,14 @@ __global__ void __launch_bounds__(TR_THREADS) scene_clear_kernel(const oi_trace_
   clear_counts(v.counts, 0);
   const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
   if (r < s.N) v.points[r * 3 + 0] = v.points[r * 3 + 1] = v.points[r * 3 + 2] = 0.f;
+}
+
+// the hit words of every element and of live to 0, before a compaction into them (oi_scene_visible, oi_scene_bounce_visible):
+// the body of a one-dimensional launch over the elements
+__device__ __forceinline__ void clear_hit_words(int* __restrict__ counts, int* __restrict__ live, int E) {
+  const int e = blockIdx.x * TR_THREADS + threadIdx.x;
+  if (e < E) counts[(long long)e * OI_TRACE_COUNT_WORDS + N_HIT_WORD] = 0;
+  if (e == 0) live[N_HIT_WORD] = 0;
 }
 
 // R (the rotation of the rigid 4 x 4 M) applied to v, contraction off: tests/helpers/scene_light_ref.py restates it
@@ -193,6 +202,15 @@ inline int check_chunk(const char* what, int L, int S, int j0, int Sc) {
   OI_TRY(check_samples(what, S));
   OI_REQUIRE(j0 >= 0 && Sc >= 1 && j0 <= S - Sc, "%s: j0=%d, Sc=%d, S=%d (the chunk [j0, j0 + Sc) within [0, S), Sc >= 1)", what,
              j0, Sc, S);
+  return OI_OK;
+}
+
+// what the resolves share: the scene's shape and the size of the chunk's trace
+inline int check_resolve(const char* what, int E, long long N, int L, int Sc, long long n_vis, int scene_S) {
+  OI_TRY(check_scene_rays(what, E, N));
+  OI_TRY(check_resolution(what, "scene S", scene_S));
+  OI_REQUIRE(n_vis >= 1 && n_vis <= E * N && (long long)E * L * Sc * n_vis < (1ll << 31),
+             "%s: n_vis=%lld (1 <= n_vis <= E * N, E * L * Sc * n_vis < 2^31)", what, n_vis);
   return OI_OK;
 }
 

@@ -146,15 +146,6 @@ __global__ void __launch_bounds__(TR_THREADS) scene_shade_ao_kernel(const oi_sce
   scene_shade_pixel(p.s, p.ambient_occlusion);
 }
 
-// what the resolves share: the scene's shape and the size of the chunk's trace
-inline int check_resolve(const char* what, int E, long long N, int L, int Sc, long long n_vis, int scene_S) {
-  OI_TRY(check_scene_rays(what, E, N));
-  OI_TRY(check_resolution(what, "scene S", scene_S));
-  OI_REQUIRE(n_vis >= 1 && n_vis <= E * N && (long long)E * L * Sc * n_vis < (1ll << 31),
-             "%s: n_vis=%lld (1 <= n_vis <= E * N, E * L * Sc * n_vis < 2^31)", what, n_vis);
-  return OI_OK;
-}
-
 }  // namespace
 
 extern "C" {

@@ -18,7 +18,9 @@ times a reflection-lobe visibility that capture_transfer(glossy_samples=...) tra
     out = cap.shade([env, env.rotated(R)])            # image / shading / specular (2, 3, H, W); nothing is prefiltered again
 
 capture_transfer(bounces=1) folds one diffuse interreflection bounce into a per-channel transfer (include/oi_envbounce.h;
-DESIGN section 4.22): an EnvLight capture then also returns the indirect part of the shading.
+DESIGN section 4.22): an EnvLight capture then also returns the indirect part of the shading.  In a scene of many instances
+(oi_amd.scene.SceneSurface.capture_transfer(bounces=1); include/oi_scene_bounce.h) the bounce is between
+the instances too: the nearest instance a transfer ray meets reflects its colour.
 
 Bands above 2 of the diffuse term, more than one bounce and the bounce under an EnvMap are out of scope."""
 import math

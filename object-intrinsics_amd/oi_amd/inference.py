@@ -333,29 +333,34 @@ def env_walk(gen, z, b2w, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64
 
 @torch.no_grad()
 def scene_env_walk(gen, zs, b2ws, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64, seed=0, bg=None, bias=None, window=None,
-                   max_shadow_rays=None, glossy_samples=None, shininess=None, specular=None, **kw):
+                   max_shadow_rays=None, glossy_samples=None, shininess=None, specular=None, bounces=0, **kw):
     """env_walk on a scene of K instances (oi_amd.scene): ONE scene trace and ONE capture
     (SceneSurface.capture_transfer: transfer_samples secondary rays per visible point, each tested against every instance),
     then n_frames rotations of the 9 x 3 coefficients on the host and one shade launch per 256 frames.  Frame 0 is `env`
     itself.  -> {"image", "shading": (n_frames, 3, S, S), "transfer": (1, 9, S, S), "mask" / "depth" / "instance" (1, 1, S, S),
     "stats"}.  An EnvMap takes the glossy path (glossy_samples, shininess: capture_transfer's; specular:
     shade's): the map is prefiltered once, when it is made, and every frame only rotates the lookup; the result also holds
-    "specular" (n_frames, 3, S, S), "spec_visibility" and "reflection".  kw: tol, omega, max_steps, readback of sphere_trace."""
+    "specular" (n_frames, 3, S, S), "spec_visibility" and "reflection".  bounces=1 (an EnvLight; capture_transfer's rules): one
+    diffuse interreflection bounce between the instances, traced once with the capture; the result also
+    holds "indirect" (n_frames, 3, S, S) and "bounce" (1, 3, 9, S, S).  kw: tol, omega, max_steps, readback of sphere_trace."""
     from . import scene, trace
     from .envlight import EnvLight, EnvMap
     if not isinstance(env, (EnvLight, EnvMap)):
         raise TypeError(f"scene_env_walk: expected an EnvLight or an EnvMap, got {type(env).__name__}")
     rots = env_walk_rotations(n_frames, axis)
-    trace._check_transfer(transfer_samples, seed, "scene_env_walk")
+    samples, _ = trace._check_transfer(transfer_samples, seed, "scene_env_walk")
+    trace._check_bounces(bounces, samples, glossy_samples, shininess, "scene_env_walk")
     trace._check_glossy(gen, glossy_samples, shininess, "scene_env_walk")
     gen.eval()
     gen.renderer.pack.check()
     limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
     s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, **kw)
-    cap = s.capture_transfer(transfer_samples, seed, limit, glossy_samples, shininess)
+    cap = s.capture_transfer(transfer_samples, seed, limit, glossy_samples, shininess, bounces)
     out = cap.shade([env.rotated(R) for R in rots], bg, specular)
     res = {k: out[k] for k in ("image", "shading", "mask", "depth", "instance")}
     res.update(transfer=cap.transfer, stats=cap.scene.stats())
+    if cap.bounce is not None:
+        res.update(indirect=out["indirect"], bounce=cap.bounce)
     if isinstance(env, EnvMap):
         res.update(specular=out["specular"], spec_visibility=cap.spec_visibility, reflection=cap.reflection)
     return res

@@ -365,6 +365,13 @@ SIGS = {
         "oi_scene_reflect": (_i, [_vp, _vp, _vp, _ll] + [_vp] * 4 + [_i, _ll, _i, _vp, _vp]),
         "oi_env_shade_glossy_dirs": (_i, [_P(EnvShadeParams), _vp, _vp, _vp, _i, _i, _i, _P(_i), _vp, _vp, _vp, _vp]),
     },
+    # include/oi_scene_bounce.h: one diffuse interreflection bounce between the instances of a scene (an addition to
+    # oi_scene_light.h and oi_envbounce.h; no struct of its own: plain arguments, and the batch of oi_trace_batch.h)
+    "oi_scene_bounce.h": {
+        "oi_scene_bounce_nearest": (_i, [_vp, _vp, _i, _ll, _vp, _vp]),
+        "oi_scene_bounce_visible": (_i, [_P(TraceBatch), _vp, _vp, _vp, _vp]),
+        "oi_scene_bounce_resolve": (_i, [_vp] * 5 + [_ll] + [_vp] * 5 + [_i, _ll, _i, _i, _i, _ll, _i, _i, _vp, _vp]),
+    },
 }
 
 

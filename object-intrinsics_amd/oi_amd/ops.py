@@ -1222,6 +1222,41 @@ def env_shade_glossy_dirs(status, hit_slot, rgb, n_hit, transfer, envs, dirs, sp
 
 
 # ------------------------------------------------------------------------------------------
+# one diffuse interreflection bounce between the instances of a scene (include/oi_scene_bounce.h); oi_amd.scene sequences these
+# ------------------------------------------------------------------------------------------
+
+def scene_bounce_nearest(status, t, E, rays):
+    """The finished states status (E, rays) uint8 and ray parameters t (E, rays) of a closest-hit batch -> winner (rays,) int32:
+    the element whose HIT is nearest (the lowest index on equal t), -1 without one or when the ray ended in any element in a
+    status other than MISS or HIT."""
+    winner = _new(t, int(rays)).view(torch.int32)
+    _l.check(_l.load().oi_scene_bounce_nearest(_p(status), _p(t), int(E), int(rays), _ip(winner), _stream()),
+             "oi_scene_bounce_nearest")
+    return winner
+
+
+def scene_bounce_visible(sb, winner):
+    """-> sel_index (E, N) int32 (the first n_sel_e entries of row e are written: the rays element e wins), sel_slot (E, N)
+    int32 (-1 where the ray is not won).  Overwrites the hit words of sb.counts and sb.live with the selected counts."""
+    sel_index = torch.empty(sb.E, sb.N, dtype=torch.int32, device=sb.t.device)
+    sel_slot = _new(sb.t, sb.E, sb.N).view(torch.int32)
+    _l.check(_l.load().oi_scene_bounce_visible(ctypes.byref(sb.c), _ip(winner), _ip(sel_index), _ip(sel_slot), _stream()),
+             "oi_scene_bounce_visible")
+    return sel_index, sel_slot
+
+
+def scene_bounce_resolve(winner, sel_slot, rays_d, grad2, rgb2, n_pad2, owner, owner_ray, vis_slot, offset, w2b, E, N, samples, j0,
+                         chunk, n_vis, S, bounce, last):
+    """Adds the chunk's front-face winners' albedo A_band y_c(world normal) to bounce (3, 9, S * S) (overwritten at j0 == 0);
+    last: divided by samples.  grad2, rgb2 (E, n_pad2, 3): the full pass at the gathered points (None with n_pad2 == 0)."""
+    g2, c2 = (_c(grad2), _c(rgb2)) if n_pad2 else (None, None)
+    _l.check(_l.load().oi_scene_bounce_resolve(_ip(winner), _ip(sel_slot), _p(rays_d), _p(g2), _p(c2), int(n_pad2), _ip(owner),
+                                               _ip(owner_ray), _ip(vis_slot), _ip(offset), _p(_c(w2b)), int(E), int(N), int(samples),
+                                               int(j0), int(chunk), int(n_vis), int(S), int(bool(last)), _p(bounce), _stream()),
+             "oi_scene_bounce_resolve")
+
+
+# ------------------------------------------------------------------------------------------
 # discriminator side
 # ------------------------------------------------------------------------------------------
 

@@ -13,7 +13,9 @@ and environment lighting (include/oi_scene_light.h).
                    against every instance: contact shadows between objects
     render_scene   both
     SceneSurface.capture_transfer  the secondary rays traced ONCE into a per-pixel SH transfer map of the whole scene ->
-                   SceneTransfer, shaded under any number of environment lights (oi_amd.envlight.EnvLight)
+                   SceneTransfer, shaded under any number of environment lights (oi_amd.envlight.EnvLight); with bounces=1 the
+                   rays that end on ANY instance carry one diffuse interreflection bounce (include/oi_scene_bounce.h; DESIGN
+                   section 4.26): the instances colour each other
     render_scene_env  trace_scene + capture_transfer + shade
 
 The union of K surfaces is traced exactly by tracing each instance in its own box frame and keeping the nearest hit per
@@ -123,6 +125,7 @@ class SceneSurface:
         self.owner = self.owner_ray = self.vis_slot = self.offset = self.points = self.grad = self.rgb = None
         self._world = self._pixel = self.vis_index = self.shadow = self.ao = self.transfer_state = None
         self.glossy_evals, self.glossy_state, self._reflect = 0, None, None
+        self.bounce_points, self.bounce_hits = 0, None
         bound = int(st.live[0].item())
         self.n_entered = st.counts[:, 0].tolist()
         if bound == 0:      # nothing enters a window: every ray is a MISS already
@@ -158,12 +161,14 @@ class SceneSurface:
                                                  sum(self.n_vis))
         return self._pixel
 
-    def _sampled(self, what, samples, seed, max_shadow_rays, resolve, lights=None, radius=None, distance=None, *, lobe=None):
+    def _sampled(self, what, samples, seed, max_shadow_rays, resolve, lights=None, radius=None, distance=None, *, lobe=None,
+                 anyhit=True):
         """The sampled any-hit trace against every instance, in chunks of the samples: a chunk holds E * L * Sc * n_vis rays, Sc
         the largest number for which that stays within max_shadow_rays and below 2^31.  resolve(sb, j0, Sc, last) accumulates
         each finished chunk.  lights and radius: caps about the lights; distance: the hemisphere about the normal; lobe (a
-        shininess): the reflection lobe about the reflected view vector (include/oi_scene_gloss.h).  -> (sdf evaluations per
-        element, the last chunk's state)."""
+        shininess): the reflection lobe about the reflected view vector (include/oi_scene_gloss.h).  anyhit False: the same rays
+        marched to their CLOSEST hit (oi_trace_batch_step), what the bounce follows (include/oi_scene_bounce.h).  -> (sdf
+        evaluations per element, the last chunk's state)."""
         L, n_vis = 1 if lights is None else lights.shape[0], sum(self.n_vis)
         per = self.E * L * n_vis
         chunk = min(int(samples), min(int(max_shadow_rays), (1 << 31) - 1) // per)
@@ -184,7 +189,7 @@ class SceneSurface:
                                      elem, pixel, pos, nrm, n_vis, self.w2b, self.bias, samples, j0, c, lobe, seed)
             bound = int(sb.live[0].item())
             if bound:
-                total, _ = _t._march_batch(self.field, sb, *self.kw, bound=bound, anyhit=True)
+                total, _ = _t._march_batch(self.field, sb, *self.kw, bound=bound, anyhit=anyhit)
                 evals += total
                 ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
             resolve(sb, j0, c, j0 + c == int(samples))
@@ -260,6 +265,40 @@ class SceneSurface:
         self.transfer_evals += evals
         return out
 
+    def transfer_bounce(self, samples, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """transfer()'s (9, S * S) map and the bounce transfer (3, 9, S * S) of the same rays (include/oi_scene_bounce.h): the rays
+        are marched to their closest hit in every instance; per chunk the direct transfer is resolved as by transfer(), then
+        the nearest instance of every ray is found, the full MLP pass runs at the hits that win (E * n_pad2 points; skipped
+        when nothing wins) and oi_scene_bounce_resolve folds their albedo and normals into the running sums.  samples >= 1.
+        Without a visible point: zeros, nothing launched."""
+        M, n_vis, E = self.S * self.S, sum(self.n_vis), self.E
+        if n_vis == 0:
+            return (torch.zeros(_l.ENV_COEFFS, M, device=self.b2w.device), torch.zeros(3, _l.ENV_COEFFS, M, device=self.b2w.device))
+        out, bounce = ops._new(self.b2w, _l.ENV_COEFFS, M), ops._new(self.b2w, 3, _l.ENV_COEFFS, M)
+
+        def resolve(sb, j0, c, last):
+            ops.scene_transfer_resolve(sb.status, sb.rays_d, self.owner, self.owner_ray, self.vis_slot, self.offset, self.w2b, E, self.N,
+                                       samples, j0, c, n_vis, self.S, out, last)
+            winner = ops.scene_bounce_nearest(sb.status, sb.t, E, sb.N)
+            sel_index, sel_slot = ops.scene_bounce_visible(sb, winner)
+            n_pad2 = int(sb.live[-1].item())
+            points2 = grad2 = rgb2 = None
+            if n_pad2:
+                self.bounce_points += sum(sb.counts[:, -1].tolist())
+                points2 = ops.trace_batch_gather(sb, sel_index, n_pad2)
+                _, grad2, rgb2 = self.field.full(points2.view(E * n_pad2, 3))
+                grad2, rgb2 = grad2.view(E, n_pad2, 3), rgb2.view(E, n_pad2, 3)
+            ops.scene_bounce_resolve(winner, sel_slot, sb.rays_d, grad2, rgb2, n_pad2, self.owner, self.owner_ray, self.vis_slot,
+                                     self.offset, self.w2b, E, self.N, samples, j0, c, n_vis, self.S, bounce, last)
+            # what oi_scene_bounce_resolve read for the last chunk (samples j0 .. j0 + c - 1; ray jj * n_vis + g)
+            self.bounce_hits = dict(j0=j0, chunk=c, winner=winner, sel_index=sel_index, sel_slot=sel_slot, n_pad2=n_pad2,
+                                    points=points2, grad=grad2, rgb=rgb2)
+
+        evals, self.transfer_state = self._sampled("SceneSurface.capture_transfer", samples, seed, max_shadow_rays, resolve,
+                                                   distance=math.inf, anyhit=False)
+        self.transfer_evals += evals
+        return out, bounce
+
     def lobe_visibility(self, samples, shininess, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
         """(S * S,) reflection-lobe visibility V_spec (include/oi_scene_gloss.h): the share of `samples` rays per visible point,
         distributed as cos^shininess about the reflected view vector, that are above the point's horizon and meet no instance
@@ -287,7 +326,8 @@ class SceneSurface:
                                                   self.vis_slot, self.w2b, self.E, self.N, self.S)
         return self._reflect
 
-    def capture_transfer(self, transfer_samples=64, seed=0, max_shadow_rays=MAX_SHADOW_RAYS, glossy_samples=None, shininess=None):
+    def capture_transfer(self, transfer_samples=64, seed=0, max_shadow_rays=MAX_SHADOW_RAYS, glossy_samples=None, shininess=None,
+                         bounces=0):
         """The scene prepared for environment lighting: `transfer_samples` (0 .. 256) cosine-weighted rays per visible point,
         each tested against EVERY instance, resolved into a 9-coefficient world-frame transfer vector per scene pixel (0: the
         unshadowed closed form, nothing traced).
@@ -295,13 +335,22 @@ class SceneSurface:
         about the reflected view vector, distributed as cos^shininess and tested against every instance, into spec_visibility;
         shininess None takes the generator's learned value; glossy_samples = 0 prepares a glossy capture without that trace
         (V_spec = 1), and a shininess without glossy_samples is refused (oi_amd.trace.capture_transfer's rules).  With both left
-        at None the launches and outputs are those of a call without them.  -> SceneTransfer."""
+        at None the launches and outputs are those of a call without them.
+        bounces = 1 (the integer; with transfer_samples >= 1, not with the glossy keywords) follows the transfer rays to their
+        nearest intersection with ANY instance and folds one diffuse interreflection bounce between the instances -- and of an
+        instance on itself -- into a per-channel transfer, SceneTransfer.bounce (include/oi_scene_bounce.h has the estimator and
+        its approximations); the direct transfer is bit for bit that of bounces = 0, which launches what it always did.
+        -> SceneTransfer."""
         samples, seed = _t._check_transfer(transfer_samples, seed, "SceneSurface.capture_transfer")
+        bounces = _t._check_bounces(bounces, samples, glossy_samples, shininess, "SceneSurface.capture_transfer")
         g_samples, shin, spec = _t._check_glossy(getattr(self, "gen", None), glossy_samples, shininess, "SceneSurface.capture_transfer")
-        transfer = self.transfer(samples, seed, max_shadow_rays)
+        if bounces:
+            transfer, bounce = self.transfer_bounce(samples, seed, max_shadow_rays)
+        else:
+            transfer, bounce = self.transfer(samples, seed, max_shadow_rays), None
         out = self._shade(None, None, None, ("depth", "position", "normal_world", "albedo", "mask", "instance"))
         if g_samples is None:
-            return SceneTransfer(self, transfer, out, samples)
+            return SceneTransfer(self, transfer, out, samples, bounce=bounce)
         vis = self.lobe_visibility(g_samples, shin, seed, max_shadow_rays) if g_samples else None
         return SceneTransfer(self, transfer, out, samples, g_samples, shin, spec, vis, self.reflection())
 
@@ -360,7 +409,7 @@ class SceneSurface:
     def stats(self):
         """Per instance: rays entered and culled, rays per status (culled rays are misses), hits, visible hits; sdf
         evaluations of the primary march and of the shadow, ambient-occlusion, transfer and reflection-lobe marches so far (every
-        instance carries the batch's bound)."""
+        instance carries the batch's bound); bounce_points: the secondary hits the bounce evaluated, over all chunks and instances."""
         st = self.state
         per = torch.stack([torch.bincount(st.status[e].long(), minlength=6)[:6] for e in range(self.E)]).tolist()
         out = []
@@ -368,7 +417,8 @@ class SceneSurface:
             s = {name: int(per[e][code]) for code, name in _l.TRACE_STATUS_NAMES.items()}
             s.update(n_rays=self.N, entered=int(self.n_entered[e]), culled=self.N - int(self.n_entered[e]), hits=int(self.n_hit[e]),
                      visible=int(self.n_vis[e]), n_evals=self.n_evals, n_steps=self.n_steps, shadow_evals=self.shadow_evals,
-                     occlusion_evals=self.occlusion_evals, transfer_evals=self.transfer_evals, glossy_evals=self.glossy_evals)
+                     occlusion_evals=self.occlusion_evals, transfer_evals=self.transfer_evals, glossy_evals=self.glossy_evals,
+                     bounce_points=self.bounce_points)
             out.append(s)
         return out
 
@@ -382,14 +432,18 @@ class SceneTransfer:
     scene: the SceneSurface; transfer (1, 9, S, S), world frame; maps: SceneSurface.shade's G-buffer maps (depth, position,
     normal_map, albedo, mask, instance); samples: the rays per visible point (0: the closed form).  A capture made with
     glossy_samples also holds the shininess its lobe was traced for, specular (the learned specular colour), spec_visibility
-    (1, 1, S, S) (None with glossy_samples = 0: V_spec = 1) and reflection (1, 3, S, S), the world-frame reflected view vector."""
+    (1, 1, S, S) (None with glossy_samples = 0: V_spec = 1) and reflection (1, 3, S, S), the world-frame reflected view vector.
+    A capture made with bounces=1 also holds bounce (1, 3, 9, S, S), the per-channel transfer of one diffuse interreflection
+    bounce between the instances (None otherwise; include/oi_scene_bounce.h)."""
 
     def __init__(self, scene, transfer, planes, samples, glossy_samples=None, shininess=None, specular=None, spec_vis=None,
-                 reflection=None):
+                 reflection=None, bounce=None):
         S = scene.S
         self.scene, self.samples, self.S = scene, samples, S
         self._transfer = transfer                       # (9, S * S), planar: what oi_env_shade reads
         self.transfer = transfer.view(1, _l.ENV_COEFFS, S, S)
+        self._bounce = bounce                           # (3, 9, S * S), planar, or None: what oi_env_shade_bounce reads
+        self.bounce = None if bounce is None else bounce.view(1, 3, _l.ENV_COEFFS, S, S)
         self.maps = {_MAP_NAMES[k]: v for k, v in _t._maps(planes, S, S).items()}
         # oi_env_shade's view of the scene's planes: every scene pixel is a ray, the owned ones are hits at their own index
         M, dev = S * S, transfer.device
@@ -406,7 +460,8 @@ class SceneTransfer:
     def shade(self, envs, bg=None, specular=None):
         """The scene under each of `envs` (any number: launches of ENV_MAX_ENVS).
         EnvLight objects: -> {"image": (F, 3, S, S) = max(shading, 0) albedo on the mask, bg off it; "shading": (F, 3, S, S), not
-        clamped; the G-buffer maps; "stats"}.
+        clamped; the G-buffer maps; "stats"}.  On a capture made with bounces=1 (oi_env_shade_bounce) shading = direct + indirect, and
+        "indirect": (F, 3, S, S) is the bounce's part.
         EnvMap objects (every element; a mixed list is refused), on a capture made with glossy_samples: the glossy path
         (include/oi_scene_gloss.h), image = max(shading, 0) albedo + specular and "specular": (F, 3, S, S) = k_s V_spec
         G_s(reflected view vector), V_spec knowing every instance.  k_s = `specular`: None takes the generator's learned specular
@@ -420,6 +475,10 @@ class SceneTransfer:
             raise ValueError("SceneTransfer.shade: EnvMap and EnvLight objects in one list (shade them in two calls)")
         if not glossy and specular is not None:
             raise ValueError("SceneTransfer.shade: specular= needs EnvMap environments (an EnvLight has no glossy half)")
+        bounce = getattr(self, "_bounce", None)
+        if glossy and bounce is not None:
+            raise ValueError("SceneTransfer.shade: EnvMap environments on a capture made with bounces=1 (the glossy shade has no "
+                             "bounce input yet; shade EnvLight objects, or capture without the bounce)")
         if glossy and self.glossy_samples is None:
             raise ValueError("SceneTransfer.shade: this capture has no reflection-lobe trace; capture_transfer(glossy_samples=S) "
                              "traces one, glossy_samples=0 with a shininess states that V_spec = 1 is meant")
@@ -430,7 +489,7 @@ class SceneTransfer:
         dev, M = self._transfer.device, S * S
         F = len(seq)
         bgv = _t._bg(bg, dev)
-        names = ops.ENV_GLOSSY_OUT if glossy else ops.ENV_SHADE_OUT
+        names = ops.ENV_GLOSSY_OUT if glossy else ops.ENV_SHADE_OUT if bounce is None else ops.ENV_BOUNCE_OUT
         view = (self._status, self._hit_slot, self._rgb, M, self._transfer)
         if s.n_pad == 0:   # no hit at all: nothing is launched
             out = {k: ops._new(self._transfer, F, 3, M) for k in names}
@@ -440,7 +499,11 @@ class SceneTransfer:
             out["image"].copy_((torch.zeros(3, device=dev) if bgv is None else bgv).view(1, 3, 1).expand(F, 3, M))
         elif not glossy:
             ev = stack_envs(seq, dev)
-            out = _t._shade_chunks(self._transfer, names, F, M, lambda a, b, out: ops.env_shade(*view, ev[a:b], bgv, out=out))
+            if bounce is None:
+                launch = lambda a, b, out: ops.env_shade(*view, ev[a:b], bgv, out=out)
+            else:
+                launch = lambda a, b, out: ops.env_shade_bounce(*view, bounce, ev[a:b], bgv, out=out)
+            out = _t._shade_chunks(self._transfer, names, F, M, launch)
         else:
             ks = self.specular if specular is None else specular
             ks = torch.as_tensor(np.broadcast_to(np.asarray(ks, dtype=np.float32), (3,)).copy()).to(dev)
@@ -486,19 +549,23 @@ def render_scene(gen, zs, b2ws, lights=None, shadows=False, bg=None, window=None
 
 @torch.no_grad()
 def render_scene_env(gen, zs, b2ws, envs, transfer_samples=64, seed=0, bg=None, window=None, bias=DEFAULT_BIAS,
-                     max_shadow_rays=MAX_SHADOW_RAYS, glossy_samples=None, shininess=None, specular=None, **trace_kw):
+                     max_shadow_rays=MAX_SHADOW_RAYS, glossy_samples=None, shininess=None, specular=None, bounces=0, **trace_kw):
     """trace_scene + capture_transfer + shade: K instances in one scene image under the environment lights `envs`
     (oi_amd.envlight.EnvLight objects, or EnvMap objects with glossy_samples given: capture_transfer's and shade's keywords pass
     through), every instance occluding the sky for itself and for the others -- and, on the glossy path, standing in the
     others' reflections.  -> SceneTransfer.shade's dict, with "transfer" (1, 9, S, S), "scene" (the SceneSurface) and "capture"
     (the SceneTransfer); on the glossy path also "specular" (F, 3, S, S), "spec_visibility" (1, 1, S, S) or None and
-    "reflection" (1, 3, S, S)."""
-    _t._check_transfer(transfer_samples, seed, "render_scene_env")
+    "reflection" (1, 3, S, S); with bounces=1 (EnvLight objects only) also "indirect" (F, 3, S, S) and "bounce" (1, 3, 9, S, S):
+    the instances colour each other."""
+    samples, _ = _t._check_transfer(transfer_samples, seed, "render_scene_env")
+    _t._check_bounces(bounces, samples, glossy_samples, shininess, "render_scene_env")
     _t._check_glossy(gen, glossy_samples, shininess, "render_scene_env")
     s = trace_scene(gen, zs, b2ws, window, bias, **trace_kw)
-    cap = s.capture_transfer(transfer_samples, seed, max_shadow_rays, glossy_samples, shininess)
+    cap = s.capture_transfer(transfer_samples, seed, max_shadow_rays, glossy_samples, shininess, bounces)
     res = cap.shade(envs, bg, specular)
     res.update(transfer=cap.transfer, scene=s, capture=cap)
+    if cap.bounce is not None:
+        res["bounce"] = cap.bounce
     if cap.glossy_samples is not None:
         res.update(spec_visibility=cap.spec_visibility, reflection=cap.reflection)
     return res

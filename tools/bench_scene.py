@@ -20,7 +20,18 @@ With --env --glossy the glossy lobe of DESIGN section 4.25 is timed per K beside
   scene_gloss_capture_ms         trace_scene + SceneSurface.capture_transfer with --glossy-samples reflection-lobe rays per
                                  visible point on top of the transfer rays, every ray tested against all K instances
   scene_gloss_shade_ms           SceneTransfer.shade of that capture under one prefiltered 64 x 128 map (one launch)
-  scene_gloss_ms                 oi_amd.scene.render_scene_env on the glossy path: the two together"""
+  scene_gloss_ms                 oi_amd.scene.render_scene_env on the glossy path: the two together
+With --env --bounce the interreflection bounce between the instances of DESIGN section 4.26 is timed per K beside the plain capture
+of the same run:
+
+  scene_env_capture_ms / scene_env_shade_ms        trace_scene + SceneSurface.capture_transfer, and SceneTransfer.shade of it under one
+                                                   environment, without the bounce (what scene_env_ms is made of)
+  scene_bounce_capture_ms / scene_bounce_shade_ms  the same with bounces=1: the transfer rays marched to their closest hit, the winner
+                                                   of every ray, one padded full MLP pass per chunk, the bounce resolve; the shade with
+                                                   the bounce transfer
+  scene_bounce_ms                oi_amd.scene.render_scene_env(bounces=1): the two together
+  bounce_points / n_pad2         the secondary hits evaluated (over all chunks and instances) and the last chunk's padded row length
+--skip-crops leaves out the crops_* rows (K single-view renders each)."""
 import argparse
 import copy
 import json
@@ -51,6 +62,8 @@ ap.add_argument("--transfer-samples", type=int, default=64)
 ap.add_argument("--glossy", action="store_true", help="with --env: also time the glossy capture and shade (scene_gloss_*_ms)")
 ap.add_argument("--glossy-samples", type=int, default=64, help="reflection-lobe rays per visible point")
 ap.add_argument("--shininess", type=float, default=10.0)
+ap.add_argument("--bounce", action="store_true", help="with --env: also time the capture and shade with bounces=1 (scene_bounce_*_ms)")
+ap.add_argument("--skip-crops", action="store_true", help="leave out the crops_* comparison rows")
 args = ap.parse_args()
 
 
@@ -74,11 +87,12 @@ gen.eval()
 out = {"tool": "bench_scene", "precision": args.precision, "res": args.res, "scene_resolution": gen.scene_resolution,
        "iters": args.iters, "warmup": args.warmup, "shadow_samples": args.shadow_samples, "light_radius": args.light_radius,
        "ao_samples": args.ao_samples, "transfer_samples": args.transfer_samples if args.env else None,
-       "glossy_samples": args.glossy_samples if args.env and args.glossy else None, "instances": {}}
+       "glossy_samples": args.glossy_samples if args.env and args.glossy else None, "bounce": bool(args.env and args.bounce),
+       "instances": {}}
 soft = dict(shadow_samples=args.shadow_samples, light_radius=args.light_radius, ao_samples=args.ao_samples)
 envs = [EnvLight.constant(1.0)]
-if args.glossy and not args.env:
-    ap.error("--glossy needs --env")
+if (args.glossy or args.bounce) and not args.env:
+    ap.error("--glossy and --bounce need --env")
 if args.env and args.glossy:   # a sky brighter towards +z, prefiltered once
     rows = torch.linspace(2.0, 0.2, 64)[None, :, None].expand(3, 64, 128)
     maps = [EnvMap.from_equirect(rows.contiguous(), args.shininess, size=(64, 128))]
@@ -102,10 +116,12 @@ with torch.no_grad():
         for name, shadows in (("", False), ("_shadows", True)):
             kw = soft if shadows else {}
             row["scene" + name + "_ms"] = median_ms(lambda: scene.render_scene(gen, zs, b2ws, shadows=shadows, **kw))
-            row["crops" + name + "_ms"] = median_ms(lambda: crops(shadows))
+            if not args.skip_crops:
+                row["crops" + name + "_ms"] = median_ms(lambda: crops(shadows))
         if args.env:
             row["scene_env_ms"] = median_ms(lambda: scene.render_scene_env(gen, zs, b2ws, envs, transfer_samples=args.transfer_samples))
-            row["crops_env_ms"] = median_ms(crops_env)
+            if not args.skip_crops:
+                row["crops_env_ms"] = median_ms(crops_env)
         if args.env and args.glossy:
             capture = lambda: scene.trace_scene(gen, zs, b2ws).capture_transfer(args.transfer_samples, 0, scene.MAX_SHADOW_RAYS,
                                                                                  args.glossy_samples, args.shininess)
@@ -113,5 +129,15 @@ with torch.no_grad():
             row["scene_gloss_capture_ms"] = median_ms(capture)
             row["scene_gloss_shade_ms"] = median_ms(lambda: cap.shade(maps))
             row["scene_gloss_ms"] = median_ms(lambda: scene.render_scene_env(gen, zs, b2ws, maps, **gloss))
+        if args.env and args.bounce:
+            for name, b in (("env", 0), ("bounce", 1)):
+                capture = lambda: scene.trace_scene(gen, zs, b2ws).capture_transfer(args.transfer_samples, 0, scene.MAX_SHADOW_RAYS, bounces=b)
+                cap = capture()
+                row[f"scene_{name}_capture_ms"] = median_ms(capture)
+                row[f"scene_{name}_shade_ms"] = median_ms(lambda: cap.shade(envs))
+            row["scene_bounce_ms"] = median_ms(lambda: scene.render_scene_env(gen, zs, b2ws, envs, transfer_samples=args.transfer_samples,
+                                                                             bounces=1))
+            row["bounce_points"] = cap.scene.bounce_points
+            row["n_pad2"] = cap.scene.bounce_hits["n_pad2"] if cap.scene.bounce_hits else 0
         out["instances"][str(K)] = row
 print(json.dumps(out))

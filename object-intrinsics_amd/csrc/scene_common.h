@@ -2,7 +2,8 @@
 // include/oi_scene_gloss.h, include/oi_scene_bounce.h; DESIGN sections 4.19, 4.21, 4.25 and 4.26): the unit sphere's chord, the
 // rigid transform and its rotation, the begin of a sampled ray against every instance (one body for the cap, the hemisphere and
 // the lobe), "missed every instance", the clearing of the hit words before a compaction into them, the per-pixel shading on the
-// owner's slices and the checks of its arguments and of the resolves'.  (What a begin kernel stores and the
+// owner's slices and the checks of its arguments and of the resolves'; for local_light.hip (include/oi_local_light.h; DESIGN
+// section 4.27) the begin of a ray aimed at a local light against every instance.  (What a begin kernel stores and the
 // compaction of the entered rays are trace_common.h's write_ray and enter_rays.)  Internal linkage, as trace_common.h.
 #ifndef OI_SCENE_COMMON_H_
 #define OI_SCENE_COMMON_H_
@@ -148,6 +149,55 @@ __device__ __forceinline__ void scene_sampled_begin(const oi_trace_state& s, int
   enter_rays(v, q, entered, px, py, pz, lds, live);
 }
 
+// One ray of oi_scene_local_light_begin (local_light.hip; include/oi_local_light.h): scene_sampled_begin's layout with the
+// direction aimed at a local light (trace_common.h's aimed_sample, drawn once in the owner's frame, where the light's world
+// position is moved) and every ray clipped to the light: the owner's far = min(t_light, the sphere's exit); another
+// instance's chord is cut at t_light, the rule `distance` has for the hemisphere.
+__device__ __forceinline__ void scene_local_begin(const oi_trace_state& s, int* __restrict__ live,
+                                                  const oi_scene_occlusion_params& p, unsigned* lds) {
+  const int eo = blockIdx.y;  // the occluder
+  const oi_trace_state v = element_view(s, eo);
+  const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
+  bool entered = false;
+  float px = 0.f, py = 0.f, pz = 0.f;
+  if (q < s.N) {
+    const long long lj = q / p.n_vis, gi = q - lj * p.n_vis;
+    const long long l = lj / p.Sc;
+    const unsigned j = (unsigned)p.j0 + (unsigned)(lj - l * p.Sc);
+    const int e = p.elem[gi];  // the point's owner
+    const long long slot = gi - p.offset[e], k = (long long)e * p.n_pad + slot;
+    const float* We = p.w2b + (long long)e * 16;
+    float n[3], o[3], lq[3], R;
+    unit_normal(p.grad, k, n[0], n[1], n[2]);
+    offset_origin(p.hit_points + k * 3, p.bias, n[0], n[1], n[2], o[0], o[1], o[2]);
+    local_light_position(p.lights + l * OI_LOCAL_LIGHT_FLOATS, We, lq, R);
+    const AimedSample a = aimed_sample(o, n, lq, R, (unsigned)p.pixel[gi], p.seed, j, p.S);
+    float d[3] = {a.d[0], a.d[1], a.d[2]};
+    float near_ = 0.f, far_ = 0.f;
+    unsigned status = a.kind == AIMED_INSIDE ? OI_TRACE_MISS : OI_TRACE_BACKFACING;
+    if (a.kind == AIMED_TRACED && e == eo) {
+      far_ = fminf(a.t_light, unit_sphere_exit(o[0], o[1], o[2], d[0], d[1], d[2]));
+      entered = true;
+      status = OI_TRACE_MARCH;
+    } else if (a.kind == AIMED_TRACED) {
+      const float* Wb = p.w2b + (long long)eo * 16;
+      float ow[3], dw[3], dd[3];
+      offset_origin(p.position + gi * 3, p.bias, p.normal[gi * 3 + 0], p.normal[gi * 3 + 1], p.normal[gi * 3 + 2], ow[0], ow[1], ow[2]);
+      transform_point(Wb, ow, o);
+      rotate_t(We, d, dw);
+      rotate(Wb, dw, dd);
+      d[0] = dd[0], d[1] = dd[1], d[2] = dd[2];
+      entered = unit_sphere_chord(o, d, near_, far_) && near_ < a.t_light;
+      far_ = fminf(far_, a.t_light);
+      status = entered ? OI_TRACE_MARCH : OI_TRACE_MISS;
+    }
+    if (!entered) near_ = far_ = 0.f;
+    write_ray(v, q, o, d, near_, far_, status);
+    px = __fmaf_rn(near_, d[0], o[0]), py = __fmaf_rn(near_, d[1], o[1]), pz = __fmaf_rn(near_, d[2], o[2]);
+  }
+  enter_rays(v, q, entered, px, py, pz, lds, live);
+}
+
 // did ray `ray` (of `rays` per element) end OI_TRACE_MISS in every element?  A fixed-order loop, no early exit.
 __device__ __forceinline__ bool escaped_everywhere(const uint8_t* __restrict__ status, int E, long long rays, long long ray) {
   bool free_ = true;
@@ -166,6 +216,8 @@ struct ElementSurface {
 };
 
 // One scene pixel of oi_scene_shade / oi_scene_shade_ao: trace_common.h's shading on the owner's slices.  ao: [S * S] or nullptr.
+// LOCAL (oi_scene_shade_local): p.lights are local records, shaded by trace_common.h's surface_shade_local_at.
+template <bool LOCAL = false>
 __device__ __forceinline__ void scene_shade_pixel(const oi_scene_shade_params& p, const float* __restrict__ ao) {
   const long long M = (long long)p.S * p.S, N = (long long)p.W * p.W;
   const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
@@ -187,7 +239,8 @@ __device__ __forceinline__ void scene_shade_pixel(const oi_scene_shade_params& p
     if (hit) transform_point(p.b2w + eo * 16, v.hit_points + (long long)v.hit_slot[r] * 3, w);
     p.position[q * 3 + 0] = w[0], p.position[q * 3 + 1] = w[1], p.position[q * 3 + 2] = w[2];
   }
-  surface_shade_at(v, ao, r, hit, q, M);
+  if constexpr (LOCAL) surface_shade_local_at(v, ao, r, hit, q, M);
+  else surface_shade_at(v, ao, r, hit, q, M);
 }
 
 // the scene's resolution; name: how the entry's message calls it ("S", or "scene S" where S counts samples)

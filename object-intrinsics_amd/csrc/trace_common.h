@@ -6,7 +6,8 @@
 // secondary rays (occlusion.hip, envgloss.hip), the lit share of a pixel's rays, the SH basis and the closed-form transfer of a
 // normal, the shadow ray of a surface point, the per-pixel shading, and the argument checks the C entries repeat (check_*).
 // (The environment shade's pixel is env_shade_common.h's; the unit normal, the view vector, the light's direction and the
-// Phong geometry are shade_common.h's, shared with the compositing kernels.)
+// Phong geometry are shade_common.h's, shared with the compositing kernels.)  Local lights (local_light.hip,
+// include/oi_local_light.h) add the shadow sample aimed at a sphere and the Phong pixel under them.
 // Everything here has internal linkage; each source file instantiates what it exports.
 #ifndef OI_TRACE_COMMON_H_
 #define OI_TRACE_COMMON_H_
@@ -14,6 +15,7 @@
 #include "shade_common.h"
 #include "../../include/oi_occlusion.h"
 #include "../../include/oi_trace_batch.h"
+#include "../../include/oi_local_light.h"
 
 namespace {
 
@@ -481,6 +483,119 @@ __device__ __forceinline__ void surface_shade_pixel(const P& p, const float* __r
   const long long r = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
   if (r >= p.N) return;
   surface_shade_at(p, ao, r, p.status[r] == OI_TRACE_HIT, r, p.N);
+}
+
+// ---- local lights (include/oi_local_light.h) ----
+
+// q = w2b (position, 1): local light lt in the box frame Wb, and its radius R (NaN / negative -> 0: fmaxf drops a NaN)
+__device__ __forceinline__ void local_light_position(const float* __restrict__ lt, const float* __restrict__ Wb, float* q, float& R) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) q[a] = Wb[a * 4 + 0] * lt[0] + Wb[a * 4 + 1] * lt[1] + Wb[a * 4 + 2] * lt[2] + Wb[a * 4 + 3];
+  R = fmaxf(lt[3], 0.f);
+}
+
+// Shadow sample j of S from the origin o (normal n, key pix) towards the sphere of radius R about q, all in one frame
+// (include/oi_local_light.h): uniform in solid angle over the cone the sphere subtends at o.  -> kind; AIMED_TRACED: the unit
+// direction d and t_light, where the ray meets the sphere (R == 0: d = (q - o) / |q - o| bit for bit, t_light = |q - o|).
+// AIMED_BACKFACING holds d too; AIMED_INSIDE (|q - o| <= R) leaves d at three zeros.
+enum AimedKind { AIMED_TRACED, AIMED_INSIDE, AIMED_BACKFACING };
+struct AimedSample {
+  float d[3], t_light;
+  AimedKind kind;
+};
+__device__ __forceinline__ AimedSample aimed_sample(const float* o, const float* n, const float* q, float R, unsigned pix,
+                                                    unsigned seed, unsigned j, int S) {
+  AimedSample a;
+  a.d[0] = a.d[1] = a.d[2] = 0.f;
+  a.t_light = 0.f;
+  const float wx = q[0] - o[0], wy = q[1] - o[1], wz = q[2] - o[2];
+  const float dc = sqrtf(wx * wx + wy * wy + wz * wz);
+  if (dc <= R) {
+    a.kind = AIMED_INSIDE;
+    return a;
+  }
+  const float ax = wx / dc, ay = wy / dc, az = wz / dc;
+  const float sin_max = R / dc, cos_max = sqrtf((1.0f - sin_max) * (1.0f + sin_max));
+  float u1, u2;
+  sample_numbers(pix, seed, j, S, u1, u2);
+  const float m = u1 * (1.0f - cos_max);
+  const float ca = 1.0f - m, sa = sqrtf(fmaxf(m * (2.0f - m), 0.f));
+  direction_about(ax, ay, az, sa, ca, u2, a.d[0], a.d[1], a.d[2]);
+  const float ds = dc * sa;
+  a.t_light = dc * ca - sqrtf(fmaxf(R * R - ds * ds, 0.f));
+  a.kind = n[0] * a.d[0] + n[1] * a.d[1] + n[2] * a.d[2] > 0.f ? AIMED_TRACED : AIMED_BACKFACING;
+  return a;
+}
+
+// One pixel of the Phong image under local lights (include/oi_local_light.h's shading), surface_shade_at's arguments with
+// p.lights pointing at local records.  The G-buffer is not written here: the caller runs surface_shade_at without an image
+// for it, so those outputs are oi_surface_shade's bytes.
+template <class P>
+__device__ __forceinline__ void local_shade_at(const P& p, const float* __restrict__ ao, long long r, bool hit, long long q,
+                                               long long M) {
+  if (!p.image) return;
+  const float b3[3] = {p.bg ? p.bg[0] : 0.f, p.bg ? p.bg[1] : 0.f, p.bg ? p.bg[2] : 0.f};
+  float pos[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f}, alb[3] = {0.f, 0.f, 0.f};
+  float vx = 0.f, vy = 0.f, vz = 0.f;
+  const float* Wb = p.w2b;
+  if (hit) {
+    const long long k = p.hit_slot[r];
+    unit_normal(p.grad, k, n[0], n[1], n[2]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) pos[a] = p.hit_points[k * 3 + a], alb[a] = p.rgb[k * 3 + a];
+    unit_view(p.rays_o[r * 3 + 0], p.rays_o[r * 3 + 1], p.rays_o[r * 3 + 2], pos[0], pos[1], pos[2], vx, vy, vz);
+  }
+  const bool occluded = ao != nullptr;
+  const float aov = occluded && hit ? ao[q] : 1.0f;
+  for (int l = 0; l < p.L; ++l) {
+    float* img = p.image + (long long)l * 3 * M + q;
+    if (!hit) {
+      img[0] = b3[0], img[M] = b3[1], img[2 * M] = b3[2];
+      continue;
+    }
+    const float* lt = p.lights + (long long)l * OI_LOCAL_LIGHT_FLOATS;
+    float lq[3], R;
+    local_light_position(lt, Wb, lq, R);
+    const float ux = lq[0] - pos[0], uy = lq[1] - pos[1], uz = lq[2] - pos[2];
+    const float dist2 = ux * ux + uy * uy + uz * uz;
+    float lx, ly, lz;  // l = u / max(|u|, 1e-6): the view vector's clamped quotient, towards the light
+    unit_view(lq[0], lq[1], lq[2], pos[0], pos[1], pos[2], lx, ly, lz);
+    const float rmin = fmaxf(R, OI_LOCAL_LIGHT_MIN_DISTANCE);
+    float k = lt[7] * lt[7] / fmaxf(dist2, rmin * rmin);
+    float spot = 1.0f;
+    if (lt[11] > -1.0f) {
+      const float a0 = lt[16], a1 = lt[17], a2 = lt[18];
+      const float an = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
+      const float cx = Wb[0] * (a0 / an) + Wb[1] * (a1 / an) + Wb[2] * (a2 / an);
+      const float cy = Wb[4] * (a0 / an) + Wb[5] * (a1 / an) + Wb[6] * (a2 / an);
+      const float cz = Wb[8] * (a0 / an) + Wb[9] * (a1 / an) + Wb[10] * (a2 / an);
+      const float c = -(lx * cx + ly * cy + lz * cz);
+      const float tt = fminf(fmaxf((c - lt[11]) / (lt[19] - lt[11]), 0.f), 1.0f);
+      spot = tt * tt * (3.0f - 2.0f * tt);
+    }
+    k *= spot;
+    if (p.visibility != nullptr) k *= p.visibility[(long long)l * M + q];
+    const PhongGeometry ph = phong_geometry(n[0], n[1], n[2], lx, ly, lz, vx, vy, vz);
+    const float rl = fmaxf(ph.ndl, 0.f) * k;
+    const float pw = powf(ph.al, lt[15]) * k;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float diff = lt[8 + c] * rl, spec = lt[12 + c] * pw;
+      const float amb = occluded ? __fmul_rn(aov, lt[4 + c]) : lt[4 + c];
+      const float shade = amb + diff;
+      img[c * M] = shade * alb[c] + spec;
+    }
+  }
+}
+
+// surface_shade_at with local lights: its G-buffer (the same body, run without an image) and local_shade_at's image
+template <class P>
+__device__ __forceinline__ void surface_shade_local_at(const P& p, const float* __restrict__ ao, long long r, bool hit, long long q,
+                                                       long long M) {
+  P g = p;
+  g.image = nullptr;
+  surface_shade_at(g, nullptr, r, hit, q, M);
+  local_shade_at(p, ao, r, hit, q, M);
 }
 
 inline unsigned n_blocks(long long n) { return (unsigned)((n + TR_THREADS - 1) / TR_THREADS); }

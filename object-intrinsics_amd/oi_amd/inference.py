@@ -291,6 +291,125 @@ def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True,
     return res
 
 
+def light_orbit_positions(centre, radius, n_frames, axis=(0.0, -1.0, 0.0), height=0.0):
+    """World-frame positions of a local light on one closed circle of `radius` about the line through `centre` along `axis`
+    (rotation_walk's axis convention), in the plane `height` along the unit axis from `centre`.  Frame 0 stands towards the
+    world axis that is least aligned with `axis`, made perpendicular to it.  -> (n_frames, 3) float64 numpy."""
+    from scipy.spatial.transform import Rotation as R
+    c, ax = np.asarray(centre, dtype=np.float64).reshape(3), np.asarray(axis, dtype=np.float64).reshape(3)
+    if not (np.isfinite(c).all() and np.isfinite(ax).all() and np.linalg.norm(ax) > 0 and math.isfinite(float(radius))
+            and float(radius) > 0 and math.isfinite(float(height))):
+        raise ValueError(f"light_orbit_positions: centre={centre!r}, radius={radius!r}, axis={axis!r}, height={height!r} (finite, a "
+                         "non-zero axis, radius > 0)")
+    if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or int(n_frames) < 1:
+        raise ValueError(f"light_orbit_positions: n_frames={n_frames!r} (a positive integer)")
+    ax = ax / np.linalg.norm(ax)
+    start = np.eye(3)[int(np.argmin(np.abs(ax)))]
+    start = start - (start @ ax) * ax
+    start = start / np.linalg.norm(start)
+    return np.stack([c + float(height) * ax + float(radius) * (R.from_rotvec(ax * (2 * math.pi * i / int(n_frames))).as_matrix() @ start)
+                     for i in range(int(n_frames))])
+
+
+def _orbit_lights(light, n_frames, centre, radius, axis, height, what):
+    """The LocalLight `light` at each of light_orbit_positions' positions.  -> (positions, the lights)."""
+    from .relight import LocalLight
+    if not isinstance(light, LocalLight):
+        raise TypeError(f"{what}: light must be a LocalLight (surface_light_walk turns a directional light)")
+    pos = light_orbit_positions(centre, radius, n_frames, axis, height)
+    return pos, [light.replace(position=tuple(p)) for p in pos]
+
+
+@torch.no_grad()
+def surface_light_orbit(gen, z, b2w, light, n_frames=128, centre=(0.0, 0.0, 0.0), radius=1.5, axis=(0, -1, 0), height=0.0,
+                        shadows=True, bg=None, bias=None, shadow_samples=1, ao_samples=0, ao_distance=0.5, seed=0, **kw):
+    """A local light (oi_amd.relight.LocalLight) carried once round the object while the view stays: ONE
+    primary trace and ONE full MLP pass at its hits for the whole orbit, then per 256 positions one trace of shadow rays that
+    end at the light and one shade launch.  The positions are light_orbit_positions(centre, radius, n_frames, axis, height) in
+    the world frame; everything else about the light stays (a cone keeps its world-frame axis).  The lights are split further
+    until one shadow trace holds at most OCCLUSION_MAX_RAYS rays; the frames do not depend on the split.  -> {"image":
+    (n_frames, 3, H, W), "visibility": (n_frames, 1, H, W) when shadows, "mask" / "depth" (1, 1, H, W), "positions" (n_frames, 3)
+    float64 numpy, "stats"}; with ao_samples also "ambient_occlusion" (1, 1, H, W), ONE trace for the orbit."""
+    from . import lib, trace
+    from .relight import stack_local_lights
+    pos, lights = _orbit_lights(light, n_frames, centre, radius, axis, height, "surface_light_orbit")
+    dev = gen.it.device
+    lt = stack_local_lights(lights, dev)
+    gen.eval()
+    gen.renderer.pack.check()
+    trace._check_occlusion(shadows, shadow_samples, 0.0, ao_samples, ao_distance, seed, n_frames, "surface_light_orbit", True)
+    s = trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw)
+    H = s.H
+    image = torch.empty(n_frames, 3, s.N, device=dev)
+    vis_all = torch.empty(n_frames, s.N, device=dev) if shadows else None
+    step = lib.RELIGHT_MAX_LIGHTS
+    if shadows:
+        step = max(1, min(step, OCCLUSION_MAX_RAYS // (int(shadow_samples) * max(1, s.n_hit))))
+    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed)) if ao_samples else None
+    maps = None
+    for a in range(0, n_frames, step):
+        b = min(n_frames, a + step)
+        vis = s.local_visibility(lt[a:b], int(shadow_samples), int(seed)) if shadows else None
+        if shadows:
+            vis_all[a:b] = vis
+        out = s.shade(lt[a:b], trace._bg(bg, dev), vis, outputs=("image",) if maps is not None else ("depth", "mask", "image"),
+                      image_out=image[a:b], ambient_occlusion=ao)
+        maps = maps or out
+    res = {"image": image.view(n_frames, 3, H, H), "mask": maps["mask"].view(1, 1, H, H), "depth": maps["depth"].view(1, 1, H, H),
+           "positions": pos, "stats": s.stats()}
+    if shadows:
+        res["visibility"] = vis_all.view(n_frames, 1, H, H)
+    if ao_samples:
+        res["ambient_occlusion"] = ao.view(1, 1, H, H)
+    return res
+
+
+@torch.no_grad()
+def scene_light_orbit(gen, zs, b2ws, light, n_frames=128, centre=(0.0, 0.0, 0.0), radius=1.5, axis=(0, -1, 0), height=0.0,
+                      shadows=True, bg=None, bias=None, window=None, max_shadow_rays=None, shadow_samples=1, ao_samples=0,
+                      ao_distance=0.5, seed=0, **kw):
+    """surface_light_orbit on a scene of K instances (oi_amd.scene): the scene is traced ONCE and the local light is carried
+    round `centre` -- between the instances, if the circle passes there -- each instance shadowing itself and the others as
+    far as the light.  The lights are split so that one shadow batch holds at most max_shadow_rays rays (default
+    oi_amd.scene.MAX_SHADOW_RAYS), counted as K * lights * shadow_samples * visible points, and at most 256 lights; a light
+    whose samples do not fit one batch is traced in chunks of samples.  The frames do not depend on the split.  -> {"image":
+    (n_frames, 3, S, S), "visibility": (n_frames, 1, S, S) when shadows, "mask" / "depth" / "instance" (1, 1, S, S),
+    "positions", "stats"}; with ao_samples also "ambient_occlusion" (1, 1, S, S)."""
+    from . import lib, scene, trace
+    from .relight import stack_local_lights
+    pos, lights = _orbit_lights(light, n_frames, centre, radius, axis, height, "scene_light_orbit")
+    dev = gen.it.device
+    lt = stack_local_lights(lights, dev)
+    gen.eval()
+    gen.renderer.pack.check()
+    trace._check_occlusion(shadows, shadow_samples, 0.0, ao_samples, ao_distance, seed, n_frames, "scene_light_orbit", True)
+    limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
+    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, **kw)
+    S, M = s.S, s.S * s.S
+    image = torch.empty(n_frames, 3, M, device=dev)
+    vis_all = torch.empty(n_frames, M, device=dev) if shadows else None
+    step = lib.RELIGHT_MAX_LIGHTS
+    if shadows:   # (one light above the limit is traced in chunks of samples; one sample above it is refused, naming the count)
+        step = max(1, min(step, limit // max(1, s.E * sum(s.n_vis) * int(shadow_samples))))
+    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples else None
+    maps = None
+    for a in range(0, n_frames, step):
+        b = min(n_frames, a + step)
+        vis = s.local_visibility(lt[a:b], int(shadow_samples), int(seed), limit) if shadows else None
+        if shadows:
+            vis_all[a:b] = vis
+        out = s._shade(lt[a:b], trace._bg(bg, dev), vis, ("image",) if maps is not None else ("depth", "mask", "instance", "image"),
+                       image[a:b], ao)
+        maps = maps or out
+    res = {"image": image.view(n_frames, 3, S, S), "positions": pos, "stats": s.stats()}
+    res.update({k: maps[k].view(1, 1, S, S) for k in ("mask", "depth", "instance")})
+    if shadows:
+        res["visibility"] = vis_all.view(n_frames, 1, S, S)
+    if ao_samples:
+        res["ambient_occlusion"] = ao.view(1, 1, S, S)
+    return res
+
+
 def env_walk_rotations(n_frames, axis=(0.0, 0.0, 1.0)):
     """World rotations through 360 degrees about `axis` (any non-zero length), frame 0 the identity.  -> n_frames (3, 3)
     float64 arrays."""

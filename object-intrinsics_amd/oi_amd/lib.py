@@ -56,6 +56,8 @@ class PrepParams(ctypes.Structure):
 
 
 RELIGHT_LIGHT_FLOATS, RELIGHT_MAX_LIGHTS = 16, 256
+# include/oi_local_light.h: floats per local light record; the smallest distance its inverse-square law is evaluated at
+LOCAL_LIGHT_FLOATS, LOCAL_LIGHT_MIN_DISTANCE = 20, 1e-3
 
 
 class RelightParams(ctypes.Structure):
@@ -371,6 +373,14 @@ SIGS = {
         "oi_scene_bounce_nearest": (_i, [_vp, _vp, _i, _ll, _vp, _vp]),
         "oi_scene_bounce_visible": (_i, [_P(TraceBatch), _vp, _vp, _vp, _vp]),
         "oi_scene_bounce_resolve": (_i, [_vp] * 5 + [_ll] + [_vp] * 5 + [_i, _ll, _i, _i, _i, _ll, _i, _i, _vp, _vp]),
+    },
+    # include/oi_local_light.h: point, spot and sphere lights in the world, with shadow rays that end at the light (an
+    # addition to oi_occlusion.h and oi_scene_light.h; no struct of its own: their structs with `lights` at local records)
+    "oi_local_light.h": {
+        "oi_local_light_begin": (_i, [_P(TraceState), _vp, _vp, _vp, _ll, _vp, _i, _i, _vp, _f, _u, _vp]),
+        "oi_surface_shade_local": (_i, [_P(SurfaceAoParams), _vp]),
+        "oi_scene_local_light_begin": (_i, [_P(TraceBatch), _P(SceneOcclusionParams), _vp]),
+        "oi_scene_shade_local": (_i, [_P(SceneShadeAoParams), _vp]),
     },
 }
 

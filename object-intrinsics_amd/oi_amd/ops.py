@@ -666,10 +666,11 @@ SURFACE_OUT = {"depth": (1,), "position": (3,), "normal": (3,), "normal_world": 
 
 
 def _surface_shade(what, P, rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b, lights, bg, visibility,
-                   outputs, image_out):
-    """The arguments surface_shade and surface_shade_ao share, filled into the struct P.  -> (outputs, tensors to keep)."""
+                   outputs, image_out, floats=_l.RELIGHT_LIGHT_FLOATS):
+    """The arguments surface_shade, surface_shade_ao and surface_shade_local share, filled into the struct P.  -> (outputs,
+    tensors to keep)."""
     N = t.shape[0]
-    res = _shade_planes(what, SURFACE_OUT, P, N, t, outputs, lights, visibility, image_out)
+    res = _shade_planes(what, SURFACE_OUT, P, N, t, outputs, lights, visibility, image_out, floats)
     P.N, P.n_hit = N, int(n_hit)
     keep = [_c(x) for x in (rays_o, rays_d, t, hit_points, grad, rgb, w2b, lights, bg, visibility)]
     (P.rays_o, P.rays_d, P.t, P.hit_points, P.grad, P.rgb, P.w2b, P.lights, P.bg, P.visibility) = (_p(x) for x in keep)
@@ -677,18 +678,18 @@ def _surface_shade(what, P, rays_o, rays_d, t, status, hit_slot, hit_points, gra
     return res, keep
 
 
-def _shade_planes(what, table, P, M, ref, outputs, lights, visibility, image_out):
+def _shade_planes(what, table, P, M, ref, outputs, lights, visibility, image_out, floats=_l.RELIGHT_LIGHT_FLOATS):
     """What the shade entries share, for M pixels and the output table `table` (SURFACE_OUT or SCENE_OUT): the checks of
     `outputs`, the lights, the visibility's shape and `image_out`, and the output planes, whose pointers and L go into the
     struct P.  -> {name: plane} of (M,) or (M, 3) for the names of `table` in `outputs` ("instance": int32) and "image"
-    (L, 3, M) (`image_out` when given)."""
+    (L, 3, M) (`image_out` when given).  floats: the floats of one light record (LOCAL_LIGHT_FLOATS for local lights)."""
     for name in outputs:
         if name not in table and name != "image":
             raise ValueError(f"{what}: unknown output {name!r} (one of {tuple(table) + ('image',)})")
     nl = 0 if lights is None else lights.shape[0]
-    if "image" in outputs and (nl < 1 or nl > _l.RELIGHT_MAX_LIGHTS or tuple(lights.shape[1:]) != (_l.RELIGHT_LIGHT_FLOATS,)):
+    if "image" in outputs and (nl < 1 or nl > _l.RELIGHT_MAX_LIGHTS or tuple(lights.shape[1:]) != (floats,)):
         raise ValueError(f"{what}: lights {None if lights is None else tuple(lights.shape)}, expected (L, "
-                         f"{_l.RELIGHT_LIGHT_FLOATS}) with 1 <= L <= {_l.RELIGHT_MAX_LIGHTS}")
+                         f"{floats}) with 1 <= L <= {_l.RELIGHT_MAX_LIGHTS}")
     if visibility is not None and tuple(visibility.shape) != (nl, M):
         raise ValueError(f"{what}: visibility {tuple(visibility.shape)}, expected {(nl, M)}")
     P.L, res = nl, {}
@@ -822,9 +823,10 @@ def scene_shade(st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_p
 
 
 def _scene_shade(what, P, st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_pad, w2b, b2w, lights, bg, visibility,
-                 outputs, image_out):
-    """The arguments scene_shade and scene_shade_ao share, filled into the struct P.  -> (outputs, tensors to keep)."""
-    res = _shade_planes(what, SCENE_OUT, P, S * S, st.t, outputs, lights, visibility, image_out)
+                 outputs, image_out, floats=_l.RELIGHT_LIGHT_FLOATS):
+    """The arguments scene_shade, scene_shade_ao and scene_shade_local share, filled into the struct P.  -> (outputs, tensors to
+    keep)."""
+    res = _shade_planes(what, SCENE_OUT, P, S * S, st.t, outputs, lights, visibility, image_out, floats)
     P.E, P.W, P.S, P.n_pad = st.E, int(W), int(S), int(n_pad)
     keep = [_c(x) for x in (hit_points, grad, rgb, w2b, b2w, lights, bg, visibility)]
     P.hit_points, P.grad, P.rgb, P.w2b, P.b2w, P.lights, P.bg, P.visibility = (_p(x) for x in keep)
@@ -977,6 +979,68 @@ def surface_shade_ao(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb,
     ao = _c(ambient_occlusion)
     P.ambient_occlusion = _p(ao)
     _l.check(_l.load().oi_surface_shade_ao(ctypes.byref(P), _stream()), "oi_surface_shade_ao")
+    return res
+
+
+# ------------------------------------------------------------------------------------------
+# local lights: point, spot and sphere lights in the world (include/oi_local_light.h); oi_amd.trace and oi_amd.scene sequence these
+# ------------------------------------------------------------------------------------------
+
+def _check_local(what, lights):
+    if not torch.is_tensor(lights) or lights.dtype != torch.float32 or lights.dim() != 2 or lights.shape[1] != _l.LOCAL_LIGHT_FLOATS:
+        raise ValueError(f"{what}: lights must be a float32 tensor of shape (L, {_l.LOCAL_LIGHT_FLOATS}) (oi_amd.relight."
+                         "stack_local_lights)")
+
+
+def local_light_begin(st, hit_points, grad, hit_index, n_hit, lights, samples, w2b, bias, seed=0):
+    """S = samples rays per (local light, hit), aimed at the light and ending there, into the TraceState st of L * S * n_hit
+    rays; lights (L, 20) float32 on the device."""
+    _check_local("local_light_begin", lights)
+    _l.check(_l.load().oi_local_light_begin(ctypes.byref(st.c), _p(hit_points), _p(grad), _ip(hit_index), int(n_hit), _p(lights),
+                                            lights.shape[0], int(samples), _p(w2b), float(bias), int(seed), _stream()),
+             "oi_local_light_begin")
+
+
+def surface_shade_local(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b, lights=None, bg=None,
+                        visibility=None, ambient_occlusion=None, outputs=tuple(SURFACE_OUT) + ("image",), image_out=None):
+    """surface_shade_ao under local lights (L, 20) (oi_surface_shade_local): the G-buffer is surface_shade's."""
+    if ambient_occlusion is not None and tuple(ambient_occlusion.shape) != (t.shape[0],):
+        raise ValueError(f"surface_shade_local: ambient_occlusion {tuple(ambient_occlusion.shape)}, expected {(t.shape[0],)}")
+    P = _l.SurfaceAoParams()
+    res, _keep = _surface_shade("surface_shade_local", P, rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_hit, w2b,
+                                lights, bg, visibility, outputs, image_out, _l.LOCAL_LIGHT_FLOATS)
+    ao = _c(ambient_occlusion)
+    P.ambient_occlusion = _p(ao)
+    _l.check(_l.load().oi_surface_shade_local(ctypes.byref(P), _stream()), "oi_surface_shade_local")
+    return res
+
+
+def scene_local_light_begin(sb, hit_points, grad, n_pad, offset, elem, pixel, position, normal, n_vis, w2b, bias, samples, j0, chunk,
+                            lights, seed=0):
+    """scene_occlusion_begin's chunk of rays aimed at local lights (L, 20) in the world frame: sb holds E occluder elements x
+    L * chunk * n_vis rays."""
+    _check_local("scene_local_light_begin", lights)
+    P = _l.SceneOcclusionParams()
+    P.L, P.S, P.j0, P.Sc, P.ambient = lights.shape[0], int(samples), int(j0), int(chunk), 0
+    P.seed, P.bias, P.distance, P.n_pad, P.n_vis = int(seed), float(bias), 0.0, int(n_pad), int(n_vis)
+    keep = [_c(x) for x in (hit_points, grad, position, normal, lights, w2b)]
+    P.hit_points, P.grad, P.position, P.normal, P.lights, P.w2b = (_p(x) for x in keep)
+    P.radius = None
+    P.offset, P.elem, P.pixel = _ip(offset), _ip(elem), _ip(pixel)
+    _l.check(_l.load().oi_scene_local_light_begin(ctypes.byref(sb.c), ctypes.byref(P), _stream()), "oi_scene_local_light_begin")
+
+
+def scene_shade_local(st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_pad, w2b, b2w, lights=None, bg=None,
+                      visibility=None, ambient_occlusion=None, outputs=tuple(SCENE_OUT) + ("image",), image_out=None):
+    """scene_shade_ao under local lights (L, 20) in the world frame (oi_scene_shade_local)."""
+    if ambient_occlusion is not None and tuple(ambient_occlusion.shape) != (S * S,):
+        raise ValueError(f"scene_shade_local: ambient_occlusion {tuple(ambient_occlusion.shape)}, expected {(S * S,)}")
+    A = _l.SceneShadeAoParams()
+    res, _keep = _scene_shade("scene_shade_local", A.s, st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rgb, n_pad, w2b, b2w,
+                              lights, bg, visibility, outputs, image_out, _l.LOCAL_LIGHT_FLOATS)
+    ao = _c(ambient_occlusion)
+    A.ambient_occlusion = _p(ao)
+    _l.check(_l.load().oi_scene_shade_local(ctypes.byref(A), _stream()), "oi_scene_shade_local")
     return res
 
 

@@ -9,10 +9,14 @@ three colours widened to RGB.
     cap = capture(gen, z=z, b2w=b2w)                 # (B, 64) latents, (B, 4, 4) poses
     base = Light.from_module(gen.light)              # the trained light, exactly
     out = relight(cap, [base, base.replace(diffuse=(1.0, 0.5, 0.2))], outputs=("image", "specular_map"))
-    out["image"]                                     # (L, B, 3, H, W)"""
+    out["image"]                                     # (L, B, 3, H, W)
+
+LocalLight is the light that stands IN the world -- a position, an inverse-square falloff, an optional cone and size -- for the
+traced surface and scenes (oi_amd.trace.render_surface, oi_amd.scene.render_scene; include/oi_local_light.h); the volume
+relighter above takes directional Lights only."""
 import dataclasses
 import math
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -94,6 +98,115 @@ def stack_lights(lights, device="cuda"):
         if not isinstance(lt, Light):
             raise TypeError(f"relight: expected Light objects, got {type(lt).__name__}")
     return torch.tensor([lt.packed() for lt in lights], dtype=torch.float32, device=device)
+
+
+def _vec3(v, name):
+    t = tuple(float(x) for x in np.asarray(v, dtype=np.float64).reshape(3))
+    if not all(math.isfinite(x) for x in t):
+        raise ValueError(f"LocalLight.{name} must be finite, got {t}")
+    return t
+
+
+@dataclasses.dataclass(frozen=True)
+class LocalLight:
+    """A Phong light that stands IN the world of a traced view or scene (include/oi_local_light.h; oi_amd.trace.render_surface
+    and oi_amd.scene.render_scene take a list of them as `lights`): its direction differs per pixel, it falls off with the
+    inverse square of the distance, and its shadow rays end at the light.
+    position: world frame.  ambient, diffuse, specular (RGB; a scalar means grey), shininess: Light's; diffuse and specular
+    are the colours at reference_distance (> 0) and scale as (reference_distance / distance)^2; ambient does not fall off.
+    radius >= 0: the emitting sphere (0: a point): shadow samples are drawn over it, and the falloff is evaluated no nearer
+    than max(radius, LOCAL_LIGHT_MIN_DISTANCE).  A spot light has cone_axis (world frame, pointing away from the light, any
+    non-zero length) and the half-angles 0 < cone_inner < cone_outer <= pi in radians: full intensity inside the inner cone,
+    none outside the outer one, a smoothstep of the angle's cosine between."""
+    position: Tuple[float, float, float]
+    ambient: Tuple[float, float, float] = (0.33, 0.33, 0.33)
+    diffuse: Tuple[float, float, float] = (0.66, 0.66, 0.66)
+    specular: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    shininess: float = 10.0
+    radius: float = 0.0
+    reference_distance: float = 1.0
+    cone_axis: Optional[Tuple[float, float, float]] = None
+    cone_inner: Optional[float] = None
+    cone_outer: Optional[float] = None
+
+    def __post_init__(self):
+        object.__setattr__(self, "position", _vec3(self.position, "position"))
+        for name in ("ambient", "diffuse", "specular"):
+            try:
+                object.__setattr__(self, name, _rgb(getattr(self, name), name))
+            except ValueError as e:
+                raise ValueError(str(e).replace("Light.", "LocalLight.", 1)) from None
+        for name in ("shininess", "radius", "reference_distance"):
+            v = float(getattr(self, name))
+            if not math.isfinite(v):
+                raise ValueError(f"LocalLight.{name} must be finite, got {v}")
+            object.__setattr__(self, name, v)
+        if self.radius < 0:
+            raise ValueError(f"LocalLight.radius must be >= 0, got {self.radius}")
+        if self.reference_distance <= 0:
+            raise ValueError(f"LocalLight.reference_distance must be > 0, got {self.reference_distance}")
+        cone = (self.cone_axis, self.cone_inner, self.cone_outer)
+        if all(c is None for c in cone):
+            return
+        if self.cone_axis is None:
+            raise ValueError("LocalLight: cone_inner / cone_outer without cone_axis (a cone needs its axis)")
+        axis = _vec3(self.cone_axis, "cone_axis")
+        if math.sqrt(sum(x * x for x in axis)) == 0.0:
+            raise ValueError("LocalLight.cone_axis must be non-zero")
+        object.__setattr__(self, "cone_axis", axis)
+        if self.cone_inner is None or self.cone_outer is None:
+            raise ValueError("LocalLight: a cone needs cone_inner and cone_outer (radians)")
+        ci, co = float(self.cone_inner), float(self.cone_outer)
+        if not (math.isfinite(ci) and math.isfinite(co) and 0 < ci < co <= math.pi):
+            raise ValueError(f"LocalLight: cone_inner={ci}, cone_outer={co} (radians, 0 < cone_inner < cone_outer <= pi)")
+        object.__setattr__(self, "cone_inner", ci)
+        object.__setattr__(self, "cone_outer", co)
+
+    @classmethod
+    def from_light(cls, light, distance, centre=(0.0, 0.0, 0.0)):
+        """The local light that stands at centre + distance * (light.direction / |direction|) with `light`'s colours at that
+        distance (reference_distance = distance): near `centre` it approaches the directional light as the distance grows."""
+        d = np.asarray(light.direction, dtype=np.float64)
+        pos = np.asarray(centre, dtype=np.float64).reshape(3) + float(distance) * d / np.linalg.norm(d)
+        return cls(position=tuple(pos), ambient=light.ambient, diffuse=light.diffuse, specular=light.specular,
+                   shininess=light.shininess, reference_distance=float(distance))
+
+    def replace(self, **changes):
+        """A copy with some fields changed; colours may be given as scalars."""
+        return dataclasses.replace(self, **changes)
+
+    def packed(self):
+        """The LOCAL_LIGHT_FLOATS floats of one light as include/oi_local_light.h lays them out."""
+        if self.cone_axis is None:
+            axis, cos_outer, cos_inner = (0.0, 0.0, 0.0), -2.0, 2.0     # cos_outer <= -1: no cone, the axis is not read
+        else:
+            # (cos(pi) is -1, the record's "no cone": the widest cone keeps its smoothstep one fp32 step above it)
+            axis, cos_outer, cos_inner = self.cone_axis, max(math.cos(self.cone_outer), -1.0 + 2.0 ** -24), math.cos(self.cone_inner)
+        return [*self.position, self.radius, *self.ambient, self.reference_distance, *self.diffuse, cos_outer, *self.specular,
+                self.shininess, *axis, cos_inner]
+
+
+def stack_local_lights(lights, device="cuda"):
+    """LocalLights -> the (L, LOCAL_LIGHT_FLOATS) float32 array the local-light entries read (include/oi_local_light.h)."""
+    lights = [lights] if isinstance(lights, LocalLight) else list(lights)
+    if not lights:
+        raise ValueError("stack_local_lights: no lights given")
+    for lt in lights:
+        if not isinstance(lt, LocalLight):
+            raise TypeError(f"stack_local_lights: expected LocalLight objects, got {type(lt).__name__}")
+    return torch.tensor([lt.packed() for lt in lights], dtype=torch.float32, device=device)
+
+
+def local_lights_given(lights):
+    """Is `lights` (None, a light or a sequence of lights) a set of LocalLights?  A list that mixes them with directional Lights
+    is refused: the two kinds are shaded by different kernels."""
+    if lights is None or isinstance(lights, Light):
+        return False
+    seq = [lights] if isinstance(lights, LocalLight) else list(lights)
+    n = sum(isinstance(lt, LocalLight) for lt in seq)
+    if n and n != len(seq):
+        raise ValueError("lights: LocalLight and Light objects in one list (render them in two calls)")
+    return n > 0
 
 
 @dataclasses.dataclass

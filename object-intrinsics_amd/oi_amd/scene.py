@@ -30,6 +30,7 @@ from . import lib as _l
 from . import ops
 from . import trace as _t
 from .fields import LatentField
+from .relight import local_lights_given
 
 DEFAULT_BIAS = _t.DEFAULT_BIAS
 MAX_SHADOW_RAYS = 1 << 24     # rays of one shadow batch, counted as E * L * n_vis (about 80 bytes of state each)
@@ -162,12 +163,13 @@ class SceneSurface:
         return self._pixel
 
     def _sampled(self, what, samples, seed, max_shadow_rays, resolve, lights=None, radius=None, distance=None, *, lobe=None,
-                 anyhit=True):
+                 anyhit=True, local=False):
         """The sampled any-hit trace against every instance, in chunks of the samples: a chunk holds E * L * Sc * n_vis rays, Sc
         the largest number for which that stays within max_shadow_rays and below 2^31.  resolve(sb, j0, Sc, last) accumulates
         each finished chunk.  lights and radius: caps about the lights; distance: the hemisphere about the normal; lobe (a
         shininess): the reflection lobe about the reflected view vector (include/oi_scene_gloss.h).  anyhit False: the same rays
-        marched to their CLOSEST hit (oi_trace_batch_step), what the bounce follows (include/oi_scene_bounce.h).  -> (sdf
+        marched to their CLOSEST hit (oi_trace_batch_step), what the bounce follows (include/oi_scene_bounce.h).  local: `lights`
+        are local records (L, 20) and the rays are aimed at them and end there (include/oi_local_light.h).  -> (sdf
         evaluations per element, the last chunk's state)."""
         L, n_vis = 1 if lights is None else lights.shape[0], sum(self.n_vis)
         per = self.E * L * n_vis
@@ -181,7 +183,10 @@ class SceneSurface:
         for j0 in range(0, int(samples), chunk):
             c = min(chunk, int(samples) - j0)
             sb = ops.trace_batch_state_empty(self.E, L * c * n_vis, pos)
-            if lobe is None:
+            if local:
+                ops.scene_local_light_begin(sb, self.points, self.grad, self.n_pad, self.offset, elem, pixel, pos, nrm, n_vis, self.w2b,
+                                            self.bias, samples, j0, c, lights, seed)
+            elif lobe is None:
                 ops.scene_occlusion_begin(sb, self.points, self.grad, self.n_pad, self.offset, elem, pixel, pos, nrm, n_vis, self.w2b,
                                           self.bias, samples, j0, c, seed, lights, radius, distance)
             else:
@@ -231,6 +236,25 @@ class SceneSurface:
             ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
         self.shadow = sb
         return ops.scene_visibility(sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, L, n_vis, self.S)
+
+    def local_visibility(self, lights, samples=1, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """(L, S * S) visibility of the local lights `lights` (L, 20), world frame (include/oi_local_light.h): `samples` rays per
+        light and visible point, aimed at the light's sphere and ending there, every ray tested against EVERY instance in its
+        any-hit form: the share of a pixel's samples that reach the light.  An instance beyond the light throws no shadow.
+        Split into chunks of samples above max_shadow_rays, which changes no byte."""
+        L, n_vis, M = lights.shape[0], sum(self.n_vis), self.S * self.S
+        if n_vis == 0:
+            return torch.ones(L, M, device=lights.device)
+        acc = []   # count, out: taken with the first chunk, so a trace that is refused leaves no output behind
+
+        def resolve(sb, j0, c, last):
+            if not acc:
+                acc.extend((ops._new(lights, L, M).view(torch.int32), ops._new(lights, L, M)))
+            ops.scene_occlusion_resolve(sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, L, samples,
+                                        j0, c, n_vis, self.S, acc[0], acc[1], last)
+        evals, self.shadow = self._sampled("SceneSurface.shade", samples, seed, max_shadow_rays, resolve, lights, local=True)
+        self.shadow_evals += evals
+        return acc[1]
 
     def ambient(self, samples, distance, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
         """(S * S,) ambient occlusion: the share of `samples` cosine-weighted hemisphere rays per visible point that meet no
@@ -361,6 +385,8 @@ class SceneSurface:
         if self.n_pad:
             args = (self.state, self.W, self.S, self.owner, self.owner_ray, self.vis_slot, self.points, self.grad, self.rgb, self.n_pad,
                     self.w2b, self.b2w, lt, bg, vis)
+            if lt is not None and _t._is_local(lt):   # local lights: their own kernel
+                return ops.scene_shade_local(*args, ao, outputs, image_out)
             return ops.scene_shade(*args, outputs, image_out) if ao is None else ops.scene_shade_ao(*args, ao, outputs, image_out)
         res = {}
         for k in outputs:
@@ -378,7 +404,8 @@ class SceneSurface:
     def shade(self, lights=None, shadows=False, bg=None, max_shadow_rays=MAX_SHADOW_RAYS, shadow_samples=1, light_radius=0.0,
               ao_samples=0, ao_distance=0.5, seed=0):
         """The scene under `lights` (oi_amd.relight.Light objects in the WORLD frame; default the generator's trained light; at
-        most RELIGHT_MAX_LIGHTS).  -> dict of image (L, 3, S, S); depth (the ray parameter; NaN off the mask), mask, instance
+        most RELIGHT_MAX_LIGHTS; or oi_amd.relight.LocalLight objects, lights that stand between the instances: their shadow
+        rays end at the light, shadow_samples sample the light's own sphere and light_radius must stay 0).  -> dict of image (L, 3, S, S); depth (the ray parameter; NaN off the mask), mask, instance
         (int32, -1 off the mask) (1, 1, S, S); position (world frame), normal_map (world frame), albedo (1, 3, S, S);
         visibility (L, 1, S, S) when `shadows` (refused above max_shadow_rays = E * L * n_vis rays); stats.  bg: (3,)
         background colour (black when None).
@@ -391,9 +418,13 @@ class SceneSurface:
         bytes are those of a call without these arguments."""
         dev = self.b2w.device
         lt = _t._stack_lights(self.gen, lights, dev, "SceneSurface.shade", "; inference.scene_light_walk splits larger sets")
+        local = _t._is_local(lt)
         radii = _t._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0],
-                                    "SceneSurface.shade")
-        vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays) if shadows else None
+                                    "SceneSurface.shade", local)
+        if local:
+            vis = self.local_visibility(lt, int(shadow_samples), int(seed), max_shadow_rays) if shadows else None
+        else:
+            vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays) if shadows else None
         ao = self.ambient(int(ao_samples), float(ao_distance), int(seed), max_shadow_rays) if ao_samples else None
         out = self._shade(lt, _t._bg(bg, dev), vis, ("depth", "position", "normal_world", "albedo", "mask", "instance", "image"), ao=ao)
         S = self.S
@@ -540,7 +571,7 @@ def render_scene(gen, zs, b2ws, lights=None, shadows=False, bg=None, window=None
     rad = light_radius.detach().cpu() if torch.is_tensor(light_radius) else light_radius
     # (before the trace; shade checks a radius per light against the lights it stacks)
     _t._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, np.size(rad) if np.ndim(rad) == 1 else 1,
-                        "render_scene")
+                        "render_scene", local_lights_given(lights))
     s = trace_scene(gen, zs, b2ws, window, bias, **trace_kw)
     res = s.shade(lights, shadows, bg, max_shadow_rays, shadow_samples, light_radius, ao_samples, ao_distance, seed)
     res["scene"] = s

@@ -10,6 +10,8 @@
                      optionally with cast shadows (one shadow ray per light and visible point, or `shadow_samples` rays
                      towards a light of angular radius `light_radius`: penumbrae) and ambient occlusion (`ao_samples` rays
                      over the hemisphere of each visible point; include/oi_occlusion.h)
+                     `lights` may also be oi_amd.relight.LocalLight objects: point, spot and sphere lights that stand in the
+                     world, whose shadow rays end at the light (include/oi_local_light.h)
     capture_transfer one view's secondary rays traced ONCE into a per-pixel SH transfer map; the TransferCapture is then shaded
                      under any number of environment lights (oi_amd.envlight.EnvLight), 256 per launch
                      (include/oi_envlight.h); with glossy_samples it also traces a reflection-lobe
@@ -308,6 +310,20 @@ class _Surface:
         self.shadow = st
         return ops.occlusion_resolve(st.status, self.res.hit_slot, self.N, self.n_hit, L, samples)
 
+    def local_visibility(self, lights, samples=1, seed=0):
+        """(L, N) visibility of the local lights `lights` (L, 20) (include/oi_local_light.h): one any-hit trace over all
+        L x samples x n_hit rays, each aimed at its light's sphere and ending there; the share of a pixel's samples that
+        reach the light (0 or 1 for a point light with one sample)."""
+        L = lights.shape[0]
+        if self.n_hit == 0:
+            return torch.ones(L, self.N, device=self.ro.device)
+        st = ops.TraceState(L * samples * self.n_hit, ref=self.ro)
+        ops.local_light_begin(st, self.res.hit_points, self.grad, self.res.hit_index, self.n_hit, lights, samples, self.w2b,
+                              self.bias, seed)
+        self.shadow_evals += self._secondary(st)
+        self.shadow = st
+        return ops.occlusion_resolve(st.status, self.res.hit_slot, self.N, self.n_hit, L, samples)
+
     def ambient(self, samples, distance, seed=0):
         """(N,) ambient occlusion: the share of `samples` cosine-weighted hemisphere rays per visible point that leave the
         point's neighbourhood (`distance`) without meeting the surface; 1 off the mask."""
@@ -381,6 +397,8 @@ class _Surface:
         dummy = self.ro   # never read when n_hit == 0
         args = (self.ro, self.rd, r.t, r.status, r.hit_slot, r.hit_points if self.n_hit else dummy,
                 self.grad if self.n_hit else dummy, self.rgb if self.n_hit else dummy, self.n_hit, self.w2b, lights, bg, visibility)
+        if lights is not None and _is_local(lights):   # local lights: their own kernel
+            return ops.surface_shade_local(*args, ambient_occlusion, outputs, image_out)
         if ambient_occlusion is None:
             return ops.surface_shade(*args, outputs, image_out)
         return ops.surface_shade_ao(*args, ambient_occlusion, outputs, image_out)
@@ -402,8 +420,9 @@ def _check_seed(seed, what):
         raise ValueError(f"{what}: seed={seed!r} (an integer, 0 <= seed < 2^32)")
 
 
-def _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_lights, what):
-    """-> the lights' angular radii as a list of n_lights floats, or None for hard shadows (one ray, no radius)."""
+def _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_lights, what, local=False):
+    """-> the lights' angular radii as a list of n_lights floats, or None for hard shadows (one ray, no radius).  local: the
+    lights are LocalLights, whose size is their own radius: a light_radius other than 0 is refused, and None is returned."""
     if not _is_count(shadow_samples, 1):
         raise ValueError(f"{what}: shadow_samples={shadow_samples!r} (an integer, 1 <= shadow_samples <= {_l.OCCLUSION_MAX_SAMPLES})")
     if not _is_count(ao_samples, 0):
@@ -417,8 +436,12 @@ def _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_dista
     if not (np.isfinite(rad).all() and (rad >= 0).all() and (rad <= np.pi / 2).all()):
         raise ValueError(f"{what}: light_radius={light_radius!r} (radians, 0 <= light_radius <= pi / 2)")
     soft = int(shadow_samples) != 1 or bool((rad != 0).any())
+    if local and bool((rad != 0).any()):
+        raise ValueError(f"{what}: light_radius={light_radius!r} with local lights (the size is the light's own: LocalLight.radius)")
     if soft and not shadows:
         raise ValueError(f"{what}: shadow_samples / light_radius need shadows=True")
+    if local:
+        return None
     return np.broadcast_to(rad, (n_lights,)).tolist() if soft else None
 
 
@@ -426,11 +449,20 @@ def _bg(bg, dev):
     return None if bg is None else torch.as_tensor(bg, dtype=torch.float32).to(dev).reshape(3).contiguous()
 
 
+def _is_local(lt):
+    """Does the stacked light array hold local records (include/oi_local_light.h)?"""
+    return lt.shape[-1] == _l.LOCAL_LIGHT_FLOATS
+
+
 def _stack_lights(gen, lights, dev, what, hint=""):
-    """`lights` (oi_amd.relight.Light objects; default the generator's trained light) as (L, 16) on dev.  More than
-    RELIGHT_MAX_LIGHTS are refused in the name of `what`; hint: where larger sets are split."""
-    from .relight import Light, stack_lights
-    lt = stack_lights(Light.from_module(gen.light) if lights is None else lights, dev)
+    """`lights` (oi_amd.relight.Light objects; default the generator's trained light) as (L, 16) on dev, or LocalLight
+    objects as (L, 20); a list that mixes the two is refused.  More than RELIGHT_MAX_LIGHTS are refused in the name of `what`;
+    hint: where larger sets are split."""
+    from .relight import Light, local_lights_given, stack_lights, stack_local_lights
+    if local_lights_given(lights):
+        lt = stack_local_lights(lights, dev)
+    else:
+        lt = stack_lights(Light.from_module(gen.light) if lights is None else lights, dev)
     if lt.shape[0] > _l.RELIGHT_MAX_LIGHTS:
         raise ValueError(f"{what}: {lt.shape[0]} lights (at most {_l.RELIGHT_MAX_LIGHTS}{hint})")
     return lt
@@ -457,7 +489,9 @@ def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAUL
     """One view of `gen` (latent z (z_dim,) or (1, z_dim), pose b2w (4, 4)) by intersecting each pixel's ray with the surface:
     -> dict of depth (1, 1, H, W) (the ray parameter; NaN off the mask), position, normal_map (world frame), normal_object,
     albedo (1, 3, H, W), mask (1, 1, H, W), image (L, 3, H, W) under `lights` (oi_amd.relight.Light objects; default the
-    generator's trained light), visibility (L, 1, H, W) when `shadows` (one shadow ray per light and visible point, offset by
+    generator's trained light; or oi_amd.relight.LocalLight objects, lights that stand in the world: include/oi_local_light.h,
+    DESIGN section 4.27 -- their shadow rays end at the light, shadow_samples sample the light's own sphere and light_radius
+    must stay 0), visibility (L, 1, H, W) when `shadows` (one shadow ray per light and visible point, offset by
     `bias` along the normal), stats (rays per status, sdf evaluations), trace (the primary TraceResult).  The rays are Generator.forward's.  bg: (3,)
     background colour (black when None).  trace_kw: tol, omega, max_steps, readback of sphere_trace.
     Soft shadows: light_radius (radians; a scalar or one value per light) gives the lights an angular size and shadow_samples
@@ -470,13 +504,16 @@ def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAUL
     z = z.to(dev).reshape(1, -1)
     s = _Surface(gen, z, b2w, bias, trace_kw)
     lt = _stack_lights(gen, lights, dev, "render_surface", "; inference.surface_light_walk splits larger sets")
-    radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surface")
+    radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surface",
+                             _is_local(lt))
     return _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev)
 
 
 def _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev):
     """The light-dependent stages of one traced view (a _Surface) and render_surface's dict."""
-    if radii is None:
+    if _is_local(lt):
+        vis = s.local_visibility(lt, int(shadow_samples), int(seed)) if shadows else None
+    elif radii is None:
         vis = s.visibility(lt) if shadows else None
     else:
         vis = s.visibility(lt, torch.tensor(radii, dtype=torch.float32, device=dev), int(shadow_samples), int(seed))
@@ -515,7 +552,8 @@ def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEF
     if len(b2ws) != E or not 1 <= E <= _l.TRACE_BATCH_MAX_ELEMS:
         raise ValueError(f"render_surfaces: {E} latents and {len(b2ws)} poses (one pose per latent, 1 .. {_l.TRACE_BATCH_MAX_ELEMS} views)")
     lt = _stack_lights(gen, lights, dev, "render_surfaces")
-    radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surfaces")
+    radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surfaces",
+                             _is_local(lt))
     field = LatentField(gen, zs, None, "render_surfaces", batch_ok=True)
     gen.eval()
     field.prepare(zs, None)

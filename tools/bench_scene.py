@@ -31,7 +31,12 @@ of the same run:
                                                    the bounce transfer
   scene_bounce_ms                oi_amd.scene.render_scene_env(bounces=1): the two together
   bounce_points / n_pad2         the secondary hits evaluated (over all chunks and instances) and the last chunk's padded row length
---skip-crops leaves out the crops_* rows (K single-view renders each)."""
+--skip-crops leaves out the crops_* rows (K single-view renders each).
+
+With --local [--light-size R] each row also gets scene_local_ms / scene_local_hard_ms /
+scene_local_sphere16_ms: render_scene under a local light 3 units from the instances' centroid along the trained light's
+direction (no shadows, one hard ray, 16 samples of a sphere of radius R), scene_directional_soft16_ms beside them, and the
+sdf evaluations of each shadow trace."""
 import argparse
 import copy
 import json
@@ -64,6 +69,8 @@ ap.add_argument("--glossy-samples", type=int, default=64, help="reflection-lobe 
 ap.add_argument("--shininess", type=float, default=10.0)
 ap.add_argument("--bounce", action="store_true", help="with --env: also time the capture and shade with bounces=1 (scene_bounce_*_ms)")
 ap.add_argument("--skip-crops", action="store_true", help="leave out the crops_* comparison rows")
+ap.add_argument("--local", action="store_true", help="also time a local light (oi_amd.relight.LocalLight) above the scene: scene_local_*_ms")
+ap.add_argument("--light-size", type=float, default=0.15, help="with --local: radius of the sphere light of the sampled row")
 args = ap.parse_args()
 
 
@@ -139,5 +146,17 @@ with torch.no_grad():
                                                                              bounces=1))
             row["bounce_points"] = cap.scene.bounce_points
             row["n_pad2"] = cap.scene.bounce_hits["n_pad2"] if cap.scene.bounce_hits else 0
+        if args.local:   # beside the directional rows: no shadows, one hard ray, 16 samples of a light with a size
+            from oi_amd.relight import Light, LocalLight
+            base = Light.from_module(gen.light)
+            centre = tuple(float(x) for x in b2ws[:, :3, 3].mean(0))
+            point = LocalLight.from_light(base, 3.0, centre)
+            cases = {"directional_soft16": dict(lights=[base], shadows=True, shadow_samples=16, light_radius=0.1),
+                     "local": dict(lights=[point]), "local_hard": dict(lights=[point], shadows=True),
+                     "local_sphere16": dict(lights=[point.replace(radius=args.light_size)], shadows=True, shadow_samples=16)}
+            for name, kw in cases.items():
+                row[f"scene_{name}_ms"] = median_ms(lambda: scene.render_scene(gen, zs, b2ws, **kw))
+                row[f"scene_{name}_shadow_evals"] = scene.render_scene(gen, zs, b2ws, **kw)["stats"][0]["shadow_evals"]
+            row["scene_directional_hard_shadow_evals"] = scene.render_scene(gen, zs, b2ws, shadows=True)["stats"][0]["shadow_evals"]
         out["instances"][str(K)] = row
 print(json.dumps(out))

@@ -24,7 +24,12 @@ same call's unchanged per-frame loop (batch=1) in the same session, without and 
 
   loop_ms / batch_ms    ms per frame;   speedup  their ratio
   evals_per_ray         sdf evaluations per primary ray (the stale and the shared bounds included)
-  n_pad_over_mean_hit   points per element of the padded full pass over the mean hit count;  padding_waste  its unread share"""
+  n_pad_over_mean_hit   points per element of the padded full pass over the mean hit count;  padding_waste  its unread share
+
+With --local [--light-size R] [--light-distance D] the tool measures ONLY, per resolution, the frame under
+the trained directional light and under a local light (oi_amd.relight.LocalLight) D along the same direction from the object's
+centre: no shadows, one hard shadow ray, and 16 samples of a light with a size (angular radius 0.1 / a sphere of radius R),
+each with the sdf evaluations of its shadow trace."""
 import argparse
 import json
 import os
@@ -51,6 +56,9 @@ ap.add_argument("--shadow-samples", type=int, default=1, help="shadow rays per l
 ap.add_argument("--light-radius", type=float, default=0.0, help="angular radius of the light, radians")
 ap.add_argument("--ao-samples", type=int, default=0, help="ambient-occlusion rays per visible point (0: none)")
 ap.add_argument("--batch", default="", help="frames per batched primary trace, e.g. 16,128: measure only the batched walk")
+ap.add_argument("--local", action="store_true", help="time local lights (oi_amd.relight.LocalLight) beside the directional path, only")
+ap.add_argument("--light-size", type=float, default=0.15, help="with --local: radius of the sphere light of the sampled row")
+ap.add_argument("--light-distance", type=float, default=2.0, help="with --local: distance of the local light from the object's centre")
 args = ap.parse_args()
 
 
@@ -147,6 +155,37 @@ def batched_walk():
                                 "frames_equal_loop": same}
     return row
 
+
+def local_rows():
+    """Per resolution: the frame under the trained directional light and under a local light at --light-distance along the same
+    direction -- no shadows, one hard shadow ray, 16 samples of a light with a size (angular radius 0.1 / sphere radius
+    --light-size) -- and the sdf evaluations of each shadow trace."""
+    from oi_amd.relight import Light, LocalLight
+    rows = {}
+    for R in (int(r) for r in args.res.split(",")):
+        gen, z, b2w = setup(R)
+        base = Light.from_module(gen.light)
+        point = LocalLight.from_light(base, args.light_distance, tuple(float(x) for x in b2w[:3, 3]))
+        cases = {"directional": dict(lights=[base]), "directional_hard": dict(lights=[base], shadows=True),
+                 "directional_soft16": dict(lights=[base], shadows=True, shadow_samples=16, light_radius=0.1),
+                 "local": dict(lights=[point]), "local_hard": dict(lights=[point], shadows=True),
+                 "local_sphere16": dict(lights=[point.replace(radius=args.light_size)], shadows=True, shadow_samples=16)}
+        row = {"rays": R * R}
+        for name, kw in cases.items():
+            row[name + "_ms"] = median_ms(lambda: trace.render_surface(gen, z, b2w, **kw))
+            st = trace.render_surface(gen, z, b2w, **kw)["stats"]
+            row[name + "_shadow_evals"] = st["shadow_evals"]
+        row["hits"] = st["hit"]
+        rows[str(R)] = row
+        del gen
+    return rows
+
+
+if args.local:
+    with torch.no_grad():
+        print(json.dumps({"tool": "bench_trace", "precision": args.precision, "iters": args.iters, "warmup": args.warmup,
+                          "light_size": args.light_size, "light_distance": args.light_distance, "local": local_rows()}))
+    sys.exit(0)
 
 if args.batch:
     with torch.no_grad():

@@ -9,6 +9,7 @@
 // No atomics, no scratch, every output element written by exactly one thread (the record: staged in LDS per workgroup and
 // written out as whole dwords, since 27-byte records are not dword aligned).  64-bit indexing: V * 27 exceeds 2^31.
 #include "oi_common.h"
+#include "mesh_quant.h"
 #include "../../include/oi_mesh_attr.h"
 
 namespace {
@@ -80,9 +81,7 @@ __device__ __forceinline__ void put_f32(unsigned char* dst, float v) {
   const unsigned w = __float_as_uint(v);
   dst[0] = (unsigned char)w, dst[1] = (unsigned char)(w >> 8), dst[2] = (unsigned char)(w >> 16), dst[3] = (unsigned char)(w >> 24);
 }
-__device__ __forceinline__ unsigned char quant8(float c) {
-  return (unsigned char)__float2int_rn(fminf(fmaxf(c, 0.f), 1.f) * 255.f);  // fmaxf(NaN, 0) = 0
-}
+using oi::quant8;   // (mesh_quant.h: the byte atlases of mesh_tex.hip hold the same rule)
 
 // The workgroup's records: thread t has staged vertex v0 + t at lds + 27 t (when it has a vertex); the bytes go out as
 // dwords (the workgroup's first byte is 6912 * blockIdx.x: dword aligned when `record` is), the last 1..3 of the mesh as bytes.

@@ -511,19 +511,34 @@ def shade_vertices(positions, normals, albedo, light, eye=None):
 
 @torch.no_grad()
 def export_mesh(gen, z, path, resolution=256, refine=2, light=None, threshold=0.0, bound_min=(-1.0, -1.0, -1.0),
-                bound_max=(1.0, 1.0, 1.0), eye=None, band=False, lipschitz=None, block=None):
+                bound_max=(1.0, 1.0, 1.0), eye=None, band=False, lipschitz=None, block=None, texture=False, texel=8,
+                max_texels=1 << 20):
     """The instance of latent z (z_dim,) or (1, z_dim) as a PLY asset at `path`: triangles, vertices on the surface, analytic
     normals and per-vertex colours (oi_amd.mesh.extract_intrinsic_mesh; save_ply's attribute layout).  Colours are the
     albedo, or with `light` (oi_amd.relight.Light, e.g. Light.from_module(gen.light)) the shaded colour of shade_vertices.
     band=True (lipschitz, block): the field comes from mesh.sdf_lattice_band; the file is the same, the BandInfo is in m.band.
     Checks the weights first (FieldPack.check: an inf / NaN weight is refused before anything is launched).
-    -> the IntrinsicMesh that was written (with `shaded` (V, 3) set when a light was given)."""
+    -> the IntrinsicMesh that was written (with `shaded` (V, 3) set when a light was given).
+    texture=True (texel, max_texels: oi_amd.mesh.extract_textured_mesh's arguments): `path` must end in .obj; the asset is a
+    Wavefront OBJ with its .mtl and the baked <stem>_albedo.png and <stem>_normal.png (oi_amd.mesh.save_obj) -- a coarse
+    mesh whose texture carries the detail; with `light` the albedo map holds the shaded colour of every texel instead.
+    -> the TexturedMesh that was written."""
     from . import mesh, ops
+    if texture:
+        mesh.obj_file_names(path)                 # ValueError unless it ends in .obj, before anything is launched
+        ops.tex_layout(0, texel)                  # and the texel size (host only)
     gen.eval()
     pack = mesh._field_pack(gen, "export_mesh")
     pack.check()
     dev = gen.it.device
     z = z.to(dev).reshape(1, -1)
+    if texture:
+        shade = None if light is None else (lambda p, n, a: shade_vertices(p, n, a, light, eye))
+        tm = mesh.extract_textured_mesh(pack, z=z, resolution=resolution, texel=texel, threshold=threshold,
+                                        bound_min=bound_min, bound_max=bound_max, refine=refine, band=band,
+                                        lipschitz=lipschitz, block=block, max_texels=max_texels, shade=shade)
+        mesh.save_obj(path, tm)
+        return tm
     m = mesh.extract_intrinsic_mesh(pack, z=z, resolution=resolution, threshold=threshold, bound_min=bound_min,
                                     bound_max=bound_max, refine=refine, want_record=light is None, band=band,
                                     lipschitz=lipschitz, block=block)

@@ -78,6 +78,9 @@ class CompositeGrads(ctypes.Structure):
 MESH_FLAG_NONFINITE, MESH_FLAG_SMALL_GRADIENT, MESH_FLAG_LIMIT = 1, 2, 4
 MESH_MAX_REFINE, MESH_RECORD_BYTES = 8, 27
 
+# include/oi_mesh_tex.h
+TEX_MIN_TEXEL, TEX_MAX_TEXEL, TEX_MAX_SIZE = 3, 64, 16384
+
 # include/oi_trace.h
 TRACE_MISS, TRACE_HIT, TRACE_LIMIT, TRACE_START_INSIDE, TRACE_NONFINITE, TRACE_BACKFACING = 0, 1, 2, 3, 4, 5
 TRACE_MARCH, TRACE_REFINE = 16, 17
@@ -381,6 +384,14 @@ SIGS = {
         "oi_surface_shade_local": (_i, [_P(SurfaceAoParams), _vp]),
         "oi_scene_local_light_begin": (_i, [_P(TraceBatch), _P(SceneOcclusionParams), _vp]),
         "oi_scene_shade_local": (_i, [_P(SceneShadeAoParams), _vp]),
+    },
+    # include/oi_mesh_tex.h: the per-triangle texture atlas of the textured mesh export (an addition to oi_mesh_attr.h; no
+    # struct of its own: plain arguments)
+    "oi_mesh_tex.h": {
+        "oi_tex_layout": (_i, [_ll, _i, _P(_i), _P(_i), _P(_i)]),
+        "oi_tex_uv": (_i, [_ll, _i, _vp, _vp]),
+        "oi_tex_points": (_i, [_vp, _vp, _ll, _ll, _i, _vp, _vp, _vp]),
+        "oi_tex_store": (_i, [_vp, _vp, _ll, _ll, _i, _ll] + [_vp] * 5),
     },
 }
 

@@ -10,9 +10,13 @@
     vertex_attributes / extract_intrinsic_mesh   the intrinsic mesh: vertices moved onto the level set, analytic normals
                      and albedo per vertex   oi_mesh_vertex_world + (oi_sdf_mlp_fwd + oi_mesh_newton) x refine +
                      oi_sdf_mlp_fwd + oi_mesh_attr_finalize   (include/oi_mesh_attr.h)
+    bake_textures / extract_textured_mesh   the textured mesh: a per-triangle UV atlas, every texel projected onto the level
+                     set, baked albedo and object-space normal maps   oi_tex_uv + per chunk (oi_tex_points + the vertex
+                     pass's chain + oi_tex_store)   (include/oi_mesh_tex.h)
+    save_png / save_obj   8-bit RGB PNG with zlib and struct only; Wavefront OBJ + MTL + the two maps of a TexturedMesh
 
 DESIGN section 4.10 has the table rule, the output order and the measured numbers; section 4.12 the vertex pass; section 4.14
-the narrow band."""
+the narrow band; section 4.28 the texture atlas."""
 import ctypes
 import dataclasses
 from typing import Optional
@@ -396,3 +400,192 @@ def extract_intrinsic_mesh(renderer_or_generator, z=None, w=None, resolution=256
     out.triangles = tris
     out.band = info
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the textured mesh (include/oi_mesh_tex.h)
+# ---------------------------------------------------------------------------------------------------------------------
+DEFAULT_TEXEL = 8
+DEFAULT_MAX_TEXELS = 1 << 20
+
+
+@dataclasses.dataclass
+class TexturedMesh:
+    """An intrinsic mesh with a per-triangle texture atlas (include/oi_mesh_tex.h has the layout): mesh: the IntrinsicMesh it
+    was built on (positions, normals, triangles); uv (F, 3, 2): texture coordinates per corner, OBJ convention (v up);
+    albedo_map, normal_map (H, W, 3) uint8: the baked colour and the object-space normal n * 0.5 + 0.5, row 0 on top;
+    albedo_f32, normal_f32 (H, W, 3) float32 or None (want_float=True): the values before quantisation (unowned pixels: 0
+    and 0.5); texel: the texel size T of a triangle; size = (W, H); texel_flags (F, n_T) uint8 and texel_residual (F, n_T):
+    the flags (oi_amd.lib.MESH_FLAG_*) and the last residual |sdf + threshold| / |d sdf/dx| of every texel's projection;
+    texel_positions (F, n_T, 3) or None (keep_points=True): the final points.  A bilinear lookup inside a triangle's UV
+    triangle reads that triangle's texels only; mip levels above 0 bleed into the neighbours, as in every per-triangle atlas."""
+    mesh: IntrinsicMesh
+    uv: torch.Tensor
+    albedo_map: torch.Tensor
+    normal_map: torch.Tensor
+    texel: int
+    size: tuple
+    texel_flags: torch.Tensor
+    texel_residual: torch.Tensor
+    albedo_f32: Optional[torch.Tensor] = None
+    normal_f32: Optional[torch.Tensor] = None
+    texel_positions: Optional[torch.Tensor] = None
+
+
+def _check_max_texels(max_texels, what):
+    if isinstance(max_texels, bool) or not isinstance(max_texels, (int, np.integer)) or not 1 <= int(max_texels) < 1 << 31:
+        raise ValueError(f"{what}: max_texels={max_texels!r} (an integer, 1 <= max_texels < 2^31)")
+    return int(max_texels)
+
+
+def bake_textures(pack_or_generator, mesh, bound_min, bound_max, resolution, z=None, w=None, texel=DEFAULT_TEXEL, refine=2,
+                  threshold=0.0, max_texels=DEFAULT_MAX_TEXELS, want_float=False, keep_points=False, shade=None):
+    """The atlas of an IntrinsicMesh with triangles (extract_intrinsic_mesh's result; bounds, resolution, latent and
+    threshold as it was extracted with) -> TexturedMesh.  Every texel of every triangle is a point in the triangle's plane
+    (gutter texels past the hypotenuse are extrapolated, not clamped), projected onto the level set by `refine` Newton steps
+    limited to half a lattice cell per axis around the planar point -- the vertex pass's own rule and kernels -- and the unit
+    normal and the albedo there go to the texel's pixel.  Chunks of whole triangles, max(1, max_texels // n_T) at a time:
+    oi_tex_points, (full MLP pass + oi_mesh_newton) x refine, the full pass, oi_mesh_attr_finalize, oi_tex_store.  Texels are
+    independent, so any max_texels gives the same bytes.  shade(points, normals, albedo) -> (n, 3) colours, optional: what the
+    albedo maps hold instead of the albedo (inference.export_mesh(..., light=...) passes shade_vertices).
+    F == 0: nothing is launched, the atlases are the filled (texel, texel + 1, 3) images.  One latent."""
+    what = "bake_textures"
+    tris = mesh.triangles
+    if tris is None or not torch.is_tensor(tris) or tris.dim() != 2 or tris.shape[1] != 3:
+        raise ValueError(f"{what}: the mesh needs its (F, 3) triangles (extract_intrinsic_mesh sets them)")
+    F, V = int(tris.shape[0]), int(mesh.positions.shape[0])
+    try:
+        W, H, _ = ops.tex_layout(F, texel)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
+    T = int(texel)
+    nT = T * (T + 1) // 2
+    refine = _check_refine(refine, what)
+    max_texels = _check_max_texels(max_texels, what)
+    f = LatentField(pack_or_generator, z, w, what)
+    if F and (int(tris.min()) < 0 or int(tris.max()) >= V):
+        raise ValueError(f"{what}: triangles index {int(tris.min())} .. {int(tris.max())}, the mesh has {V} vertices")
+    pos_v = mesh.positions
+    if not pos_v.is_cuda:
+        raise _l.OiHipError(f"{what}: the mesh must be on the GPU (there is no CPU path)")
+    dev = pos_v.device
+    fill = lambda t, v: t.fill_(v)
+    albedo_u8 = fill(ops._bytes(pos_v, H * W * 3).view(H, W, 3), 0)
+    normal_u8 = fill(ops._bytes(pos_v, H * W * 3).view(H, W, 3), 128)
+    albedo_f32 = fill(ops._new(pos_v, H, W, 3), 0.0) if want_float else None
+    normal_f32 = fill(ops._new(pos_v, H, W, 3), 0.5) if want_float else None
+    flags = ops._bytes(pos_v, F * nT)
+    residual = ops._new(pos_v, F * nT)
+    points = ops._new(pos_v, F * nT, 3) if keep_points else None
+    out = TexturedMesh(mesh, None, albedo_u8, normal_u8, T, (W, H), flags.view(F, nT), residual.view(F, nT), albedo_f32,
+                       normal_f32, points.view(F, nT, 3) if keep_points else None)
+    if F == 0:
+        out.uv = torch.empty(0, 3, 2, dtype=torch.float32, device=dev)
+        return out
+    with torch.no_grad():
+        f.prepare(z, w)
+        pos_v = pos_v.detach().float().contiguous()
+        tris = tris.detach().to(torch.int32).contiguous()
+        out.uv = ops.tex_uv(F, T, pos_v)
+        bmin, bmax = ([float(v) for v in _host(b).reshape(-1)] for b in (bound_min, bound_max))
+        res = (resolution,) * 3 if np.isscalar(resolution) else tuple(resolution)
+        limits = [0.5 * (bmax[a] - bmin[a]) / (int(res[a]) - 1) for a in range(3)]
+        nf_max = min(F, max(1, max_texels // nT))
+        buf = None if keep_points else ops._new(pos_v, nf_max * nT, 3)
+        buf0 = ops._new(pos_v, nf_max * nT, 3) if refine else None
+        scratch = torch.empty(ops.mlp_scratch_bytes(1, nf_max * nT, f.prec), dtype=torch.uint8, device=dev)
+        for f0 in range(0, F, nf_max):
+            nf = min(nf_max, F - f0)
+            a, b = f0 * nT, (f0 + nf) * nT
+            pts, fl = ops.tex_points(pos_v, tris, f0, nf, T, out=points[a:b] if keep_points else buf, flags=flags[a:b])
+            if refine:
+                pts0 = buf0[:b - a].copy_(pts)
+                for _ in range(refine):
+                    sdf, grad, _ = f.full(pts, scratch)
+                    ops.mesh_newton(pts, pts0, sdf, grad, threshold, limits, None, fl)
+            sdf, grad, rgb = f.full(pts, scratch)
+            normals, albedo, _ = ops.mesh_attr_finalize(pts, sdf, grad, rgb, threshold, residual[a:b])
+            if shade is not None:
+                albedo = shade(pts, normals, albedo).contiguous()
+            ops.tex_store(normals, albedo, f0, nf, T, F, albedo_f32, normal_f32, albedo_u8, normal_u8)
+    return out
+
+
+def extract_textured_mesh(renderer_or_generator, z=None, w=None, resolution=64, texel=DEFAULT_TEXEL, threshold=0.0,
+                          bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), refine=2, band=False, lipschitz=None,
+                          block=None, max_texels=DEFAULT_MAX_TEXELS, want_float=False, keep_points=False, shade=None):
+    """extract_intrinsic_mesh (band, lipschitz, block: its arguments) followed by bake_textures: a coarse mesh whose texture
+    carries the detail of the albedo and of the analytic normal field -> TexturedMesh (save_obj writes it)."""
+    what = "extract_textured_mesh"
+    try:
+        ops.tex_layout(0, texel)      # the texel size, before anything is launched
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
+    _check_max_texels(max_texels, what)
+    m = extract_intrinsic_mesh(renderer_or_generator, z=z, w=w, resolution=resolution, threshold=threshold,
+                               bound_min=bound_min, bound_max=bound_max, refine=refine, band=band, lipschitz=lipschitz,
+                               block=block)
+    pack = LatentField(renderer_or_generator, z, w, what).pack
+    return bake_textures(pack, m, bound_min, bound_max, resolution, z=z, w=w, texel=texel, refine=refine,
+                         threshold=threshold, max_texels=max_texels, want_float=want_float, keep_points=keep_points,
+                         shade=shade)
+
+
+PNG_COMPRESSION = 6   # fixed: the same image gives the same bytes
+
+
+def save_png(path, image_u8):
+    """8-bit RGB PNG of an (H, W, 3) uint8 image (tensor or array), row 0 on top, with zlib and struct alone: one IDAT chunk,
+    filter type 0 on every row, compression level PNG_COMPRESSION.  The same input gives the same bytes."""
+    import struct
+    import zlib
+    img = _host(image_u8)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"save_png: expected an (H, W, 3) uint8 image, got {img.dtype} {tuple(img.shape)}")
+    H, W = img.shape[:2]
+    rows = np.zeros((H, 1 + 3 * W), dtype=np.uint8)   # filter byte 0, then the row
+    rows[:, 1:] = img.reshape(H, 3 * W)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)) +
+                 chunk(b"IDAT", zlib.compress(rows.tobytes(), PNG_COMPRESSION)) + chunk(b"IEND", b""))
+
+
+def obj_file_names(path):
+    """The four files of save_obj(path, ...), and the stem they share without its folder: (obj, mtl, albedo png, normal png,
+    stem).  ValueError unless path ends in .obj."""
+    import os
+    if not str(path).lower().endswith(".obj"):
+        raise ValueError(f"save_obj: {path!r} must end in .obj")
+    stem = str(path)[:-4]
+    return str(path), stem + ".mtl", stem + "_albedo.png", stem + "_normal.png", os.path.basename(stem)
+
+
+def save_obj(path, textured_mesh, light_map=None):
+    """Wavefront OBJ of a TexturedMesh, four files: `path` (<stem>.obj) with v and vn per vertex, vt per corner (3 F of them)
+    and f a/ta/a b/tb/b c/tc/c, 1-based, floats as %.9g (float32 values round-trip exactly); <stem>.mtl with newmtl intrinsic,
+    Kd 1 1 1, map_Kd <stem>_albedo.png and norm <stem>_normal.png; and the two PNGs (save_png).  light_map (H, W, 3) uint8,
+    optional: the image written as <stem>_albedo.png instead of the albedo map (e.g. a shaded one)."""
+    obj, mtl, png_a, png_n, stem = obj_file_names(path)
+    tm = textured_mesh
+    v = np.asarray(_host(tm.mesh.positions), dtype=np.float32).reshape(-1, 3)
+    n = np.asarray(_host(tm.mesh.normals), dtype=np.float32).reshape(-1, 3)
+    t = np.asarray(_host(tm.mesh.triangles), dtype=np.int64).reshape(-1, 3)
+    uv = np.asarray(_host(tm.uv), dtype=np.float32).reshape(-1, 2)
+    if len(uv) != 3 * len(t) or len(n) != len(v):
+        raise ValueError(f"save_obj: {len(t)} triangles but {len(uv)} texture coordinates, {len(v)} vertices but {len(n)} normals")
+    g = lambda x: "%.9g" % x
+    lines = [f"mtllib {stem}.mtl", "usemtl intrinsic"]
+    lines += ["v " + " ".join(map(g, r)) for r in v.tolist()]
+    lines += ["vn " + " ".join(map(g, r)) for r in n.tolist()]
+    lines += ["vt " + " ".join(map(g, r)) for r in uv.tolist()]
+    lines += ["f " + " ".join(f"{a + 1}/{3 * k + m + 1}/{a + 1}" for m, a in enumerate(r)) for k, r in enumerate(t.tolist())]
+    with open(obj, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    with open(mtl, "w") as fh:
+        fh.write(f"newmtl intrinsic\nKd 1 1 1\nmap_Kd {stem}_albedo.png\nnorm {stem}_normal.png\n")
+    save_png(png_a, tm.albedo_map if light_map is None else light_map)
+    save_png(png_n, tm.normal_map)

@@ -588,6 +588,51 @@ def mesh_vertex_record(pos, normals, rgb):
 
 
 # ------------------------------------------------------------------------------------------
+# textured mesh export (include/oi_mesh_tex.h); oi_amd.mesh.bake_textures sequences these around the vertex pass's chain
+# ------------------------------------------------------------------------------------------
+
+def tex_layout(F, T):
+    """The atlas of F triangles at texel size T -> (W, H, cols): oi_tex_layout, a host-only query (no device is touched).
+    ValueError for a texel size outside its range or an atlas above lib.TEX_MAX_SIZE."""
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or not _l.TEX_MIN_TEXEL <= int(T) <= _l.TEX_MAX_TEXEL:
+        raise ValueError(f"texel={T!r} (an integer, {_l.TEX_MIN_TEXEL} <= texel <= {_l.TEX_MAX_TEXEL})")
+    W, H, cols = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    L = _l.load()
+    if L.oi_tex_layout(int(F), int(T), ctypes.byref(W), ctypes.byref(H), ctypes.byref(cols)) != 0:
+        raise ValueError(L.oi_last_error().decode())
+    return W.value, H.value, cols.value
+
+
+def _tris(triangles):
+    if triangles.dtype != torch.int32 or not triangles.is_cuda or not triangles.is_contiguous():
+        raise _l.OiHipError("expected a contiguous int32 CUDA tensor of triangles (there is no CPU path)")
+    return _vp(triangles.data_ptr())
+
+
+def tex_uv(F, T, ref):
+    """Texture coordinates (F, 3, 2) of every corner of the atlas of F triangles at texel size T (on ref's device)."""
+    uv = _new(ref, F, 3, 2)
+    _l.check(_l.load().oi_tex_uv(F, int(T), _p(uv), _stream()), "oi_tex_uv")
+    return uv
+
+
+def tex_points(pos, triangles, f0, nf, T, out=None, flags=None):
+    """The planar texel points (nf * n_T, 3) of triangles f0 .. f0 + nf - 1 and their cleared flags (nf * n_T,) uint8; `out`
+    and `flags`: caller-provided buffers of at least that many rows, whose leading rows are written and returned."""
+    n = nf * (T * (T + 1) // 2)
+    out = _new(pos, n, 3) if out is None else out[:n]
+    flags = _bytes(pos, n) if flags is None else flags[:n]
+    _l.check(_l.load().oi_tex_points(_p(pos), _tris(triangles), f0, nf, int(T), _p(out), _p(flags), _stream()), "oi_tex_points")
+    return out, flags
+
+
+def tex_store(normals, rgb, f0, nf, T, F, albedo_f32=None, normal_f32=None, albedo_u8=None, normal_u8=None):
+    """Scatter the normals and colours (nf * n_T, 3) of a chunk into the atlases given (H, W, 3), float32 or uint8."""
+    _l.check(_l.load().oi_tex_store(_p(normals), _p(rgb), f0, nf, int(T), F, _p(albedo_f32), _p(normal_f32), _p(albedo_u8),
+                                    _p(normal_u8), _stream()), "oi_tex_store")
+
+
+# ------------------------------------------------------------------------------------------
 # sphere-traced surface rendering (include/oi_trace.h); oi_amd.trace sequences these around sdf_mlp_fwd
 # ------------------------------------------------------------------------------------------
 

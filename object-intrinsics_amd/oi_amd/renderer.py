@@ -145,6 +145,12 @@ class NeuSRenderer:
         return (m.positions.cpu().numpy().astype(np.float64), m.triangles.cpu().numpy().astype(np.int64),
                 m.normals.cpu().numpy(), m.albedo.cpu().numpy())
 
+    def extract_textured_geometry(self, z=None, w=None, resolution=64, texel=8, **kw):
+        """oi_amd.mesh.extract_textured_mesh on this renderer: a coarse intrinsic mesh with a per-triangle UV atlas and baked
+        albedo and normal maps -> oi_amd.mesh.TexturedMesh (mesh.save_obj writes it)."""
+        from . import mesh
+        return mesh.extract_textured_mesh(self, z=z, w=w, resolution=resolution, texel=texel, **kw)
+
 
 class _RenderScalars(torch.autograd.Function):
     """(gradient_error, surface_loss) from the compositing reductions in one launch each way (oi_render_scalars_fwd / _bwd);

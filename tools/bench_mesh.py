@@ -17,7 +17,14 @@ and band timed in the same session:
   extract_dense_ms / extract_band_ms   NeuSRenderer.extract_geometry(band=False / True)
   intrinsic_dense_ms / intrinsic_band_ms   mesh.extract_intrinsic_mesh(refine=2, band=False / True)
   active_fraction (of the blocks), evaluated_fraction a (active-block points / lattice points), points_evaluated, n_triangles,
-  identical (vertices, triangles and records byte-identical), bar_ms = 1.5 (a field_dense_ms + coarse_ms), bar_met"""
+  identical (vertices, triangles and records byte-identical), bar_ms = 1.5 (a field_dense_ms + coarse_ms), bar_met
+
+--texture [--texel T]: the textured export instead, per resolution (default 64,128), both timed in the
+same session:
+  intrinsic_ms / textured_ms   mesh.extract_intrinsic_mesh(refine=2) / mesh.extract_textured_mesh(refine=2, texel=T)
+  bake_ms                      mesh.bake_textures alone on the extracted mesh; full_pass_ms: one full MLP pass (sdf, gradient,
+                               albedo) over as many points as the atlas has texels; bake_ms_per_mtexel / full_pass_ms_per_mtexel
+  n_triangles, n_texels (F n_T), atlas = [W, H], flagged texels"""
 import argparse
 import json
 import os
@@ -36,11 +43,13 @@ from oi_amd.renderer import NeuSRenderer  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--res", default=None)
 ap.add_argument("--band", action="store_true")
+ap.add_argument("--texture", action="store_true")
+ap.add_argument("--texel", type=int, default=8)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=10)
 args = ap.parse_args()
 if args.res is None:
-    args.res = "128,256,512,1024" if args.band else "128,256,512"
+    args.res = "128,256,512,1024" if args.band else "64,128" if args.texture else "128,256,512"
 
 
 def median_ms(fn):
@@ -93,6 +102,30 @@ if args.band:
                 out["band"].setdefault(str(R), {})[str(block)] = {k: (round(x, 4) if isinstance(x, float) else x) for k, x in row.items()}
                 del m1, v1, t1
             del m0, v0, t0
+            torch.cuda.empty_cache()
+    print(json.dumps(out))
+    sys.exit(0)
+
+if args.texture:
+    from oi_amd.fields import LatentField  # noqa: E402
+    out.update(texture={}, texel=args.texel)
+    box = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
+    with torch.no_grad():
+        for R in (int(x) for x in args.res.split(",")):
+            m = mesh.extract_intrinsic_mesh(r, z=z, resolution=R, refine=2)
+            tm = mesh.bake_textures(r.pack, m, *box, R, z=z, texel=args.texel)
+            n = tm.texel_flags.numel()
+            fld = LatentField(r.pack, z, None, "bench_mesh").prepare(z, None)
+            pts = torch.rand(n, 3, device="cuda") * 2 - 1
+            row = {"intrinsic_ms": median_ms(lambda: mesh.extract_intrinsic_mesh(r, z=z, resolution=R, refine=2)),
+                   "textured_ms": median_ms(lambda: mesh.extract_textured_mesh(r, z=z, resolution=R, refine=2, texel=args.texel)),
+                   "bake_ms": median_ms(lambda: mesh.bake_textures(r.pack, m, *box, R, z=z, texel=args.texel)),
+                   "full_pass_ms": median_ms(lambda: fld.full(pts))}
+            row.update(bake_ms_per_mtexel=row["bake_ms"] / n * 1e6, full_pass_ms_per_mtexel=row["full_pass_ms"] / n * 1e6,
+                       n_triangles=int(m.triangles.shape[0]), n_texels=n, atlas=list(tm.size),
+                       flagged=int((tm.texel_flags != 0).sum()))
+            out["texture"][str(R)] = {k: (round(x, 4) if isinstance(x, float) else x) for k, x in row.items()}
+            del m, tm, pts
             torch.cuda.empty_cache()
     print(json.dumps(out))
     sys.exit(0)

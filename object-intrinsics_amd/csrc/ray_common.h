@@ -20,13 +20,17 @@ __device__ __forceinline__ float linspace_at(float start, float end, int n, int 
 struct RayOD {
   float o[3], d[3], near_, far_;
 };
-__device__ __forceinline__ RayOD make_ray(const float* __restrict__ M /* c2b 4x4 */, const float* __restrict__ kinv, float offx,
-                                          float offy, int R, int x, int y) {
+// build_rays: pixels = linspace(0,1,R) * recp_size + offset   (generator.py:325-329): the coordinate of pixel i of R
+__device__ __forceinline__ float pixel_coord(int R, int i, float off) {
+#pragma clang fp contract(off)
+  return linspace_at(0.f, 1.f, R, i) * (float)R + off;
+}
+
+// the ray through the pixel coordinates (px, py): a pixel centre (make_ray) or a point inside a pixel (aa.hip's sub-pixel rays)
+__device__ __forceinline__ RayOD make_ray_at(const float* __restrict__ M /* c2b 4x4 */, const float* __restrict__ kinv, float px,
+                                             float py) {
 #pragma clang fp contract(off)
   RayOD r;
-  // build_rays: pixels = linspace(0,1,R) * recp_size + offset   (generator.py:325-329)
-  const float px = linspace_at(0.f, 1.f, R, x) * (float)R + offx;
-  const float py = linspace_at(0.f, 1.f, R, y) * (float)R + offy;
   float p[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) p[i] = kinv[i * 3 + 0] * px + kinv[i * 3 + 1] * py + kinv[i * 3 + 2];
@@ -46,6 +50,11 @@ __device__ __forceinline__ RayOD make_ray(const float* __restrict__ M /* c2b 4x4
   r.near_ = mid - 1.0f;
   r.far_ = mid + 1.0f;
   return r;
+}
+
+__device__ __forceinline__ RayOD make_ray(const float* __restrict__ M /* c2b 4x4 */, const float* __restrict__ kinv, float offx,
+                                          float offy, int R, int x, int y) {
+  return make_ray_at(M, kinv, pixel_coord(R, x, offx), pixel_coord(R, y, offy));
 }
 
 }  // namespace

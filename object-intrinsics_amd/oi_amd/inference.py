@@ -140,6 +140,7 @@ def light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), **kw):
 
 
 SURFACE_KEYS = ("image", "depth", "position", "normal_map", "normal_object", "albedo", "mask", "visibility", "ambient_occlusion")
+AA_KEYS = ("coverage", "aa_mask")   # with aa_samples > 1
 
 # Bytes of device memory per ray of one secondary (shadow / ambient-occlusion) trace: the arrays of an ops.TraceState (rays_o
 # 12, rays_d 12, near 4, far 4, t 4, status 1, steps 2, bracket 16, side 1, active 2 x 4, points 12 = 76), the sdf buffer of
@@ -153,7 +154,7 @@ OCCLUSION_MAX_RAYS = min((2 << 30) // TRACE_BYTES_PER_RAY, (1 << 31) - 1)
 
 @torch.no_grad()
 def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"), lights=None, shadows=False, bg=None, batch=1,
-                   **kw):
+                   aa_samples=1, aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, **kw):
     """render_frames by ray / surface intersection (oi_amd.trace.render_surface) instead of the volume render: one frame per
     (z, b2w) pair under ONE light (`lights`: a Light, default the trained one).  -> {key: (n, C, H, W)} for keys of
     SURFACE_KEYS ("visibility" needs shadows=True, "ambient_occlusion" ao_samples > 0).  Keyword arguments: render_surface's
@@ -161,12 +162,20 @@ def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"),
     batch: frames per primary trace, 1 .. 1024.  1: one render_surface per frame.  E > 1: the frames go through
     oi_amd.trace.render_surfaces in groups of E (the last group may be smaller) -- one chain of trace steps and one full MLP
     pass per group instead of per frame; shadow and occlusion rays are still traced per frame.  The
-    frames are those of batch=1."""
+    frames are those of batch=1.
+    aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern: render_surface's anti-aliasing, with the keys
+    "coverage" and "aa_mask"; it is per view, so aa_samples > 1 needs batch=1."""
     from . import lib, trace
     from .relight import Light
     if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= int(batch) <= lib.TRACE_BATCH_MAX_ELEMS:
         raise ValueError(f"surface_frames: batch={batch!r} (an integer, 1 <= batch <= {lib.TRACE_BATCH_MAX_ELEMS})")
-    unknown = [k for k in keys if k not in SURFACE_KEYS]
+    aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "surface_frames")
+    if aa is not None and batch > 1:
+        raise ValueError(f"surface_frames: aa_samples={aa_samples!r} with batch={batch!r} (the batched trace has no anti-aliasing "
+                         "stage: batch=1)")
+    if aa is not None:
+        kw.update(aa_samples=aa_samples, aa_adaptive=aa_adaptive, aa_plane=aa_plane, aa_cos=aa_cos, aa_pattern=aa_pattern)
+    unknown = [k for k in keys if k not in SURFACE_KEYS + (AA_KEYS if aa is not None else ())]
     if unknown or ("visibility" in keys and not shadows):
         raise ValueError(f"surface_frames: keys {unknown or ['visibility']} (one of {SURFACE_KEYS}; visibility with shadows=True)")
     if "ambient_occlusion" in keys and not kw.get("ao_samples", 0):
@@ -192,18 +201,78 @@ def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"),
     return {k: torch.stack(v) for k, v in frames.items()}
 
 
+def _walk_frames(s, lt, step, shadows, visibility, bg, ao, ao_sub):
+    """The frames of a light walk or orbit over the traced view s (a trace._Surface) under the stacked lights lt: per `step`
+    lights one shadow trace, visibility(surface, a, b) -> (b - a, N), and one shade launch.  With an anti-aliasing stage the
+    sub-sample surface s.sub, traced once with the view, passes the same two per chunk (ao_sub: its ambient occlusion) and
+    oi_aa_resolve writes the frames.  -> image (n, 3, N), visibility (n, N) or None, the first chunk's depth and mask,
+    coverage (N,) or None."""
+    from . import trace
+    n, dev = lt.shape[0], lt.device
+    image = torch.empty(n, 3, s.N, device=dev)
+    vis_all = torch.empty(n, s.N, device=dev) if shadows else None
+    maps = coverage = None
+    for a in range(0, n, step):
+        b = min(n, a + step)
+        vis = visibility(s, a, b) if shadows else None
+        if shadows:
+            vis_all[a:b] = vis
+        first = maps is None
+        out = s.shade(lt[a:b], trace._bg(bg, dev), vis, outputs=("depth", "mask", "image") if first else ("image",),
+                      image_out=image[a:b] if s.aa is None else None, ambient_occlusion=ao)
+        maps = maps or out
+        if s.aa is not None:
+            vis_sub = visibility(s.sub, a, b) if shadows and s.sub is not None else None
+            _, cov = trace._resolved(s, lt[a:b], trace._bg(bg, dev), {"image": out["image"], "mask": maps["mask"]}, vis_sub,
+                                     ao_sub, image_out=image[a:b], want_mask=first)
+            coverage = cov if first else coverage
+    return image, vis_all, maps, coverage
+
+
+def _most_hits(s):
+    """The larger hit count of the view and of its sub-sample surface (at least 1): what bounds a shadow trace's rays per light."""
+    return max(1, s.n_hit, s.sub.n_hit if s.sub is not None else 0)
+
+
+def _walk_ambient(s, ao_samples, ao_distance, seed):
+    """-> the ambient occlusion of the view and of its sub-sample surface (each None when there is none to trace)."""
+    if not ao_samples:
+        return None, None
+    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed))
+    return ao, s.sub.ambient(int(ao_samples), float(ao_distance), int(seed)) if s.sub is not None else None
+
+
+def _walk_result(s, image, vis_all, maps, coverage, ao, **extra):
+    """The dict surface_light_walk and surface_light_orbit return."""
+    n, H = image.shape[0], s.H
+    res = {"image": image.view(n, 3, H, H), "mask": maps["mask"].view(1, 1, H, H), "depth": maps["depth"].view(1, 1, H, H), **extra,
+           "stats": s.stats()}
+    if vis_all is not None:
+        res["visibility"] = vis_all.view(n, 1, H, H)
+    if ao is not None:
+        res["ambient_occlusion"] = ao.view(1, 1, H, H)
+    if s.aa is not None:
+        res["coverage"], res["aa_mask"] = coverage.view(1, 1, H, H), (s.edge_slot >= 0).float().view(1, 1, H, H)
+    return res
+
+
 @torch.no_grad()
 def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True, bg=None, bias=None, shadow_samples=1,
-                       light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0, **kw):
+                       light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0, aa_samples=1, aa_adaptive=True, aa_plane=0.5,
+                       aa_cos=0.5, aa_pattern=None, **kw):
     """light_walk on the traced surface, with cast shadows: ONE primary trace and ONE full MLP pass at its hits for the whole
     walk, one shadow trace and one shade launch per 256 lights.  Frame 0 is the trained light.  -> {"image": (n_frames, 3,
     H, W), "visibility": (n_frames, 1, H, W) when shadows, "mask" / "depth" (1, 1, H, W), "stats"}.
     shadow_samples, light_radius (a scalar or one value per frame), ao_samples, ao_distance, seed: render_surface's.  Soft shadows trace
     shadow_samples rays per light and visible point, so the lights are split further until one trace holds at most
     OCCLUSION_MAX_RAYS rays; the frames do not depend on the split (rays are independent, the samples keyed on pixel and seed).
-    Ambient occlusion does not depend on the light: ONE trace for the walk, returned as "ambient_occlusion" (1, 1, H, W)."""
+    Ambient occlusion does not depend on the light: ONE trace for the walk, returned as "ambient_occlusion" (1, 1, H, W).
+    aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern: render_surface's anti-aliasing.  The sub-samples
+    are traced ONCE for the walk, then shaded and resolved per chunk of lights; "coverage" and "aa_mask" (1, 1, H, W) are returned
+    too, and stats gains aa_pixels, aa_rays, aa_evals."""
     from . import lib, trace
     from .relight import Light, stack_lights
+    aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "surface_light_walk")
     base = Light.from_module(gen.light)
     dirs = light_walk_directions(base.direction, n_frames, axis)
     dev = gen.it.device
@@ -212,33 +281,16 @@ def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True,
     gen.renderer.pack.check()
     radii = trace._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_frames,
                                    "surface_light_walk")
-    s = trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw)
-    H = s.H
-    image = torch.empty(n_frames, 3, s.N, device=dev)
-    vis_all = torch.empty(n_frames, s.N, device=dev) if shadows else None
+    s = trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw, aa=aa)
     step = lib.RELIGHT_MAX_LIGHTS
     if radii is not None:
-        step = max(1, min(step, OCCLUSION_MAX_RAYS // (int(shadow_samples) * max(1, s.n_hit))))
+        step = max(1, min(step, OCCLUSION_MAX_RAYS // (int(shadow_samples) * _most_hits(s))))
         radii = torch.tensor(radii, dtype=torch.float32, device=dev)
-    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed)) if ao_samples else None
-    maps = None
-    for a in range(0, n_frames, step):
-        b = min(n_frames, a + step)
-        if shadows:
-            vis = s.visibility(lt[a:b]) if radii is None else s.visibility(lt[a:b], radii[a:b], int(shadow_samples), int(seed))
-            vis_all[a:b] = vis
-        else:
-            vis = None
-        out = s.shade(lt[a:b], trace._bg(bg, dev), vis, outputs=("image",) if maps is not None else ("depth", "mask", "image"),
-                      image_out=image[a:b], ambient_occlusion=ao)
-        maps = maps or out
-    res = {"image": image.view(n_frames, 3, H, H), "mask": maps["mask"].view(1, 1, H, H), "depth": maps["depth"].view(1, 1, H, H),
-           "stats": s.stats()}
-    if shadows:
-        res["visibility"] = vis_all.view(n_frames, 1, H, H)
-    if ao_samples:
-        res["ambient_occlusion"] = ao.view(1, 1, H, H)
-    return res
+    ao, ao_sub = _walk_ambient(s, ao_samples, ao_distance, seed)
+
+    def visibility(surface, a, b):
+        return trace._visibility(surface, lt[a:b], None if radii is None else radii[a:b], True, shadow_samples, seed)
+    return _walk_result(s, *_walk_frames(s, lt, step, shadows, visibility, bg, ao, ao_sub), ao)
 
 
 @torch.no_grad()
@@ -322,46 +374,34 @@ def _orbit_lights(light, n_frames, centre, radius, axis, height, what):
 
 @torch.no_grad()
 def surface_light_orbit(gen, z, b2w, light, n_frames=128, centre=(0.0, 0.0, 0.0), radius=1.5, axis=(0, -1, 0), height=0.0,
-                        shadows=True, bg=None, bias=None, shadow_samples=1, ao_samples=0, ao_distance=0.5, seed=0, **kw):
+                        shadows=True, bg=None, bias=None, shadow_samples=1, ao_samples=0, ao_distance=0.5, seed=0, aa_samples=1,
+                        aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, **kw):
     """A local light (oi_amd.relight.LocalLight) carried once round the object while the view stays: ONE
     primary trace and ONE full MLP pass at its hits for the whole orbit, then per 256 positions one trace of shadow rays that
     end at the light and one shade launch.  The positions are light_orbit_positions(centre, radius, n_frames, axis, height) in
     the world frame; everything else about the light stays (a cone keeps its world-frame axis).  The lights are split further
     until one shadow trace holds at most OCCLUSION_MAX_RAYS rays; the frames do not depend on the split.  -> {"image":
     (n_frames, 3, H, W), "visibility": (n_frames, 1, H, W) when shadows, "mask" / "depth" (1, 1, H, W), "positions" (n_frames, 3)
-    float64 numpy, "stats"}; with ao_samples also "ambient_occlusion" (1, 1, H, W), ONE trace for the orbit."""
+    float64 numpy, "stats"}; with ao_samples also "ambient_occlusion" (1, 1, H, W), ONE trace for the orbit.
+    aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern: as surface_light_walk's."""
     from . import lib, trace
     from .relight import stack_local_lights
+    aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "surface_light_orbit")
     pos, lights = _orbit_lights(light, n_frames, centre, radius, axis, height, "surface_light_orbit")
     dev = gen.it.device
     lt = stack_local_lights(lights, dev)
     gen.eval()
     gen.renderer.pack.check()
     trace._check_occlusion(shadows, shadow_samples, 0.0, ao_samples, ao_distance, seed, n_frames, "surface_light_orbit", True)
-    s = trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw)
-    H = s.H
-    image = torch.empty(n_frames, 3, s.N, device=dev)
-    vis_all = torch.empty(n_frames, s.N, device=dev) if shadows else None
+    s = trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw, aa=aa)
     step = lib.RELIGHT_MAX_LIGHTS
     if shadows:
-        step = max(1, min(step, OCCLUSION_MAX_RAYS // (int(shadow_samples) * max(1, s.n_hit))))
-    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed)) if ao_samples else None
-    maps = None
-    for a in range(0, n_frames, step):
-        b = min(n_frames, a + step)
-        vis = s.local_visibility(lt[a:b], int(shadow_samples), int(seed)) if shadows else None
-        if shadows:
-            vis_all[a:b] = vis
-        out = s.shade(lt[a:b], trace._bg(bg, dev), vis, outputs=("image",) if maps is not None else ("depth", "mask", "image"),
-                      image_out=image[a:b], ambient_occlusion=ao)
-        maps = maps or out
-    res = {"image": image.view(n_frames, 3, H, H), "mask": maps["mask"].view(1, 1, H, H), "depth": maps["depth"].view(1, 1, H, H),
-           "positions": pos, "stats": s.stats()}
-    if shadows:
-        res["visibility"] = vis_all.view(n_frames, 1, H, H)
-    if ao_samples:
-        res["ambient_occlusion"] = ao.view(1, 1, H, H)
-    return res
+        step = max(1, min(step, OCCLUSION_MAX_RAYS // (int(shadow_samples) * _most_hits(s))))
+    ao, ao_sub = _walk_ambient(s, ao_samples, ao_distance, seed)
+
+    def visibility(surface, a, b):
+        return surface.local_visibility(lt[a:b], int(shadow_samples), int(seed))
+    return _walk_result(s, *_walk_frames(s, lt, step, shadows, visibility, bg, ao, ao_sub), ao, positions=pos)
 
 
 @torch.no_grad()

@@ -113,6 +113,9 @@ class SurfaceAoParams(ctypes.Structure):
     _fields_ = SurfaceParams._fields_ + [("ambient_occlusion", _vp)]
 
 
+# include/oi_aa.h
+AA_MAX_SAMPLES, AA_DEFAULT_PLANE, AA_DEFAULT_COS = 64, 0.5, 0.5
+
 # include/oi_mesh_band.h
 BAND_MIN_RES, BAND_MAX_RES = 2, 1024
 
@@ -392,6 +395,13 @@ SIGS = {
         "oi_tex_uv": (_i, [_ll, _i, _vp, _vp]),
         "oi_tex_points": (_i, [_vp, _vp, _ll, _ll, _i, _vp, _vp, _vp]),
         "oi_tex_store": (_i, [_vp, _vp, _ll, _ll, _i, _ll] + [_vp] * 5),
+    },
+    # include/oi_aa.h: adaptive anti-aliasing of the traced surface (an addition to oi_trace.h; no struct of its own: plain
+    # arguments, and the state of oi_trace.h)
+    "oi_aa.h": {
+        "oi_aa_classify": (_i, [_vp] * 4 + [_ll, _i, _i, _f, _f, _vp, _vp, _vp, _vp]),
+        "oi_aa_begin": (_i, [_P(TraceState), _vp, _vp, _vp, _i, _vp, _ll, _vp, _i, _vp]),
+        "oi_aa_resolve": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _i, _vp, _vp]),
     },
 }
 

@@ -1060,6 +1060,57 @@ def surface_shade_local(rays_o, rays_d, t, status, hit_slot, hit_points, grad, r
     return res
 
 
+# ------------------------------------------------------------------------------------------
+# adaptive anti-aliasing of the traced surface (include/oi_aa.h); oi_amd.trace sequences these
+# ------------------------------------------------------------------------------------------
+
+def aa_classify(status, hit_slot, hit_points, grad, n_hit, H, W, plane_threshold=_l.AA_DEFAULT_PLANE,
+                cos_threshold=_l.AA_DEFAULT_COS):
+    """The pixels of an H x W primary trace that need more samples (oi_aa_classify).  -> edge_index (N,) int32 (its first
+    `count` entries are written: the flagged pixels, in no fixed order), edge_slot (N,) int32 (the pixel's position in
+    edge_index, or -1), count (1,) int32 on the device."""
+    N = int(H) * int(W)
+    if status.shape[0] != N or hit_slot.shape[0] != N:
+        raise ValueError(f"aa_classify: status {tuple(status.shape)}, hit_slot {tuple(hit_slot.shape)} for {H} x {W} pixels")
+    edge_index = torch.empty(N, dtype=torch.int32, device=status.device)   # (partly written by contract, as trace_finish's hit_index)
+    edge_slot = _new(status, N).view(torch.int32)
+    count = _new(status, 1).view(torch.int32)
+    _l.check(_l.load().oi_aa_classify(_p(status), _ip(hit_slot), _p(hit_points) if n_hit else None, _p(grad) if n_hit else None,
+                                      int(n_hit), int(H), int(W), float(plane_threshold), float(cos_threshold), _ip(edge_index),
+                                      _ip(edge_slot), _ip(count), _stream()), "oi_aa_classify")
+    return edge_index, edge_slot, count
+
+
+def aa_begin(st, c2b, kinv, offs, R, edge_index, n_edge, offsets):
+    """The sub-pixel rays of the first n_edge pixels of edge_index into the TraceState st of (S - 1) * n_edge rays, started as
+    trace_begin starts rays (oi_aa_begin).  c2b (16 floats), kinv (3, 3), offs (2 floats): gen_rays' at B = 1; offsets (S, 2)
+    float32 on the device, in units of the pixel pitch (row 0, the centre, is not read)."""
+    if offsets.dim() != 2 or offsets.shape[1] != 2 or offsets.dtype != torch.float32:
+        raise ValueError(f"aa_begin: offsets {tuple(offsets.shape)} {offsets.dtype}, expected float32 (S, 2)")
+    if c2b.numel() != 16 or kinv.numel() != 9 or offs.numel() != 2:
+        raise ValueError("aa_begin: c2b, kinv and offs must hold 16, 9 and 2 floats (one view)")
+    keep = [_c(c2b), _c(kinv), _c(offs), _c(offsets)]
+    _l.check(_l.load().oi_aa_begin(ctypes.byref(st.c), _p(keep[0]), _p(keep[1]), _p(keep[2]), int(R), _ip(edge_index), int(n_edge),
+                                   _p(keep[3]), offsets.shape[0], _stream()), "oi_aa_begin")
+
+
+def aa_resolve(centre, sub, edge_slot, n_edge, S, out=None):
+    """centre (P, N) and the sub-samples sub (P, (S - 1) * n_edge) (None with n_edge == 0) -> (P, N): centre off the flagged
+    pixels, the mean of the S samples on them (oi_aa_resolve), written into `out` when given."""
+    P, N = centre.shape
+    if n_edge and (sub is None or tuple(sub.shape) != (P, (int(S) - 1) * int(n_edge))):
+        raise ValueError(f"aa_resolve: sub {None if sub is None else tuple(sub.shape)}, expected {(P, (int(S) - 1) * int(n_edge))}")
+    if edge_slot.shape[0] != N or edge_slot.dtype != torch.int32:
+        raise ValueError(f"aa_resolve: edge_slot {tuple(edge_slot.shape)} {edge_slot.dtype}, expected int32 ({N},)")
+    if out is None:
+        out = _new(centre, P, N)
+    elif tuple(out.shape) != (P, N) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError(f"aa_resolve: out must be a contiguous float32 {(P, N)} tensor")
+    _l.check(_l.load().oi_aa_resolve(_p(centre), _p(sub) if n_edge else None, _ip(edge_slot), N, int(n_edge), int(S), P, _p(out),
+                                     _stream()), "oi_aa_resolve")
+    return out
+
+
 def scene_local_light_begin(sb, hit_points, grad, n_pad, offset, elem, pixel, position, normal, n_vis, w2b, bias, samples, j0, chunk,
                             lights, seed=0):
     """scene_occlusion_begin's chunk of rays aimed at local lights (L, 20) in the world frame: sb holds E occluder elements x

@@ -12,6 +12,9 @@
                      over the hemisphere of each visible point; include/oi_occlusion.h)
                      `lights` may also be oi_amd.relight.LocalLight objects: point, spot and sphere lights that stand in the
                      world, whose shadow rays end at the light (include/oi_local_light.h)
+                     aa_samples > 1: adaptive anti-aliasing -- the pixels at a geometric edge get sub-pixel rays, which go
+                     through the same march and shade, and the image is the mean of a pixel's samples (include/oi_aa.h,
+                     DESIGN section 4.29)
     capture_transfer one view's secondary rays traced ONCE into a per-pixel SH transfer map; the TransferCapture is then shaded
                      under any number of environment lights (oi_amd.envlight.EnvLight), 256 per launch
                      (include/oi_envlight.h); with glossy_samples it also traces a reflection-lobe
@@ -226,14 +229,69 @@ def _trace_batch(field, st, tol, omega, max_steps, readback):
     return out
 
 
-def _view_rays(gen, b2w):
-    """The rays of Generator.forward for one pose (4, 4): its own oi_gen_rays path.  -> rays_o, rays_d (N, 3), near, far (N,),
-    w2b (4, 4)."""
+def _view_rays_camera(gen, b2w):
+    """_view_rays and the view's camera, what oi_gen_rays was given: -> rays_o, rays_d (N, 3), near, far (N,), w2b (4, 4), c2b
+    (4, 4), kinv (3, 3), offs (2,).  The sub-pixel rays of the anti-aliasing stage are generated from the last three."""
     dev = gen.it.device
     prior = gen.sample_prior(1, {"b2w": b2w.to(dev, torch.float32).reshape(1, 4, 4)})
     rays = gen.gen_rays_at({}, prior)
+    offs = torch.stack([rays["x_offset"][0], rays["y_offset"][0]]).float().contiguous()
     return (rays["rays_o"].reshape(-1, 3), rays["rays_d"].reshape(-1, 3), rays["near"].reshape(-1), rays["far"].reshape(-1),
-            prior["w2b"][0].contiguous())
+            prior["w2b"][0].contiguous(), prior["c2b"][0].float().contiguous(), gen._kinv(dev), offs)
+
+
+def _view_rays(gen, b2w):
+    """The rays of Generator.forward for one pose (4, 4): its own oi_gen_rays path.  -> rays_o, rays_d (N, 3), near, far (N,),
+    w2b (4, 4)."""
+    return _view_rays_camera(gen, b2w)[:5]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# anti-aliasing (include/oi_aa.h; DESIGN section 4.29)
+# ---------------------------------------------------------------------------------------------------------------------
+AA_R2 = (0.7548776662466927, 0.5698402909980532)   # 1 / g and 1 / g^2 of the plastic number g: the R2 low-discrepancy sequence
+
+
+def aa_pattern_r2(S):
+    """The default sub-pixel pattern: offsets[j] = frac(0.5 + j AA_R2) - 0.5 in float64, rounded to float32.  -> (S, 2) numpy
+    float32 in units of the pixel pitch; row 0 (the pixel centre) is (0, 0), every row lies in [-0.5, 0.5)."""
+    v = 0.5 + np.arange(int(S), dtype=np.float64)[:, None] * np.asarray(AA_R2, dtype=np.float64)[None]
+    return (v - np.floor(v) - 0.5).astype(np.float32)
+
+
+@dataclasses.dataclass
+class _AA:
+    """Checked anti-aliasing parameters: S samples per flagged pixel (the centre included), offsets (S, 2) numpy float32."""
+    S: int
+    adaptive: bool
+    plane: float
+    cos: float
+    offsets: np.ndarray
+
+
+def _check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, what):
+    """-> None for aa_samples == 1 (no anti-aliasing stage), else the _AA.  Everything is checked either way."""
+    if not _is_count(aa_samples, 1, _l.AA_MAX_SAMPLES):
+        raise ValueError(f"{what}: aa_samples={aa_samples!r} (an integer, 1 <= aa_samples <= {_l.AA_MAX_SAMPLES})")
+    if not isinstance(aa_adaptive, (bool, np.bool_)):
+        raise ValueError(f"{what}: aa_adaptive={aa_adaptive!r} (True or False)")
+    for name, v in (("aa_plane", aa_plane), ("aa_cos", aa_cos)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= float(v) < 1:   # (NaN fails the comparison)
+            raise ValueError(f"{what}: {name}={v!r} (a number, 0 <= {name} < 1)")
+    S = int(aa_samples)
+    if aa_pattern is None:
+        offsets = aa_pattern_r2(S)
+    else:
+        try:
+            pat = np.asarray(aa_pattern.detach().cpu() if torch.is_tensor(aa_pattern) else aa_pattern, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: aa_pattern must be an array of shape ({S}, 2)") from None
+        if pat.shape != (S, 2):
+            raise ValueError(f"{what}: aa_pattern of shape {pat.shape} (one row per sample: ({S}, 2))")
+        if not (np.isfinite(pat).all() and (np.abs(pat) <= 0.5).all() and (pat[0] == 0).all()):
+            raise ValueError(f"{what}: aa_pattern (row 0, the pixel centre, must be (0, 0); every row within [-0.5, 0.5] pixel pitches)")
+        offsets = pat.astype(np.float32)
+    return None if S == 1 else _AA(S, bool(aa_adaptive), float(aa_plane), float(aa_cos), offsets)
 
 
 class _Surface:
@@ -252,13 +310,13 @@ class _Surface:
             raise ValueError(f"{what}: bias={bias!r} (>= 0 and finite)")
         return (float(tol), float(omega), int(max_steps), readback), float(bias)
 
-    def __init__(self, gen, z, b2w, bias, trace_kw, w=None):
+    def __init__(self, gen, z, b2w, bias, trace_kw, w=None, aa=None):
         kw, bias = self.params(bias, trace_kw)
         field = LatentField(gen, z, w, "render_surface")
         gen.eval()
         dev = gen.it.device
         field.prepare(None if z is None else z.to(dev), None if w is None else w.to(dev))
-        ro, rd, near, far, w2b = _view_rays(gen, b2w)
+        ro, rd, near, far, w2b, *camera = _view_rays_camera(gen, b2w)
         st = ops.TraceState(ro.shape[0], ro, rd, near, far)
         ops.trace_begin(st)
         res = _finish(st, *_march(field, st, st.N, *kw))
@@ -266,6 +324,8 @@ class _Surface:
         if res.hit_index.shape[0]:
             _, grad, rgb = field.full(res.hit_points)
         self._set(field, kw, bias, ro, rd, w2b, gen.resolution, res, grad, rgb)
+        if aa is not None:
+            self._antialias(aa, *camera)
 
     def _set(self, field, kw, bias, ro, rd, w2b, H, res, grad, rgb):
         self.kw, self.bias, self.field = kw, bias, field
@@ -273,6 +333,8 @@ class _Surface:
         self.res, self.n_hit, self.grad, self.rgb = res, res.hit_index.shape[0], grad, rgb
         self.shadow_evals = self.ao_evals = self.transfer_evals = self.glossy_evals = self.bounce_points = 0
         self.shadow = self.ao = self.transfer_state = self.glossy_state = self.bounce_hits = None
+        self.aa = self.sub = self.edge_slot = None   # the anti-aliasing stage (_antialias), when there is one
+        self.n_edge = 0
 
     @classmethod
     def from_batch(cls, field, kw, bias, ro, rd, w2b, H, res, grad, rgb):
@@ -280,6 +342,35 @@ class _Surface:
         self = cls.__new__(cls)
         self._set(field, kw, bias, ro, rd, w2b, H, res, grad, rgb)
         return self
+
+    def _antialias(self, aa, c2b, kinv, offs):
+        """The anti-aliasing stage (include/oi_aa.h): the flagged pixels (adaptive: oi_aa_classify and one read-back of their
+        number; otherwise every pixel), their aa.S - 1 sub-pixel rays each, the march on those rays (closest hit) and one full
+        MLP pass at their hits.  self.sub: the sub-sample rays as one more _Surface (ray (j - 1) * n_edge + e: sample j of
+        flagged pixel e), which the light-dependent stages treat as they treat this one; None without a flagged pixel."""
+        r, H = self.res, self.H
+        if aa.adaptive:
+            edge_index, edge_slot, count = ops.aa_classify(r.status, r.hit_slot, r.hit_points, self.grad, self.n_hit, H, H,
+                                                           aa.plane, aa.cos)
+            n_edge = int(count.item())
+            if n_edge:
+                # The compaction's order differs from run to run, and the sub-sample ray index keys the shadow and occlusion
+                # samples: the flagged pixels in ascending order make the frame a function of its arguments alone.
+                edge_index[:n_edge] = torch.sort(edge_index[:n_edge]).values
+                edge_slot[edge_index[:n_edge].long()] = torch.arange(n_edge, dtype=torch.int32, device=edge_slot.device)
+        else:
+            edge_index = edge_slot = torch.arange(self.N, dtype=torch.int32, device=self.ro.device)
+            n_edge = self.N
+        self.aa, self.edge_slot, self.n_edge = aa, edge_slot, n_edge
+        if n_edge == 0:
+            return
+        st = ops.TraceState((aa.S - 1) * n_edge, ref=self.ro)
+        ops.aa_begin(st, c2b, kinv, offs, H, edge_index, n_edge, torch.from_numpy(aa.offsets).to(self.ro.device))
+        res = _finish(st, *_march(self.field, st, st.N, *self.kw))
+        grad = rgb = None
+        if res.hit_index.shape[0]:
+            _, grad, rgb = self.field.full(res.hit_points)
+        self.sub = _Surface.from_batch(self.field, self.kw, self.bias, st.rays_o, st.rays_d, self.w2b, H, res, grad, rgb)
 
     def _secondary(self, st, anyhit=True):
         """The loop on a state of secondary rays that a begin entry has filled (any-hit after an oi_occlusion_*_begin); rays in
@@ -407,6 +498,10 @@ class _Surface:
         s = self.res.counts()
         s.update(n_rays=self.N, n_evals=self.res.n_evals, n_steps=self.res.n_steps, shadow_evals=self.shadow_evals,
                  ao_evals=self.ao_evals)
+        if self.aa is not None:   # aa_evals: every sdf evaluation the sub-samples cost (their march, shadow and occlusion rays)
+            sub = self.sub
+            s.update(aa_pixels=self.n_edge, aa_rays=(self.aa.S - 1) * self.n_edge,
+                     aa_evals=0 if sub is None else sub.res.n_evals + sub.shadow_evals + sub.ao_evals)
         return s
 
 
@@ -485,7 +580,8 @@ _MAP_NAMES = {"depth": "depth", "position": "position", "normal_world": "normal_
 
 @torch.no_grad()
 def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAULT_BIAS, shadow_samples=1, light_radius=0.0,
-                   ao_samples=0, ao_distance=0.5, seed=0, **trace_kw):
+                   ao_samples=0, ao_distance=0.5, seed=0, aa_samples=1, aa_adaptive=True, aa_plane=_l.AA_DEFAULT_PLANE,
+                   aa_cos=_l.AA_DEFAULT_COS, aa_pattern=None, **trace_kw):
     """One view of `gen` (latent z (z_dim,) or (1, z_dim), pose b2w (4, 4)) by intersecting each pixel's ray with the surface:
     -> dict of depth (1, 1, H, W) (the ray parameter; NaN off the mask), position, normal_map (world frame), normal_object,
     albedo (1, 3, H, W), mask (1, 1, H, W), image (L, 3, H, W) under `lights` (oi_amd.relight.Light objects; default the
@@ -499,29 +595,71 @@ def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAUL
     Ambient occlusion: ao_samples > 0 sends that many cosine-weighted rays over each visible point's hemisphere, as far as
     ao_distance; the share that escapes multiplies the ambient term and is returned as ambient_occlusion (1, 1, H, W).  The
     samples are a function of pixel, sample number and `seed` alone.  With shadow_samples == 1, light_radius == 0 and
-    ao_samples == 0 the launches are those of a call without these arguments."""
+    ao_samples == 0 the launches are those of a call without these arguments.
+    Anti-aliasing (include/oi_aa.h): aa_samples = S in 2 .. 64 takes S samples inside each FLAGGED pixel --
+    the centre and S - 1 sub-pixel rays at aa_pattern (S, 2), offsets in pixel pitches within [-0.5, 0.5] whose row 0 is
+    (0, 0); default aa_pattern_r2(S) -- and `image` is the mean of their shaded values, off-surface samples carrying bg.  A
+    pixel is flagged when a neighbour differs in the mask, lies off its tangent plane by more than asin(aa_plane), or has a
+    normal more than acos(aa_cos) away; aa_adaptive=False flags every pixel.  The sub-samples pass the same stages as the
+    centres (shadows, occlusion, local lights; their sample numbers keyed by the sub-sample ray).  New keys: coverage
+    (1, 1, H, W), the mean of the mask over a pixel's samples; aa_mask (1, 1, H, W), the flagged pixels; aa_trace, the
+    sub-samples' TraceResult (ray (j - 1) * aa_pixels + e: sample j of the e-th flagged pixel in ascending order; None without one); stats
+    gains aa_pixels, aa_rays, aa_evals.  Every other map stays the centre sample's.  With aa_samples == 1 nothing of this runs."""
+    aa = _check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "render_surface")
     dev = gen.it.device
     z = z.to(dev).reshape(1, -1)
-    s = _Surface(gen, z, b2w, bias, trace_kw)
+    s = _Surface(gen, z, b2w, bias, trace_kw, aa=aa)
     lt = _stack_lights(gen, lights, dev, "render_surface", "; inference.surface_light_walk splits larger sets")
     radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surface",
                              _is_local(lt))
     return _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev)
 
 
+def _visibility(s, lt, radii, shadows, shadow_samples, seed):
+    """The (L, N) visibility of the lights lt at the surface s, or None without shadows.  radii: None for hard shadows, else
+    the (L,) angular radii on the device; local lights carry their own size."""
+    if not shadows:
+        return None
+    if _is_local(lt):
+        return s.local_visibility(lt, int(shadow_samples), int(seed))
+    return s.visibility(lt) if radii is None else s.visibility(lt, radii, int(shadow_samples), int(seed))
+
+
+def _resolved(s, lt, bgv, centre, vis_sub, ao_sub, image_out=None, want_mask=False):
+    """The anti-aliased image of a view with an anti-aliasing stage: the sub-sample surface shaded as the centre was (under lt,
+    with its own visibility and occlusion) and oi_aa_resolve over centre["image"] (L, 3, N).  -> image (L, 3, N) (written into
+    image_out when given), coverage (N,) or None (want_mask: the same mean over centre["mask"])."""
+    L, sub = lt.shape[0], None
+    if s.sub is not None:
+        sub = s.sub.shade(lt, bgv, vis_sub, outputs=("mask", "image") if want_mask else ("image",), ambient_occlusion=ao_sub)
+    image = ops.aa_resolve(centre["image"].view(3 * L, s.N), None if sub is None else sub["image"].view(3 * L, -1), s.edge_slot,
+                           s.n_edge, s.aa.S, out=None if image_out is None else image_out.view(3 * L, s.N)).view(L, 3, s.N)
+    coverage = None
+    if want_mask:
+        coverage = ops.aa_resolve(centre["mask"].view(1, s.N), None if sub is None else sub["mask"].view(1, -1), s.edge_slot,
+                                  s.n_edge, s.aa.S).view(s.N)
+    return image, coverage
+
+
 def _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev):
     """The light-dependent stages of one traced view (a _Surface) and render_surface's dict."""
-    if _is_local(lt):
-        vis = s.local_visibility(lt, int(shadow_samples), int(seed)) if shadows else None
-    elif radii is None:
-        vis = s.visibility(lt) if shadows else None
-    else:
-        vis = s.visibility(lt, torch.tensor(radii, dtype=torch.float32, device=dev), int(shadow_samples), int(seed))
+    if radii is not None:
+        radii = torch.tensor(radii, dtype=torch.float32, device=dev)
+    vis = _visibility(s, lt, radii, shadows, shadow_samples, seed)
     ao = s.ambient(int(ao_samples), float(ao_distance), int(seed)) if ao_samples else None
     out = s.shade(lt, _bg(bg, dev), vis, ambient_occlusion=ao)
     H = s.H
     res = {_MAP_NAMES[k]: v for k, v in _maps({k: v for k, v in out.items() if k != "image"}, H, H).items()}
     res["image"] = out["image"].view(-1, 3, H, H)
+    if s.aa is not None:   # the sub-samples through the same stages, then the mean over each flagged pixel's samples
+        vis_sub = ao_sub = None
+        if s.sub is not None:
+            vis_sub = _visibility(s.sub, lt, radii, shadows, shadow_samples, seed)
+            ao_sub = s.sub.ambient(int(ao_samples), float(ao_distance), int(seed)) if ao_samples else None
+        image, coverage = _resolved(s, lt, _bg(bg, dev), out, vis_sub, ao_sub, want_mask=True)
+        res["image"], res["coverage"] = image.view(-1, 3, H, H), coverage.view(1, 1, H, H)
+        res["aa_mask"] = (s.edge_slot >= 0).float().view(1, 1, H, H)
+        res["aa_trace"] = None if s.sub is None else s.sub.res
     if shadows:
         res["visibility"] = vis.view(-1, 1, H, H)
         res["shadow_trace"] = s.shadow   # ops.TraceState of the L x n_hit shadow rays (ray l * n_hit + i), or None without a hit

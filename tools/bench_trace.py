@@ -29,7 +29,12 @@ same call's unchanged per-frame loop (batch=1) in the same session, without and 
 With --local [--light-size R] [--light-distance D] the tool measures ONLY, per resolution, the frame under
 the trained directional light and under a local light (oi_amd.relight.LocalLight) D along the same direction from the object's
 centre: no shadows, one hard shadow ray, and 16 samples of a light with a size (angular radius 0.1 / a sphere of radius R),
-each with the sdf evaluations of its shadow trace."""
+each with the sdf evaluations of its shadow trace.
+
+With --aa S [--aa-full] the tool measures ONLY, per resolution and in one session, the frame of
+render_surface under the trained light with one sample per pixel (aa_samples=1: the path without the stage), with S samples in
+the flagged pixels (adaptive), and -- with --aa-full -- with S samples in every pixel (aa_adaptive=False); with each the flagged
+pixels, the sub-sample rays, their sdf evaluations and the steps of the second chain."""
 import argparse
 import json
 import os
@@ -59,6 +64,8 @@ ap.add_argument("--batch", default="", help="frames per batched primary trace, e
 ap.add_argument("--local", action="store_true", help="time local lights (oi_amd.relight.LocalLight) beside the directional path, only")
 ap.add_argument("--light-size", type=float, default=0.15, help="with --local: radius of the sphere light of the sampled row")
 ap.add_argument("--light-distance", type=float, default=2.0, help="with --local: distance of the local light from the object's centre")
+ap.add_argument("--aa", type=int, default=0, help="samples per flagged pixel: time anti-aliased frames beside the one-sample frame, only")
+ap.add_argument("--aa-full", action="store_true", help="with --aa: also time aa_adaptive=False (every pixel flagged)")
 args = ap.parse_args()
 
 
@@ -180,6 +187,36 @@ def local_rows():
         del gen
     return rows
 
+
+def aa_rows():
+    """Per resolution: the one-sample frame, the adaptive frame and (--aa-full) the fully supersampled frame."""
+    rows = {}
+    for R in (int(r) for r in args.res.split(",")):
+        gen, z, b2w = setup(R)
+        cases = {"one_sample": dict(aa_samples=1), "adaptive": dict(aa_samples=args.aa)}
+        if args.aa_full:
+            cases["full"] = dict(aa_samples=args.aa, aa_adaptive=False)
+        row = {"rays": R * R}
+        for name, kw in cases.items():
+            row[name + "_ms"] = median_ms(lambda: trace.render_surface(gen, z, b2w, **kw))
+            out = trace.render_surface(gen, z, b2w, **kw)
+            st = out["stats"]
+            row["n_evals"], row["n_steps"] = st["n_evals"], st["n_steps"]
+            if name != "one_sample":
+                sub = out["aa_trace"]
+                row[name] = {"aa_pixels": st["aa_pixels"], "aa_share": st["aa_pixels"] / (R * R), "aa_rays": st["aa_rays"],
+                             "aa_evals": st["aa_evals"], "aa_steps": 0 if sub is None else sub.n_steps,
+                             "ms_over_one_sample": row[name + "_ms"] / row["one_sample_ms"]}
+        rows[str(R)] = row
+        del gen
+    return rows
+
+
+if args.aa:
+    with torch.no_grad():
+        print(json.dumps({"tool": "bench_trace", "precision": args.precision, "iters": args.iters, "warmup": args.warmup,
+                          "aa_samples": args.aa, "aa": aa_rows()}))
+    sys.exit(0)
 
 if args.local:
     with torch.no_grad():

@@ -4,32 +4,16 @@
 //              the flagged pixels compacted like a trace step's survivors (trace_common.h's wg_slot)
 //   begin      the sub-pixel camera rays of the flagged pixels (ray_common.h's make_ray_at: oi_gen_rays' arithmetic), started
 //              as oi_trace_begin starts rays
-//   resolve    the centre value, or the mean of a flagged pixel's samples
+//   resolve    the centre value, or the mean of a flagged pixel's samples (the planes of the sub-samples at any stride)
 // The classifier reads its eight neighbours straight from global memory: an image's status, slots, points and gradients are
 // L2-resident, and the kernel is a few microseconds beside the 64-step chain that follows it.  No LDS beyond the compaction's
 // five words, no scratch, no float atomics.
+#include "aa_common.h"
 #include "ray_common.h"
-#include "trace_common.h"
-#include "../../include/oi_aa.h"
+
+#include "../../include/oi_scene_aa.h"  // oi_aa_resolve_strided: oi_aa_resolve's kernel at the scene's stride
 
 namespace {
-
-// (a . b) summed x, y, z in that order, every product and sum rounded on its own
-__device__ __forceinline__ float dot3(const float* a, const float* b) {
-#pragma clang fp contract(off)
-  return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-}
-
-// oi_aa.h's off(a): (g . u)^2 > ((s s) (g . g)) (u . u)
-__device__ __forceinline__ bool off_plane(const float* g, float gg, const float* u, float uu, float s2) {
-#pragma clang fp contract(off)
-  const float du = dot3(g, u);
-  return du * du > (s2 * gg) * uu;
-}
-
-__global__ void __launch_bounds__(64) aa_clear_kernel(int* __restrict__ count) {
-  if (threadIdx.x == 0) *count = 0;
-}
 
 __global__ void __launch_bounds__(TR_THREADS) aa_classify_kernel(const uint8_t* __restrict__ status, const int* __restrict__ hit_slot,
                                                                  const float* __restrict__ hit_points,
@@ -62,13 +46,10 @@ __global__ void __launch_bounds__(TR_THREADS) aa_classify_kernel(const uint8_t* 
         const bool hq = kq >= 0 && kq < n_hit;
         if (hq != hp) flag = true;
         if (!(hq && hp)) continue;
-        float u[3], gq[3];
+        float pq[3], gq[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) u[a] = hit_points[kq * 3 + a] - xp[a], gq[a] = grad[kq * 3 + a];
-        const float uu = dot3(u, u), gqq = dot3(gq, gq);
-        if (off_plane(gp, gpp, u, uu, s2) || off_plane(gq, gqq, u, uu, s2)) flag = true;  // ((g . -u)^2 == (g . u)^2 exactly)
-        const float d = dot3(gp, gq);
-        if (d <= 0.f || d * d < (c2 * gpp) * gqq) flag = true;
+        for (int a = 0; a < 3; ++a) pq[a] = hit_points[kq * 3 + a], gq[a] = grad[kq * 3 + a];
+        if (aa_pair_edge(xp, gp, gpp, pq, gq, s2, c2)) flag = true;
       }
     }
   }
@@ -102,23 +83,34 @@ __global__ void __launch_bounds__(TR_THREADS) aa_begin_kernel(const oi_trace_sta
 
 __global__ void __launch_bounds__(TR_THREADS) aa_resolve_kernel(const float* __restrict__ centre, const float* __restrict__ sub,
                                                                 const int* __restrict__ edge_slot, long long N, long long n_edge,
-                                                                int S, long long total, float* __restrict__ out) {
+                                                                int S, long long sub_stride, long long total, float* __restrict__ out) {
   const long long i = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
   if (i >= total) return;
   const long long plane = i / N, p = i - plane * N;
   const long long e = edge_slot[p];
   float acc = centre[i];
   if (e >= 0 && e < n_edge) {
-    const float* __restrict__ sp = sub + plane * (S - 1) * n_edge + e;
+    const float* __restrict__ sp = sub + plane * sub_stride + e;
     for (int j = 1; j < S; ++j) acc += sp[(long long)(j - 1) * n_edge];
     acc /= (float)S;
   }
   out[i] = acc;
 }
 
-inline int check_aa_samples(const char* what, int S) {
-  OI_REQUIRE(S >= 2 && S <= OI_AA_MAX_SAMPLES, "%s: S=%d (2 .. %d samples)", what, S, OI_AA_MAX_SAMPLES);
-  return OI_OK;
+// Arguments of oi_aa_resolve and oi_aa_resolve_strided, then the launch: one kernel for both.
+inline int launch_resolve(const char* what, const float* centre, const float* sub, long long sub_stride, const int* edge_slot,
+                          long long N, long long n_edge, int S, int P, float* out, oi_stream_t stream) {
+  OI_TRY(check_pixels(what, N, n_edge));
+  OI_TRY(check_aa_samples(what, S));
+  OI_REQUIRE((S - 1) * n_edge < (1ll << 31), "%s: S=%d x n_edge=%lld sub-samples ((S - 1) * n_edge < 2^31)", what, S, n_edge);
+  OI_REQUIRE(sub_stride >= (S - 1) * n_edge && sub_stride < (1ll << 31),
+             "%s: sub_stride=%lld ((S - 1) * n_edge = %lld <= sub_stride < 2^31)", what, sub_stride, (S - 1) * n_edge);
+  OI_REQUIRE(P >= 1 && (long long)P * N < (1ll << 39), "%s: P=%d planes of N=%lld (P >= 1, P * N < 2^39)", what, P, N);
+  OI_REQUIRE(centre && edge_slot && out && (sub || n_edge == 0), "%s: null pointer", what);
+  const long long total = (long long)P * N;
+  hipLaunchKernelGGL(aa_resolve_kernel, dim3(n_blocks(total)), dim3(TR_THREADS), 0, oi::as_stream(stream), centre, sub, edge_slot, N,
+                     n_edge, S, sub_stride, total, out);
+  return oi::check_launch(what);
 }
 
 }  // namespace
@@ -131,8 +123,7 @@ int oi_aa_classify(const uint8_t* status, const int* hit_slot, const float* hit_
   const char* what = "oi_aa_classify";
   OI_REQUIRE(H >= 1 && W >= 1, "%s: H=%d, W=%d", what, H, W);
   OI_TRY(check_pixels(what, (long long)H * W, n_hit));
-  OI_REQUIRE(plane_threshold >= 0.f && plane_threshold < 1.f && cos_threshold >= 0.f && cos_threshold < 1.f,
-             "%s: plane_threshold %g, cos_threshold %g (both in [0, 1))", what, (double)plane_threshold, (double)cos_threshold);
+  OI_TRY(check_aa_thresholds(what, plane_threshold, cos_threshold));
   OI_REQUIRE(status && hit_slot && edge_index && edge_slot && count, "%s: null pointer", what);
   OI_REQUIRE(n_hit == 0 || (hit_points && grad), "%s: null hit arrays with n_hit=%lld", what, n_hit);
   const hipStream_t st = oi::as_stream(stream);
@@ -157,18 +148,14 @@ int oi_aa_begin(const oi_trace_state* s, const float* c2b, const float* kinv, co
   return oi::check_launch(what);
 }
 
+int oi_aa_resolve_strided(const float* centre, const float* sub, long long sub_stride, const int* edge_slot, long long N,
+                          long long n_edge, int S, int P, float* out, oi_stream_t stream) {
+  return launch_resolve("oi_aa_resolve_strided", centre, sub, sub_stride, edge_slot, N, n_edge, S, P, out, stream);
+}
+
 int oi_aa_resolve(const float* centre, const float* sub, const int* edge_slot, long long N, long long n_edge, int S, int P,
                   float* out, oi_stream_t stream) {
-  const char* what = "oi_aa_resolve";
-  OI_TRY(check_pixels(what, N, n_edge));
-  OI_TRY(check_aa_samples(what, S));
-  OI_REQUIRE((S - 1) * n_edge < (1ll << 31), "%s: S=%d x n_edge=%lld sub-samples ((S - 1) * n_edge < 2^31)", what, S, n_edge);
-  OI_REQUIRE(P >= 1 && (long long)P * N < (1ll << 39), "%s: P=%d planes of N=%lld (P >= 1, P * N < 2^39)", what, P, N);
-  OI_REQUIRE(centre && edge_slot && out && (sub || n_edge == 0), "%s: null pointer", what);
-  const long long total = (long long)P * N;
-  hipLaunchKernelGGL(aa_resolve_kernel, dim3(n_blocks(total)), dim3(TR_THREADS), 0, oi::as_stream(stream), centre, sub, edge_slot, N,
-                     n_edge, S, total, out);
-  return oi::check_launch(what);
+  return launch_resolve("oi_aa_resolve", centre, sub, (S - 1) * n_edge, edge_slot, N, n_edge, S, P, out, stream);
 }
 
 }  // extern "C"

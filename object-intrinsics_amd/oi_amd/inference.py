@@ -293,9 +293,54 @@ def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True,
     return _walk_result(s, *_walk_frames(s, lt, step, shadows, visibility, bg, ao, ao_sub), ao)
 
 
+def _scene_walk(s, lt, shadows, per_light, visibility, bg, ao_samples, ao_distance, seed, limit, **extra):
+    """The frames of a light walk or orbit over the traced scene s (a scene.SceneSurface) under the stacked lights lt, and the
+    dict scene_light_walk and scene_light_orbit return.  The lights are split so that one shadow batch of visibility(surface,
+    a, b) -> (b - a, S * S) holds at most `limit` rays, counted as per_light rays per light and visible point, and at most 256
+    lights; one shade launch per chunk.  With an anti-aliasing stage the sub-sample surface s.sub, traced once with the scene,
+    passes the same two per chunk, the chunks sized by the larger visible count of the two surfaces, and
+    oi_aa_resolve_strided writes the frames; ambient occlusion is traced once for each surface."""
+    from . import lib, trace
+    n, dev = lt.shape[0], lt.device
+    S, M = s.S, s.S * s.S
+    image = torch.empty(n, 3, M, device=dev)
+    vis_all = torch.empty(n, M, device=dev) if shadows else None
+    step = lib.RELIGHT_MAX_LIGHTS
+    if shadows:   # (one light above the limit is traced in chunks of samples; one sample above it is refused, naming the count)
+        n_vis = max(sum(s.n_vis), sum(s.sub.n_vis) if s.sub is not None else 0)
+        step = max(1, min(step, limit // max(1, s.E * n_vis * per_light)))
+    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples else None
+    ao_sub = s.sub.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples and s.sub is not None else None
+    maps = coverage = None
+    for a in range(0, n, step):
+        b = min(n, a + step)
+        vis = visibility(s, a, b) if shadows else None
+        if shadows:
+            vis_all[a:b] = vis
+        first = maps is None
+        out = s._shade(lt[a:b], trace._bg(bg, dev), vis, ("depth", "mask", "instance", "image") if first else ("image",),
+                       image[a:b] if s.aa is None else None, ao)
+        maps = maps or out
+        if s.aa is not None:
+            vis_sub = visibility(s.sub, a, b) if shadows and s.sub is not None else None
+            _, cov = s.resolved(lt[a:b], trace._bg(bg, dev), {"image": out["image"], "mask": maps["mask"]}, vis_sub, ao_sub,
+                                image_out=image[a:b], want_mask=first)
+            coverage = cov if first else coverage
+    res = {"image": image.view(n, 3, S, S), **extra, "stats": s.stats()}
+    res.update({k: maps[k].view(1, 1, S, S) for k in ("mask", "depth", "instance")})
+    if shadows:
+        res["visibility"] = vis_all.view(n, 1, S, S)
+    if ao_samples:
+        res["ambient_occlusion"] = ao.view(1, 1, S, S)
+    if s.aa is not None:
+        res["coverage"], res["aa_mask"] = coverage.view(1, 1, S, S), (s.edge_slot >= 0).float().view(1, 1, S, S)
+    return res
+
+
 @torch.no_grad()
 def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True, bg=None, bias=None, window=None,
-                     max_shadow_rays=None, shadow_samples=1, light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0, **kw):
+                     max_shadow_rays=None, shadow_samples=1, light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0, aa_samples=1,
+                     aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, **kw):
     """surface_light_walk on a scene of K instances (oi_amd.scene): the scene is traced ONCE -- one batched
     march, one depth resolve, one full MLP pass at the visible hits -- and shaded under the walk of lights, each instance
     shadowing itself and the others.  Frame 0 is the trained light.  The lights are split so that one shadow batch holds at
@@ -305,9 +350,13 @@ def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True,
     shadow_samples, light_radius (a scalar or one value per frame), ao_samples, ao_distance, seed: SceneSurface.shade's soft
     shadows and ambient occlusion between the instances; a light whose samples do not fit one batch is
     traced in chunks of samples.  Ambient occlusion does not depend on the light: ONE trace for the walk, returned as
-    "ambient_occlusion" (1, 1, S, S).  kw: tol, omega, max_steps, readback of sphere_trace."""
-    from . import lib, scene, trace
+    "ambient_occlusion" (1, 1, S, S).  kw: tol, omega, max_steps, readback of sphere_trace.
+    aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern: trace_scene's anti-aliasing.  The sub-samples
+    are traced ONCE for the walk, then shaded and resolved per chunk of lights; "coverage" and "aa_mask" (1, 1, S, S) are
+    returned too, and stats gains aa_pixels, aa_rays, aa_evals."""
+    from . import scene, trace
     from .relight import Light, stack_lights
+    trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "scene_light_walk")
     base = Light.from_module(gen.light)
     dirs = light_walk_directions(base.direction, n_frames, axis)
     dev = gen.it.device
@@ -316,31 +365,14 @@ def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True,
     gen.renderer.pack.check()
     radii = trace._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_frames, "scene_light_walk")
     limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
-    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, **kw)
-    S, M = s.S, s.S * s.S
-    image = torch.empty(n_frames, 3, M, device=dev)
-    vis_all = torch.empty(n_frames, M, device=dev) if shadows else None
-    step = lib.RELIGHT_MAX_LIGHTS
-    if shadows:   # (one light above the limit: SceneSurface.visibility refuses it, naming the count)
-        per_light = s.E * sum(s.n_vis) * (int(shadow_samples) if radii is not None else 1)
-        step = max(1, min(step, limit // max(1, per_light)))
-    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples else None
-    maps = None
-    for a in range(0, n_frames, step):
-        b = min(n_frames, a + step)
-        vis = s.visibility(lt[a:b], None if radii is None else radii[a:b], int(shadow_samples), int(seed), limit) if shadows else None
-        if shadows:
-            vis_all[a:b] = vis
-        out = s._shade(lt[a:b], trace._bg(bg, dev), vis, ("image",) if maps is not None else ("depth", "mask", "instance", "image"),
-                       image[a:b], ao)
-        maps = maps or out
-    res = {"image": image.view(n_frames, 3, S, S), "stats": s.stats()}
-    res.update({k: maps[k].view(1, 1, S, S) for k in ("mask", "depth", "instance")})
-    if shadows:
-        res["visibility"] = vis_all.view(n_frames, 1, S, S)
-    if ao_samples:
-        res["ambient_occlusion"] = ao.view(1, 1, S, S)
-    return res
+    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, aa_samples, aa_adaptive, aa_plane,
+                          aa_cos, aa_pattern, **kw)
+
+    def visibility(surface, a, b):
+        return surface.visibility(lt[a:b], None if radii is None else radii[a:b], int(shadow_samples), int(seed), limit)
+    # (one light above the limit: SceneSurface.visibility refuses it, naming the count)
+    return _scene_walk(s, lt, shadows, int(shadow_samples) if radii is not None else 1, visibility, bg, ao_samples, ao_distance, seed,
+                       limit)
 
 
 def light_orbit_positions(centre, radius, n_frames, axis=(0.0, -1.0, 0.0), height=0.0):
@@ -407,16 +439,18 @@ def surface_light_orbit(gen, z, b2w, light, n_frames=128, centre=(0.0, 0.0, 0.0)
 @torch.no_grad()
 def scene_light_orbit(gen, zs, b2ws, light, n_frames=128, centre=(0.0, 0.0, 0.0), radius=1.5, axis=(0, -1, 0), height=0.0,
                       shadows=True, bg=None, bias=None, window=None, max_shadow_rays=None, shadow_samples=1, ao_samples=0,
-                      ao_distance=0.5, seed=0, **kw):
+                      ao_distance=0.5, seed=0, aa_samples=1, aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, **kw):
     """surface_light_orbit on a scene of K instances (oi_amd.scene): the scene is traced ONCE and the local light is carried
     round `centre` -- between the instances, if the circle passes there -- each instance shadowing itself and the others as
     far as the light.  The lights are split so that one shadow batch holds at most max_shadow_rays rays (default
     oi_amd.scene.MAX_SHADOW_RAYS), counted as K * lights * shadow_samples * visible points, and at most 256 lights; a light
     whose samples do not fit one batch is traced in chunks of samples.  The frames do not depend on the split.  -> {"image":
     (n_frames, 3, S, S), "visibility": (n_frames, 1, S, S) when shadows, "mask" / "depth" / "instance" (1, 1, S, S),
-    "positions", "stats"}; with ao_samples also "ambient_occlusion" (1, 1, S, S)."""
-    from . import lib, scene, trace
+    "positions", "stats"}; with ao_samples also "ambient_occlusion" (1, 1, S, S).
+    aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern: as scene_light_walk's."""
+    from . import scene, trace
     from .relight import stack_local_lights
+    trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "scene_light_orbit")
     pos, lights = _orbit_lights(light, n_frames, centre, radius, axis, height, "scene_light_orbit")
     dev = gen.it.device
     lt = stack_local_lights(lights, dev)
@@ -424,30 +458,12 @@ def scene_light_orbit(gen, zs, b2ws, light, n_frames=128, centre=(0.0, 0.0, 0.0)
     gen.renderer.pack.check()
     trace._check_occlusion(shadows, shadow_samples, 0.0, ao_samples, ao_distance, seed, n_frames, "scene_light_orbit", True)
     limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
-    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, **kw)
-    S, M = s.S, s.S * s.S
-    image = torch.empty(n_frames, 3, M, device=dev)
-    vis_all = torch.empty(n_frames, M, device=dev) if shadows else None
-    step = lib.RELIGHT_MAX_LIGHTS
-    if shadows:   # (one light above the limit is traced in chunks of samples; one sample above it is refused, naming the count)
-        step = max(1, min(step, limit // max(1, s.E * sum(s.n_vis) * int(shadow_samples))))
-    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples else None
-    maps = None
-    for a in range(0, n_frames, step):
-        b = min(n_frames, a + step)
-        vis = s.local_visibility(lt[a:b], int(shadow_samples), int(seed), limit) if shadows else None
-        if shadows:
-            vis_all[a:b] = vis
-        out = s._shade(lt[a:b], trace._bg(bg, dev), vis, ("image",) if maps is not None else ("depth", "mask", "instance", "image"),
-                       image[a:b], ao)
-        maps = maps or out
-    res = {"image": image.view(n_frames, 3, S, S), "positions": pos, "stats": s.stats()}
-    res.update({k: maps[k].view(1, 1, S, S) for k in ("mask", "depth", "instance")})
-    if shadows:
-        res["visibility"] = vis_all.view(n_frames, 1, S, S)
-    if ao_samples:
-        res["ambient_occlusion"] = ao.view(1, 1, S, S)
-    return res
+    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, aa_samples, aa_adaptive, aa_plane,
+                          aa_cos, aa_pattern, **kw)
+
+    def visibility(surface, a, b):
+        return surface.local_visibility(lt[a:b], int(shadow_samples), int(seed), limit)
+    return _scene_walk(s, lt, shadows, int(shadow_samples), visibility, bg, ao_samples, ao_distance, seed, limit, positions=pos)
 
 
 def env_walk_rotations(n_frames, axis=(0.0, 0.0, 1.0)):
@@ -513,7 +529,8 @@ def scene_env_walk(gen, zs, b2ws, env, n_frames=128, axis=(0, 0, 1), transfer_sa
     gen.eval()
     gen.renderer.pack.check()
     limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
-    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, **kw)
+    # (the constructor, not trace_scene: the environment paths take no aa_* keyword)
+    s = scene.SceneSurface(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, kw)
     cap = s.capture_transfer(transfer_samples, seed, limit, glossy_samples, shininess, bounces)
     out = cap.shade([env.rotated(R) for R in rots], bg, specular)
     res = {k: out[k] for k in ("image", "shading", "mask", "depth", "instance")}

@@ -403,6 +403,13 @@ SIGS = {
         "oi_aa_begin": (_i, [_P(TraceState), _vp, _vp, _vp, _i, _vp, _ll, _vp, _i, _vp]),
         "oi_aa_resolve": (_i, [_vp, _vp, _vp, _ll, _ll, _i, _i, _vp, _vp]),
     },
+    # include/oi_scene_aa.h: adaptive anti-aliasing of a scene of many instances (an addition to oi_scene.h and oi_aa.h; no
+    # struct of its own)
+    "oi_scene_aa.h": {
+        "oi_scene_aa_classify": (_i, [_vp] * 5 + [_i, _ll, _ll, _i, _f, _f, _vp, _vp, _vp, _vp]),
+        "oi_scene_aa_begin": (_i, [_P(TraceBatch), _vp, _vp, _vp, _i, _i, _vp, _ll, _vp, _i, _vp]),
+        "oi_aa_resolve_strided": (_i, [_vp, _vp, _ll, _vp, _ll, _ll, _i, _i, _vp, _vp]),
+    },
 }
 
 

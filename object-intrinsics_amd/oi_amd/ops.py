@@ -1111,6 +1111,62 @@ def aa_resolve(centre, sub, edge_slot, n_edge, S, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------
+# adaptive anti-aliasing of a scene of many instances (include/oi_scene_aa.h); oi_amd.scene sequences these
+# ------------------------------------------------------------------------------------------
+
+def scene_aa_classify(owner, owner_ray, vis_slot, hit_points, grad, n_pad, S, plane_threshold=_l.AA_DEFAULT_PLANE,
+                      cos_threshold=_l.AA_DEFAULT_COS):
+    """The scene pixels of a traced scene that need more samples (oi_scene_aa_classify).  owner, owner_ray (S * S,) int32,
+    vis_slot (E, N) int32, hit_points and grad (E, n_pad, 3) (None with n_pad == 0).  -> edge_index (S * S,) int32 (its first
+    `count` entries are written: the flagged pixels, in no fixed order), edge_slot (S * S,) int32 (the pixel's position in
+    edge_index, or -1), count (1,) int32 on the device."""
+    M = int(S) * int(S)
+    E, N = vis_slot.shape
+    if owner.shape[0] != M or owner_ray.shape[0] != M:
+        raise ValueError(f"scene_aa_classify: owner {tuple(owner.shape)}, owner_ray {tuple(owner_ray.shape)} for {S} x {S} pixels")
+    edge_index = torch.empty(M, dtype=torch.int32, device=owner.device)   # (partly written by contract, as aa_classify's)
+    edge_slot = _new(owner, M).view(torch.int32)
+    count = _new(owner, 1).view(torch.int32)
+    _l.check(_l.load().oi_scene_aa_classify(_ip(owner), _ip(owner_ray), _ip(vis_slot), _p(hit_points) if n_pad else None,
+                                            _p(grad) if n_pad else None, int(E), int(N), int(n_pad), int(S), float(plane_threshold),
+                                            float(cos_threshold), _ip(edge_index), _ip(edge_slot), _ip(count), _stream()),
+             "oi_scene_aa_classify")
+    return edge_index, edge_slot, count
+
+
+def scene_aa_begin(st, c2b, kinv, window, W, S, edge_index, n_edge, offsets):
+    """The sub-pixel rays of the first n_edge pixels of edge_index in every instance's box frame, into the TraceBatchState st
+    of E elements x at least (Sa - 1) * n_edge rays (oi_scene_aa_begin).  c2b (E, 4, 4), kinv (3, 3), window (E, 2) int32, W, S:
+    scene_begin's; offsets (Sa, 2) float32 on the device, in units of the pixel pitch (row 0, the centre, is not read)."""
+    if offsets.dim() != 2 or offsets.shape[1] != 2 or offsets.dtype != torch.float32:
+        raise ValueError(f"scene_aa_begin: offsets {tuple(offsets.shape)} {offsets.dtype}, expected float32 (Sa, 2)")
+    if c2b.numel() != st.E * 16 or kinv.numel() != 9 or window.numel() != st.E * 2:
+        raise ValueError(f"scene_aa_begin: c2b, kinv and window must hold {st.E} x 16, 9 and {st.E} x 2 values")
+    keep = [_c(c2b), _c(kinv), _c(offsets)]
+    _l.check(_l.load().oi_scene_aa_begin(ctypes.byref(st.c), _p(keep[0]), _p(keep[1]), _ip(window), int(W), int(S), _ip(edge_index),
+                                         int(n_edge), _p(keep[2]), offsets.shape[0], _stream()), "oi_scene_aa_begin")
+
+
+def aa_resolve_strided(centre, sub, edge_slot, n_edge, S, out=None):
+    """aa_resolve with the sub-samples' planes at a stride of their own (oi_aa_resolve_strided): sub (P, stride), stride >=
+    (S - 1) * n_edge, of which the first (S - 1) * n_edge of every plane are read (None with n_edge == 0)."""
+    P, N = centre.shape
+    if n_edge and (sub is None or sub.dim() != 2 or sub.shape[0] != P or sub.shape[1] < (int(S) - 1) * int(n_edge)):
+        raise ValueError(f"aa_resolve_strided: sub {None if sub is None else tuple(sub.shape)}, expected ({P}, at least "
+                         f"{(int(S) - 1) * int(n_edge)})")
+    if edge_slot.shape[0] != N or edge_slot.dtype != torch.int32:
+        raise ValueError(f"aa_resolve_strided: edge_slot {tuple(edge_slot.shape)} {edge_slot.dtype}, expected int32 ({N},)")
+    if out is None:
+        out = _new(centre, P, N)
+    elif tuple(out.shape) != (P, N) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError(f"aa_resolve_strided: out must be a contiguous float32 {(P, N)} tensor")
+    stride = sub.shape[1] if n_edge else 0
+    _l.check(_l.load().oi_aa_resolve_strided(_p(centre), _p(sub) if n_edge else None, stride, _ip(edge_slot), N, int(n_edge), int(S),
+                                             P, _p(out), _stream()), "oi_aa_resolve_strided")
+    return out
+
+
 def scene_local_light_begin(sb, hit_points, grad, n_pad, offset, elem, pixel, position, normal, n_vis, w2b, bias, samples, j0, chunk,
                             lights, seed=0):
     """scene_occlusion_begin's chunk of rays aimed at local lights (L, 20) in the world frame: sb holds E occluder elements x

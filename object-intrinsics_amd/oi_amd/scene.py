@@ -12,6 +12,10 @@ and environment lighting (include/oi_scene_light.h).
                    and ambient occlusion (`ao_samples` rays over the hemisphere of each visible point), all of them tested
                    against every instance: contact shadows between objects
     render_scene   both
+                   aa_samples > 1 (trace_scene, render_scene): adaptive anti-aliasing -- the scene pixels at an outline, at a
+                   contour between two instances or at a geometric edge get sub-pixel rays in every instance, which pass the
+                   same march, resolve and shade, and the image is the mean of a pixel's samples (include/oi_scene_aa.h;
+                   DESIGN section 4.30)
     SceneSurface.capture_transfer  the secondary rays traced ONCE into a per-pixel SH transfer map of the whole scene ->
                    SceneTransfer, shaded under any number of environment lights (oi_amd.envlight.EnvLight); with bounces=1 the
                    rays that end on ANY instance carry one diffuse interreflection bounce (include/oi_scene_bounce.h; DESIGN
@@ -91,14 +95,26 @@ def scene_windows(gen, b2ws, window=None, what="trace_scene"):
     return W, origin
 
 
+def virtual_image_size(n_sub, E, what="trace_scene"):
+    """The side Q of the virtual scene image that holds n_sub sub-sample rays per instance (include/oi_scene_aa.h): the
+    smallest Q with Q * Q >= n_sub, so fewer than 2 Q + 1 of its pixels are padding.  Refused: E * Q * Q >= 2^31, or Q above the
+    scene entries' largest resolution."""
+    Q = math.isqrt(int(n_sub) - 1) + 1 if n_sub > 0 else 0
+    if E * Q * Q >= 1 << 31 or Q > _l.SCENE_MAX_RESOLUTION:
+        raise ValueError(f"{what}: {n_sub} sub-sample rays per instance need a virtual image of {Q} x {Q} pixels, {E} instances x "
+                         f"{Q} x {Q} = {E * Q * Q} rays (E * Q^2 < 2^31, Q <= {_l.SCENE_MAX_RESOLUTION}): fewer aa_samples, or "
+                         "aa_adaptive=True")
+    return Q
+
+
 class SceneSurface:
     """One traced scene and what the light-dependent stages reuse: the batched state (rays, t, status per instance), the
     owner map, the visible hits of every instance and the gradient and albedo there.
     E instances, window W, scene resolution S; window (E, 2) int32; n_entered / n_hit / n_vis: per instance the rays
     entered, the hits and the hits that own their pixel; n_pad = max(n_vis); state: ops.TraceBatchState."""
 
-    def __init__(self, gen, zs, b2ws, window, bias, trace_kw):
-        self.kw, self.bias = _t._Surface.params(bias, trace_kw, "trace_scene")
+    def __init__(self, gen, zs, b2ws, window, bias, trace_kw, aa=None):
+        kw, bias = _t._Surface.params(bias, trace_kw, "trace_scene")
         dev = gen.it.device
         zs = _t._latents(zs, dev)
         b2ws = (b2ws if torch.is_tensor(b2ws) else torch.stack([torch.as_tensor(b) for b in b2ws])).float().reshape(-1, 4, 4)
@@ -112,21 +128,35 @@ class SceneSurface:
         S = int(gen.scene_resolution)
         if not 1 <= S <= _l.SCENE_MAX_RESOLUTION:
             raise ValueError(f"trace_scene: scene_resolution={S} (1 .. {_l.SCENE_MAX_RESOLUTION})")
-        self.gen, self.E, self.W, self.S, self.N = gen, E, W, S, W * W
-        self.field = LatentField(gen, zs, None, "trace_scene", batch_ok=True)
+        field = LatentField(gen, zs, None, "trace_scene", batch_ok=True)
         gen.eval()
-        self.field.prepare(zs, None)
+        field.prepare(zs, None)
         prior = gen.sample_prior(E, {"b2w": b2ws.to(dev)})
-        self.b2w, self.w2b = prior["b2w"].contiguous(), prior["w2b"].contiguous()
-        self.window = torch.from_numpy(origin.astype(np.int32)).to(dev)
-        st = self.state = ops.trace_batch_state_empty(E, self.N, self.b2w)
-        ops.scene_begin(st, prior["c2b"].contiguous(), gen._kinv(dev), self.window, W, S)
+        b2w = prior["b2w"].contiguous()
+        win = torch.from_numpy(origin.astype(np.int32)).to(dev)
+        st = ops.trace_batch_state_empty(E, W * W, b2w)
+        c2b, kinv = prior["c2b"].contiguous(), gen._kinv(dev)
+        ops.scene_begin(st, c2b, kinv, win, W, S)
+        self._set(gen, field, kw, bias, b2w, prior["w2b"].contiguous(), win, W, S, st)
+        if aa is not None:
+            self._antialias(aa, c2b, kinv)
+
+    def _set(self, gen, field, kw, bias, b2w, w2b, window, W, S, st):
+        """Everything behind the begin entry, on a batch st of E elements x W * W rays that oi_scene_begin or
+        oi_scene_aa_begin has filled: the march, the finish, the depth resolve, the visible lists, the gather, the full MLP
+        pass at the visible hits and their prefix offsets.  What the primary surface and the sub-sample surface share."""
+        E, dev = st.E, b2w.device
+        self.gen, self.field, self.kw, self.bias = gen, field, kw, bias
+        self.E, self.W, self.S, self.N = E, W, S, W * W
+        self.b2w, self.w2b, self.window, self.state = b2w, w2b, window, st
         self.n_evals = self.n_steps = self.shadow_evals = self.occlusion_evals = self.transfer_evals = self.n_pad = 0
         self.n_hit = self.n_vis = [0] * E
         self.owner = self.owner_ray = self.vis_slot = self.offset = self.points = self.grad = self.rgb = None
         self._world = self._pixel = self.vis_index = self.shadow = self.ao = self.transfer_state = None
         self.glossy_evals, self.glossy_state, self._reflect = 0, None, None
         self.bounce_points, self.bounce_hits = 0, None
+        self.aa = self.sub = self.edge_slot = None   # the anti-aliasing stage (_antialias), when there is one
+        self.n_edge = 0
         bound = int(st.live[0].item())
         self.n_entered = st.counts[:, 0].tolist()
         if bound == 0:      # nothing enters a window: every ray is a MISS already
@@ -146,6 +176,48 @@ class SceneSurface:
         _, grad, rgb = self.field.full(self.points.view(E * self.n_pad, 3))
         self.grad, self.rgb = grad.view(E, self.n_pad, 3), rgb.view(E, self.n_pad, 3)
         self.offset = torch.tensor(np.concatenate([[0], np.cumsum(self.n_vis)[:-1]]), dtype=torch.int32, device=dev)
+
+    @classmethod
+    def from_batch(cls, parent, st, Q):
+        """The SceneSurface of a begun batch st of parent.E elements x Q * Q rays whose layout is a VIRTUAL scene image of Q x
+        Q pixels (include/oi_scene_aa.h): every window is the whole image, local ray q of every element is virtual pixel q.
+        Field, trace parameters, bias and poses are the parent's."""
+        self = cls.__new__(cls)
+        window = torch.zeros(parent.E, 2, dtype=torch.int32, device=parent.b2w.device)
+        self._set(parent.gen, parent.field, parent.kw, parent.bias, parent.b2w, parent.w2b, window, Q, Q, st)
+        return self
+
+    def _antialias(self, aa, c2b, kinv):
+        """The anti-aliasing stage (include/oi_scene_aa.h): the flagged scene pixels (adaptive:
+        oi_scene_aa_classify and ONE read-back of their number; otherwise every scene pixel), per instance their aa.S - 1
+        sub-pixel rays each (oi_scene_aa_begin), and everything _set does, on those rays.  self.sub: the sub-samples as one more
+        SceneSurface over a virtual image of Q x Q pixels -- virtual pixel (j - 1) * n_edge + e is sample j of the e-th
+        flagged pixel in ascending order -- which the light-dependent stages treat as they treat this one; None without a
+        flagged pixel or without a primary hit."""
+        M, dev = self.S * self.S, self.b2w.device
+        self.aa = aa
+        self.edge_slot = torch.full((M,), -1, dtype=torch.int32, device=dev)
+        if self.n_pad == 0:
+            return
+        if aa.adaptive:
+            edge_index, edge_slot, count = ops.scene_aa_classify(self.owner, self.owner_ray, self.vis_slot, self.points, self.grad,
+                                                                 self.n_pad, self.S, aa.plane, aa.cos)
+            n_edge = int(count.item())
+            if n_edge:
+                # The compaction's order differs from run to run, and the virtual pixel keys the shadow and occlusion samples:
+                # the flagged pixels in ascending order make the frame a function of its arguments alone.
+                edge_index[:n_edge] = torch.sort(edge_index[:n_edge]).values
+                edge_slot[edge_index[:n_edge].long()] = torch.arange(n_edge, dtype=torch.int32, device=dev)
+        else:
+            edge_index = edge_slot = torch.arange(M, dtype=torch.int32, device=dev)
+            n_edge = M
+        self.edge_slot, self.n_edge = edge_slot, n_edge
+        if n_edge == 0:
+            return
+        Q = virtual_image_size((aa.S - 1) * n_edge, self.E, "trace_scene")
+        st = ops.trace_batch_state_empty(self.E, Q * Q, self.b2w)
+        ops.scene_aa_begin(st, c2b, kinv, self.window, self.W, self.S, edge_index, n_edge, torch.from_numpy(aa.offsets).to(dev))
+        self.sub = SceneSurface.from_batch(self, st, Q)
 
     def world_points(self):
         """position, normal (n_vis, 3) in the world frame and elem (n_vis,) int32 of the visible points of all instances, point
@@ -365,6 +437,10 @@ class SceneSurface:
         instance on itself -- into a per-channel transfer, SceneTransfer.bounce (include/oi_scene_bounce.h has the estimator and
         its approximations); the direct transfer is bit for bit that of bounces = 0, which launches what it always did.
         -> SceneTransfer."""
+        aa = getattr(self, "aa", None)
+        if aa is not None:
+            raise ValueError(f"SceneSurface.capture_transfer: the scene was traced with aa_samples={aa.S}; the environment "
+                             "paths have no anti-aliasing stage (trace the scene with aa_samples=1)")
         samples, seed = _t._check_transfer(transfer_samples, seed, "SceneSurface.capture_transfer")
         bounces = _t._check_bounces(bounces, samples, glossy_samples, shininess, "SceneSurface.capture_transfer")
         g_samples, shin, spec = _t._check_glossy(getattr(self, "gen", None), glossy_samples, shininess, "SceneSurface.capture_transfer")
@@ -415,27 +491,62 @@ class SceneSurface:
         units), tested against every instance; the share that escapes multiplies the ambient term and is returned as
         ambient_occlusion (1, 1, S, S).  The samples are a function of scene pixel, sample number and `seed` alone; traces
         above max_shadow_rays are split into chunks of samples, which changes no byte.  At the defaults the launches and the
-        bytes are those of a call without these arguments."""
+        bytes are those of a call without these arguments.
+        On a scene traced with aa_samples > 1 (trace_scene) the sub-sample surface passes the same stages
+        with the same arguments and `image` is the mean over each flagged pixel's samples, off-surface samples carrying bg; new
+        keys coverage (1, 1, S, S), the mean of the mask over a pixel's samples, and aa_mask (1, 1, S, S), the flagged pixels;
+        every other map stays the centre sample's."""
         dev = self.b2w.device
         lt = _t._stack_lights(self.gen, lights, dev, "SceneSurface.shade", "; inference.scene_light_walk splits larger sets")
         local = _t._is_local(lt)
         radii = _t._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0],
                                     "SceneSurface.shade", local)
-        if local:
-            vis = self.local_visibility(lt, int(shadow_samples), int(seed), max_shadow_rays) if shadows else None
-        else:
-            vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays) if shadows else None
-        ao = self.ambient(int(ao_samples), float(ao_distance), int(seed), max_shadow_rays) if ao_samples else None
+        vis, ao = self._occlusion(lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays)
         out = self._shade(lt, _t._bg(bg, dev), vis, ("depth", "position", "normal_world", "albedo", "mask", "instance", "image"), ao=ao)
         S = self.S
         res = {_MAP_NAMES[k]: v for k, v in _t._maps({k: v for k, v in out.items() if k != "image"}, S, S).items()}
         res["image"] = out["image"].view(-1, 3, S, S)
+        if self.aa is not None:   # the sub-samples through the same stages, then the mean over each flagged pixel's samples
+            vis_sub = ao_sub = None
+            if self.sub is not None:
+                vis_sub, ao_sub = self.sub._occlusion(lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays)
+            image, coverage = self.resolved(lt, _t._bg(bg, dev), out, vis_sub, ao_sub, want_mask=True)
+            res["image"], res["coverage"] = image.view(-1, 3, S, S), coverage.view(1, 1, S, S)
+            res["aa_mask"] = (self.edge_slot >= 0).float().view(1, 1, S, S)
         if shadows:
             res["visibility"] = vis.view(-1, 1, S, S)
         if ao_samples:
             res["ambient_occlusion"] = ao.view(1, 1, S, S)
         res["stats"] = self.stats()
         return res
+
+    def _occlusion(self, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays):
+        """shade's secondary rays on this surface: -> (visibility (L, S * S) or None, ambient occlusion (S * S,) or None)."""
+        vis = None
+        if shadows and _t._is_local(lt):
+            vis = self.local_visibility(lt, int(shadow_samples), int(seed), max_shadow_rays)
+        elif shadows:
+            vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays)
+        ao = self.ambient(int(ao_samples), float(ao_distance), int(seed), max_shadow_rays) if ao_samples else None
+        return vis, ao
+
+    def resolved(self, lt, bgv, centre, vis_sub, ao_sub, image_out=None, want_mask=False):
+        """The anti-aliased image of a scene traced with an anti-aliasing stage: the sub-sample surface shaded as the centres
+        were (under lt, with its own visibility and occlusion; off-surface samples carry bg) and oi_aa_resolve_strided over
+        centre["image"] (L, 3, S * S), the sub-samples' planes Q * Q apart.  -> image (L, 3, S * S) (written into image_out when
+        given), coverage (S * S,) or None (want_mask: the same mean over centre["mask"]).  Without a sub-sample surface the
+        resolve is a copy."""
+        L, M, sub = lt.shape[0], self.S * self.S, None
+        if self.sub is not None:
+            sub = self.sub._shade(lt, bgv, vis_sub, ("mask", "image") if want_mask else ("image",), ao=ao_sub)
+        image = ops.aa_resolve_strided(centre["image"].view(3 * L, M), None if sub is None else sub["image"].view(3 * L, -1),
+                                       self.edge_slot, self.n_edge, self.aa.S,
+                                       out=None if image_out is None else image_out.view(3 * L, M)).view(L, 3, M)
+        coverage = None
+        if want_mask:
+            coverage = ops.aa_resolve_strided(centre["mask"].view(1, M), None if sub is None else sub["mask"].view(1, -1),
+                                              self.edge_slot, self.n_edge, self.aa.S).view(M)
+        return image, coverage
 
     def stats(self):
         """Per instance: rays entered and culled, rays per status (culled rays are misses), hits, visible hits; sdf
@@ -450,6 +561,10 @@ class SceneSurface:
                      visible=int(self.n_vis[e]), n_evals=self.n_evals, n_steps=self.n_steps, shadow_evals=self.shadow_evals,
                      occlusion_evals=self.occlusion_evals, transfer_evals=self.transfer_evals, glossy_evals=self.glossy_evals,
                      bounce_points=self.bounce_points)
+            if self.aa is not None:   # aa_evals: every sdf evaluation the sub-samples cost (their march, shadow and occlusion rays)
+                sub = self.sub
+                s.update(aa_pixels=self.n_edge, aa_rays=(self.aa.S - 1) * self.n_edge,
+                         aa_evals=0 if sub is None else sub.n_evals + sub.shadow_evals + sub.occlusion_evals)
             out.append(s)
         return out
 
@@ -550,29 +665,40 @@ class SceneTransfer:
 
 
 @torch.no_grad()
-def trace_scene(gen, zs, b2ws, window=None, bias=DEFAULT_BIAS, **trace_kw):
+def trace_scene(gen, zs, b2ws, window=None, bias=DEFAULT_BIAS, aa_samples=1, aa_adaptive=True, aa_plane=_l.AA_DEFAULT_PLANE,
+                aa_cos=_l.AA_DEFAULT_COS, aa_pattern=None, **trace_kw):
     """The scene of K instances of `gen` (latents zs: K of (z_dim,) or (K, z_dim); rigid poses b2ws: K of (4, 4), as
     sample_prior takes them), 1 <= K <= 1024, in the S x S scene image of the generator's camera (S = gen.scene_resolution),
     traced once: -> SceneSurface.  window: the side W of every instance's window in scene pixels (default: the smallest that
     holds every unit sphere's projection; scene_windows); K * W^2 < 2^31.  trace_kw: tol, omega, max_steps, readback of
     sphere_trace.  Refused with ValueError, naming the instance: a camera inside or within 1 of an instance's unit sphere, an
-    instance behind the camera."""
-    return SceneSurface(gen, zs, b2ws, window, bias, trace_kw)
+    instance behind the camera.
+    Anti-aliasing (include/oi_scene_aa.h): aa_samples = Sa in 2 .. 64 takes Sa samples inside each FLAGGED
+    scene pixel -- the centre and Sa - 1 sub-pixel rays per instance at aa_pattern (Sa, 2), oi_amd.trace.render_surface's
+    keywords with its default pattern.  A pixel is flagged when a neighbour differs in the mask or belongs to another
+    instance, or -- same instance -- lies off its tangent plane by more than asin(aa_plane) or has a normal more than
+    acos(aa_cos) away; aa_adaptive=False flags every scene pixel.  The sub-samples are SceneSurface.sub, one more SceneSurface
+    over a virtual image of Q x Q pixels, Q = ceil(sqrt((Sa - 1) * flagged pixels)); K * Q^2 >= 2^31 is refused.  With
+    aa_samples == 1 nothing of this runs."""
+    aa = _t._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "trace_scene")
+    return SceneSurface(gen, zs, b2ws, window, bias, trace_kw, aa=aa)
 
 
 @torch.no_grad()
 def render_scene(gen, zs, b2ws, lights=None, shadows=False, bg=None, window=None, bias=DEFAULT_BIAS,
                  max_shadow_rays=MAX_SHADOW_RAYS, shadow_samples=1, light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0,
+                 aa_samples=1, aa_adaptive=True, aa_plane=_l.AA_DEFAULT_PLANE, aa_cos=_l.AA_DEFAULT_COS, aa_pattern=None,
                  **trace_kw):
     """trace_scene + SceneSurface.shade: K instances in one scene image, nearer instances hiding farther ones and, with
     `shadows`, every instance throwing its shadow on itself and on the others; shadow_samples, light_radius, ao_samples,
-    ao_distance, seed: shade's soft shadows and ambient occlusion between the instances.  -> SceneSurface.shade's dict, with
-    "scene" (the SceneSurface)."""
+    ao_distance, seed: shade's soft shadows and ambient occlusion between the instances; aa_samples, aa_adaptive, aa_plane,
+    aa_cos, aa_pattern: trace_scene's anti-aliasing.  -> SceneSurface.shade's dict, with "scene" (the SceneSurface)."""
     rad = light_radius.detach().cpu() if torch.is_tensor(light_radius) else light_radius
     # (before the trace; shade checks a radius per light against the lights it stacks)
     _t._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, np.size(rad) if np.ndim(rad) == 1 else 1,
                         "render_scene", local_lights_given(lights))
-    s = trace_scene(gen, zs, b2ws, window, bias, **trace_kw)
+    _t._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "render_scene")
+    s = trace_scene(gen, zs, b2ws, window, bias, aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, **trace_kw)
     res = s.shade(lights, shadows, bg, max_shadow_rays, shadow_samples, light_radius, ao_samples, ao_distance, seed)
     res["scene"] = s
     return res
@@ -591,7 +717,7 @@ def render_scene_env(gen, zs, b2ws, envs, transfer_samples=64, seed=0, bg=None, 
     samples, _ = _t._check_transfer(transfer_samples, seed, "render_scene_env")
     _t._check_bounces(bounces, samples, glossy_samples, shininess, "render_scene_env")
     _t._check_glossy(gen, glossy_samples, shininess, "render_scene_env")
-    s = trace_scene(gen, zs, b2ws, window, bias, **trace_kw)
+    s = SceneSurface(gen, zs, b2ws, window, bias, trace_kw)   # (not trace_scene: the environment paths take no aa_* keyword)
     cap = s.capture_transfer(transfer_samples, seed, max_shadow_rays, glossy_samples, shininess, bounces)
     res = cap.shade(envs, bg, specular)
     res.update(transfer=cap.transfer, scene=s, capture=cap)

@@ -36,7 +36,13 @@ of the same run:
 With --local [--light-size R] each row also gets scene_local_ms / scene_local_hard_ms /
 scene_local_sphere16_ms: render_scene under a local light 3 units from the instances' centroid along the trained light's
 direction (no shadows, one hard ray, 16 samples of a sphere of radius R), scene_directional_soft16_ms beside them, and the
-sdf evaluations of each shadow trace."""
+sdf evaluations of each shadow trace.
+
+With --aa S [--aa-full] the tool measures ONLY, per K and in one session, the frame of render_scene under
+the trained light with one sample per pixel (aa_samples=1: the path without the stage), with S samples in the flagged scene
+pixels (adaptive), and -- with --aa-full -- with S samples in every scene pixel (aa_adaptive=False); with each the flagged
+pixels, the sub-sample rays per instance, the side Q of their virtual image, their sdf evaluations and the steps of the
+second chain."""
 import argparse
 import copy
 import json
@@ -71,6 +77,8 @@ ap.add_argument("--bounce", action="store_true", help="with --env: also time the
 ap.add_argument("--skip-crops", action="store_true", help="leave out the crops_* comparison rows")
 ap.add_argument("--local", action="store_true", help="also time a local light (oi_amd.relight.LocalLight) above the scene: scene_local_*_ms")
 ap.add_argument("--light-size", type=float, default=0.15, help="with --local: radius of the sphere light of the sampled row")
+ap.add_argument("--aa", type=int, default=0, help="samples per flagged scene pixel: time anti-aliased frames beside the one-sample frame, only")
+ap.add_argument("--aa-full", action="store_true", help="with --aa: also time aa_adaptive=False (every scene pixel flagged)")
 args = ap.parse_args()
 
 
@@ -91,6 +99,40 @@ def median_ms(fn):
 
 gen, _ = build_models(args.res, 256, 64, 1, args.precision, "cuda")
 gen.eval()
+
+
+def aa_rows():
+    """Per K: the one-sample frame, the adaptive frame and (--aa-full) the fully supersampled frame."""
+    rows = {}
+    for K in (int(k) for k in args.instances.split(",")):
+        zs, b2ws = scene.sample_scene(gen, K, args.seed)
+        cases = {"one_sample": dict(aa_samples=1), "adaptive": dict(aa_samples=args.aa)}
+        if args.aa_full:
+            cases["full"] = dict(aa_samples=args.aa, aa_adaptive=False)
+        row = {}
+        for name, kw in cases.items():
+            frame = lambda: scene.render_scene(gen, zs, b2ws, **kw)
+            row[name + "_ms"] = median_ms(frame)
+            res = frame()
+            s, st = res["scene"], res["stats"][0]
+            if name == "one_sample":
+                row.update(window=s.W, rays=K * s.N, visible=sum(s.n_vis), n_evals=st["n_evals"], n_steps=st["n_steps"])
+            else:
+                sub = s.sub
+                row[name] = {"aa_pixels": st["aa_pixels"], "aa_share": st["aa_pixels"] / (s.S * s.S), "aa_rays": st["aa_rays"],
+                             "Q": 0 if sub is None else sub.S, "aa_visible": 0 if sub is None else sum(sub.n_vis),
+                             "aa_evals": st["aa_evals"], "aa_steps": 0 if sub is None else sub.n_steps,
+                             "ms_over_one_sample": row[name + "_ms"] / row["one_sample_ms"]}
+        rows[str(K)] = row
+    return rows
+
+
+if args.aa:
+    with torch.no_grad():
+        print(json.dumps({"tool": "bench_scene", "precision": args.precision, "res": args.res, "scene_resolution": gen.scene_resolution,
+                          "iters": args.iters, "warmup": args.warmup, "aa_samples": args.aa, "aa": aa_rows()}))
+    sys.exit(0)
+
 out = {"tool": "bench_scene", "precision": args.precision, "res": args.res, "scene_resolution": gen.scene_resolution,
        "iters": args.iters, "warmup": args.warmup, "shadow_samples": args.shadow_samples, "light_radius": args.light_radius,
        "ao_samples": args.ao_samples, "transfer_samples": args.transfer_samples if args.env else None,

@@ -527,6 +527,33 @@ __device__ __forceinline__ AimedSample aimed_sample(const float* o, const float*
   return a;
 }
 
+// Local light lt seen from the point pos in the box frame Wb (include/oi_local_light.h's shading): -> att spot, and the unit
+// direction l = u / max(|u|, 1e-6) towards the light (the view vector's clamped quotient).  local_shade_at's and the ground
+// plane's (ground.hip, with the identity for Wb: the world frame).
+__device__ __forceinline__ float local_light_factor(const float* __restrict__ lt, const float* __restrict__ Wb, const float* pos,
+                                                    float& lx, float& ly, float& lz) {
+  float lq[3], R;
+  local_light_position(lt, Wb, lq, R);
+  const float ux = lq[0] - pos[0], uy = lq[1] - pos[1], uz = lq[2] - pos[2];
+  const float dist2 = ux * ux + uy * uy + uz * uz;
+  unit_view(lq[0], lq[1], lq[2], pos[0], pos[1], pos[2], lx, ly, lz);
+  const float rmin = fmaxf(R, OI_LOCAL_LIGHT_MIN_DISTANCE);
+  float k = lt[7] * lt[7] / fmaxf(dist2, rmin * rmin);
+  float spot = 1.0f;
+  if (lt[11] > -1.0f) {
+    const float a0 = lt[16], a1 = lt[17], a2 = lt[18];
+    const float an = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
+    const float cx = Wb[0] * (a0 / an) + Wb[1] * (a1 / an) + Wb[2] * (a2 / an);
+    const float cy = Wb[4] * (a0 / an) + Wb[5] * (a1 / an) + Wb[6] * (a2 / an);
+    const float cz = Wb[8] * (a0 / an) + Wb[9] * (a1 / an) + Wb[10] * (a2 / an);
+    const float c = -(lx * cx + ly * cy + lz * cz);
+    const float tt = fminf(fmaxf((c - lt[11]) / (lt[19] - lt[11]), 0.f), 1.0f);
+    spot = tt * tt * (3.0f - 2.0f * tt);
+  }
+  k *= spot;
+  return k;
+}
+
 // One pixel of the Phong image under local lights (include/oi_local_light.h's shading), surface_shade_at's arguments with
 // p.lights pointing at local records.  The G-buffer is not written here: the caller runs surface_shade_at without an image
 // for it, so those outputs are oi_surface_shade's bytes.
@@ -554,26 +581,8 @@ __device__ __forceinline__ void local_shade_at(const P& p, const float* __restri
       continue;
     }
     const float* lt = p.lights + (long long)l * OI_LOCAL_LIGHT_FLOATS;
-    float lq[3], R;
-    local_light_position(lt, Wb, lq, R);
-    const float ux = lq[0] - pos[0], uy = lq[1] - pos[1], uz = lq[2] - pos[2];
-    const float dist2 = ux * ux + uy * uy + uz * uz;
-    float lx, ly, lz;  // l = u / max(|u|, 1e-6): the view vector's clamped quotient, towards the light
-    unit_view(lq[0], lq[1], lq[2], pos[0], pos[1], pos[2], lx, ly, lz);
-    const float rmin = fmaxf(R, OI_LOCAL_LIGHT_MIN_DISTANCE);
-    float k = lt[7] * lt[7] / fmaxf(dist2, rmin * rmin);
-    float spot = 1.0f;
-    if (lt[11] > -1.0f) {
-      const float a0 = lt[16], a1 = lt[17], a2 = lt[18];
-      const float an = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
-      const float cx = Wb[0] * (a0 / an) + Wb[1] * (a1 / an) + Wb[2] * (a2 / an);
-      const float cy = Wb[4] * (a0 / an) + Wb[5] * (a1 / an) + Wb[6] * (a2 / an);
-      const float cz = Wb[8] * (a0 / an) + Wb[9] * (a1 / an) + Wb[10] * (a2 / an);
-      const float c = -(lx * cx + ly * cy + lz * cz);
-      const float tt = fminf(fmaxf((c - lt[11]) / (lt[19] - lt[11]), 0.f), 1.0f);
-      spot = tt * tt * (3.0f - 2.0f * tt);
-    }
-    k *= spot;
+    float lx, ly, lz;
+    float k = local_light_factor(lt, Wb, pos, lx, ly, lz);
     if (p.visibility != nullptr) k *= p.visibility[(long long)l * M + q];
     const PhongGeometry ph = phong_geometry(n[0], n[1], n[2], lx, ly, lz, vx, vy, vz);
     const float rl = fmaxf(ph.ndl, 0.f) * k;

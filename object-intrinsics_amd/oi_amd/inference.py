@@ -293,23 +293,31 @@ def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True,
     return _walk_result(s, *_walk_frames(s, lt, step, shadows, visibility, bg, ao, ao_sub), ao)
 
 
-def _scene_walk(s, lt, shadows, per_light, visibility, bg, ao_samples, ao_distance, seed, limit, **extra):
+def _scene_walk(s, lt, shadows, per_light, visibility, bg, ao_samples, ao_distance, seed, limit, ground=None,
+                ground_visibility=None, **extra):
     """The frames of a light walk or orbit over the traced scene s (a scene.SceneSurface) under the stacked lights lt, and the
     dict scene_light_walk and scene_light_orbit return.  The lights are split so that one shadow batch of visibility(surface,
     a, b) -> (b - a, S * S) holds at most `limit` rays, counted as per_light rays per light and visible point, and at most 256
     lights; one shade launch per chunk.  With an anti-aliasing stage the sub-sample surface s.sub, traced once with the scene,
     passes the same two per chunk, the chunks sized by the larger visible count of the two surfaces, and
-    oi_aa_resolve_strided writes the frames; ambient occlusion is traced once for each surface."""
+    oi_aa_resolve_strided writes the frames; ambient occlusion is traced once for each surface.
+    ground (a scene.Ground): the plane's ambient occlusion is traced once, its shadows per chunk of lights by
+    ground_visibility(ground surface, a, b) -> (b - a, n_g), and oi_ground_shade writes it into each chunk's frames; the chunks
+    are sized by the larger of the visible points and the ground points."""
     from . import lib, trace
     n, dev = lt.shape[0], lt.device
     S, M = s.S, s.S * s.S
+    gs = None if ground is None else s.ground(ground)
     image = torch.empty(n, 3, M, device=dev)
     vis_all = torch.empty(n, M, device=dev) if shadows else None
     step = lib.RELIGHT_MAX_LIGHTS
     if shadows:   # (one light above the limit is traced in chunks of samples; one sample above it is refused, naming the count)
-        n_vis = max(sum(s.n_vis), sum(s.sub.n_vis) if s.sub is not None else 0)
+        n_vis = max(sum(s.n_vis), sum(s.sub.n_vis) if s.sub is not None else 0, gs.n_g if gs is not None else 0)
         step = max(1, min(step, limit // max(1, s.E * n_vis * per_light)))
-    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples else None
+    gkw = {} if gs is None else {"ground": gs}
+    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed), limit, **gkw) if ao_samples else None
+    g_ao = gs.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples and gs is not None else None
+    matte = torch.empty(n, 3, M, device=dev) if gs is not None else None
     ao_sub = s.sub.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples and s.sub is not None else None
     maps = coverage = None
     for a in range(0, n, step):
@@ -321,6 +329,9 @@ def _scene_walk(s, lt, shadows, per_light, visibility, bg, ao_samples, ao_distan
         out = s._shade(lt[a:b], trace._bg(bg, dev), vis, ("depth", "mask", "instance", "image") if first else ("image",),
                        image[a:b] if s.aa is None else None, ao)
         maps = maps or out
+        if gs is not None:   # (no anti-aliasing stage with a ground: `out` holds views of the walk's frames)
+            g_vis = ground_visibility(gs, a, b) if shadows else None
+            ground_mask, matte[a:b] = gs.shade(out, lt[a:b], g_vis, g_ao)
         if s.aa is not None:
             vis_sub = visibility(s.sub, a, b) if shadows and s.sub is not None else None
             _, cov = s.resolved(lt[a:b], trace._bg(bg, dev), {"image": out["image"], "mask": maps["mask"]}, vis_sub, ao_sub,
@@ -334,13 +345,17 @@ def _scene_walk(s, lt, shadows, per_light, visibility, bg, ao_samples, ao_distan
         res["ambient_occlusion"] = ao.view(1, 1, S, S)
     if s.aa is not None:
         res["coverage"], res["aa_mask"] = coverage.view(1, 1, S, S), (s.edge_slot >= 0).float().view(1, 1, S, S)
+    if gs is not None:
+        res["ground_mask"], res["shadow_matte"] = ground_mask.view(1, 1, S, S), matte.view(n, 3, S, S)
+        for st in res["stats"]:
+            st.update(ground_pixels=gs.n_g, ground_evals=gs.evals)
     return res
 
 
 @torch.no_grad()
 def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True, bg=None, bias=None, window=None,
                      max_shadow_rays=None, shadow_samples=1, light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0, aa_samples=1,
-                     aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, **kw):
+                     aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, ground=None, **kw):
     """surface_light_walk on a scene of K instances (oi_amd.scene): the scene is traced ONCE -- one batched
     march, one depth resolve, one full MLP pass at the visible hits -- and shaded under the walk of lights, each instance
     shadowing itself and the others.  Frame 0 is the trained light.  The lights are split so that one shadow batch holds at
@@ -353,10 +368,14 @@ def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True,
     "ambient_occlusion" (1, 1, S, S).  kw: tol, omega, max_steps, readback of sphere_trace.
     aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern: trace_scene's anti-aliasing.  The sub-samples
     are traced ONCE for the walk, then shaded and resolved per chunk of lights; "coverage" and "aa_mask" (1, 1, S, S) are
-    returned too, and stats gains aa_pixels, aa_rays, aa_evals."""
+    returned too, and stats gains aa_pixels, aa_rays, aa_evals.
+    ground (a scene.Ground; not with aa_samples > 1): SceneSurface.shade's ground plane in every frame.  Its
+    ambient occlusion is traced ONCE, its shadows per chunk of lights; "ground_mask" (1, 1, S, S) and "shadow_matte" (n_frames,
+    3, S, S) are returned too, and stats gains ground_pixels and ground_evals."""
     from . import scene, trace
     from .relight import Light, stack_lights
-    trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "scene_light_walk")
+    aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "scene_light_walk")
+    scene.check_ground_keyword(ground, aa, "scene_light_walk")
     base = Light.from_module(gen.light)
     dirs = light_walk_directions(base.direction, n_frames, axis)
     dev = gen.it.device
@@ -368,11 +387,16 @@ def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True,
     s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, aa_samples, aa_adaptive, aa_plane,
                           aa_cos, aa_pattern, **kw)
 
+    gkw = {} if ground is None else {"ground": ground}
+
     def visibility(surface, a, b):
-        return surface.visibility(lt[a:b], None if radii is None else radii[a:b], int(shadow_samples), int(seed), limit)
+        return surface.visibility(lt[a:b], None if radii is None else radii[a:b], int(shadow_samples), int(seed), limit, **gkw)
+
+    def ground_visibility(gs, a, b):
+        return gs.visibility(lt[a:b], None if radii is None else radii[a:b], int(shadow_samples), int(seed), limit)
     # (one light above the limit: SceneSurface.visibility refuses it, naming the count)
     return _scene_walk(s, lt, shadows, int(shadow_samples) if radii is not None else 1, visibility, bg, ao_samples, ao_distance, seed,
-                       limit)
+                       limit, **({} if ground is None else {"ground": ground, "ground_visibility": ground_visibility}))
 
 
 def light_orbit_positions(centre, radius, n_frames, axis=(0.0, -1.0, 0.0), height=0.0):
@@ -439,7 +463,8 @@ def surface_light_orbit(gen, z, b2w, light, n_frames=128, centre=(0.0, 0.0, 0.0)
 @torch.no_grad()
 def scene_light_orbit(gen, zs, b2ws, light, n_frames=128, centre=(0.0, 0.0, 0.0), radius=1.5, axis=(0, -1, 0), height=0.0,
                       shadows=True, bg=None, bias=None, window=None, max_shadow_rays=None, shadow_samples=1, ao_samples=0,
-                      ao_distance=0.5, seed=0, aa_samples=1, aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, **kw):
+                      ao_distance=0.5, seed=0, aa_samples=1, aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, ground=None,
+                      **kw):
     """surface_light_orbit on a scene of K instances (oi_amd.scene): the scene is traced ONCE and the local light is carried
     round `centre` -- between the instances, if the circle passes there -- each instance shadowing itself and the others as
     far as the light.  The lights are split so that one shadow batch holds at most max_shadow_rays rays (default
@@ -447,10 +472,12 @@ def scene_light_orbit(gen, zs, b2ws, light, n_frames=128, centre=(0.0, 0.0, 0.0)
     whose samples do not fit one batch is traced in chunks of samples.  The frames do not depend on the split.  -> {"image":
     (n_frames, 3, S, S), "visibility": (n_frames, 1, S, S) when shadows, "mask" / "depth" / "instance" (1, 1, S, S),
     "positions", "stats"}; with ao_samples also "ambient_occlusion" (1, 1, S, S).
-    aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern: as scene_light_walk's."""
+    aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, ground: as scene_light_walk's (the ground catches the local light's
+    shadows and blocks the instances' ambient rays; it does not block their local-light rays)."""
     from . import scene, trace
     from .relight import stack_local_lights
-    trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "scene_light_orbit")
+    aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "scene_light_orbit")
+    scene.check_ground_keyword(ground, aa, "scene_light_orbit")
     pos, lights = _orbit_lights(light, n_frames, centre, radius, axis, height, "scene_light_orbit")
     dev = gen.it.device
     lt = stack_local_lights(lights, dev)
@@ -463,7 +490,11 @@ def scene_light_orbit(gen, zs, b2ws, light, n_frames=128, centre=(0.0, 0.0, 0.0)
 
     def visibility(surface, a, b):
         return surface.local_visibility(lt[a:b], int(shadow_samples), int(seed), limit)
-    return _scene_walk(s, lt, shadows, int(shadow_samples), visibility, bg, ao_samples, ao_distance, seed, limit, positions=pos)
+
+    def ground_visibility(gs, a, b):
+        return gs.local_visibility(lt[a:b], int(shadow_samples), int(seed), limit)
+    return _scene_walk(s, lt, shadows, int(shadow_samples), visibility, bg, ao_samples, ao_distance, seed, limit, positions=pos,
+                       **({} if ground is None else {"ground": ground, "ground_visibility": ground_visibility}))
 
 
 def env_walk_rotations(n_frames, axis=(0.0, 0.0, 1.0)):
@@ -508,7 +539,7 @@ def env_walk(gen, z, b2w, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64
 
 @torch.no_grad()
 def scene_env_walk(gen, zs, b2ws, env, n_frames=128, axis=(0, 0, 1), transfer_samples=64, seed=0, bg=None, bias=None, window=None,
-                   max_shadow_rays=None, glossy_samples=None, shininess=None, specular=None, bounces=0, **kw):
+                   max_shadow_rays=None, glossy_samples=None, shininess=None, specular=None, bounces=0, ground=None, **kw):
     """env_walk on a scene of K instances (oi_amd.scene): ONE scene trace and ONE capture
     (SceneSurface.capture_transfer: transfer_samples secondary rays per visible point, each tested against every instance),
     then n_frames rotations of the 9 x 3 coefficients on the host and one shade launch per 256 frames.  Frame 0 is `env`
@@ -517,7 +548,10 @@ def scene_env_walk(gen, zs, b2ws, env, n_frames=128, axis=(0, 0, 1), transfer_sa
     shade's): the map is prefiltered once, when it is made, and every frame only rotates the lookup; the result also holds
     "specular" (n_frames, 3, S, S), "spec_visibility" and "reflection".  bounces=1 (an EnvLight; capture_transfer's rules): one
     diffuse interreflection bounce between the instances, traced once with the capture; the result also
-    holds "indirect" (n_frames, 3, S, S) and "bounce" (1, 3, 9, S, S).  kw: tol, omega, max_steps, readback of sphere_trace."""
+    holds "indirect" (n_frames, 3, S, S) and "bounce" (1, 3, 9, S, S).  kw: tol, omega, max_steps, readback of sphere_trace.
+    ground: refused unless None (the environment paths have no ground plane yet)."""
+    from .scene import refuse_env_ground
+    refuse_env_ground(ground, "scene_env_walk")
     from . import scene, trace
     from .envlight import EnvLight, EnvMap
     if not isinstance(env, (EnvLight, EnvMap)):

@@ -177,6 +177,12 @@ class SceneOcclusionParams(ctypes.Structure):
                 [(n, _vp) for n in ("hit_points", "grad", "offset", "elem", "pixel", "position", "normal", "lights", "radius", "w2b")])
 
 
+# include/oi_ground.h
+GROUND_FLOATS = 12
+GROUND_RAYS_CAP, GROUND_RAYS_HEMISPHERE, GROUND_RAYS_LOCAL = 0, 1, 2
+
+
+
 SIGS = {
     # include/oi_hip.h: the drop-in boundary, what replaces the reference's modules
     "oi_hip.h": {
@@ -409,6 +415,15 @@ SIGS = {
         "oi_scene_aa_classify": (_i, [_vp] * 5 + [_i, _ll, _ll, _i, _f, _f, _vp, _vp, _vp, _vp]),
         "oi_scene_aa_begin": (_i, [_P(TraceBatch), _vp, _vp, _vp, _i, _i, _vp, _ll, _vp, _i, _vp]),
         "oi_aa_resolve_strided": (_i, [_vp, _vp, _ll, _vp, _ll, _ll, _i, _i, _vp, _vp]),
+    },
+    # include/oi_ground.h: a ground plane that catches the instances' shadows (an addition to oi_scene_light.h and
+    # oi_local_light.h; no struct of its own: plain arguments, and the rays' begin takes oi_scene_light.h's parameters)
+    "oi_ground.h": {
+        "oi_ground_begin": (_i, [_vp, _vp, _i] + [_vp] * 5 + [_i, _i, _vp, _vp, _vp, _vp]),
+        "oi_ground_rays_begin": (_i, [_P(TraceBatch), _P(SceneOcclusionParams), _i, _vp, _vp, _i, _vp, _vp, _vp]),
+        "oi_ground_resolve": (_i, [_vp, _i, _ll, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+        "oi_ground_shade": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _ll, _vp, _i, _i] + [_vp] * 12),
+        "oi_ground_occlude": (_i, [_P(TraceBatch), _vp, _vp, _vp, _ll, _f, _vp]),
     },
 }
 

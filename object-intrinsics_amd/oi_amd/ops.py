@@ -1197,6 +1197,111 @@ def scene_shade_local(st, W, S, owner, owner_ray, vis_slot, hit_points, grad, rg
 
 
 # ------------------------------------------------------------------------------------------
+# a ground plane that catches the instances' shadows (include/oi_ground.h); oi_amd.scene sequences these
+# ------------------------------------------------------------------------------------------
+
+def _check_ground_record(what, record):
+    if not torch.is_tensor(record) or record.dtype != torch.float32 or tuple(record.shape) != (_l.GROUND_FLOATS,):
+        raise ValueError(f"{what}: the ground record must be a float32 tensor of shape ({_l.GROUND_FLOATS},)")
+
+
+def ground_begin(c2w, kinv, S, record, owner, owner_ray, t, window, W, E):
+    """The ground pixels of a scene (oi_ground_begin).  c2w (4, 4), kinv (3, 3), record (12,) float32; owner, owner_ray (S * S,)
+    int32, t (E, W * W), window (E, 2) int32 -- or owner None: no pixel is owned.  -> ground_t (S * S,) (NaN off the ground),
+    ground_index (S * S,) int32 (its first `count` entries are written, in no fixed order), count (1,) int32 on the device."""
+    _check_ground_record("ground_begin", record)
+    M = int(S) * int(S)
+    if c2w.numel() != 16 or kinv.numel() != 9:
+        raise ValueError("ground_begin: c2w and kinv must hold 16 and 9 values")
+    if owner is not None and (owner.shape[0] != M or owner_ray.shape[0] != M or t.numel() != int(E) * int(W) * int(W)):
+        raise ValueError(f"ground_begin: owner {tuple(owner.shape)}, owner_ray {tuple(owner_ray.shape)}, t {tuple(t.shape)} for "
+                         f"{S} x {S} pixels and {E} x {W} x {W} rays")
+    keep = [_c(c2w), _c(kinv)]
+    ground_t = _new(record, M)
+    ground_index = torch.empty(M, dtype=torch.int32, device=record.device)   # (partly written by contract, as aa_classify's)
+    count = _new(record, 1).view(torch.int32)
+    _l.check(_l.load().oi_ground_begin(_p(keep[0]), _p(keep[1]), int(S), _p(record), _ip(owner), _ip(owner_ray), _p(t), _ip(window),
+                                       int(W), int(E), _p(ground_t), _ip(ground_index), _ip(count), _stream()), "oi_ground_begin")
+    return ground_t, ground_index, count
+
+
+def ground_rays_begin(sb, c2w, kinv, S, record, ground_t, ground_index, n_g, w2b, bias, samples, j0, chunk, seed=0, lights=None,
+                      radius=None, distance=None):
+    """sb: TraceBatchState of E occluder elements x L * chunk * n_g rays: the samples [j0, j0 + chunk) of the secondary rays of
+    the n_g ground points against every instance (oi_ground_rays_begin).  lights (L, 16) and radius (L,) float32: caps about
+    directional lights; lights (L, 20): rays aimed at local lights; distance (a float, inf allowed) instead: the cosine
+    hemisphere about the plane's normal."""
+    _check_ground_record("ground_rays_begin", record)
+    hemi = lights is None
+    if hemi == (distance is None):
+        raise ValueError("ground_rays_begin: give lights, or distance (the hemisphere)")
+    local = not hemi and lights.shape[-1] == _l.LOCAL_LIGHT_FLOATS
+    if not hemi and not local and (not torch.is_tensor(radius) or radius.dtype != torch.float32
+                                   or tuple(radius.shape) != (lights.shape[0],)):
+        raise ValueError(f"ground_rays_begin: radius must be a float32 tensor of shape ({lights.shape[0]},), one per light")
+    if ground_index.dtype != torch.int32 or ground_index.numel() < int(n_g) or ground_t.numel() != int(S) * int(S):
+        raise ValueError(f"ground_rays_begin: ground_index {tuple(ground_index.shape)} {ground_index.dtype}, ground_t "
+                         f"{tuple(ground_t.shape)} for {n_g} ground points of {S} x {S} pixels")
+    P = _l.SceneOcclusionParams()   # oi_scene_occlusion_begin's parameters: n_vis = n_g, pixel = the ground pixels
+    P.L, P.S, P.j0, P.Sc, P.ambient = 1 if hemi else lights.shape[0], int(samples), int(j0), int(chunk), int(hemi)
+    P.seed, P.bias, P.distance, P.n_pad, P.n_vis = int(seed), float(bias), float(distance) if hemi else 0.0, 0, int(n_g)
+    keep = [_c(x) for x in (lights, None if local else radius, w2b, c2w, kinv)]
+    P.lights, P.radius, P.w2b = (_p(x) for x in keep[:3])
+    P.pixel = _ip(ground_index)
+    mode = _l.GROUND_RAYS_HEMISPHERE if hemi else _l.GROUND_RAYS_LOCAL if local else _l.GROUND_RAYS_CAP
+    _l.check(_l.load().oi_ground_rays_begin(ctypes.byref(sb.c), ctypes.byref(P), mode, _p(keep[3]), _p(keep[4]), int(S), _p(record),
+                                            _p(ground_t), _stream()), "oi_ground_rays_begin")
+
+
+def ground_resolve(status, E, n_g, L, samples, j0, chunk, count, out, last):
+    """Adds the chunk's escaped samples to count (L, n_g) int32 (overwritten at j0 == 0); last: out (L, n_g) = count / samples."""
+    _l.check(_l.load().oi_ground_resolve(_p(status), int(E), int(n_g), int(L), int(samples), int(j0), int(chunk), int(bool(last)),
+                                         _ip(count), _p(out), _stream()), "oi_ground_resolve")
+
+
+GROUND_OUT = ("image", "depth", "position", "normal_world", "albedo", "mask", "instance")
+
+
+def ground_shade(c2w, kinv, S, record, ground_t, ground_index, n_g, lights, maps, visibility=None, ambient_occlusion=None):
+    """The ground into the scene's maps, IN PLACE at the ground pixels (oi_ground_shade).  maps: {name: tensor} for names of
+    GROUND_OUT -- image (L, 3, S * S), depth, mask (S * S,), position, normal_world, albedo (S * S, 3), instance (S * S,) int32 --
+    as scene_shade returns them.  lights (L, 16) directional or (L, 20) local records; visibility (L, n_g), ambient_occlusion
+    (n_g,) or None.  -> ground_mask (S * S,): 1 on the ground, 0 off it; shadow_matte (L, 3, S * S): 1 off the ground."""
+    _check_ground_record("ground_shade", record)
+    M, L = int(S) * int(S), lights.shape[0]
+    shapes = {"image": (L, 3, M), "depth": (M,), "mask": (M,), "instance": (M,), "position": (M, 3), "normal_world": (M, 3),
+              "albedo": (M, 3)}
+    for k, v in maps.items():
+        if k not in shapes or tuple(v.shape) != shapes[k] or not v.is_contiguous():
+            raise ValueError(f"ground_shade: {k} {tuple(v.shape)}, expected a contiguous {shapes.get(k)} of {GROUND_OUT}")
+    if visibility is not None and tuple(visibility.shape) != (L, int(n_g)):
+        raise ValueError(f"ground_shade: visibility {tuple(visibility.shape)}, expected {(L, int(n_g))}")
+    if ambient_occlusion is not None and tuple(ambient_occlusion.shape) != (int(n_g),):
+        raise ValueError(f"ground_shade: ambient_occlusion {tuple(ambient_occlusion.shape)}, expected {(int(n_g),)}")
+    ground_mask, matte = _new(record, M), _new(record, L, 3, M)
+    ground_mask.zero_()
+    matte.fill_(1.0)
+    if int(n_g) == 0:
+        return ground_mask, matte
+    keep = [_c(x) for x in (c2w, kinv, lights, visibility, ambient_occlusion)]
+    outs = [(_ip if k == "instance" else _p)(maps.get(k)) for k in GROUND_OUT]
+    _l.check(_l.load().oi_ground_shade(_p(keep[0]), _p(keep[1]), int(S), _p(record), _p(ground_t), _ip(ground_index), int(n_g),
+                                       _p(keep[2]), L, int(lights.shape[-1] == _l.LOCAL_LIGHT_FLOATS), _p(keep[3]), _p(keep[4]), *outs,
+                                       _p(ground_mask), _p(matte), _stream()), "oi_ground_shade")
+    return ground_mask, matte
+
+
+def ground_occlude(sb, record, elem, b2w, n_vis, limit):
+    """The ground as occluder of the instances' rays (oi_ground_occlude): in the finished chunk sb of scene_occlusion_begin or
+    scene_shadow_begin, the owner's ray of every visible point turns from MISS to HIT where it meets the plane before `limit`
+    (inf for directional rays)."""
+    _check_ground_record("ground_occlude", record)
+    keep = _c(b2w)
+    _l.check(_l.load().oi_ground_occlude(ctypes.byref(sb.c), _p(record), _ip(elem), _p(keep), int(n_vis), float(limit), _stream()),
+             "oi_ground_occlude")
+
+
+# ------------------------------------------------------------------------------------------
 # environment lighting on the traced surface (include/oi_envlight.h)
 # ------------------------------------------------------------------------------------------
 

@@ -21,6 +21,10 @@ and environment lighting (include/oi_scene_light.h).
                    rays that end on ANY instance carry one diffuse interreflection bounce (include/oi_scene_bounce.h; DESIGN
                    section 4.26): the instances colour each other
     render_scene_env  trace_scene + capture_transfer + shade
+    Ground         a plane in the scene's world frame that catches the instances' shadows and contact darkening and blocks their
+                   own ambient and directional rays (include/oi_ground.h): ground= on SceneSurface.shade,
+                   render_scene and the light walks; SceneSurface.ground -> GroundSurface, the plane's pixels and their
+                   secondary rays; composite_over puts the result over a photograph by its shadow matte
 
 The union of K surfaces is traced exactly by tracing each instance in its own box frame and keeping the nearest hit per
 pixel: the camera is shared and the poses are rigid, so the ray parameter of one scene pixel is comparable between
@@ -107,6 +111,181 @@ def virtual_image_size(n_sub, E, what="trace_scene"):
     return Q
 
 
+class Ground:
+    """A ground plane in the world frame of a scene (include/oi_ground.h): the points x with normal . x =
+    offset within `extent` of `centre`, a Lambertian surface of colour `albedo` seen from the side the normal points to.
+    Refused with ValueError: a normal that is not unit to 1e-4, a non-finite offset or centre, an albedo outside [0, 1], an
+    extent that is not positive (inf is allowed)."""
+
+    def __init__(self, normal, offset, albedo=(0.8, 0.8, 0.8), extent=math.inf, centre=(0.0, 0.0, 0.0)):
+        as3 = lambda v, name: np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64).reshape(-1)
+        n, a, c = as3(normal, "normal"), np.broadcast_to(as3(albedo, "albedo"), (3,)).copy(), as3(centre, "centre")
+        if n.shape != (3,) or not np.isfinite(n).all() or abs(np.linalg.norm(n) - 1.0) > 1e-4:
+            raise ValueError(f"Ground: normal={normal!r} (three finite numbers of unit length, to 1e-4)")
+        if c.shape != (3,) or not np.isfinite(c).all():
+            raise ValueError(f"Ground: centre={centre!r} (three finite numbers)")
+        if not math.isfinite(float(offset)):
+            raise ValueError(f"Ground: offset={offset!r} (a finite number)")
+        if not ((a >= 0).all() and (a <= 1).all()):
+            raise ValueError(f"Ground: albedo={albedo!r} (within [0, 1])")
+        if not float(extent) > 0:
+            raise ValueError(f"Ground: extent={extent!r} (> 0; inf is allowed)")
+        self.normal, self.offset, self.albedo = tuple(n.tolist()), float(offset), tuple(a.tolist())
+        self.extent, self.centre = float(extent), tuple(c.tolist())
+
+    @classmethod
+    def through(cls, point, normal, **kw):
+        """The plane through the world point `point`."""
+        p = np.asarray(point.detach().cpu() if torch.is_tensor(point) else point, dtype=np.float64).reshape(3)
+        n = np.asarray(normal.detach().cpu() if torch.is_tensor(normal) else normal, dtype=np.float64).reshape(3)
+        return cls(normal, float(n @ p), **kw)
+
+    @classmethod
+    def below(cls, points, normal, gap=0.0, **kw):
+        """The plane at min(normal . p) - gap over the world points `points` (n, 3), for example
+        SceneSurface.world_points()[0]: what the instances stand on."""
+        p = np.asarray(points.detach().cpu() if torch.is_tensor(points) else points, dtype=np.float64).reshape(-1, 3)
+        n = np.asarray(normal.detach().cpu() if torch.is_tensor(normal) else normal, dtype=np.float64).reshape(3)
+        if len(p) == 0 or not np.isfinite(p).all():
+            raise ValueError("Ground.below: points must be a non-empty (n, 3) array of finite numbers")
+        return cls(normal, float((p @ n).min()) - float(gap), **kw)
+
+    def packed(self):
+        """The record [OI_GROUND_FLOATS] as float32 numpy."""
+        return np.array([*self.normal, self.offset, *self.albedo, self.extent, *self.centre, 0.0], dtype=np.float32)
+
+
+def check_ground_keyword(ground, aa, what):
+    """The `ground` keyword of `what` before anything is traced: a Ground or None, and not together with anti-aliasing."""
+    if ground is None:
+        return
+    if not isinstance(ground, Ground):
+        raise ValueError(f"{what}: ground={ground!r} (an oi_amd.scene.Ground)")
+    if aa is not None:
+        raise ValueError(f"{what}: ground with aa_samples={aa.S}; the ground plane has no anti-aliasing stage yet (aa_samples=1)")
+
+
+def refuse_env_ground(ground, what):
+    """The `ground` keyword of an environment path: refused unless None (capture_transfer's maps know no ground plane yet)."""
+    if ground is not None:
+        raise ValueError(f"{what}: ground= is not supported by capture_transfer and the environment paths (the ground plane is "
+                         "shaded by SceneSurface.shade under directional and local lights)")
+
+
+class GroundSurface:
+    """A Ground in one traced scene (SceneSurface.ground): record (12,) on the device; t (S * S,), the ground's ray parameter
+    per scene pixel, NaN off the ground; n_g ground pixels, index (n_g,) int32 ascending, slot (S * S,) int32 (a pixel's
+    position in index, -1 off the ground); evals: the sdf evaluations of its secondary rays so far."""
+
+    def __init__(self, scene, ground):
+        s, dev = scene, scene.b2w.device
+        c2w = s.c2w.detach().cpu().double().numpy()
+        rec = ground.packed()
+        height = float(np.asarray(ground.normal) @ c2w[:3, 3]) - ground.offset
+        if not height > 0:
+            raise ValueError(f"SceneSurface.ground: the camera is on or below the plane (normal . eye - offset = {height:.4g}, > 0 "
+                             "needed)")
+        self.scene, self.ground, self.evals = s, ground, 0
+        self.record = torch.from_numpy(rec).to(dev)
+        M = s.S * s.S
+        owned = s.owner is not None
+        self.t, index, count = ops.ground_begin(s.c2w, s.kinv, s.S, self.record, s.owner, s.owner_ray if owned else None,
+                                                s.state.t if owned else None, s.window if owned else None, s.W, s.E)
+        self.n_g = int(count.item())
+        # The compaction's order differs from run to run, and the pixel keys the samples: ascending order makes the frame a
+        # function of its arguments alone (as SceneSurface._antialias does for the flagged pixels).
+        self.index = torch.sort(index[:self.n_g]).values.contiguous()
+        self.slot = torch.full((M,), -1, dtype=torch.int32, device=dev)
+        self.slot[self.index.long()] = torch.arange(self.n_g, dtype=torch.int32, device=dev)
+
+    def _args(self):
+        s = self.scene
+        return s.c2w, s.kinv, s.S, self.record, self.t, self.index, self.n_g
+
+    def _sampled(self, what, samples, seed, max_shadow_rays, lights=None, radius=None, distance=None):
+        """The sampled any-hit trace of the ground points against every instance, in chunks of the samples under
+        max_shadow_rays as SceneSurface._sampled's: a chunk holds E * L * Sc * n_g rays.  -> out (L, n_g)."""
+        s = self.scene
+        L = 1 if lights is None else lights.shape[0]
+        per = s.E * L * self.n_g
+        chunk = min(int(samples), min(int(max_shadow_rays), (1 << 31) - 1) // per)
+        if chunk < 1:
+            raise ValueError(f"{what}: {s.E} instances x {L} lights x {self.n_g} ground points = E * L * n_g = {per} rays per sample "
+                             f"(at most max_shadow_rays={max_shadow_rays} and below 2^31; inference.scene_light_walk splits the lights)")
+        count, out = ops._new(self.record, L, self.n_g).view(torch.int32), ops._new(self.record, L, self.n_g)
+        for j0 in range(0, int(samples), chunk):
+            c = min(chunk, int(samples) - j0)
+            sb = ops.trace_batch_state_empty(s.E, L * c * self.n_g, self.record)
+            ops.ground_rays_begin(sb, *self._args(), s.w2b, s.bias, samples, j0, c, seed, lights, radius, distance)
+            bound = int(sb.live[0].item())
+            if bound:
+                total, _ = _t._march_batch(s.field, sb, *s.kw, bound=bound, anyhit=True)
+                self.evals += total
+                ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
+            ops.ground_resolve(sb.status, s.E, self.n_g, L, samples, j0, c, count, out, j0 + c == int(samples))
+            self.last = sb
+        return out
+
+    def visibility(self, lights, radius=None, samples=1, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """(L, n_g): the share of `samples` rays per directional light (L, 16) and ground point, over the light's cap of angular
+        radius radius[l] (None: 0, the hard shadow ray), that miss EVERY instance."""
+        L = lights.shape[0]
+        if self.n_g == 0:
+            return torch.ones(L, 0, device=lights.device)
+        radius = torch.zeros(L, device=lights.device) if radius is None else \
+            torch.as_tensor(radius, dtype=torch.float32).reshape(-1).to(lights.device)
+        return self._sampled("GroundSurface.visibility", samples, seed, max_shadow_rays, lights, radius)
+
+    def local_visibility(self, lights, samples=1, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """(L, n_g): the share of `samples` rays per local light (L, 20) and ground point, aimed at the light's sphere and ending
+        there, that miss every instance.  An instance beyond the light throws no shadow on the ground."""
+        if self.n_g == 0:
+            return torch.ones(lights.shape[0], 0, device=lights.device)
+        return self._sampled("GroundSurface.local_visibility", samples, seed, max_shadow_rays, lights)
+
+    def ambient(self, samples, distance, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+        """(n_g,): the share of `samples` cosine-weighted rays over the plane's hemisphere per ground point that meet no instance
+        within `distance`: the contact shadow."""
+        if self.n_g == 0:
+            return torch.ones(0, device=self.record.device)
+        return self._sampled("GroundSurface.ambient", samples, seed, max_shadow_rays, distance=float(distance)).view(self.n_g)
+
+    def occlusion(self, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays):
+        """shade's secondary rays of the ground points: -> (visibility (L, n_g) or None, ambient occlusion (n_g,) or None)."""
+        vis = None
+        if shadows and _t._is_local(lt):
+            vis = self.local_visibility(lt, int(shadow_samples), int(seed), max_shadow_rays)
+        elif shadows:
+            vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays)
+        ao = self.ambient(int(ao_samples), float(ao_distance), int(seed), max_shadow_rays) if ao_samples else None
+        return vis, ao
+
+    def shade(self, maps, lt, vis=None, ao=None):
+        """oi_ground_shade: the ground into `maps` (ops.GROUND_OUT's names), in place.  -> ground_mask (S * S,), shadow_matte (L,
+        3, S * S)."""
+        return ops.ground_shade(*self._args(), lt, {k: v for k, v in maps.items() if k in ops.GROUND_OUT}, vis, ao)
+
+    def shade_into(self, maps, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays):
+        """occlusion() and shade()."""
+        vis, ao = self.occlusion(lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays)
+        return self.shade(maps, lt, vis, ao)
+
+
+def composite_over(result, photo):
+    """A rendered scene with a ground plane (SceneSurface.shade's dict with ground=) over a photograph: `image` on the
+    instances' mask, photo * shadow_matte elsewhere -- the photograph darkened by the instances' shadows and contact
+    occlusion where the ground catches them, untouched off the ground.  photo: (3, S, S) or (L, 3, S, S).  -> (L, 3, S, S)."""
+    if "shadow_matte" not in result:
+        raise ValueError("composite_over: the result has no shadow_matte (render the scene with ground=)")
+    image, matte, mask = result["image"], result["shadow_matte"], result["mask"]
+    photo = torch.as_tensor(photo, dtype=image.dtype).to(image.device)
+    if photo.dim() == 3:
+        photo = photo[None]
+    if photo.shape[-3:] != image.shape[-3:] or photo.shape[0] not in (1, image.shape[0]):
+        raise ValueError(f"composite_over: photo {tuple(photo.shape)} for an image {tuple(image.shape)}")
+    return torch.where(mask > 0, image, photo * matte)
+
+
 class SceneSurface:
     """One traced scene and what the light-dependent stages reuse: the batched state (rays, t, status per instance), the
     owner map, the visible hits of every instance and the gradient and albedo there.
@@ -138,6 +317,7 @@ class SceneSurface:
         c2b, kinv = prior["c2b"].contiguous(), gen._kinv(dev)
         ops.scene_begin(st, c2b, kinv, win, W, S)
         self._set(gen, field, kw, bias, b2w, prior["w2b"].contiguous(), win, W, S, st)
+        self.c2w, self.kinv = gen.camera.c2w.detach().to(dev).float().contiguous(), kinv   # the scene's world rays (ground())
         if aa is not None:
             self._antialias(aa, c2b, kinv)
 
@@ -156,6 +336,7 @@ class SceneSurface:
         self.glossy_evals, self.glossy_state, self._reflect = 0, None, None
         self.bounce_points, self.bounce_hits = 0, None
         self.aa = self.sub = self.edge_slot = None   # the anti-aliasing stage (_antialias), when there is one
+        self._grounds = {}                           # GroundSurface per ground record (ground())
         self.n_edge = 0
         bound = int(st.live[0].item())
         self.n_entered = st.counts[:, 0].tolist()
@@ -234,15 +415,32 @@ class SceneSurface:
                                                  sum(self.n_vis))
         return self._pixel
 
+    def ground(self, ground):
+        """The ground plane `ground` (a Ground) in this scene: -> GroundSurface, its ground pixels classified against the owner
+        map (oi_ground_begin) and listed in ascending order; cached per record.  Refused: a scene traced with aa_samples > 1, a
+        camera on or below the plane."""
+        if isinstance(ground, GroundSurface):
+            return ground
+        if not isinstance(ground, Ground):
+            raise ValueError(f"SceneSurface.ground: ground={ground!r} (an oi_amd.scene.Ground)")
+        if getattr(self, "aa", None) is not None:
+            raise ValueError(f"SceneSurface.ground: the scene was traced with aa_samples={self.aa.S}; the ground plane has no "
+                             "anti-aliasing stage yet (trace the scene with aa_samples=1)")
+        key = ground.packed().tobytes()
+        if key not in self._grounds:
+            self._grounds[key] = GroundSurface(self, ground)
+        return self._grounds[key]
+
     def _sampled(self, what, samples, seed, max_shadow_rays, resolve, lights=None, radius=None, distance=None, *, lobe=None,
-                 anyhit=True, local=False):
+                 anyhit=True, local=False, ground=None):
         """The sampled any-hit trace against every instance, in chunks of the samples: a chunk holds E * L * Sc * n_vis rays, Sc
         the largest number for which that stays within max_shadow_rays and below 2^31.  resolve(sb, j0, Sc, last) accumulates
         each finished chunk.  lights and radius: caps about the lights; distance: the hemisphere about the normal; lobe (a
         shininess): the reflection lobe about the reflected view vector (include/oi_scene_gloss.h).  anyhit False: the same rays
         marched to their CLOSEST hit (oi_trace_batch_step), what the bounce follows (include/oi_scene_bounce.h).  local: `lights`
-        are local records (L, 20) and the rays are aimed at them and end there (include/oi_local_light.h).  -> (sdf
-        evaluations per element, the last chunk's state)."""
+        are local records (L, 20) and the rays are aimed at them and end there (include/oi_local_light.h).  ground (a
+        GroundSurface; caps and the hemisphere only): the plane blocks the owner's ray of every finished chunk
+        (oi_ground_occlude) before its resolve.  -> (sdf evaluations per element, the last chunk's state)."""
         L, n_vis = 1 if lights is None else lights.shape[0], sum(self.n_vis)
         per = self.E * L * n_vis
         chunk = min(int(samples), min(int(max_shadow_rays), (1 << 31) - 1) // per)
@@ -269,16 +467,20 @@ class SceneSurface:
                 total, _ = _t._march_batch(self.field, sb, *self.kw, bound=bound, anyhit=anyhit)
                 evals += total
                 ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
+            if ground is not None:
+                ops.ground_occlude(sb, ground.record, elem, self.b2w, n_vis, math.inf if distance is None else distance)
             resolve(sb, j0, c, j0 + c == int(samples))
         return evals, sb
 
-    def visibility(self, lights, radius=None, samples=1, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+    def visibility(self, lights, radius=None, samples=1, seed=0, max_shadow_rays=MAX_SHADOW_RAYS, ground=None):
         """(L, S * S) visibility of `lights` (L, 16).  radius None (or all zero) and one sample: one shadow ray per light and
         visible point, marched against EVERY instance in one batch of E occluder elements; a pixel is lit (1) when its ray
         missed them all, else 0.  Otherwise radius (L,) holds the lights' angular radii and `samples` rays per light and
         visible point sample each light's cap, every ray tested against every instance in its any-hit form: the share in
-        [0, 1] of a pixel's samples that reach the light.  Split into chunks of samples above max_shadow_rays."""
+        [0, 1] of a pixel's samples that reach the light.  Split into chunks of samples above max_shadow_rays.
+        ground (a Ground): the plane blocks the instances' shadow rays too (oi_ground_occlude on each chunk)."""
         L, n_vis = lights.shape[0], sum(self.n_vis)
+        ground = None if ground is None else self.ground(ground)
         if n_vis == 0:
             return torch.ones(L, self.S * self.S, device=lights.device)
         if radius is not None:
@@ -291,7 +493,8 @@ class SceneSurface:
             resolve = lambda sb, j0, c, last: ops.scene_occlusion_resolve(
                 sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, L, samples, j0, c, n_vis, self.S,
                 count, out, last)
-            evals, self.shadow = self._sampled("SceneSurface.shade", samples, seed, max_shadow_rays, resolve, lights, radius)
+            evals, self.shadow = self._sampled("SceneSurface.shade", samples, seed, max_shadow_rays, resolve, lights, radius,
+                                               ground=ground)
             self.shadow_evals += evals
             return out
         rays = self.E * L * n_vis
@@ -306,6 +509,8 @@ class SceneSurface:
             total, _ = _t._march_batch(self.field, sb, *self.kw, bound=bound)
             self.shadow_evals += total
             ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
+        if ground is not None:
+            ops.ground_occlude(sb, ground.record, elem, self.b2w, n_vis, math.inf)
         self.shadow = sb
         return ops.scene_visibility(sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, L, n_vis, self.S)
 
@@ -328,17 +533,20 @@ class SceneSurface:
         self.shadow_evals += evals
         return acc[1]
 
-    def ambient(self, samples, distance, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
+    def ambient(self, samples, distance, seed=0, max_shadow_rays=MAX_SHADOW_RAYS, ground=None):
         """(S * S,) ambient occlusion: the share of `samples` cosine-weighted hemisphere rays per visible point that meet no
-        instance -- the point's own or any other -- within `distance` (world units; inf allowed); 1 off the mask."""
+        instance -- the point's own or any other -- within `distance` (world units; inf allowed); 1 off the mask.  ground (a
+        Ground): nor the plane (oi_ground_occlude on each chunk): an instance darkens where it nears the ground."""
         M, n_vis, dev = self.S * self.S, sum(self.n_vis), self.b2w.device
+        ground = None if ground is None else self.ground(ground)
         if n_vis == 0:
             return torch.ones(M, device=dev)
         count, out = ops._new(self.b2w, 1, M).view(torch.int32), ops._new(self.b2w, 1, M)
         resolve = lambda sb, j0, c, last: ops.scene_occlusion_resolve(
             sb.status, self.owner, self.owner_ray, self.vis_slot, self.offset, self.E, self.N, 1, samples, j0, c, n_vis, self.S, count,
             out, last)
-        evals, self.ao = self._sampled("SceneSurface.ambient", samples, seed, max_shadow_rays, resolve, distance=float(distance))
+        evals, self.ao = self._sampled("SceneSurface.ambient", samples, seed, max_shadow_rays, resolve, distance=float(distance),
+                                       ground=ground)
         self.occlusion_evals += evals
         return out.view(M)
 
@@ -436,6 +644,8 @@ class SceneSurface:
         nearest intersection with ANY instance and folds one diffuse interreflection bounce between the instances -- and of an
         instance on itself -- into a per-channel transfer, SceneTransfer.bounce (include/oi_scene_bounce.h has the estimator and
         its approximations); the direct transfer is bit for bit that of bounces = 0, which launches what it always did.
+        (The transfer map knows no ground plane: render_scene_env and inference.scene_env_walk refuse ground=; DESIGN section
+        4.31.)
         -> SceneTransfer."""
         aa = getattr(self, "aa", None)
         if aa is not None:
@@ -478,7 +688,7 @@ class SceneSurface:
         return res
 
     def shade(self, lights=None, shadows=False, bg=None, max_shadow_rays=MAX_SHADOW_RAYS, shadow_samples=1, light_radius=0.0,
-              ao_samples=0, ao_distance=0.5, seed=0):
+              ao_samples=0, ao_distance=0.5, seed=0, ground=None):
         """The scene under `lights` (oi_amd.relight.Light objects in the WORLD frame; default the generator's trained light; at
         most RELIGHT_MAX_LIGHTS; or oi_amd.relight.LocalLight objects, lights that stand between the instances: their shadow
         rays end at the light, shadow_samples sample the light's own sphere and light_radius must stay 0).  -> dict of image (L, 3, S, S); depth (the ray parameter; NaN off the mask), mask, instance
@@ -495,15 +705,25 @@ class SceneSurface:
         On a scene traced with aa_samples > 1 (trace_scene) the sub-sample surface passes the same stages
         with the same arguments and `image` is the mean over each flagged pixel's samples, off-surface samples carrying bg; new
         keys coverage (1, 1, S, S), the mean of the mask over a pixel's samples, and aa_mask (1, 1, S, S), the flagged pixels;
-        every other map stays the centre sample's."""
+        every other map stays the centre sample's.
+        ground (a Ground): a plane in the world that is visible where no instance is nearer, shaded as a
+        Lambertian surface under the lights, and that catches the instances' shadows (with `shadows`) and ambient occlusion
+        (with ao_samples) and blocks their own ambient and directional shadow rays (not their local-light rays).  It is
+        written into every map at its pixels -- there mask = 0 and instance = -1 -- and adds ground_mask (1, 1, S, S) and
+        shadow_matte (L, 3, S, S), the shaded ground over the unoccluded one (1 off the ground; composite_over); stats gains
+        ground_pixels and ground_evals.  Refused on a scene traced with aa_samples > 1.  None: the launches and bytes of a
+        call without the keyword."""
         dev = self.b2w.device
+        gs = None if ground is None else self.ground(ground)
         lt = _t._stack_lights(self.gen, lights, dev, "SceneSurface.shade", "; inference.scene_light_walk splits larger sets")
         local = _t._is_local(lt)
         radii = _t._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0],
                                     "SceneSurface.shade", local)
-        vis, ao = self._occlusion(lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays)
+        vis, ao = self._occlusion(lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays, gs)
         out = self._shade(lt, _t._bg(bg, dev), vis, ("depth", "position", "normal_world", "albedo", "mask", "instance", "image"), ao=ao)
         S = self.S
+        if gs is not None:
+            ground_mask, matte = gs.shade_into(out, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays)
         res = {_MAP_NAMES[k]: v for k, v in _t._maps({k: v for k, v in out.items() if k != "image"}, S, S).items()}
         res["image"] = out["image"].view(-1, 3, S, S)
         if self.aa is not None:   # the sub-samples through the same stages, then the mean over each flagged pixel's samples
@@ -518,16 +738,22 @@ class SceneSurface:
         if ao_samples:
             res["ambient_occlusion"] = ao.view(1, 1, S, S)
         res["stats"] = self.stats()
+        if gs is not None:
+            res["ground_mask"], res["shadow_matte"] = ground_mask.view(1, 1, S, S), matte.view(-1, 3, S, S)
+            for st in res["stats"]:
+                st.update(ground_pixels=gs.n_g, ground_evals=gs.evals)
         return res
 
-    def _occlusion(self, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays):
-        """shade's secondary rays on this surface: -> (visibility (L, S * S) or None, ambient occlusion (S * S,) or None)."""
+    def _occlusion(self, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays, ground=None):
+        """shade's secondary rays on this surface: -> (visibility (L, S * S) or None, ambient occlusion (S * S,) or None).
+        ground (a GroundSurface): the plane blocks the ambient and the directional rays."""
         vis = None
+        kw = {} if ground is None else {"ground": ground}
         if shadows and _t._is_local(lt):
             vis = self.local_visibility(lt, int(shadow_samples), int(seed), max_shadow_rays)
         elif shadows:
-            vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays)
-        ao = self.ambient(int(ao_samples), float(ao_distance), int(seed), max_shadow_rays) if ao_samples else None
+            vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays, **kw)
+        ao = self.ambient(int(ao_samples), float(ao_distance), int(seed), max_shadow_rays, **kw) if ao_samples else None
         return vis, ao
 
     def resolved(self, lt, bgv, centre, vis_sub, ao_sub, image_out=None, want_mask=False):
@@ -688,25 +914,28 @@ def trace_scene(gen, zs, b2ws, window=None, bias=DEFAULT_BIAS, aa_samples=1, aa_
 def render_scene(gen, zs, b2ws, lights=None, shadows=False, bg=None, window=None, bias=DEFAULT_BIAS,
                  max_shadow_rays=MAX_SHADOW_RAYS, shadow_samples=1, light_radius=0.0, ao_samples=0, ao_distance=0.5, seed=0,
                  aa_samples=1, aa_adaptive=True, aa_plane=_l.AA_DEFAULT_PLANE, aa_cos=_l.AA_DEFAULT_COS, aa_pattern=None,
-                 **trace_kw):
+                 ground=None, **trace_kw):
     """trace_scene + SceneSurface.shade: K instances in one scene image, nearer instances hiding farther ones and, with
     `shadows`, every instance throwing its shadow on itself and on the others; shadow_samples, light_radius, ao_samples,
     ao_distance, seed: shade's soft shadows and ambient occlusion between the instances; aa_samples, aa_adaptive, aa_plane,
-    aa_cos, aa_pattern: trace_scene's anti-aliasing.  -> SceneSurface.shade's dict, with "scene" (the SceneSurface)."""
+    aa_cos, aa_pattern: trace_scene's anti-aliasing; ground: shade's ground plane (a Ground; not with aa_samples > 1).
+    -> SceneSurface.shade's dict, with "scene" (the SceneSurface)."""
     rad = light_radius.detach().cpu() if torch.is_tensor(light_radius) else light_radius
     # (before the trace; shade checks a radius per light against the lights it stacks)
     _t._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, np.size(rad) if np.ndim(rad) == 1 else 1,
                         "render_scene", local_lights_given(lights))
-    _t._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "render_scene")
+    aa = _t._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "render_scene")
+    check_ground_keyword(ground, aa, "render_scene")
     s = trace_scene(gen, zs, b2ws, window, bias, aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, **trace_kw)
-    res = s.shade(lights, shadows, bg, max_shadow_rays, shadow_samples, light_radius, ao_samples, ao_distance, seed)
+    res = s.shade(lights, shadows, bg, max_shadow_rays, shadow_samples, light_radius, ao_samples, ao_distance, seed, ground)
     res["scene"] = s
     return res
 
 
 @torch.no_grad()
 def render_scene_env(gen, zs, b2ws, envs, transfer_samples=64, seed=0, bg=None, window=None, bias=DEFAULT_BIAS,
-                     max_shadow_rays=MAX_SHADOW_RAYS, glossy_samples=None, shininess=None, specular=None, bounces=0, **trace_kw):
+                     max_shadow_rays=MAX_SHADOW_RAYS, glossy_samples=None, shininess=None, specular=None, bounces=0, ground=None,
+                     **trace_kw):
     """trace_scene + capture_transfer + shade: K instances in one scene image under the environment lights `envs`
     (oi_amd.envlight.EnvLight objects, or EnvMap objects with glossy_samples given: capture_transfer's and shade's keywords pass
     through), every instance occluding the sky for itself and for the others -- and, on the glossy path, standing in the
@@ -714,6 +943,7 @@ def render_scene_env(gen, zs, b2ws, envs, transfer_samples=64, seed=0, bg=None, 
     (the SceneTransfer); on the glossy path also "specular" (F, 3, S, S), "spec_visibility" (1, 1, S, S) or None and
     "reflection" (1, 3, S, S); with bounces=1 (EnvLight objects only) also "indirect" (F, 3, S, S) and "bounce" (1, 3, 9, S, S):
     the instances colour each other."""
+    refuse_env_ground(ground, "render_scene_env")
     samples, _ = _t._check_transfer(transfer_samples, seed, "render_scene_env")
     _t._check_bounces(bounces, samples, glossy_samples, shininess, "render_scene_env")
     _t._check_glossy(gen, glossy_samples, shininess, "render_scene_env")

@@ -42,7 +42,12 @@ With --aa S [--aa-full] the tool measures ONLY, per K and 
 the trained light with one sample per pixel (aa_samples=1: the path without the stage), with S samples in the flagged scene
 pixels (adaptive), and -- with --aa-full -- with S samples in every scene pixel (aa_adaptive=False); with each the flagged
 pixels, the sub-sample rays per instance, the side Q of their virtual image, their sdf evaluations and the steps of the
-second chain."""
+second chain.
+
+With --ground each row also gets scene_ground_ms: the shadowed frame (scene_shadows_ms's keywords) with
+a ground plane oi_amd.scene.Ground.below the instances' visible points (gap 0.02, a disc of radius --ground-extent about their
+centroid), and with it ground_pixels, the ground's secondary rays per frame (ground_rays = K * ground_pixels * (shadow samples +
+ambient samples)), ground_evals and ground_share, its share of the frame's sdf evaluations."""
 import argparse
 import copy
 import json
@@ -79,6 +84,8 @@ ap.add_argument("--local", action="store_true", help="also time a local light (o
 ap.add_argument("--light-size", type=float, default=0.15, help="with --local: radius of the sphere light of the sampled row")
 ap.add_argument("--aa", type=int, default=0, help="samples per flagged scene pixel: time anti-aliased frames beside the one-sample frame, only")
 ap.add_argument("--aa-full", action="store_true", help="with --aa: also time aa_adaptive=False (every scene pixel flagged)")
+ap.add_argument("--ground", action="store_true", help="also time the shadowed frame with a ground plane below the instances: scene_ground_ms")
+ap.add_argument("--ground-extent", type=float, default=8.0, help="with --ground: radius of the plane about the instances' centroid")
 args = ap.parse_args()
 
 
@@ -167,6 +174,16 @@ with torch.no_grad():
             row["scene" + name + "_ms"] = median_ms(lambda: scene.render_scene(gen, zs, b2ws, shadows=shadows, **kw))
             if not args.skip_crops:
                 row["crops" + name + "_ms"] = median_ms(lambda: crops(shadows))
+        if args.ground:
+            pts = s.world_points()[0]
+            ground = scene.Ground.below(pts, (0.0, -1.0, 0.0), gap=0.02, extent=args.ground_extent,
+                                        centre=tuple(float(x) for x in pts.mean(0)))
+            frame = lambda: scene.render_scene(gen, zs, b2ws, shadows=True, ground=ground, **soft)
+            row["scene_ground_ms"] = median_ms(frame)
+            st = frame()["stats"][0]
+            evals = st["n_evals"] + st["shadow_evals"] + st["occlusion_evals"] + st["ground_evals"]
+            row.update(ground_pixels=st["ground_pixels"], ground_rays=K * st["ground_pixels"] * (args.shadow_samples + args.ao_samples),
+                       ground_evals=st["ground_evals"], ground_share=st["ground_evals"] / max(1, evals))
         if args.env:
             row["scene_env_ms"] = median_ms(lambda: scene.render_scene_env(gen, zs, b2ws, envs, transfer_samples=args.transfer_samples))
             if not args.skip_crops:

@@ -50,8 +50,9 @@
  *     valid input of the full pass for every element, one without a hit included; what the pass writes for them is never read.
  *   - n_pad == 0 (no element has a hit): nothing more is launched.
  *
- * What is batched: the primary trace and the full pass at its hits.  Secondary rays (shadows, soft shadows, ambient
- * occlusion) are traced per element by oi_trace.h / oi_occlusion.h on the element's slices.
+ * What is batched here: the primary trace and the full pass at its hits.  Secondary rays (shadows, soft shadows, ambient
+ * occlusion) are traced per element by oi_trace.h / oi_occlusion.h on the element's slices, or for all elements in one chain
+ * by include/oi_occlusion_batch.h.
  */
 #ifndef OI_TRACE_BATCH_H_
 #define OI_TRACE_BATCH_H_

@@ -23,23 +23,15 @@ __global__ void __launch_bounds__(TR_THREADS) local_light_begin_kernel(const oi_
                                                                        const float* __restrict__ w2b, float bias, unsigned seed) {
   __shared__ unsigned lds[TR_WAVES + 1];
   const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  bool traced = false;
-  float o[3] = {0.f, 0.f, 0.f};
+  BeginRay ry = {};
   if (q < s.N) {
     const long long lj = q / n_hit, i = q - lj * n_hit;
     const long long l = lj / S;
     const unsigned j = (unsigned)(lj - l * S);
-    float n[3], lq[3], R;
-    unit_normal(grad, i, n[0], n[1], n[2]);
-    offset_origin(hit_points + i * 3, bias, n[0], n[1], n[2], o[0], o[1], o[2]);
-    local_light_position(lights + l * OI_LOCAL_LIGHT_FLOATS, w2b, lq, R);
-    const AimedSample a = aimed_sample(o, n, lq, R, (unsigned)hit_index[i], seed, j, S);
-    traced = a.kind == AIMED_TRACED;
-    const float far = traced ? fminf(a.t_light, unit_sphere_exit(o[0], o[1], o[2], a.d[0], a.d[1], a.d[2])) : 0.f;
-    write_ray(s, q, o, a.d, 0.f, far,
-              traced ? OI_TRACE_MARCH : a.kind == AIMED_INSIDE ? OI_TRACE_MISS : OI_TRACE_BACKFACING);
+    ry = begin_ray<BEGIN_LOCAL>(hit_points, grad, hit_index, i, l, j, S, lights, nullptr, w2b, bias, 0.f, seed);
+    write_ray(s, q, ry.o, ry.d, 0.f, ry.far_, ry.status);
   }
-  enter_rays(s, q, traced, o[0], o[1], o[2], lds);
+  enter_rays(s, q, ry.entered, ry.o[0], ry.o[1], ry.o[2], lds);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) scene_local_light_begin_kernel(const oi_trace_state s, int* __restrict__ live,

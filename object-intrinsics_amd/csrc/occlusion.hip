@@ -24,23 +24,15 @@ __global__ void __launch_bounds__(TR_THREADS) occlusion_begin_kernel(const oi_tr
                                                                      unsigned seed) {
   __shared__ unsigned lds[TR_WAVES + 1];
   const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  bool traced = false;
-  float ox = 0.f, oy = 0.f, oz = 0.f;
+  BeginRay ry = {};
   if (q < s.N) {
     const long long lj = q / n_hit, i = q - lj * n_hit;
     const long long l = lj / S;
     const unsigned j = (unsigned)(lj - l * S);
-    float nx, ny, nz, dx, dy, dz;
-    unit_normal(grad, i, nx, ny, nz);
-    traced = occlusion_direction<AMBIENT>(nx, ny, nz, (unsigned)hit_index[i], seed, j, S, lights + l * OI_RELIGHT_LIGHT_FLOATS, radius,
-                                          l, w2b, dx, dy, dz);
-    offset_origin(hit_points + i * 3, bias, nx, ny, nz, ox, oy, oz);
-    float far = unit_sphere_exit(ox, oy, oz, dx, dy, dz);
-    if (AMBIENT) far = fminf(far, distance);
-    const float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz};
-    write_ray(s, q, o, d, 0.f, far, traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING);
+    ry = begin_ray<AMBIENT ? BEGIN_HEMISPHERE : BEGIN_CAP>(hit_points, grad, hit_index, i, l, j, S, lights, radius, w2b, bias, distance, seed);
+    write_ray(s, q, ry.o, ry.d, 0.f, ry.far_, ry.status);
   }
-  enter_rays(s, q, traced, ox, oy, oz, lds);
+  enter_rays(s, q, ry.entered, ry.o[0], ry.o[1], ry.o[2], lds);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) occlusion_resolve_kernel(const uint8_t* __restrict__ status,

@@ -32,13 +32,13 @@ __global__ void __launch_bounds__(TR_THREADS) trace_shadow_begin_kernel(const oi
                                                                         const float* __restrict__ w2b, float bias) {
   __shared__ unsigned lds[TR_WAVES + 1];
   const long long q = (long long)blockIdx.x * TR_THREADS + threadIdx.x;
-  ShadowRay ry = {};
+  BeginRay ry = {};
   if (q < s.N) {
     const long long l = q / n_hit, i = q - l * n_hit;
-    ry = shadow_ray(hit_points, grad, i, lights + l * OI_RELIGHT_LIGHT_FLOATS, w2b, bias);
-    write_ray(s, q, ry.o, ry.l, 0.f, ry.far_, ry.traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING);
+    ry = begin_ray<BEGIN_SHADOW>(hit_points, grad, nullptr, i, l, 0u, 1, lights, nullptr, w2b, bias, 0.f, 0u);
+    write_ray(s, q, ry.o, ry.d, 0.f, ry.far_, ry.status);
   }
-  enter_rays(s, q, ry.traced, ry.o[0], ry.o[1], ry.o[2], lds);
+  enter_rays(s, q, ry.entered, ry.o[0], ry.o[1], ry.o[2], lds);
 }
 
 __global__ void __launch_bounds__(TR_THREADS) trace_visibility_kernel(const uint8_t* __restrict__ status,

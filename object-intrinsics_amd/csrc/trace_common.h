@@ -607,6 +607,54 @@ __device__ __forceinline__ void surface_shade_local_at(const P& p, const float* 
   local_shade_at(p, ao, r, hit, q, M);
 }
 
+// The secondary ray of hit i (pixel key hit_index[i]) under light l, sample j of S: what the begin kernels of trace.hip,
+// occlusion.hip, local_light.hip and occlusion_batch.hip write with write_ray and enter with enter_rays.  One function per kind,
+// NOT inlined: it is compiled on its own, so the single-view kernels and the batched kernels (include/oi_occlusion_batch.h)
+// run the same instructions and a ray is the same bits whichever of them writes it -- inlined, the compiler contracts and packs
+// these sums differently from kernel to kernel.  Everything is returned in registers: no memory.
+enum BeginKind { BEGIN_SHADOW = 0, BEGIN_CAP = 1, BEGIN_HEMISPHERE = 2, BEGIN_LOCAL = 3 };
+struct BeginRay {
+  float o[3], d[3], far_;
+  unsigned status;
+  bool entered;
+};
+template <int KIND>
+__device__ __noinline__ BeginRay begin_ray(const float* __restrict__ hit_points, const float* __restrict__ grad,
+                                           const int* __restrict__ hit_index, long long i, long long l, unsigned j, int S,
+                                           const float* __restrict__ lights, const float* __restrict__ radius,
+                                           const float* __restrict__ w2b, float bias, float distance, unsigned seed) {
+  BeginRay r;
+  if constexpr (KIND == BEGIN_SHADOW) {
+    const ShadowRay ry = shadow_ray(hit_points, grad, i, lights + l * OI_RELIGHT_LIGHT_FLOATS, w2b, bias);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) r.o[a] = ry.o[a], r.d[a] = ry.l[a];
+    r.far_ = ry.far_;
+    r.entered = ry.traced;
+    r.status = ry.traced ? OI_TRACE_MARCH : OI_TRACE_BACKFACING;
+  } else if constexpr (KIND == BEGIN_LOCAL) {
+    float n[3], lq[3], R;
+    unit_normal(grad, i, n[0], n[1], n[2]);
+    offset_origin(hit_points + i * 3, bias, n[0], n[1], n[2], r.o[0], r.o[1], r.o[2]);
+    local_light_position(lights + l * OI_LOCAL_LIGHT_FLOATS, w2b, lq, R);
+    const AimedSample a = aimed_sample(r.o, n, lq, R, (unsigned)hit_index[i], seed, j, S);
+    r.entered = a.kind == AIMED_TRACED;
+    r.d[0] = a.d[0], r.d[1] = a.d[1], r.d[2] = a.d[2];
+    r.far_ = r.entered ? fminf(a.t_light, unit_sphere_exit(r.o[0], r.o[1], r.o[2], a.d[0], a.d[1], a.d[2])) : 0.f;
+    r.status = r.entered ? OI_TRACE_MARCH : a.kind == AIMED_INSIDE ? OI_TRACE_MISS : OI_TRACE_BACKFACING;
+  } else {
+    constexpr bool AMBIENT = KIND == BEGIN_HEMISPHERE;
+    float nx, ny, nz;
+    unit_normal(grad, i, nx, ny, nz);
+    r.entered = occlusion_direction<AMBIENT>(nx, ny, nz, (unsigned)hit_index[i], seed, j, S, lights + l * OI_RELIGHT_LIGHT_FLOATS, radius,
+                                             l, w2b, r.d[0], r.d[1], r.d[2]);
+    offset_origin(hit_points + i * 3, bias, nx, ny, nz, r.o[0], r.o[1], r.o[2]);
+    r.far_ = unit_sphere_exit(r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2]);
+    if (AMBIENT) r.far_ = fminf(r.far_, distance);
+    r.status = r.entered ? OI_TRACE_MARCH : OI_TRACE_BACKFACING;
+  }
+  return r;
+}
+
 inline unsigned n_blocks(long long n) { return (unsigned)((n + TR_THREADS - 1) / TR_THREADS); }
 
 // a check's refusal is the entry's

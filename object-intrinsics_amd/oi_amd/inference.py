@@ -154,7 +154,8 @@ OCCLUSION_MAX_RAYS = min((2 << 30) // TRACE_BYTES_PER_RAY, (1 << 31) - 1)
 
 @torch.no_grad()
 def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"), lights=None, shadows=False, bg=None, batch=1,
-                   aa_samples=1, aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, **kw):
+                   aa_samples=1, aa_adaptive=True, aa_plane=0.5, aa_cos=0.5, aa_pattern=None, batch_secondary=False,
+                   max_secondary_rays=None, **kw):
     """render_frames by ray / surface intersection (oi_amd.trace.render_surface) instead of the volume render: one frame per
     (z, b2w) pair under ONE light (`lights`: a Light, default the trained one).  -> {key: (n, C, H, W)} for keys of
     SURFACE_KEYS ("visibility" needs shadows=True, "ambient_occlusion" ao_samples > 0).  Keyword arguments: render_surface's
@@ -163,12 +164,19 @@ def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"),
     oi_amd.trace.render_surfaces in groups of E (the last group may be smaller) -- one chain of trace steps and one full MLP
     pass per group instead of per frame; shadow and occlusion rays are still traced per frame.  The
     frames are those of batch=1.
+    batch_secondary=True (with batch > 1): each group's shadow rays, occlusion rays and shade go through ONE
+    chain each as well (render_surfaces' keyword, as max_secondary_rays, the cap on the rays of one such chain); the frames are
+    the same, bit for bit.
     aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern: render_surface's anti-aliasing, with the keys
     "coverage" and "aa_mask"; it is per view, so aa_samples > 1 needs batch=1."""
     from . import lib, trace
     from .relight import Light
     if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= int(batch) <= lib.TRACE_BATCH_MAX_ELEMS:
         raise ValueError(f"surface_frames: batch={batch!r} (an integer, 1 <= batch <= {lib.TRACE_BATCH_MAX_ELEMS})")
+    trace._check_batch_secondary(batch_secondary, max_secondary_rays, "surface_frames")
+    if batch_secondary and batch == 1:
+        raise ValueError("surface_frames: batch_secondary=True with batch=1 (the secondary rays are batched over the views of one "
+                         "primary trace: batch > 1)")
     aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "surface_frames")
     if aa is not None and batch > 1:
         raise ValueError(f"surface_frames: aa_samples={aa_samples!r} with batch={batch!r} (the batched trace has no anti-aliasing "
@@ -190,7 +198,8 @@ def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"),
         for a in range(0, len(pairs), int(batch)):
             group = pairs[a:a + int(batch)]
             for out in trace.render_surfaces(gen, [z for z, _ in group], [b for _, b in group], lights=lights, shadows=shadows,
-                                             bg=bg, **kw):
+                                             bg=bg, batch_secondary=bool(batch_secondary),
+                                             max_secondary_rays=max_secondary_rays, **kw):
                 for k in keys:
                     frames[k].append(out[k][0])
         return {k: torch.stack(v) for k, v in frames.items()}

@@ -181,6 +181,8 @@ class SceneOcclusionParams(ctypes.Structure):
 GROUND_FLOATS = 12
 GROUND_RAYS_CAP, GROUND_RAYS_HEMISPHERE, GROUND_RAYS_LOCAL = 0, 1, 2
 
+# include/oi_occlusion_batch.h
+OCCLUSION_BATCH_SHADOW, OCCLUSION_BATCH_CAP, OCCLUSION_BATCH_HEMISPHERE, OCCLUSION_BATCH_LOCAL = 0, 1, 2, 3
 
 
 SIGS = {
@@ -424,6 +426,13 @@ SIGS = {
         "oi_ground_resolve": (_i, [_vp, _i, _ll, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
         "oi_ground_shade": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _ll, _vp, _i, _i] + [_vp] * 12),
         "oi_ground_occlude": (_i, [_P(TraceBatch), _vp, _vp, _vp, _ll, _f, _vp]),
+    },
+    # include/oi_occlusion_batch.h: the secondary rays and the shade of E views in one chain (an addition to oi_trace_batch.h,
+    # oi_occlusion.h and oi_local_light.h; no struct of its own: the batch, oi_occlusion.h's shade parameters, plain arguments)
+    "oi_occlusion_batch.h": {
+        "oi_occlusion_batch_begin": (_i, [_P(TraceBatch), _i] + [_vp] * 4 + [_ll, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _u, _vp]),
+        "oi_occlusion_batch_resolve": (_i, [_vp, _vp, _vp, _i, _ll, _ll, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+        "oi_surface_shade_batch": (_i, [_P(SurfaceAoParams), _i, _ll, _i, _vp]),
     },
 }
 

@@ -1061,6 +1061,97 @@ def surface_shade_local(rays_o, rays_d, t, status, hit_slot, hit_points, grad, r
 
 
 # ------------------------------------------------------------------------------------------
+# the secondary rays and the shade of E views in one chain (include/oi_occlusion_batch.h); oi_amd.trace sequences these
+# ------------------------------------------------------------------------------------------
+
+def occlusion_batch_begin(sb, mode, hit_points, grad, hit_index, counts, n_pad, samples, j0, chunk, bias, seed=0, lights=None,
+                          radius=None, w2b=None, distance=None):
+    """sb: TraceBatchState of E views x L * chunk * n_pad rays (trace_batch_state_empty): the samples [j0, j0 + chunk) of
+    `samples` strata at every view's own hits.  mode: lib.OCCLUSION_BATCH_*.  hit_points, grad (E, n_pad, 3), hit_index (E, N)
+    int32 and counts (E, TRACE_COUNT_WORDS) int32 of the primary batch; lights (L, 16) -- LOCAL: (L, 20) --, radius (L,)
+    float32 for CAP, w2b (E, 4, 4); HEMISPHERE: distance instead, one set of rays."""
+    what = "occlusion_batch_begin"
+    ambient = mode == _l.OCCLUSION_BATCH_HEMISPHERE
+    if ambient == (distance is None) or ambient != (lights is None):
+        raise ValueError(f"{what}: give distance for the hemisphere, lights for every other mode")
+    if mode == _l.OCCLUSION_BATCH_LOCAL:
+        _check_local(what, lights)
+    if mode == _l.OCCLUSION_BATCH_CAP and (not torch.is_tensor(radius) or radius.dtype != torch.float32
+                                           or tuple(radius.shape) != (lights.shape[0],)):
+        raise ValueError(f"{what}: radius must be a float32 tensor of shape ({lights.shape[0]},), one per light")
+    if hit_index.dim() != 2 or hit_index.shape[0] != sb.E or tuple(counts.shape) != (sb.E, _l.TRACE_COUNT_WORDS):
+        raise ValueError(f"{what}: hit_index {tuple(hit_index.shape)}, counts {tuple(counts.shape)} for {sb.E} views")
+    if tuple(hit_points.shape) != (sb.E, int(n_pad), 3) or tuple(grad.shape) != (sb.E, int(n_pad), 3):
+        raise ValueError(f"{what}: hit_points {tuple(hit_points.shape)}, grad {tuple(grad.shape)}, expected {(sb.E, int(n_pad), 3)}")
+    if w2b is not None and w2b.numel() != sb.E * 16:
+        raise ValueError(f"{what}: w2b {tuple(w2b.shape)}, expected ({sb.E}, 4, 4)")
+    keep = [_c(x) for x in (lights, w2b)]
+    _l.check(_l.load().oi_occlusion_batch_begin(ctypes.byref(sb.c), int(mode), _p(hit_points), _p(grad), _ip(hit_index), _ip(counts),
+                                                hit_index.shape[1], int(n_pad), 1 if ambient else lights.shape[0], int(samples),
+                                                int(j0), int(chunk), _p(keep[0]), _p(radius), _p(keep[1]), float(bias),
+                                                float(distance) if ambient else 0.0, int(seed), _stream()), what)
+
+
+def occlusion_batch_maps(ref, E, L, N, n_pad):
+    """-> count (E, L, n_pad) int32 and out (E, L, N) float32 for occlusion_batch_resolve."""
+    # (int32 through _new, the same width: the tests' guarded arenas see it)
+    return _new(ref, E, L, n_pad).view(torch.int32), _new(ref, E, L, N)
+
+
+def occlusion_batch_resolve(status, hit_slot, counts, n_pad, L, samples, j0, chunk, count, out, last):
+    """Adds the chunk's rays that ended TRACE_MISS to count (E, L, n_pad) int32 (overwritten at j0 == 0); last: out (E, L, N) =
+    count / samples on the mask, 1 off it.  status (E, L * chunk * n_pad) uint8, hit_slot (E, N) int32."""
+    E, N = hit_slot.shape
+    if (tuple(status.shape) != (E, L * chunk * n_pad) or tuple(count.shape) != (E, L, n_pad) or tuple(out.shape) != (E, L, N)
+            or tuple(counts.shape) != (E, _l.TRACE_COUNT_WORDS)):
+        raise ValueError(f"occlusion_batch_resolve: status {tuple(status.shape)}, count {tuple(count.shape)}, out {tuple(out.shape)}, "
+                         f"counts {tuple(counts.shape)} for E={E}, N={N}, n_pad={n_pad}, L={L}, chunk={chunk}")
+    _l.check(_l.load().oi_occlusion_batch_resolve(_p(status), _ip(hit_slot), _ip(counts), int(E), int(N), int(n_pad), int(L),
+                                                  int(samples), int(j0), int(chunk), int(bool(last)), _ip(count), _p(out),
+                                                  _stream()), "oi_occlusion_batch_resolve")
+
+
+def surface_shade_batch(rays_o, rays_d, t, status, hit_slot, hit_points, grad, rgb, n_pad, w2b, lights=None, bg=None,
+                        visibility=None, ambient_occlusion=None, outputs=tuple(SURFACE_OUT) + ("image",)):
+    """surface_shade_ao -- under local lights (L, 20): surface_shade_local -- for E views in ONE launch
+    (oi_surface_shade_batch).  rays_o, rays_d (E, N, 3), t, status, hit_slot (E, N); hit_points, grad, rgb (E, n_pad, 3) (None
+    with n_pad == 0); w2b (E, 4, 4); visibility (E, L, N), ambient_occlusion (E, N) or None.  -> {name: (E, N) or (E, N, 3)}
+    for the names of SURFACE_OUT in `outputs`, and "image" (E, L, 3, N)."""
+    what = "surface_shade_batch"
+    E, N = t.shape
+    for name in outputs:
+        if name not in SURFACE_OUT and name != "image":
+            raise ValueError(f"{what}: unknown output {name!r} (one of {tuple(SURFACE_OUT) + ('image',)})")
+    nl = 0 if lights is None else lights.shape[0]
+    local = lights is not None and lights.shape[-1] == _l.LOCAL_LIGHT_FLOATS
+    floats = _l.LOCAL_LIGHT_FLOATS if local else _l.RELIGHT_LIGHT_FLOATS
+    if "image" in outputs and (nl < 1 or nl > _l.RELIGHT_MAX_LIGHTS or tuple(lights.shape[1:]) != (floats,)):
+        raise ValueError(f"{what}: lights {None if lights is None else tuple(lights.shape)}, expected (L, {floats}) with "
+                         f"1 <= L <= {_l.RELIGHT_MAX_LIGHTS}")
+    if visibility is not None and tuple(visibility.shape) != (E, nl, N):
+        raise ValueError(f"{what}: visibility {tuple(visibility.shape)}, expected {(E, nl, N)}")
+    if ambient_occlusion is not None and tuple(ambient_occlusion.shape) != (E, N):
+        raise ValueError(f"{what}: ambient_occlusion {tuple(ambient_occlusion.shape)}, expected {(E, N)}")
+    if w2b.numel() != E * 16 or (n_pad and any(tuple(x.shape) != (E, int(n_pad), 3) for x in (hit_points, grad, rgb))):
+        raise ValueError(f"{what}: w2b {tuple(w2b.shape)} or the hit arrays do not hold {E} views of n_pad={n_pad} points")
+    P = _l.SurfaceAoParams()
+    P.N, P.n_hit, P.L, res = N, int(n_pad), nl, {}
+    for name, sh in SURFACE_OUT.items():
+        if name in outputs:
+            res[name] = _new(t, E, N) if sh == (1,) else _new(t, E, N, 3)
+        setattr(P, name, _p(res.get(name)))
+    if "image" in outputs:
+        res["image"] = _new(t, E, nl, 3, N)
+    P.image = _p(res.get("image"))
+    keep = [_c(x) for x in (rays_o, rays_d, t, hit_points, grad, rgb, w2b, lights, bg, visibility, ambient_occlusion)]
+    (P.rays_o, P.rays_d, P.t, P.hit_points, P.grad, P.rgb, P.w2b, P.lights, P.bg, P.visibility,
+     P.ambient_occlusion) = (_p(x) for x in keep)
+    P.status, P.hit_slot = _p(status), _ip(hit_slot)
+    _l.check(_l.load().oi_surface_shade_batch(ctypes.byref(P), int(E), int(n_pad), int(local), _stream()), "oi_surface_shade_batch")
+    return res
+
+
+# ------------------------------------------------------------------------------------------
 # adaptive anti-aliasing of the traced surface (include/oi_aa.h); oi_amd.trace sequences these
 # ------------------------------------------------------------------------------------------
 

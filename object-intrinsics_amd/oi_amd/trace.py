@@ -167,6 +167,7 @@ class TraceResults(list):
     (counts[e][k]: rays of element e in flight before step k; live[k] their maximum)."""
     n_evals = n_steps = n_pad = 0
     hit_points_padded = counts = live = None
+    hit_index = hit_slot = None   # (E, N) int32, oi_trace_batch_finish's arrays: what the batched secondary rays read
     n_hit = ()
 
 
@@ -225,7 +226,7 @@ def _trace_batch(field, st, tol, omega, max_steps, readback):
     out = TraceResults(TraceResult(st.t[e], st.status[e], st.steps[e], hit_index[e, :n_hit[e]], total, k, padded[e, :n_hit[e]],
                                    hit_slot[e]) for e in range(st.E))
     out.n_evals, out.n_steps, out.n_pad, out.hit_points_padded, out.n_hit = st.E * total, k, n_pad, padded, tuple(n_hit)
-    out.counts, out.live = st.counts, st.live
+    out.counts, out.live, out.hit_index, out.hit_slot = st.counts, st.live, hit_index, hit_slot
     return out
 
 
@@ -672,18 +673,140 @@ def _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, b
     return res
 
 
+MAX_SECONDARY_RAYS = 1 << 24   # rays of one batch of secondary rays (oi_amd.scene.MAX_SHADOW_RAYS' value), counted as E_g * L * Sc * n_pad
+
+
+def _check_batch_secondary(batch_secondary, max_secondary_rays, what):
+    """-> the cap on the rays of one secondary batch (default MAX_SECONDARY_RAYS).  Both keywords are checked either way."""
+    if not isinstance(batch_secondary, (bool, np.bool_)):
+        raise ValueError(f"{what}: batch_secondary={batch_secondary!r} (True or False)")
+    if max_secondary_rays is None:
+        return MAX_SECONDARY_RAYS
+    if not _is_count(max_secondary_rays, 1, 1 << 62):
+        raise ValueError(f"{what}: max_secondary_rays={max_secondary_rays!r} (a positive integer, or None for {MAX_SECONDARY_RAYS})")
+    return int(max_secondary_rays)
+
+
+def plan_secondary(E, L, S, n_pad, max_secondary_rays, what="render_surfaces"):
+    """How E views' S samples per (light, hit slot) are cut into batches of at most max_secondary_rays rays (and below 2^31),
+    a batch of E_g views and Sc samples counted as E_g * L * Sc * n_pad.  A pure function.  Samples are split first: while one
+    sample of all views fits, every view is in one group and Sc is the largest number that fits; otherwise Sc = 1 and the
+    views are split into consecutive groups of the largest size that fits, which keep the batch's n_pad.  One sample of a
+    single view that does not fit is refused.  -> (groups [(e0, e1)], chunks [(j0, Sc)]); n_pad == 0: ([], [])."""
+    E, L, S, n_pad = int(E), int(L), int(S), int(n_pad)
+    if n_pad == 0:
+        return [], []
+    cap, per = min(int(max_secondary_rays), (1 << 31) - 1), L * n_pad
+    if per > cap:
+        raise ValueError(f"{what}: 1 view x {L} lights x {n_pad} hit slots = L * n_pad = {per} rays per sample of one view (at most "
+                         f"max_secondary_rays={max_secondary_rays} and below 2^31)")
+    group, chunk = (E, min(S, cap // (E * per))) if E * per <= cap else (cap // per, 1)
+    return ([(a, min(E, a + group)) for a in range(0, E, group)],
+            [(j0, min(chunk, S - j0)) for j0 in range(0, S, chunk)])
+
+
+def _secondary_batch(field, kw, bias, st, res, grad, w2b, mode, L, S, cap, seed=0, lights=None, radius=None, distance=None):
+    """One kind of secondary rays for all E views of a batched primary trace (include/oi_occlusion_batch.h): per group of
+    views and chunk of samples (plan_secondary) ONE chain -- begin, the batched march on the views' own fields, finish,
+    resolve.  st, res: the primary ops.TraceBatchState and its TraceResults; grad (E, n_pad, 3); w2b (E, 4, 4).  -> the map
+    (E, L, N), and per view the sdf evaluations of the chains in its segment, sum_k bound_k."""
+    import copy
+    E, N, n_pad = st.E, st.N, res.n_pad
+    groups, chunks = plan_secondary(E, L, S, n_pad, cap)
+    count, out = ops.occlusion_batch_maps(st.t, E, L, N, n_pad)
+    evals = [0] * E
+    for a, b in groups:
+        sub = field
+        if (a, b) != (0, E):   # the group's own FiLM rows
+            sub = copy.copy(field)
+            sub.B, sub.gamma, sub.beta = b - a, field.gamma[a:b], field.beta[a:b]
+        for j0, c in chunks:
+            sb = ops.trace_batch_state_empty(b - a, L * c * n_pad, st.t)
+            ops.occlusion_batch_begin(sb, mode, res.hit_points_padded[a:b], grad[a:b], res.hit_index[a:b], st.counts[a:b], n_pad, S,
+                                      j0, c, bias, seed, lights, radius, None if distance is not None else w2b[a:b], distance)
+            bound = int(sb.live[0].item())
+            if bound:
+                total, _ = _march_batch(sub, sb, *kw, bound=bound, anyhit=mode != _l.OCCLUSION_BATCH_SHADOW)
+                for e in range(a, b):
+                    evals[e] += total
+                ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
+            ops.occlusion_batch_resolve(sb.status, res.hit_slot[a:b], st.counts[a:b], n_pad, L, S, j0, c, count[a:b], out[a:b],
+                                        j0 + c == S)
+    return out, evals
+
+
+def _lit_batch(field, kw, bias, st, res, grad, rgb, w2b, H, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg,
+               cap, dev):
+    """_lit for all E views of a batched primary trace with ONE chain per stage: the visibility _visibility would choose per
+    view (hard shadows, soft shadows or local lights), the ambient occlusion, and one shade launch.  -> E dicts as _lit
+    returns them, shadow_trace / ao_trace None (the states are shared and chunked)."""
+    E, N, n_pad, L = st.E, st.N, res.n_pad, lt.shape[0]
+    S, A, seed = int(shadow_samples), int(ao_samples), int(seed)
+    if n_pad:   # both plans before anything is launched: a refusal leaves nothing half done
+        if shadows:
+            plan_secondary(E, L, S, n_pad, cap)
+        if A:
+            plan_secondary(E, 1, A, n_pad, cap)
+    vis = ao = None
+    shadow_evals, ao_evals = [0] * E, [0] * E
+    if shadows and n_pad == 0:
+        vis = torch.ones(E, L, N, device=dev)
+    elif shadows:
+        if _is_local(lt):
+            mode, extra = _l.OCCLUSION_BATCH_LOCAL, {}
+        elif radii is None:
+            mode, extra = _l.OCCLUSION_BATCH_SHADOW, {}
+        else:
+            mode, extra = _l.OCCLUSION_BATCH_CAP, dict(radius=torch.tensor(radii, dtype=torch.float32, device=dev))
+        vis, shadow_evals = _secondary_batch(field, kw, bias, st, res, grad, w2b, mode, L, S, cap, seed, lt, **extra)
+    if A and n_pad == 0:
+        ao = torch.ones(E, N, device=dev)
+    elif A:
+        ao, ao_evals = _secondary_batch(field, kw, bias, st, res, grad, w2b, _l.OCCLUSION_BATCH_HEMISPHERE, 1, A, cap, seed,
+                                        distance=float(ao_distance))
+        ao = ao.view(E, N)
+    out = ops.surface_shade_batch(st.rays_o, st.rays_d, st.t, st.status, res.hit_slot, res.hit_points_padded if n_pad else None,
+                                  grad, rgb, n_pad, w2b, lt, _bg(bg, dev), vis, ao)
+    K = 8   # the final status codes are below it
+    per_status = torch.bincount((st.status.long() + K * torch.arange(E, device=dev)[:, None]).view(-1), minlength=K * E).view(E, K).tolist()
+    results = []
+    for e in range(E):
+        r = {_MAP_NAMES[k]: v for k, v in _maps({k: v[e] for k, v in out.items() if k != "image"}, H, H).items()}
+        r["image"] = out["image"][e].view(-1, 3, H, H)
+        if shadows:
+            r["visibility"], r["shadow_trace"] = vis[e].view(-1, 1, H, H), None
+        if A:
+            r["ambient_occlusion"], r["ao_trace"] = ao[e].view(1, 1, H, H), None
+        stats = {name: int(per_status[e][code]) for code, name in _l.TRACE_STATUS_NAMES.items()}
+        stats.update(n_rays=N, n_evals=res[e].n_evals, n_steps=res[e].n_steps, shadow_evals=shadow_evals[e], ao_evals=ao_evals[e],
+                     secondary_batched=True)
+        r["stats"], r["trace"] = stats, res[e]
+        results.append(r)
+    return results
+
+
 @torch.no_grad()
 def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEFAULT_BIAS, shadow_samples=1, light_radius=0.0,
-                    ao_samples=0, ao_distance=0.5, seed=0, **trace_kw):
+                    ao_samples=0, ao_distance=0.5, seed=0, batch_secondary=False, max_secondary_rays=None, **trace_kw):
     """render_surface for E views at once (latents zs: E of (z_dim,) or (E, z_dim); poses b2ws: E of (4, 4)), 1 <= E <= 1024:
     ONE batched primary trace (sphere_trace_batch's chain of steps for all E * H * W rays) and ONE full MLP pass at the hits
     of all views, padded per view to the largest hit count.  Each view then is what render_surface holds -- slices of the
     batched arrays, its own w2b and FiLM rows -- and the light-dependent stages run per view, unchanged: the shading, and with
-    `shadows` / `ao_samples` the single-latent shadow and occlusion traces.  Batching those secondary rays is out of scope.
+    `shadows` / `ao_samples` the single-latent shadow and occlusion traces.
+    batch_secondary=True (include/oi_occlusion_batch.h) puts those stages into ONE chain each for all E
+    views: the visibility (hard shadows, soft shadows or local lights, as for a single view), the ambient occlusion, and one
+    shade launch; every view's rays are tested against its own field only.  The list of dicts and their keys are unchanged and
+    the maps are the same, bit for bit; shadow_trace and ao_trace are None (the ray state is shared and chunked), stats gains
+    secondary_batched=True, and shadow_evals / ao_evals are the sdf evaluations of the shared chains in the view's segment,
+    sum_k bound_k.  A batch of secondary rays holds at most max_secondary_rays rays (default MAX_SECONDARY_RAYS), counted as
+    E_g * L * Sc * n_pad: samples are split first; if one sample of all views does not fit, the views are split into consecutive
+    groups that keep the batch's n_pad; a single view that does not fit is refused before anything of these stages is launched.
+    No split changes a byte.  Without a hit in any view nothing of these stages is launched.
     The other arguments are render_surface's, the same for every view.  -> a list of E dicts as render_surface returns
     them; per view the maps are render_surface's own, bit for bit."""
     import copy
     dev = gen.it.device
+    cap = _check_batch_secondary(batch_secondary, max_secondary_rays, "render_surfaces")
     kw, bias = _Surface.params(bias, trace_kw, "render_surfaces")
     zs = _latents(zs, dev)
     E = zs.shape[0]
@@ -704,6 +827,9 @@ def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEF
     if res.n_pad:   # the full pass: the library's own, B = E elements of n_pad points
         _, grad, rgb = field.full(res.hit_points_padded.view(E * res.n_pad, 3))
         grad, rgb = grad.view(E, res.n_pad, 3), rgb.view(E, res.n_pad, 3)
+    if batch_secondary:
+        return _lit_batch(field, kw, bias, st, res, grad, rgb, torch.stack([v[4] for v in views]).contiguous(), gen.resolution, lt,
+                          radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, cap, dev)
     out = []
     for e in range(E):
         one = copy.copy(field)   # the element's own FiLM rows: the field of one latent

@@ -26,6 +26,16 @@ same call's unchanged per-frame loop (batch=1) in the same session, without and 
   evals_per_ray         sdf evaluations per primary ray (the stale and the shared bounds included)
   n_pad_over_mean_hit   points per element of the padded full pass over the mean hit count;  padding_waste  its unread share
 
+With --batch E[,E...] --batch-secondary the tool measures ONLY, per E and in one session, the walk through
+inference.surface_frames(batch=E) WITH secondary rays -- the --shadow-samples / --light-radius / --ao-samples given, one hard
+shadow ray without them -- once with the per-view chains (batch_secondary=False) and once with one chain per stage
+(batch_secondary=True), --iters walks after --warmup each:
+
+  loop_ms / batched_ms  ms per frame;   speedup  their ratio;   frames_equal  the two walks' frames, bit for bit
+  calls_per_frame       calls into the library per frame, both ways (a begin entry is two launches, every other entry one)
+  padding               E * n_pad / sum_e n_hit_e over the walk's groups: the hit slots the shared chains carry per real hit
+  shadow_evals, ao_evals  sdf evaluations of the secondary chains per frame, both ways
+
 With --local [--light-size R] [--light-distance D] the tool measures ONLY, per resolution, the frame under
 the trained directional light and under a local light (oi_amd.relight.LocalLight) D along the same direction from the object's
 centre: no shadows, one hard shadow ray, and 16 samples of a light with a size (angular radius 0.1 / a sphere of radius R),
@@ -61,6 +71,7 @@ ap.add_argument("--shadow-samples", type=int, default=1, help="shadow rays per l
 ap.add_argument("--light-radius", type=float, default=0.0, help="angular radius of the light, radians")
 ap.add_argument("--ao-samples", type=int, default=0, help="ambient-occlusion rays per visible point (0: none)")
 ap.add_argument("--batch", default="", help="frames per batched primary trace, e.g. 16,128: measure only the batched walk")
+ap.add_argument("--batch-secondary", action="store_true", help="with --batch: time the walk with secondary rays, per-view chains against one chain per stage, only")
 ap.add_argument("--local", action="store_true", help="time local lights (oi_amd.relight.LocalLight) beside the directional path, only")
 ap.add_argument("--light-size", type=float, default=0.15, help="with --local: radius of the sphere light of the sampled row")
 ap.add_argument("--light-distance", type=float, default=2.0, help="with --local: distance of the local light from the object's centre")
@@ -163,6 +174,63 @@ def batched_walk():
     return row
 
 
+def batched_secondary_walk():
+    """Per E of --batch: the walk with secondary rays through surface_frames(batch=E), per-view chains against one chain per
+    stage, in one session."""
+    from oi_amd import lib
+    gen, _, _ = setup(args.walk_res)
+    n = args.walk_frames
+    g = torch.Generator().manual_seed(0)
+    z0, z1 = torch.randn(64, generator=g), torch.randn(64, generator=g)
+    zs = [torch.lerp(z0, z1, i / max(1, n - 1)) for i in range(n)]
+    np.random.seed(0)
+    b2ws = list(torch.tensor(gen.pose_prior(n), dtype=torch.float32))
+    sec = dict(SOFT_KW or {"shadows": True}, **AO_KW)
+    keys = ("image", "mask", "normal_map", "depth", "visibility") + (("ambient_occlusion",) if AO_KW else ())
+    frames = lambda E, flag: inference.surface_frames(gen, zs, b2ws, keys=keys, batch=E, batch_secondary=flag, **sec)
+    L = lib.load()
+    entries = [name for table in lib.SIGS.values() for name in table]
+
+    def calls(fn):
+        """Calls into the library during fn(): every entry of the binding table counted on the handle, then put back."""
+        count, real = [0], {name: getattr(L, name) for name in entries}
+
+        def counted(f):
+            def call(*a):
+                count[0] += 1
+                return f(*a)
+            return call
+        for name, f in real.items():
+            setattr(L, name, counted(f))
+        try:
+            fn()
+        finally:
+            for name, f in real.items():
+                setattr(L, name, f)
+        return count[0]
+
+    row = {"res": args.walk_res, "frames": n, "secondary": {k: v for k, v in sec.items()}, "batch": {}}
+    for E in (int(e) for e in args.batch.split(",")):
+        ms = {flag: median_ms(lambda: frames(E, flag)) / n for flag in (False, True)}
+        a, b = frames(E, False), frames(E, True)
+        same = all(bool(((a[k] == b[k]) | (a[k].isnan() & b[k].isnan())).all()) for k in keys)
+        pad = hits = 0
+        evals = {False: [0, 0], True: [0, 0]}
+        for i in range(0, n, E):
+            for flag in (False, True):
+                res = trace.render_surfaces(gen, zs[i:i + E], b2ws[i:i + E], batch_secondary=flag, **sec)
+                evals[flag][0] += sum(o["stats"]["shadow_evals"] for o in res)
+                evals[flag][1] += sum(o["stats"]["ao_evals"] for o in res)
+            pad += len(res) * max(len(o["trace"].hit_index) for o in res)
+            hits += sum(len(o["trace"].hit_index) for o in res)
+        row["batch"][str(E)] = {"loop_ms": ms[False], "batched_ms": ms[True], "speedup": ms[False] / ms[True], "frames_equal": same,
+                                "calls_per_frame": {"loop": calls(lambda: frames(E, False)) / n, "batched": calls(lambda: frames(E, True)) / n},
+                                "padding": pad / max(1, hits),
+                                "shadow_evals": {"loop": evals[False][0] / n, "batched": evals[True][0] / n},
+                                "ao_evals": {"loop": evals[False][1] / n, "batched": evals[True][1] / n}}
+    return row
+
+
 def local_rows():
     """Per resolution: the frame under the trained directional light and under a local light at --light-distance along the same
     direction -- no shadows, one hard shadow ray, 16 samples of a light with a size (angular radius 0.1 / sphere radius
@@ -222,6 +290,12 @@ if args.local:
     with torch.no_grad():
         print(json.dumps({"tool": "bench_trace", "precision": args.precision, "iters": args.iters, "warmup": args.warmup,
                           "light_size": args.light_size, "light_distance": args.light_distance, "local": local_rows()}))
+    sys.exit(0)
+
+if args.batch and args.batch_secondary:
+    with torch.no_grad():
+        print(json.dumps({"tool": "bench_trace", "precision": args.precision, "iters": args.iters, "warmup": args.warmup,
+                          "batched_secondary_walk": batched_secondary_walk()}))
     sys.exit(0)
 
 if args.batch:

@@ -8,7 +8,7 @@ snapshot to the GPU box.  No torch headers are involved: the library has a plain
 include/oi_occlusion.h, include/oi_trace_batch.h, include/oi_envlight.h, include/oi_scene.h,
 include/oi_envgloss.h, include/oi_scene_light.h, include/oi_envbounce.h, include/oi_scene_gloss.h,
 include/oi_scene_bounce.h, include/oi_local_light.h, include/oi_mesh_tex.h, include/oi_aa.h,
-include/oi_scene_aa.h, include/oi_ground.h, include/oi_occlusion_batch.h)."""
+include/oi_scene_aa.h, include/oi_ground.h, include/oi_occlusion_batch.h, include/oi_raster.h)."""
 import hashlib
 import os
 import subprocess
@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "oi_amd")
 LIB = os.path.join(OUT_DIR, "liboi_hip.so")
 STAMP = os.path.join(OUT_DIR, ".liboi_hip.stamp")
-SOURCES = ["mlp.hip", "mlp_fwd3.hip", "mlp_fwd3b.hip", "color_head.hip", "render.hip", "disc.hip", "disc_small.hip", "disc_large.hip", "mlp_bwd.hip", "render_bwd.hip", "disc_bwd.hip", "optim.hip", "loss.hip", "mesh.hip", "relight.hip", "mesh_attr.hip", "trace.hip", "mesh_band.hip", "occlusion.hip", "trace_batch.hip", "envlight.hip", "scene.hip", "envgloss.hip", "scene_light.hip", "envbounce.hip", "scene_gloss.hip", "scene_bounce.hip", "local_light.hip", "mesh_tex.hip", "aa.hip", "scene_aa.hip", "ground.hip", "occlusion_batch.hip"]
+SOURCES = ["mlp.hip", "mlp_fwd3.hip", "mlp_fwd3b.hip", "color_head.hip", "render.hip", "disc.hip", "disc_small.hip", "disc_large.hip", "mlp_bwd.hip", "render_bwd.hip", "disc_bwd.hip", "optim.hip", "loss.hip", "mesh.hip", "relight.hip", "mesh_attr.hip", "trace.hip", "mesh_band.hip", "occlusion.hip", "trace_batch.hip", "envlight.hip", "scene.hip", "envgloss.hip", "scene_light.hip", "envbounce.hip", "scene_gloss.hip", "scene_bounce.hip", "local_light.hip", "mesh_tex.hip", "aa.hip", "scene_aa.hip", "ground.hip", "occlusion_batch.hip", "raster.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"] + os.environ.get("OI_FLAGS", "").split()
 # per-file extra flags.  mlp_fwd3.hip pins 256 parked values to the AGPR half of the register file; hipcc's default
 # (AGPR-form MFMA accumulators) would need 32 more AGPRs than exist, the VGPR form keeps the accumulators with the VALU.

@@ -242,16 +242,22 @@ class Generator(nn.Module):
             return {"z": data["z"]}
         return {"z": torch.randn(bs, self.z_dim, device=self.it.device)}
 
+    def crop_offsets(self, b2w):
+        """(x_offset, y_offset) (bs, 2) of the crops of the poses b2w (bs, 4, 4) on the device: generator.py:262-268 as
+        tensor arithmetic.  gen_rays_at's offsets for given poses, and oi_amd.raster's."""
+        R = self.resolution
+        b2c_t = torch.einsum("ij,bjk->bik", self.camera.w2c, b2w)[..., :3, 3]
+        cx = self.camera.cam_dist / b2c_t[..., 2] * b2c_t[..., 0] * R / 2 + 0.5 * self.scene_resolution
+        cy = self.camera.cam_dist / b2c_t[..., 2] * b2c_t[..., 1] * R / 2 + 0.5 * self.scene_resolution
+        return torch.stack([cx - R / 2, cy - R / 2], -1)
+
     def gen_rays_at(self, data, prior_info, with_light=False):
         """generator.py:255-279 + build_rays :317-333 + near_far_from_sphere :336-342 (one kernel).  `with_light`: the
         same launch also evaluates prior_info["light"].direction() (lighting.py:115-119) -> "light_dir"."""
         b2w, R = prior_info["b2w"], self.resolution
         xy = getattr(self, "_xy_off", None)
         if xy is None:  # poses given on the device (eval / inference): the reference's tensor arithmetic
-            b2c_t = torch.einsum("ij,bjk->bik", self.camera.w2c, b2w)[..., :3, 3]
-            cx = self.camera.cam_dist / b2c_t[..., 2] * b2c_t[..., 0] * R / 2 + 0.5 * self.scene_resolution
-            cy = self.camera.cam_dist / b2c_t[..., 2] * b2c_t[..., 1] * R / 2 + 0.5 * self.scene_resolution
-            xy = torch.stack([cx - R / 2, cy - R / 2], -1)
+            xy = self.crop_offsets(b2w)
         x_off, y_off = xy[:, 0], xy[:, 1]
         kinv = self._kinv(b2w.device)
         out = {"x_offset": x_off, "y_offset": y_off}

@@ -650,3 +650,68 @@ def export_mesh(gen, z, path, resolution=256, refine=2, light=None, threshold=0.
             torch.empty(0, mesh.RECORD_DTYPE.itemsize, dtype=torch.uint8, device=dev)
     mesh.save_ply(path, record, m.triangles)
     return m
+
+
+MESH_KEYS = ("image", "mask", "normal_map", "normal_object", "depth", "position", "albedo", "triangle", "barycentric")
+
+
+@torch.no_grad()
+def mesh_frames(gen, mesh, b2ws, keys=("image", "mask", "normal_map", "depth"), lights=None, bg=None, batch=16):
+    """The camera walk of a FIXED mesh (oi_amd.raster.render_mesh): one frame per pose of b2ws under
+    ONE light (`lights`: a Light or LocalLight, default the trained one), `batch` views per raster launch (1 .. 1024).  No
+    network is evaluated.  -> what surface_frames returns: {key: (n, C, H, W)} for keys of MESH_KEYS."""
+    from . import lib, raster
+    from .relight import Light, LocalLight
+    if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= int(batch) <= lib.RASTER_MAX_VIEWS:
+        raise ValueError(f"mesh_frames: batch={batch!r} (an integer, 1 <= batch <= {lib.RASTER_MAX_VIEWS})")
+    unknown = [k for k in keys if k not in MESH_KEYS]
+    if unknown:
+        raise ValueError(f"mesh_frames: keys {unknown} (one of {MESH_KEYS})")
+    if lights is not None and not isinstance(lights, (Light, LocalLight)):
+        raise TypeError("mesh_frames: one Light or LocalLight per walk")
+    poses = torch.stack([torch.as_tensor(b).reshape(4, 4) for b in b2ws])
+    frames = {k: [] for k in keys}
+    for a in range(0, len(poses), int(batch)):
+        for out in raster.render_mesh(gen, mesh, poses[a:a + int(batch)], lights=None if lights is None else [lights], bg=bg):
+            for k in keys:
+                frames[k].append(out[k][0])
+    return {k: torch.stack(v) for k, v in frames.items()}
+
+
+def _psnr(a, b):
+    """Peak signal-to-noise ratio in dB of two images with values in [0, 1] (inf when they are equal)."""
+    mse = float(((a.double() - b.double()) ** 2).mean())
+    return float("inf") if mse == 0 else -10.0 * math.log10(mse)
+
+
+@torch.no_grad()
+def mesh_fidelity(gen, z, mesh, b2ws, lights=None, source=None, **trace_kw):
+    """How close the rasterised mesh is to the traced surface it was extracted from, ON THE COMMON MASK (the silhouette is
+    mask_iou's; the PSNR figures here exclude it and do not compare with whole-image PSNR): oi_amd.raster.render_mesh against
+    oi_amd.trace.render_surface at the same latent z, poses b2ws ((4, 4) or (E, 4, 4)) and lights (no shadows; trace_kw:
+    render_surface's tol, omega, max_steps).  -> per view a dict: mask_iou; depth_rms, the RMS difference of the ray
+    parameter on the common mask; normal_angle, the mean angle in degrees between the object-space normals there;
+    albedo_psnr and image_psnr (the first light's image), both over the pixels of the common mask, so that they measure the
+    surface's attributes and not the silhouette, which mask_iou has; common, the pixels of the common mask.  A list of E
+    dicts for (E, 4, 4)."""
+    from . import raster, trace
+    poses = torch.as_tensor(b2ws)
+    single = poses.dim() == 2
+    poses = poses.reshape(-1, 4, 4)
+    got = raster.render_mesh(gen, mesh, poses, lights=lights, source=source)
+    out = []
+    for b2w, m in zip(poses, got):
+        s = trace.render_surface(gen, z, b2w, lights=lights, **trace_kw)
+        ma, mb = m["mask"][0, 0] > 0, s["mask"][0, 0] > 0
+        both = ma & mb
+        n = int(both.sum())
+        union = int((ma | mb).sum())
+        d = (m["depth"][0, 0][both] - s["depth"][0, 0][both]).double()
+        cos = (m["normal_object"][0][:, both] * s["normal_object"][0][:, both]).sum(0).clamp(-1, 1).double()
+        out.append({"mask_iou": n / union if union else 1.0,
+                    "depth_rms": float((d * d).mean().sqrt()) if n else 0.0,
+                    "normal_angle": float(torch.rad2deg(torch.acos(cos)).mean()) if n else 0.0,
+                    "albedo_psnr": _psnr(m["albedo"][0][:, both], s["albedo"][0][:, both]) if n else float("inf"),
+                    "image_psnr": _psnr(m["image"][0][:, both], s["image"][0][:, both]) if n else float("inf"),
+                    "common": n})
+    return out[0] if single else out

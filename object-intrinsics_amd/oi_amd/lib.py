@@ -184,6 +184,11 @@ GROUND_RAYS_CAP, GROUND_RAYS_HEMISPHERE, GROUND_RAYS_LOCAL = 0, 1, 2
 # include/oi_occlusion_batch.h
 OCCLUSION_BATCH_SHADOW, OCCLUSION_BATCH_CAP, OCCLUSION_BATCH_HEMISPHERE, OCCLUSION_BATCH_LOCAL = 0, 1, 2, 3
 
+# include/oi_raster.h
+RASTER_MAX_VIEWS, RASTER_MAX_RESOLUTION, RASTER_MAX_COORD = 1024, 16384, 1 << 22
+RASTER_DROPPED, RASTER_EMPTY, RASTER_SMALL, RASTER_LARGE = 0, 1, 2, 3
+RASTER_VERTEX, RASTER_TEXTURE = 0, 1
+
 
 SIGS = {
     # include/oi_hip.h: the drop-in boundary, what replaces the reference's modules
@@ -433,6 +438,13 @@ SIGS = {
         "oi_occlusion_batch_begin": (_i, [_P(TraceBatch), _i] + [_vp] * 4 + [_ll, _ll, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _u, _vp]),
         "oi_occlusion_batch_resolve": (_i, [_vp, _vp, _vp, _i, _ll, _ll, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
         "oi_surface_shade_batch": (_i, [_P(SurfaceAoParams), _i, _ll, _i, _vp]),
+    },
+    # include/oi_raster.h: the mesh rasteriser, a G-buffer for oi_trace.h's shade from a triangle mesh (an addition to
+    # oi_trace.h and oi_mesh_tex.h; no struct of its own: plain arguments)
+    "oi_raster.h": {
+        "oi_raster_setup": (_i, [_vp] * 3 + [_i, _i, _vp, _vp, _ll, _ll, _f, _ll] + [_vp] * 7),
+        "oi_raster_fill": (_i, [_vp] * 3 + [_i, _i, _vp, _vp, _ll, _ll] + [_vp] * 7),
+        "oi_raster_resolve": (_i, [_vp] * 3 + [_i, _i, _vp, _vp, _ll, _ll, _vp, _i, _vp, _vp, _vp, _i, _i] + [_vp] * 15),
     },
 }
 

@@ -589,3 +589,110 @@ def save_obj(path, textured_mesh, light_map=None):
         fh.write(f"newmtl intrinsic\nKd 1 1 1\nmap_Kd {stem}_albedo.png\nnorm {stem}_normal.png\n")
     save_png(png_a, tm.albedo_map if light_map is None else light_map)
     save_png(png_n, tm.normal_map)
+
+
+def load_png(path):
+    """The (H, W, 3) uint8 numpy image of a PNG as save_png writes it: 8-bit RGB, non-interlaced, filter type 0 on every row,
+    with zlib and struct alone.  Anything else -- another bit depth or colour type, an interlaced image, a filtered row, a
+    damaged chunk -- is refused by name."""
+    import struct
+    import zlib
+    with open(path, "rb") as fh:
+        data = fh.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"load_png: {path!r} is not a PNG file")
+    at, head, idat, ended = 8, None, b"", False
+    while at + 12 <= len(data) and not ended:
+        n, tag = struct.unpack(">I4s", data[at:at + 8])
+        body = data[at + 8:at + 8 + n]
+        if len(body) != n or at + 12 + n > len(data) or struct.unpack(">I", data[at + 8 + n:at + 12 + n])[0] != zlib.crc32(tag + body) & 0xffffffff:
+            raise ValueError(f"load_png: {path!r}: chunk {tag!r} is truncated or fails its CRC")
+        if tag == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat += body
+        elif tag == b"IEND":
+            ended = True
+        elif not tag[:1].islower():   # (an ancillary chunk may be skipped, a critical one may not)
+            raise ValueError(f"load_png: {path!r}: critical chunk {tag!r} is not supported")
+        at += 12 + n
+    if head is None or not ended:
+        raise ValueError(f"load_png: {path!r} has no IHDR or no IEND chunk")
+    W, H, depth, colour, comp, filt, interlace = head
+    if depth != 8:
+        raise ValueError(f"load_png: {path!r} has bit depth {depth} (8-bit only)")
+    if colour != 2:
+        raise ValueError(f"load_png: {path!r} has colour type {colour} (2, RGB, only)")
+    if interlace != 0:
+        raise ValueError(f"load_png: {path!r} is interlaced (non-interlaced only)")
+    if comp != 0 or filt != 0 or W < 1 or H < 1:
+        raise ValueError(f"load_png: {path!r}: compression {comp}, filter method {filt}, size {W} x {H}")
+    raw = zlib.decompress(idat)
+    if len(raw) != H * (1 + 3 * W):
+        raise ValueError(f"load_png: {path!r} holds {len(raw)} bytes, {H * (1 + 3 * W)} expected for {W} x {H} RGB")
+    rows = np.frombuffer(raw, dtype=np.uint8).reshape(H, 1 + 3 * W)
+    if rows[:, 0].any():
+        raise ValueError(f"load_png: {path!r}: row filter type {int(rows[:, 0].max())} (save_png writes type 0 on every row)")
+    return rows[:, 1:].reshape(H, W, 3).copy()
+
+
+def load_obj(path, device=None):
+    """The TexturedMesh of the four files save_obj writes, and only those: <stem>.obj with mtllib, usemtl, v, vn, vt and
+    f a/ta/a b/tb/b c/tc/c (1-based; the normal's index is the vertex's), <stem>.mtl with newmtl, Kd, map_Kd and norm, and the
+    two PNGs (load_png), next to the OBJ.  Any other statement or face form is refused by name.  -> TexturedMesh on `device`
+    (default cuda when there is one): mesh.positions, mesh.normals (V, 3), mesh.triangles (F, 3) int32, uv (F, 3, 2),
+    albedo_map, normal_map (H, W, 3) uint8, size (W, H); what a file does not hold is None (mesh.albedo, residual, flags, the
+    texel size, texel_flags, texel_residual)."""
+    import os
+    obj = obj_file_names(path)[0]
+    dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+    v, vn, vt, faces, mtllib = [], [], [], [], None
+    with open(obj) as fh:
+        for no, line in enumerate(fh, 1):
+            w = line.split()
+            if not w or w[0].startswith("#"):
+                continue
+            if w[0] == "mtllib" and len(w) == 2:
+                mtllib = w[1]
+            elif w[0] == "usemtl" and len(w) == 2:
+                pass
+            elif w[0] in ("v", "vn") and len(w) == 4:
+                (v if w[0] == "v" else vn).append([float(x) for x in w[1:]])
+            elif w[0] == "vt" and len(w) == 3:
+                vt.append([float(x) for x in w[1:]])
+            elif w[0] == "f" and len(w) == 4:
+                c = [x.split("/") for x in w[1:]]
+                if any(len(x) != 3 or x[0] != x[2] or not (x[0].isdigit() and x[1].isdigit()) for x in c):
+                    raise ValueError(f"load_obj: {obj}:{no}: face {line.strip()!r} (only v/vt/vn corners with vn == v)")
+                faces.append([[int(x[0]) - 1, int(x[1]) - 1] for x in c])
+            else:
+                raise ValueError(f"load_obj: {obj}:{no}: unsupported statement {line.strip()!r}")
+    if mtllib is None:
+        raise ValueError(f"load_obj: {obj} names no material library (mtllib)")
+    maps = {}
+    folder = os.path.dirname(obj)
+    with open(os.path.join(folder, mtllib)) as fh:
+        for no, line in enumerate(fh, 1):
+            w = line.split()
+            if not w or w[0].startswith("#") or w[0] in ("newmtl", "Kd"):
+                continue
+            if w[0] in ("map_Kd", "norm") and len(w) == 2:
+                maps[w[0]] = w[1]
+            else:
+                raise ValueError(f"load_obj: {mtllib}:{no}: unsupported statement {line.strip()!r}")
+    if set(maps) != {"map_Kd", "norm"}:
+        raise ValueError(f"load_obj: {mtllib} must name map_Kd and norm, has {sorted(maps)}")
+    albedo, normal = (load_png(os.path.join(folder, maps[k])) for k in ("map_Kd", "norm"))
+    if albedo.shape != normal.shape:
+        raise ValueError(f"load_obj: the maps differ in size: {albedo.shape[:2]} and {normal.shape[:2]}")
+    if len(vn) != len(v):
+        raise ValueError(f"load_obj: {len(v)} vertices but {len(vn)} normals")
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3, 2)
+    if len(f) and (f.min() < 0 or f[..., 0].max() >= len(v) or f[..., 1].max() >= len(vt)):
+        raise ValueError(f"load_obj: {obj}: a face index lies outside the {len(v)} vertices or {len(vt)} texture coordinates")
+    t32 = lambda a, *sh: torch.from_numpy(np.asarray(a, dtype=np.float32).reshape(*sh)).to(dev)
+    uv = np.asarray(vt, dtype=np.float32).reshape(-1, 2)[f[..., 1]] if len(f) else np.zeros((0, 3, 2), dtype=np.float32)
+    m = IntrinsicMesh(t32(v, -1, 3), t32(vn, -1, 3), None, None, None,
+                      triangles=torch.from_numpy(f[..., 0].astype(np.int32).reshape(-1, 3)).to(dev))
+    return TexturedMesh(m, t32(uv, -1, 3, 2), torch.from_numpy(albedo).to(dev), torch.from_numpy(normal).to(dev), None,
+                        (albedo.shape[1], albedo.shape[0]), None, None)

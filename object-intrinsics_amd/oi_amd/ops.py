@@ -1061,6 +1061,102 @@ def surface_shade_local(rays_o, rays_d, t, status, hit_slot, hit_points, grad, r
 
 
 # ------------------------------------------------------------------------------------------
+# the mesh rasteriser (include/oi_raster.h); oi_amd.raster.render_mesh sequences these in front of the shade above
+# ------------------------------------------------------------------------------------------
+
+def _ints(ref, *shape):
+    """int32 output through _new, the same width: the tests' guarded arenas see it."""
+    return _new(ref, *shape).view(torch.int32)
+
+
+def _raster_views(what, cams, R):
+    """cams: (c2b or b2c (E, 4, 4), kinv or K (3, 3), offs (E, 2) or None), float32 on the device.  -> E and the pointers."""
+    m, k, offs = cams
+    E = m.shape[0]
+    if tuple(m.shape) != (E, 4, 4) or tuple(k.shape) != (3, 3) or (offs is not None and tuple(offs.shape) != (E, 2)):
+        raise ValueError(f"{what}: camera matrices {tuple(m.shape)}, intrinsics {tuple(k.shape)}, offsets "
+                         f"{None if offs is None else tuple(offs.shape)}, expected (E, 4, 4), (3, 3) and (E, 2)")
+    return E, (_p(m), _p(k), _p(offs), int(R), E)
+
+
+def raster_setup(b2c, K, offs, R, pos, triangles, near, small_max):
+    """The setup stage for E views of R x R pixels (oi_raster_setup).  b2c (E, 4, 4), K (3, 3), offs (E, 2) or None; pos (V, 3)
+    float32, triangles (F, 3) int32.  -> dict of corners (E, F, 3, 2), bbox (E, F, 4) int32, cls (E, F) uint8, small_list,
+    large_list (E, F) int32 (their first counts[e] entries are written), counts (E, 2) int32.  F == 0 launches nothing."""
+    E, views = _raster_views("raster_setup", (b2c, K, offs), R)
+    V, F = pos.shape[0], triangles.shape[0]
+    out = {"corners": _ints(pos, E, F, 3, 2), "bbox": _ints(pos, E, F, 4),
+           "cls": torch.empty(E, F, dtype=torch.uint8, device=pos.device),
+           "small_list": torch.empty(E, F, dtype=torch.int32, device=pos.device),
+           "large_list": torch.empty(E, F, dtype=torch.int32, device=pos.device),
+           "counts": torch.zeros(E, 2, dtype=torch.int32, device=pos.device)}
+    _l.check(_l.load().oi_raster_setup(*views, _p(pos), _tris(triangles), V, F, float(near), int(small_max), _ip(out["corners"]),
+                                       _ip(out["bbox"]), _ip(out["cls"]), _ip(out["small_list"]), _ip(out["large_list"]),
+                                       _ip(out["counts"]), _stream()), "oi_raster_setup")
+    return out
+
+
+def raster_fill(c2b, kinv, offs, R, pos, triangles, setup):
+    """The visible triangle per pixel (oi_raster_fill) from raster_setup's dict.  -> zbuf (E, R * R) int64: the keys
+    (float_as_uint(t) << 32) | f as signed words, -1 where no triangle covers the centre."""
+    E, views = _raster_views("raster_fill", (c2b, kinv, offs), R)
+    zbuf = _new(pos, E, R * R, 2).view(torch.int64).view(E, R * R)
+    zbuf.fill_(-1)
+    _l.check(_l.load().oi_raster_fill(*views, _p(pos), _tris(triangles), pos.shape[0], triangles.shape[0], _ip(setup["corners"]),
+                                      _ip(setup["bbox"]), _ip(setup["small_list"]), _ip(setup["large_list"]), _ip(setup["counts"]),
+                                      _ip(zbuf), _stream()), "oi_raster_fill")
+    return zbuf
+
+
+RASTER_OUT = {"rays_o": (3,), "rays_d": (3,), "t": (), "status": (), "hit_slot": (), "hit_points": (3,), "grad": (3,),
+              "rgb": (3,), "triangle": (), "barycentric": (3,)}
+
+
+def raster_resolve(c2b, kinv, offs, R, pos, triangles, zbuf, vertex=None, texture=None, outputs=tuple(RASTER_OUT)):
+    """The ray state and the G-buffer of E rasterised views (oi_raster_resolve).  vertex: (normals, albedo) (V, 3) float32;
+    texture: (uv (F, 3, 2), albedo atlas, normal atlas), the atlases (H, W, 3) uint8 or float32; exactly one of the two.
+    -> {name: (E, N) or (E, N, 3)} for the names of RASTER_OUT in `outputs` (status uint8; hit_slot, triangle int32)."""
+    what = "raster_resolve"
+    E, views = _raster_views(what, (c2b, kinv, offs), R)
+    V, F, N = pos.shape[0], triangles.shape[0], R * R
+    if (vertex is None) == (texture is None):
+        raise ValueError(f"{what}: give exactly one of vertex=(normals, albedo) and texture=(uv, albedo atlas, normal atlas)")
+    for name in outputs:
+        if name not in RASTER_OUT:
+            raise ValueError(f"{what}: unknown output {name!r} (one of {tuple(RASTER_OUT)})")
+    if tuple(zbuf.shape) != (E, N) or zbuf.dtype != torch.int64:
+        raise ValueError(f"{what}: zbuf {tuple(zbuf.shape)} {zbuf.dtype}, expected {(E, N)} int64")
+    src = [None] * 9   # vnormal, valbedo, uv, W, H, albedo_u8, albedo_f32, normal_u8, normal_f32
+    src[3] = src[4] = 0
+    if vertex is not None:
+        vn, va = vertex
+        if tuple(vn.shape) != (V, 3) or tuple(va.shape) != (V, 3):
+            raise ValueError(f"{what}: vertex normals {tuple(vn.shape)}, albedo {tuple(va.shape)}, expected {(V, 3)}")
+        src[0], src[1], mode = _p(vn), _p(va), _l.RASTER_VERTEX
+    else:
+        uv, am, nm = texture
+        if tuple(uv.shape) != (F, 3, 2) or am.dim() != 3 or am.shape[2] != 3 or am.shape != nm.shape:
+            raise ValueError(f"{what}: uv {tuple(uv.shape)}, atlases {tuple(am.shape)} and {tuple(nm.shape)}, expected "
+                             f"{(F, 3, 2)} and two (H, W, 3)")
+        src[2], src[3], src[4], mode = _p(uv), am.shape[1], am.shape[0], _l.RASTER_TEXTURE
+        src[5 if am.dtype == torch.uint8 else 6] = _p(am)
+        src[7 if nm.dtype == torch.uint8 else 8] = _p(nm)
+    res = {}
+    for name, sh in RASTER_OUT.items():
+        if name not in outputs:
+            continue
+        if name == "status":
+            res[name] = torch.empty(E, N, dtype=torch.uint8, device=pos.device)
+        elif name in ("hit_slot", "triangle"):
+            res[name] = _ints(pos, E, N)
+        else:
+            res[name] = _new(pos, E, N, *sh)
+    _l.check(_l.load().oi_raster_resolve(*views, _p(pos), _tris(triangles), V, F, _ip(zbuf), mode, *src,
+                                         *(_ip(res.get(name)) for name in RASTER_OUT), _stream()), "oi_raster_resolve")
+    return res
+
+
+# ------------------------------------------------------------------------------------------
 # the secondary rays and the shade of E views in one chain (include/oi_occlusion_batch.h); oi_amd.trace sequences these
 # ------------------------------------------------------------------------------------------
 

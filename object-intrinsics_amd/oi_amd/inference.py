@@ -210,58 +210,100 @@ def surface_frames(gen, zs, b2ws, keys=("image", "mask", "normal_map", "depth"),
     return {k: torch.stack(v) for k, v in frames.items()}
 
 
-def _walk_frames(s, lt, step, shadows, visibility, bg, ao, ao_sub):
-    """The frames of a light walk or orbit over the traced view s (a trace._Surface) under the stacked lights lt: per `step`
-    lights one shadow trace, visibility(surface, a, b) -> (b - a, N), and one shade launch.  With an anti-aliasing stage the
-    sub-sample surface s.sub, traced once with the view, passes the same two per chunk (ao_sub: its ambient occlusion) and
-    oi_aa_resolve writes the frames.  -> image (n, 3, N), visibility (n, N) or None, the first chunk's depth and mask,
-    coverage (N,) or None."""
+def _walk_surface(gen, lt, what, traced, shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed):
+    """The prologue of the four light walks, after their lights are stacked (lt): eval mode, the weights checked, the
+    occlusion keywords checked for lt, then ONE trace, traced() -> the surface (a trace._Surface or a scene.SceneSurface).
+    -> (the surface, trace._checked_occlusion's tuple)."""
     from . import trace
-    n, dev = lt.shape[0], lt.device
-    image = torch.empty(n, 3, s.N, device=dev)
-    vis_all = torch.empty(n, s.N, device=dev) if shadows else None
+    gen.eval()
+    gen.renderer.pack.check()
+    occlusion = trace._checked_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt, what)
+    return traced(), occlusion
+
+
+def _walk_lights(gen, n_frames, axis):
+    """The trained light turning through 360 degrees about `axis`, frame 0 the light itself: -> (n_frames, 16) on the
+    generator's device."""
+    from .relight import Light, stack_lights
+    base = Light.from_module(gen.light)
+    dirs = light_walk_directions(base.direction, n_frames, axis)
+    return stack_lights([base] + [base.replace(direction=tuple(d)) for d in dirs[1:]], gen.it.device)
+
+
+def _scene_walk(gen, zs, b2ws, what, lights, shadows, bg, bias, window, max_shadow_rays, shadow_samples, light_radius, ao_samples,
+                ao_distance, seed, aa, ground, kw):
+    """scene_light_walk and scene_light_orbit but for their lights: lights() -> (the stacked lights, the result's own keys).
+    The lights are split so that one shadow batch holds at most max_shadow_rays rays, counted per light as instances x the
+    largest count of points among the scene, its sub-samples and its ground x the rays per light and point."""
+    from . import lib, scene, trace
+    scene.check_ground_keyword(ground, trace._check_aa(*aa, what), what)
+    lt, extra = lights()
+    limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
+    s, occlusion = _walk_surface(gen, lt, what,
+                                 lambda: scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, *aa, **kw),
+                                 shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed)
+    gs = None if ground is None else s.ground(ground)
+    radii, _, samples = occlusion[:3]
+    per_light = samples if radii is not None or trace._is_local(lt) else 1
+    # (one light above the limit is traced in chunks of samples; one sample above it is refused, naming the count)
+    step = limit // max(1, s.E * _most_points(s, gs) * per_light) if shadows else lib.RELIGHT_MAX_LIGHTS
+    return _light_walk(s, lt, occlusion, step, bg, limit, gs, **extra)
+
+
+def _most_points(s, gs=None):
+    """The largest count of visible points among the surface, its sub-sample surface and its ground: what bounds a shadow
+    trace's rays per light."""
+    return max(s.n_points, s.sub.n_points if s.sub is not None else 0, gs.n_g if gs is not None else 0)
+
+
+def _light_walk(s, lt, occlusion, step, bg, limit=None, ground=None, **extra):
+    """The frames of a light walk or orbit over the traced surface s (a trace._Surface or a scene.SceneSurface; trace._Stages)
+    under the stacked lights lt, and the dict the four walks return.  The ambient occlusion is traced once; per `step` lights
+    (at most 256) one shadow trace and one shade launch, which writes its frames in place.  With an anti-aliasing stage the
+    sub-sample surface s.sub, traced once with s, passes the same stages per chunk and s.resolve writes the frames.
+    limit: the cap on the rays of one shadow batch of a scene.  ground (a scene.GroundSurface): the plane
+    blocks the scene's ambient and directional rays, its own ambient occlusion is traced once, its shadows per chunk of
+    lights, and oi_ground_shade writes it into each chunk's frames (no anti-aliasing stage with a ground: the shaded planes
+    are views of the walk's frames)."""
+    from . import lib, trace
+    radii, shadows, samples, ao_samples, ao_distance, seed = occlusion
+    n, dev, M, H = lt.shape[0], lt.device, s.n_pixels, s.side
+    bgv, gkw = trace._bg(bg, dev), {} if ground is None else {"ground": ground}
+    keep = tuple(k for k in ("depth", "mask", "instance") if k in s.OUTPUTS)
+    image = torch.empty(n, 3, M, device=dev)
+    vis_all = torch.empty(n, M, device=dev) if shadows else None
+    matte = torch.empty(n, 3, M, device=dev) if ground is not None else None
+    ambient = lambda surface, **kw: surface.ambient(ao_samples, ao_distance, seed, limit, **kw) if ao_samples and surface is not None else None
+    ao, g_ao, ao_sub = ambient(s, **gkw), ambient(ground), ambient(s.sub)
     maps = coverage = None
+    step = max(1, min(lib.RELIGHT_MAX_LIGHTS, step))
     for a in range(0, n, step):
         b = min(n, a + step)
-        vis = visibility(s, a, b) if shadows else None
+        visible = lambda surface, **kw: surface.light_visibility(lt[a:b], None if radii is None else radii[a:b], samples, seed, limit,
+                                                                 **kw) if shadows and surface is not None else None
+        vis = visible(s, **gkw)
         if shadows:
             vis_all[a:b] = vis
         first = maps is None
-        out = s.shade(lt[a:b], trace._bg(bg, dev), vis, outputs=("depth", "mask", "image") if first else ("image",),
-                      image_out=image[a:b] if s.aa is None else None, ambient_occlusion=ao)
+        out = s._shade(lt[a:b], bgv, vis, keep + ("image",) if first else ("image",), image[a:b] if s.aa is None else None, ao)
         maps = maps or out
+        if ground is not None:
+            ground_mask, matte[a:b] = ground.shade(out, lt[a:b], visible(ground), g_ao)
         if s.aa is not None:
-            vis_sub = visibility(s.sub, a, b) if shadows and s.sub is not None else None
-            _, cov = trace._resolved(s, lt[a:b], trace._bg(bg, dev), {"image": out["image"], "mask": maps["mask"]}, vis_sub,
-                                     ao_sub, image_out=image[a:b], want_mask=first)
+            _, cov = s.resolve(lt[a:b], bgv, {"image": out["image"], "mask": maps["mask"]}, visible(s.sub), ao_sub, image_out=image[a:b],
+                               want_mask=first)
             coverage = cov if first else coverage
-    return image, vis_all, maps, coverage
-
-
-def _most_hits(s):
-    """The larger hit count of the view and of its sub-sample surface (at least 1): what bounds a shadow trace's rays per light."""
-    return max(1, s.n_hit, s.sub.n_hit if s.sub is not None else 0)
-
-
-def _walk_ambient(s, ao_samples, ao_distance, seed):
-    """-> the ambient occlusion of the view and of its sub-sample surface (each None when there is none to trace)."""
-    if not ao_samples:
-        return None, None
-    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed))
-    return ao, s.sub.ambient(int(ao_samples), float(ao_distance), int(seed)) if s.sub is not None else None
-
-
-def _walk_result(s, image, vis_all, maps, coverage, ao, **extra):
-    """The dict surface_light_walk and surface_light_orbit return."""
-    n, H = image.shape[0], s.H
-    res = {"image": image.view(n, 3, H, H), "mask": maps["mask"].view(1, 1, H, H), "depth": maps["depth"].view(1, 1, H, H), **extra,
-           "stats": s.stats()}
-    if vis_all is not None:
+    res = {"image": image.view(n, 3, H, H), **{k: maps[k].view(1, 1, H, H) for k in keep}, **extra, "stats": s.stats()}
+    if shadows:
         res["visibility"] = vis_all.view(n, 1, H, H)
-    if ao is not None:
+    if ao_samples:
         res["ambient_occlusion"] = ao.view(1, 1, H, H)
     if s.aa is not None:
         res["coverage"], res["aa_mask"] = coverage.view(1, 1, H, H), (s.edge_slot >= 0).float().view(1, 1, H, H)
+    if ground is not None:
+        res["ground_mask"], res["shadow_matte"] = ground_mask.view(1, 1, H, H), matte.view(n, 3, H, H)
+        for st in res["stats"]:
+            st.update(ground_pixels=ground.n_g, ground_evals=ground.evals)
     return res
 
 
@@ -280,85 +322,14 @@ def surface_light_walk(gen, z, b2w, n_frames=128, axis=(0, -1, 0), shadows=True,
     are traced ONCE for the walk, then shaded and resolved per chunk of lights; "coverage" and "aa_mask" (1, 1, H, W) are returned
     too, and stats gains aa_pixels, aa_rays, aa_evals."""
     from . import lib, trace
-    from .relight import Light, stack_lights
     aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "surface_light_walk")
-    base = Light.from_module(gen.light)
-    dirs = light_walk_directions(base.direction, n_frames, axis)
-    dev = gen.it.device
-    lt = stack_lights([base] + [base.replace(direction=tuple(d)) for d in dirs[1:]], dev)
-    gen.eval()
-    gen.renderer.pack.check()
-    radii = trace._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_frames,
-                                   "surface_light_walk")
-    s = trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw, aa=aa)
-    step = lib.RELIGHT_MAX_LIGHTS
-    if radii is not None:
-        step = max(1, min(step, OCCLUSION_MAX_RAYS // (int(shadow_samples) * _most_hits(s))))
-        radii = torch.tensor(radii, dtype=torch.float32, device=dev)
-    ao, ao_sub = _walk_ambient(s, ao_samples, ao_distance, seed)
-
-    def visibility(surface, a, b):
-        return trace._visibility(surface, lt[a:b], None if radii is None else radii[a:b], True, shadow_samples, seed)
-    return _walk_result(s, *_walk_frames(s, lt, step, shadows, visibility, bg, ao, ao_sub), ao)
-
-
-def _scene_walk(s, lt, shadows, per_light, visibility, bg, ao_samples, ao_distance, seed, limit, ground=None,
-                ground_visibility=None, **extra):
-    """The frames of a light walk or orbit over the traced scene s (a scene.SceneSurface) under the stacked lights lt, and the
-    dict scene_light_walk and scene_light_orbit return.  The lights are split so that one shadow batch of visibility(surface,
-    a, b) -> (b - a, S * S) holds at most `limit` rays, counted as per_light rays per light and visible point, and at most 256
-    lights; one shade launch per chunk.  With an anti-aliasing stage the sub-sample surface s.sub, traced once with the scene,
-    passes the same two per chunk, the chunks sized by the larger visible count of the two surfaces, and
-    oi_aa_resolve_strided writes the frames; ambient occlusion is traced once for each surface.
-    ground (a scene.Ground): the plane's ambient occlusion is traced once, its shadows per chunk of lights by
-    ground_visibility(ground surface, a, b) -> (b - a, n_g), and oi_ground_shade writes it into each chunk's frames; the chunks
-    are sized by the larger of the visible points and the ground points."""
-    from . import lib, trace
-    n, dev = lt.shape[0], lt.device
-    S, M = s.S, s.S * s.S
-    gs = None if ground is None else s.ground(ground)
-    image = torch.empty(n, 3, M, device=dev)
-    vis_all = torch.empty(n, M, device=dev) if shadows else None
-    step = lib.RELIGHT_MAX_LIGHTS
-    if shadows:   # (one light above the limit is traced in chunks of samples; one sample above it is refused, naming the count)
-        n_vis = max(sum(s.n_vis), sum(s.sub.n_vis) if s.sub is not None else 0, gs.n_g if gs is not None else 0)
-        step = max(1, min(step, limit // max(1, s.E * n_vis * per_light)))
-    gkw = {} if gs is None else {"ground": gs}
-    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed), limit, **gkw) if ao_samples else None
-    g_ao = gs.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples and gs is not None else None
-    matte = torch.empty(n, 3, M, device=dev) if gs is not None else None
-    ao_sub = s.sub.ambient(int(ao_samples), float(ao_distance), int(seed), limit) if ao_samples and s.sub is not None else None
-    maps = coverage = None
-    for a in range(0, n, step):
-        b = min(n, a + step)
-        vis = visibility(s, a, b) if shadows else None
-        if shadows:
-            vis_all[a:b] = vis
-        first = maps is None
-        out = s._shade(lt[a:b], trace._bg(bg, dev), vis, ("depth", "mask", "instance", "image") if first else ("image",),
-                       image[a:b] if s.aa is None else None, ao)
-        maps = maps or out
-        if gs is not None:   # (no anti-aliasing stage with a ground: `out` holds views of the walk's frames)
-            g_vis = ground_visibility(gs, a, b) if shadows else None
-            ground_mask, matte[a:b] = gs.shade(out, lt[a:b], g_vis, g_ao)
-        if s.aa is not None:
-            vis_sub = visibility(s.sub, a, b) if shadows and s.sub is not None else None
-            _, cov = s.resolved(lt[a:b], trace._bg(bg, dev), {"image": out["image"], "mask": maps["mask"]}, vis_sub, ao_sub,
-                                image_out=image[a:b], want_mask=first)
-            coverage = cov if first else coverage
-    res = {"image": image.view(n, 3, S, S), **extra, "stats": s.stats()}
-    res.update({k: maps[k].view(1, 1, S, S) for k in ("mask", "depth", "instance")})
-    if shadows:
-        res["visibility"] = vis_all.view(n, 1, S, S)
-    if ao_samples:
-        res["ambient_occlusion"] = ao.view(1, 1, S, S)
-    if s.aa is not None:
-        res["coverage"], res["aa_mask"] = coverage.view(1, 1, S, S), (s.edge_slot >= 0).float().view(1, 1, S, S)
-    if gs is not None:
-        res["ground_mask"], res["shadow_matte"] = ground_mask.view(1, 1, S, S), matte.view(n, 3, S, S)
-        for st in res["stats"]:
-            st.update(ground_pixels=gs.n_g, ground_evals=gs.evals)
-    return res
+    dev, lt = gen.it.device, _walk_lights(gen, n_frames, axis)
+    s, occlusion = _walk_surface(gen, lt, "surface_light_walk",
+                                 lambda: trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw, aa=aa),
+                                 shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed)
+    radii, _, samples = occlusion[:3]   # (radii None, hard shadows: one ray per light and hit, 256 lights per trace)
+    step = OCCLUSION_MAX_RAYS // (samples * max(1, _most_points(s))) if radii is not None else lib.RELIGHT_MAX_LIGHTS
+    return _light_walk(s, lt, occlusion, step, bg)
 
 
 @torch.no_grad()
@@ -381,31 +352,9 @@ def scene_light_walk(gen, zs, b2ws, n_frames=128, axis=(0, -1, 0), shadows=True,
     ground (a scene.Ground; not with aa_samples > 1): SceneSurface.shade's ground plane in every frame.  Its
     ambient occlusion is traced ONCE, its shadows per chunk of lights; "ground_mask" (1, 1, S, S) and "shadow_matte" (n_frames,
     3, S, S) are returned too, and stats gains ground_pixels and ground_evals."""
-    from . import scene, trace
-    from .relight import Light, stack_lights
-    aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "scene_light_walk")
-    scene.check_ground_keyword(ground, aa, "scene_light_walk")
-    base = Light.from_module(gen.light)
-    dirs = light_walk_directions(base.direction, n_frames, axis)
-    dev = gen.it.device
-    lt = stack_lights([base] + [base.replace(direction=tuple(d)) for d in dirs[1:]], dev)
-    gen.eval()
-    gen.renderer.pack.check()
-    radii = trace._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, n_frames, "scene_light_walk")
-    limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
-    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, aa_samples, aa_adaptive, aa_plane,
-                          aa_cos, aa_pattern, **kw)
-
-    gkw = {} if ground is None else {"ground": ground}
-
-    def visibility(surface, a, b):
-        return surface.visibility(lt[a:b], None if radii is None else radii[a:b], int(shadow_samples), int(seed), limit, **gkw)
-
-    def ground_visibility(gs, a, b):
-        return gs.visibility(lt[a:b], None if radii is None else radii[a:b], int(shadow_samples), int(seed), limit)
-    # (one light above the limit: SceneSurface.visibility refuses it, naming the count)
-    return _scene_walk(s, lt, shadows, int(shadow_samples) if radii is not None else 1, visibility, bg, ao_samples, ao_distance, seed,
-                       limit, **({} if ground is None else {"ground": ground, "ground_visibility": ground_visibility}))
+    return _scene_walk(gen, zs, b2ws, "scene_light_walk", lambda: (_walk_lights(gen, n_frames, axis), {}), shadows, bg, bias, window,
+                       max_shadow_rays, shadow_samples, light_radius, ao_samples, ao_distance, seed,
+                       (aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern), ground, kw)
 
 
 def light_orbit_positions(centre, radius, n_frames, axis=(0.0, -1.0, 0.0), height=0.0):
@@ -428,13 +377,14 @@ def light_orbit_positions(centre, radius, n_frames, axis=(0.0, -1.0, 0.0), heigh
                      for i in range(int(n_frames))])
 
 
-def _orbit_lights(light, n_frames, centre, radius, axis, height, what):
-    """The LocalLight `light` at each of light_orbit_positions' positions.  -> (positions, the lights)."""
-    from .relight import LocalLight
+def _orbit_lights(gen, light, n_frames, centre, radius, axis, height, what):
+    """The LocalLight `light` at each of light_orbit_positions' positions.  -> (the lights, stacked (n_frames, 20) on the
+    generator's device; the orbits' own result key: positions)."""
+    from .relight import LocalLight, stack_local_lights
     if not isinstance(light, LocalLight):
         raise TypeError(f"{what}: light must be a LocalLight (surface_light_walk turns a directional light)")
     pos = light_orbit_positions(centre, radius, n_frames, axis, height)
-    return pos, [light.replace(position=tuple(p)) for p in pos]
+    return stack_local_lights([light.replace(position=tuple(p)) for p in pos], gen.it.device), {"positions": pos}
 
 
 @torch.no_grad()
@@ -450,23 +400,14 @@ def surface_light_orbit(gen, z, b2w, light, n_frames=128, centre=(0.0, 0.0, 0.0)
     float64 numpy, "stats"}; with ao_samples also "ambient_occlusion" (1, 1, H, W), ONE trace for the orbit.
     aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern: as surface_light_walk's."""
     from . import lib, trace
-    from .relight import stack_local_lights
     aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "surface_light_orbit")
-    pos, lights = _orbit_lights(light, n_frames, centre, radius, axis, height, "surface_light_orbit")
     dev = gen.it.device
-    lt = stack_local_lights(lights, dev)
-    gen.eval()
-    gen.renderer.pack.check()
-    trace._check_occlusion(shadows, shadow_samples, 0.0, ao_samples, ao_distance, seed, n_frames, "surface_light_orbit", True)
-    s = trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw, aa=aa)
-    step = lib.RELIGHT_MAX_LIGHTS
-    if shadows:
-        step = max(1, min(step, OCCLUSION_MAX_RAYS // (int(shadow_samples) * _most_hits(s))))
-    ao, ao_sub = _walk_ambient(s, ao_samples, ao_distance, seed)
-
-    def visibility(surface, a, b):
-        return surface.local_visibility(lt[a:b], int(shadow_samples), int(seed))
-    return _walk_result(s, *_walk_frames(s, lt, step, shadows, visibility, bg, ao, ao_sub), ao, positions=pos)
+    lt, extra = _orbit_lights(gen, light, n_frames, centre, radius, axis, height, "surface_light_orbit")
+    s, occlusion = _walk_surface(gen, lt, "surface_light_orbit",
+                                 lambda: trace._Surface(gen, z.to(dev).reshape(1, -1), b2w, trace.DEFAULT_BIAS if bias is None else bias, kw, aa=aa),
+                                 shadows, shadow_samples, 0.0, ao_samples, ao_distance, seed)
+    step = OCCLUSION_MAX_RAYS // (occlusion[2] * max(1, _most_points(s))) if shadows else lib.RELIGHT_MAX_LIGHTS   # [2]: shadow_samples
+    return _light_walk(s, lt, occlusion, step, bg, **extra)
 
 
 @torch.no_grad()
@@ -483,27 +424,9 @@ def scene_light_orbit(gen, zs, b2ws, light, n_frames=128, centre=(0.0, 0.0, 0.0)
     "positions", "stats"}; with ao_samples also "ambient_occlusion" (1, 1, S, S).
     aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, ground: as scene_light_walk's (the ground catches the local light's
     shadows and blocks the instances' ambient rays; it does not block their local-light rays)."""
-    from . import scene, trace
-    from .relight import stack_local_lights
-    aa = trace._check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, "scene_light_orbit")
-    scene.check_ground_keyword(ground, aa, "scene_light_orbit")
-    pos, lights = _orbit_lights(light, n_frames, centre, radius, axis, height, "scene_light_orbit")
-    dev = gen.it.device
-    lt = stack_local_lights(lights, dev)
-    gen.eval()
-    gen.renderer.pack.check()
-    trace._check_occlusion(shadows, shadow_samples, 0.0, ao_samples, ao_distance, seed, n_frames, "scene_light_orbit", True)
-    limit = scene.MAX_SHADOW_RAYS if max_shadow_rays is None else int(max_shadow_rays)
-    s = scene.trace_scene(gen, zs, b2ws, window, trace.DEFAULT_BIAS if bias is None else bias, aa_samples, aa_adaptive, aa_plane,
-                          aa_cos, aa_pattern, **kw)
-
-    def visibility(surface, a, b):
-        return surface.local_visibility(lt[a:b], int(shadow_samples), int(seed), limit)
-
-    def ground_visibility(gs, a, b):
-        return gs.local_visibility(lt[a:b], int(shadow_samples), int(seed), limit)
-    return _scene_walk(s, lt, shadows, int(shadow_samples), visibility, bg, ao_samples, ao_distance, seed, limit, positions=pos,
-                       **({} if ground is None else {"ground": ground, "ground_visibility": ground_visibility}))
+    lights = lambda: _orbit_lights(gen, light, n_frames, centre, radius, axis, height, "scene_light_orbit")
+    return _scene_walk(gen, zs, b2ws, "scene_light_orbit", lights, shadows, bg, bias, window, max_shadow_rays, shadow_samples, 0.0,
+                       ao_samples, ao_distance, seed, (aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern), ground, kw)
 
 
 def env_walk_rotations(n_frames, axis=(0.0, 0.0, 1.0)):

@@ -172,7 +172,7 @@ def refuse_env_ground(ground, what):
                          "shaded by SceneSurface.shade under directional and local lights)")
 
 
-class GroundSurface:
+class GroundSurface(_t._Stages):
     """A Ground in one traced scene (SceneSurface.ground): record (12,) on the device; t (S * S,), the ground's ray parameter
     per scene pixel, NaN off the ground; n_g ground pixels, index (n_g,) int32 ascending, slot (S * S,) int32 (a pixel's
     position in index, -1 off the ground); evals: the sdf evaluations of its secondary rays so far."""
@@ -192,11 +192,8 @@ class GroundSurface:
         self.t, index, count = ops.ground_begin(s.c2w, s.kinv, s.S, self.record, s.owner, s.owner_ray if owned else None,
                                                 s.state.t if owned else None, s.window if owned else None, s.W, s.E)
         self.n_g = int(count.item())
-        # The compaction's order differs from run to run, and the pixel keys the samples: ascending order makes the frame a
-        # function of its arguments alone (as SceneSurface._antialias does for the flagged pixels).
-        self.index = torch.sort(index[:self.n_g]).values.contiguous()
         self.slot = torch.full((M,), -1, dtype=torch.int32, device=dev)
-        self.slot[self.index.long()] = torch.arange(self.n_g, dtype=torch.int32, device=dev)
+        self.index = _t._ascending(index, self.n_g, self.slot).contiguous()
 
     def _args(self):
         s = self.scene
@@ -208,22 +205,14 @@ class GroundSurface:
         s = self.scene
         L = 1 if lights is None else lights.shape[0]
         per = s.E * L * self.n_g
-        chunk = min(int(samples), min(int(max_shadow_rays), (1 << 31) - 1) // per)
-        if chunk < 1:
-            raise ValueError(f"{what}: {s.E} instances x {L} lights x {self.n_g} ground points = E * L * n_g = {per} rays per sample "
-                             f"(at most max_shadow_rays={max_shadow_rays} and below 2^31; inference.scene_light_walk splits the lights)")
+        chunks = _t.sample_chunks(samples, per, max_shadow_rays, what,
+                                  f"{s.E} instances x {L} lights x {self.n_g} ground points = E * L * n_g = {per} rays per sample")
         count, out = ops._new(self.record, L, self.n_g).view(torch.int32), ops._new(self.record, L, self.n_g)
-        for j0 in range(0, int(samples), chunk):
-            c = min(chunk, int(samples) - j0)
-            sb = ops.trace_batch_state_empty(s.E, L * c * self.n_g, self.record)
-            ops.ground_rays_begin(sb, *self._args(), s.w2b, s.bias, samples, j0, c, seed, lights, radius, distance)
-            bound = int(sb.live[0].item())
-            if bound:
-                total, _ = _t._march_batch(s.field, sb, *s.kw, bound=bound, anyhit=True)
-                self.evals += total
-                ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
-            ops.ground_resolve(sb.status, s.E, self.n_g, L, samples, j0, c, count, out, j0 + c == int(samples))
-            self.last = sb
+        evals, self.last = _t.sampled_trace(
+            s.field, s.kw, self.record, s.E, L * self.n_g, samples, chunks,
+            lambda sb, j0, c: ops.ground_rays_begin(sb, *self._args(), s.w2b, s.bias, samples, j0, c, seed, lights, radius, distance),
+            lambda sb, j0, c, last: ops.ground_resolve(sb.status, s.E, self.n_g, L, samples, j0, c, count, out, last))
+        self.evals += evals
         return out
 
     def visibility(self, lights, radius=None, samples=1, seed=0, max_shadow_rays=MAX_SHADOW_RAYS):
@@ -250,25 +239,10 @@ class GroundSurface:
             return torch.ones(0, device=self.record.device)
         return self._sampled("GroundSurface.ambient", samples, seed, max_shadow_rays, distance=float(distance)).view(self.n_g)
 
-    def occlusion(self, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays):
-        """shade's secondary rays of the ground points: -> (visibility (L, n_g) or None, ambient occlusion (n_g,) or None)."""
-        vis = None
-        if shadows and _t._is_local(lt):
-            vis = self.local_visibility(lt, int(shadow_samples), int(seed), max_shadow_rays)
-        elif shadows:
-            vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays)
-        ao = self.ambient(int(ao_samples), float(ao_distance), int(seed), max_shadow_rays) if ao_samples else None
-        return vis, ao
-
     def shade(self, maps, lt, vis=None, ao=None):
         """oi_ground_shade: the ground into `maps` (ops.GROUND_OUT's names), in place.  -> ground_mask (S * S,), shadow_matte (L,
         3, S * S)."""
         return ops.ground_shade(*self._args(), lt, {k: v for k, v in maps.items() if k in ops.GROUND_OUT}, vis, ao)
-
-    def shade_into(self, maps, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays):
-        """occlusion() and shade()."""
-        vis, ao = self.occlusion(lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays)
-        return self.shade(maps, lt, vis, ao)
 
 
 def composite_over(result, photo):
@@ -286,11 +260,14 @@ def composite_over(result, photo):
     return torch.where(mask > 0, image, photo * matte)
 
 
-class SceneSurface:
+class SceneSurface(_t._Stages):
     """One traced scene and what the light-dependent stages reuse: the batched state (rays, t, status per instance), the
     owner map, the visible hits of every instance and the gradient and albedo there.
     E instances, window W, scene resolution S; window (E, 2) int32; n_entered / n_hit / n_vis: per instance the rays
     entered, the hits and the hits that own their pixel; n_pad = max(n_vis); state: ops.TraceBatchState."""
+    OUTPUTS, AA_RESOLVE = ("depth", "position", "normal_world", "albedo", "mask", "instance", "image"), "aa_resolve_strided"
+    n_pixels, side, n_points = property(lambda self: self.S * self.S), property(lambda self: self.S), property(lambda self: sum(self.n_vis))
+    device = property(lambda self: self.b2w.device)
 
     def __init__(self, gen, zs, b2ws, window, bias, trace_kw, aa=None):
         kw, bias = _t._Surface.params(bias, trace_kw, "trace_scene")
@@ -380,19 +357,9 @@ class SceneSurface:
         self.edge_slot = torch.full((M,), -1, dtype=torch.int32, device=dev)
         if self.n_pad == 0:
             return
-        if aa.adaptive:
-            edge_index, edge_slot, count = ops.scene_aa_classify(self.owner, self.owner_ray, self.vis_slot, self.points, self.grad,
-                                                                 self.n_pad, self.S, aa.plane, aa.cos)
-            n_edge = int(count.item())
-            if n_edge:
-                # The compaction's order differs from run to run, and the virtual pixel keys the shadow and occlusion samples:
-                # the flagged pixels in ascending order make the frame a function of its arguments alone.
-                edge_index[:n_edge] = torch.sort(edge_index[:n_edge]).values
-                edge_slot[edge_index[:n_edge].long()] = torch.arange(n_edge, dtype=torch.int32, device=dev)
-        else:
-            edge_index = edge_slot = torch.arange(M, dtype=torch.int32, device=dev)
-            n_edge = M
-        self.edge_slot, self.n_edge = edge_slot, n_edge
+        edge_index, self.edge_slot, n_edge = _t._flagged(aa, M, dev, lambda: ops.scene_aa_classify(
+            self.owner, self.owner_ray, self.vis_slot, self.points, self.grad, self.n_pad, self.S, aa.plane, aa.cos))
+        self.n_edge = n_edge
         if n_edge == 0:
             return
         Q = virtual_image_size((aa.S - 1) * n_edge, self.E, "trace_scene")
@@ -441,36 +408,25 @@ class SceneSurface:
         are local records (L, 20) and the rays are aimed at them and end there (include/oi_local_light.h).  ground (a
         GroundSurface; caps and the hemisphere only): the plane blocks the owner's ray of every finished chunk
         (oi_ground_occlude) before its resolve.  -> (sdf evaluations per element, the last chunk's state)."""
-        L, n_vis = 1 if lights is None else lights.shape[0], sum(self.n_vis)
+        L, n_vis = 1 if lights is None else lights.shape[0], self.n_points
         per = self.E * L * n_vis
-        chunk = min(int(samples), min(int(max_shadow_rays), (1 << 31) - 1) // per)
-        if chunk < 1:
-            raise ValueError(f"{what}: {self.E} instances x {L} lights x {n_vis} visible points = {per} rays per sample (at most "
-                             f"max_shadow_rays={max_shadow_rays} and below 2^31; inference.scene_light_walk splits the lights)")
+        chunks = _t.sample_chunks(samples, per, max_shadow_rays, what,
+                                  f"{self.E} instances x {L} lights x {n_vis} visible points = {per} rays per sample")
         pos, nrm, elem = self.world_points()
         pixel = self.point_pixels()
-        evals, sb = 0, None
-        for j0 in range(0, int(samples), chunk):
-            c = min(chunk, int(samples) - j0)
-            sb = ops.trace_batch_state_empty(self.E, L * c * n_vis, pos)
-            if local:
-                ops.scene_local_light_begin(sb, self.points, self.grad, self.n_pad, self.offset, elem, pixel, pos, nrm, n_vis, self.w2b,
-                                            self.bias, samples, j0, c, lights, seed)
-            elif lobe is None:
-                ops.scene_occlusion_begin(sb, self.points, self.grad, self.n_pad, self.offset, elem, pixel, pos, nrm, n_vis, self.w2b,
-                                          self.bias, samples, j0, c, seed, lights, radius, distance)
-            else:
-                ops.scene_lobe_begin(sb, self.state.rays_o, self.vis_index, self.N, self.points, self.grad, self.n_pad, self.offset,
-                                     elem, pixel, pos, nrm, n_vis, self.w2b, self.bias, samples, j0, c, lobe, seed)
-            bound = int(sb.live[0].item())
-            if bound:
-                total, _ = _t._march_batch(self.field, sb, *self.kw, bound=bound, anyhit=anyhit)
-                evals += total
-                ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
-            if ground is not None:
+        points = (self.points, self.grad, self.n_pad, self.offset, elem, pixel, pos, nrm, n_vis, self.w2b, self.bias, samples)
+        if local:
+            begin = lambda sb, j0, c: ops.scene_local_light_begin(sb, *points, j0, c, lights, seed)
+        elif lobe is None:
+            begin = lambda sb, j0, c: ops.scene_occlusion_begin(sb, *points, j0, c, seed, lights, radius, distance)
+        else:
+            begin = lambda sb, j0, c: ops.scene_lobe_begin(sb, self.state.rays_o, self.vis_index, self.N, *points, j0, c, lobe, seed)
+        done = resolve
+        if ground is not None:
+            def done(sb, j0, c, last):
                 ops.ground_occlude(sb, ground.record, elem, self.b2w, n_vis, math.inf if distance is None else distance)
-            resolve(sb, j0, c, j0 + c == int(samples))
-        return evals, sb
+                resolve(sb, j0, c, last)
+        return _t.sampled_trace(self.field, self.kw, pos, self.E, L * n_vis, samples, chunks, begin, done, anyhit)
 
     def visibility(self, lights, radius=None, samples=1, seed=0, max_shadow_rays=MAX_SHADOW_RAYS, ground=None):
         """(L, S * S) visibility of `lights` (L, 16).  radius None (or all zero) and one sample: one shadow ray per light and
@@ -658,19 +614,19 @@ class SceneSurface:
             transfer, bounce = self.transfer_bounce(samples, seed, max_shadow_rays)
         else:
             transfer, bounce = self.transfer(samples, seed, max_shadow_rays), None
-        out = self._shade(None, None, None, ("depth", "position", "normal_world", "albedo", "mask", "instance"))
+        out = self._shade(None, None, outputs=self.OUTPUTS[:-1])
         if g_samples is None:
             return SceneTransfer(self, transfer, out, samples, bounce=bounce)
         vis = self.lobe_visibility(g_samples, shin, seed, max_shadow_rays) if g_samples else None
         return SceneTransfer(self, transfer, out, samples, g_samples, shin, spec, vis, self.reflection())
 
-    def _shade(self, lt, bg, vis, outputs, image_out=None, ao=None):
-        """ops.scene_shade on this scene (ao: ops.scene_shade_ao, the occlusion factor (S * S,) on the ambient term); without a
-        visible hit nothing is launched and every map is its off-mask value."""
+    def _shade(self, lt, bg, visibility=None, outputs=OUTPUTS, image_out=None, ao=None):
+        """ops.scene_shade on this scene (ao: ops.scene_shade_ao, the occlusion factor (S * S,) on the ambient
+        term); without a visible hit nothing is launched and every map is its off-mask value."""
         M, dev = self.S * self.S, lt.device if lt is not None else self.b2w.device
         if self.n_pad:
             args = (self.state, self.W, self.S, self.owner, self.owner_ray, self.vis_slot, self.points, self.grad, self.rgb, self.n_pad,
-                    self.w2b, self.b2w, lt, bg, vis)
+                    self.w2b, self.b2w, lt, bg, visibility)
             if lt is not None and _t._is_local(lt):   # local lights: their own kernel
                 return ops.scene_shade_local(*args, ao, outputs, image_out)
             return ops.scene_shade(*args, outputs, image_out) if ao is None else ops.scene_shade_ao(*args, ao, outputs, image_out)
@@ -716,63 +672,18 @@ class SceneSurface:
         dev = self.b2w.device
         gs = None if ground is None else self.ground(ground)
         lt = _t._stack_lights(self.gen, lights, dev, "SceneSurface.shade", "; inference.scene_light_walk splits larger sets")
-        local = _t._is_local(lt)
-        radii = _t._check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0],
-                                    "SceneSurface.shade", local)
-        vis, ao = self._occlusion(lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays, gs)
-        out = self._shade(lt, _t._bg(bg, dev), vis, ("depth", "position", "normal_world", "albedo", "mask", "instance", "image"), ao=ao)
+        occlusion = _t._checked_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt, "SceneSurface.shade")
         S = self.S
-        if gs is not None:
-            ground_mask, matte = gs.shade_into(out, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays)
-        res = {_MAP_NAMES[k]: v for k, v in _t._maps({k: v for k, v in out.items() if k != "image"}, S, S).items()}
-        res["image"] = out["image"].view(-1, 3, S, S)
-        if self.aa is not None:   # the sub-samples through the same stages, then the mean over each flagged pixel's samples
-            vis_sub = ao_sub = None
-            if self.sub is not None:
-                vis_sub, ao_sub = self.sub._occlusion(lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays)
-            image, coverage = self.resolved(lt, _t._bg(bg, dev), out, vis_sub, ao_sub, want_mask=True)
-            res["image"], res["coverage"] = image.view(-1, 3, S, S), coverage.view(1, 1, S, S)
-            res["aa_mask"] = (self.edge_slot >= 0).float().view(1, 1, S, S)
-        if shadows:
-            res["visibility"] = vis.view(-1, 1, S, S)
-        if ao_samples:
-            res["ambient_occlusion"] = ao.view(1, 1, S, S)
+
+        def grounded(planes):   # the ground's own secondary rays, and the plane into the shaded planes
+            ground_mask, matte = gs.shade(planes, lt, *_t._occlusion(gs, lt, *occlusion, max_shadow_rays))
+            return {"ground_mask": ground_mask.view(1, 1, S, S), "shadow_matte": matte.view(-1, 3, S, S)}
+        res = _t._lit_stages(self, lt, _t._bg(bg, dev), occlusion, max_shadow_rays, gs, None if gs is None else grounded)
         res["stats"] = self.stats()
         if gs is not None:
-            res["ground_mask"], res["shadow_matte"] = ground_mask.view(1, 1, S, S), matte.view(-1, 3, S, S)
             for st in res["stats"]:
                 st.update(ground_pixels=gs.n_g, ground_evals=gs.evals)
         return res
-
-    def _occlusion(self, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, max_shadow_rays, ground=None):
-        """shade's secondary rays on this surface: -> (visibility (L, S * S) or None, ambient occlusion (S * S,) or None).
-        ground (a GroundSurface): the plane blocks the ambient and the directional rays."""
-        vis = None
-        kw = {} if ground is None else {"ground": ground}
-        if shadows and _t._is_local(lt):
-            vis = self.local_visibility(lt, int(shadow_samples), int(seed), max_shadow_rays)
-        elif shadows:
-            vis = self.visibility(lt, radii, int(shadow_samples), int(seed), max_shadow_rays, **kw)
-        ao = self.ambient(int(ao_samples), float(ao_distance), int(seed), max_shadow_rays, **kw) if ao_samples else None
-        return vis, ao
-
-    def resolved(self, lt, bgv, centre, vis_sub, ao_sub, image_out=None, want_mask=False):
-        """The anti-aliased image of a scene traced with an anti-aliasing stage: the sub-sample surface shaded as the centres
-        were (under lt, with its own visibility and occlusion; off-surface samples carry bg) and oi_aa_resolve_strided over
-        centre["image"] (L, 3, S * S), the sub-samples' planes Q * Q apart.  -> image (L, 3, S * S) (written into image_out when
-        given), coverage (S * S,) or None (want_mask: the same mean over centre["mask"]).  Without a sub-sample surface the
-        resolve is a copy."""
-        L, M, sub = lt.shape[0], self.S * self.S, None
-        if self.sub is not None:
-            sub = self.sub._shade(lt, bgv, vis_sub, ("mask", "image") if want_mask else ("image",), ao=ao_sub)
-        image = ops.aa_resolve_strided(centre["image"].view(3 * L, M), None if sub is None else sub["image"].view(3 * L, -1),
-                                       self.edge_slot, self.n_edge, self.aa.S,
-                                       out=None if image_out is None else image_out.view(3 * L, M)).view(L, 3, M)
-        coverage = None
-        if want_mask:
-            coverage = ops.aa_resolve_strided(centre["mask"].view(1, M), None if sub is None else sub["mask"].view(1, -1),
-                                              self.edge_slot, self.n_edge, self.aa.S).view(M)
-        return image, coverage
 
     def stats(self):
         """Per instance: rays entered and culled, rays per status (culled rays are misses), hits, visible hits; sdf
@@ -795,10 +706,6 @@ class SceneSurface:
         return out
 
 
-_MAP_NAMES = {"depth": "depth", "position": "position", "normal_world": "normal_map", "albedo": "albedo", "mask": "mask",
-              "instance": "instance"}
-
-
 class SceneTransfer:
     """One traced scene and its SH transfer map: everything shade() needs, none of which depends on the light.
     scene: the SceneSurface; transfer (1, 9, S, S), world frame; maps: SceneSurface.shade's G-buffer maps (depth, position,
@@ -816,7 +723,7 @@ class SceneTransfer:
         self.transfer = transfer.view(1, _l.ENV_COEFFS, S, S)
         self._bounce = bounce                           # (3, 9, S * S), planar, or None: what oi_env_shade_bounce reads
         self.bounce = None if bounce is None else bounce.view(1, 3, _l.ENV_COEFFS, S, S)
-        self.maps = {_MAP_NAMES[k]: v for k, v in _t._maps(planes, S, S).items()}
+        self.maps = {_t._MAP_NAMES[k]: v for k, v in _t._maps(planes, S, S).items()}
         # oi_env_shade's view of the scene's planes: every scene pixel is a ray, the owned ones are hits at their own index
         M, dev = S * S, transfer.device
         on = planes["instance"] >= 0

@@ -295,8 +295,61 @@ def _check_aa(aa_samples, aa_adaptive, aa_plane, aa_cos, aa_pattern, what):
     return None if S == 1 else _AA(S, bool(aa_adaptive), float(aa_plane), float(aa_cos), offsets)
 
 
-class _Surface:
+def _ascending(index, n, slot):
+    """The compaction's order differs from run to run, and a compacted pixel's position keys its shadow and occlusion samples:
+    ascending order makes the frame a function of its arguments alone.  -> index[:n] sorted; slot[index[k]] = k is written."""
+    order = torch.sort(index[:n]).values
+    slot[order.long()] = torch.arange(n, dtype=torch.int32, device=slot.device)
+    return order
+
+
+def _flagged(aa, n_pixels, dev, classify):
+    """The pixels that get sub-samples: -> (edge_index, edge_slot, n_edge).  Adaptive: classify() -> (edge_index, edge_slot,
+    count) and ONE read-back of the count, the flagged pixels in ascending order; otherwise every pixel."""
+    if not aa.adaptive:
+        every = torch.arange(n_pixels, dtype=torch.int32, device=dev)
+        return every, every, n_pixels
+    edge_index, edge_slot, count = classify()
+    n_edge = int(count.item())
+    if n_edge:
+        edge_index[:n_edge] = _ascending(edge_index, n_edge, edge_slot)
+    return edge_index, edge_slot, n_edge
+
+
+class _Stages:
+    """What the light-dependent stages (_lit_stages, oi_amd.inference's light walks) read of a traced surface, the same for a
+    view (_Surface) and a scene (oi_amd.scene.SceneSurface): n_pixels, the pixels its maps cover, side x side; n_points, its
+    visible points; device; OUTPUTS, _shade's default; visibility / local_visibility / ambient, whose `limit` caps the rays
+    of one trace; _shade(lights, bg, visibility, outputs, image_out, ao); with an anti-aliasing stage aa,
+    sub (the sub-samples, one more surface of the same kind, or None), edge_slot, n_edge and AA_RESOLVE, the resolve entry
+    that reads sub's planes.  A scene's ground (oi_amd.scene.GroundSurface) has the visibility half."""
+
+    def light_visibility(self, lt, radii, samples, seed, limit=None, **ground):
+        """The visibility of the stacked lights lt, (L, pixels): local lights (their own size; a ground plane does not block
+        their rays), else caps of the angular radii `radii` (L,), None for the hard shadow ray."""
+        if _is_local(lt):
+            return self.local_visibility(lt, samples, seed, limit)
+        return self.visibility(lt, radii, samples, seed, limit, **ground)
+
+    def resolve(self, lt, bgv, centre, vis_sub, ao_sub, image_out=None, want_mask=False):
+        """The anti-aliased image of a surface with an anti-aliasing stage: the sub-sample surface shaded as the centres were
+        (under lt, with its own visibility and occlusion; off-surface samples carry bg) and the mean over each flagged pixel's
+        samples, centre["image"] (L, 3, pixels) elsewhere (AA_RESOLVE; without a sub-sample surface a copy).  -> image (L, 3,
+        pixels) (written into image_out when given), coverage (pixels,) or None (want_mask: the same mean over centre["mask"])."""
+        L, M, sub = lt.shape[0], self.n_pixels, None
+        if self.sub is not None:
+            sub = self.sub._shade(lt, bgv, vis_sub, ("mask", "image") if want_mask else ("image",), ao=ao_sub)
+        mean = lambda k, P, out=None: getattr(ops, self.AA_RESOLVE)(centre[k].view(P, M), None if sub is None else sub[k].view(P, -1),
+                                                                   self.edge_slot, self.n_edge, self.aa.S, out=out)
+        image = mean("image", 3 * L, None if image_out is None else image_out.view(3 * L, M)).view(L, 3, M)
+        return image, mean("mask", 1).view(M) if want_mask else None
+
+
+class _Surface(_Stages):
     """One traced view and everything the light-dependent stages reuse: the primary trace, the full MLP pass at its hits."""
+    OUTPUTS, AA_RESOLVE = tuple(ops.SURFACE_OUT) + ("image",), "aa_resolve"
+    n_pixels, side, n_points = property(lambda self: self.N), property(lambda self: self.H), property(lambda self: self.n_hit)
+    device = property(lambda self: self.ro.device)
 
     @staticmethod
     def params(bias, trace_kw, what="render_surface"):
@@ -350,18 +403,8 @@ class _Surface:
         MLP pass at their hits.  self.sub: the sub-sample rays as one more _Surface (ray (j - 1) * n_edge + e: sample j of
         flagged pixel e), which the light-dependent stages treat as they treat this one; None without a flagged pixel."""
         r, H = self.res, self.H
-        if aa.adaptive:
-            edge_index, edge_slot, count = ops.aa_classify(r.status, r.hit_slot, r.hit_points, self.grad, self.n_hit, H, H,
-                                                           aa.plane, aa.cos)
-            n_edge = int(count.item())
-            if n_edge:
-                # The compaction's order differs from run to run, and the sub-sample ray index keys the shadow and occlusion
-                # samples: the flagged pixels in ascending order make the frame a function of its arguments alone.
-                edge_index[:n_edge] = torch.sort(edge_index[:n_edge]).values
-                edge_slot[edge_index[:n_edge].long()] = torch.arange(n_edge, dtype=torch.int32, device=edge_slot.device)
-        else:
-            edge_index = edge_slot = torch.arange(self.N, dtype=torch.int32, device=self.ro.device)
-            n_edge = self.N
+        edge_index, edge_slot, n_edge = _flagged(aa, self.N, self.ro.device, lambda: ops.aa_classify(
+            r.status, r.hit_slot, r.hit_points, self.grad, self.n_hit, H, H, aa.plane, aa.cos))
         self.aa, self.edge_slot, self.n_edge = aa, edge_slot, n_edge
         if n_edge == 0:
             return
@@ -380,8 +423,8 @@ class _Surface:
         ops.trace_finish(st)
         return n_evals
 
-    def visibility(self, lights, radius=None, samples=1, seed=0):
-        """(L, N) visibility of `lights` (L, 16).  radius None and one sample: one shadow trace over all L x n_hit rays (0 or
+    def visibility(self, lights, radius=None, samples=1, seed=0, limit=None):
+        """(L, N) visibility of `lights` (L, 16) (limit: not read; a view's walks size their chunks of lights instead).  radius None and one sample: one shadow trace over all L x n_hit rays (0 or
         1 per pixel).  Otherwise radius (L,) holds the lights' angular radii and one any-hit trace runs over all
         L x samples x n_hit rays: the share of a pixel's samples that reach the light."""
         L = lights.shape[0]
@@ -402,7 +445,7 @@ class _Surface:
         self.shadow = st
         return ops.occlusion_resolve(st.status, self.res.hit_slot, self.N, self.n_hit, L, samples)
 
-    def local_visibility(self, lights, samples=1, seed=0):
+    def local_visibility(self, lights, samples=1, seed=0, limit=None):
         """(L, N) visibility of the local lights `lights` (L, 20) (include/oi_local_light.h): one any-hit trace over all
         L x samples x n_hit rays, each aimed at its light's sphere and ending there; the share of a pixel's samples that
         reach the light (0 or 1 for a point light with one sample)."""
@@ -416,7 +459,7 @@ class _Surface:
         self.shadow = st
         return ops.occlusion_resolve(st.status, self.res.hit_slot, self.N, self.n_hit, L, samples)
 
-    def ambient(self, samples, distance, seed=0):
+    def ambient(self, samples, distance, seed=0, limit=None):
         """(N,) ambient occlusion: the share of `samples` cosine-weighted hemisphere rays per visible point that leave the
         point's neighbourhood (`distance`) without meeting the surface; 1 off the mask."""
         if self.n_hit == 0:
@@ -483,17 +526,20 @@ class _Surface:
         self.glossy_state = st
         return ops.occlusion_resolve(st.status, self.res.hit_slot, self.N, self.n_hit, 1, samples).view(self.N)
 
-    def shade(self, lights, bg, visibility=None, outputs=tuple(ops.SURFACE_OUT) + ("image",), image_out=None,
-              ambient_occlusion=None):
+    def _shade(self, lights, bg, visibility=None, outputs=OUTPUTS, image_out=None, ao=None):
         r = self.res
         dummy = self.ro   # never read when n_hit == 0
         args = (self.ro, self.rd, r.t, r.status, r.hit_slot, r.hit_points if self.n_hit else dummy,
                 self.grad if self.n_hit else dummy, self.rgb if self.n_hit else dummy, self.n_hit, self.w2b, lights, bg, visibility)
         if lights is not None and _is_local(lights):   # local lights: their own kernel
-            return ops.surface_shade_local(*args, ambient_occlusion, outputs, image_out)
-        if ambient_occlusion is None:
+            return ops.surface_shade_local(*args, ao, outputs, image_out)
+        if ao is None:
             return ops.surface_shade(*args, outputs, image_out)
-        return ops.surface_shade_ao(*args, ambient_occlusion, outputs, image_out)
+        return ops.surface_shade_ao(*args, ao, outputs, image_out)
+
+    def shade(self, lights, bg, visibility=None, outputs=OUTPUTS, image_out=None, ambient_occlusion=None):
+        """_shade under the name and keywords a view's callers know (a scene's `shade` is its public entry)."""
+        return self._shade(lights, bg, visibility, outputs, image_out, ambient_occlusion)
 
     def stats(self):
         s = self.res.counts()
@@ -541,6 +587,15 @@ def _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_dista
     return np.broadcast_to(rad, (n_lights,)).tolist() if soft else None
 
 
+def _checked_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt, what):
+    """_check_occlusion for the stacked lights lt, and the checked values coerced ONCE for everything below: -> the occlusion
+    tuple (radii (L,) float32 on the lights' device or None, shadows, shadow_samples, ao_samples, ao_distance, seed)."""
+    radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], what, _is_local(lt))
+    if radii is not None:
+        radii = torch.tensor(radii, dtype=torch.float32, device=lt.device)
+    return radii, bool(shadows), int(shadow_samples), int(ao_samples), float(ao_distance), int(seed)
+
+
 def _bg(bg, dev):
     return None if bg is None else torch.as_tensor(bg, dtype=torch.float32).to(dev).reshape(3).contiguous()
 
@@ -576,7 +631,7 @@ def _maps(out, H, W):
 
 
 _MAP_NAMES = {"depth": "depth", "position": "position", "normal_world": "normal_map", "normal": "normal_object",
-              "albedo": "albedo", "mask": "mask"}
+              "albedo": "albedo", "mask": "mask", "instance": "instance"}   # (instance: a scene's)
 
 
 @torch.no_grad()
@@ -611,63 +666,60 @@ def render_surface(gen, z, b2w, lights=None, shadows=False, bg=None, bias=DEFAUL
     z = z.to(dev).reshape(1, -1)
     s = _Surface(gen, z, b2w, bias, trace_kw, aa=aa)
     lt = _stack_lights(gen, lights, dev, "render_surface", "; inference.surface_light_walk splits larger sets")
-    radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surface",
-                             _is_local(lt))
-    return _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev)
+    return _lit(s, lt, *_checked_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt, "render_surface"),
+                bg, dev)
 
 
-def _visibility(s, lt, radii, shadows, shadow_samples, seed):
-    """The (L, N) visibility of the lights lt at the surface s, or None without shadows.  radii: None for hard shadows, else
-    the (L,) angular radii on the device; local lights carry their own size."""
-    if not shadows:
-        return None
-    if _is_local(lt):
-        return s.local_visibility(lt, int(shadow_samples), int(seed))
-    return s.visibility(lt) if radii is None else s.visibility(lt, radii, int(shadow_samples), int(seed))
+def _occlusion(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, limit=None, **ground):
+    """The secondary rays of the light-dependent stages on s (a view, a scene, its sub-samples or its ground; _Stages):
+    -> (visibility (L, pixels) or None without shadows, ambient occlusion (pixels,) or None without ao_samples).  ground (a
+    scene's): the plane blocks the ambient and the directional rays."""
+    return (s.light_visibility(lt, radii, shadow_samples, seed, limit, **ground) if shadows else None,
+            s.ambient(ao_samples, ao_distance, seed, limit, **ground) if ao_samples else None)
 
 
-def _resolved(s, lt, bgv, centre, vis_sub, ao_sub, image_out=None, want_mask=False):
-    """The anti-aliased image of a view with an anti-aliasing stage: the sub-sample surface shaded as the centre was (under lt,
-    with its own visibility and occlusion) and oi_aa_resolve over centre["image"] (L, 3, N).  -> image (L, 3, N) (written into
-    image_out when given), coverage (N,) or None (want_mask: the same mean over centre["mask"])."""
-    L, sub = lt.shape[0], None
-    if s.sub is not None:
-        sub = s.sub.shade(lt, bgv, vis_sub, outputs=("mask", "image") if want_mask else ("image",), ambient_occlusion=ao_sub)
-    image = ops.aa_resolve(centre["image"].view(3 * L, s.N), None if sub is None else sub["image"].view(3 * L, -1), s.edge_slot,
-                           s.n_edge, s.aa.S, out=None if image_out is None else image_out.view(3 * L, s.N)).view(L, 3, s.N)
-    coverage = None
-    if want_mask:
-        coverage = ops.aa_resolve(centre["mask"].view(1, s.N), None if sub is None else sub["mask"].view(1, -1), s.edge_slot,
-                                  s.n_edge, s.aa.S).view(s.N)
-    return image, coverage
-
-
-def _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev):
-    """The light-dependent stages of one traced view (a _Surface) and render_surface's dict."""
-    if radii is not None:
-        radii = torch.tensor(radii, dtype=torch.float32, device=dev)
-    vis = _visibility(s, lt, radii, shadows, shadow_samples, seed)
-    ao = s.ambient(int(ao_samples), float(ao_distance), int(seed)) if ao_samples else None
-    out = s.shade(lt, _bg(bg, dev), vis, ambient_occlusion=ao)
-    H = s.H
+def _lit_stages(s, lt, bgv, occlusion, limit=None, ground=None, after_shade=None):
+    """The light-dependent stages of one traced surface s (a view or a scene; _Stages) under the stacked lights lt: occlusion
+    (_occlusion's radii .. seed), shade, the maps under their public names, and with an anti-aliasing stage the same on the
+    sub-samples and the mean over each flagged pixel's samples.  after_shade(planes): the caller's hook on the shaded planes
+    before they are named (a scene's ground writes itself into them), -> its own keys of the result.  -> the dict of maps, image, coverage / aa_mask,
+    visibility, ambient_occlusion that render_surface and SceneSurface.shade share."""
+    shadows, ao_samples = occlusion[1], occlusion[3]
+    vis, ao = _occlusion(s, lt, *occlusion, limit, **({} if ground is None else {"ground": ground}))
+    out = s._shade(lt, bgv, vis, ao=ao)
+    extra = {} if after_shade is None else after_shade(out)
+    H = s.side
     res = {_MAP_NAMES[k]: v for k, v in _maps({k: v for k, v in out.items() if k != "image"}, H, H).items()}
     res["image"] = out["image"].view(-1, 3, H, H)
     if s.aa is not None:   # the sub-samples through the same stages, then the mean over each flagged pixel's samples
-        vis_sub = ao_sub = None
-        if s.sub is not None:
-            vis_sub = _visibility(s.sub, lt, radii, shadows, shadow_samples, seed)
-            ao_sub = s.sub.ambient(int(ao_samples), float(ao_distance), int(seed)) if ao_samples else None
-        image, coverage = _resolved(s, lt, _bg(bg, dev), out, vis_sub, ao_sub, want_mask=True)
+        vis_sub, ao_sub = (None, None) if s.sub is None else _occlusion(s.sub, lt, *occlusion, limit)
+        image, coverage = s.resolve(lt, bgv, out, vis_sub, ao_sub, want_mask=True)
         res["image"], res["coverage"] = image.view(-1, 3, H, H), coverage.view(1, 1, H, H)
         res["aa_mask"] = (s.edge_slot >= 0).float().view(1, 1, H, H)
-        res["aa_trace"] = None if s.sub is None else s.sub.res
     if shadows:
         res["visibility"] = vis.view(-1, 1, H, H)
-        res["shadow_trace"] = s.shadow   # ops.TraceState of the L x n_hit shadow rays (ray l * n_hit + i), or None without a hit
-                                         # (soft shadows: L x shadow_samples x n_hit, ray (l * S + j) * n_hit + i)
     if ao_samples:
         res["ambient_occlusion"] = ao.view(1, 1, H, H)
-        res["ao_trace"] = s.ao           # ops.TraceState of the ao_samples x n_hit rays (ray j * n_hit + i), or None
+    res.update(extra)
+    return res
+
+
+def _lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev):
+    """The light-dependent stages of one traced view (a _Surface) and render_surface's dict: _lit_stages' and the view's own
+    ray states and statistics."""
+    if radii is not None:
+        radii = torch.as_tensor(radii, dtype=torch.float32, device=dev)
+    # each stage's ray state goes behind the map it made (the order of the keys is _lit_batch's):
+    # shadow_trace: ops.TraceState of the L x n_hit shadow rays (ray l * n_hit + i), or None without a hit (soft shadows: L x
+    # shadow_samples x n_hit, ray (l * S + j) * n_hit + i); ao_trace: of the ao_samples x n_hit rays (ray j * n_hit + i), or None
+    staged = _lit_stages(s, lt, _bg(bg, dev), (radii, shadows, shadow_samples, ao_samples, ao_distance, seed))
+    states = {"aa_mask": ("aa_trace", None if s.sub is None else s.sub.res), "visibility": ("shadow_trace", s.shadow),
+              "ambient_occlusion": ("ao_trace", s.ao)}
+    res = {}
+    for k, v in staged.items():
+        res[k] = v
+        if k in states:
+            res.update([states[k]])
     res["stats"] = s.stats()
     res["trace"] = s.res
     return res
@@ -697,19 +749,49 @@ def plan_secondary(E, L, S, n_pad, max_secondary_rays, what="render_surfaces"):
     if n_pad == 0:
         return [], []
     cap, per = min(int(max_secondary_rays), (1 << 31) - 1), L * n_pad
-    if per > cap:
-        raise ValueError(f"{what}: 1 view x {L} lights x {n_pad} hit slots = L * n_pad = {per} rays per sample of one view (at most "
-                         f"max_secondary_rays={max_secondary_rays} and below 2^31)")
-    group, chunk = (E, min(S, cap // (E * per))) if E * per <= cap else (cap // per, 1)
-    return ([(a, min(E, a + group)) for a in range(0, E, group)],
-            [(j0, min(chunk, S - j0)) for j0 in range(0, S, chunk)])
+    words = (what, f"1 view x {L} lights x {n_pad} hit slots = L * n_pad = {per} rays per sample of one view", "max_secondary_rays", "")
+    sample_chunks(1, per, max_secondary_rays, *words)   # one sample of a single view has to fit
+    if E * per <= cap:
+        group, chunks = E, sample_chunks(S, E * per, max_secondary_rays, *words)
+    else:
+        group, chunks = cap // per, [(j0, 1) for j0 in range(S)]
+    return [(a, min(E, a + group)) for a in range(0, E, group)], chunks
+
+
+def sample_chunks(samples, per, cap, what, rays, cap_name="max_shadow_rays", hint="; inference.scene_light_walk splits the lights"):
+    """The chunk rule of every sampled secondary trace: `samples` samples of `per` rays each, cut into chunks of Sc samples, Sc
+    the largest number for which Sc * per stays within `cap` and below 2^31.  A pure function.  -> [(j0, Sc)]: the chunk of
+    samples j0 .. j0 + Sc - 1 (the last one may be smaller).  One sample that does not fit is refused in the name of `what`;
+    rays: the sentence that says what `per` counts, cap_name and hint: how the cap is called and what else the caller may do."""
+    samples = int(samples)
+    chunk = min(samples, min(int(cap), (1 << 31) - 1) // per)
+    if chunk < 1:
+        raise ValueError(f"{what}: {rays} (at most {cap_name}={cap} and below 2^31{hint})")
+    return [(j0, min(chunk, samples - j0)) for j0 in range(0, samples, chunk)]
+
+
+def sampled_trace(field, kw, like, E, per, samples, chunks, begin, resolve, anyhit=True):
+    """The one chunked loop of sampled secondary rays on a batch of E elements: per chunk (j0, Sc) of sample_chunks a fresh state
+    of per * Sc rays per element (on like's device), begin(sb, j0, Sc), one read of the rays entered, the batched march
+    (anyhit: a ray ends at its first occluder), finish (in-flight rays -> LIMIT) and resolve(sb, j0, Sc, last), which
+    accumulates the chunk.  -> (sdf evaluations per element, the last chunk's state)."""
+    evals, sb = 0, None
+    for j0, c in chunks:
+        sb = ops.trace_batch_state_empty(E, per * c, like)
+        begin(sb, j0, c)
+        bound = int(sb.live[0].item())
+        if bound:
+            evals += _march_batch(field, sb, *kw, bound=bound, anyhit=anyhit)[0]
+            ops.trace_batch_finish(sb)
+        resolve(sb, j0, c, j0 + c == samples)
+    return evals, sb
 
 
 def _secondary_batch(field, kw, bias, st, res, grad, w2b, mode, L, S, cap, seed=0, lights=None, radius=None, distance=None):
     """One kind of secondary rays for all E views of a batched primary trace (include/oi_occlusion_batch.h): per group of
-    views and chunk of samples (plan_secondary) ONE chain -- begin, the batched march on the views' own fields, finish,
-    resolve.  st, res: the primary ops.TraceBatchState and its TraceResults; grad (E, n_pad, 3); w2b (E, 4, 4).  -> the map
-    (E, L, N), and per view the sdf evaluations of the chains in its segment, sum_k bound_k."""
+    views (plan_secondary) one sampled_trace on the views' own fields.  st, res: the primary ops.TraceBatchState and its
+    TraceResults; grad (E, n_pad, 3); w2b (E, 4, 4).  -> the map (E, L, N), and per view the sdf evaluations of the chains in
+    its segment, sum_k bound_k."""
     import copy
     E, N, n_pad = st.E, st.N, res.n_pad
     groups, chunks = plan_secondary(E, L, S, n_pad, cap)
@@ -720,28 +802,22 @@ def _secondary_batch(field, kw, bias, st, res, grad, w2b, mode, L, S, cap, seed=
         if (a, b) != (0, E):   # the group's own FiLM rows
             sub = copy.copy(field)
             sub.B, sub.gamma, sub.beta = b - a, field.gamma[a:b], field.beta[a:b]
-        for j0, c in chunks:
-            sb = ops.trace_batch_state_empty(b - a, L * c * n_pad, st.t)
-            ops.occlusion_batch_begin(sb, mode, res.hit_points_padded[a:b], grad[a:b], res.hit_index[a:b], st.counts[a:b], n_pad, S,
-                                      j0, c, bias, seed, lights, radius, None if distance is not None else w2b[a:b], distance)
-            bound = int(sb.live[0].item())
-            if bound:
-                total, _ = _march_batch(sub, sb, *kw, bound=bound, anyhit=mode != _l.OCCLUSION_BATCH_SHADOW)
-                for e in range(a, b):
-                    evals[e] += total
-                ops.trace_batch_finish(sb)   # in-flight rays -> LIMIT
-            ops.occlusion_batch_resolve(sb.status, res.hit_slot[a:b], st.counts[a:b], n_pad, L, S, j0, c, count[a:b], out[a:b],
-                                        j0 + c == S)
+        begin = lambda sb, j0, c: ops.occlusion_batch_begin(
+            sb, mode, res.hit_points_padded[a:b], grad[a:b], res.hit_index[a:b], st.counts[a:b], n_pad, S, j0, c, bias, seed, lights,
+            radius, None if distance is not None else w2b[a:b], distance)
+        resolve = lambda sb, j0, c, last: ops.occlusion_batch_resolve(sb.status, res.hit_slot[a:b], st.counts[a:b], n_pad, L, S, j0, c,
+                                                                      count[a:b], out[a:b], last)
+        evals[a:b] = [sampled_trace(sub, kw, st.t, b - a, L * n_pad, S, chunks, begin, resolve, mode != _l.OCCLUSION_BATCH_SHADOW)[0]] * (b - a)
     return out, evals
 
 
 def _lit_batch(field, kw, bias, st, res, grad, rgb, w2b, H, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg,
                cap, dev):
-    """_lit for all E views of a batched primary trace with ONE chain per stage: the visibility _visibility would choose per
+    """_lit for all E views of a batched primary trace with ONE chain per stage: the visibility light_visibility would choose per
     view (hard shadows, soft shadows or local lights), the ambient occlusion, and one shade launch.  -> E dicts as _lit
     returns them, shadow_trace / ao_trace None (the states are shared and chunked)."""
     E, N, n_pad, L = st.E, st.N, res.n_pad, lt.shape[0]
-    S, A, seed = int(shadow_samples), int(ao_samples), int(seed)
+    S, A = shadow_samples, ao_samples
     if n_pad:   # both plans before anything is launched: a refusal leaves nothing half done
         if shadows:
             plan_secondary(E, L, S, n_pad, cap)
@@ -757,13 +833,13 @@ def _lit_batch(field, kw, bias, st, res, grad, rgb, w2b, H, lt, radii, shadows, 
         elif radii is None:
             mode, extra = _l.OCCLUSION_BATCH_SHADOW, {}
         else:
-            mode, extra = _l.OCCLUSION_BATCH_CAP, dict(radius=torch.tensor(radii, dtype=torch.float32, device=dev))
+            mode, extra = _l.OCCLUSION_BATCH_CAP, dict(radius=radii)
         vis, shadow_evals = _secondary_batch(field, kw, bias, st, res, grad, w2b, mode, L, S, cap, seed, lt, **extra)
     if A and n_pad == 0:
         ao = torch.ones(E, N, device=dev)
     elif A:
         ao, ao_evals = _secondary_batch(field, kw, bias, st, res, grad, w2b, _l.OCCLUSION_BATCH_HEMISPHERE, 1, A, cap, seed,
-                                        distance=float(ao_distance))
+                                        distance=ao_distance)
         ao = ao.view(E, N)
     out = ops.surface_shade_batch(st.rays_o, st.rays_d, st.t, st.status, res.hit_slot, res.hit_points_padded if n_pad else None,
                                   grad, rgb, n_pad, w2b, lt, _bg(bg, dev), vis, ao)
@@ -813,8 +889,7 @@ def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEF
     if len(b2ws) != E or not 1 <= E <= _l.TRACE_BATCH_MAX_ELEMS:
         raise ValueError(f"render_surfaces: {E} latents and {len(b2ws)} poses (one pose per latent, 1 .. {_l.TRACE_BATCH_MAX_ELEMS} views)")
     lt = _stack_lights(gen, lights, dev, "render_surfaces")
-    radii = _check_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt.shape[0], "render_surfaces",
-                             _is_local(lt))
+    occlusion = _checked_occlusion(shadows, shadow_samples, light_radius, ao_samples, ao_distance, seed, lt, "render_surfaces")
     field = LatentField(gen, zs, None, "render_surfaces", batch_ok=True)
     gen.eval()
     field.prepare(zs, None)
@@ -829,7 +904,7 @@ def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEF
         grad, rgb = grad.view(E, res.n_pad, 3), rgb.view(E, res.n_pad, 3)
     if batch_secondary:
         return _lit_batch(field, kw, bias, st, res, grad, rgb, torch.stack([v[4] for v in views]).contiguous(), gen.resolution, lt,
-                          radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, cap, dev)
+                          *occlusion, bg, cap, dev)
     out = []
     for e in range(E):
         one = copy.copy(field)   # the element's own FiLM rows: the field of one latent
@@ -837,7 +912,7 @@ def render_surfaces(gen, zs, b2ws, lights=None, shadows=False, bg=None, bias=DEF
         n = res.n_hit[e]
         s = _Surface.from_batch(one, kw, bias, st.rays_o[e], st.rays_d[e], views[e][4], gen.resolution, res[e],
                                 grad[e, :n] if n else None, rgb[e, :n] if n else None)
-        out.append(_lit(s, lt, radii, shadows, shadow_samples, ao_samples, ao_distance, seed, bg, dev))
+        out.append(_lit(s, lt, *occlusion, bg, dev))
     return out
 
 
@@ -993,7 +1068,7 @@ def capture_transfer(gen, z, b2w, transfer_samples=64, seed=0, bias=DEFAULT_BIAS
     dev = gen.it.device
     s = _Surface(gen, z.to(dev).reshape(1, -1), b2w, bias, trace_kw)
     transfer, bounce = s.transfer_bounce(samples, seed) if bounces else (s.transfer(samples, seed), None)
-    g = s.shade(None, None, outputs=tuple(ops.SURFACE_OUT))
+    g = s._shade(None, None, outputs=tuple(ops.SURFACE_OUT))
     maps = {_MAP_NAMES[k]: v for k, v in _maps(g, s.H, s.H).items()}
     vis = s.lobe_visibility(g_samples, shin, seed) if g_samples else None
     return TransferCapture(s, transfer, maps, samples, g_samples, shin, vis, spec, bounce)

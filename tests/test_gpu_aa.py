@@ -374,6 +374,41 @@ def test_light_orbit_traces_the_sub_samples_once(precision, monkeypatch):
     assert torch.equal(orbit["coverage"], one["coverage"]) and torch.equal(orbit["aa_mask"], one["aa_mask"])
 
 
+WALK_KW = dict(shadows=True, shadow_samples=4, ao_samples=4, aa_samples=2, bg=BG, seed=R.SEED)
+WALK_MAPS = ("mask", "depth", "ambient_occlusion", "coverage", "aa_mask")   # what does not depend on the light
+
+
+def walk_frames_are_single_renders(walk, single, lights, maps):
+    """Every stage at once through the walk loop: frame k is the single render under light k alone, bit for bit (NaN depth
+    included), and the light-independent maps are that render's."""
+    assert len(lights) == walk["image"].shape[0] == 3
+    for k, lt in enumerate(lights):
+        one = single(lt)
+        for name in maps:
+            per_frame = walk[name].shape[0] == 3
+            assert _same_bits(walk[name][k] if per_frame else walk[name], one[name][0] if per_frame else one[name]), (k, name)
+
+
+@pytest.mark.parametrize("entry", ["walk", "orbit"])
+def test_walk_frames_are_the_single_renders(entry):
+    from oi_amd import inference, trace
+    from oi_amd.relight import Light
+    seed, pose = R.SOFT_VIEWS[1]
+    gen, z, b2w = view("f16x3", seed, pose)
+    if entry == "walk":
+        base = Light.from_module(gen.light)
+        lights = [base] + [base.replace(direction=tuple(d)) for d in inference.light_walk_directions(base.direction, 3)[1:]]
+        walk = inference.surface_light_walk(gen, z, b2w, n_frames=3, **WALK_KW)
+    else:
+        light = LLT.golden_lights(pose)[1]
+        walk = inference.surface_light_orbit(gen, z, b2w, light, n_frames=3, centre=tuple(float(x) for x in b2w[:3, 3]), radius=1.6,
+                                             height=0.4, **WALK_KW)
+        lights = [light.replace(position=tuple(p)) for p in walk["positions"]]
+    assert walk["stats"]["aa_pixels"] > 0 and walk["stats"]["shadow_evals"] > 0 and walk["stats"]["ao_evals"] > 0
+    walk_frames_are_single_renders(walk, lambda lt: trace.render_surface(gen, z, b2w, lights=[lt], **WALK_KW), lights,
+                                   ("image", "visibility") + WALK_MAPS)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 10. guarded shapes through the C ABI
 # ---------------------------------------------------------------------------------------------------------------------

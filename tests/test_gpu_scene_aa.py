@@ -572,6 +572,35 @@ def test_light_orbit_traces_the_sub_samples_once(precision, monkeypatch):
     assert torch.equal(orbit["coverage"], one["coverage"]) and torch.equal(orbit["aa_mask"], one["aa_mask"])
 
 
+@pytest.mark.parametrize("ground", [False, True], ids=["aa", "ground"])
+@pytest.mark.parametrize("entry", ["walk", "orbit"])
+def test_walk_frames_are_the_single_renders(entry, ground):
+    """test_gpu_aa's check of the walk loop on the two scene walks; with a ground plane (which has no anti-aliasing stage:
+    aa_samples=1) also its mask and the shadow matte of every frame."""
+    from oi_amd import inference, scene
+    from oi_amd.relight import Light
+    import test_gpu_ground as GG
+    gen = TS.make_gen("f16x3")
+    zs, b2ws, win = scene_args("pair", 9)
+    kw = dict(GA.WALK_KW, seed=SEED, **win)
+    maps = ("image", "visibility", "instance") + GA.WALK_MAPS
+    if ground:
+        kw.update(aa_samples=1, ground=GG.golden_ground(TS.traced("f16x3", "pair", 9)))
+        maps = tuple(k for k in maps if k not in ("coverage", "aa_mask")) + ("ground_mask", "shadow_matte")
+    if entry == "walk":
+        base = Light.from_module(gen.light)
+        lights = [base] + [base.replace(direction=tuple(d)) for d in inference.light_walk_directions(base.direction, 3)[1:]]
+        walk = inference.scene_light_walk(gen, zs, b2ws, n_frames=3, **kw)
+    else:
+        c = SLL.centres("pair")
+        walk = inference.scene_light_orbit(gen, zs, b2ws, SLL.scene_lights("pair")[1], n_frames=3, centre=tuple((c[0] + c[1]) / 2),
+                                           radius=1.9, height=0.5, **kw)
+        lights = [SLL.scene_lights("pair")[1].replace(position=tuple(p)) for p in walk["positions"]]
+    stats = walk["stats"][0]
+    assert stats["shadow_evals"] > 0 and stats["occlusion_evals"] > 0 and (stats["ground_pixels"] if ground else stats["aa_pixels"]) > 0
+    GA.walk_frames_are_single_renders(walk, lambda lt: scene.render_scene(gen, zs, b2ws, lights=[lt], **kw), lights, maps)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 10. guarded shapes through the C ABI
 # ---------------------------------------------------------------------------------------------------------------------

@@ -224,6 +224,51 @@ def test_planner_against_brute_force():
     assert groups == [(0, 3), (3, 4)] and chunks == [(j, 1) for j in range(8)]
 
 
+def test_chunk_rule_is_the_three_rules_it_replaced():
+    """trace.sample_chunks, the one chunk rule, against the three it replaced, restated here as they stood -- the sample loops
+    of SceneSurface._sampled and GroundSurface._sampled and plan_secondary's sample split: equal chunks, and refusals equal word
+    for word.  The grid holds per > cap, caps beyond 2^31 (so that the 2^31 bound decides) and samples that are no multiple of
+    the chunk."""
+    from oi_amd import trace
+    seen = set()
+
+    def outcome(fn):
+        try:
+            return fn()
+        except ValueError as e:
+            return str(e)
+
+    def old_loop(S, per, cap, refusal):
+        chunk = min(int(S), min(int(cap), (1 << 31) - 1) // per)
+        if chunk < 1:
+            raise ValueError(refusal)
+        return [(j0, min(chunk, int(S) - j0)) for j0 in range(0, int(S), chunk)]
+
+    def old_plan(E, L, S, n_pad, max_secondary_rays, what="render_surfaces"):
+        cap, per = min(int(max_secondary_rays), (1 << 31) - 1), L * n_pad
+        if per > cap:
+            raise ValueError(f"{what}: 1 view x {L} lights x {n_pad} hit slots = L * n_pad = {per} rays per sample of one view (at most "
+                             f"max_secondary_rays={max_secondary_rays} and below 2^31)")
+        group, chunk = (E, min(S, cap // (E * per))) if E * per <= cap else (cap // per, 1)
+        return ([(a, min(E, a + group)) for a in range(0, E, group)], [(j0, min(chunk, S - j0)) for j0 in range(0, S, chunk)])
+
+    for E, L, S, n in itertools.product((1, 2, 7), (1, 2, 256), (1, 4, 256), (1, 150, 1 << 20)):
+        per = E * L * n
+        for cap in (per - 1, per, 1 << 24, 1 << 40):
+            tail = f"(at most max_shadow_rays={cap} and below 2^31; inference.scene_light_walk splits the lights)"
+            for what, rays in (("SceneSurface.ambient", f"{E} instances x {L} lights x {n} visible points = {per} rays per sample"),
+                               ("GroundSurface.ambient", f"{E} instances x {L} lights x {n} ground points = E * L * n_g = {per} rays per sample")):
+                old = outcome(lambda: old_loop(S, per, cap, f"{what}: {rays} {tail}"))
+                assert outcome(lambda: trace.sample_chunks(S, per, cap, what, rays)) == old, (E, L, S, n, cap)
+            seen.add("refused" if isinstance(old, str) else "whole" if len(old) == 1 else "ragged" if old[-1][1] != old[0][1] else "even")
+            if not isinstance(old, str) and min(cap, (1 << 31) - 1) // per != cap // per:
+                seen.add("2^31 decides")
+            old = outcome(lambda: old_plan(E, L, S, n, cap))
+            assert outcome(lambda: trace.plan_secondary(E, L, S, n, cap)) == old, (E, L, S, n, cap)
+            seen.add("plan refused" if isinstance(old, str) else "plan groups" if len(old[0]) > 1 else "plan samples")
+    assert seen == {"refused", "whole", "ragged", "even", "2^31 decides", "plan refused", "plan groups", "plan samples"}
+
+
 def test_the_away_view_of_the_gpu_test_misses_on_the_oracle():
     """tests/test_gpu_occlusion_batch.py builds its view without a hit from trace_batch_ref.away_rays(130), repeated to the
     view's 48 x 48 rays: on the oracle's fields every one of the 130 misses on its first sample (float64)."""
